@@ -294,6 +294,25 @@ def time_steps(fn, warmup, steps):
     return (time.perf_counter() - t0) / steps
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """Write one step's results as dirname/<name>.npy: float64 stays float64, everything else becomes float32.  Every array has
+    the batch as its leading axis; if they exceed DUMP_LIMIT_BYTES together, a fixed seeded sample of batch rows is written
+    instead, and its row numbers go to pose_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: (v.double() if v.dtype == torch.float64 else v.float()).cpu().numpy() for k, v in arrays.items()}
+    B = next(iter(host.values())).shape[0]
+    row_bytes = sum(a.nbytes for a in host.values()) // B
+    if row_bytes * B > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(seed).choice(B, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["pose_index"] = idx.astype(np.float64)
+    for k, a in host.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), np.ascontiguousarray(a))
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py <same args>` as a child
     process (one rank per GPU over RCCL, what the driver's own N > 1 command does), pass its output through and return its exit code."""
@@ -395,7 +414,12 @@ def main():
     ap.add_argument("--mode-warmup", type=int, default=2, help="untimed steps in front of each extra mode leg")
     ap.add_argument("--debug-flags", type=int, default=0, help="kernel A/B switches (rgbm_debug_flags); a non-zero value is echoed in config")
     ap.add_argument("--no-accuracy", action="store_true", help="skip the golden-vector accuracy leg (profiling runs: keeps the trace to the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's batch: the ten network outputs, world boxes "
+                         "`bbox`, post-processing `ts`, `valid` flags) as DIR/<name>.npy in float32 / float64; inputs are seeded")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if os.environ.get("RGBM_BENCH_CHOOSE") == "uniform":      # rounds 1-3 spelling of --inputs uniform
         args.inputs = "uniform"
 
@@ -447,7 +471,7 @@ def main():
         def f():
             out = n(dd["img1"], dd["choose1"], dd["img2"], dd["choose2"], dd["P1"], dd["P2"], dd["depths"])
             bbox, ts, valid = postprocess(out["view1_nocs"], out["view1_depth"], out["view1_r"], dd["choose1"], dd["K1"], dd["E1"])
-            return out, bbox, valid
+            return out, bbox, ts, valid
         return f
     step = mkstep(net, d)
 
@@ -476,10 +500,12 @@ def main():
         _lib.check(lib.rgbm_prof_start(), "rgbm_prof_start")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        out, bbox, valid = step()
+        out, bbox, ts, valid = step()
     barrier()
     elapsed_local = time.perf_counter() - t0
     elapsed = elapsed_local
+    if args.dump_outputs and rank == 0:      # after the clock stopped: what the last timed step handed its caller
+        dump_outputs(args.dump_outputs, {**out, "bbox": bbox, "ts": ts, "valid": valid})
     if args.no_prof:      # timing experiment (one rank): the step time without the per-launch events, nothing else
         print(json.dumps({"ms_per_step": round(elapsed / args.steps * 1e3, 3), "note": "--no-prof: no per-launch HIP events in the timed region"}))
         return
@@ -510,7 +536,7 @@ def main():
         # the at-batch accuracy check uses one more forward of the same batch on a POISONED workspace (every byte 0xFF in front of the
         # forward): it must reproduce the timed step bit for bit — nothing read may come from a previous run — and is what the oracle sees
         net.poison_workspace = True
-        pout, _, _ = step()
+        pout, _, _, _ = step()
         torch.cuda.synchronize()
         net.poison_workspace = False
         poison_same = all(torch.equal(pout[k].view(torch.int32), out[k].view(torch.int32)) for k in OUT_KEYS)

@@ -168,7 +168,7 @@ def test_bench_plain_launch_spawns_its_ranks_on_one_device():
     assert r.returncode != 0 and not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
-def test_bench_single_process_line_has_every_leg():
+def test_bench_single_process_line_has_every_leg(tmp_path):
     """`python bench.py` as the driver runs it at N = 1, shrunk (batch 16, 1 step): every leg of the line must come back — a crash in
     one of them at round end would lose the whole bench record.  Checks the keys the round-3 verdict asked for (dense / worst-case /
     survey legs promoted to top level, the renamed algorithmic figure, plugin boundary, small batches) and basic sanity of each."""
@@ -177,10 +177,17 @@ def test_bench_single_process_line_has_every_leg():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--batch", "16", "--steps", "1", "--warmup", "1", "--ppo-envs", "16", "--ppo-iters", "1",
-           "--mode-steps", "1"]
+           "--mode-steps", "1", "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    # --dump-outputs: what the last timed step computed, one float array per output, batch first
+    dump = {f.stem: np.load(f) for f in (tmp_path / "dump").iterdir()}
+    assert sorted(dump) == sorted(["view1_nocs", "view2_nocs", "view1_depth", "view2_depth", "view1_r", "view2_r", "view1_t", "view2_t",
+                                   "view1_s", "view2_s", "bbox", "ts", "valid"])
+    assert all(a.shape[0] == 16 and a.dtype in (np.float32, np.float64) for a in dump.values())
+    assert dump["view1_nocs"].shape == (16, 1024, 3) and dump["bbox"].shape == (16, 8, 3)
+    assert int(dump["valid"].sum()) == line["valid_poses_last_step"] and np.isfinite(dump["bbox"]).all() == line["outputs_finite"]
     assert line["metric"] == "adapose_poses_per_sec_batch256" and line["n_gpus"] == 1 and line["value"] > 0 and line["dtype"] == "bf16"
     assert line["config"]["inputs"] == "crop" and 0.0 < line["sweep_tiles_needed_frac"] <= 1.0
     for k in ("value_dense", "value_worst_case", "value_survey_masks", "value_two_streams", "mfma_frac_executed_flops_dense",
