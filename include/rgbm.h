@@ -59,7 +59,8 @@ typedef struct rgbm_adapose_out {   /* device fp32, shapes of the reference's ou
  * norm_mode: 0 = eval-mode BatchNorm3d folded into the convs (the default and the benchmarked path);
  *            1 = per-sample statistics: every BatchNorm3d of the cost-regularisation net normalises a view's volume with that
  *                volume's own biased mean / variance — what the reference as shipped computes (interface_v5.py:39-56 never calls
- *                .eval() and runs one pose per call), with Dropout2d as identity.  Generic kernels, materialised volume. */
+ *                .eval() and runs one pose per call), with Dropout2d as identity unless rgbm_adapose_set_dropout turns it on.  Generic
+ *                kernels, materialised volume. */
 int rgbm_adapose_create(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype, int norm_mode);
 int rgbm_adapose_destroy(rgbm_adapose_t* h);
 /* views per cost-volume chunk (default 512 = batch 256 in one chunk); bounds the workspace */
@@ -88,6 +89,22 @@ int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views);
  * Set before querying the workspace size. */
 int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value);
 int rgbm_adapose_workspace_bytes(rgbm_adapose_t* h, int B, size_t* bytes);
+/* Seeded Dropout2d of PSPNet (pspnet.py:122,150,154: p = 0.15 after up_1 and after up_2), active in the reference as shipped
+ * (interface_v5.py:39-56 never calls .eval()).  p = 0 is off (the default: no kernel changes); otherwise 0 < p < 1.  Every
+ * (pose, view, site, channel) gets one keep decision, a pure function of (seed, global pose index, view, site, channel)
+ * (DESIGN.md "Seeded Dropout2d"): kept channels are scaled by fp32(1 / (1 - p)), dropped ones zeroed, in the epilogue of the
+ * tap combination that writes up_1 / up_2 (option upconv bits 0 and 1 are required).  The global pose index of pose b of a forward is
+ * a device counter + b; the forward advances the counter by B, so masks do not depend on how poses are batched, chunked or replayed
+ * from a graph (a replay draws fresh masks).  set_dropout resets the counter to 0 after synchronising the device and invalidates
+ * captured graphs.  Forwards with dropout on, issued to one handle from two streams at the same time, share the counter and the
+ * factor buffer: unsupported (the same rule as the per-stream K-split scratch of rgbm_adapose_forward_graph). */
+int rgbm_adapose_set_dropout(rgbm_adapose_t* h, float p, uint64_t seed);
+/* The factors the last forward used (drawn or set), batch B: out_dev [2B][320] fp32, views = the view-1 crops of the batch, then the
+ * view-2 crops; per view up_1's 256 channels, then up_2's 64.  Synchronises the device. */
+int rgbm_adapose_dropout_masks(rgbm_adapose_t* h, int B, float* out_dev);
+/* Explicit factors (same layout) for the next forward of batch B, which uses them instead of drawing and does not advance the counter
+ * (whether or not set_dropout is on); a forward_graph call runs that forward eagerly.  Synchronises the device. */
+int rgbm_adapose_set_dropout_masks(rgbm_adapose_t* h, int B, const float* masks_dev);
 /* img1/img2 [B,3,224,224] fp32 NCHW normalised; choose1/2 [B,1024] int32; P1/P2 [B,4,4] fp32; depths [B,24] fp32.
  * Same argument meaning as network_v5.py:418 (view1_img, view1_choose, view2_img, view2_choose, view1_proj,
  * view2_proj, depth_values).  workspace must be 256-byte aligned. */

@@ -96,6 +96,9 @@ SIGNATURES = {
     "rgbm_adapose_set_chunk": (_i, [_vp, _i]),
     "rgbm_adapose_set_option": (_i, [_vp, C.c_char_p, _i]),
     "rgbm_adapose_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),
+    "rgbm_adapose_set_dropout": (_i, [_vp, _f, C.c_uint64]),
+    "rgbm_adapose_dropout_masks": (_i, [_vp, _i, _vp]),
+    "rgbm_adapose_set_dropout_masks": (_i, [_vp, _i, _vp]),
     "rgbm_adapose_forward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp]),
     "rgbm_adapose_forward_ex": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _i, _vp]),
     "rgbm_adapose_forward_graph": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp, C.POINTER(C.c_int32),

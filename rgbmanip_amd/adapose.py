@@ -24,7 +24,7 @@ class AdaPoseNet:
     def __init__(self, state_dict, dtype: str = "fp32", device: int = 0, max_chunk_views: int | None = None,
                  cost_impl: int | None = None, sparse_tail: int | None = None, options: dict | None = None,
                  norm_mode: int | str = 0, poison_workspace: bool = False, graph: bool = False, graph_max_batch: int = 32,
-                 split_streams: bool | int = False, split_min_batch: int = 128):
+                 split_streams: bool | int = False, split_min_batch: int = 128, dropout: float = 0.0, dropout_seed: int = 0):
         self.lib = _lib.load()
         # graph: forwards of at most `graph_max_batch` poses are replayed from a hipGraph captured per batch size
         # (rgbm_adapose_forward_graph): static input / output / workspace buffers per batch size, one hipGraphLaunch instead of ~150
@@ -86,6 +86,39 @@ class AdaPoseNet:
             self.options[key] = int(val)
         self._ws = None
         self._ws_B = None
+        # dropout: PSPNet's Dropout2d as the reference runs it as shipped (never .eval()): seeded masks, fresh on every forward
+        # (rgbm_adapose_set_dropout; 0 = off)
+        self.dropout, self.dropout_seed = 0.0, 0
+        self._drop_explicit = False
+        if dropout:
+            self.set_dropout(dropout, dropout_seed)
+
+    # ------------------------------------------------------------------
+    def set_dropout(self, p: float, seed: int = 0):
+        """Turn PSPNet's Dropout2d on (0 < p < 1) or off (p = 0) and restart its mask sequence at pose 0 of `seed`.
+        Synchronises the device."""
+        p = float(p)
+        if not (p == 0.0 or 0.0 < p < 1.0):
+            raise ValueError(f"dropout p must be 0 (off) or lie in (0, 1), got {p}")
+        _lib.check(self.lib.rgbm_adapose_set_dropout(self._h, p, int(seed) & (2 ** 64 - 1)), "rgbm_adapose_set_dropout")
+        self.dropout, self.dropout_seed = p, int(seed)
+
+    def dropout_masks(self, B: int) -> torch.Tensor:
+        """The Dropout2d factors the last forward (batch B) used: [2B, 320] fp32 — rows: the view-1 crops, then the view-2 crops;
+        columns: up_1's 256 channels, then up_2's 64.  Synchronises the device."""
+        out = torch.empty(2 * B, 320, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.rgbm_adapose_dropout_masks(self._h, int(B), _lib.ptr(out)), "rgbm_adapose_dropout_masks")
+        return out
+
+    def set_dropout_masks(self, masks):
+        """Explicit factors ([2B, 320], layout of `dropout_masks`) for the next forward of batch B, used instead of drawn ones (and
+        the mask sequence does not advance).  Synchronises the device."""
+        t = self._prep(masks, torch.float32)
+        if t.dim() != 2 or t.shape[1] != 320 or t.shape[0] % 2:
+            raise ValueError(f"dropout masks must be [2B, 320], got {tuple(t.shape)}")
+        torch.cuda.synchronize(self.device)
+        _lib.check(self.lib.rgbm_adapose_set_dropout_masks(self._h, t.shape[0] // 2, _lib.ptr(t)), "rgbm_adapose_set_dropout_masks")
+        self._drop_explicit = True
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -137,6 +170,7 @@ class AdaPoseNet:
             ws = torch.empty(self.workspace_bytes(B) + 256, dtype=torch.uint8, device=self.device)
             st = self._static[B] = (ins, out, ws)
         ins, out, ws = st
+        self._drop_explicit = False
         for dst, src in zip(ins, args):
             assert tuple(src.shape) == tuple(dst.shape), (tuple(src.shape), tuple(dst.shape))
             dst.copy_(src, non_blocking=True)              # converts dtype / uploads as needed, on the caller's stream
@@ -185,10 +219,14 @@ class AdaPoseNet:
             "view1_t": torch.empty(B, 3, **f32), "view2_t": torch.empty(B, 3, **f32),
             "view1_s": torch.empty(B, 3, **f32), "view2_s": torch.empty(B, 3, **f32),
         }
-        if self.split_streams and stop_after == 0 and B >= self.split_min_batch and B % self.split_parts == 0:
+        # with dropout the parts would share the handle's pose counter and factor buffer (rgbm.h): the forward runs on one stream (the
+        # split forward computes the same outputs)
+        if self.split_streams and stop_after == 0 and B >= self.split_min_batch and B % self.split_parts == 0 and not self.dropout \
+                and not self._drop_explicit:
             self._forward_split(B, (img1, img2, ch1, ch2, P1, P2, dep), out, stream)
             return out
         self._last_split = False
+        self._drop_explicit = False
         o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
         ws_ptr, ws_bytes = self._workspace(B)
         if self.poison_workspace:

@@ -260,6 +260,9 @@ void AdaPose::destroy() {
   for (auto& l : psp) l.destroy();
   up1.destroy(); up2.destroy(); up3.destroy(); fin.destroy();
   up1c.destroy(); up2c.destroy(); tail.destroy();
+  if (drop_masks) (void)hipFree(drop_masks);
+  if (drop_state) (void)hipFree(drop_state);
+  drop_masks = nullptr; drop_state = nullptr; drop_cap_views = 0; drop_p = 0.f; drop_explicit = 0; drop_last_B = 0;
   for (auto& l : c3d) l.destroy();
   for (auto& l : dc) l.destroy();
   for (auto& l : c3d_raw) l.destroy();
@@ -389,7 +392,7 @@ size_t AdaPose::workspace_bytes(int B) const {
   return A.peak + 256;
 }
 
-int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* img2, hipStream_t s) const {
+int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* img2, hipStream_t s, const float* drop) const {
   const int S = img;
   int H = S / 2, W = S / 2;
   if (stem && stem_w) {
@@ -459,14 +462,16 @@ int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* im
   }
   // up_1 / up_2: 1x1 GEMM at the low resolution (nine taps stacked on the output channels, z in `ups`: 9/16 of the up-sampled
   // tensor it replaces) + tap combination; or, for A/B, the x2 resize followed by the 3x3 conv on the up-sampled grid
+  // Dropout2d (drop: factors [V][kDropoutPerView]) is applied in the tap combination's epilogue only: the A/B paths refuse it
+  RGBM_REQUIRE(drop == nullptr || (upconv & 3) == 3, "dropout needs option upconv bits 0 and 1 (up_1 / up_2 through the tap combination)");
   if (upconv & 1) {
-    if (int rc = up1c.run(bf.cat, bf.ups, bf.u1, V, H, W, 256, s)) return rc;
+    if (int rc = up1c.run(bf.cat, bf.ups, bf.u1, V, H, W, 256, s, drop)) return rc;
   } else {
     if (int rc = launch_resize_bilinear_ac(dtype, bf.cat, bf.ups, V, H, W, 1024, 2 * H, 2 * W, 1024, 0, s)) return rc;
     if (int rc = up1.run(bf.ups, bf.u1, V, 1, 2 * H, 2 * W, 256, nullptr, 0, nullptr, 0, s)) return rc;
   }
   if (upconv & 2) {
-    if (int rc = up2c.run(bf.u1, bf.ups, bf.u2, V, 2 * H, 2 * W, 64, s)) return rc;
+    if (int rc = up2c.run(bf.u1, bf.ups, bf.u2, V, 2 * H, 2 * W, 64, s, drop ? drop + 256 : nullptr)) return rc;
   } else {
     if (int rc = launch_resize_bilinear_ac(dtype, bf.u1, bf.ups, V, 2 * H, 2 * W, 256, 4 * H, 4 * W, 256, 0, s)) return rc;
     if (int rc = up2.run(bf.ups, bf.u2, V, 1, 4 * H, 4 * W, 64, nullptr, 0, nullptr, 0, s)) return rc;
@@ -630,7 +635,21 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
 
   // ---- stage inputs: views = [view1 batch ; view2 batch] ----
   if (int rc = launch_stage_in(P1, P2, choose1, choose2, bf.Pviews, bf.choose, B, P, s)) return rc;
-  if (int rc = pspnet(bf, V, img1, img2, s)) return rc;
+  // Dropout2d: masks loaded for this forward (rgbm_adapose_set_dropout_masks), or drawn for poses counter .. counter + B - 1
+  const float* drop = nullptr;
+  if (drop_active()) {
+    RGBM_REQUIRE(V <= drop_cap_views && drop_masks && (drop_explicit || drop_state), "dropout: mask buffer smaller than the batch");
+    RGBM_REQUIRE((upconv & 3) == 3, "dropout needs option upconv bits 0 and 1 (up_1 / up_2 through the tap combination)");
+    if (drop_explicit) {
+      RGBM_REQUIRE(drop_explicit == B, "dropout: the masks set for the next forward are for batch " + std::to_string(drop_explicit));
+      drop_explicit = 0;
+    } else {
+      if (int rc = launch_dropout_masks(drop_masks, drop_state, B, drop_p, drop_seed, drop_no_advance ? 0 : 1, s)) return rc;
+    }
+    drop = drop_masks;
+    drop_last_B = B;
+  }
+  if (int rc = pspnet(bf, V, img1, img2, s, drop)) return rc;
   if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
   // bf16x3 nets: everything that GATHERS from the feature map (plane sweep, point heads) reads a plain fp32 copy of it
   const void* featg = bf.feat;

@@ -73,6 +73,20 @@ struct AdaPose {
   float* head_w[3][3] = {{nullptr}};
   float* head_b[3][3] = {{nullptr}};
 
+  // Seeded Dropout2d of PSPNet (dropout.hip; set through rgbm_adapose_set_dropout): p = 0 is off.  drop_masks [drop_cap_views][kDropoutPerView]
+  // holds the factors of the last forward, drop_state the device pose counter (+ the mask kernel's ticket).  drop_explicit: B of masks
+  // loaded by rgbm_adapose_set_dropout_masks, used by the next forward instead of drawing; drop_no_advance: draw without advancing the
+  // counter (the eager warm-up in front of a graph capture, which the replay draws again)
+  float drop_p = 0.f;
+  unsigned long long drop_seed = 0;
+  float* drop_masks = nullptr;
+  unsigned long long* drop_state = nullptr;
+  int drop_cap_views = 0;
+  mutable int drop_explicit = 0;
+  mutable int drop_last_B = 0;
+  int drop_no_advance = 0;
+  bool drop_active() const { return drop_p > 0.f || drop_explicit > 0; }
+
   struct Buffers {
     float *Pviews, *homog; int* choose; void* feat;
     unsigned char* masks;           // sparse cost regularisation: tile masks of the 3-D layers per view of a cost-volume chunk (prob_sparse.hip)
@@ -102,7 +116,7 @@ struct AdaPose {
 
   // exposed for layer-level tests
   int plan(int B, Arena& A, Buffers& bf) const;
-  int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, hipStream_t s) const;
+  int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, hipStream_t s, const float* drop = nullptr) const;
   int cost_volume(const Buffers& bf, int V, int B, const float* depths, hipStream_t s) const;
   int chunk_views(int V) const;
   // bf16x3 on the default path: nothing reads the split-pair feature map (the sweep and the point heads gather from plain fp32), so

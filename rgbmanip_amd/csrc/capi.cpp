@@ -4,6 +4,7 @@
 
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -37,6 +38,23 @@ struct rgbm_adapose {
   std::vector<ForwardGraph> graphs;    // at most kMaxGraphs, least recently used evicted
 };
 static const size_t kMaxGraphs = 8;
+
+// Dropout2d factor buffer for batches of up to B poses (grown, never shrunk; a new address invalidates captured graphs)
+static int ensure_dropout_capacity(rgbm_adapose* h, int B) {
+  AdaPose& n = h->net;
+  if (2 * B <= n.drop_cap_views) return 0;
+  const int views = std::max(2 * B, 2 * n.drop_cap_views);
+  float* m = nullptr;
+  RGBM_CHECK_HIP(hipMalloc(&m, (size_t)views * kDropoutPerView * sizeof(float)));
+  if (n.drop_masks) {
+    (void)hipDeviceSynchronize();      // a forward in flight may still read the old buffer
+    (void)hipFree(n.drop_masks);
+  }
+  n.drop_masks = m;
+  n.drop_cap_views = views;
+  ++h->opt_version;
+  return 0;
+}
 
 static void drop_graph(ForwardGraph& g) {
   if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -105,6 +123,39 @@ int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value) {
   return 0;
 }
 
+int rgbm_adapose_set_dropout(rgbm_adapose_t* h, float p, uint64_t seed) {
+  RGBM_REQUIRE(h && (p == 0.f || (p > 0.f && p < 1.f)), "set_dropout: p must be 0 (off) or lie in (0, 1)");
+  RGBM_CHECK_HIP(hipSetDevice(h->device));
+  if (!h->net.drop_state) RGBM_CHECK_HIP(hipMalloc(&h->net.drop_state, 2 * sizeof(unsigned long long)));
+  RGBM_CHECK_HIP(hipDeviceSynchronize());      // every forward issued before this call has drawn its masks
+  RGBM_CHECK_HIP(hipMemset(h->net.drop_state, 0, 2 * sizeof(unsigned long long)));
+  RGBM_CHECK_HIP(hipDeviceSynchronize());
+  h->net.drop_p = p;
+  h->net.drop_seed = (unsigned long long)seed;
+  ++h->opt_version;
+  return 0;
+}
+
+int rgbm_adapose_dropout_masks(rgbm_adapose_t* h, int B, float* out_dev) {
+  RGBM_REQUIRE(h && out_dev && B > 0, "dropout_masks arguments");
+  RGBM_REQUIRE(h->net.drop_last_B == B && h->net.drop_masks, "dropout_masks: the last forward with dropout had batch " +
+               std::to_string(h->net.drop_last_B) + ", not " + std::to_string(B));
+  RGBM_CHECK_HIP(hipSetDevice(h->device));
+  RGBM_CHECK_HIP(hipDeviceSynchronize());
+  RGBM_CHECK_HIP(hipMemcpy(out_dev, h->net.drop_masks, (size_t)2 * B * kDropoutPerView * sizeof(float), hipMemcpyDeviceToDevice));
+  return 0;
+}
+
+int rgbm_adapose_set_dropout_masks(rgbm_adapose_t* h, int B, const float* masks_dev) {
+  RGBM_REQUIRE(h && masks_dev && B > 0, "set_dropout_masks arguments");
+  RGBM_CHECK_HIP(hipSetDevice(h->device));
+  if (int rc = ensure_dropout_capacity(h, B)) return rc;
+  RGBM_CHECK_HIP(hipDeviceSynchronize());      // no forward in flight reads the buffer any more
+  RGBM_CHECK_HIP(hipMemcpy(h->net.drop_masks, masks_dev, (size_t)2 * B * kDropoutPerView * sizeof(float), hipMemcpyDeviceToDevice));
+  h->net.drop_explicit = B;
+  return 0;
+}
+
 int rgbm_adapose_workspace_bytes(rgbm_adapose_t* h, int B, size_t* bytes) {
   RGBM_REQUIRE(h && bytes && B > 0, "workspace_bytes arguments");
   *bytes = h->net.workspace_bytes(B);
@@ -122,6 +173,8 @@ int rgbm_adapose_forward_ex(rgbm_adapose_t* h, int B, const float* img1, const f
                             const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
                             size_t workspace_bytes, const rgbm_adapose_out* out, int stop_after, void* stream) {
   RGBM_REQUIRE(h && img1 && img2 && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward arguments");
+  if (h->net.drop_p > 0.f && B > 0)
+    if (int rc = ensure_dropout_capacity(h, B)) return rc;
   return h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out),
                         (hipStream_t)stream, stop_after);
 }
@@ -147,7 +200,10 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
   if (n_nodes) *n_nodes = 0;
   if (captured) *captured = 0;
   // the in-library profiler records events around launches: not capturable, and a timing run wants the launches themselves
-  if (prof_enabled()) {
+  if (h->net.drop_p > 0.f && B > 0)
+    if (int rc = ensure_dropout_capacity(h, B)) return rc;
+  // masks loaded by rgbm_adapose_set_dropout_masks are for one forward: not captured
+  if (prof_enabled() || h->net.drop_explicit) {
     if (captured) *captured = -1;
     return h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), s, 0);
   }
@@ -168,7 +224,11 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
   if (!hit) {
     // an eager forward first: it sets the dynamic-LDS attributes of the kernels this shape uses and loads their code objects (neither
     // may happen inside a capture), and reports argument errors with their own messages
-    if (int rc = h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), s, 0)) return rc;
+    // with dropout the warm-up draws the masks the replay draws again: the pose counter advances once
+    h->net.drop_no_advance = 1;
+    const int rw = h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), s, 0);
+    h->net.drop_no_advance = 0;
+    if (rw) return rw;
     ForwardGraph g;
     g.B = B; memcpy(g.in, in, sizeof(in)); g.ws = workspace; g.ws_bytes = workspace_bytes; g.out = *out;
     g.opt_version = h->opt_version; g.tuning_version = g_tuning_version;

@@ -25,11 +25,19 @@ int launch_build_volume(int dtype, const void* feat, const float* homog, const f
 
 // upconv.hip — tap-combining half of PSPUpsample evaluated as a low-resolution 1x1 GEMM (layers.h, UpConvLayer):
 // z [V][h][w][9*Co] (tap-major) -> out [V][2h][2w][ldo] = act(bias + sum_t bilinear(z_t)(p + t))
+// drop (optional): Dropout2d factors of this site, drop[v * kDropoutPerView + c], multiplied in after the activation (dropout.hip)
 int launch_upconv_combine(int dtype, const void* z, const float* bias, void* out, int V, int h, int w, int Co, int ldo, int act,
-                          float slope, hipStream_t s);
+                          float slope, hipStream_t s, const float* drop = nullptr);
 // up_3 + final of the PSPNet tail in one kernel (upconv_final.hip): x [V][h][w][64] -> out [V][2h][2w][32]
 int launch_upconv_final(int dtype, const void* x, const void* wz, const float* bias, float slope, const void* wf, const float* biasf,
                         void* out, int out_f32, int V, int h, int w, hipStream_t s, const void* wf_f16 = nullptr);      // wf_f16: `final` weights in f16 (out_f32 == 2)
+
+// dropout.hip — seeded Dropout2d of PSPNet (up_1: 256 channels, up_2: 64): factors masks[V][kDropoutPerView] (up_1's channels, then
+// up_2's), each 0 or dropout_scale(p); pose index = state[0] + the pose's place in the batch, state[0] += B when `advance`
+constexpr int kDropoutPerView = 256 + 64;
+unsigned dropout_threshold(float p);
+float dropout_scale(float p);
+int launch_dropout_masks(float* masks, unsigned long long* state, int B, float p, unsigned long long seed, int advance, hipStream_t s);
 
 // bn_kernels.hip — per-sample (train-mode, batch 1) BatchNorm3d + ReLU + skip add, in place on the un-normalised conv output
 size_t bn_scratch_bytes(int V);

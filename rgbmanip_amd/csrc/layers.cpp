@@ -325,11 +325,11 @@ void UpConvLayer::destroy() {
   bias = nullptr;
 }
 
-int UpConvLayer::run(const void* in, void* z, void* out, int V, int h, int w, int ldo, hipStream_t s) const {
+int UpConvLayer::run(const void* in, void* z, void* out, int V, int h, int w, int ldo, hipStream_t s, const float* drop) const {
   if (int rc = gemm.run(in, z, V, 1, h, w, 9 * Cout, nullptr, RES_NONE, nullptr, 0, s)) return rc;
   if (split)
     if (int rc = gemm2.run(in, reinterpret_cast<char*>(z) + (size_t)split * dtype_size(gemm.dtype), V, 1, h, w, 9 * Cout, nullptr, RES_NONE, nullptr, 0, s)) return rc;
-  return launch_upconv_combine(gemm.dtype, z, bias, out, V, h, w, Cout, ldo, act, slope, s);
+  return launch_upconv_combine(gemm.dtype, z, bias, out, V, h, w, Cout, ldo, act, slope, s, drop);
 }
 
 int UpConvFinal::init(int dtype_, const float* w3, const float* b3, float slope_, const float* wfin, const float* bfin) {

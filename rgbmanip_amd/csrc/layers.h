@@ -76,7 +76,8 @@ struct UpConvLayer {
   void destroy();
   size_t scratch_elems(int V, int h, int w) const { return (size_t)V * h * w * 9 * Cout; }
   // in [V][h][w][Cin] -> z scratch [V][h][w][9*Cout] -> out [V][2h][2w][ldo]
-  int run(const void* in, void* z, void* out, int V, int h, int w, int ldo, hipStream_t s) const;
+  // drop (optional): Dropout2d factors, drop[v * kDropoutPerView + channel] (kernels.h)
+  int run(const void* in, void* z, void* out, int V, int h, int w, int ldo, hipStream_t s, const float* drop = nullptr) const;
 };
 
 // PSPNet tail: up_3 (x2 bilinear -> conv3x3 64 -> 64 + bias -> PReLU) and `final` (conv1x1 64 -> 32 + bias) in ONE kernel

@@ -97,10 +97,12 @@ struct UpTap {
   }
 };
 
-template <typename T, int BR, int BC>
+// DROP: Dropout2d factors drop[v * kDropoutPerView + channel] multiply the activated values before the store (split pairs: in fp32,
+// before the hi / lo split).  A separate instantiation, so that the path without dropout is the same code as before the option.
+template <typename T, int BR, int BC, bool DROP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? 3 : 2, 8))) void upconv_combine_kernel(const T* __restrict__ z, const float* __restrict__ bias,
                                                                T* __restrict__ out, int V, int h, int w, int Co, int ldo,
-                                                               float nslope, float sy, float sx) {
+                                                               float nslope, float sy, float sx, const float* __restrict__ drop) {
   constexpr int E = 4;
   typedef typename Raw4<T>::type raw_t;
   constexpr int NR = BR / 2 + 2, NC = BC / 2 + 2;
@@ -178,6 +180,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 #undef UP_STEP
     UpTap<T, BR, BC, 2, 2>::accumulate(ra, wy, wx, acc);
     T* ob = out + ((long long)vv * Ho * Wo) * ldo + cc * E;
+    float df[E];
+    if constexpr (DROP) {
+      const float4 d4 = *reinterpret_cast<const float4*>(drop + (long long)vv * kDropoutPerView + cc * E);
+      df[0] = d4.x; df[1] = d4.y; df[2] = d4.z; df[3] = d4.w;
+    }
 #pragma unroll
     for (int a = 0; a < BR; ++a) {
       const int oy = BR * bi + a;
@@ -188,6 +195,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
         float r[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) r[e] = acc[a][b][e] < 0.f ? __builtin_fmaxf(acc[a][b][e], -3.402823466e38f) * nslope : acc[a][b][e];      // NaN stays NaN
+        if constexpr (DROP) {
+#pragma unroll
+          for (int e = 0; e < E; ++e) r[e] *= df[e];
+        }
         store4(ob + ((long long)oy * Wo + ox) * ldo, r);
       }
     }
@@ -196,7 +207,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 
 template <typename T>
 int launch_t(const void* z, const float* bias, void* out, int V, int h, int w, int Co, int ldo, float nslope, float sy, float sx,
-             hipStream_t s) {
+             hipStream_t s, const float* drop) {
 #ifndef UPC_BC
 #define UPC_BC 4
 #endif
@@ -206,8 +217,12 @@ int launch_t(const void* z, const float* bias, void* out, int V, int h, int w, i
   RGBM_REQUIRE((2 * h) % BR == 0 && (2 * w) % BC == 0, "upconv combine: output size must be a multiple of the thread block shape");
   const long long blocks = (total + 255) / 256;
   const unsigned grid = (unsigned)(blocks < (1ll << 20) ? blocks : (1ll << 20));
-  hipLaunchKernelGGL((upconv_combine_kernel<T, BR, BC>), dim3(grid), dim3(256), 0, s, (const T*)z, bias, (T*)out, V, h, w, Co, ldo,
-                     nslope, sy, sx);
+  if (drop)
+    hipLaunchKernelGGL((upconv_combine_kernel<T, BR, BC, true>), dim3(grid), dim3(256), 0, s, (const T*)z, bias, (T*)out, V, h, w, Co, ldo,
+                       nslope, sy, sx, drop);
+  else
+    hipLaunchKernelGGL((upconv_combine_kernel<T, BR, BC, false>), dim3(grid), dim3(256), 0, s, (const T*)z, bias, (T*)out, V, h, w, Co, ldo,
+                       nslope, sy, sx, drop);
   RGBM_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -216,7 +231,8 @@ int launch_t(const void* z, const float* bias, void* out, int V, int h, int w, i
 
 // z [V][h][w][9*Co] (tap-major channel blocks) -> out [V][2h][2w][ldo] (first Co channels) = act(bias + sum over taps)
 int launch_upconv_combine(int dtype, const void* z, const float* bias, void* out, int V, int h, int w, int Co, int ldo, int act,
-                          float slope, hipStream_t s) {
+                          float slope, hipStream_t s, const float* drop) {
+  RGBM_REQUIRE(drop == nullptr || (((uintptr_t)drop & 15) == 0 && Co <= 256), "upconv combine: dropout factors (16-byte aligned, <= 256 channels)");
   RGBM_REQUIRE(Co % 4 == 0 && ldo % dtype_chunk(dtype) == 0 && h >= 2 && w >= 2, "upconv combine geometry");
   RGBM_REQUIRE(act == ACT_NONE || act == ACT_RELU || act == ACT_PRELU, "upconv combine activation");
   const float sy = (float)(h - 1) / (float)(2 * h - 1), sx = (float)(w - 1) / (float)(2 * w - 1);
@@ -228,10 +244,10 @@ int launch_upconv_combine(int dtype, const void* z, const float* bias, void* out
   // made hipcc sink every accumulation chain into the epilogue (all interpolated values live at once)
   const float nslope = act == ACT_NONE ? 1.f : act == ACT_RELU ? 0.f : slope;
   int rc;
-  if (dtype == BF16) rc = launch_t<unsigned short>(z, bias, out, V, h, w, Co, ldo, nslope, sy, sx, s);
-  else if (dtype == F16) rc = launch_t<f16_t>(z, bias, out, V, h, w, Co, ldo, nslope, sy, sx, s);
-  else if (dtype == BF16X3) rc = launch_t<bx3_t>(z, bias, out, V, h, w, Co, ldo, nslope, sy, sx, s);
-  else rc = launch_t<float>(z, bias, out, V, h, w, Co, ldo, nslope, sy, sx, s);
+  if (dtype == BF16) rc = launch_t<unsigned short>(z, bias, out, V, h, w, Co, ldo, nslope, sy, sx, s, drop);
+  else if (dtype == F16) rc = launch_t<f16_t>(z, bias, out, V, h, w, Co, ldo, nslope, sy, sx, s, drop);
+  else if (dtype == BF16X3) rc = launch_t<bx3_t>(z, bias, out, V, h, w, Co, ldo, nslope, sy, sx, s, drop);
+  else rc = launch_t<float>(z, bias, out, V, h, w, Co, ldo, nslope, sy, sx, s, drop);
   prof_end_launch(s);
   return rc;
 }

@@ -130,6 +130,18 @@ def _split(n, parts):
     return [(n * i // parts, n * (i + 1) // parts) for i in range(parts)]
 
 
+def dropout_cfg(cfg) -> tuple:
+    """(hip_norm_mode, hip_dropout, hip_dropout_seed) of an estimator cfg.  hip_as_shipped: true is the reference as shipped
+    (interface_v5.py:39-56 never calls .eval(), rl_pose.py predicts one pose per call): per-sample BatchNorm3d statistics and
+    PSPNet's Dropout2d(p = 0.15) — shorthand for hip_norm_mode: per_sample + hip_dropout: 0.15; keys given explicitly win."""
+    shipped = bool(cfg.get("hip_as_shipped", False))
+    norm_mode = cfg.get("hip_norm_mode", "per_sample" if shipped else "eval")
+    p = float(cfg.get("hip_dropout", 0.15 if shipped else 0.0))
+    if not (p == 0.0 or 0.0 < p < 1.0):
+        raise ValueError(f"hip_dropout must be 0 (off) or lie in (0, 1), got {p}")
+    return norm_mode, p, int(cfg.get("hip_dropout_seed", 0))
+
+
 class AdaPoseEstimator_v5(BasePoseEstimator):
     def __init__(self, env, cfg, logger, state_dict=None, dtype=None, device=0, net=None):
         """`net`: an already built `AdaPoseNet` to share (weights + workspace) instead of building one from `state_dict`."""
@@ -151,8 +163,10 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         # ten outputs and `predict` builds the box from view1_nocs / view1_depth / view1_r alone (interface_v5.py:318-374), so the
         # cost volume, point heads and pose regression of the view-2 crops are skipped — the backbone still runs on both views
         self.view2_heads = bool(cfg.get("hip_view2_heads", not cfg.get("direct_regression", True) and not cfg.get("use_depth", True)))
+        # hip_dropout / hip_dropout_seed / hip_as_shipped (dropout_cfg): PSPNet's Dropout2d, seeded, fresh masks on every forward
+        norm_mode, drop_p, drop_seed = dropout_cfg(cfg)
         self.estimator = net if net is not None else AdaPoseNet(state_dict, dtype=self.dtype, device=device,
-                                                                norm_mode=cfg.get("hip_norm_mode", "eval"),
+                                                                norm_mode=norm_mode, dropout=drop_p, dropout_seed=drop_seed,
                                                                 graph=bool(cfg.get("hip_graph", False)),
                                                                 graph_max_batch=int(cfg.get("hip_graph_max_batch", 32)),
                                                                 options={**{str(k): int(v) for k, v in dict(cfg.get("hip_options", {}) or {}).items()},
@@ -167,6 +181,10 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                 raise ValueError("AdaPoseEstimator_v5: this cfg needs the view-2 heads (hip_view2_heads, or the PnP tail of "
                                  "direct_regression=False / use_depth=False), but the shared net was built with view2_heads=0")
             self.view2_heads = net_v2
+            # ... and Dropout2d: the shared handle draws one mask sequence (resetting it here would restart the other users' sequence)
+            if float(np.float32(net.dropout)) != float(np.float32(drop_p)) or (drop_p > 0 and net.dropout_seed != drop_seed):
+                raise ValueError(f"AdaPoseEstimator_v5: this cfg asks for dropout p={drop_p} seed={drop_seed} (hip_dropout / hip_as_shipped), "
+                                 f"but the shared net runs p={net.dropout} seed={net.dropout_seed}")
             # ... and the same for hip_options: a key this cfg names must already hold on the shared net (round-5 advice: silently
             # ignoring e.g. {"sweep_f16": 0} would run the f16 feature map the user opted out of)
             want = {str(k): int(v) for k, v in dict(cfg.get("hip_options", {}) or {}).items()}

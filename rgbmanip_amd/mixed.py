@@ -36,6 +36,9 @@ class MixedObjectNet:
         (tests/test_gpu_adapose.py::test_mixed_object_batch_equals_per_head_runs).  Measured at 4 x 64 poses (tools/mixed_ab.py, one box):
         fp16 50.7 -> 45.6 ms, bf16 45.6 -> 41.1 ms per mixed batch of 256.  (One network's batch cut into equal parts on as many
         streams does not gain: tools/split_parts_ab.py, -1 % with two parts, +3 % with four.)"""
+        if net_kw.get("dropout") or net_kw.get("dropout_seed"):
+            raise ValueError("MixedObjectNet: Dropout2d (dropout / dropout_seed) is not supported for mixed batches; build one "
+                             "AdaPoseNet(dropout=...) per object instead")
         self.state_dicts, self.dtype, self.device, self.net_kw = dict(state_dicts), dtype, device, net_kw
         self.nets = {}
         self.head_streams = bool(head_streams)

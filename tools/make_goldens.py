@@ -191,6 +191,61 @@ def gen_adapose_trainbn(out_dir):
         print("trainbn", k, v.shape, float(np.abs(v).mean()), bool(np.isfinite(v).all()))
 
 
+def gen_adapose_dropout(out_dir):
+    """The as-shipped estimator in full: the reference module in .train() with its Dropout2d ACTIVE, one pose per call (as
+    gen_adapose_trainbn).  Torch's random stream is not reproducible on the device, so every call of PSPNet.drop is wrapped: the keep
+    mask of the call is recorded (the module run on a ones tensor under the saved RNG state), the RNG state restored, the module run
+    on the real input, and the two checked to agree.  Saves the masks in the C ABI's order (rgbm_adapose_set_dropout_masks:
+    masks[V][up_1's 256 channels, then up_2's 64], views = the view-1 crops of the batch, then the view-2 crops) and the ten outputs."""
+    from models.pose_estimator.AdaPose.lib.network_v5 import StereoPoseNet_with_depth
+    from rgbmanip_amd import synth
+
+    torch.manual_seed(1234)
+    net = StereoPoseNet_with_depth(n_cat=1, nv_pts=1024, regress_pose=True)
+    sd = synth.adapose_state_dict(seed=0)
+    net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    net.train()
+    drop = net.img_extractor.drop
+    assert isinstance(drop, torch.nn.Dropout2d) and drop.p == 0.15
+    inner = drop.forward
+    calls = []
+
+    def recording_forward(x):
+        state = torch.get_rng_state()
+        m = inner(torch.ones_like(x))
+        torch.set_rng_state(state)
+        y = inner(x)
+        mc = m[:, :, 0, 0]
+        assert torch.equal(m, mc[:, :, None, None].expand_as(m))          # one factor per (sample, channel)
+        assert torch.equal(y, x * mc[:, :, None, None])
+        calls.append(mc[0].clone())
+        return y
+
+    drop.forward = recording_forward
+    B = 2
+    inp = synth.adapose_inputs(B, seed=0)
+    tin = {k: torch.from_numpy(v) for k, v in inp.items()}
+    outs = []
+    masks = np.zeros((2 * B, 320), np.float32)
+    with torch.no_grad():
+        for b in range(B):
+            one = lambda k: tin[k][b:b + 1]  # noqa: E731
+            calls.clear()
+            outs.append(net(one("img1"), one("choose1"), one("img2"), one("choose2"), one("P1"), one("P2"), one("depths")))
+            # img_extractor(view1) then img_extractor(view2) (network_v5.py:423-424), each: drop after up_1, drop after up_2
+            assert [c.numel() for c in calls] == [256, 64, 256, 64], [c.numel() for c in calls]
+            for side in range(2):
+                masks[side * B + b, :256] = calls[2 * side].numpy()
+                masks[side * B + b, 256:] = calls[2 * side + 1].numpy()
+    assert set(np.unique(masks).tolist()) <= {0.0, float(np.float32(1.0) / np.float32(0.85))}, np.unique(masks)
+    save = {k: torch.cat([o[k] for o in outs]).numpy() for k in outs[0]}
+    save["masks"] = masks
+    np.savez_compressed(os.path.join(out_dir, "adapose_b2_dropout.npz"), **save)
+    print("dropout keep fraction", float((masks != 0).mean()))
+    for k, v in save.items():
+        print("dropout", k, v.shape, float(np.abs(v).mean()), bool(np.isfinite(v).all()))
+
+
 def gen_postproc(out_dir, net_out, inp):
     from models.pose_estimator.AdaPose.lib import utils as U
 
@@ -682,7 +737,8 @@ if __name__ == "__main__":
     out_dir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(out_dir, exist_ok=True)
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["adapose", "adapose_trainbn", "postproc", "ppo", "ppo_run", "control", "control_step", "control_save", "align"]
+    which = sys.argv[1:] or ["adapose", "adapose_trainbn", "postproc", "ppo", "ppo_run", "control", "control_step", "control_save", "align",
+                             "adapose_dropout"]
     if "adapose_trainbn" in which:
         gen_adapose_trainbn(out_dir)
     net_out = inp = None
@@ -702,4 +758,6 @@ if __name__ == "__main__":
         gen_control_save(out_dir)
     if "align" in which:
         gen_align(out_dir)
+    if "adapose_dropout" in which:        # last: its torch.manual_seed cannot reach the generators above
+        gen_adapose_dropout(out_dir)
     print("done")
