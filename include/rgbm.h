@@ -303,6 +303,13 @@ int rgbm_conv_nd(int dtype, const void* in_dev, int N, int D, int H, int W, int 
                  int Cout, int Cout_pad, int KD, int KH, int KW, int stride_d, int stride_hw, int pad_d, int pad_hw,
                  int dil_hw, int transposed, const float* bias_host, const float* bn_scale_host, const float* bn_shift_host,
                  const void* res_dev, int res_mode, int act, float slope, void* out_dev, void* stream);
+/* Per-sample BatchNorm3d of the as-shipped mode (norm_mode = 1), in place: y_dev [V][nvox][C] (C % 4 == 0, C <= 64) in `dtype`
+ * -> relu(gamma * (y - mean_v) / sqrt(var_v + 1e-5) + beta) + res, with the biased mean / variance of each view v's own volume;
+ * relu 0 skips the ReLU, res_dev may be null (post-activation skip add otherwise, same layout).  gamma_dev / beta_dev [C] fp32;
+ * scratch_dev holds rgbm_bn_per_sample_scratch_bytes(V) bytes. */
+int rgbm_bn_per_sample_scratch_bytes(int V, size_t* bytes);
+int rgbm_bn_per_sample(int dtype, void* y_dev, const void* res_dev, const float* gamma_dev, const float* beta_dev, void* scratch_dev,
+                       int V, int64_t nvox, int C, int relu, void* stream);
 /* Halo-tiled 3-D conv of the cost-regularisation stack, one layer: layer 0..6 = conv0..conv6 (k3, pad 1, stride 1/2),
  * 7..9 = conv7/conv9/conv11 (ConvTranspose3d k3 s2 p1 op1).  Channels are fixed by the layer (network_v5.py:263-278);
  * in_dev [N][D][H][W][Cin], out_dev [N][Do][Ho][Wo][Cout], folded BN scale/shift on the host, ReLU, optional

@@ -118,6 +118,8 @@ SIGNATURES = {
     "rgbm_ppo_clip_adam": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp]),
     "rgbm_conv_nd": (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                           _vp, _i, _i, _f, _vp, _vp]),
+    "rgbm_bn_per_sample_scratch_bytes": (_i, [_i, C.POINTER(_sz)]),
+    "rgbm_bn_per_sample": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     "rgbm_conv3d_tile": (_i, [_i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_upsample_conv3x3": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
     "rgbm_upsample_conv3x3_final": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp]),

@@ -51,14 +51,15 @@ __global__ void bn_finalize_kernel(const double* __restrict__ part, const float*
   const double mean = a * inv_n;
   double var = b * inv_n - mean * mean;                    // biased variance: what BatchNorm normalises with in training mode
   if (var < 0) var = 0;
-  const float scale = gamma[c] * (float)(1.0 / sqrt(var + (double)eps));
-  ss[2 * i] = scale;
-  ss[2 * i + 1] = beta[c] - (float)mean * scale;
+  ss[2 * i] = gamma[c] * (float)(1.0 / sqrt(var + (double)eps));
+  ss[2 * i + 1] = (float)mean;                             // (y - mean) * scale + beta, as BatchNorm forms it: folding the mean into
+                                                           // one shift, y * scale + (beta - mean * scale), cancels in fp32 when
+                                                           // |mean| * scale >> the output (a near-constant channel: scale ~ gamma / sqrt(eps))
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void bn_apply_kernel(T* __restrict__ y, const float* __restrict__ ss, const T* __restrict__ res,
-                                                         long long nvox, int C, int V, int relu) {
+__global__ __launch_bounds__(256) void bn_apply_kernel(T* __restrict__ y, const float* __restrict__ ss, const float* __restrict__ beta,
+                                                         const T* __restrict__ res, long long nvox, int C, int V, int relu) {
   const int cg = C >> 2;
   const long long per_view = nvox * cg, total = per_view * V;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(T* __restrict__ y, const 
     const float* t = ss + ((long long)v * C + g * 4) * 2;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float o = f[e] * t[2 * e] + t[2 * e + 1];
+      float o = (f[e] - t[2 * e + 1]) * t[2 * e] + beta[g * 4 + e];
       if (relu) o = o < 0.f ? 0.f : o;                     // NaN propagates, like torch.relu
       f[e] = o + r[e];                                     // skip adds are post-ReLU (network_v5.py:287-289)
     }
@@ -85,7 +86,7 @@ int run_t(void* y, const void* res, const float* gamma, const float* beta, doubl
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((V * C + 127) / 128), dim3(128), 0, s, part, gamma, beta, ss, V, C, 1.0 / (double)nvox, 1e-5f);
   const long long total = nvox * (C >> 2) * V;
   const long long blocks = (total + 255) / 256;
-  hipLaunchKernelGGL(bn_apply_kernel<T>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, (T*)y, ss, (const T*)res,
+  hipLaunchKernelGGL(bn_apply_kernel<T>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, (T*)y, ss, beta, (const T*)res,
                      nvox, C, V, relu);
   RGBM_CHECK_HIP(hipGetLastError());
   return 0;

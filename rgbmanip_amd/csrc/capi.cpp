@@ -389,6 +389,16 @@ int rgbm_stem(int dtype, const float* img1_dev, const float* img2_dev, const flo
   return rc;
 }
 
+int rgbm_bn_per_sample_scratch_bytes(int V, size_t* bytes) {
+  RGBM_REQUIRE(V > 0 && bytes, "bn_per_sample_scratch_bytes arguments");
+  *bytes = bn_scratch_bytes(V);
+  return 0;
+}
+int rgbm_bn_per_sample(int dtype, void* y_dev, const void* res_dev, const float* gamma_dev, const float* beta_dev, void* scratch_dev,
+                       int V, int64_t nvox, int C, int relu, void* stream) {
+  RGBM_REQUIRE(y_dev && gamma_dev && beta_dev && scratch_dev, "bn_per_sample arguments");
+  return launch_bn_per_sample(dtype, y_dev, res_dev, gamma_dev, beta_dev, scratch_dev, V, (long long)nvox, C, relu, (hipStream_t)stream);
+}
 int rgbm_maxpool3x3s2(int dtype, const void* in_dev, void* out_dev, int V, int H, int W, int C, void* stream) {
   return launch_maxpool3x3s2(dtype, in_dev, out_dev, V, H, W, C, (hipStream_t)stream);
 }

@@ -946,7 +946,9 @@ static int m32_ksplit_buffers(hipStream_t s, float** scratch, unsigned** count) 
     float* sc = nullptr; unsigned* cn = nullptr;
     RGBM_CHECK_HIP(hipMalloc(&sc, kM32SplitFloats * sizeof(float)));
     RGBM_CHECK_HIP(hipMalloc(&cn, kM32SplitCounters * sizeof(unsigned)));
-    RGBM_CHECK_HIP(hipMemset(cn, 0, kM32SplitCounters * sizeof(unsigned)));
+    // zeroed on the stream that uses them: a plain hipMemset goes to the null stream, which a non-blocking stream (torch's side streams)
+    // does not wait for — the first split launch there could read the counters before they were zero
+    RGBM_CHECK_HIP(hipMemsetAsync(cn, 0, kM32SplitCounters * sizeof(unsigned), s));
     e.first = sc; e.second = cn;
   }
   *scratch = e.first; *count = e.second;

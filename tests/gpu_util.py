@@ -98,9 +98,10 @@ def host_f32(a):
     return arr, C.c_void_p(arr.ctypes.data)
 
 
-def conv_nd(dtype, x, w, *, stride=1, stride_d=None, pad=0, pad_d=None, dil=1, transposed=False, bias=None, bn_scale=None,
-            bn_shift=None, res=None, res_mode=0, act=0, slope=0.0, cin_pad=None, cout_pad=None):
-    """x [N,C,D,H,W] or [N,C,H,W] cpu fp32; w torch layout.  Returns cpu fp32 [N,Cout,...] via the HIP conv."""
+def conv_nd_launcher(dtype, x, w, *, stride=1, stride_d=None, pad=0, pad_d=None, dil=1, transposed=False, bias=None, bn_scale=None,
+                     bn_shift=None, res=None, res_mode=0, act=0, slope=0.0, cin_pad=None, cout_pad=None):
+    """Uploads the operands of a HIP conv (arguments as conv_nd) and returns (launch, fetch): launch() runs rgbm_conv_nd on the current
+    stream into a fresh NaN-filled output and returns it (device, channels-last); fetch(out) -> cpu fp32 [N,Cout,...]."""
     lib = _lib.load()
     is2d = x.dim() == 4
     if is2d:
@@ -126,19 +127,156 @@ def conv_nd(dtype, x, w, *, stride=1, stride_d=None, pad=0, pad_d=None, dil=1, t
     cout_pad = cout_pad or (Cout + 3) // 4 * 4
     xd = to_channels_last(x, dtype, cin_pad)
     rd = to_channels_last(res, dtype, cout_pad) if res is not None else None
-    out = empty_out((N, Do, Ho, Wo, cout_pad), dtype)
     wa, wp = host_f32(w)
     ba, bp = host_f32(bias)
     sa, sp = host_f32(bn_scale)
     ha, hp = host_f32(bn_shift)
     sd = stride_d if stride_d is not None else (1 if is2d else stride)
     pd = pad_d if pad_d is not None else (0 if is2d else pad)
+
+    def launch():
+        out = empty_out((N, Do, Ho, Wo, cout_pad), dtype)
+        keep = (wa, ba, sa, ha)      # noqa: F841  (host arrays alive for the call)
+        rc = lib.rgbm_conv_nd(dtype, _lib.ptr(xd), N, D, H, W, Cin, cin_pad, wp, Cout, cout_pad, KD, KH, KW,
+                              2 if transposed else sd, 2 if transposed else stride, 1 if transposed else pd,
+                              1 if transposed else pad, dil, int(transposed), bp, sp, hp, _lib.ptr(rd), res_mode, act, slope,
+                              _lib.ptr(out), _lib.stream_ptr())
+        _lib.check(rc, "rgbm_conv_nd")
+        return out
+
+    def fetch(out):
+        y = from_channels_last(out, Cout)
+        return y.squeeze(2) if is2d else y
+    return launch, fetch
+
+
+def conv_nd(dtype, x, w, **kw):
+    """x [N,C,D,H,W] or [N,C,H,W] cpu fp32; w torch layout.  Returns cpu fp32 [N,Cout,...] via the HIP conv."""
+    launch, fetch = conv_nd_launcher(dtype, x, w, **kw)
     torch.cuda.synchronize()
-    rc = lib.rgbm_conv_nd(dtype, _lib.ptr(xd), N, D, H, W, Cin, cin_pad, wp, Cout, cout_pad, KD, KH, KW,
-                          2 if transposed else sd, 2 if transposed else stride, 1 if transposed else pd,
-                          1 if transposed else pad, dil, int(transposed), bp, sp, hp, _lib.ptr(rd), res_mode, act, slope,
-                          _lib.ptr(out), _lib.stream_ptr())
-    _lib.check(rc, "rgbm_conv_nd")
+    out = launch()
     torch.cuda.synchronize()
-    y = from_channels_last(out, Cout)
-    return y.squeeze(2) if is2d else y
+    return fetch(out)
+
+
+# ---------------------------------------------------------------- small-launch dispatch mirror
+# A restatement of the branch of conv_igemm_glds.hip::launch_dtype_g that picks the small-batch tiles (m32_small_choice) and of the K split
+# (conv_igemm_m32.inc::m32_ksplit_choice), for a conv at its defaults (uniform taps, aligned rows, gemm_kernel = 2, debug flags 0).  The
+# small-batch tests state the path they expect with it; tests/test_small_batch_dispatch.py checks that their cases reach every branch.
+
+WS_MIN_ROWS = 1024                  # ws_min_rows(): GEMM rows from which the persistent kernels (and these tiles) are used
+KSPLIT_MAX, KSPLIT_MINSTEPS = 4, 8  # M32_KSPLIT_MAX / M32_KSPLIT_MINSTEPS
+KSPLIT_FLOATS, KSPLIT_COUNTERS = 8 << 20, 16384
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def device_n_cu(device=0):
+    """persistent_grid_cus(): the device's compute units rounded down to a multiple of the 8 XCDs (at least 8)."""
+    return max(torch.cuda.get_device_properties(device).multi_processor_count // 8 * 8, 8)
+
+
+def m32_small_choice(M, Cout, n_cu, slim_ok):
+    """channel tile of the 128-pixel small launch (64 / 128 / 256), or 0 for 'keep the 64 x 256 tile of conv_igemm_ws_kernel'."""
+    p128, p256 = _cdiv(M, 128), _cdiv(M, 256)
+
+    def cost(tiles, kb):
+        return float(_cdiv(tiles, n_cu)) * (kb + 8)
+    best = cost(p256 * (Cout // 64), 40) if slim_ok else 1e30
+    pick = 0
+    for bch, kb in ((64, 24), (128, 32), (256, 48)):
+        if Cout % bch:
+            continue
+        c = cost(p128 * (Cout // bch), kb)
+        if c < best * 0.999:
+            best, pick = c, bch
+    return pick
+
+
+def m32_ksplit_choice(KT, tiles, n_cu, bch, n_waves=4):
+    """K parts of a small launch (1: no split)."""
+    if tiles <= 0 or bch > 128:
+        return 1
+    n = min(n_cu // tiles, KSPLIT_MAX)
+    while n > 1 and KT // n < KSPLIT_MINSTEPS:
+        n -= 1
+    if n < 2 or tiles * n * bch * 128 > KSPLIT_FLOATS or tiles * n_waves > KSPLIT_COUNTERS:
+        return 1
+    return n
+
+
+def small_launch_plan(M, Cout, KT, n_cu):
+    """(tile channels, tile pixels, K parts) of a 16-bit / split-pair conv with M GEMM rows, or None where the small-batch branch does
+    not apply (fp32, <= 64 channels, fewer than WS_MIN_ROWS rows, or enough tiles to fill the grid)."""
+    if Cout <= 64 or Cout % 64 or M < WS_MIN_ROWS:
+        return None
+    slim_tiles = _cdiv(M, 256) * (Cout // 64)
+    if Cout % 256 == 0 and _cdiv(M, 256) * (Cout // 256) < n_cu:
+        pick = m32_small_choice(M, Cout, n_cu, slim_tiles <= n_cu)
+        if pick:
+            return pick, 128, m32_ksplit_choice(KT, _cdiv(M, 128) * _cdiv(Cout, pick), n_cu, pick)
+    if Cout == 128 and _cdiv(M, 128) * 2 * 2 <= n_cu:
+        return 64, 128, m32_ksplit_choice(KT, _cdiv(M, 128) * 2, n_cu, 64)
+    if slim_tiles <= n_cu:
+        return 64, 256, 1
+    return None
+
+
+def conv_out_hw(H, W, k, stride, pad, dil):
+    return (H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+
+
+def conv_case_plan(case, dtype, n_cu):
+    """The mirror applied to a conv case (name, N, Cin, H, W, Cout, k, stride, pad, dil, bias, act, res_mode) as conv_nd launches it.
+    Returns a dict: tile (channels, pixels) or None, parts, KT, and the residual path of a small launch ('epilogue': the Cout = 128
+    tile adds it after the reduction; 'identity': 256-multiple channels add a pre-activation residual by identity K steps)."""
+    _, N, Cin, H, W, Cout, k, stride, pad, dil, _, _, res_mode = case
+    Ho, Wo = conv_out_hw(H, W, k, stride, pad, dil)
+    M = N * Ho * Wo
+    if dtype == _lib.F32:
+        return {"M": M, "KT": None, "tile": None, "parts": 1, "res": None}
+    E = 4 if dtype == _lib.BF16X3 else 8
+    BK = 8 * E
+    cin_pad = _cdiv(Cin, E) * E
+    assert k == 1 or cin_pad & (cin_pad - 1) == 0, "multi-tap convs need a power-of-two Cin"
+    KT = _cdiv(k * k * cin_pad, BK)
+    plan = small_launch_plan(M, Cout, KT, n_cu)
+    tile, parts = (plan[:2], plan[2]) if plan else (None, 1)
+    res = None
+    if tile is not None and tile[1] == 128 and res_mode:
+        res = "identity" if Cout % 256 == 0 and res_mode == 1 else "epilogue"
+    return {"M": M, "KT": KT, "tile": tile, "parts": parts, "res": res}
+
+
+def _backbone_small_cases():
+    # ResNet-34 layer2..4 as PSPNet runs them (oracle/adapose_ref.py RESNET34_LAYERS) on a 28 x 28 feature map (layer2's block 0 reads
+    # layer1's 56 x 56), at 2 .. 16 views = 1 .. 8 poses
+    shapes = [
+        # tag, Cin, H, Cout, k, stride, pad, dil, act, res_mode
+        ("l2_b0_conv1", 64, 56, 128, 3, 2, 1, 1, 1, 0),
+        ("l2_b0_down", 64, 56, 128, 1, 2, 0, 1, 0, 0),
+        ("l2_conv2_res", 128, 28, 128, 3, 1, 1, 1, 1, 1),
+        ("l3_b0_conv1", 128, 28, 256, 3, 1, 1, 1, 1, 0),
+        ("l3_b0_down", 128, 28, 256, 1, 1, 0, 1, 0, 0),
+        ("l3_conv2_res", 256, 28, 256, 3, 1, 2, 2, 1, 1),
+        ("l4_b0_conv1", 256, 28, 512, 3, 1, 1, 1, 1, 0),
+        ("l4_b0_down", 256, 28, 512, 1, 1, 0, 1, 0, 0),
+        ("l4_conv2_res", 512, 28, 512, 3, 1, 4, 4, 1, 1),
+    ]
+    out = []
+    for tag, Cin, H, Cout, k, s, p, d, act, rm in shapes:
+        for N in (2, 4, 6, 8, 10, 16):
+            out.append((f"{tag}_n{N}", N, Cin, H, H, Cout, k, s, p, d, False, act, rm))
+    return out
+
+
+SMALL_CONV_CASES = _backbone_small_cases() + [
+    # synthetic (1x1: the only multi-K-step convs with a Cin that is not a power of two): K loops that do not divide into their parts
+    # (25 / 50 K steps in 2, 3 or 4 parts: part p starts at p * KT / n, the parts differ in length), post-activation residuals, biases
+    ("syn_1x1_cin1600_post_n2", 2, 1600, 28, 28, 128, 1, 1, 0, 1, True, 1, 2),
+    ("syn_1x1_cin1600_post_n8", 8, 1600, 28, 28, 128, 1, 1, 0, 1, True, 2, 2),
+    ("syn_1x1_cin1600_c256_res_n2", 2, 1600, 28, 28, 256, 1, 1, 0, 1, False, 1, 1),
+    ("syn_1x1_cin1600_c256_post_n4", 4, 1600, 28, 28, 256, 1, 1, 0, 1, True, 2, 2),
+]

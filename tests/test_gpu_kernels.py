@@ -230,12 +230,24 @@ def test_conv2d_k_split_is_stable_over_many_runs(dtype):
             assert torch.equal(run(), y0), (name, i)
 
 
+SAT_SMALL_CASES = [
+    # the small-batch launches (B = 1 .. 4 poses at 28 x 28; tile and K parts on 256 CUs from tests/gpu_util.py::small_launch_plan):
+    # layer2's 128-channel layer on the 64 x 128 K-split tile with its residual in the epilogue (2 parts), layer3 on the 64 x 128 tile
+    # (4 parts, residual by identity K steps), layer4 on the 128 x 128 and 256 x 128 tiles, a post-activation residual behind 3 parts
+    ("sat_l2_res_n2", 2, 128, 28, 28, 128, 3, 1, 1, 1, False, 1, 1),
+    ("sat_l3_res_n2", 2, 256, 28, 28, 256, 3, 1, 2, 2, False, 1, 1),
+    ("sat_l4_res_n6", 6, 256, 28, 28, 512, 3, 1, 4, 4, False, 1, 1),
+    ("sat_l4_res_n8", 8, 512, 28, 28, 512, 3, 1, 4, 4, False, 1, 1),
+    ("sat_1x1_post_n2", 2, 1600, 28, 28, 128, 1, 1, 0, 1, True, 1, 2),
+]
+
+
 @pytest.mark.parametrize("name", ["l2_3x3_s2", "up_prelu", "ws128_res_pre", "ws128_1x1_s1", "ws64_prelu_bias", "ws64_rowhalo_dil2",
-                                  "ws64_1x1_res_post_prelu"])
+                                  "ws64_1x1_res_post_prelu"] + [c[0] for c in SAT_SMALL_CASES])
 def test_conv2d_fp16_stores_saturate(name):
     """fp16 storage: results beyond +-65504 are stored as +-65504, not inf, for every kernel variant the dispatcher can pick."""
     from gpu_util import conv_nd
-    case = [c for c in CONV2D_CASES if c[0] == name][0]
+    case = [c for c in CONV2D_CASES + SAT_SMALL_CASES if c[0] == name][0]
     _, N, Cin, H, W, Cout, k, stride, pad, dil, has_bias, act, res_mode = case
     g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000)
     x = (torch.randn(N, Cin, H, W, generator=g) * 2000.0).half().float()
@@ -243,6 +255,10 @@ def test_conv2d_fp16_stores_saturate(name):
     b = torch.randn(Cout, generator=g) * 0.1 if has_bias else None
     res = (torch.randn(N, Cout, (H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1,
                        generator=g) * 3e4).half().float() if res_mode else None
+    if res is not None and name.startswith("sat_"):
+        # finite residuals: an fp16 activation is never inf (every store saturates), and the identity K steps of the 256-multiple
+        # small launches add a whole residual block with weights 0 / 1 (0 * inf would be NaN)
+        res = res.clamp(-65504.0, 65504.0)
     ref = F.conv2d(x, w, b, stride, pad, dil)
     if res_mode == 1:
         ref = ref + res
