@@ -5,13 +5,19 @@ One "step" = one pass of the estimator hot path over one batch of 256 synthetic 
   HIP network forward (2 x 256 views of 224x224, all 10 outputs)  +  device post-processing to world boxes,
 with every input already resident in HBM.  The headline inputs come through the reference's own crop logic (480x640 frames with an
 elliptical object mask -> crop window of lib/utils.py:10-38 -> 224x224 crop + 1024 chosen pixels, rgbm_prepare_inputs), so the
-masks span their crops as the reference's do; `value_dense` (every layer computed densely), `value_worst_case` (chosen pixels all
-over the crop) and `value_survey_masks` (SURVEY 8d's ellipses inside the crop, the headline of rounds 1-3) are timed in the same run.  N > 1: one process per GPU (torch.distributed, RCCL); poses are
+masks span their crops as the reference's do.  N > 1: one process per GPU (torch.distributed, RCCL); poses are
 independent, so ranks shard the batch with no data-path collective (weak scaling, 256 poses per GPU).
 
 Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events around every launch of the
-dominant kernel (the library's rgbm_prof_* hooks, same stream as the launches); `cpu_baseline` times the CPU
-oracle (PyTorch-CPU restatement of the reference, proven equal to it on golden vectors) on this box's host cores.
+dominant kernel (the library's rgbm_prof_* hooks, same stream as the launches).
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  Every
+other leg runs only with --full: `value_dense` (every layer computed densely), `value_worst_case` (chosen pixels all over the
+crop) and `value_survey_masks` (SURVEY 8d's ellipses inside the crop, the headline of rounds 1-3), the bf16x3 / fp32 modes, the
+accuracy against the golden vectors and against the oracle on the timed batch, two streams, the plugin boundary, small batches,
+achievable peaks, prepare_model_input, mixed objects, PPO, and `cpu_baseline`, which times the CPU oracle (PyTorch-CPU
+restatement of the reference, proven equal to it on golden vectors) on the host cores.  The --no-* switches skip single legs of a
+--full run.
 """
 import argparse
 import ctypes as C
@@ -393,6 +399,9 @@ def main():
     ap.add_argument("--inputs", default="crop", choices=["crop", "survey", "uniform"],
                     help="headline inputs: crop = 480x640 frames through the reference's crop window (masks span their crops); survey = "
                          "SURVEY 8d's ellipses inside the 224 crop (rounds 1-3); uniform = chosen pixels all over the crop")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg after the headline (modes, dense / worst-case / survey inputs, accuracy, two streams, plugin "
+                         "boundary, small batches, peaks, prepare, mixed objects, PPO, CPU baseline); a plain run times the headline alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--chunk", type=int, default=0, help="views per cost-volume chunk (0 = library default)")
     ap.add_argument("--ppo-envs", type=int, default=512, help="envs per GPU for the PPO leg (0 = skip it)")
@@ -422,6 +431,11 @@ def main():
         ap.error("--steps must be at least 1")
     if os.environ.get("RGBM_BENCH_CHOOSE") == "uniform":      # rounds 1-3 spelling of --inputs uniform
         args.inputs = "uniform"
+    if not args.full:      # the headline alone: every side leg off; the warm-up, the profiled step and the timed steps are the same either way
+        for leg in ("no_cpu_baseline", "no_modes", "no_dense_leg", "no_boundary", "no_small_batch", "no_peaks", "no_prepare", "no_mixed",
+                    "no_accuracy"):
+            setattr(args, leg, True)
+        args.ppo_envs = 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -966,7 +980,7 @@ def main():
         res = {
             "metric": "adapose_poses_per_sec_batch256", "value": round(value, 3), "unit": "poses/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": f"adapose_cabinet forward + post-processing, batch={B} poses ({2 * B} views of 224x224) per GPU, "
                                    "synthetic RGB, random-init weights of the reference architecture; inputs: " + inputs_desc,
                        "poses_per_gpu": B, "unique_poses": n_unique, "outputs": "all 10 network outputs + world bbox", "parallelism": f"dp{world}",
