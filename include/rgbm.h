@@ -261,8 +261,13 @@ int rgbm_gae(int T, int N, const float* rewards, const uint8_t* dones, const flo
 int rgbm_adv_normalise(int64_t n_local, float* adv, const double* sums, double count_total, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
- * PPO policy (actor-critic MLPs obs -> h0 -> h1 -> h2 -> {act, 1}, ELU) on a flat fp32 parameter vector laid out in the
- * reference's state_dict order (log_std, actor.{0,2,4,6}.{weight,bias}, critic.{0,2,4,6}.{weight,bias}).
+ * PPO policy (actor-critic MLPs) on a flat fp32 parameter vector laid out in the reference's state_dict order
+ * (log_std, actor.{0,2,..}.{weight,bias}, critic.{0,2,..}.{weight,bias}).  Two descriptors: rgbm_policy_layout is the
+ * shipped shape (obs -> h0 -> h1 -> h2 -> {act, 1}, ELU, both nets alike, widths <= 128, action dim <= 16);
+ * rgbm_policy_desc and the *_ex entry points cover every ActorCritic the reference builds (module.py:10-54): per net 1..6
+ * hidden layers of width 1..512, observation / state dim 1..512, action dim 1..32, one of six activations, an optional
+ * second input for the critic, clipped or plain-MSE value loss.  A descriptor of the shipped shape runs the same kernels
+ * through either set of entry points.  fp32 throughout; a descriptor outside the bounds is an error, nothing is launched.
  * Replaces: ActorCritic.act / act_inference / evaluate   algo/ppo/ppo/module.py:73-107
  *           one minibatch of PPO.update                   algo/ppo/ppo/ppo.py:472-528
  * ---------------------------------------------------------------------------------------------------------- */
@@ -291,6 +296,43 @@ int rgbm_ppo_minibatch_fwd_bwd(const float* params, const rgbm_policy_layout* L,
 int rgbm_ppo_clip_adam(float* params, const float* grads_flat, float* exp_avg, float* exp_avg_sq, void* opt_state,
                        const rgbm_policy_layout* L, float inv_world, float max_norm, float desired_kl, float lr_min,
                        float lr_max, int adaptive, void* stream);
+
+#define RGBM_POLICY_MAX_HIDDEN 6      /* hidden layers per net */
+#define RGBM_POLICY_MAX_WIDTH 512     /* hidden width, observation dim, state dim */
+#define RGBM_POLICY_MAX_ACT 32        /* action dim */
+#define RGBM_ACT_ELU 0
+#define RGBM_ACT_SELU 1               /* torch's scale / alpha */
+#define RGBM_ACT_RELU 2               /* the reference's "relu" and "crelu" */
+#define RGBM_ACT_LRELU 3              /* LeakyReLU(0.01) */
+#define RGBM_ACT_TANH 4
+#define RGBM_ACT_SIGMOID 5
+typedef struct rgbm_policy_desc {
+  int obs_dim, state_dim, act_dim;
+  int activation;                     /* RGBM_ACT_*, both nets */
+  int asymmetric;                     /* 1: the critic's first layer reads states [n,state_dim] instead of obs */
+  int n_hidden[2];                    /* [net: 0 actor, 1 critic] */
+  int hidden[2][RGBM_POLICY_MAX_HIDDEN];
+  int w[2][RGBM_POLICY_MAX_HIDDEN + 1];   /* n_hidden+1 linear layers per net: weight offsets (floats), row-major [out][in] */
+  int b[2][RGBM_POLICY_MAX_HIDDEN + 1];
+  int log_std;
+  int total;                          /* number of parameters */
+} rgbm_policy_desc;
+/* rgbm_policy_forward for any descriptor; states may be NULL unless asymmetric and mode != 1. */
+int rgbm_policy_forward_ex(const float* params, const rgbm_policy_desc* D, int n, int mode, const float* obs, const float* states,
+                           const float* noise, float* actions, float* logp, float* value, float* mu, void* stream);
+/* floats of device scratch rgbm_ppo_minibatch_fwd_bwd_ex needs for n rows: per 64-row tile the partial gradient and, for the
+ * general kernels, the activations and deltas of both nets (the backward pass keeps them in global memory, not in LDS). */
+int rgbm_ppo_scratch_floats_ex(const rgbm_policy_desc* D, int n, int clipped_value_loss, size_t* count);
+/* rgbm_ppo_minibatch_fwd_bwd for any descriptor.  clipped_value_loss 1: max((v-ret)^2, (v_clipped-ret)^2) (ppo.py:505-510);
+ * 0: mean((ret-v)^2) (ppo.py:512), old_values may then be NULL.  Same grads_flat layout; the reduction over tiles is
+ * fixed-order, so the same inputs give the same bits. */
+int rgbm_ppo_minibatch_fwd_bwd_ex(const float* params, const rgbm_policy_desc* D, int n, const float* obs, const float* states,
+                                  const float* actions, const float* old_logp, const float* adv, const float* returns,
+                                  const float* old_values, const float* old_mu, const float* old_log_std, float clip, float vcoef,
+                                  float ecoef, int clipped_value_loss, float* scratch, float* grads_flat, void* stream);
+/* rgbm_ppo_clip_adam by parameter count. */
+int rgbm_ppo_clip_adam_ex(float* params, const float* grads_flat, float* exp_avg, float* exp_avg_sq, void* opt_state, int total,
+                          float inv_world, float max_norm, float desired_kl, float lr_min, float lr_max, int adaptive, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Layer-level entry points (used by the parity tests and by the Python host for pieces it drives itself).

@@ -67,6 +67,17 @@ class PolicyLayout(C.Structure):
     _fields_ = [("dims", C.c_int * 5), ("log_std", C.c_int), ("w", (C.c_int * 4) * 2), ("b", (C.c_int * 4) * 2), ("total", C.c_int)]
 
 
+POLICY_MAX_HIDDEN, POLICY_MAX_WIDTH, POLICY_MAX_ACT = 6, 512, 32
+POLICY_ACTIVATIONS = {"elu": 0, "selu": 1, "relu": 2, "crelu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5}      # RGBM_ACT_*
+
+
+class PolicyDesc(C.Structure):                   # rgbm_policy_desc
+    _fields_ = [("obs_dim", C.c_int), ("state_dim", C.c_int), ("act_dim", C.c_int), ("activation", C.c_int), ("asymmetric", C.c_int),
+                ("n_hidden", C.c_int * 2), ("hidden", (C.c_int * POLICY_MAX_HIDDEN) * 2),
+                ("w", (C.c_int * (POLICY_MAX_HIDDEN + 1)) * 2), ("b", (C.c_int * (POLICY_MAX_HIDDEN + 1)) * 2),
+                ("log_std", C.c_int), ("total", C.c_int)]
+
+
 class AdaposeOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("view1_nocs", "view2_nocs", "view1_depth", "view2_depth", "view1_r", "view2_r",
                                            "view1_t", "view2_t", "view1_s", "view2_s")]
@@ -116,6 +127,10 @@ SIGNATURES = {
     "rgbm_ppo_partial_floats": (_i, [_vp, _i, C.POINTER(_sz)]),
     "rgbm_ppo_minibatch_fwd_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "rgbm_ppo_clip_adam": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp]),
+    "rgbm_policy_forward_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rgbm_ppo_scratch_floats_ex": (_i, [_vp, _i, _i, C.POINTER(_sz)]),
+    "rgbm_ppo_minibatch_fwd_bwd_ex": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp, _vp]),
+    "rgbm_ppo_clip_adam_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _i, _vp]),
     "rgbm_conv_nd": (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                           _vp, _i, _i, _f, _vp, _vp]),
     "rgbm_bn_per_sample_scratch_bytes": (_i, [_i, C.POINTER(_sz)]),

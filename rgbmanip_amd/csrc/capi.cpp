@@ -631,6 +631,39 @@ int rgbm_ppo_minibatch_fwd_bwd(const float* params, const rgbm_policy_layout* L,
   return launch_ppo_minibatch(params, *reinterpret_cast<const PolicyLayout*>(L), n, obs, actions, old_logp, adv, returns,
                               old_values, old_mu, old_log_std, clip, vcoef, ecoef, partial_scratch, grads_flat, (hipStream_t)stream);
 }
+static_assert(sizeof(rgbm_policy_desc) == sizeof(rgbm::PolicyDesc), "policy desc ABI mismatch");
+static_assert(RGBM_POLICY_MAX_HIDDEN == rgbm::POLICY_MAX_HIDDEN && RGBM_POLICY_MAX_WIDTH == rgbm::POLICY_MAX_WIDTH &&
+                  RGBM_POLICY_MAX_ACT == rgbm::POLICY_MAX_ACT && RGBM_ACT_ELU == rgbm::PACT_ELU && RGBM_ACT_SIGMOID == rgbm::PACT_SIGMOID,
+              "policy desc constants");
+
+int rgbm_policy_forward_ex(const float* params, const rgbm_policy_desc* D, int n, int mode, const float* obs, const float* states,
+                           const float* noise, float* actions, float* logp, float* value, float* mu, void* stream) {
+  RGBM_REQUIRE(params && D && obs && mu, "policy_forward_ex arguments");
+  RGBM_REQUIRE(mode == 1 || (logp && value && actions), "policy_forward_ex outputs");
+  RGBM_REQUIRE(mode != 0 || noise, "policy_forward_ex: act needs noise");
+  return launch_policy_forward_ex(params, *reinterpret_cast<const PolicyDesc*>(D), n, mode, obs, states, noise, actions, logp, value,
+                                  mu, (hipStream_t)stream);
+}
+int rgbm_ppo_scratch_floats_ex(const rgbm_policy_desc* D, int n, int clipped_value_loss, size_t* count) {
+  RGBM_REQUIRE(D && count && n > 0, "ppo_scratch_floats_ex arguments");
+  return ppo_scratch_floats_ex(*reinterpret_cast<const PolicyDesc*>(D), n, clipped_value_loss, count);
+}
+int rgbm_ppo_minibatch_fwd_bwd_ex(const float* params, const rgbm_policy_desc* D, int n, const float* obs, const float* states,
+                                  const float* actions, const float* old_logp, const float* adv, const float* returns,
+                                  const float* old_values, const float* old_mu, const float* old_sigma, float clip, float vcoef,
+                                  float ecoef, int clipped_value_loss, float* scratch, float* grads_flat, void* stream) {
+  RGBM_REQUIRE(params && D && obs && actions && old_logp && adv && returns && old_mu && old_sigma && scratch && grads_flat,
+               "ppo_minibatch_ex arguments");
+  return launch_ppo_minibatch_ex(params, *reinterpret_cast<const PolicyDesc*>(D), n, obs, states, actions, old_logp, adv, returns,
+                                 old_values, old_mu, old_sigma, clip, vcoef, ecoef, clipped_value_loss, scratch, grads_flat,
+                                 (hipStream_t)stream);
+}
+int rgbm_ppo_clip_adam_ex(float* params, const float* grads_flat, float* exp_avg, float* exp_avg_sq, void* opt_state, int total,
+                          float inv_world, float max_norm, float desired_kl, float lr_min, float lr_max, int adaptive, void* stream) {
+  RGBM_REQUIRE(params && grads_flat && exp_avg && exp_avg_sq && opt_state && total > 0, "ppo_clip_adam_ex arguments");
+  return launch_ppo_adam(params, grads_flat, exp_avg, exp_avg_sq, reinterpret_cast<PolicyOptState*>(opt_state), total, inv_world,
+                         max_norm, desired_kl, lr_min, lr_max, adaptive, (hipStream_t)stream);
+}
 int rgbm_ppo_clip_adam(float* params, const float* grads_flat, float* exp_avg, float* exp_avg_sq, void* opt_state,
                        const rgbm_policy_layout* L, float inv_world, float max_norm, float desired_kl, float lr_min,
                        float lr_max, int adaptive, void* stream) {

@@ -181,6 +181,25 @@ int launch_ppo_minibatch(const float* params, const PolicyLayout& L, int n, cons
                          const float* old_logp, const float* adv, const float* returns, const float* old_values,
                          const float* old_mu, const float* old_sigma, float clip, float vcoef, float ecoef, float* partial,
                          float* grads, hipStream_t s);
+// General descriptor (rgbm_policy_desc in rgbm.h): per-net hidden widths, activation id, optional second input for the critic.
+constexpr int POLICY_MAX_HIDDEN = 6, POLICY_MAX_WIDTH = 512, POLICY_MAX_ACT = 32;
+enum { PACT_ELU = 0, PACT_SELU = 1, PACT_RELU = 2, PACT_LRELU = 3, PACT_TANH = 4, PACT_SIGMOID = 5 };
+struct PolicyDesc {
+  int obs_dim, state_dim, act_dim, activation, asymmetric;
+  int n_hidden[2];
+  int hidden[2][POLICY_MAX_HIDDEN];
+  int w[2][POLICY_MAX_HIDDEN + 1];
+  int b[2][POLICY_MAX_HIDDEN + 1];
+  int log_std, total;
+};
+// These forward to the kernels of the shipped shape when the descriptor is that shape, else run the general kernels.
+int launch_policy_forward_ex(const float* params, const PolicyDesc& D, int n, int mode, const float* obs, const float* states,
+                             const float* noise, float* actions, float* logp, float* value, float* mu, hipStream_t s);
+int ppo_scratch_floats_ex(const PolicyDesc& D, int n, int clipped_vloss, size_t* count);
+int launch_ppo_minibatch_ex(const float* params, const PolicyDesc& D, int n, const float* obs, const float* states,
+                            const float* actions, const float* old_logp, const float* adv, const float* returns,
+                            const float* old_values, const float* old_mu, const float* old_sigma, float clip, float vcoef, float ecoef,
+                            int clipped_vloss, float* scratch, float* grads, hipStream_t s);
 int launch_ppo_adam(float* params, const float* grads, float* m, float* v, PolicyOptState* st, int total, float inv_world,
                     float max_norm, float desired_kl, float lr_min, float lr_max, int adaptive, hipStream_t s);
 

@@ -1,10 +1,11 @@
 """ActorCritic on a flat fp32 parameter vector, evaluated by the HIP policy kernels.
 
 Mirrors `/root/reference/algo/ppo/ppo/module.py:8-107`: same constructor arguments, `act`, `act_inference`,
-`evaluate`, `state_dict` key names (`log_std`, `actor.{0,2,4,6}.{weight,bias}`, `critic.{0,2,4,6}.{weight,bias}`),
-orthogonal initialisation with the reference's gains, and the reference's Gaussian
-(`scale_tril = diag(exp(log_std)**2)`, module.py:76-77).  Sampling noise is drawn from torch's generator
-(`torch.randn`) so RNG stays with the caller; everything else runs in `rgbm_policy_forward`.
+`evaluate`, `state_dict` key names (`log_std`, `actor.{0,2,..}.{weight,bias}`, `critic.{0,2,..}.{weight,bias}`) for any depth,
+every hidden-size list, activation name and the asymmetric critic the reference builds, orthogonal initialisation with the
+reference's gains drawn in its order, and the reference's Gaussian (`scale_tril = diag(exp(log_std)**2)`, module.py:76-77).
+Sampling noise is drawn from torch's generator (`torch.randn`) so RNG stays with the caller; everything else runs in
+`rgbm_policy_forward_ex`.
 """
 from __future__ import annotations
 
@@ -18,52 +19,80 @@ import torch.nn as nn
 from .. import _lib
 
 
+_ACTIVATIONS = {"elu": nn.ELU, "selu": nn.SELU, "relu": nn.ReLU, "crelu": nn.ReLU, "lrelu": nn.LeakyReLU, "tanh": nn.Tanh,
+                "sigmoid": nn.Sigmoid}
+
+
 def get_activation(act_name):
-    if act_name != "elu":
-        raise NotImplementedError(f"the HIP policy kernels implement the shipped cfg's ELU only (got {act_name!r})")
-    return nn.ELU()
+    """The reference's names (module.py:109-126); an unknown one is an error here, not a `None` inside `nn.Sequential`."""
+    if act_name not in _ACTIVATIONS:
+        raise ValueError(f"unknown activation {act_name!r}: expected one of {sorted(_ACTIVATIONS)}")
+    return _ACTIVATIONS[act_name]()
 
 
 class ActorCritic:
     def __init__(self, obs_shape, states_shape, actions_shape, initial_std, model_cfg, asymmetric=False):
-        if asymmetric:
-            raise NotImplementedError("asymmetric critic is not used by cfg/controller/rl.yaml (asymmetric: False)")
-        self.asymmetric = asymmetric
-        if model_cfg is None:
-            raise NotImplementedError("model_cfg=None (256x3 SELU) is not on the shipped path")
-        a_h, c_h = list(model_cfg["pi_hid_sizes"]), list(model_cfg["vf_hid_sizes"])
-        get_activation(model_cfg["activation"])
-        if a_h != c_h or len(a_h) != 3:
-            raise NotImplementedError("actor and critic must share three hidden sizes (cfg/controller/rl.yaml:30-31)")
+        self.asymmetric = bool(asymmetric)
+        if model_cfg is None:      # module.py:15-18
+            a_h, c_h, act_name = [256, 256, 256], [256, 256, 256], "selu"
+        else:
+            a_h, c_h, act_name = list(model_cfg["pi_hid_sizes"]), list(model_cfg["vf_hid_sizes"]), model_cfg["activation"]
+        get_activation(act_name)
+        self.activation = act_name
         self.obs_dim, self.act_dim = int(obs_shape[0]), int(actions_shape[0])
+        self.state_dim = int(states_shape[0]) if self.asymmetric else self.obs_dim
+        a_h, c_h = [int(h) for h in a_h], [int(h) for h in c_h]
+        for name, hid in (("pi_hid_sizes", a_h), ("vf_hid_sizes", c_h)):
+            if not 1 <= len(hid) <= _lib.POLICY_MAX_HIDDEN or not all(1 <= h <= _lib.POLICY_MAX_WIDTH for h in hid):
+                raise ValueError(f"{name}={hid}: the policy kernels take 1..{_lib.POLICY_MAX_HIDDEN} hidden layers of width "
+                                 f"1..{_lib.POLICY_MAX_WIDTH}")
+        if not (1 <= self.obs_dim <= _lib.POLICY_MAX_WIDTH and 1 <= self.state_dim <= _lib.POLICY_MAX_WIDTH
+                and 1 <= self.act_dim <= _lib.POLICY_MAX_ACT):
+            raise ValueError(f"observation / state dim must be in 1..{_lib.POLICY_MAX_WIDTH} and action dim in 1..{_lib.POLICY_MAX_ACT}")
         self.hidden = a_h
-        dims = [self.obs_dim] + a_h
+        self.critic_hidden = c_h
+        a_dims = [self.obs_dim] + a_h + [self.act_dim]
+        c_dims = [self.state_dim if self.asymmetric else self.obs_dim] + c_h + [1]
         # ---- layout of the flat vector = the reference's state_dict order ----
         self.keys = OrderedDict()
         off = 0
         self.keys["log_std"] = (off, (self.act_dim,))
         off += self.act_dim
-        L = _lib.PolicyLayout()
-        for k, d in enumerate(dims + [self.act_dim]):
-            L.dims[k] = d
-        L.log_std = 0
-        for net, name, out_dim in ((0, "actor", self.act_dim), (1, "critic", 1)):
-            for l in range(4):
-                i, o = dims[l], (dims[l + 1] if l < 3 else out_dim)
+        D = _lib.PolicyDesc()
+        D.obs_dim, D.state_dim, D.act_dim = self.obs_dim, self.state_dim, self.act_dim
+        D.activation, D.asymmetric, D.log_std = _lib.POLICY_ACTIVATIONS[act_name], int(self.asymmetric), 0
+        for net, (name, dims) in enumerate((("actor", a_dims), ("critic", c_dims))):
+            D.n_hidden[net] = len(dims) - 2
+            for l in range(len(dims) - 1):
+                i, o = dims[l], dims[l + 1]
+                if l < len(dims) - 2:
+                    D.hidden[net][l] = o
                 self.keys[f"{name}.{2 * l}.weight"] = (off, (o, i))
-                L.w[net][l] = off
+                D.w[net][l] = off
                 off += o * i
                 self.keys[f"{name}.{2 * l}.bias"] = (off, (o,))
-                L.b[net][l] = off
+                D.b[net][l] = off
                 off += o
-        L.total = off
-        self.layout = L
+        D.total = off
+        self.desc = D
         self.total = off
+        # the shipped shape's descriptor, for callers of the four original entry points
+        self.layout = None
+        if a_h == c_h and len(a_h) == 3 and not self.asymmetric:
+            L = _lib.PolicyLayout()
+            for k, d in enumerate(a_dims):
+                L.dims[k] = d
+            L.log_std = 0
+            for net in range(2):
+                for l in range(4):
+                    L.w[net][l], L.b[net][l] = D.w[net][l], D.b[net][l]
+            L.total = off
+            self.layout = L
         # ---- initialisation exactly like the reference: nn.Linear defaults, then orthogonal_ with its gains ----
-        actor = [nn.Linear(dims[l], dims[l + 1] if l < 3 else self.act_dim) for l in range(4)]
-        critic = [nn.Linear(dims[l], dims[l + 1] if l < 3 else 1) for l in range(4)]
+        actor = [nn.Linear(a_dims[l], a_dims[l + 1]) for l in range(len(a_dims) - 1)]
+        critic = [nn.Linear(c_dims[l], c_dims[l + 1]) for l in range(len(c_dims) - 1)]
         log_std = np.log(initial_std) * torch.ones(self.act_dim)
-        for mods, gains in ((actor, [np.sqrt(2)] * 3 + [0.01]), (critic, [np.sqrt(2)] * 3 + [1.0])):
+        for mods, gains in ((actor, [np.sqrt(2)] * len(a_h) + [0.01]), (critic, [np.sqrt(2)] * len(c_h) + [1.0])):
             for m, gain in zip(mods, gains):
                 torch.nn.init.orthogonal_(m.weight, gain=gain)
         flat = torch.zeros(off, dtype=torch.float32)
@@ -118,13 +147,20 @@ class ActorCritic:
         raise NotImplementedError
 
     # ---- the three entry points of module.py:73-107 ----
-    def _run(self, mode, observations, noise=None, actions=None):
+    def _run(self, mode, observations, states=None, noise=None, actions=None):
         if self.flat.device.type != "cuda":
             raise _lib.RgbmError("ActorCritic runs on the HIP policy kernels only: move it to a cuda device (no CPU fallback)")
         lib = _lib.load()
         obs = observations.to(device=self.flat.device, dtype=torch.float32).contiguous()
         n = obs.shape[0]
         dev = self.flat.device
+        st = None
+        if self.asymmetric and mode != 1:
+            if states is None:
+                raise ValueError("an asymmetric ActorCritic needs `states` for act / evaluate")
+            st = states.to(device=dev, dtype=torch.float32).contiguous()
+            if st.shape != (n, self.state_dim):
+                raise ValueError(f"states must be [{n}, {self.state_dim}], got {tuple(st.shape)}")
         mu = torch.empty(n, self.act_dim, device=dev)
         logp = torch.empty(n, device=dev)
         value = torch.empty(n, 1, device=dev)
@@ -132,9 +168,9 @@ class ActorCritic:
             actions = torch.empty(n, self.act_dim, device=dev)
         elif mode == 2:
             actions = actions.to(device=dev, dtype=torch.float32).contiguous()
-        _lib.check(lib.rgbm_policy_forward(_lib.ptr(self.flat), C.byref(self.layout), n, mode, _lib.ptr(obs), _lib.ptr(noise),
-                                           _lib.ptr(actions), _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mu),
-                                           _lib.stream_ptr()), "rgbm_policy_forward")
+        _lib.check(lib.rgbm_policy_forward_ex(_lib.ptr(self.flat), C.byref(self.desc), n, mode, _lib.ptr(obs), _lib.ptr(st),
+                                              _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mu),
+                                              _lib.stream_ptr()), "rgbm_policy_forward_ex")
         return actions, logp, value, mu
 
     def act(self, observations, states, noise=None):
@@ -142,7 +178,7 @@ class ActorCritic:
         if noise is None:
             noise = torch.randn(n, self.act_dim, device=self.flat.device)
         noise = noise.to(device=self.flat.device, dtype=torch.float32).contiguous()
-        actions, logp, value, mu = self._run(0, observations, noise=noise)
+        actions, logp, value, mu = self._run(0, observations, states=states, noise=noise)
         return actions, logp, value, mu, self.log_std.repeat(n, 1).detach()
 
     def act_inference(self, observations):
@@ -150,7 +186,7 @@ class ActorCritic:
 
     def evaluate(self, observations, states, actions, contrastive=False):
         n = observations.shape[0]
-        _, logp, value, mu = self._run(2, observations, actions=actions)
+        _, logp, value, mu = self._run(2, observations, states=states, actions=actions)
         k = self.act_dim
         entropy = (0.5 * k * (1.0 + np.log(2 * np.pi)) + 2.0 * self.log_std.sum()).expand(n)
         return logp, entropy, value, mu, self.log_std.repeat(n, 1), 0

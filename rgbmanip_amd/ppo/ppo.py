@@ -3,8 +3,8 @@
 Same public surface as `/root/reference/algo/ppo/ppo/ppo.py` (`PPO(vec_env, learn_cfg)`, `run`, `update`, `save`, `load`,
 `test`, `eval`, `play`, attributes `.actor_critic`, `.device`, `.storage`, `.step_size`) and the same cfg keys
 (`cfg/controller/rl.yaml`), but the learn phase is four HIP launches per minibatch with no host synchronisation:
-`rgbm_ppo_minibatch_fwd_bwd` (forward + clipped losses + backward + deterministic reduction), an optional RCCL all-reduce
-of the flat gradient when several ranks train one policy, and `rgbm_ppo_clip_adam` (grad-norm clip, KL-adaptive learning
+`rgbm_ppo_minibatch_fwd_bwd_ex` (forward + losses + backward + deterministic reduction), an optional RCCL all-reduce
+of the flat gradient when several ranks train one policy, and `rgbm_ppo_clip_adam_ex` (grad-norm clip, KL-adaptive learning
 rate, Adam) — the reference does ~60 small launches and two `.item()` syncs per minibatch (ppo.py:472-528).
 
 Multi-GPU: one process per GPU, each rank steps its own slice of the environments; minibatch b of a
@@ -82,8 +82,7 @@ class PPO:
         self.gamma, self.lam = lc["gamma"], lc["lam"]
         self.max_grad_norm = lc["max_grad_norm"]
         self.use_clipped_value_loss = lc["use_clipped_value_loss"]
-        if not self.use_clipped_value_loss or self.contrastive:
-            raise NotImplementedError("the HIP update implements the shipped cfg: clipped value loss, no contrastive term")
+        # `contrastive` changes nothing: ActorCritic.evaluate returns 0 for that loss term (module.py:93-107)
         if learn_cfg["policy"]["actor_critic_class"] != "ActorCritic":
             raise NotImplementedError(learn_cfg["policy"]["actor_critic_class"])
         self.process_group = process_group
@@ -309,12 +308,15 @@ class PPO:
         if ac.flat.device.type != "cuda":
             raise _lib.RgbmError("PPO.update runs on the HIP kernels: use a cuda device (no CPU fallback)")
         T, N = st.num_transitions_per_env, st.num_envs
-        flat = {k: getattr(st, k).reshape(T * N, -1) for k in ("observations", "actions", "values", "returns",
-                                                               "actions_log_prob", "advantages", "mu", "sigma")}
+        names = ["observations", "actions", "values", "returns", "actions_log_prob", "advantages", "mu", "sigma"]
+        if self.asymmetric:
+            names.append("states")
+        flat = {k: getattr(st, k).reshape(T * N, -1) for k in names}
         batches = st.mini_batch_generator(self.num_mini_batches)
         mb = len(batches[0])
+        clipped = int(bool(self.use_clipped_value_loss))
         need = C.c_size_t()
-        _lib.check(lib.rgbm_ppo_partial_floats(C.byref(ac.layout), mb, C.byref(need)), "rgbm_ppo_partial_floats")
+        _lib.check(lib.rgbm_ppo_scratch_floats_ex(C.byref(ac.desc), mb, clipped, C.byref(need)), "rgbm_ppo_scratch_floats_ex")
         if self._partial is None or self._partial.numel() < need.value:
             self._partial = torch.empty(need.value, device=ac.flat.device)
         s0 = self._read_opt_state()
@@ -327,17 +329,18 @@ class PPO:
                 else:
                     ii = torch.as_tensor(idx, device=ac.flat.device)
                     sl = {k: v[ii].contiguous() for k, v in flat.items()}
-                _lib.check(lib.rgbm_ppo_minibatch_fwd_bwd(
-                    _lib.ptr(ac.flat), C.byref(ac.layout), mb, _lib.ptr(sl["observations"]), _lib.ptr(sl["actions"]),
-                    _lib.ptr(sl["actions_log_prob"]), _lib.ptr(sl["advantages"]), _lib.ptr(sl["returns"]), _lib.ptr(sl["values"]),
-                    _lib.ptr(sl["mu"]), _lib.ptr(sl["sigma"]), float(self.clip_param), float(self.value_loss_coef),
-                    float(self.entropy_coef), _lib.ptr(self._partial), _lib.ptr(self._grads), stream), "rgbm_ppo_minibatch_fwd_bwd")
+                _lib.check(lib.rgbm_ppo_minibatch_fwd_bwd_ex(
+                    _lib.ptr(ac.flat), C.byref(ac.desc), mb, _lib.ptr(sl["observations"]), _lib.ptr(sl.get("states")),
+                    _lib.ptr(sl["actions"]), _lib.ptr(sl["actions_log_prob"]), _lib.ptr(sl["advantages"]), _lib.ptr(sl["returns"]),
+                    _lib.ptr(sl["values"]), _lib.ptr(sl["mu"]), _lib.ptr(sl["sigma"]), float(self.clip_param),
+                    float(self.value_loss_coef), float(self.entropy_coef), clipped, _lib.ptr(self._partial), _lib.ptr(self._grads),
+                    stream), "rgbm_ppo_minibatch_fwd_bwd_ex")
                 # sum over ranks of (gradient of the local minibatch mean | loss / KL sums); the optimiser applies 1/world
                 inv_world = dist_utils.average_flat_gradient(self._grads, self.process_group)
-                _lib.check(lib.rgbm_ppo_clip_adam(
+                _lib.check(lib.rgbm_ppo_clip_adam_ex(
                     _lib.ptr(ac.flat), _lib.ptr(self._grads), _lib.ptr(self._exp_avg), _lib.ptr(self._exp_avg_sq),
-                    _lib.ptr(self._opt_state), C.byref(ac.layout), inv_world, float(self.max_grad_norm),
-                    float(self.desired_kl or 0.0), self.lr_lower, self.lr_upper, adaptive, stream), "rgbm_ppo_clip_adam")
+                    _lib.ptr(self._opt_state), ac.total, inv_world, float(self.max_grad_norm),
+                    float(self.desired_kl or 0.0), self.lr_lower, self.lr_upper, adaptive, stream), "rgbm_ppo_clip_adam_ex")
         s1 = self._read_opt_state()            # the only host sync of the learn phase
         n_up = max(s1["n_updates"] - s0["n_updates"], 1)
         self.step_size = s1["lr"]

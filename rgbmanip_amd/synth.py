@@ -241,6 +241,40 @@ def policy_state_dict(seed: int = 0, obs=60, act=12, hid=(96, 96, 32), init_std=
     return sd
 
 
+# the ActorCritic variants of tests/golden/ppo_variants.npz (tools/make_goldens.py::gen_ppo_variants): name -> (model_cfg or
+# None for the class default, asymmetric, use_clipped_value_loss); observation 60, state 75, action 12 throughout
+PPO_VARIANTS = OrderedDict([
+    ("default", (None, False, True)),
+    ("asym_tanh", (dict(pi_hid_sizes=[128, 64], vf_hid_sizes=[256, 128, 64, 32], activation="tanh"), True, True)),
+    ("lrelu64_mse", (dict(pi_hid_sizes=[64], vf_hid_sizes=[64], activation="lrelu"), False, False)),
+    ("relu", (dict(pi_hid_sizes=[96, 96, 32], vf_hid_sizes=[96, 96, 32], activation="relu"), False, True)),
+    ("sigmoid", (dict(pi_hid_sizes=[96, 96, 32], vf_hid_sizes=[96, 96, 32], activation="sigmoid"), False, True)),
+    ("selu", (dict(pi_hid_sizes=[96, 96, 32], vf_hid_sizes=[96, 96, 32], activation="selu"), False, True)),
+    ("awkward", (dict(pi_hid_sizes=[33, 7, 130], vf_hid_sizes=[5], activation="elu"), False, True)),
+])
+
+
+def policy_variant_state_dict(name: str, seed: int = 0, obs=60, states=75, act=12, init_std=0.6):
+    """Seeded state_dict of one of PPO_VARIANTS in the reference's key order: scaled orthogonal weights with the reference's
+    gains, uniform biases (as `policy_state_dict` builds the shipped shape)."""
+    cfg, asym, _ = PPO_VARIANTS[name]
+    pi, vf = ([256] * 3, [256] * 3) if cfg is None else (cfg["pi_hid_sizes"], cfg["vf_hid_sizes"])
+    sd = OrderedDict()
+    sd["log_std"] = np.full((act,), np.log(init_std), dtype=np.float32)
+    for net, in_dim, hid, out_dim, last in (("actor", obs, pi, act, 0.01), ("critic", states if asym else obs, vf, 1, 1.0)):
+        dims = (in_dim,) + tuple(hid) + (out_dim,)
+        gains = [np.sqrt(2)] * len(hid) + [last]
+        for li, (a, b) in enumerate(zip(dims[:-1], dims[1:])):
+            g = _rng(f"variant.{name}.{net}.{2 * li}", seed)
+            q, r = np.linalg.qr(g.normal(size=(max(a, b), min(a, b))))
+            q = q * np.sign(np.diag(r))[None]
+            w = q if b >= a else q.T
+            sd[f"{net}.{2 * li}.weight"] = np.ascontiguousarray(gains[li] * w[:b, :a], dtype=np.float32)
+            bound = 1.0 / np.sqrt(a)
+            sd[f"{net}.{2 * li}.bias"] = g.uniform(-bound, bound, size=(b,)).astype(np.float32)
+    return sd
+
+
 def ppo_rollout(T: int, N: int, seed: int = 0, obs=60, states=75, act=12):
     """A recorded rollout with plausible statistics (rewards ~ reference reward scale)."""
     g = np.random.default_rng(777 + seed)

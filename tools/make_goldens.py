@@ -8,6 +8,7 @@ stub torchvision/cv2/ipdb/gym/sapien/tensorboard, make Tensor.cuda the identity
 
 Inputs and weights come from rgbmanip_amd.synth (seeded; regenerated identically by tests).
 """
+import copy
 import os
 import sys
 import types
@@ -385,6 +386,76 @@ def gen_ppo(out_dir):
     np.savez_compressed(os.path.join(out_dir, "ppo.npz"), **save)
 
 
+def gen_ppo_variants(out_dir):
+    """The reference's `ActorCritic` / `PPO` for every variant of rgbmanip_amd.synth.PPO_VARIANTS (hidden-size lists, activations,
+    asymmetric critic, plain-MSE value loss): state_dict keys and shapes, a strided slice of the seeded initialisation, `act` with
+    a recorded noise draw, `evaluate`, and one `PPO.update` at N = 32 filled as gen_ppo fills it.  Parameters after the update are
+    stored as a strided slice of 2048 (the 256-wide default has 300 k of them)."""
+    from algo.ppo.ppo import PPO
+    from rgbmanip_amd import synth
+
+    base = yaml.safe_load(open(os.path.join(REF, "cfg/controller/rl.yaml")))
+    base["learn"].update(device="cpu", log_dir="/tmp/rgbm_gold_logs", save_dir="/tmp/rgbm_gold_saves")
+    N, save = 32, {}
+    T = base["learn"]["num_transitions_per_env"]
+    roll = synth.ppo_rollout(T, N, seed=0)
+    tr = {k: torch.from_numpy(v) for k, v in roll.items()}
+
+    class FakeEnv:
+        num_envs = N
+        observation_space = _Box(-1.5, 1.5, (60,))
+        state_space = _Box(-1.5, 1.5, (75,))
+        action_space = _Box(-1.5, 1.5, (12,))
+    for name, (mcfg, asym, clipped) in synth.PPO_VARIANTS.items():
+        cfg = copy.deepcopy(base)
+        cfg["learn"].update(asymmetric=asym, use_clipped_value_loss=clipped)
+        cfg["policy"] = dict(actor_critic_class="ActorCritic", **mcfg) if mcfg is not None else None
+        if mcfg is None:      # PPO reads policy["actor_critic_class"] and hands the same dict to ActorCritic: None only directly
+            cfg["policy"] = dict(actor_critic_class="ActorCritic", pi_hid_sizes=[256] * 3, vf_hid_sizes=[256] * 3, activation="selu")
+            from algo.ppo.ppo import ActorCritic
+            torch.manual_seed(1234)
+            direct = ActorCritic((60,), (75,), (12,), 0.6, None, asymmetric=False)
+        torch.manual_seed(1234)
+        ppo = PPO(FakeEnv(), cfg)
+        ac = ppo.actor_critic
+        sd0 = ac.state_dict()
+        if mcfg is None:      # the class default builds what the explicit 256x3 SELU cfg builds
+            assert list(direct.state_dict().keys()) == list(sd0.keys())
+            assert all(torch.equal(a, b) for a, b in zip(direct.state_dict().values(), sd0.values()))
+        tag = name + "_"
+        save[tag + "keys"] = np.array(list(sd0.keys()))
+        save[tag + "shapes"] = np.array([list(v.shape) + [0] * (2 - v.dim()) for v in sd0.values()], dtype=np.int64)
+        save[tag + "init_slice"] = strided(torch.cat([v.reshape(-1) for v in sd0.values()]), 256)
+        sd = synth.policy_variant_state_dict(name, seed=0)
+        ac.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+        torch.manual_seed(123)
+        a, logp, v, mu, sig = ac.act(tr["observations"][0], tr["states"][0])
+        torch.manual_seed(123)
+        eps = torch.randn(N, 12)
+        recon = mu + torch.exp(2 * ac.log_std.detach()) * eps
+        assert (recon - a).abs().max().item() < 1e-6
+        save.update({tag + "act_eps": eps.numpy(), tag + "act_a": a.numpy(), tag + "act_logp": logp.numpy(),
+                     tag + "act_v": v.numpy(), tag + "act_mu": mu.numpy()})
+        with torch.no_grad():
+            for t in range(T):
+                lp, ent, vv, mm, ss, _ = ac.evaluate(tr["observations"][t], tr["states"][t], tr["actions"][t])
+                mm = mm + 0.02 * torch.sin(torch.arange(12.0))[None]
+                ppo.storage.add_transitions(tr["observations"][t], tr["states"][t], tr["actions"][t],
+                                            tr["rewards"][t].view(-1), tr["dones"][t].view(-1), tr["values"][t],
+                                            lp - 0.01, mm, ss - 0.005)
+                if t == 0:
+                    save.update({tag + "eval_logp": lp.numpy(), tag + "eval_ent": ent.numpy(), tag + "eval_v": vv.numpy()})
+        ppo.storage.compute_returns(tr["last_values"], cfg["learn"]["gamma"], cfg["learn"]["lam"])
+        mvl, msl = ppo.update(0)
+        flat = torch.cat([p.detach().reshape(-1) for p in ac.state_dict().values()])
+        print(f"{name}: {flat.numel()} parameters; update: value_loss {mvl:.6f} surrogate {msl:.6f} lr {ppo.step_size}")
+        save[tag + "params_after_slice"] = strided(flat, 2048)
+        save[tag + "mvl"] = np.array(mvl)
+        save[tag + "msl"] = np.array(msl)
+        save[tag + "lr_after"] = np.array(ppo.step_size)
+    np.savez_compressed(os.path.join(out_dir, "ppo_variants.npz"), **save)
+
+
 def gen_ppo_run(out_dir):
     """`PPO.run` of the reference (ppo.py:203-312, log: 356-447) for two learning iterations on rgbmanip_amd.synth.StubVecEnv:
     the class as shipped, a recording SummaryWriter, the policy noise reproduced from the seed.  Saved: the noise draws, every
@@ -738,7 +809,7 @@ if __name__ == "__main__":
     os.makedirs(out_dir, exist_ok=True)
     torch.set_num_threads(8)
     which = sys.argv[1:] or ["adapose", "adapose_trainbn", "postproc", "ppo", "ppo_run", "control", "control_step", "control_save", "align",
-                             "adapose_dropout"]
+                             "ppo_variants", "adapose_dropout"]
     if "adapose_trainbn" in which:
         gen_adapose_trainbn(out_dir)
     net_out = inp = None
@@ -750,6 +821,8 @@ if __name__ == "__main__":
         gen_ppo(out_dir)
     if "ppo_run" in which:
         gen_ppo_run(out_dir)
+    if "ppo_variants" in which:
+        gen_ppo_variants(out_dir)
     if "control" in which:
         gen_control(out_dir)
     if "control_step" in which:
