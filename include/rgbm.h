@@ -345,6 +345,19 @@ int rgbm_conv_nd(int dtype, const void* in_dev, int N, int D, int H, int W, int 
                  int Cout, int Cout_pad, int KD, int KH, int KW, int stride_d, int stride_hw, int pad_d, int pad_hw,
                  int dil_hw, int transposed, const float* bias_host, const float* bn_scale_host, const float* bn_shift_host,
                  const void* res_dev, int res_mode, int act, float slope, void* out_dev, void* stream);
+/* What rgbm_conv_nd would launch for this geometry (same arguments; has_bias / res_mode say whether there is a bias / residual buffer),
+ * without launching anything: buffers are taken as 16-byte aligned, debug flags and tuning are the process's current ones.  cls: sub-pixel
+ * class 0..7 of a transposed conv (one launch each), else 0.  n_cu: compute units to plan for; 0 = the current device's, any positive value
+ * is taken as given and the HIP runtime is not touched (works without a GPU).  plan[RGBM_CONV_PLAN_INTS]:
+ *   [0] kernel: 0 generic tile, 1 v3, 2 ws 128 x 256, 3 ws wide 256 x 128, 4 ws slim 64 x 256, 5 ws64, 6 ws64 row halo,
+ *       7 m32 main + tail launch (256-multiple channels), 8 m32 small launch (one launch of 128-pixel tiles that does not fill the grid)
+ *   [1] [2] tile channels x pixels (kernel 7: of the main launch)      [3] K parts the launch asks for (1 = no split)
+ *   [4] kernel 7: GEMM rows on 256 x 256 tiles      [5] kernel 7: channel tile of the 128-pixel tail launch (0 = none)
+ *   [6] 1 = residual added through identity K steps, 0 = in the epilogue (or none)      [7] GEMM rows M      [8] K tiles KT */
+#define RGBM_CONV_PLAN_INTS 9
+int rgbm_conv_plan(int dtype, int N, int D, int H, int W, int Cin, int Cin_pad, int Cout, int Cout_pad, int KD, int KH, int KW,
+                   int stride_d, int stride_hw, int pad_d, int pad_hw, int dil_hw, int transposed, int has_bias, int res_mode, int act,
+                   int cls, int n_cu, int32_t* plan);
 /* Per-sample BatchNorm3d of the as-shipped mode (norm_mode = 1), in place: y_dev [V][nvox][C] (C % 4 == 0, C <= 64) in `dtype`
  * -> relu(gamma * (y - mean_v) / sqrt(var_v + 1e-5) + beta) + res, with the biased mean / variance of each view v's own volume;
  * relu 0 skips the ReLU, res_dev may be null (post-activation skip add otherwise, same layout).  gamma_dev / beta_dev [C] fp32;

@@ -290,21 +290,21 @@ void AdaPose::destroy() {
 }
 
 bool AdaPose::feat_f32_only() const {
-  return dtype == BF16X3 && cost_impl == 3 && sweep_w != nullptr && norm_mode == 0 && !(g_debug_flags & 4096);
+  return dtype == BF16X3 && cost_impl == 3 && sweep_w != nullptr && norm_mode == 0 && !(g_debug_flags & DBG_TILE_CONV0);
 }
 
 // bf16 nets: what `final` writes and what the plane sweep and the point heads read is f16 - same bytes, three more mantissa bits, and the
 // sweep's blend becomes four v_pk_fma_f16 per dword.  Needs the one-kernel up_3 + final (its epilogue knows the f16 form) and the
 // depth-sweeping conv0 (the halo-tile / volume paths read the storage type).
 bool AdaPose::feat_f16() const {
-  return dtype == BF16 && sweep_f16 != 0 && cost_impl == 3 && sweep_w_f16 != nullptr && norm_mode == 0 && !(g_debug_flags & 4096) && (upconv & 4) &&
+  return dtype == BF16 && sweep_f16 != 0 && cost_impl == 3 && sweep_w_f16 != nullptr && norm_mode == 0 && !(g_debug_flags & DBG_TILE_CONV0) && (upconv & 4) &&
          tail.ready() && tail.f16_ready();
 }
 
 bool AdaPose::sparse_active() const {
   const bool b16 = dtype_size(dtype) == 2;
   return sparse_dec != 0 && norm_mode == 0 && cost_impl == 3 && (b16 || (dtype == BF16X3 && w11_x3)) && sparse_tail && sweep_w != nullptr &&
-         !(g_debug_flags & 4096);
+         !(g_debug_flags & DBG_TILE_CONV0);
 }
 
 int AdaPose::chunk_views(int V) const {
@@ -429,7 +429,7 @@ int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* im
   const void* f = bf.lb[xi];                    // [V][H][W][512], H = W = S/8
   last_f_index = xi;
   RGBM_REQUIRE(H == S / 8 && W == S / 8, "feature stride");
-  if (g_debug_flags & 1024) {      // the PSP stage as rounds 1-5 ran it: copy, pooling, four GEMM launches, four resizes
+  if (g_debug_flags & DBG_PSP_STAGE_R5) {      // the PSP stage as rounds 1-5 ran it: copy, pooling, four GEMM launches, four resizes
     if (int rc = launch_copy_channels(dtype, f, bf.cat, (long long)V * H * W, 512, 1024, 0, s)) return rc;
     {
       void* outs[4] = {bf.pooled[0], bf.pooled[1], bf.pooled[2], bf.pooled[3]};
@@ -517,12 +517,12 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, h
                     (double)Vc * Do * Ho * Wo * t3d[li].Cout * (res ? 2 : 1)) * (double)dtype_size(dtype);
     // debug flag 4096: the halo-tile conv0 instead of either depth-sweeping kernel, in every storage type (the runtime way out
     // should a compiler update bring the sweep kernels' hand-counted asm gathers out of step)
-    if (layer == 10 && cost_impl == 3 && b16 && sweep_w && !(g_debug_flags & 4096)) {
+    if (layer == 10 && cost_impl == 3 && b16 && sweep_w && !(g_debug_flags & DBG_TILE_CONV0)) {
       d.wgt = sweep_w;
       if (feat_f16()) { d.wgt = sweep_w_f16; d.feat_f16 = 1; }
       return launch_conv0_sweep(d, dtype, s);
     }
-    if (layer == 10 && cost_impl == 3 && dtype == BF16X3 && sweep_w && !(g_debug_flags & 4096)) {
+    if (layer == 10 && cost_impl == 3 && dtype == BF16X3 && sweep_w && !(g_debug_flags & DBG_TILE_CONV0)) {
       d.wgt = sweep_w;
       d.feat = bf.featf;
       return launch_conv0_sweep_x3(d, s);
@@ -664,7 +664,7 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
 
   const int Vh = view2_heads ? V : B;      // views that get heads: both crops of every pose, or the view-1 crops only (option view2_heads)
   // ---- per-point NOCS branch (network_v5.py:432-444) ----
-  if (pmlp_table != nullptr && !(g_debug_flags & 2048) && ((long long)Vh * P) % 64 == 0) {
+  if (pmlp_table != nullptr && !(g_debug_flags & DBG_POINT_MLP_R5) && ((long long)Vh * P) % 64 == 0) {
     // gather + the six layers in one launch (head_kernels.hip): a wave carries 16 points through the whole branch, weights and activations in LDS
     PointMlpDesc pd{};
     pd.table = pmlp_table; pd.feat = featg; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = P; pd.HW = S * S;

@@ -10,6 +10,7 @@
 
 #include "adapose.h"
 #include "control.h"
+#include "conv_plan.h"
 #include "prof.h"
 
 using namespace rgbm;
@@ -338,21 +339,50 @@ int rgbm_adv_normalise(int64_t n_local, float* adv, const double* sums, double c
   return launch_adv_normalise(n_local, adv, sums, count_total, (hipStream_t)stream);
 }
 
+static ConvGeom conv_nd_geom(int Cin, int Cout, int KD, int KH, int KW, int stride_d, int stride_hw, int pad_d, int pad_hw, int dil_hw,
+                             int transposed, int act, float slope) {
+  ConvGeom g;
+  g.Cin = Cin; g.Cout = Cout; g.KD = KD; g.KH = KH; g.KW = KW;
+  g.sd = stride_d; g.sh = g.sw = stride_hw; g.pd = pad_d; g.ph = g.pw = pad_hw;
+  g.dild = 1; g.dilh = g.dilw = dil_hw; g.transposed = transposed != 0; g.act = act; g.slope = slope;
+  return g;
+}
+
 int rgbm_conv_nd(int dtype, const void* in_dev, int N, int D, int H, int W, int Cin, int Cin_pad, const float* w_host,
                  int Cout, int Cout_pad, int KD, int KH, int KW, int stride_d, int stride_hw, int pad_d, int pad_hw,
                  int dil_hw, int transposed, const float* bias_host, const float* bn_scale_host, const float* bn_shift_host,
                  const void* res_dev, int res_mode, int act, float slope, void* out_dev, void* stream) {
   RGBM_REQUIRE(in_dev && w_host && out_dev, "conv arguments");
-  ConvGeom g;
-  g.Cin = Cin; g.Cout = Cout; g.KD = KD; g.KH = KH; g.KW = KW;
-  g.sd = stride_d; g.sh = g.sw = stride_hw; g.pd = pad_d; g.ph = g.pw = pad_hw;
-  g.dild = 1; g.dilh = g.dilw = dil_hw; g.transposed = transposed != 0; g.act = act; g.slope = slope;
+  const ConvGeom g = conv_nd_geom(Cin, Cout, KD, KH, KW, stride_d, stride_hw, pad_d, pad_hw, dil_hw, transposed, act, slope);
   ConvLayer L;
   int rc = L.init(dtype, g, w_host, bias_host, bn_scale_host, bn_shift_host, Cin_pad, Cout_pad);
   if (!rc) rc = L.run(in_dev, out_dev, N, D, H, W, Cout_pad, res_dev, res_mode, nullptr, 0, (hipStream_t)stream);
   if (!rc) { hipError_t e = hipStreamSynchronize((hipStream_t)stream); if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = -2; } }
   L.destroy();
   return rc;
+}
+
+int rgbm_conv_plan(int dtype, int N, int D, int H, int W, int Cin, int Cin_pad, int Cout, int Cout_pad, int KD, int KH, int KW,
+                   int stride_d, int stride_hw, int pad_d, int pad_hw, int dil_hw, int transposed, int has_bias, int res_mode, int act,
+                   int cls, int n_cu, int32_t* plan) {
+  RGBM_REQUIRE(plan && n_cu >= 0 && dtype >= F32 && dtype <= BF16X3 && N > 0 && D > 0 && H > 0 && W > 0, "conv_plan arguments");
+  const ConvGeom g = conv_nd_geom(Cin, Cout, KD, KH, KW, stride_d, stride_hw, pad_d, pad_hw, dil_hw, transposed, act, 0.f);
+  PackedConv pc;
+  if (int rc = conv_pack_geom(g, dtype, Cin_pad, Cout_pad, cls, &pc)) return rc;
+  ConvDesc d;
+  conv_desc_geom(d, g, pc, Cin_pad, Cout_pad, N, D, H, W, Cout_pad, cls);
+  alignas(16) static const float buffer[4] = {};      // stands for every device buffer: never read, 16-byte aligned as rgbm_conv_nd's callers' are
+  d.in = d.wgt = buffer; d.out = const_cast<float*>(buffer);
+  d.bias = has_bias ? buffer : nullptr;
+  d.res = res_mode != RES_NONE ? buffer : nullptr;
+  d.res_mode = res_mode;
+  ConvTuning t;
+  ConvPlan p;
+  if (int rc = conv_tuning(n_cu, &t)) return rc;
+  if (int rc = plan_conv(d, dtype, t, &p)) return rc;
+  const int32_t v[RGBM_CONV_PLAN_INTS] = {p.kernel, p.bch, p.bpix, p.ksplit, (int32_t)p.main_rows, p.tail_bch, p.identity_residual, (int32_t)d.M, d.KT};
+  memcpy(plan, v, sizeof(v));
+  return 0;
 }
 
 int rgbm_upsample_conv3x3(int dtype, const void* in_dev, int V, int h, int w, int Cin, const float* w_host, int Cout,

@@ -1009,8 +1009,8 @@ int launch_conv0_sweep(const Conv3dTileDesc& t, int dtype, hipStream_t s) {
   // (sweep 15.3 -> 14.6 ms dense).  bf16 feature maps (option sweep_f16 = 0): the plain fp32 blend (mode 0; on the library
   // without packed fp32 instructions the three bf16 modes are level - 44.11 / 44.15 / 44.09 ms per forward - and the dot2 form rounds the
   // bilinear weights to 8 bits); debug flag 4194304 = v_perm + v_dot2_f32_bf16 (the round-4 default), 2097152 = fp32 FMAs from inline asm.
-  const bool f21 = (g_debug_flags & (1 << 21)) != 0, f22 = (g_debug_flags & (1 << 22)) != 0;
-  if (((dtype == BF16 && t.feat_f16) || dtype == F16) && !(g_debug_flags & (1 << 28))) {
+  const bool f21 = (g_debug_flags & DBG_SWEEP_ALT_BLEND) != 0, f22 = (g_debug_flags & DBG_SWEEP_DOT2) != 0;
+  if (((dtype == BF16 && t.feat_f16) || dtype == F16) && !(g_debug_flags & DBG_SWEEP_PER_TILE)) {
     // the persistent form (debug flag 268435456 = one workgroup per tile, for A/B); fp16 nets (round 6): with their fp32-accumulating blend,
     // debug flag 2097152 = the packed blend for them too
     auto kern = dtype == BF16 ? conv0_sweep_persistent_kernel<u16, false> : f21 ? conv0_sweep_persistent_kernel<f16_t, false>

@@ -23,10 +23,6 @@
 
 namespace rgbm {
 
-extern int g_debug_flags;
-int launch_conv_glds(const ConvDesc& d, int dtype, hipStream_t s);
-
-
 int conv_ch_tile(int Cout) {
   if (Cout <= 16) return 16;
   if (Cout <= 32) return 32;
@@ -35,19 +31,5 @@ int conv_ch_tile(int Cout) {
 }
 int conv_bk(int dtype) { return 8 * dtype_chunk(dtype); }      // 128 bytes per row
 
-
-int launch_conv(const ConvDesc& d, int dtype, hipStream_t s) {
-  RGBM_REQUIRE(d.M > 0 && d.M < (1ll << 31), "conv M out of range");
-  RGBM_REQUIRE(d.Cout % 4 == 0 && d.ldo % 4 == 0, "conv Cout/ldo must be multiples of 4");
-  RGBM_REQUIRE(d.KT > 0 && d.Kpad == d.KT * conv_bk(dtype), "conv K padding mismatch");
-  const int E = dtype_chunk(dtype);
-  RGBM_REQUIRE(d.Cin % E == 0, "conv Cin must be a multiple of the 16-byte chunk");
-  if (d.lcin >= 0) {
-    RGBM_REQUIRE((1 << d.lcin) == d.Cin, "conv lcin mismatch");
-  } else {
-    RGBM_REQUIRE(d.ntaps == 1, "linear-K mode needs a single tap");
-  }
-  return launch_conv_glds(d, dtype, s);      // the LDS-DMA kernels (conv_igemm_glds.hip)
-}
 
 }  // namespace rgbm

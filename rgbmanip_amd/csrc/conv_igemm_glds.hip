@@ -9,6 +9,8 @@
 #include <type_traits>
 #include <vector>
 #include "common.h"
+#include "conv_plan.h"
+#include "kernels.h"
 #include "prof.h"
 
 #ifndef WS_BUF
@@ -17,8 +19,6 @@
 
 namespace rgbm {
 
-extern int g_debug_flags;
-extern long long g_ws_min_rows;
 // kernel of the 256-channel x 128-pixel launches (layer3 / layer4 / up_1), rgbm_set_tuning("gemm_kernel"): 0 = conv_igemm_ws_kernel
 // (16x16x32 MFMAs, 8 multiply waves, 256 x 128 tile), 1 = conv_igemm_m32_kernel<256 x 128>, 2 = conv_igemm_m32_kernel<256 x 256> (default)
 int g_gemm_kernel = 2;
@@ -1327,15 +1327,8 @@ static void make_fastdiv(int dvs, unsigned& m, int& sh) {
   m = (unsigned)(((1ull << sh) + (unsigned long long)dvs - 1ull) / (unsigned long long)dvs);
 }
 
-// both operands addressable with 32-bit byte offsets from one buffer descriptor each (the request waves' blds16 form)
-static bool conv_buffer_offsets_ok(const ConvDesc& d, int bch, size_t esz) {
-  const long long xbytes = ((long long)d.N * d.Di * d.Hi * d.Wi + (long long)(d.pd * d.Hi + d.ph) * d.Wi + d.pw) * d.Cin * (long long)esz;
-  const long long wbytes = (long long)((d.Cout + bch - 1) / bch) * bch * d.Kpad * (long long)esz;
-  return xbytes < (1ll << 32) - 65536 && wbytes < (1ll << 32) - 65536 && d.pd >= 0 && d.ph >= 0 && d.pw >= 0;
-}
-
 template <typename T, bool WIDE, bool RH, bool SLIM = false>
-static int launch_ws(ConvDesc d, hipStream_t s) {
+static int launch_ws(ConvDesc d, const ConvPlan& p, hipStream_t s) {
   constexpr int BCH = SLIM ? 64 : WIDE ? 256 : 128, BPIX = (WIDE && !SLIM) ? 128 : 256;
   constexpr size_t LDS = (RH ? (3 * (size_t)(BCH + 136) * 8 + 8) : 3 * (size_t)(BCH + BPIX) * 8) * sizeof(uint4) + 2048 * sizeof(float);      // K-tile ring(s) + per-channel bias table
   d.n_pix_tiles = (int)((d.M + BPIX - 1) / BPIX);
@@ -1346,8 +1339,8 @@ static int launch_ws(ConvDesc d, hipStream_t s) {
   make_fastdiv(d.Wq, d.fd_m[0], d.fd_s[0]);
   make_fastdiv(d.Hq, d.fd_m[1], d.fd_s[1]);
   make_fastdiv(d.Dq, d.fd_m[2], d.fd_s[2]);
-  d.korder = (g_debug_flags & (1 << 20)) ? 0 : 1;          // debug flag 1048576: taps outer, channels inner (the order before round 3) for A/B
-  d.buf_ok = conv_buffer_offsets_ok(d, BCH, sizeof(T)) && !(g_debug_flags & (1 << 27));      // debug flag 134217728: 64-bit global addresses + zero page (A/B)
+  d.korder = p.korder;
+  d.buf_ok = p.buf_ok;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_igemm_ws_kernel<T, WIDE, RH, SLIM>), (int)LDS)) return rc;
   int n_cu = 0;
   if (int rc = persistent_grid_cus(&n_cu)) return rc;
@@ -1821,17 +1814,9 @@ __global__ __launch_bounds__(768) void conv_igemm_ws64_kernel(const ConvDesc d) 
   RGBM_BARRIER();
 }
 
-// row-halo variant of the 64-channel kernel: 2-D 3x3, stride 1, "same" padding, Cin a multiple of 64
-static bool conv_rowhalo_ok(const ConvDesc& d) {
-  return d.KD == 1 && d.KH == 3 && d.KW == 3 && d.sd == 1 && d.sh == 1 && d.sw == 1 && d.Dq == 1 && d.Di == 1 &&
-         d.dilh == d.dilw && d.dilw >= 1 && d.dilw <= 4 && d.ph == d.dilh && d.pw == d.dilw && d.pd == 0 &&
-         d.lcin >= 6 && d.Hq == d.Hi && d.Wq == d.Wi && d.Wi > 2 * d.dilw && d.osh == 1 && d.osw == 1 && !(g_debug_flags & 256);
-}
-
 template <typename T>
-static int launch_ws64(ConvDesc d, hipStream_t s) {
+static int launch_ws64(ConvDesc d, bool rh, hipStream_t s) {
   constexpr int BCH = 64, BPIX = 256;
-  const bool rh = conv_rowhalo_ok(d);
   const size_t LDS = (rh ? 2 * (size_t)(3 * BCH + 264) * 8 * sizeof(uint4) + 128 + (size_t)BPIX * 144
                          : 3 * (size_t)(BCH + BPIX) * 8 * sizeof(uint4) + (size_t)BPIX * 144) + BCH * sizeof(float);   // + bias table
   d.n_pix_tiles = (int)((d.M + BPIX - 1) / BPIX);
@@ -1851,20 +1836,6 @@ static int launch_ws64(ConvDesc d, hipStream_t s) {
   prof_end_launch(s);
   RGBM_CHECK_HIP(hipGetLastError());
   return 0;
-}
-
-// GEMM rows (output pixels) from which the persistent role-specialised kernels replace the generic tiles.  Rounds 1-3 used 65 536
-// (one 256-pixel tile per CU).  Round 4, forward + post-processing latency at small batches on one box: with the 64 x 256 tile taken
-// for launches that fit one round of the grid (launch_dtype_g) the persistent kernels win from ~1000 rows on in every 16-bit and
-// split-pair case — bf16 B = 1 (1568 rows in layer3) 1.86 -> 1.54 ms, B = 8 2.65 -> 2.43 ms; split pairs B = 1 3.35 -> 2.51 ms, B = 2
-// 3.56 -> 2.83, B = 4 4.02 -> 3.36, B = 8 5.18 -> 4.62 ms — and fp32 does not care (7.1 / 8.3 / 11.0 / 17.6 ms either way).
-static long long ws_min_rows(size_t /*elem_bytes*/) { return g_ws_min_rows > 0 ? g_ws_min_rows : 1024; }
-
-// every K tile inside one tap (see the UNI comment at the 2-stage kernel)
-static bool conv_uniform_taps(const ConvDesc& d, int bk) {
-  if (d.KD > 8 || d.KH > 8 || d.KW > 8) return false;
-  if (d.lcin < 0) return d.ntaps == 1;
-  return d.Cin % bk == 0;
 }
 
 template <typename T, bool UNI>
@@ -1896,94 +1867,61 @@ static int launch_one_g(ConvDesc d, hipStream_t s) {
   return 0;
 }
 
-template <typename T, bool UNI>
-static int launch_t_g(const ConvDesc& d, hipStream_t s) {
-  switch (conv_ch_tile(d.Cout)) {
-    case 16: return launch_one_g<T, 16, 256, UNI>(d, s);
-    case 32: return launch_one_g<T, 32, 256, UNI>(d, s);
-    case 64: return launch_one_g<T, 64, 256, UNI>(d, s);
-    default: return launch_one_g<T, 128, 128, UNI>(d, s);
-  }
+// process-wide settings of the decision (rgbm_debug_flags, rgbm_set_tuning) and the current device's persistent grid; n_cu > 0: plan for
+// that many CUs instead (no HIP runtime call)
+int conv_tuning(int n_cu, ConvTuning* t) {
+  *t = ConvTuning{g_debug_flags, g_gemm_kernel, g_ws_min_rows, n_cu};
+  return n_cu > 0 ? 0 : persistent_grid_cus(&t->n_cu);
 }
 
+// (the cases stand in the order in which the kernels have always been named here: the code object keeps its layout)
 template <typename T>
-static int launch_dtype_g(const ConvDesc& d, hipStream_t s) {
-  const bool uni = conv_uniform_taps(d, 8 * (16 / (int)sizeof(T))) && !(g_debug_flags & 16);
-  if (d.out_f32) {      // only the generic tile's epilogue knows the plain-fp32 output form
-    RGBM_REQUIRE((std::is_same<T, bx3_t>::value) && d.w2 == nullptr, "out_f32 is a bf16x3 option of the generic kernel");
-    return uni ? launch_t_g<T, true>(d, s) : launch_t_g<T, false>(d, s);
-  }
-  // >= 128 output channels and enough pixel tiles to fill the chip: the 256x128 three-stage kernel
-  if (conv_ch_tile(d.Cout) == 128 && !(g_debug_flags & 8) && d.M >= ws_min_rows(sizeof(T))) {
-    // role-specialised (uniform taps, 16-byte aligned output / residual rows)
-    const unsigned long long al = (unsigned long long)d.out | ((unsigned long long)d.ldo * sizeof(T)) | (d.res ? (unsigned long long)d.res : 0ull);
-    if (uni && !(g_debug_flags & 64) && (al & 15ull) == 0ull) {
-      // Small launches (B = 1 .. 8): the 256 x 128 / 128 x 256 tiles leave most CUs idle (layer3 at B = 1: 13 tiles), and every tile walks
-      // the whole K range.  The 64-channel x 256-pixel shape of the same kernel makes 2-4x as many tiles of a quarter / half of the work;
-      // taken while even those fit one round of the persistent grid (debug flag 16777216: never).
-      if (!(g_debug_flags & (1 << 24)) && d.Cout % 64 == 0 && d.M < (1ll << 31)) {
-        int n_cu = 0;
-        if (int rc = persistent_grid_cus(&n_cu)) return rc;
-        const long long slim_tiles = ((d.M + 255) / 256) * (d.Cout / 64);
-        if constexpr (sizeof(T) == 2 || std::is_same<T, bx3_t>::value) {
-          // round 6: launches that do not fill the grid with 256-pixel tiles of the 256-channel layers pick their tile by requested bytes
-          // (m32_small_choice; debug flag 1073741824: as in round 5)
-          if (d.Cout % 256 == 0 && ((d.M + 255) / 256) * (d.Cout / 256) < n_cu && g_gemm_kernel >= 1 && !(g_debug_flags & ((1 << 30) | 65536)) &&
-              conv_buffer_offsets_ok(d, 256, sizeof(T))) {
-            // (gemm_kernel = 1, the A/B reference: the same arithmetic on 256-channel x 128-pixel tiles - bit-identical results)
-            const int pick = g_gemm_kernel == 1 ? 256 : m32_small_choice(d, n_cu, slim_tiles <= n_cu);
-            if (pick) return launch_m32_small<T>(d, s, pick);
-          }
-          // layer2's 128-channel layers at one to four poses (13-52 tiles of 64 x 256): 64-channel x 128-pixel tiles of the 32x32x16 kernel with
-          // their K loop split (conv_igemm_m32.inc) — taken only where the split applies, i.e. while twice the tiles still fit the grid
-          if (d.Cout == 128 && ((d.M + 127) / 128) * 2 * 2 <= n_cu && g_gemm_kernel == 2 && !(g_debug_flags & ((1 << 30) | 65536 | 16384 | 32768)) &&
-              d.w2 == nullptr && conv_buffer_offsets_ok(d, 64, sizeof(T)))
-            return launch_m32_small<T>(d, s, 64);
+static int launch_plan(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
+  constexpr bool M32 = sizeof(T) == 2 || std::is_same<T, bx3_t>::value;
+  switch (p.kernel) {
+    case CONV_GENERIC: {
+      auto tile = [&](auto uni) {
+        constexpr bool UNI = decltype(uni)::value;
+        switch (p.bch) {
+          case 16: return launch_one_g<T, 16, 256, UNI>(d, s);
+          case 32: return launch_one_g<T, 32, 256, UNI>(d, s);
+          case 64: return launch_one_g<T, 64, 256, UNI>(d, s);
+          default: return launch_one_g<T, 128, 128, UNI>(d, s);
         }
-        if (slim_tiles <= n_cu) return launch_ws<T, false, false, true>(d, s);
-      }
-      if (d.Cout % 256 == 0 && !(g_debug_flags & 65536)) {
-        if constexpr (sizeof(T) == 2 || std::is_same<T, bx3_t>::value) {
-          if (conv_buffer_offsets_ok(d, 256, sizeof(T))) {      // its request waves address both operands through 32-bit buffer offsets
-            if (g_gemm_kernel >= 1) return launch_m32<T>(d, s, g_gemm_kernel);
-          }
-        }
-        return launch_ws<T, true, false>(d, s);
-      }
-      // (round 6 measured layer2's 128-channel layers on 128 x 256 tiles of the 32x32x16 kernel: 0.122 against 0.119 ms per launch in bf16,
-      // 0.293 against 0.291 in split pairs - a 128-channel tile needs 48 KB per 1024 cycles of MFMA and is request-bound in either kernel)
-      return launch_ws<T, false, false>(d, s);
+      };
+      return p.uniform_taps ? tile(IC<true>{}) : tile(IC<false>{});
     }
-    return uni ? launch_v3<T, true>(d, s) : launch_v3<T, false>(d, s);
+    case CONV_M32_SMALL:
+      if constexpr (M32) return launch_m32_small<T>(d, p, s);
+      break;
+    case CONV_WS_SLIM: return launch_ws<T, false, false, true>(d, p, s);
+    case CONV_M32:
+      if constexpr (M32) return launch_m32<T>(d, p, s);
+      break;
+    case CONV_WS_WIDE: return launch_ws<T, true, false>(d, p, s);
+    case CONV_WS: return launch_ws<T, false, false>(d, p, s);
+    case CONV_V3: return p.uniform_taps ? launch_v3<T, true>(d, s) : launch_v3<T, false>(d, s);
+    case CONV_WS64:
+    case CONV_WS64_ROWHALO:
+      if constexpr (sizeof(T) == 2) return launch_ws64<T>(d, p.kernel == CONV_WS64_ROWHALO, s);
+      break;
   }
-  // 33..64 output channels, bf16, no residual, >= 2 K tiles, 16-byte aligned output rows: three-role persistent kernel
-  // 33..64 output channels, 16-bit storage: the three-role persistent kernel
-  if constexpr (sizeof(T) == 2) {
-    if (conv_ws64_eligible(d, BF16)) return launch_ws64<T>(d, s);
-  }
-  RGBM_REQUIRE(d.w2 == nullptr, "a fused 1x1 needs the ws64 kernel (check conv_ws64_eligible first)");
-  // 33..64 output channels where there is no ws64 kernel (split pairs, fp32) or it does not apply (residual adds): the
-  // role-specialised kernel with a 64 x 256 tile and four multiply waves
-  if (conv_ch_tile(d.Cout) == 64 && uni && d.M >= ws_min_rows(sizeof(T)) && d.M < (1ll << 31) && !(g_debug_flags & (8 | 64 | 262144))) {
-    const unsigned long long al = (unsigned long long)d.out | ((unsigned long long)d.ldo * sizeof(T)) | (d.res ? (unsigned long long)d.res : 0ull);
-    // (round 6 measured 64-channel x 256-pixel tiles of the 32x32x16 kernel for layer1's 64-channel layers at batch 256: split pairs 0.542 ms
-    // per launch against 0.475 on this tile, bf16 38.39 ms per forward against 38.10 with the row-halo ws64 kernel — not dispatched)
-    if ((al & 15ull) == 0ull) return launch_ws<T, false, false, true>(d, s);
-  }
-  return uni ? launch_t_g<T, true>(d, s) : launch_t_g<T, false>(d, s);
+  RGBM_REQUIRE(false, "conv plan names a kernel this storage type does not have");
+}
+
+int launch_conv(const ConvDesc& d, int dtype, hipStream_t s) {
+  ConvTuning t;
+  ConvPlan p;
+  if (int rc = conv_tuning(0, &t)) return rc;
+  if (int rc = plan_conv(d, dtype, t, &p)) return rc;
+  return dtype == BF16 ? launch_plan<unsigned short>(d, p, s) : dtype == F16 ? launch_plan<f16_t>(d, p, s)
+         : dtype == BF16X3 ? launch_plan<bx3_t>(d, p, s) : launch_plan<float>(d, p, s);
 }
 
 bool conv_ws64_eligible(const ConvDesc& d, int dtype) {
-  if ((dtype != BF16 && dtype != F16) || (g_debug_flags & (4 | 16 | 128))) return false;
-  if (!conv_uniform_taps(d, 64) || conv_ch_tile(d.Cout) != 64 || d.res_mode != RES_NONE || d.KT < 2) return false;
-  if (d.M < ws_min_rows(2) || d.M >= (1ll << 31)) return false;
-  if (d.w2) return d.Cout == 64 && d.kpad2 == 64 && (d.cout2 == 16 || d.cout2 == 32) && d.ldo2 % 4 == 0;
-  return (((unsigned long long)d.out | ((unsigned long long)d.ldo * 2ull)) & 15ull) == 0ull;
-}
-
-int launch_conv_glds(const ConvDesc& d, int dtype, hipStream_t s) {
-  return dtype == BF16 ? launch_dtype_g<unsigned short>(d, s) : dtype == F16 ? launch_dtype_g<f16_t>(d, s)
-         : dtype == BF16X3 ? launch_dtype_g<bx3_t>(d, s) : launch_dtype_g<float>(d, s);
+  ConvTuning t;
+  ConvPlan p;
+  return !conv_tuning(0, &t) && !plan_conv(d, dtype, t, &p) && (p.kernel == CONV_WS64 || p.kernel == CONV_WS64_ROWHALO);
 }
 
 }  // namespace rgbm

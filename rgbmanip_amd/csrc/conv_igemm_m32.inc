@@ -134,7 +134,7 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
     int tkd = 0, tkh = 0, tkw = 0, tc = 0;   // wave-uniform tap walker
     unsigned wko = 0;                        // byte offset of the walker's K index in a weight row
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr(lds3 + pw * 64));      // this wave's first piece, stage 0
-    // Both operands through buffer descriptors (launch_m32 checked that they fit 32-bit offsets).  X offsets are taken from
+    // Both operands through buffer descriptors (plan_conv checked that they fit 32-bit offsets).  X offsets are taken from
     // (input base - xbias) so that a row whose tap (0,0,0) lies in the padding still has a non-negative offset; a padded lane gets
     // an offset beyond num_records and lands as zeros.
     const long long xbias = ((long long)(d.pd * d.Hi + d.ph) * d.Wi + d.pw) * d.Cin * (long long)sizeof(T);
@@ -815,7 +815,6 @@ static int launch_m32_range(ConvDesc d, hipStream_t s) {
   make_fastdiv(d.Wq, d.fd_m[0], d.fd_s[0]);
   make_fastdiv(d.Hq, d.fd_m[1], d.fd_s[1]);
   make_fastdiv(d.Dq, d.fd_m[2], d.fd_s[2]);
-  d.korder = (g_debug_flags & (1 << 20)) ? 0 : 1;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_igemm_m32_kernel<T, BPIX, BCH>), (int)LDS)) return rc;
   int n_cu = 0;
   if (int rc = persistent_grid_cus(&n_cu)) return rc;
@@ -857,82 +856,9 @@ static int m32_identity(const void** out) {
   return 0;
 }
 
-// Layers whose output channels are a multiple of 256 (layer3 / layer4 / up_1 / the first 512 stacked rows of up_2), 16-bit storage or split pairs:
-// whole rounds of BCH x 256 tiles over the persistent grid, the rest of the rows (a partial last round, a ragged last pixel tile) on 128-pixel
-// tiles in a second launch — cut in channels too (round 6) so that the rest gives every CU a tile: the smallest of 64 / 128 / 256 channels
-// whose tile count still fits one round (layer3's 8192 left-over rows: 64 tiles of 256 x 128 on a quarter of the chip before, 256 tiles of
-// 64 x 128 now).  Returns 1 if the layer is not for these kernels (the caller falls back to conv_igemm_ws_kernel).
-template <typename T, int BCH>
-static int launch_m32_bch(ConvDesc d, hipStream_t s, int mode) {
-  const bool dense_out = d.osd == 1 && d.osh == 1 && d.osw == 1 && d.opd == 0 && d.oph == 0 && d.opw == 0 && d.Dq == d.Do && d.Hq == d.Ho && d.Wq == d.Wo;
-  const bool big_ok = dense_out && (d.bias == nullptr || (d.bias_stride == 0 && d.Cout <= 2560)) && d.act != ACT_TANH && d.Cout % BCH == 0 &&
-                      (d.res_mode == RES_NONE || (d.res_mode == RES_PRE_ACT && d.res != nullptr)) &&
-                      d.M * d.ldo * (long long)sizeof(T) < (1ll << 32) - 65536;
-  if (mode == 1) return launch_m32_range<T, 128, BCH>(d, s);
-  int n_cu = 0;
-  if (int rc = persistent_grid_cus(&n_cu)) return rc;
-  const long long P = d.M / 256, n_ch = d.Cout / BCH, tiles = P * n_ch;
-  long long Pm = 0;
-  if (big_ok && tiles >= n_cu) {
-    const long long rem = tiles % n_cu;
-    // a last round that fills less than ~60 % of the chip costs more on 256-pixel tiles than its rows cost on 128-pixel tiles afterwards
-    Pm = (rem == 0 || rem * 10 >= (long long)n_cu * 6) ? P : (tiles - rem) / n_ch;
-  }
-  if (Pm > 0) {
-    ConvDesc m = d;
-    m.M = Pm * 256;
-    const double frac = (double)m.M / (double)d.M;
-    m.algo_flops = d.algo_flops * frac; m.algo_bytes = d.algo_bytes * frac;
-    if (int rc = launch_m32_range<T, 256, BCH>(m, s)) return rc;
-    if (m.M == d.M) return 0;
-    d.m0 = m.M;
-    d.algo_flops *= 1.0 - frac; d.algo_bytes *= 1.0 - frac;
-  }
-  // the rest: 128-pixel tiles, channels cut so that the tiles fill (at most) one round of the grid
-  const long long pt = (d.M - d.m0 + 127) / 128;
-  if (!(g_debug_flags & (1 << 30))) {      // debug flag 1073741824: tails on BCH-channel tiles as in round 5 (A/B)
-    if (d.Cout % 64 == 0 && BCH >= 64 && pt * (d.Cout / 64) <= n_cu) return launch_m32_range<T, 128, 64>(d, s);
-    if (d.Cout % 128 == 0 && BCH >= 128 && pt * (d.Cout / 128) <= n_cu) return launch_m32_range<T, 128, 128>(d, s);
-  }
-  return launch_m32_range<T, 128, BCH>(d, s);
-}
-
-template <typename T>
-static int launch_m32(const ConvDesc& d0, hipStream_t s, int mode) {
-  ConvDesc d = d0;
-  d.m0 = 0;
-  d.ident = nullptr;
-  const bool dense_out = d.osd == 1 && d.osh == 1 && d.osw == 1 && d.opd == 0 && d.oph == 0 && d.opw == 0 && d.Dq == d.Do && d.Hq == d.Ho && d.Wq == d.Wo;
-  // the residual of every launch goes through the matrix pipe (identity K steps): the same arithmetic whichever tile a row falls into
-  if (dense_out && d.res_mode == RES_PRE_ACT && d.res != nullptr && d.M * d.ldo * (long long)sizeof(T) < (1ll << 32) - 65536)
-    if (int rc = m32_identity<T>(&d.ident)) return rc;
-  RGBM_REQUIRE(d.Cout % 256 == 0, "conv_igemm_m32: output channels must be a multiple of 256");
-  return launch_m32_bch<T, 256>(d, s, mode);
-}
-
-// Small launches (round 6; the deployment shape: B = 1 .. 8 poses, cfg/task/open_cabinet.yaml:4 ships num_envs: 8): a layer whose tiles do not
-// fill the persistent grid on the 256-pixel shapes.  Every tile walks the layer's whole K range at one K tile per (request-bound) step, so
-// a launch costs  rounds x steps x (bytes requested per step)  and fewer bytes per tile win while the rounds do not grow: 128-pixel tiles of
-// 64 / 128 / 256 channels (24 / 32 / 48 KB per step) against the 16x16x32 kernel's 64-channel x 256-pixel tile (40 KB).  Returns the channel
-// tile to use (64 / 128 / 256), or 0 for "keep the 64 x 256 tile of conv_igemm_ws_kernel".
-static int m32_small_choice(const ConvDesc& d, int n_cu, bool slim_ok) {
-  const long long p128 = (d.M + 127) / 128, p256 = (d.M + 255) / 256;
-  auto cost = [&](long long tiles, int kb) { return (double)((tiles + n_cu - 1) / n_cu) * (double)(kb + 8); };      // + 8: the step's fixed part
-  double best = slim_ok ? cost(p256 * (d.Cout / 64), 40) : 1e30;
-  int pick = 0;
-  const int bch[3] = {64, 128, 256}, kb[3] = {24, 32, 48};
-  for (int i = 0; i < 3; ++i) {
-    if (d.Cout % bch[i]) continue;
-    const double c = cost(p128 * (d.Cout / bch[i]), kb[i]);
-    if (c < best * 0.999) { best = c; pick = bch[i]; }
-  }
-  return pick;
-}
-
 // K-split scratch of a stream (launches on one stream are ordered; forwards on other streams have their own): 32 MB of partial
 // accumulators + 16384 arrival counters (zero: every launch leaves them so), allocated at the first small launch on that stream —
 // in an eager forward: rgbm_adapose_forward_graph runs one in front of a capture
-constexpr size_t kM32SplitFloats = 8u << 20, kM32SplitCounters = 16384;
 static int m32_ksplit_buffers(hipStream_t s, float** scratch, unsigned** count) {
   static std::mutex mu;
   static std::map<std::pair<int, hipStream_t>, std::pair<float*, unsigned*>> per_stream;
@@ -955,43 +881,45 @@ static int m32_ksplit_buffers(hipStream_t s, float** scratch, unsigned** count) 
   return 0;
 }
 
-// parts to cut a small launch's K loop into: the tiles fill at most half the CUs, every part keeps at least eight K steps
-#ifndef M32_KSPLIT_MAX
-#define M32_KSPLIT_MAX 4
-#endif
-#ifndef M32_KSPLIT_MINSTEPS
-#define M32_KSPLIT_MINSTEPS 8
-#endif
-static int m32_ksplit_choice(const ConvDesc& d, long long tiles, int n_cu, int bch, int n_waves) {
-  if ((g_debug_flags & 16384) || tiles <= 0 || bch > 128) return 1;
-  int n = (int)(n_cu / tiles);
-  if (n > M32_KSPLIT_MAX) n = M32_KSPLIT_MAX;
-  while (n > 1 && d.KT / n < M32_KSPLIT_MINSTEPS) --n;
-  if (n < 2) return 1;
-  if ((size_t)tiles * n * bch * 128 > kM32SplitFloats || (size_t)tiles * n_waves > kM32SplitCounters) return 1;
-  return n;
+// What plan_conv (conv_plan.cpp) decided, for both launch forms of this kernel.  Two things are facts of the launch, not of the plan: a
+// stream that is being captured before it has K-split scratch runs unsplit, and the identity matrix is per device.
+template <typename T>
+static int m32_setup(ConvDesc& d, const ConvPlan& p, hipStream_t s) {
+  d.m0 = 0;
+  d.ident = nullptr;
+  d.korder = p.korder;
+  d.ksplit = 1; d.kscratch = nullptr; d.kcount = nullptr;
+  if (p.ksplit > 1) {
+    if (int rc = m32_ksplit_buffers(s, &d.kscratch, &d.kcount)) return rc;
+    if (d.kscratch) d.ksplit = p.ksplit;
+  }
+  return p.identity_residual ? m32_identity<T>(&d.ident) : 0;
 }
 
 template <typename T>
-static int launch_m32_small(const ConvDesc& d0, hipStream_t s, int bch) {
-  ConvDesc d = d0;
-  d.m0 = 0;
-  d.ident = nullptr;
-  d.ksplit = 1; d.kscratch = nullptr; d.kcount = nullptr;
-  {
-    int n_cu = 0;
-    if (int rc = persistent_grid_cus(&n_cu)) return rc;
-    const long long tiles = ((d.M + 127) / 128) * ((d.Cout + bch - 1) / bch);
-    const int n = m32_ksplit_choice(d, tiles, n_cu, bch, 4);
-    if (n > 1) {
-      if (int rc = m32_ksplit_buffers(s, &d.kscratch, &d.kcount)) return rc;
-      if (d.kscratch) d.ksplit = n;
-    }
-  }
-  const bool dense_out = d.osd == 1 && d.osh == 1 && d.osw == 1 && d.opd == 0 && d.oph == 0 && d.opw == 0 && d.Dq == d.Do && d.Hq == d.Ho && d.Wq == d.Wo;
-  // (layers of fewer than 256 channels — layer2 at one to four poses — add their residual in the epilogue: the identity steps turn an
-  // infinite residual into NaN, and these layers' launches are held to the saturating-store contract of the kernels they replace)
-  if (d.Cout % 256 == 0 && dense_out && d.res_mode == RES_PRE_ACT && d.res != nullptr && d.M * d.ldo * (long long)sizeof(T) < (1ll << 32) - 65536)
-    if (int rc = m32_identity<T>(&d.ident)) return rc;
+static int launch_m32_tiles128(const ConvDesc& d, int bch, hipStream_t s) {
   return bch == 64 ? launch_m32_range<T, 128, 64>(d, s) : bch == 128 ? launch_m32_range<T, 128, 128>(d, s) : launch_m32_range<T, 128, 256>(d, s);
+}
+
+// CONV_M32_SMALL: every row on bch x 128 tiles
+template <typename T>
+static int launch_m32_small(ConvDesc d, const ConvPlan& p, hipStream_t s) {
+  if (int rc = m32_setup<T>(d, p, s)) return rc;
+  return launch_m32_tiles128<T>(d, p.bch, s);
+}
+
+// CONV_M32: rows [0, main_rows) on 256 x 256 tiles, the rest on tail_bch x 128 tiles in a second launch
+template <typename T>
+static int launch_m32(ConvDesc d, const ConvPlan& p, hipStream_t s) {
+  if (int rc = m32_setup<T>(d, p, s)) return rc;
+  if (p.main_rows > 0) {
+    ConvDesc m = d;
+    m.M = p.main_rows;
+    const double frac = (double)m.M / (double)d.M;
+    m.algo_flops = d.algo_flops * frac; m.algo_bytes = d.algo_bytes * frac;
+    if (int rc = launch_m32_range<T, 256, 256>(m, s)) return rc;
+    d.m0 = m.M;
+    d.algo_flops *= 1.0 - frac; d.algo_bytes *= 1.0 - frac;
+  }
+  return p.tail_bch ? launch_m32_tiles128<T>(d, p.tail_bch, s) : 0;
 }

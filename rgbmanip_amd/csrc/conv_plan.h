@@ -1,0 +1,49 @@
+// Which kernel, tile and K split an implicit-GEMM convolution runs on: the decision, and nothing else.  plan_conv is a pure function
+// of its arguments (no HIP runtime call, no global read), so it can be asked without a GPU (rgbm_conv_plan in rgbm.h) and tested
+// directly; launch_conv (conv_igemm_glds.hip) gathers the ConvTuning, calls it and launches what it says.
+#pragma once
+#include "common.h"
+
+namespace rgbm {
+
+// everything outside the ConvDesc that the decision depends on
+struct ConvTuning {
+  int flags;               // rgbm_debug_flags word (DebugFlag, kernels.h)
+  int gemm_kernel;         // rgbm_set_tuning "gemm_kernel"
+  long long ws_min_rows;   // rgbm_set_tuning "ws_min_rows" (0 = the default)
+  int n_cu;                // persistent_grid_cus()
+};
+
+// (the values are the kernel ids of rgbm_conv_plan, rgbm.h)
+enum ConvKernel {
+  CONV_GENERIC = 0,        // conv_igemm_glds_kernel, bch x bpix tile
+  CONV_V3 = 1,             // conv_igemm_v3_kernel 128 x 256
+  CONV_WS = 2,             // conv_igemm_ws_kernel 128 x 256
+  CONV_WS_WIDE = 3,        // ... 256 x 128
+  CONV_WS_SLIM = 4,        // ... 64 x 256, four multiply waves
+  CONV_WS64 = 5,           // conv_igemm_ws64_kernel
+  CONV_WS64_ROWHALO = 6,   // ... row-halo variant
+  CONV_M32 = 7,            // conv_igemm_m32_kernel: main_rows on 256 x 256 tiles, the rest on tail_bch x 128 tiles
+  CONV_M32_SMALL = 8,      // ... one launch of bch x 128 tiles that does not fill the grid, K loop cut into ksplit parts
+};
+
+struct ConvPlan {
+  int kernel;              // ConvKernel
+  int bch, bpix;           // tile (of the main launch for CONV_M32)
+  bool uniform_taps;       // every K tile inside one tap (the UNI forms of the generic / v3 kernels)
+  long long main_rows;     // CONV_M32: rows [0, main_rows) on 256 x 256 tiles
+  int tail_bch;            // CONV_M32: channel tile of the 128-pixel launch of rows [main_rows, M) (0 = no tail)
+  int ksplit;              // K parts the launch asks for (1 = none); the executor runs unsplit where the stream has no scratch
+  bool identity_residual;  // the m32 kernels add the residual through identity K steps (else in the epilogue)
+  int korder, buf_ok;      // ConvDesc fields of the same names
+};
+
+// K-split scratch of a stream: fp32 partial accumulators and arrival counters (m32_ksplit_buffers); a split that would not fit is not planned
+constexpr size_t kM32SplitFloats = 8u << 20, kM32SplitCounters = 16384;
+
+// 0, or -1 with the error set where no kernel takes d (a malformed descriptor)
+int plan_conv(const ConvDesc& d, int dtype, const ConvTuning& t, ConvPlan* out);
+// the process's current tuning (conv_igemm_glds.hip); n_cu = 0: the current device's, else as given without a HIP runtime call
+int conv_tuning(int n_cu, ConvTuning* t);
+
+}  // namespace rgbm

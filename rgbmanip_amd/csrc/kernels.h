@@ -108,6 +108,14 @@ struct Conv3dTileDesc {
   const unsigned char* tile_mask;   // optional [N][nth][ntw]: a workgroup whose (view, row tile, column tile) byte is 0 returns at once (its
                                     // output tile is never read: sparse decoder, see launch_decoder_tile_masks); all depth tiles share a byte
 };
+// bits of g_debug_flags (rgbm_debug_flags): what each one switches is described in the table at rgbm_debug_flags in include/rgbm.h
+enum DebugFlag {
+  DBG_NO_WS = 8, DBG_NONUNIFORM_TAPS = 16, DBG_V3_FOR_WS = 64, DBG_NO_WS64 = 128, DBG_NO_ROWHALO = 256, DBG_GENERIC_RESIZE = 512,
+  DBG_PSP_STAGE_R5 = 1024, DBG_POINT_MLP_R5 = 2048, DBG_TILE_CONV0 = 4096, DBG_NO_KSPLIT = 16384, DBG_L2_SLIM_TILE = 32768,
+  DBG_WS_128x256 = 65536, DBG_NO_SLIM64 = 262144, DBG_KORDER_TAPS_OUTER = 1 << 20, DBG_SWEEP_ALT_BLEND = 1 << 21, DBG_SWEEP_DOT2 = 1 << 22,
+  DBG_PP_ONE_KERNEL = 1 << 23, DBG_NO_SLIM_SMALL = 1 << 24, DBG_PP_GENERIC_SELECT = 1 << 25, DBG_PP_GUARD = 1 << 26, DBG_GLOBAL_ADDR = 1 << 27,
+  DBG_SWEEP_PER_TILE = 1 << 28, DBG_SPARSE_TAIL_R5 = 1 << 29, DBG_M32_TAILS_R5 = 1 << 30,
+};
 extern int g_debug_flags;
 extern long long g_ws_min_rows;
 extern int g_tuning_version;

@@ -116,16 +116,36 @@ int upload_packed(const std::vector<float>& w, int dtype, void** dev) {
   return 0;
 }
 
+int conv_pack_geom(const ConvGeom& g, int dtype, int Cin_pad, int Cout_pad, int cls, PackedConv* pc) {
+  const int BK = conv_bk(dtype);
+  RGBM_REQUIRE(Cin_pad % dtype_chunk(dtype) == 0 && Cin_pad >= g.Cin, "Cin_pad");
+  RGBM_REQUIRE(Cout_pad % 4 == 0 && Cout_pad >= g.Cout, "Cout_pad");
+  *pc = PackedConv();
+  if (!g.transposed) {
+    pc->KD = g.KD; pc->KH = g.KH; pc->KW = g.KW;
+  } else {
+    // ConvTranspose3d(k=3, s=2, p=1, op=1): out o = 2q+p.  p=0 -> single tap k=1 at input q;
+    // p=1 -> taps (delta=0 -> k=2 at q), (delta=1 -> k=0 at q+1).
+    RGBM_REQUIRE(g.KD == 3 && g.KH == 3 && g.KW == 3 && g.sd == 2 && g.sh == 2 && g.sw == 2, "transposed conv geometry");
+    RGBM_REQUIRE(cls >= 0 && cls < 8, "sub-pixel class");
+    pc->KD = 1 + ((cls >> 2) & 1); pc->KH = 1 + ((cls >> 1) & 1); pc->KW = 1 + (cls & 1);
+  }
+  pc->ntaps = pc->KD * pc->KH * pc->KW;
+  if (pc->ntaps > 1 || g.transposed) RGBM_REQUIRE(is_pow2(Cin_pad), "multi-tap / transposed conv needs power-of-two Cin_pad");
+  const int K = pc->ntaps * Cin_pad;
+  pc->Kpad = (K + BK - 1) / BK * BK;
+  pc->KT = pc->Kpad / BK;
+  return 0;
+}
+
 int ConvLayer::init(int dtype_, const ConvGeom& g_, const float* w, const float* bias_h, const float* bn_scale,
                     const float* bn_shift, int Cin_pad_, int Cout_pad_) {
   g = g_;
   dtype = dtype_;
   Cin_pad = Cin_pad_;
   Cout_pad = Cout_pad_;
-  const int E = dtype_chunk(dtype);
-  const int BK = conv_bk(dtype);
-  RGBM_REQUIRE(Cin_pad % E == 0 && Cin_pad >= g.Cin, "Cin_pad");
-  RGBM_REQUIRE(Cout_pad % 4 == 0 && Cout_pad >= g.Cout, "Cout_pad");
+  PackedConv pc;
+  if (int rc = conv_pack_geom(g, dtype, Cin_pad, Cout_pad, 0, &pc)) return rc;
   const int bch = conv_ch_tile(Cout_pad);
   const int rows = (Cout_pad + bch - 1) / bch * bch;   // weight rows padded to the channel tile
 
@@ -150,13 +170,6 @@ int ConvLayer::init(int dtype_, const ConvGeom& g_, const float* w, const float*
   };
 
   if (!g.transposed) {
-    PackedConv pc;
-    pc.KD = g.KD; pc.KH = g.KH; pc.KW = g.KW;
-    pc.ntaps = g.KD * g.KH * g.KW;
-    if (pc.ntaps > 1) RGBM_REQUIRE(is_pow2(Cin_pad), "multi-tap conv needs power-of-two Cin_pad");
-    const int K = pc.ntaps * Cin_pad;
-    pc.Kpad = (K + BK - 1) / BK * BK;
-    pc.KT = pc.Kpad / BK;
     std::vector<float> packed((size_t)rows * pc.Kpad, 0.f);
     const long long kvol = (long long)g.KD * g.KH * g.KW;
     for (int o = 0; o < g.Cout; ++o) {
@@ -168,18 +181,10 @@ int ConvLayer::init(int dtype_, const ConvGeom& g_, const float* w, const float*
     return finish(pc, packed);
   }
 
-  // ConvTranspose3d(k=3, s=2, p=1, op=1): out o = 2q+p.  p=0 -> single tap k=1 at input q;
-  // p=1 -> taps (delta=0 -> k=2 at q), (delta=1 -> k=0 at q+1).   weight layout [Cin][Cout][3][3][3].
-  RGBM_REQUIRE(g.KD == 3 && g.KH == 3 && g.KW == 3 && g.sd == 2 && g.sh == 2 && g.sw == 2, "transposed conv geometry");
-  RGBM_REQUIRE(is_pow2(Cin_pad), "transposed conv needs power-of-two Cin_pad");
+  // one weight set per sub-pixel class (conv_pack_geom); weight layout [Cin][Cout][3][3][3]
   for (int cls = 0; cls < 8; ++cls) {
     const int pd_ = (cls >> 2) & 1, ph_ = (cls >> 1) & 1, pw_ = cls & 1;
-    PackedConv pc;
-    pc.KD = 1 + pd_; pc.KH = 1 + ph_; pc.KW = 1 + pw_;
-    pc.ntaps = pc.KD * pc.KH * pc.KW;
-    const int K = pc.ntaps * Cin_pad;
-    pc.Kpad = (K + BK - 1) / BK * BK;
-    pc.KT = pc.Kpad / BK;
+    if (int rc = conv_pack_geom(g, dtype, Cin_pad, Cout_pad, cls, &pc)) return rc;
     std::vector<float> packed((size_t)rows * pc.Kpad, 0.f);
     auto kidx = [](int p, int delta) { return p == 0 ? 1 : (delta == 0 ? 2 : 0); };
     for (int o = 0; o < g.Cout; ++o) {
@@ -206,30 +211,23 @@ void ConvLayer::destroy() {
   bias = nullptr;
 }
 
-void ConvLayer::out_dims(int Di, int Hi, int Wi, int& Do, int& Ho, int& Wo) const {
+void conv_out_dims(const ConvGeom& g, int Di, int Hi, int Wi, int& Do, int& Ho, int& Wo) {
   if (g.transposed) { Do = 2 * Di; Ho = 2 * Hi; Wo = 2 * Wi; return; }
   Do = (Di + 2 * g.pd - g.dild * (g.KD - 1) - 1) / g.sd + 1;
   Ho = (Hi + 2 * g.ph - g.dilh * (g.KH - 1) - 1) / g.sh + 1;
   Wo = (Wi + 2 * g.pw - g.dilw * (g.KW - 1) - 1) / g.sw + 1;
 }
 
-int ConvLayer::build_desc(ConvDesc& d, const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res,
-                          int res_mode, const float* bias_override, int bias_stride, int cls) const {
-  RGBM_REQUIRE(!packs.empty(), "conv layer not initialised");
-  int Do, Ho, Wo;
-  out_dims(Di, Hi, Wi, Do, Ho, Wo);
+void ConvLayer::out_dims(int Di, int Hi, int Wi, int& Do, int& Ho, int& Wo) const { conv_out_dims(g, Di, Hi, Wi, Do, Ho, Wo); }
+
+void conv_desc_geom(ConvDesc& d, const ConvGeom& g, const PackedConv& pc, int Cin_pad, int Cout_pad, int N, int Di, int Hi, int Wi,
+                    int ldo, int cls) {
   memset(&d, 0, sizeof(d));
-  d.in = in; d.out = out; d.res = res;
-  d.bias = bias_override ? bias_override : bias;
-  d.bias_stride = bias_override ? bias_stride : 0;
+  conv_out_dims(g, Di, Hi, Wi, d.Do, d.Ho, d.Wo);
   d.N = N; d.Di = Di; d.Hi = Hi; d.Wi = Wi;
   d.Cin = Cin_pad;
   d.Cout = Cout_pad; d.ldo = ldo;
-  d.Do = Do; d.Ho = Ho; d.Wo = Wo;
-  d.act = g.act; d.slope = g.slope; d.res_mode = res ? res_mode : RES_NONE;
-  d.out_f32 = (out_plain_f32 && dtype == BF16X3) ? 1 : 0;
-  const PackedConv& pc = packs[cls];
-  d.wgt = pc.w;
+  d.act = g.act; d.slope = g.slope;
   d.KD = pc.KD; d.KH = pc.KH; d.KW = pc.KW;
   d.ntaps = pc.ntaps; d.KT = pc.KT; d.Kpad = pc.Kpad;
   d.lcin = (pc.ntaps > 1 || is_pow2(Cin_pad)) ? ilog2(Cin_pad) : -1;
@@ -240,13 +238,25 @@ int ConvLayer::build_desc(ConvDesc& d, const void* in, void* out, int N, int Di,
     d.osd = d.osh = d.osw = 2;
     d.opd = (cls >> 2) & 1; d.oph = (cls >> 1) & 1; d.opw = cls & 1;
   } else {
-    d.Dq = Do; d.Hq = Ho; d.Wq = Wo;
+    d.Dq = d.Do; d.Hq = d.Ho; d.Wq = d.Wo;
     d.sd = g.sd; d.sh = g.sh; d.sw = g.sw; d.pd = g.pd; d.ph = g.ph; d.pw = g.pw;
     d.dild = g.dild; d.dilh = g.dilh; d.dilw = g.dilw;
     d.osd = d.osh = d.osw = 1;
     d.opd = d.oph = d.opw = 0;
   }
   d.M = (long long)N * d.Dq * d.Hq * d.Wq;
+}
+
+int ConvLayer::build_desc(ConvDesc& d, const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res,
+                          int res_mode, const float* bias_override, int bias_stride, int cls) const {
+  RGBM_REQUIRE(!packs.empty(), "conv layer not initialised");
+  const PackedConv& pc = packs[cls];
+  conv_desc_geom(d, g, pc, Cin_pad, Cout_pad, N, Di, Hi, Wi, ldo, cls);
+  d.in = in; d.out = out; d.res = res; d.wgt = pc.w;
+  d.bias = bias_override ? bias_override : bias;
+  d.bias_stride = bias_override ? bias_stride : 0;
+  d.res_mode = res ? res_mode : RES_NONE;
+  d.out_f32 = (out_plain_f32 && dtype == BF16X3) ? 1 : 0;
   // algorithmic work: real (unpadded) channels, every tap counted (zero padding included, as usual)
   d.algo_flops = 2.0 * (double)d.M * g.Cout * (double)pc.ntaps * g.Cin;
   d.algo_bytes = ((double)d.M * g.Cout + (cls == 0 ? (double)N * Di * Hi * Wi * g.Cin : 0.0) +

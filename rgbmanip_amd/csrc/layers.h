@@ -33,6 +33,13 @@ struct PackedConv {
   int KD = 1, KH = 1, KW = 1, ntaps = 1, Kpad = 0, KT = 0;
 };
 
+// The geometry half of a layer and of its ConvDesc: what needs no device memory (ConvLayer fills in the pointers; rgbm_conv_plan asks
+// plan_conv about a shape with these alone).  cls: sub-pixel class of a transposed conv (0 otherwise).
+int conv_pack_geom(const ConvGeom& g, int dtype, int Cin_pad, int Cout_pad, int cls, PackedConv* pc);      // taps and K padding (pc->w stays null)
+void conv_out_dims(const ConvGeom& g, int Di, int Hi, int Wi, int& Do, int& Ho, int& Wo);
+void conv_desc_geom(ConvDesc& d, const ConvGeom& g, const PackedConv& pc, int Cin_pad, int Cout_pad, int N, int Di, int Hi, int Wi,
+                    int ldo, int cls);      // zeroes d, then every field that is not a pointer
+
 struct ConvLayer {
   ConvGeom g;
   int dtype = F32;

@@ -249,7 +249,7 @@ int launch_resize_bilinear_ac(int dtype, const void* in, void* out, int V, int H
   RGBM_REQUIRE(C % E == 0 && ldo % E == 0 && ch_off % E == 0, "resize channel alignment");
   const float sy = Ho > 1 ? (float)(Hs - 1) / (float)(Ho - 1) : 0.f;
   const float sx = Wo > 1 ? (float)(Ws - 1) / (float)(Wo - 1) : 0.f;
-  if (Ho == 2 * Hs && Wo == 2 * Ws && Hs >= 2 && Ws >= 2 && (long long)V * Hs * Ws * (C / E) < (1ll << 31) && !(g_debug_flags & 512)) {
+  if (Ho == 2 * Hs && Wo == 2 * Ws && Hs >= 2 && Ws >= 2 && (long long)V * Hs * Ws * (C / E) < (1ll << 31) && !(g_debug_flags & DBG_GENERIC_RESIZE)) {
     const long long blocks = (long long)V * ((Hs + 1) / 2) * ((Ws + 1) / 2) * (C / E);      // one thread per 2 x 2 input block and 16-byte chunk
     if (dtype == BF16)
       hipLaunchKernelGGL(resize2x_ac_kernel<unsigned short>, dim3(grid_for(blocks)), dim3(256), 0, s, (const unsigned short*)in,

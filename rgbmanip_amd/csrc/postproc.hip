@@ -605,9 +605,9 @@ int launch_postprocess(const float* nocs, const float* depth, const float* rot, 
                        void* scratch, size_t scratch_bytes) {
   RGBM_REQUIRE(P >= 2 && P <= PP_MAXP && (P % 2) == 0 && (PP_THREADS % (P / 2)) == 0, "postprocess needs even P<=1024 dividing 2048");
   // debug flags: 33554432 = generic (fp64 radix) selection only, 67108864 = guard band in every even-count pose (tests)
-  const int flags = ((g_debug_flags & (1 << 25)) ? PP_F_GENERIC : 0) | ((g_debug_flags & (1 << 26)) ? PP_F_GUARD : 0);
+  const int flags = ((g_debug_flags & DBG_PP_GENERIC_SELECT) ? PP_F_GENERIC : 0) | ((g_debug_flags & DBG_PP_GUARD) ? PP_F_GUARD : 0);
   const int G = scratch && !(flags & PP_F_GENERIC) ? postprocess_slices(B) : 1;
-  if (G > 1 && !(g_debug_flags & (1 << 23))) {        // debug flag 8388608: one-kernel form even when scratch is given (A/B)
+  if (G > 1 && !(g_debug_flags & DBG_PP_ONE_KERNEL)) {        // debug flag 8388608: one-kernel form even when scratch is given (A/B)
     RGBM_REQUIRE(scratch_bytes >= postprocess_scratch_bytes(B) && ((uintptr_t)scratch & 7) == 0, "postprocess scratch too small or misaligned");
     PPScratch* scr = reinterpret_cast<PPScratch*>(scratch);
     RGBM_CHECK_HIP(hipMemsetAsync(scr, 0, postprocess_scratch_bytes(B), s));

@@ -26,8 +26,6 @@
 
 namespace rgbm {
 
-extern int g_debug_flags;
-
 namespace {
 
 constexpr int PS_DMAX = 24;
@@ -619,7 +617,7 @@ int launch_prob_sparse(const void* u9, const void* c0, const void* w11_packed, c
   d.v0 = v0; d.Vc = Vc; d.B = B; d.P = P; d.D = D; d.H = H; d.W = W;
   const long long npts = (long long)Vc * P;
   RGBM_REQUIRE(npts > 0 && (npts + 3) / 4 < (1ll << 31), "prob_sparse grid out of range");
-  if (w11_taps != nullptr && !(g_debug_flags & (1 << 29))) {
+  if (w11_taps != nullptr && !(g_debug_flags & DBG_SPARSE_TAIL_R5)) {
     // the round-6 kernel (w11_taps: prob_sparse_pack's operands)
     RGBM_REQUIRE((long long)(D / 2) * (H / 2) * (W / 2) * 16 * 4 < (1ll << 31) && (long long)D * H * W * 8 * 4 < (1ll << 31), "prob_sparse view too large for 32-bit offsets");
     d.w11 = w11_taps;

@@ -145,4 +145,15 @@ nocs, dep, r, ch = f32(B, P, 3), f32(B, P), f32(B, 3, 3), np.zeros((B, P), np.in
 K, E, bbox, ts, valid = f64(B, 3, 3), f64(B, 4, 4), f64(B, 8, 3), f64(B, 8), np.zeros(B, np.int32)
 _lib.check(lib.rgbm_adapose_postprocess(B, P, 224, vp(nocs), vp(dep), vp(r), vp(ch), vp(K), vp(E), vp(bbox), vp(ts), vp(valid), None),
            "postprocess")
+
+# rgbm_conv_plan: the geometry half of a ConvDesc without device memory and the dispatch decision, for 256 CUs (no runtime call): a small
+# launch, a main + tail launch, a sub-pixel class of a transposed conv, an fp32 conv.  plan = [kernel, bch, bpix, parts, ...] (rgbm.h)
+plan = (C.c_int32 * 9)()
+for dtype, N, D, H, Cin, Cout, KD, k, sd, s, pd, p, dil, tr, res_mode, cls, kernels in (
+        (_lib.BF16, 2, 1, 28, 256, 256, 1, 3, 1, 1, 0, 2, 2, 0, 1, 0, (8,)), (_lib.BF16X3, 512, 1, 28, 256, 256, 1, 3, 1, 1, 0, 2, 2, 0, 1, 0, (7,)),
+        (_lib.F16, 2, 12, 28, 16, 8, 3, 3, 2, 2, 1, 1, 1, 1, 0, 5, (0,)), (_lib.F32, 2, 1, 28, 256, 256, 1, 3, 1, 1, 0, 2, 2, 0, 1, 0, (2, 3, 4))):
+    _lib.check(lib.rgbm_conv_plan(dtype, N, D, H, H, Cin, Cin, Cout, Cout, KD, k, k, sd, s, pd, p, dil, tr, 0, res_mode, 1, cls, 256, plan),
+               "conv_plan")
+    assert plan[0] in kernels and plan[7] == N * D * H * H, list(plan)
+assert lib.rgbm_conv_plan(_lib.BF16, 2, 1, 28, 28, 24, 24, 64, 64, 1, 3, 3, 1, 1, 0, 1, 1, 0, 0, 0, 0, 0, 256, plan) != 0      # 3 x 3 taps: Cin_pad must be a power of two
 print("ASAN_HOST_OK", runs, "configurations")

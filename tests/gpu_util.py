@@ -159,18 +159,9 @@ def conv_nd(dtype, x, w, **kw):
     return fetch(out)
 
 
-# ---------------------------------------------------------------- small-launch dispatch mirror
-# A restatement of the branch of conv_igemm_glds.hip::launch_dtype_g that picks the small-batch tiles (m32_small_choice) and of the K split
-# (conv_igemm_m32.inc::m32_ksplit_choice), for a conv at its defaults (uniform taps, aligned rows, gemm_kernel = 2, debug flags 0).  The
-# small-batch tests state the path they expect with it; tests/test_small_batch_dispatch.py checks that their cases reach every branch.
-
-WS_MIN_ROWS = 1024                  # ws_min_rows(): GEMM rows from which the persistent kernels (and these tiles) are used
-KSPLIT_MAX, KSPLIT_MINSTEPS = 4, 8  # M32_KSPLIT_MAX / M32_KSPLIT_MINSTEPS
-KSPLIT_FLOATS, KSPLIT_COUNTERS = 8 << 20, 16384
-
-
-def _cdiv(a, b):
-    return -(-a // b)
+# ---------------------------------------------------------------- what the library would launch
+PLAN_FIELDS = ("kernel", "bch", "bpix", "parts", "main_rows", "tail_bch", "identity", "M", "KT")      # rgbm_conv_plan's array (include/rgbm.h)
+KERNEL_WS_SLIM, KERNEL_M32, KERNEL_M32_SMALL = 4, 7, 8
 
 
 def device_n_cu(device=0):
@@ -178,76 +169,32 @@ def device_n_cu(device=0):
     return max(torch.cuda.get_device_properties(device).multi_processor_count // 8 * 8, 8)
 
 
-def m32_small_choice(M, Cout, n_cu, slim_ok):
-    """channel tile of the 128-pixel small launch (64 / 128 / 256), or 0 for 'keep the 64 x 256 tile of conv_igemm_ws_kernel'."""
-    p128, p256 = _cdiv(M, 128), _cdiv(M, 256)
-
-    def cost(tiles, kb):
-        return float(_cdiv(tiles, n_cu)) * (kb + 8)
-    best = cost(p256 * (Cout // 64), 40) if slim_ok else 1e30
-    pick = 0
-    for bch, kb in ((64, 24), (128, 32), (256, 48)):
-        if Cout % bch:
-            continue
-        c = cost(p128 * (Cout // bch), kb)
-        if c < best * 0.999:
-            best, pick = c, bch
-    return pick
-
-
-def m32_ksplit_choice(KT, tiles, n_cu, bch, n_waves=4):
-    """K parts of a small launch (1: no split)."""
-    if tiles <= 0 or bch > 128:
-        return 1
-    n = min(n_cu // tiles, KSPLIT_MAX)
-    while n > 1 and KT // n < KSPLIT_MINSTEPS:
-        n -= 1
-    if n < 2 or tiles * n * bch * 128 > KSPLIT_FLOATS or tiles * n_waves > KSPLIT_COUNTERS:
-        return 1
-    return n
-
-
-def small_launch_plan(M, Cout, KT, n_cu):
-    """(tile channels, tile pixels, K parts) of a 16-bit / split-pair conv with M GEMM rows, or None where the small-batch branch does
-    not apply (fp32, <= 64 channels, fewer than WS_MIN_ROWS rows, or enough tiles to fill the grid)."""
-    if Cout <= 64 or Cout % 64 or M < WS_MIN_ROWS:
-        return None
-    slim_tiles = _cdiv(M, 256) * (Cout // 64)
-    if Cout % 256 == 0 and _cdiv(M, 256) * (Cout // 256) < n_cu:
-        pick = m32_small_choice(M, Cout, n_cu, slim_tiles <= n_cu)
-        if pick:
-            return pick, 128, m32_ksplit_choice(KT, _cdiv(M, 128) * _cdiv(Cout, pick), n_cu, pick)
-    if Cout == 128 and _cdiv(M, 128) * 2 * 2 <= n_cu:
-        return 64, 128, m32_ksplit_choice(KT, _cdiv(M, 128) * 2, n_cu, 64)
-    if slim_tiles <= n_cu:
-        return 64, 256, 1
-    return None
-
-
 def conv_out_hw(H, W, k, stride, pad, dil):
     return (H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
+def conv_plan(dtype, N, Cin, H, W, Cout, k, stride, pad, dil, has_bias=False, res_mode=0, act=0, n_cu=0):
+    """rgbm_conv_plan for a 2-D conv as conv_nd launches it (channels padded the same way), under the process's current debug flags and
+    tuning; n_cu = 0 asks the current device, a positive value needs no GPU.  Returns the array as a dict (PLAN_FIELDS)."""
+    E = 4 if dtype in (_lib.F32, _lib.BF16X3) else 8
+    out = (C.c_int32 * len(PLAN_FIELDS))()
+    _lib.check(_lib.load().rgbm_conv_plan(dtype, N, 1, H, W, Cin, (Cin + E - 1) // E * E, Cout, (Cout + 3) // 4 * 4, 1, k, k, 1, stride, 0, pad,
+                                          dil, 0, int(has_bias), res_mode, act, 0, n_cu, out), "rgbm_conv_plan")
+    return dict(zip(PLAN_FIELDS, out))
+
+
 def conv_case_plan(case, dtype, n_cu):
-    """The mirror applied to a conv case (name, N, Cin, H, W, Cout, k, stride, pad, dil, bias, act, res_mode) as conv_nd launches it.
-    Returns a dict: tile (channels, pixels) or None, parts, KT, and the residual path of a small launch ('epilogue': the Cout = 128
-    tile adds it after the reduction; 'identity': 256-multiple channels add a pre-activation residual by identity K steps)."""
-    _, N, Cin, H, W, Cout, k, stride, pad, dil, _, _, res_mode = case
-    Ho, Wo = conv_out_hw(H, W, k, stride, pad, dil)
-    M = N * Ho * Wo
-    if dtype == _lib.F32:
-        return {"M": M, "KT": None, "tile": None, "parts": 1, "res": None}
-    E = 4 if dtype == _lib.BF16X3 else 8
-    BK = 8 * E
-    cin_pad = _cdiv(Cin, E) * E
-    assert k == 1 or cin_pad & (cin_pad - 1) == 0, "multi-tap convs need a power-of-two Cin"
-    KT = _cdiv(k * k * cin_pad, BK)
-    plan = small_launch_plan(M, Cout, KT, n_cu)
-    tile, parts = (plan[:2], plan[2]) if plan else (None, 1)
-    res = None
-    if tile is not None and tile[1] == 128 and res_mode:
-        res = "identity" if Cout % 256 == 0 and res_mode == 1 else "epilogue"
-    return {"M": M, "KT": KT, "tile": tile, "parts": parts, "res": res}
+    """The library's plan for a conv case (name, N, Cin, H, W, Cout, k, stride, pad, dil, bias, act, res_mode) as conv_nd launches it.
+    Returns a dict: tile (channels, pixels) of a small launch - the 128-pixel tiles of conv_igemm_m32_kernel, or the 64 x 256 tile of
+    conv_igemm_ws_kernel kept for a layer of more than 64 channels - else None; parts; M; KT; and the residual path of a 128-pixel small
+    launch ('epilogue': the Cout = 128 tile adds it after the reduction; 'identity': 256-multiple channels add a pre-activation residual
+    by identity K steps)."""
+    _, N, Cin, H, W, Cout, k, stride, pad, dil, has_bias, act, res_mode = case
+    p = conv_plan(dtype, N, Cin, H, W, Cout, k, stride, pad, dil, has_bias, res_mode, act, n_cu)
+    small = p["kernel"] == KERNEL_M32_SMALL
+    tile = (p["bch"], p["bpix"]) if small or (p["kernel"] == KERNEL_WS_SLIM and Cout > 64) else None
+    res = ("identity" if p["identity"] else "epilogue") if small and res_mode else None
+    return {"M": p["M"], "KT": p["KT"], "tile": tile, "parts": p["parts"], "res": res}
 
 
 def _backbone_small_cases():

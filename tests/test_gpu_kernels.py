@@ -231,7 +231,7 @@ def test_conv2d_k_split_is_stable_over_many_runs(dtype):
 
 
 SAT_SMALL_CASES = [
-    # the small-batch launches (B = 1 .. 4 poses at 28 x 28; tile and K parts on 256 CUs from tests/gpu_util.py::small_launch_plan):
+    # the small-batch launches (B = 1 .. 4 poses at 28 x 28; tile and K parts on 256 CUs from rgbm_conv_plan, tests/gpu_util.py::conv_plan):
     # layer2's 128-channel layer on the 64 x 128 K-split tile with its residual in the epilogue (2 parts), layer3 on the 64 x 128 tile
     # (4 parts, residual by identity K steps), layer4 on the 128 x 128 and 256 x 128 tiles, a post-activation residual behind 3 parts
     ("sat_l2_res_n2", 2, 128, 28, 28, 128, 3, 1, 1, 1, False, 1, 1),

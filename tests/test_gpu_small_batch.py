@@ -1,9 +1,9 @@
 """-m gpu: the paths that only run at deployment batch sizes (B = 1 .. 8 poses; the reference runs one pose per env and ships 8 envs)
 against high-precision references.
 
- * conv level: the small-launch tiles of conv_igemm_glds.hip::launch_dtype_g (64 / 128 / 256-channel x 128-pixel tiles, the kept
+ * conv level: the small-launch tiles of conv_plan.cpp::plan_conv (64 / 128 / 256-channel x 128-pixel tiles, the kept
    64 x 256 tile) and the K split of conv_igemm_m32.inc, at ResNet-34 layer2..4's own shapes (28 x 28, 2 .. 16 views) and synthetic
-   ones, against F.conv2d in float64 on the same rounded operands; the expected path comes from the dispatch mirror in gpu_util.py;
+   ones, against F.conv2d in float64 on the same rounded operands; the expected path comes from the library (rgbm_conv_plan);
  * network level: AdaPoseNet at B = 1, 3, 4, 5, 8 against the CPU oracle pose by pose, in every storage type, and the estimator's
    default cfg at B = 8 against the oracle pipeline;
  * per-sample BatchNorm3d (norm_mode = 1): its kernels against float64 at small volumes (constant channels included), and the network
@@ -85,11 +85,11 @@ def _unsplit(dtype, x, w, **kw):
 @pytest.mark.parametrize("dtype", DT16, ids=DT16_IDS)
 @pytest.mark.parametrize("case", SMALL_CONV_CASES, ids=[c[0] for c in SMALL_CONV_CASES])
 def test_small_launch_conv_vs_float64(case, dtype):
-    """Every small-batch conv within the storage type's TOL of F.conv2d in float64 on the same rounded operands.  Where the mirror
-    predicts a K split: four default runs are bit-identical (whichever part arrives last adds the parts in the same order), the
+    """Every small-batch conv within the storage type's TOL of F.conv2d in float64 on the same rounded operands.  Where the library
+    plans a K split: four default runs are bit-identical (whichever part arrives last adds the parts in the same order), the
     split result is within the storage type's rounding of the unsplit launch, and that one is within TOL of float64 too.  (The unsplit
     launch, debug flag 16384, keeps the 64 / 128 / 256 x 128 tile for 256-multiple channels; for Cout = 128 the flag also turns off the
-    64 x 128 tile, conv_igemm_glds.hip::launch_dtype_g, so there it is the 64 x 256 tile of conv_igemm_ws_kernel.)"""
+    64 x 128 tile, conv_plan.cpp::plan_conv, so there it is the 64 x 256 tile of conv_igemm_ws_kernel.)"""
     x, w, b, res = _operands(case, dtype)
     ref = _ref64(case, x, w, b, res)
     kw = _kw(case, x, w, b, res)
@@ -105,7 +105,7 @@ def test_small_launch_conv_vs_float64(case, dtype):
         assert torch.isfinite(y1).all() and rel_err(y1, ref) < TOL[dtype], (case[0], "unsplit", rel_err(y1, ref))
         assert rel_err(y, y1) < SPLIT_VS_UNSPLIT[dtype], (case[0], plan, rel_err(y, y1))
         if dtype != _lib.BF16X3:        # the split sums in another order: in 16-bit storage some outputs round differently
-            assert not torch.equal(y, y1), (case[0], plan, "the mirror predicts a K split, but the launch did not split")
+            assert not torch.equal(y, y1), (case[0], plan, "the plan asks for a K split, but the launch did not split")
 
 
 def _nan_cases():
