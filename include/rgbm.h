@@ -438,6 +438,32 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
                                const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
                                size_t workspace_bytes, const rgbm_adapose_out* out, void* stream, int32_t* n_nodes, int32_t* captured);
 int rgbm_adapose_graph_clear(rgbm_adapose_t* h);
+/* Feature cache: the forward split where the PSPNet ends.  A view's 32-channel feature map depends on its image alone (shared weights,
+ * no Dropout2d in eval mode), so a caller that meets a frame in two forwards - the controller loop pairs frame t with frame t - 1 in
+ * every step - computes the map once, keeps it in a pool of records it owns, and runs the rest of the forward from slot tables.
+ * rgbm_adapose_feature_bytes: size of one view's record = exactly what the stages behind the PSPNet read with the handle's current
+ *   options: the f16 (option sweep_f16 = 0: bf16) map for bf16 nets, the fp16 map for fp16 nets, the fp32 map for fp32 and bf16x3
+ *   nets; bf16x3 nets on the paths that still read the split-pair map (norm_mode 1, cost_impl < 3) keep that map in front of the
+ *   fp32 one (twice the size).  Query it after the options are set; records written under other options are not interchangeable.
+ * rgbm_adapose_features: the PSPNet - the launches and arithmetic of rgbm_adapose_forward - on V >= 1 views (odd V included) of one
+ *   array img [V,3,224,224] fp32; view v's record goes to pool + slots_dev[v] * feature_bytes.  pool: pool_records records, 16-byte
+ *   aligned.  workspace: rgbm_adapose_features_workspace_bytes(V) bytes, 256-byte aligned (the one of rgbm_adapose_workspace_bytes(B)
+ *   serves V <= 2 B views).
+ * rgbm_adapose_forward_cached: rgbm_adapose_forward with the PSPNet replaced by reading records slot1_dev[b] / slot2_dev[b] ([B] int32
+ *   each) for the view-1 / view-2 crop of pose b; every option (view2_heads, sparse_dec, chunking, norm_mode ...) holds as in the plain
+ *   forward, and the workspace is that of rgbm_adapose_workspace_bytes(B).  With records written by one rgbm_adapose_features call on
+ *   the 2 B views in [view1 batch ; view2 batch] order the outputs are bit-identical to rgbm_adapose_forward's.
+ * Refused (error through rgbm_last_error, nothing launched): a handle with Dropout2d on (set_dropout p > 0 or explicit masks pending) -
+ *   the masks are per pose and per forward, a kept map would change the as-shipped semantics.  A slot outside [0, pool_records) is
+ *   checked on the device: features writes nothing for it; forward_cached reads nothing, and that pose's ten outputs are NaN (the
+ *   other poses are unaffected).  Not provided: a graph-replayed or split-stream cached forward. */
+int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes);
+int rgbm_adapose_features_workspace_bytes(rgbm_adapose_t* h, int V, size_t* bytes);
+int rgbm_adapose_features(rgbm_adapose_t* h, int V, const float* img, const int32_t* slots_dev, void* pool, int pool_records,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int pool_records, const int32_t* slot1_dev,
+                                const int32_t* slot2_dev, const int32_t* choose1, const int32_t* choose2, const float* P1, const float* P2,
+                                const float* depths, void* workspace, size_t workspace_bytes, const rgbm_adapose_out* out, void* stream);
 int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* name, float* out_dev, size_t capacity,
                        size_t* n_elems, void* stream);
 

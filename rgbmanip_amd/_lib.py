@@ -115,6 +115,10 @@ SIGNATURES = {
     "rgbm_adapose_forward_graph": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32)]),
     "rgbm_adapose_graph_clear": (_i, [_vp]),
+    "rgbm_adapose_feature_bytes": (_i, [_vp, C.POINTER(_sz)]),
+    "rgbm_adapose_features_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),
+    "rgbm_adapose_features": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "rgbm_adapose_forward_cached": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp]),
     "rgbm_adapose_fetch": (_i, [_vp, _i, _vp, C.c_char_p, _vp, _sz, C.POINTER(_sz), _vp]),
     "rgbm_adapose_postprocess": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_adapose_postprocess_scratch_bytes": (_i, [_i, C.POINTER(_sz)]),

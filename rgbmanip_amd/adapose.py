@@ -271,6 +271,87 @@ class AdaPoseNet:
 
     __call__ = forward
 
+    # ------------------------------------------------------------------ feature cache (include/rgbm.h: rgbm_adapose_features)
+    @property
+    def feature_bytes(self) -> int:
+        """Size of one view's feature record with the current options: what the stages behind the PSPNet read of it."""
+        n = C.c_size_t()
+        _lib.check(self.lib.rgbm_adapose_feature_bytes(self._h, C.byref(n)), "rgbm_adapose_feature_bytes")
+        return n.value
+
+    def feature_pool(self, records: int) -> torch.Tensor:
+        """An uninitialised pool of `records` feature records (uint8 CUDA tensor, [records, feature_bytes])."""
+        return torch.empty(int(records), self.feature_bytes, dtype=torch.uint8, device=self.device)
+
+    def _workspace_at_least(self, need: int):
+        if self._ws is None or self._ws.numel() < need + 256:
+            self._ws = None
+            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            self._ws_B = None                         # sized by bytes, not by a batch: a plain forward sizes its own again
+        off = (-self._ws.data_ptr()) % 256
+        return self._ws.data_ptr() + off, self._ws.numel() - off
+
+    def _pool_records(self, pool) -> int:
+        if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()):
+            raise ValueError("feature pool: a contiguous uint8 CUDA tensor (AdaPoseNet.feature_pool)")
+        fb = self.feature_bytes
+        if pool.numel() < fb or pool.numel() % fb:
+            raise ValueError(f"feature pool: {pool.numel()} bytes is not a whole number of {fb}-byte records")
+        return pool.numel() // fb
+
+    def features(self, img, slots, pool, stream=None):
+        """Run the PSPNet on the V >= 1 views img [V,3,224,224] and write view v's feature record to record slots[v] of `pool`
+        (a slot outside the pool is skipped on the device).  Refused with Dropout2d on."""
+        img = self._prep(img, torch.float32)
+        slots = self._prep(slots, torch.int32)
+        V = img.shape[0]
+        assert img.shape == (V, 3, 224, 224) and slots.shape == (V,), (img.shape, slots.shape)
+        records = self._pool_records(pool)
+        n = C.c_size_t()
+        _lib.check(self.lib.rgbm_adapose_features_workspace_bytes(self._h, V, C.byref(n)), "rgbm_adapose_features_workspace_bytes")
+        ws_ptr, ws_bytes = self._workspace_at_least(n.value)
+        if self.poison_workspace:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                self._ws.fill_(0xFF)
+        _lib.check(self.lib.rgbm_adapose_features(self._h, V, _lib.ptr(img), _lib.ptr(slots), _lib.ptr(pool), records, C.c_void_p(ws_ptr),
+                                                  ws_bytes, _lib.stream_ptr(stream)), "rgbm_adapose_features")
+        self._last_feat = (img, slots)                    # keep inputs alive until the stream has consumed them
+
+    def forward_cached(self, pool, slot1, slot2, view1_choose, view2_choose, view1_proj, view2_proj, depth_values, stream=None):
+        """`forward` with the two crops of pose b read from feature records slot1[b] / slot2[b] of `pool` instead of computed from
+        images; returns the same output dict.  A pose with a slot outside the pool gets NaN outputs.  Refused with Dropout2d on."""
+        s1 = self._prep(slot1, torch.int32)
+        s2 = self._prep(slot2, torch.int32)
+        ch1 = self._prep(view1_choose, torch.int32)
+        ch2 = self._prep(view2_choose, torch.int32)
+        P1 = self._prep(view1_proj, torch.float32)
+        P2 = self._prep(view2_proj, torch.float32)
+        dep = self._prep(depth_values, torch.float32)
+        B = ch1.shape[0]
+        assert s1.shape == (B,) and s2.shape == (B,) and ch1.shape == (B, 1024) and ch2.shape == ch1.shape
+        assert P1.shape == (B, 4, 4) and P2.shape == (B, 4, 4) and dep.shape == (B, 24)
+        records = self._pool_records(pool)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        out = {
+            "view1_nocs": torch.empty(B, 1024, 3, **f32), "view2_nocs": torch.empty(B, 1024, 3, **f32),
+            "view1_depth": torch.empty(B, 1024, **f32), "view2_depth": torch.empty(B, 1024, **f32),
+            "view1_r": torch.empty(B, 3, 3, **f32), "view2_r": torch.empty(B, 3, 3, **f32),
+            "view1_t": torch.empty(B, 3, **f32), "view2_t": torch.empty(B, 3, **f32),
+            "view1_s": torch.empty(B, 3, **f32), "view2_s": torch.empty(B, 3, **f32),
+        }
+        o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
+        ws_ptr, ws_bytes = self._workspace_at_least(self.workspace_bytes(B))
+        if self.poison_workspace:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                self._ws.fill_(0xFF)
+        _lib.check(self.lib.rgbm_adapose_forward_cached(self._h, B, _lib.ptr(pool), records, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(ch1),
+                                                        _lib.ptr(ch2), _lib.ptr(P1), _lib.ptr(P2), _lib.ptr(dep), C.c_void_p(ws_ptr), ws_bytes,
+                                                        C.byref(o), _lib.stream_ptr(stream)), "rgbm_adapose_forward_cached")
+        self._last_split = False
+        self._last_graph = False
+        self._last = (s1, s2, ch1, ch2, P1, P2, dep)
+        return out
+
     def fetch(self, B: int, name: str, max_elems: int) -> torch.Tensor:
         """Debug/test access to a named intermediate of the last forward (fp32, flat)."""
         if self._last_split:

@@ -141,6 +141,11 @@ class ControlInterface:
         self.gt_bbox = z(T, N, 8, 3)
         self.available_num = z(N, dtype=torch.int32)
         self.accumulate_steps = 0
+        # feature cache of the estimator (cfg hip_feature_cache): queue rows written since the last estimation (host data), and every
+        # kept feature map is forgotten with the queue
+        self._fresh_rows = []
+        if hasattr(self.estimator, "invalidate_features"):
+            self.estimator.invalidate_features()
 
     def _dev(self, x, dtype):
         return torch.as_tensor(x).to(device=self.device, dtype=dtype)
@@ -160,6 +165,7 @@ class ControlInterface:
     # ------------------------------------------------------------------ rl_pose.py:118-150
     def add_view(self, image, cam_pose):
         k = self.accumulate_steps % self.max_steps
+        self._fresh_rows.append(k)
         cam = image["camera0"]
         mask = (self._dev(cam["Mask"], torch.uint8) != 0).to(torch.uint8).contiguous()
         self.image_queue[k] = self._dev(cam["Color"], torch.float32)
@@ -231,8 +237,13 @@ class ControlInterface:
             # the estimator reads the selected frames straight out of the queue: no [N,480,640,3] gather copies
             env = torch.arange(N, device=self.device)
             fmap = [torch.where(has[s], idx[s] * N + env, torch.full_like(env, -1)).to(torch.int32) for s in (0, 1)]
+            kw = {}
+            if (getattr(self.estimator, "cfg", None) or {}).get("hip_feature_cache"):
+                # the estimator keeps the PSPNet feature map of every queue entry: only the rows written since the last estimation are new
+                kw["fresh"] = [e for k in dict.fromkeys(self._fresh_rows) for e in range(k * N, (k + 1) * N)]
+                self._fresh_rows = []
             bbox = self.estimator.estimate_device_indexed(K[0], self.image_queue.view(T * N, self.H, self.W, 3),
-                                                          self.mask_queue.view(T * N, self.H, self.W), E[0], E[1], fmap[0], fmap[1])
+                                                          self.mask_queue.view(T * N, self.H, self.W), E[0], E[1], fmap[0], fmap[1], **kw)
         else:
             rgb = [self._gather(self.image_queue, idx[s], has[s]) for s in (0, 1)]
             mask = [self._gather(self.mask_queue, idx[s], has[s]) for s in (0, 1)]

@@ -397,12 +397,15 @@ int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* im
   int H = S / 2, W = S / 2;
   if (stem && stem_w) {
     // NCHW fp32 images -> conv1 + ReLU + max-pool in one kernel (no padded copy, no 112 x 112 x 64 tensor)
-    if (int rc = launch_stem(dtype, img1, img2, stem_w, bf.lb[0], V / 2, V, S, s)) return rc;
+    // img2 == nullptr (features()): all V views, any V >= 1, lie in img1
+    if (img2 == nullptr) { if (int rc = launch_stem_views(dtype, img1, stem_w, bf.lb[0], V, S, s)) return rc; }
+    else if (int rc = launch_stem(dtype, img1, img2, stem_w, bf.lb[0], V / 2, V, S, s)) return rc;
   } else {
     const size_t es = dtype_size(dtype);
-    const int B = V / 2;
+    const int B = img2 == nullptr ? V : V / 2;
     if (int rc = launch_nchw_to_nhwc_pad(dtype, img1, bf.imgpad, B, 3, S, S, img_cpad, s)) return rc;
-    if (int rc = launch_nchw_to_nhwc_pad(dtype, img2, (char*)bf.imgpad + (size_t)B * S * S * img_cpad * es, B, 3, S, S, img_cpad, s)) return rc;
+    if (img2 != nullptr)
+      if (int rc = launch_nchw_to_nhwc_pad(dtype, img2, (char*)bf.imgpad + (size_t)B * S * S * img_cpad * es, B, 3, S, S, img_cpad, s)) return rc;
     if (int rc = conv1.run(bf.imgpad, bf.c1, V, 1, S, S, 64, nullptr, 0, nullptr, 0, s)) return rc;
     if (int rc = launch_maxpool3x3s2(dtype, bf.c1, bf.lb[0], V, H, W, 64, s)) return rc;
   }
@@ -652,15 +655,20 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   if (int rc = pspnet(bf, V, img1, img2, s, drop)) return rc;
   if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
   // bf16x3 nets: everything that GATHERS from the feature map (plane sweep, point heads) reads a plain fp32 copy of it
+  if (dtype == BF16X3 && !feat_f32_only())
+    if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * S * S * 32, s)) return rc;
+  if (stop_after == 1) return 0;
+  (void)VP; (void)P; (void)D;
+  return heads(bf, B, depths, out, s, stop_after);
+}
+
+// Everything behind the PSPNet: reads the feature map(s) in bf.feat / bf.featf, bf.homog, bf.choose (forward() and forward_cached() fill them)
+int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs& out, hipStream_t s, int stop_after) const {
+  const int V = 2 * B, P = n_pts, S = img, D = n_depth;
   const void* featg = bf.feat;
   int fdt = dtype;
-  if (dtype == BF16X3) {
-    if (!feat_f32_only())
-      if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * S * S * 32, s)) return rc;
-    featg = bf.featf; fdt = F32;
-  }
+  if (dtype == BF16X3) { featg = bf.featf; fdt = F32; }
   if (feat_f16()) fdt = F16;
-  if (stop_after == 1) return 0;
 
   const int Vh = view2_heads ? V : B;      // views that get heads: both crops of every pose, or the view-1 crops only (option view2_heads)
   // ---- per-point NOCS branch (network_v5.py:432-444) ----
@@ -718,8 +726,78 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
     float* const os[2] = {out.s1, out.s2};
     if (int rc = launch_stage_out(bf.nocs4, bf.depth, bf.R, bf.tv, bf.sv, on, od, orr, ot, os, B, P, view2_heads, s)) return rc;
   }
-  (void)VP;
   return 0;
+}
+
+// ---- feature cache (feature_cache.hip, DESIGN.md "Feature cache") ----
+// A record is what heads() reads of one view's feature map: bf.feat for 16-bit and fp32 storage, bf.featf for split pairs - preceded by
+// the split-pair map where something still reads it (per-sample BN, the halo-tile conv0 and the materialised volume do).
+int AdaPose::feature_parts(const Buffers& bf, FeaturePart parts[2]) const {
+  const size_t one = (size_t)img * img * 32;
+  if (dtype != BF16X3) { parts[0] = {bf.feat, 0, one * dtype_size(dtype)}; return 1; }
+  if (feat_f32_only()) { parts[0] = {bf.featf, 0, one * 4}; return 1; }
+  parts[0] = {bf.feat, 0, one * 4};
+  parts[1] = {bf.featf, one * 4, one * 4};
+  return 2;
+}
+
+size_t AdaPose::feature_bytes() const {
+  Buffers bf{};
+  FeaturePart parts[2];
+  const int n = feature_parts(bf, parts);
+  return parts[n - 1].off + parts[n - 1].bytes;
+}
+
+size_t AdaPose::features_workspace_bytes(int V) const { return workspace_bytes((V + 1) / 2); }
+
+int AdaPose::features(int V, const float* images, const int* slots, void* pool, int pool_records, void* workspace, size_t workspace_size,
+                      hipStream_t s) const {
+  RGBM_REQUIRE(V > 0 && pool_records > 0, "features: views and pool records");
+  RGBM_REQUIRE(!drop_active(), "features: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would change "
+               "what the net computes); the feature cache needs set_dropout(0)");
+  RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "features: workspace must be 256-byte, pool 16-byte aligned");
+  const size_t need = features_workspace_bytes(V);
+  RGBM_REQUIRE(workspace_size >= need, "features workspace too small: need " + std::to_string(need));
+  Arena A(workspace, workspace_size);
+  Buffers bf;
+  plan((V + 1) / 2, A, bf);
+  if (int rc = pspnet(bf, V, images, nullptr, s, nullptr)) return rc;
+  if (dtype == BF16X3 && !feat_f32_only())
+    if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * img * img * 32, s)) return rc;
+  FeaturePart parts[2];
+  const int np = feature_parts(bf, parts);
+  const size_t rec = feature_bytes();
+  for (int i = 0; i < np; ++i)
+    if (int rc = launch_feature_store(parts[i].buf, pool, slots, V, pool_records, parts[i].off, parts[i].bytes, rec, s)) return rc;
+  return 0;
+}
+
+int AdaPose::forward_cached(int B, const void* pool, int pool_records, const int* slot1, const int* slot2, const int* choose1,
+                            const int* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
+                            size_t workspace_size, const Outputs& out, hipStream_t s) const {
+  RGBM_REQUIRE(B > 0 && pool_records > 0, "forward_cached: batch and pool records");
+  RGBM_REQUIRE(!drop_active(), "forward_cached: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would "
+               "change what the net computes); the feature cache needs set_dropout(0)");
+  RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "forward_cached: workspace must be 256-byte, pool 16-byte aligned");
+  RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
+  const size_t need = workspace_bytes(B);
+  RGBM_REQUIRE(workspace_size >= need, "workspace too small: need " + std::to_string(need));
+  Arena A(workspace, workspace_size);
+  Buffers bf;
+  plan(B, A, bf);
+  const int V = 2 * B, P = n_pts;
+  if (int rc = launch_stage_in(P1, P2, choose1, choose2, bf.Pviews, bf.choose, B, P, s)) return rc;
+  FeaturePart parts[2];
+  const int np = feature_parts(bf, parts);
+  const size_t rec = feature_bytes();
+  for (int i = 0; i < np; ++i)
+    if (int rc = launch_feature_gather(pool, parts[i].buf, slot1, slot2, B, pool_records, parts[i].off, parts[i].bytes, rec, s)) return rc;
+  if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
+  if (int rc = heads(bf, B, depths, out, s, 0)) return rc;
+  // a slot outside the pool: that pose's ten outputs are NaN (nothing was read for it; every other pose is what a clean call gives)
+  float* const o[10] = {out.nocs1, out.nocs2, out.depth1, out.depth2, out.r1, out.r2, out.t1, out.t2, out.s1, out.s2};
+  const int per[10] = {3 * P, 3 * P, P, P, 9, 9, 3, 3, 3, 3};
+  return launch_feature_bad_slot_nan(slot1, slot2, B, pool_records, o, per, s);
 }
 
 }  // namespace rgbm

@@ -112,10 +112,25 @@ struct AdaPose {
   int forward(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
               const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
               hipStream_t s, int stop_after = 0) const;
+  // Feature cache: the forward split at the PSPNet's output.  features() runs the PSPNet on V >= 1 views of one image array
+  // [V][3][img][img] and writes view v's record (feature_bytes() long) to pool + slots[v] * feature_bytes(); forward_cached() is
+  // forward() with the PSPNet replaced by reading records slot1[b] / slot2[b].  Both refuse a net with Dropout2d on.  A slot outside
+  // [0, pool_records) is neither written nor read; forward_cached() returns NaN outputs for such a pose.
+  size_t feature_bytes() const;
+  size_t features_workspace_bytes(int V) const;
+  int features(int V, const float* images, const int* slots, void* pool, int pool_records, void* workspace, size_t workspace_size,
+               hipStream_t s) const;
+  int forward_cached(int B, const void* pool, int pool_records, const int* slot1, const int* slot2, const int* choose1, const int* choose2,
+                     const float* P1, const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
+                     hipStream_t s) const;
+  struct FeaturePart { void* buf; size_t off, bytes; };      // a feature buffer of the workspace and its place inside a record
+  int feature_parts(const Buffers& bf, FeaturePart parts[2]) const;
+  int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, hipStream_t s, int stop_after) const;
   mutable int last_f_index = 0;   // which rotating buffer holds the layer4 output (debug fetch)
 
   // exposed for layer-level tests
   int plan(int B, Arena& A, Buffers& bf) const;
+  // img2 == nullptr: all V views (any V >= 1) lie in img1
   int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, hipStream_t s, const float* drop = nullptr) const;
   int cost_volume(const Buffers& bf, int V, int B, const float* depths, hipStream_t s) const;
   int chunk_views(int V) const;

@@ -186,6 +186,32 @@ int rgbm_adapose_forward(rgbm_adapose_t* h, int B, const float* img1, const floa
   return rgbm_adapose_forward_ex(h, B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, out, 0, stream);
 }
 
+int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes) {
+  RGBM_REQUIRE(h && bytes, "feature_bytes arguments");
+  *bytes = h->net.feature_bytes();
+  return 0;
+}
+
+int rgbm_adapose_features_workspace_bytes(rgbm_adapose_t* h, int V, size_t* bytes) {
+  RGBM_REQUIRE(h && bytes && V > 0, "features_workspace_bytes arguments");
+  *bytes = h->net.features_workspace_bytes(V);
+  return 0;
+}
+
+int rgbm_adapose_features(rgbm_adapose_t* h, int V, const float* img, const int32_t* slots_dev, void* pool, int pool_records,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  RGBM_REQUIRE(h && img && slots_dev && pool && workspace, "features arguments");
+  return h->net.features(V, img, slots_dev, pool, pool_records, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int pool_records, const int32_t* slot1_dev,
+                                const int32_t* slot2_dev, const int32_t* choose1, const int32_t* choose2, const float* P1, const float* P2,
+                                const float* depths, void* workspace, size_t workspace_bytes, const rgbm_adapose_out* out, void* stream) {
+  RGBM_REQUIRE(h && pool && slot1_dev && slot2_dev && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward_cached arguments");
+  return h->net.forward_cached(B, pool, pool_records, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, workspace_bytes,
+                               to_out(out), (hipStream_t)stream);
+}
+
 int rgbm_adapose_graph_clear(rgbm_adapose_t* h) {
   RGBM_REQUIRE(h, "graph_clear arguments");
   for (auto& g : h->graphs) drop_graph(g);

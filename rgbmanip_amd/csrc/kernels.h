@@ -59,6 +59,19 @@ int launch_f32_to_f16(const float* in, void* out, long long n, hipStream_t s);
 // ResNet stem in one kernel (stem.hip): NCHW fp32 images -> maxpool3x3s2(relu(conv7x7s2)) [V][S/4][S/4][64]
 void stem_pack(const float* w, std::vector<float>& packed);
 int launch_stem(int dtype, const float* img1, const float* img2, const void* wpk, void* out, int B, int V, int S, hipStream_t s);
+// the same kernel on V views (any V >= 1) of ONE image array [V][3][S][S]
+int launch_stem_views(int dtype, const float* img, const void* wpk, void* out, int V, int S, hipStream_t s);
+// feature_cache.hip — records of the PSPNet's feature map in a caller-owned pool.  A record is `record_bytes` long; a part of it
+// ([part_off, part_off + part_bytes), all multiples of 16) is copied per launch.  store: view v of `src` ([V][part_bytes]) -> record
+// slots[v]; gather: record slot1[b] / slot2[b] -> view b / B + b of `dst` ([2B][part_bytes]).  A slot outside [0, pool_records) is
+// neither written nor read: the gather fills the view with zeros and launch_feature_bad_slot_nan turns the pose's outputs into NaN.
+int launch_feature_store(const void* src, void* pool, const int* slots, int V, int pool_records, size_t part_off, size_t part_bytes,
+                         size_t record_bytes, hipStream_t s);
+int launch_feature_gather(const void* pool, void* dst, const int* slot1, const int* slot2, int B, int pool_records, size_t part_off,
+                          size_t part_bytes, size_t record_bytes, hipStream_t s);
+// out[k]: the k-th output tensor [B][per_pose[k]] fp32
+int launch_feature_bad_slot_nan(const int* slot1, const int* slot2, int B, int pool_records, float* const out[10], const int per_pose[10],
+                                hipStream_t s);
 int launch_f32_to_bx3(const float* in, void* out, long long n, hipStream_t s);     // plain fp32 -> split pairs (n % 4 == 0; in place allowed)
 int launch_view_linear(const float* x, const float* W, const float* bias, float* out, int V, int I, int O, int ldw, int i0,
                        int relu, hipStream_t s);

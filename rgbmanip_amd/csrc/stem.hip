@@ -223,4 +223,14 @@ int launch_stem(int dtype, const float* img1, const float* img2, const void* wpk
   return launch_t<bx3_t, 4>(img1, img2, wpk, out, B, V, S, s);
 }
 
+// One image array [V][3][S][S] of any V >= 1 views (the feature cache computes the views of the frames that are new): the same kernel,
+// told that every view lies in the first array.
+int launch_stem_views(int dtype, const float* img, const void* wpk, void* out, int V, int S, hipStream_t s) {
+  RGBM_REQUIRE(dtype == BF16 || dtype == F16 || dtype == BF16X3, "stem kernel: 16-bit or split-pair storage");
+  RGBM_REQUIRE(S % (4 * kPT) == 0 && V > 0 && img && wpk && out, "stem kernel geometry");
+  if (dtype == BF16) return launch_t<unsigned short, 8>(img, img, wpk, out, V, V, S, s);
+  if (dtype == F16) return launch_t<f16_t, 8>(img, img, wpk, out, V, V, S, s);
+  return launch_t<bx3_t, 4>(img, img, wpk, out, V, V, S, s);
+}
+
 }  // namespace rgbm

@@ -165,6 +165,17 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         self.view2_heads = bool(cfg.get("hip_view2_heads", not cfg.get("direct_regression", True) and not cfg.get("use_depth", True)))
         # hip_dropout / hip_dropout_seed / hip_as_shipped (dropout_cfg): PSPNet's Dropout2d, seeded, fresh masks on every forward
         norm_mode, drop_p, drop_seed = dropout_cfg(cfg)
+        # hip_feature_cache (default off): `estimate_device_indexed(..., fresh=...)` keeps every pool frame's PSPNet feature map in a
+        # record pool and runs the PSPNet only on the frames named fresh (DESIGN.md "Feature cache").  Dropout2d draws its masks per pose
+        # and per forward, so a kept map would change what the as-shipped estimator computes: the combination is refused
+        self.feature_cache = bool(cfg.get("hip_feature_cache", False))
+        if self.feature_cache and drop_p > 0:
+            raise ValueError("AdaPoseEstimator_v5: hip_feature_cache keeps feature maps across forwards, Dropout2d (hip_dropout / "
+                             f"hip_as_shipped: p={drop_p}) draws fresh masks on every forward; turn one of them off")
+        self.feature_views_computed = 0       # views the PSPNet has run on through this estimator's device paths
+        self._feat_pool = None                # [M + 1, feature_bytes]: one record per frame-pool entry; record M = the all-zero crop's map
+        self._slot_valid = None               # [M + 1] bool on the device: record holds the map of the entry's current frame (M: always)
+        self._fresh_dev = {}
         self.estimator = net if net is not None else AdaPoseNet(state_dict, dtype=self.dtype, device=device,
                                                                 norm_mode=norm_mode, dropout=drop_p, dropout_seed=drop_seed,
                                                                 graph=bool(cfg.get("hip_graph", False)),
@@ -445,21 +456,72 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         b = prepare_inputs(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=frame0)
         return self._estimate_prepared(a, b, E1, E2, Kd)
 
-    def estimate_device_indexed(self, K, rgb_pool, mask_pool, E1, E2, map1, map2):
+    def estimate_device_indexed(self, K, rgb_pool, mask_pool, E1, E2, map1, map2, fresh=None):
         """`estimate_device` reading the two views of sample i from entries map1[i] / map2[i] of a frame pool
         (rgb_pool [M,H,W,3] float32, mask_pool [M,H,W] uint8 — e.g. the controller's view queue) instead of from gathered
         batches; a negative entry means "no such view" (the reference hands an all-zero frame over, which is skipped).
-        K [N,3,3] (both views use it, interface_v5.py:213-227), E1 / E2 [N,4,4]."""
+        K [N,3,3] (both views use it, interface_v5.py:213-227), E1 / E2 [N,4,4].
+
+        With cfg hip_feature_cache, `fresh` (a host sequence of pool entries; None = today's path) names the entries whose frames were
+        written since their features were last computed: the PSPNet runs on exactly those len(fresh) views, their records are marked
+        valid, and the network runs from the records of map1 / map2.  A pose that refers to an entry without a valid record gets
+        `default_bbox`.  The caller owns the bookkeeping: an entry rewritten without being named keeps its old frame's map
+        (`invalidate_features` forgets all of them)."""
         S = self.cfg["img_size"]
         wp = self._pnp_branch()
+        cached = None
+        if self.feature_cache and fresh is not None:
+            cached = self._update_features(rgb_pool, mask_pool, S, fresh, map1, map2)
         a = prepare_inputs(rgb_pool, mask_pool, K, S, 1024, self.prepare_seed, frame_map=map1, want_pts2d=wp)
         b = prepare_inputs(rgb_pool, mask_pool, K, S, 1024, self.prepare_seed + 1, frame_map=map2, want_pts2d=wp)
-        return self._estimate_prepared(a, b, E1, E2, K)
+        return self._estimate_prepared(a, b, E1, E2, K, cached=cached)
+
+    def invalidate_features(self):
+        """Forget every cached feature map (the frame pool is about to be rewritten: `ControlInterface.reset_queue`)."""
+        if self._slot_valid is not None:
+            self._slot_valid[:-1] = False
+
+    def _update_features(self, rgb_pool, mask_pool, S, fresh, map1, map2):
+        """Feature records of the `fresh` pool entries; returns (slot1, slot2, ok): the records poses read and whether both are valid."""
+        net, dev = self.estimator, self.estimator.device
+        M = int(rgb_pool.shape[0])
+        if self._feat_pool is None or self._feat_pool.shape != (M + 1, net.feature_bytes):
+            self._feat_pool = self._slot_valid = None
+            self._feat_pool = net.feature_pool(M + 1)
+            self._slot_valid = torch.zeros(M + 1, dtype=torch.bool, device=dev)
+            # record M: the map of an all-zero crop, read in place of a missing view (map entry < 0) or of an entry without a valid record
+            net.features(torch.zeros(1, 3, S, S, dtype=torch.float32, device=dev), torch.full((1,), M, dtype=torch.int32, device=dev),
+                         self._feat_pool)
+            self._slot_valid[M] = True
+        fresh = [int(e) for e in fresh]
+        if fresh:
+            if min(fresh) < 0 or max(fresh) >= M:
+                raise ValueError(f"estimate_device_indexed: fresh entries must lie in [0, {M}), got {min(fresh)} .. {max(fresh)}")
+            key = tuple(fresh)
+            fd = self._fresh_dev.get(key)
+            if fd is None:
+                if len(self._fresh_dev) >= 64:
+                    self._fresh_dev.clear()
+                # the crop windows' intrinsics are not needed for the image: any K serves this preparation
+                fd = self._fresh_dev[key] = (torch.as_tensor(np.asarray(fresh, dtype=np.int32)).to(dev),
+                                             torch.eye(3, dtype=torch.float64, device=dev).expand(len(fresh), 3, 3).contiguous())
+            img = prepare_inputs(rgb_pool, mask_pool, fd[1], S, 1024, self.prepare_seed, frame_map=fd[0])["img"]
+            net.features(img, fd[0], self._feat_pool)
+            self._slot_valid[fd[0].long()] = True
+            self.feature_views_computed += len(fresh)
+        slots = []
+        for m in (map1, map2):
+            m = torch.as_tensor(m).to(device=dev, dtype=torch.int64)
+            m = torch.where((m < 0) | (m > M), torch.full_like(m, M), m)
+            slots.append(m)
+        ok = self._slot_valid[slots[0]] & self._slot_valid[slots[1]]
+        s1, s2 = (torch.where(self._slot_valid[m], m, torch.full_like(m, M)).to(torch.int32) for m in slots)
+        return s1, s2, ok
 
     def _pnp_branch(self):
         return not self.cfg.get("direct_regression", True) and not self.cfg.get("use_depth", True)
 
-    def _estimate_prepared(self, a, b, E1, E2, K=None):
+    def _estimate_prepared(self, a, b, E1, E2, K=None, cached=None):
         S = self.cfg["img_size"]
         dev = self.estimator.device
         E1d = torch.as_tensor(E1).to(device=dev, dtype=torch.float64)
@@ -478,9 +540,17 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             consts = self._dev_consts = (torch.from_numpy(DEFAULT_BBOX).to(dev),
                                          torch.from_numpy(np.arange(0.1, 0.1 * (24 - 0.5) + 0.1, 0.1, dtype=np.float32)).to(dev))
         depths = consts[1][None].expand(n, 24).contiguous()
-        pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], proj(a["Kcrop"], E1d), proj(b["Kcrop"], E2d), depths)
+        if cached is None:
+            pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], proj(a["Kcrop"], E1d), proj(b["Kcrop"], E2d), depths)
+            self.feature_views_computed += 2 * n
+        else:      # (slot1, slot2, both records valid) of _update_features: the network from the kept feature maps
+            pred = self.estimator.forward_cached(self._feat_pool, cached[0], cached[1], a["choose"], b["choose"], proj(a["Kcrop"], E1d),
+                                                 proj(b["Kcrop"], E2d), depths)
         bbox = self._bbox_tail(pred, a["choose"], a["Kcrop"], E1d, pts2d=(a.get("pts2d"), b.get("pts2d")), E2=E2d, K=K)
-        ok = ((a["valid"] != 0) & (b["valid"] != 0)).view(n, 1, 1)
+        ok = (a["valid"] != 0) & (b["valid"] != 0)
+        if cached is not None:
+            ok = ok & cached[2]
+        ok = ok.view(n, 1, 1)
         return torch.where(ok, bbox, consts[0].expand(n, 8, 3))
 
     def _bbox_tail(self, pred, choose, Kcrop, E1, pts2d=None, E2=None, K=None):
