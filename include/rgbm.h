@@ -466,6 +466,17 @@ int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int 
                                 const float* depths, void* workspace, size_t workspace_bytes, const rgbm_adapose_out* out, void* stream);
 int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* name, float* out_dev, size_t capacity,
                        size_t* n_elems, void* stream);
+/* Content key of prepared crops: a caller that gets its frames as fresh arrays on every call (the numpy `estimate` boundary) has no
+ * slot to name a frame by; it recognises the PSPNet's input, img[v] ([3,S,S] fp32 = n_words 32-bit words), by two 64-bit words
+ *   keys_out[v][k] = sum over i < n_words of mix((bits(w_i) | (uint64)i << 32) ^ SEED_k)   (mod 2^64),   k = 0, 1,
+ *   mix(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31      (splitmix64's finaliser),
+ *   SEED_0 = 0x9E3779B97F4A7C15, SEED_1 = 0xD1B54A32D192ED03.
+ * Integer arithmetic throughout, and the sum commutes: the keys do not depend on the grid or on the order of the partial sums.  The
+ * bit pattern is hashed, not the value: +0.0 and -0.0 differ, every NaN pattern is its own.  img: V rows of n_words words, dense, 4-byte
+ * aligned (rows that are not 16-byte aligned are read through a scalar head and tail); V in [1, 65535], n_words >= 1; keys_out: [V,2]
+ * uint64 on the device, written by this call (zeroed, then summed into).  One launch for any V.  (rgbmanip_amd/feature_keys.py holds
+ * the numpy restatement and the host table that turns keys into record slots.) */
+int rgbm_crop_fingerprint(const float* img, int V, int n_words, uint64_t* keys_out, void* stream);
 
 /* Live per-kernel timing for bench.py's roofline figure: between start and stop every convolution launch is
  * bracketed by HIP events recorded on its own stream.  stats: host double[RGBM_PROF_ROWS * 4], one row per kernel family,

@@ -119,6 +119,7 @@ SIGNATURES = {
     "rgbm_adapose_features_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),
     "rgbm_adapose_features": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "rgbm_adapose_forward_cached": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp]),
+    "rgbm_crop_fingerprint": (_i, [_vp, _i, _i, _vp, _vp]),
     "rgbm_adapose_fetch": (_i, [_vp, _i, _vp, C.c_char_p, _vp, _sz, C.POINTER(_sz), _vp]),
     "rgbm_adapose_postprocess": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_adapose_postprocess_scratch_bytes": (_i, [_i, C.POINTER(_sz)]),

@@ -204,6 +204,10 @@ int rgbm_adapose_features(rgbm_adapose_t* h, int V, const float* img, const int3
   return h->net.features(V, img, slots_dev, pool, pool_records, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int rgbm_crop_fingerprint(const float* img, int V, int n_words, uint64_t* keys_out, void* stream) {
+  return rgbm::launch_crop_fingerprint(img, V, n_words, reinterpret_cast<unsigned long long*>(keys_out), (hipStream_t)stream);
+}
+
 int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int pool_records, const int32_t* slot1_dev,
                                 const int32_t* slot2_dev, const int32_t* choose1, const int32_t* choose2, const float* P1, const float* P2,
                                 const float* depths, void* workspace, size_t workspace_bytes, const rgbm_adapose_out* out, void* stream) {

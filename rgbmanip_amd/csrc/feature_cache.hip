@@ -5,6 +5,8 @@
 //   gather: pool record slot1[b] / slot2[b]             -> workspace feature map of view b / B + b  ([view1 batch ; view2 batch])
 // and the kernel that turns the ten outputs of a pose whose slot lies outside the pool into NaN (the gather wrote zeros for it and
 // read nothing).
+// And the content key of a prepared crop ("content keys"): two 64-bit sums of a mixed (word, position) pair over
+// the crop's 32-bit words, by which a caller that gets frames as fresh arrays recognises one it has kept the map of.
 #include "kernels.h"
 
 namespace rgbm {
@@ -77,7 +79,94 @@ int copy_grid_x(int V, long long n16, unsigned* gx) {
   return 0;
 }
 
+// ---- content key.  key[v][k] = sum over the words w_i of view v of mix((w_i | i << 32) ^ seed_k)  (mod 2^64), mix = the splitmix64
+// finaliser.  Integer arithmetic only and the sum commutes: lane sums, wave shuffles, LDS partials and one 64-bit vector atomic per
+// workgroup and key word give the same bits in any order.
+constexpr int kKeyThreads = 256;
+constexpr int kKeyUnroll = 4;        // 16-byte loads in flight per lane
+constexpr unsigned long long kKeySeed0 = 0x9E3779B97F4A7C15ull, kKeySeed1 = 0xD1B54A32D192ED03ull;
+
+__device__ __forceinline__ unsigned long long key_mix(unsigned long long x) {
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+__device__ __forceinline__ void key_add(unsigned w, unsigned i, unsigned long long& k0, unsigned long long& k1) {
+  const unsigned long long x = (unsigned long long)w | ((unsigned long long)i << 32);
+  k0 += key_mix(x ^ kKeySeed0);
+  k1 += key_mix(x ^ kKeySeed1);
+}
+
+// grid (pieces of a view, V).  A row starts at any 4-byte address: up to three head words bring it to a 16-byte boundary, the body is
+// read 16 bytes per lane, up to three tail words follow (head and tail: workgroup 0 of the view).  keys: zero on entry.
+__global__ __launch_bounds__(kKeyThreads) void crop_fingerprint_kernel(const unsigned* __restrict__ img, int n_words,
+                                                                       unsigned long long* __restrict__ keys) {
+  const int v = blockIdx.y;
+  const unsigned* row = img + (long long)v * n_words;
+  int head = (int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 2);
+  if (head > n_words) head = n_words;
+  const int n16 = (n_words - head) >> 2;
+  const int tail0 = head + 4 * n16;                      // first tail word; n_words - tail0 in [0, 3]
+  const uint4* body = reinterpret_cast<const uint4*>(row + head);
+  unsigned long long k0 = 0, k1 = 0;
+  const int step = (int)gridDim.x * kKeyThreads;
+  int i = (int)blockIdx.x * kKeyThreads + (int)threadIdx.x;
+  for (; i < n16 - (kKeyUnroll - 1) * step; i += kKeyUnroll * step) {      // (n16 < 2^29: the bound cannot wrap)
+    uint4 r[kKeyUnroll];
+#pragma unroll
+    for (int u = 0; u < kKeyUnroll; ++u) r[u] = body[i + u * step];
+#pragma unroll
+    for (int u = 0; u < kKeyUnroll; ++u) {
+      const unsigned w0 = (unsigned)(head + 4 * (i + u * step));
+      key_add(r[u].x, w0, k0, k1); key_add(r[u].y, w0 + 1, k0, k1); key_add(r[u].z, w0 + 2, k0, k1); key_add(r[u].w, w0 + 3, k0, k1);
+    }
+  }
+  for (; i < n16; i += step) {
+    const uint4 r = body[i];
+    const unsigned w0 = (unsigned)(head + 4 * i);
+    key_add(r.x, w0, k0, k1); key_add(r.y, w0 + 1, k0, k1); key_add(r.z, w0 + 2, k0, k1); key_add(r.w, w0 + 3, k0, k1);
+  }
+  if (blockIdx.x == 0) {
+    const int t = (int)threadIdx.x;
+    if (t < head) key_add(row[t], (unsigned)t, k0, k1);
+    if (t < n_words - tail0) key_add(row[tail0 + t], (unsigned)(tail0 + t), k0, k1);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    k0 += __shfl_down(k0, off, 64);
+    k1 += __shfl_down(k1, off, 64);
+  }
+  __shared__ unsigned long long part[2][kKeyThreads / 64];
+  const int wave = (int)threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { part[0][wave] = k0; part[1][wave] = k1; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    unsigned long long s = 0;
+#pragma unroll
+    for (int w = 0; w < kKeyThreads / 64; ++w) s += part[threadIdx.x][w];
+    atomicAdd(&keys[2 * v + (int)threadIdx.x], s);
+  }
+}
+
 }  // namespace
+
+int launch_crop_fingerprint(const float* img, int V, int n_words, unsigned long long* keys_out, hipStream_t s) {
+  RGBM_REQUIRE(img && keys_out && V > 0 && V < 65536 && n_words >= 1, "crop_fingerprint arguments");
+  RGBM_REQUIRE((((uintptr_t)img) & 3) == 0 && (((uintptr_t)keys_out) & 7) == 0, "crop_fingerprint: 4-byte aligned words, 8-byte aligned keys");
+  int n_cu = 0;
+  if (int rc = persistent_grid_cus(&n_cu)) return rc;
+  // about 8 workgroups per CU over all views; no more than one 16-byte load per lane would fill (a lone view still spreads over the CUs)
+  long long want = ((long long)n_cu * 8 + V - 1) / V;
+  const long long cap = ((long long)(n_words / 4) + kKeyThreads - 1) / kKeyThreads;
+  if (want > cap) want = cap;
+  if (want < 1) want = 1;
+  RGBM_CHECK_HIP(hipMemsetAsync(keys_out, 0, (size_t)V * 2 * sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(crop_fingerprint_kernel, dim3((unsigned)want, (unsigned)V), dim3(kKeyThreads), 0, s,
+                     reinterpret_cast<const unsigned*>(img), n_words, keys_out);
+  RGBM_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 
 int launch_feature_store(const void* src, void* pool, const int* slots, int V, int pool_records, size_t part_off, size_t part_bytes,
                          size_t record_bytes, hipStream_t s) {

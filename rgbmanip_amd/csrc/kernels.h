@@ -72,6 +72,8 @@ int launch_feature_gather(const void* pool, void* dst, const int* slot1, const i
 // out[k]: the k-th output tensor [B][per_pose[k]] fp32
 int launch_feature_bad_slot_nan(const int* slot1, const int* slot2, int B, int pool_records, float* const out[10], const int per_pose[10],
                                 hipStream_t s);
+// content key of V prepared crops of n_words 32-bit words each (include/rgbm.h: rgbm_crop_fingerprint): keys_out [V][2], zeroed here
+int launch_crop_fingerprint(const float* img, int V, int n_words, unsigned long long* keys_out, hipStream_t s);
 int launch_f32_to_bx3(const float* in, void* out, long long n, hipStream_t s);     // plain fp32 -> split pairs (n % 4 == 0; in place allowed)
 int launch_view_linear(const float* x, const float* W, const float* bias, float* out, int V, int I, int O, int ldw, int i0,
                        int relu, hipStream_t s);

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from .adapose import AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, prepare_inputs
+from .feature_keys import FeatureKeyTable
 
 DEFAULT_BBOX = np.asarray([[0, 0, 0], [0, 0, 1], [0, 1, 0], [0, 1, 1], [1, 0, 0], [1, 0, 1], [1, 1, 0], [1, 1, 1]],
                           dtype=np.float64) + 10.0
@@ -167,8 +168,15 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         norm_mode, drop_p, drop_seed = dropout_cfg(cfg)
         # hip_feature_cache (default off): `estimate_device_indexed(..., fresh=...)` keeps every pool frame's PSPNet feature map in a
         # record pool and runs the PSPNet only on the frames named fresh (DESIGN.md "Feature cache").  Dropout2d draws its masks per pose
-        # and per forward, so a kept map would change what the as-shipped estimator computes: the combination is refused
-        self.feature_cache = bool(cfg.get("hip_feature_cache", False))
+        # and per forward, so a kept map would change what the as-shipped estimator computes: the combination is refused.
+        # "content" is True plus the same for `estimate` / `estimate_device`, whose frames arrive as fresh arrays: every prepared crop is
+        # fingerprinted on the device (rgbm_crop_fingerprint), a host table (feature_keys.py) maps key -> record of a pool of
+        # hip_feature_cache_records records (0: twice the poses of the largest call so far), and the PSPNet runs on the crops not met before
+        mode = cfg.get("hip_feature_cache", False)
+        if isinstance(mode, str) and mode != "content":
+            raise ValueError(f'AdaPoseEstimator_v5: hip_feature_cache is False, True or "content", got {mode!r}')
+        self.feature_cache = bool(mode)
+        self.feature_content = mode == "content"
         if self.feature_cache and drop_p > 0:
             raise ValueError("AdaPoseEstimator_v5: hip_feature_cache keeps feature maps across forwards, Dropout2d (hip_dropout / "
                              f"hip_as_shipped: p={drop_p}) draws fresh masks on every forward; turn one of them off")
@@ -176,6 +184,14 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         self._feat_pool = None                # [M + 1, feature_bytes]: one record per frame-pool entry; record M = the all-zero crop's map
         self._slot_valid = None               # [M + 1] bool on the device: record holds the map of the entry's current frame (M: always)
         self._fresh_dev = {}
+        self.feature_cache_bypassed = 0       # "content": calls / chunks with more distinct crops than the pool has records (run on the plain path)
+        self._key_records = int(cfg.get("hip_feature_cache_records", 0))
+        if self._key_records < 0:
+            raise ValueError(f"hip_feature_cache_records must be 0 (twice the poses of the largest call) or a record count, got {self._key_records}")
+        self._key_pool = None                 # [records, feature_bytes]: the content-keyed records, apart from _feat_pool
+        self._key_table = None                # FeatureKeyTable(records), built with the pool ("content" only)
+        self._key_tie = None                  # (feature_bytes, options) the records were written under
+        self._key_poses = 0                   # poses of the largest call so far
         self.estimator = net if net is not None else AdaPoseNet(state_dict, dtype=self.dtype, device=device,
                                                                 norm_mode=norm_mode, dropout=drop_p, dropout_seed=drop_seed,
                                                                 graph=bool(cfg.get("hip_graph", False)),
@@ -301,7 +317,12 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         on its own stream and the kernels (dtype conversion, crop / resize / subset, network, post-processing) work on chunk c - 1.
         Poses are independent, but a chunk is a smaller batch: below ~1000 GEMM rows per launch and at launches that fit one round of the
         persistent grid the dispatcher picks other tiles (summation order), so a pose's box agrees with the unchunked call's to the
-        storage type's rounding (1e-6 .. 1e-5 relative in fp32 / bf16x3), not bit for bit (include/rgbm.h, rgbm_set_tuning)."""
+        storage type's rounding (1e-6 .. 1e-5 relative in fp32 / bf16x3), not bit for bit (include/rgbm.h, rgbm_set_tuning).
+
+        With hip_feature_cache: "content" the network of a chunk cannot be enqueued before the chunk's keys are on the host, and a wait
+        for them on the kernels' stream would also wait for the previous chunk's network (staging, copy and kernels back to back again).
+        So the crop preparation and the fingerprint of chunk c run on the upload stream behind that chunk's copy, and its network is
+        enqueued one loop iteration later, after chunk c + 1 has been staged and its copy started: by then the keys have long arrived."""
         n = len(rgb1)
         chunk = int(self.cfg.get("hip_upload_chunk", 32))
         on_dev = any(isinstance(x, torch.Tensor) and x.is_cuda for x in (rgb1, rgb2))
@@ -333,6 +354,19 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         cur = torch.cuda.current_stream(dev)
         out = torch.empty(n, 8, 3, dtype=torch.float64, device=dev)
         used = [False, False]
+        content = self.feature_content
+        if content:
+            self._content_reserve(n)
+            consts_ev = torch.cuda.Event()
+            consts_ev.record(cur)                          # Kd was written on this stream, the upload stream's preparation reads it
+            self._pipe_stream.wait_event(consts_ev)
+            S, wp = self.cfg["img_size"], self._pnp_branch()
+        pending = None
+
+        def finish(p):      # "content": the network of an earlier chunk, from its keys
+            if p["ev"]: p["ev"][2].record(cur)
+            out[p["a"]:p["b"]] = self._content_finish(p["keys"], E1d[p["a"]:p["b"]], E2d[p["a"]:p["b"]], Kd[p["a"]:p["b"]])
+            if p["ev"]: p["ev"][3].record(cur)
 
         def stage(slot, a, b):
             tasks = []
@@ -362,13 +396,26 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                 trace.append((round((t1 - t0) * 1e3, 2), round((time.perf_counter() - t1) * 1e3, 2)))
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if trace is not None else None
             with torch.cuda.stream(self._pipe_stream):
-                if used[slot]:
+                if used[slot] and not content:             # ("content": this stream's own preparation reads them, in order)
                     self._pipe_stream.wait_event(self._pipe_done[slot])      # the kernels that read this slot's device buffers are done
                 if ev: ev[0].record(self._pipe_stream)
                 for i in range(4):
                     self._pipe_dev[slot][i][: b - a].copy_(self._pipe_pin[slot][i][: b - a], non_blocking=True)
                 self._pipe_h2d[slot].record(self._pipe_stream)
                 if ev: ev[1].record(self._pipe_stream)
+                if content:
+                    d = [t[: b - a] for t in self._pipe_dev[slot]]
+                    pa = prepare_inputs(self._upload_frames(d[0]), d[2], Kd[a:b], S, 1024, self.prepare_seed, want_pts2d=wp, frame0=a)
+                    pb = prepare_inputs(self._upload_frames(d[1]), d[3], Kd[a:b], S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=a)
+                    keys = self._content_keys(pa, pb)
+            if content:
+                if pending is not None:
+                    finish(pending)
+                pending = {"a": a, "b": b, "keys": keys, "ev": ev}
+                if ev:
+                    trace[-1] = trace[-1] + (round((time.perf_counter() - t0) * 1e3, 2), ev)
+                used[slot] = True
+                continue
             cur.wait_event(self._pipe_h2d[slot])
             if ev: ev[2].record(cur)
             d = [t[: b - a] for t in self._pipe_dev[slot]]
@@ -378,6 +425,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                 ev[3].record(cur)
                 trace[-1] = trace[-1] + (round((time.perf_counter() - t0) * 1e3, 2), ev)
             used[slot] = True
+        if pending is not None:
+            finish(pending)
         res = out.cpu().numpy()
         if trace is not None:
             e00 = trace[0][3][0]
@@ -454,6 +503,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         wp = self._pnp_branch()
         a = prepare_inputs(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, S, 1024, self.prepare_seed, want_pts2d=wp, frame0=frame0)
         b = prepare_inputs(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=frame0)
+        if self.feature_content:      # one host synchronisation per call: the keys must be on the host before the network can be enqueued
+            self._content_reserve(int(Kd.shape[0]))
+            return self._content_finish(self._content_keys(a, b), E1, E2, Kd)
         return self._estimate_prepared(a, b, E1, E2, Kd)
 
     def estimate_device_indexed(self, K, rgb_pool, mask_pool, E1, E2, map1, map2, fresh=None):
@@ -480,6 +532,67 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         """Forget every cached feature map (the frame pool is about to be rewritten: `ControlInterface.reset_queue`)."""
         if self._slot_valid is not None:
             self._slot_valid[:-1] = False
+        if self._key_table is not None:
+            self._key_table.clear()
+
+    # ------------------------------------------------------------------ content-keyed records (cfg hip_feature_cache: "content")
+    def _content_reserve(self, n):
+        """The pool and the table for calls of up to n poses; both start empty when the pool is (re)allocated: a larger call than any
+        before (hip_feature_cache_records: 0), or a net whose record size or options changed (records are not interchangeable)."""
+        net = self.estimator
+        self._key_poses = max(self._key_poses, int(n))
+        records = self._key_records or 2 * self._key_poses
+        tie = (net.feature_bytes, tuple(sorted(net.options.items())))
+        if self._key_pool is None or self._key_pool.shape[0] != records or self._key_tie != tie:
+            self._key_pool = None
+            self._key_pool = net.feature_pool(records)
+            self._key_table = FeatureKeyTable(records)
+            self._key_tie = tie
+
+    def _content_keys(self, a, b):
+        """Enqueue on the current stream: fingerprint of cat(img1, img2) and the copy of the [2n,2] keys to pinned host memory."""
+        img = torch.cat((a["img"], b["img"]))
+        V = int(img.shape[0])
+        keys = torch.empty(V, 2, dtype=torch.int64, device=img.device)
+        _lib.check(_lib.load().rgbm_crop_fingerprint(_lib.ptr(img), V, int(img[0].numel()), _lib.ptr(keys), _lib.stream_ptr()),
+                   "rgbm_crop_fingerprint")
+        host = torch.empty(V, 2, dtype=torch.int64, pin_memory=True)
+        host.copy_(keys, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return {"a": a, "b": b, "img": img, "keys_dev": keys, "keys": host, "ev": ev, "stream": torch.cuda.current_stream(img.device)}
+
+    def _content_finish(self, pend, E1, E2, K):
+        """Wait for the keys of `_content_keys` (the host waits for that stream's work up to the key copy, nothing else), assign record
+        slots, run the PSPNet on the crops not met before and the rest of the network from the records, on the current stream."""
+        a, b, img = pend["a"], pend["b"], pend["img"]
+        dev = img.device
+        cur = torch.cuda.current_stream(dev)
+        pend["ev"].synchronize()
+        if cur != pend["stream"]:
+            cur.wait_event(pend["ev"])
+            for t in [img, pend["keys_dev"]] + [v for d in (a, b) for v in d.values() if isinstance(v, torch.Tensor)]:
+                t.record_stream(cur)                      # allocated on the other stream: not to be handed out again while this one reads
+        n = int(img.shape[0]) // 2
+        got = self._key_table.assign(pend["keys"].numpy().view(np.uint64))
+        if got is None:                                    # more distinct crops than records: the plain path, bit for bit
+            self.feature_cache_bypassed += 1
+            return self._estimate_prepared(a, b, E1, E2, K)
+        slots, compute = got
+        # slot tables and miss lists go up in one copy from pinned memory (a pageable copy would block the host until the stream has drained)
+        m = len(compute)
+        tab = torch.empty(2 * n + 2 * m, dtype=torch.int32, pin_memory=True)
+        tab_np = tab.numpy()
+        tab_np[: 2 * n] = slots
+        if m:
+            tab_np[2 * n:] = np.asarray(compute, dtype=np.int32).T.reshape(-1)
+        tab_d = tab.to(dev, non_blocking=True)
+        if m:
+            whole = m == 2 * n and [v for v, _ in compute] == list(range(2 * n))
+            miss = img if whole else img.index_select(0, tab_d[2 * n: 2 * n + m])
+            self.estimator.features(miss, tab_d[2 * n + m:], self._key_pool)
+            self.feature_views_computed += m
+        return self._estimate_prepared(a, b, E1, E2, K, cached=(tab_d[:n], tab_d[n: 2 * n], None), pool=self._key_pool)
 
     def _update_features(self, rgb_pool, mask_pool, S, fresh, map1, map2):
         """Feature records of the `fresh` pool entries; returns (slot1, slot2, ok): the records poses read and whether both are valid."""
@@ -521,7 +634,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     def _pnp_branch(self):
         return not self.cfg.get("direct_regression", True) and not self.cfg.get("use_depth", True)
 
-    def _estimate_prepared(self, a, b, E1, E2, K=None, cached=None):
+    def _estimate_prepared(self, a, b, E1, E2, K=None, cached=None, pool=None):
         S = self.cfg["img_size"]
         dev = self.estimator.device
         E1d = torch.as_tensor(E1).to(device=dev, dtype=torch.float64)
@@ -543,12 +656,12 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         if cached is None:
             pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], proj(a["Kcrop"], E1d), proj(b["Kcrop"], E2d), depths)
             self.feature_views_computed += 2 * n
-        else:      # (slot1, slot2, both records valid) of _update_features: the network from the kept feature maps
-            pred = self.estimator.forward_cached(self._feat_pool, cached[0], cached[1], a["choose"], b["choose"], proj(a["Kcrop"], E1d),
+        else:      # (slot1, slot2, both records valid) of _update_features / _content_finish (its own pool, every record valid: None)
+            pred = self.estimator.forward_cached(pool if pool is not None else self._feat_pool, cached[0], cached[1], a["choose"], b["choose"], proj(a["Kcrop"], E1d),
                                                  proj(b["Kcrop"], E2d), depths)
         bbox = self._bbox_tail(pred, a["choose"], a["Kcrop"], E1d, pts2d=(a.get("pts2d"), b.get("pts2d")), E2=E2d, K=K)
         ok = (a["valid"] != 0) & (b["valid"] != 0)
-        if cached is not None:
+        if cached is not None and cached[2] is not None:
             ok = ok & cached[2]
         ok = ok.view(n, 1, 1)
         return torch.where(ok, bbox, consts[0].expand(n, 8, 3))

@@ -1,0 +1,233 @@
+"""CPU-only checks of the content-keyed feature cache ("content keys"): the fingerprint entry point is declared,
+bound and exported; `FeatureKeyTable` follows its rules; the numpy restatement of the key has the properties the cache relies on;
+and the estimator cfg accepts "content" as a superset of True."""
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+from rgbmanip_amd import _lib
+from rgbmanip_amd.feature_keys import SEEDS, FeatureKeyTable, crop_keys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_fingerprint_is_declared_bound_and_exported():
+    src = open(os.path.join(ROOT, "include", "rgbm.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    m = re.search(r"int\s+rgbm_crop_fingerprint\s*\(([^)]*)\)\s*;", src)
+    assert m, "rgbm_crop_fingerprint is not declared in include/rgbm.h"
+    args = [a.strip() for a in m.group(1).split(",")]
+    assert [re.sub(r"\s*\w+$", "", a) for a in args] == ["const float*", "int", "int", "uint64_t*", "void*"], args
+    assert "rgbm_crop_fingerprint" in _lib.SIGNATURES
+    res, argtypes = _lib.SIGNATURES["rgbm_crop_fingerprint"]
+    assert len(argtypes) == 5
+    lib = _lib.load()
+    assert getattr(lib, "rgbm_crop_fingerprint") is not None
+    assert lib.rgbm_crop_fingerprint(None, 1, 1, None, None) != 0 and b"crop_fingerprint" in lib.rgbm_last_error()      # refused, nothing launched
+
+
+# ---------------------------------------------------------------------------------------------------------------- FeatureKeyTable
+def _k(*names):
+    """Keys from small integers: (i, ~i) as the two words."""
+    return np.array([[i, (1 << 64) - 1 - i] for i in names], dtype=np.uint64)
+
+
+def test_table_hit_and_miss():
+    t = FeatureKeyTable(4)
+    slots, compute = t.assign(_k(10, 11))
+    assert slots.dtype == np.int32 and slots.tolist() == [0, 1] and compute == [(0, 0), (1, 1)]      # free slots, lowest first
+    slots, compute = t.assign(_k(12, 11))
+    assert slots.tolist() == [2, 1] and compute == [(0, 2)]                                            # 11 is a hit, 12 is new
+    assert len(t) == 3 and (11, (1 << 64) - 12) in t and (13, (1 << 64) - 14) not in t
+    # both words make the key: the same first word with another second word is another crop
+    slots, compute = t.assign(np.array([[11, 5]], dtype=np.uint64))
+    assert slots.tolist() == [3] and compute == [(0, 3)]
+
+
+def test_table_duplicates_inside_a_call_share_a_slot_and_are_computed_once():
+    t = FeatureKeyTable(8)
+    slots, compute = t.assign(_k(7, 8, 7, 7, 9, 8))
+    assert slots.tolist() == [0, 1, 0, 0, 2, 1]
+    assert compute == [(0, 0), (1, 1), (4, 2)]              # the first view that carries each key
+    slots, compute = t.assign(_k(9, 9, 7))
+    assert slots.tolist() == [2, 2, 0] and compute == []
+
+
+def test_table_evicts_least_recently_used_over_several_calls():
+    t = FeatureKeyTable(4)
+    assert t.assign(_k(1, 2))[0].tolist() == [0, 1]
+    assert t.assign(_k(3, 4))[0].tolist() == [2, 3]
+    slots, compute = t.assign(_k(1))                        # a hit refreshes key 1
+    assert slots.tolist() == [0] and compute == []
+    slots, compute = t.assign(_k(5))                        # the oldest is key 2 (slot 1), not key 1
+    assert slots.tolist() == [1] and compute == [(0, 1)]
+    slots, compute = t.assign(_k(6, 7))                     # then keys 3 and 4 (equal age: the lower slot first)
+    assert slots.tolist() == [2, 3] and compute == [(0, 2), (1, 3)]
+    slots, compute = t.assign(_k(1, 5, 2))                  # 1 and 5 are still there, 2 is gone and takes the oldest slot not in this call
+    assert slots.tolist() == [0, 1, 2] and compute == [(2, 2)]
+    assert [k[0] for k in t._key_of] == [1, 5, 2, 7]
+
+
+def test_table_never_evicts_a_slot_of_the_call_being_assigned():
+    t = FeatureKeyTable(3)
+    t.assign(_k(1, 2, 3))                                   # slots 0, 1, 2, all of one age
+    slots, compute = t.assign(_k(4, 1))                     # 1 (slot 0) is the oldest by slot order and is in this call: slot 1 goes
+    assert slots.tolist() == [1, 0] and compute == [(0, 1)]
+    slots, compute = t.assign(_k(3, 5, 6))                  # 3 (slot 2) is the oldest now and is in this call: slots 0 and 1 go
+    assert slots.tolist() == [2, 0, 1] and compute == [(1, 0), (2, 1)]
+    assert len(set(slots.tolist())) == 3
+
+
+def test_table_reports_overflow_and_stays_untouched():
+    t = FeatureKeyTable(3)
+    t.assign(_k(1, 2))
+    before = (dict(t._slot_of), list(t._key_of), list(t._used), t._clock)
+    assert t.assign(_k(1, 2, 3, 4)) is None                 # four distinct records, three slots
+    assert (t._slot_of, t._key_of, t._used, t._clock) == before
+    assert t.assign(_k(3, 3, 3, 1, 2, 2))[1] == [(0, 2)]    # six views, three distinct: fits
+    with pytest.raises(ValueError):
+        FeatureKeyTable(0)
+
+
+def test_table_clear_forgets_everything():
+    t = FeatureKeyTable(2)
+    t.assign(_k(1, 2))
+    t.clear()
+    assert len(t) == 0
+    slots, compute = t.assign(_k(2, 1))
+    assert slots.tolist() == [0, 1] and compute == [(0, 0), (1, 1)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the key itself
+def _slow_keys(row):
+    """The definition in Python integers, one word at a time."""
+    out = []
+    for seed in SEEDS:
+        acc = 0
+        for i, w in enumerate(np.asarray(row).view(np.uint32).tolist()):
+            x = ((w | (i << 32)) ^ seed) & (2 ** 64 - 1)
+            x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) % 2 ** 64
+            x ^= x >> 27; x = (x * 0x94D049BB133111EB) % 2 ** 64
+            x ^= x >> 31
+            acc = (acc + x) % 2 ** 64
+        out.append(acc)
+    return out
+
+
+def test_numpy_keys_are_the_definition():
+    rng = np.random.default_rng(0)
+    w = rng.integers(0, 2 ** 32, size=(3, 101), dtype=np.uint32)
+    got = crop_keys(w)
+    assert got.dtype == np.uint64 and got.shape == (3, 2)
+    for v in range(3):
+        assert got[v].tolist() == _slow_keys(w[v])
+    assert crop_keys(w.view(np.float32)).tolist() == got.tolist()          # bit patterns, whatever the 4-byte dtype
+    assert crop_keys(w[1]).tolist() == got[1:2].tolist()                   # one row
+    assert crop_keys(w.reshape(3, 1, 101)).tolist() == got.tolist()        # [V, ...]
+    with pytest.raises(TypeError):
+        crop_keys(w.astype(np.float64))
+
+
+def test_key_properties():
+    rng = np.random.default_rng(1)
+    w = rng.integers(0, 2 ** 32, size=(4, 257), dtype=np.uint32)
+    base = crop_keys(w[0])[0]
+    perm = w[0].copy()
+    perm[[3, 200]] = perm[[200, 3]]
+    assert perm[3] != w[0][3]
+    p = crop_keys(perm)[0]
+    assert p[0] != base[0] and p[1] != base[1]                              # the position is part of what is hashed
+    for bit in (0, 13, 31):
+        flip = w[0].copy()
+        flip[77] ^= np.uint32(1 << bit)
+        f = crop_keys(flip)[0]
+        assert f[0] != base[0] and f[1] != base[1], bit
+    z = np.zeros((2, 16), dtype=np.float32)
+    z[1, 5] = -0.0
+    kz = crop_keys(z)
+    assert kz[0, 0] != kz[1, 0] and kz[0, 1] != kz[1, 1]                    # +0.0 and -0.0 are different inputs of the network's bit pattern
+    assert base[0] != base[1]                                               # the two lanes are two hashes
+    # rows are keyed on their own: a batch's keys are the keys of its rows taken alone
+    both = crop_keys(w)
+    for v in range(4):
+        assert both[v].tolist() == crop_keys(w[v:v + 1])[0].tolist()
+    assert crop_keys(np.concatenate((w[2:], w[:2])))[:2].tolist() == both[2:].tolist()
+
+
+# ---------------------------------------------------------------------------------------------------------------- the cfg
+def _stub_net():
+    return types.SimpleNamespace(options={"view2_heads": 0}, dropout=0.0, dropout_seed=0, device="cpu", feature_bytes=64)
+
+
+def _est(net=None, **kw):
+    from rgbmanip_amd.config import ADAPOSE_CFGS
+    from rgbmanip_amd.estimator import AdaPoseEstimator_v5
+    return AdaPoseEstimator_v5(None, dict(ADAPOSE_CFGS["adapose_cabinet"], load=False, **kw), None, net=net or _stub_net())
+
+
+def test_content_mode_with_dropout_is_refused():
+    from rgbmanip_amd.config import ADAPOSE_CFGS
+    from rgbmanip_amd.estimator import AdaPoseEstimator_v5
+    cfg = dict(ADAPOSE_CFGS["adapose_cabinet"], load=False, hip_feature_cache="content")
+    for extra in ({"hip_dropout": 0.15}, {"hip_as_shipped": True}):
+        with pytest.raises(ValueError, match="hip_feature_cache"):
+            AdaPoseEstimator_v5(None, dict(cfg, **extra), None, state_dict={})
+    with pytest.raises(ValueError, match="hip_feature_cache"):
+        AdaPoseEstimator_v5(None, dict(cfg, hip_feature_cache="contents"), None, state_dict={})      # a misspelt mode is not "on"
+    with pytest.raises(ValueError, match="hip_feature_cache_records"):
+        _est(hip_feature_cache="content", hip_feature_cache_records=-1)
+
+
+def test_content_mode_is_a_superset_of_true(monkeypatch):
+    est = _est(hip_feature_cache="content")
+    assert est.feature_cache is True and est.feature_content is True
+    assert est.cfg.get("hip_feature_cache")                 # what ControlInterface reads before it names the fresh rows
+    assert est.feature_cache_bypassed == 0 and est.feature_views_computed == 0
+    # estimate_device_indexed(..., fresh=...) takes the slot-addressed path exactly as with True
+    from rgbmanip_amd import estimator as em
+    seen = []
+    monkeypatch.setattr(em, "prepare_inputs", lambda *a, **kw: {"frame_map": kw.get("frame_map")})
+    for mode in (True, "content"):
+        e = _est(hip_feature_cache=mode)
+        monkeypatch.setattr(e, "_update_features", lambda *a: seen.append(("update", a[3])) or "CACHED")
+        monkeypatch.setattr(e, "_estimate_prepared", lambda a, b, E1, E2, K, cached=None: seen.append(("run", cached)) or "BOX")
+        assert e.estimate_device_indexed("K", "rgb", "mask", "E1", "E2", [0], [1], fresh=[1]) == "BOX"
+    assert seen == [("update", [1]), ("run", "CACHED")] * 2
+
+
+@pytest.mark.parametrize("mode", [False, True])
+def test_other_modes_construct_no_table(mode):
+    est = _est(hip_feature_cache=mode)
+    assert est.feature_cache is bool(mode) and est.feature_content is False
+    assert est._key_table is None and est._key_pool is None
+    est.invalidate_features()                               # nothing to clear, nothing built
+    assert est._key_table is None
+
+
+def test_content_table_is_built_with_the_pool_and_cleared_by_invalidate(monkeypatch):
+    import torch
+    net = _stub_net()
+    net.feature_pool = lambda records: torch.empty(int(records), net.feature_bytes, dtype=torch.uint8)
+    est = _est(hip_feature_cache="content", net=net)
+    assert est._key_table is None                           # built with the first call, sized by it
+    est._content_reserve(3)
+    assert est._key_table.records == 6 and est._key_pool.shape == (6, 64)
+    est._key_table.assign(_k(1, 2))
+    table = est._key_table
+    est._content_reserve(2)                                 # a smaller call keeps pool and table
+    assert est._key_table is table and len(table) == 2
+    est.invalidate_features()
+    assert est._key_table is table and len(table) == 0
+    table.assign(_k(1))
+    est._content_reserve(5)                                 # a larger call: a larger pool, empty
+    assert est._key_table.records == 10 and len(est._key_table) == 0
+    est._key_table.assign(_k(1))
+    net.options["sweep_f16"] = 0                            # records written under other options are not interchangeable
+    est._content_reserve(5)
+    assert len(est._key_table) == 0
+    fixed = _est(hip_feature_cache="content", hip_feature_cache_records=7, net=net)
+    fixed._content_reserve(100)
+    assert fixed._key_table.records == 7
