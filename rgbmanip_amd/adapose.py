@@ -21,6 +21,8 @@ _DTYPES = {"fp32": _lib.F32, "f32": _lib.F32, "float32": _lib.F32, "bf16": _lib.
 
 
 class AdaPoseNet:
+    _h = None                                            # the C handle; None until rgbm_adapose_create has run (close / __del__ read it)
+
     def __init__(self, state_dict, dtype: str = "fp32", device: int = 0, max_chunk_views: int | None = None,
                  cost_impl: int | None = None, sparse_tail: int | None = None, options: dict | None = None,
                  norm_mode: int | str = 0, poison_workspace: bool = False, graph: bool = False, graph_max_batch: int = 32,
@@ -35,6 +37,7 @@ class AdaPoseNet:
         self._static = {}
         self._gstream = None
         self.last_graph_nodes = 0
+        self._last_graph = False
         # debug: fill the whole workspace with 0xFF bytes (NaN in every storage type, -1 in index lists) in front of EVERY forward, so
         # that a kernel reading a tile the sparse cost regularisation skipped — or anything else a forward did not write itself —
         # cannot find a previous run's (correct) values there (tests/test_gpu_at_batch.py, bench.py's at-batch check)
@@ -121,7 +124,7 @@ class AdaPoseNet:
         self._drop_explicit = True
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
+        if self._h is not None and self._h.value:
             self.lib.rgbm_adapose_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -142,13 +145,29 @@ class AdaPoseNet:
             self._ws = None
             self._ws = torch.empty(self.workspace_bytes(B) + 256, dtype=torch.uint8, device=self.device)
             self._ws_B = B
-        off = (-self._ws.data_ptr()) % 256
-        return self._ws.data_ptr() + off, self._ws.numel() - off
+        return self._aligned(self._ws)
 
     def _prep(self, t, dtype):
         if not isinstance(t, torch.Tensor):
             t = torch.as_tensor(np.asarray(t))
         return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _empty_outputs(self, B):
+        """The ten outputs of the reference network (network_v5.py:301-519), uninitialised."""
+        shapes = {"nocs": (B, 1024, 3), "depth": (B, 1024), "r": (B, 3, 3), "t": (B, 3), "s": (B, 3)}
+        return {f"view{v}_{k}": torch.empty(*shp, dtype=torch.float32, device=self.device) for k, shp in shapes.items() for v in (1, 2)}
+
+    @staticmethod
+    def _aligned(ws):
+        """(256-byte aligned pointer into the workspace tensor, bytes behind it)"""
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def _poison(self, ws, stream=None):
+        """poison_workspace: 0xFF bytes over `ws` on the stream the forward runs on (None: the current one)."""
+        if self.poison_workspace:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                ws.fill_(0xFF)
 
     def _forward_graph(self, args):
         """Replay (first call per batch size: capture) the forward on static buffers; returns fresh output tensors."""
@@ -162,11 +181,7 @@ class AdaPoseNet:
             i32 = dict(dtype=torch.int32, device=self.device)
             ins = [torch.empty(B, 3, 224, 224, **f32), torch.empty(B, 1024, **i32), torch.empty(B, 3, 224, 224, **f32), torch.empty(B, 1024, **i32),
                    torch.empty(B, 4, 4, **f32), torch.empty(B, 4, 4, **f32), torch.empty(B, 24, **f32)]
-            out = {"view1_nocs": torch.empty(B, 1024, 3, **f32), "view2_nocs": torch.empty(B, 1024, 3, **f32),
-                   "view1_depth": torch.empty(B, 1024, **f32), "view2_depth": torch.empty(B, 1024, **f32),
-                   "view1_r": torch.empty(B, 3, 3, **f32), "view2_r": torch.empty(B, 3, 3, **f32),
-                   "view1_t": torch.empty(B, 3, **f32), "view2_t": torch.empty(B, 3, **f32),
-                   "view1_s": torch.empty(B, 3, **f32), "view2_s": torch.empty(B, 3, **f32)}
+            out = self._empty_outputs(B)
             ws = torch.empty(self.workspace_bytes(B) + 256, dtype=torch.uint8, device=self.device)
             st = self._static[B] = (ins, out, ws)
         ins, out, ws = st
@@ -179,16 +194,14 @@ class AdaPoseNet:
         cur = torch.cuda.current_stream(self.device)
         gs = self._gstream
         gs.wait_stream(cur)
-        off = (-ws.data_ptr()) % 256
+        ws_ptr, ws_bytes = self._aligned(ws)
         o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
         nodes, cap = C.c_int32(), C.c_int32()
-        if self.poison_workspace:
-            with torch.cuda.stream(gs):
-                ws.fill_(0xFF)
+        self._poison(ws, gs)
         # (img1, choose1, img2, choose2, P1, P2, depths) -> the C ABI's (img1, img2, choose1, choose2, P1, P2, depths)
         _lib.check(self.lib.rgbm_adapose_forward_graph(self._h, B, _lib.ptr(ins[0]), _lib.ptr(ins[2]), _lib.ptr(ins[1]), _lib.ptr(ins[3]),
-                                                       _lib.ptr(ins[4]), _lib.ptr(ins[5]), _lib.ptr(ins[6]), C.c_void_p(ws.data_ptr() + off),
-                                                       ws.numel() - off, C.byref(o), C.c_void_p(gs.cuda_stream), C.byref(nodes), C.byref(cap)),
+                                                       _lib.ptr(ins[4]), _lib.ptr(ins[5]), _lib.ptr(ins[6]), C.c_void_p(ws_ptr),
+                                                       ws_bytes, C.byref(o), C.c_void_p(gs.cuda_stream), C.byref(nodes), C.byref(cap)),
                    "rgbm_adapose_forward_graph")
         self.last_graph_nodes = nodes.value
         cur.wait_stream(gs)
@@ -211,14 +224,7 @@ class AdaPoseNet:
         assert img1.shape == (B, 3, 224, 224) and img2.shape == img1.shape, img1.shape
         assert ch1.shape == (B, 1024) and ch2.shape == ch1.shape
         assert P1.shape == (B, 4, 4) and P2.shape == (B, 4, 4) and dep.shape == (B, 24)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        out = {
-            "view1_nocs": torch.empty(B, 1024, 3, **f32), "view2_nocs": torch.empty(B, 1024, 3, **f32),
-            "view1_depth": torch.empty(B, 1024, **f32), "view2_depth": torch.empty(B, 1024, **f32),
-            "view1_r": torch.empty(B, 3, 3, **f32), "view2_r": torch.empty(B, 3, 3, **f32),
-            "view1_t": torch.empty(B, 3, **f32), "view2_t": torch.empty(B, 3, **f32),
-            "view1_s": torch.empty(B, 3, **f32), "view2_s": torch.empty(B, 3, **f32),
-        }
+        out = self._empty_outputs(B)
         # with dropout the parts would share the handle's pose counter and factor buffer (rgbm.h): the forward runs on one stream (the
         # split forward computes the same outputs)
         if self.split_streams and stop_after == 0 and B >= self.split_min_batch and B % self.split_parts == 0 and not self.dropout \
@@ -229,9 +235,7 @@ class AdaPoseNet:
         self._drop_explicit = False
         o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
         ws_ptr, ws_bytes = self._workspace(B)
-        if self.poison_workspace:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-                self._ws.fill_(0xFF)
+        self._poison(self._ws, stream)
         _lib.check(self.lib.rgbm_adapose_forward_ex(self._h, B, _lib.ptr(img1), _lib.ptr(img2), _lib.ptr(ch1), _lib.ptr(ch2),
                                                     _lib.ptr(P1), _lib.ptr(P2), _lib.ptr(dep), C.c_void_p(ws_ptr), ws_bytes,
                                                     C.byref(o), stop_after, _lib.stream_ptr(stream)), "rgbm_adapose_forward")
@@ -253,15 +257,13 @@ class AdaPoseNet:
         for i in range(n):
             si, ws = side[i], wss[i]
             si.wait_event(fork)                       # inputs (and the previous use of the outputs) are ordered on `cur`
-            off = (-ws.data_ptr()) % 256
-            if self.poison_workspace:
-                with torch.cuda.stream(si):
-                    ws.fill_(0xFF)
+            ws_ptr, ws_bytes = self._aligned(ws)
+            self._poison(ws, si)
             sl = slice(i * h, (i + 1) * h)
             o = _lib.AdaposeOut(*[out[n][sl].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
             a = [t[sl] for t in args]                  # leading-dimension slices of contiguous tensors: contiguous views
-            _lib.check(self.lib.rgbm_adapose_forward_ex(self._h, h, *[_lib.ptr(t) for t in a], C.c_void_p(ws.data_ptr() + off),
-                                                        ws.numel() - off, C.byref(o), 0, _lib.stream_ptr(si)), "rgbm_adapose_forward")
+            _lib.check(self.lib.rgbm_adapose_forward_ex(self._h, h, *[_lib.ptr(t) for t in a], C.c_void_p(ws_ptr),
+                                                        ws_bytes, C.byref(o), 0, _lib.stream_ptr(si)), "rgbm_adapose_forward")
         for si in side:
             join = torch.cuda.Event()
             join.record(si)
@@ -288,8 +290,7 @@ class AdaPoseNet:
             self._ws = None
             self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
             self._ws_B = None                         # sized by bytes, not by a batch: a plain forward sizes its own again
-        off = (-self._ws.data_ptr()) % 256
-        return self._ws.data_ptr() + off, self._ws.numel() - off
+        return self._aligned(self._ws)
 
     def _pool_records(self, pool) -> int:
         if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()):
@@ -310,9 +311,7 @@ class AdaPoseNet:
         n = C.c_size_t()
         _lib.check(self.lib.rgbm_adapose_features_workspace_bytes(self._h, V, C.byref(n)), "rgbm_adapose_features_workspace_bytes")
         ws_ptr, ws_bytes = self._workspace_at_least(n.value)
-        if self.poison_workspace:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-                self._ws.fill_(0xFF)
+        self._poison(self._ws, stream)
         _lib.check(self.lib.rgbm_adapose_features(self._h, V, _lib.ptr(img), _lib.ptr(slots), _lib.ptr(pool), records, C.c_void_p(ws_ptr),
                                                   ws_bytes, _lib.stream_ptr(stream)), "rgbm_adapose_features")
         self._last_feat = (img, slots)                    # keep inputs alive until the stream has consumed them
@@ -331,19 +330,10 @@ class AdaPoseNet:
         assert s1.shape == (B,) and s2.shape == (B,) and ch1.shape == (B, 1024) and ch2.shape == ch1.shape
         assert P1.shape == (B, 4, 4) and P2.shape == (B, 4, 4) and dep.shape == (B, 24)
         records = self._pool_records(pool)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        out = {
-            "view1_nocs": torch.empty(B, 1024, 3, **f32), "view2_nocs": torch.empty(B, 1024, 3, **f32),
-            "view1_depth": torch.empty(B, 1024, **f32), "view2_depth": torch.empty(B, 1024, **f32),
-            "view1_r": torch.empty(B, 3, 3, **f32), "view2_r": torch.empty(B, 3, 3, **f32),
-            "view1_t": torch.empty(B, 3, **f32), "view2_t": torch.empty(B, 3, **f32),
-            "view1_s": torch.empty(B, 3, **f32), "view2_s": torch.empty(B, 3, **f32),
-        }
+        out = self._empty_outputs(B)
         o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
         ws_ptr, ws_bytes = self._workspace_at_least(self.workspace_bytes(B))
-        if self.poison_workspace:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-                self._ws.fill_(0xFF)
+        self._poison(self._ws, stream)
         _lib.check(self.lib.rgbm_adapose_forward_cached(self._h, B, _lib.ptr(pool), records, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(ch1),
                                                         _lib.ptr(ch2), _lib.ptr(P1), _lib.ptr(P2), _lib.ptr(dep), C.c_void_p(ws_ptr), ws_bytes,
                                                         C.byref(o), _lib.stream_ptr(stream)), "rgbm_adapose_forward_cached")
@@ -356,7 +346,7 @@ class AdaPoseNet:
         """Debug/test access to a named intermediate of the last forward (fp32, flat)."""
         if self._last_split:
             raise _lib.RgbmError("fetch: the last forward ran as two half batches (split_streams); run it with split_streams=False for taps")
-        if getattr(self, "_last_graph", False):
+        if self._last_graph:
             raise _lib.RgbmError("fetch: the last forward replayed a captured graph (its intermediates live in the graph's own workspace); "
                                  "run it with graph=False for taps")
         buf = torch.empty(max_elems, dtype=torch.float32, device=self.device)

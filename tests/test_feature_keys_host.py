@@ -192,7 +192,7 @@ def test_content_mode_is_a_superset_of_true(monkeypatch):
     monkeypatch.setattr(em, "prepare_inputs", lambda *a, **kw: {"frame_map": kw.get("frame_map")})
     for mode in (True, "content"):
         e = _est(hip_feature_cache=mode)
-        monkeypatch.setattr(e, "_update_features", lambda *a: seen.append(("update", a[3])) or "CACHED")
+        monkeypatch.setattr(e._slots, "update", lambda *a: seen.append(("update", a[3])) or "CACHED")
         monkeypatch.setattr(e, "_estimate_prepared", lambda a, b, E1, E2, K, cached=None: seen.append(("run", cached)) or "BOX")
         assert e.estimate_device_indexed("K", "rgb", "mask", "E1", "E2", [0], [1], fresh=[1]) == "BOX"
     assert seen == [("update", [1]), ("run", "CACHED")] * 2
@@ -202,9 +202,9 @@ def test_content_mode_is_a_superset_of_true(monkeypatch):
 def test_other_modes_construct_no_table(mode):
     est = _est(hip_feature_cache=mode)
     assert est.feature_cache is bool(mode) and est.feature_content is False
-    assert est._key_table is None and est._key_pool is None
+    assert est._content.table is None and est._content.pool is None
     est.invalidate_features()                               # nothing to clear, nothing built
-    assert est._key_table is None
+    assert est._content.table is None
 
 
 def test_content_table_is_built_with_the_pool_and_cleared_by_invalidate(monkeypatch):
@@ -212,22 +212,58 @@ def test_content_table_is_built_with_the_pool_and_cleared_by_invalidate(monkeypa
     net = _stub_net()
     net.feature_pool = lambda records: torch.empty(int(records), net.feature_bytes, dtype=torch.uint8)
     est = _est(hip_feature_cache="content", net=net)
-    assert est._key_table is None                           # built with the first call, sized by it
-    est._content_reserve(3)
-    assert est._key_table.records == 6 and est._key_pool.shape == (6, 64)
-    est._key_table.assign(_k(1, 2))
-    table = est._key_table
-    est._content_reserve(2)                                 # a smaller call keeps pool and table
-    assert est._key_table is table and len(table) == 2
+    assert est._content.table is None                           # built with the first call, sized by it
+    est._content.reserve(3)
+    assert est._content.table.records == 6 and est._content.pool.shape == (6, 64)
+    est._content.table.assign(_k(1, 2))
+    table = est._content.table
+    est._content.reserve(2)                                 # a smaller call keeps pool and table
+    assert est._content.table is table and len(table) == 2
     est.invalidate_features()
-    assert est._key_table is table and len(table) == 0
+    assert est._content.table is table and len(table) == 0
     table.assign(_k(1))
-    est._content_reserve(5)                                 # a larger call: a larger pool, empty
-    assert est._key_table.records == 10 and len(est._key_table) == 0
-    est._key_table.assign(_k(1))
+    est._content.reserve(5)                                 # a larger call: a larger pool, empty
+    assert est._content.table.records == 10 and len(est._content.table) == 0
+    est._content.table.assign(_k(1))
     net.options["sweep_f16"] = 0                            # records written under other options are not interchangeable
-    est._content_reserve(5)
-    assert len(est._key_table) == 0
+    est._content.reserve(5)
+    assert len(est._content.table) == 0
     fixed = _est(hip_feature_cache="content", hip_feature_cache_records=7, net=net)
-    fixed._content_reserve(100)
-    assert fixed._key_table.records == 7
+    fixed._content.reserve(100)
+    assert fixed._content.table.records == 7
+
+
+# ---------------------------------------------------------------------------------------------------------------- the result protocol
+def test_slot_cache_result_reaches_estimate_prepared(monkeypatch):
+    """estimate_device_indexed(..., fresh=[1]) hands _estimate_prepared the very CachedViews the slot cache returned."""
+    from rgbmanip_amd import estimator as em
+    from rgbmanip_amd.feature_cache import CachedViews
+    monkeypatch.setattr(em, "prepare_inputs", lambda *a, **kw: {"frame_map": kw.get("frame_map")})
+    est = _est(hip_feature_cache=True)
+    views = CachedViews("POOL", "S1", "S2", "OK")
+    calls, seen = [], []
+    monkeypatch.setattr(est._slots, "update", lambda *a: calls.append(a) or views)
+    monkeypatch.setattr(est, "_estimate_prepared", lambda a, b, E1, E2, K, cached=None: seen.append(cached) or "BOX")
+    assert est.estimate_device_indexed("K", "rgb", "mask", "E1", "E2", [0], [1], fresh=[1]) == "BOX"
+    assert calls == [("rgb", "mask", est.cfg["img_size"], [1], [0], [1], est.prepare_seed)]
+    assert len(seen) == 1 and seen[0] is views and seen[0].pool == "POOL" and seen[0].ok == "OK"
+    assert est.estimate_device_indexed("K", "rgb", "mask", "E1", "E2", [0], [1]) == "BOX" and seen[1] is None      # no fresh: the plain path
+
+
+def test_content_finish_overflow_returns_none_and_counts_one_bypass(monkeypatch):
+    """Three distinct crops, two records: finish returns None (the caller runs the plain path), feature_cache_bypassed goes up by
+    exactly one, the table is unchanged and no view is counted as computed."""
+    import torch
+    from rgbmanip_amd.feature_cache import PendingKeys
+    net = _stub_net()
+    net.feature_pool = lambda records: torch.empty(int(records), net.feature_bytes, dtype=torch.uint8)
+    est = _est(hip_feature_cache="content", hip_feature_cache_records=2, net=net)
+    est._content.reserve(2)
+    stream = object()
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: stream)
+    keys = torch.from_numpy(_k(1, 2, 3, 1).view(np.int64).copy())
+    pend = PendingKeys({}, {}, torch.zeros(4, 3, 2, 2), None, keys, types.SimpleNamespace(synchronize=lambda: None), stream)
+    assert est.feature_cache_bypassed == 0
+    assert est._content.finish(pend) is None
+    assert est.feature_cache_bypassed == 1 and est._content.bypassed == 1
+    assert len(est._content.table) == 0 and est.feature_views_computed == 0

@@ -147,7 +147,7 @@ def test_estimate_device_computes_only_the_new_view(dtype):
         got, c_on = _call_device(on, a, b)
         assert c_off == 2 * n and c_on == count, (name, c_off, c_on)
         _check_boxes(got, want, f"{dtype} call {name}")
-    assert on.feature_cache_bypassed == 0 and on._key_table.records == 2 * n
+    assert on.feature_cache_bypassed == 0 and on._content.table.records == 2 * n
 
 
 def test_numpy_estimate_through_the_chunk_pipeline():
@@ -165,7 +165,7 @@ def test_numpy_estimate_through_the_chunk_pipeline():
         assert isinstance(got, np.ndarray) and got.shape == (n, 8, 3)
         assert on.feature_views_computed - before == count, (name, on.feature_views_computed - before)
         _check_boxes(got, want, f"estimate() call {name}")
-    assert on.feature_cache_bypassed == 0 and on._key_table.records == 2 * n      # sized by the call, not by its chunks
+    assert on.feature_cache_bypassed == 0 and on._content.table.records == 2 * n      # sized by the call, not by its chunks
 
 
 def test_duplicate_crops_are_computed_once():
@@ -197,7 +197,7 @@ def test_eviction_and_overflow():
         wants.append(want)
         assert count == 2 * n, (i, count)
         _check_boxes(got, want, f"records 6, call {i}")
-    assert on._key_table.records == 6 and on.feature_cache_bypassed == 0
+    assert on._content.table.records == 6 and on.feature_cache_bypassed == 0
     got, count = _call_device(on, *calls[3])
     assert count == 0                                                   # the latest call's four records are all there
     got, count = _call_device(on, *calls[0])
@@ -208,7 +208,7 @@ def test_eviction_and_overflow():
     got, count = _call_device(small, *calls[0])
     assert small.feature_cache_bypassed == 1 and count == 2 * n
     assert np.array_equal(got, wants[0])
-    assert len(small._key_table) == 0
+    assert len(small._content.table) == 0
 
 
 def test_invalidate_features_forgets_the_keys():

@@ -142,7 +142,7 @@ def run_boundary(dtype, mode, K, sets, calls, warmup=3):
     res = {"boundary": "estimate() float64 host frames", "dtype": dtype, "cache": mode or "off", "poses": len(K), "calls": calls,
            "ms_per_call_median": round(statistics.median(ms[warmup:]), 2), "ms_per_call_min": round(min(ms[warmup:]), 2),
            "ms_per_call_all": [round(t, 1) for t in ms[warmup:]], "psp_views_per_call": views[warmup:],
-           "bypassed": est.feature_cache_bypassed, "records": 0 if est._key_pool is None else int(est._key_pool.shape[0]),
+           "bypassed": est.feature_cache_bypassed, "records": 0 if est._content.pool is None else int(est._content.pool.shape[0]),
            "feature_bytes": est.estimator.feature_bytes}
     del est
     import gc

@@ -29,6 +29,6 @@ for chunk in (64, 32, 16, 8, 16, 32, 64, 24):
     ms = (time.perf_counter() - t) / 4 * 1e3
     if base is None:
         base = bb
-    print(f"{dt} {fdt.__name__} chunk {chunk}: {ms:.1f} ms per call = {256 / ms * 1e3:.0f} poses/s, pinned {sum(t.numel() * t.element_size() for s in est._pipe_pin for t in s) / 1e9:.2f} GB, max |box - chunk-64 box| {np.abs(bb - base).max():.2e}")
+    print(f"{dt} {fdt.__name__} chunk {chunk}: {ms:.1f} ms per call = {256 / ms * 1e3:.0f} poses/s, pinned {est._pipe.ring.pinned_bytes / 1e9:.2f} GB, max |box - chunk-64 box| {np.abs(bb - base).max():.2e}")
     del est
     torch.cuda.empty_cache()

@@ -5,11 +5,11 @@ os.environ["RGBM_UPLOAD_TRACE"] = "1"
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
-from rgbmanip_amd import synth, estimator as E
+from rgbmanip_amd import synth, estimator as E, upload
 from rgbmanip_amd.config import ADAPOSE_CFGS
 chunk = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 if len(sys.argv) > 2:
-    E._HOST_THREADS = int(sys.argv[2])
+    upload._HOST_THREADS = int(sys.argv[2])
 dev = torch.device("cuda", 0)
 _, d, fr = bench.make_inputs_crop(256, dev, seed=0, keep_frames=True)
 Kh, E1h, E2h = fr["K"].cpu().numpy(), fr["E1"].cpu().numpy(), fr["E2"].cpu().numpy()
@@ -21,4 +21,4 @@ est = E.AdaPoseEstimator_v5(None, dict(ADAPOSE_CFGS["adapose_cabinet"], load=Fal
 for _ in range(3):
     t = time.perf_counter()
     est.estimate(Kh, r1, m1, E1h, r2, m2, E2h)
-    print(f"call: {(time.perf_counter() - t) * 1e3:.1f} ms  (threads {E._HOST_THREADS})", file=sys.stderr)
+    print(f"call: {(time.perf_counter() - t) * 1e3:.1f} ms  (threads {upload._HOST_THREADS})", file=sys.stderr)
