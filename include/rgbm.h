@@ -488,7 +488,8 @@ int rgbm_crop_fingerprint(const float* img, int V, int n_words, uint64_t* keys_o
  *  14     conv0_sweep[_persistent]_kernel (16-bit)            15  conv_igemm_ws64_kernel (16-bit)
  *  16..25 conv3d_tile_kernel 16-bit per layer (conv0..conv6, conv7, conv9, conv11)
  *  26..29 bf16x3: generic implicit GEMM, 3-D layers, conv0 + plane sweep, ws 128 x 256 tile
- *  30     (unused since round 6)                     31 / 32  ws 256 x 128 tile 16-bit / (32: unused since round 6)
+ *  30 / 32 pose_mlp1_kernel / pose_mlp2_kernel: the per-point layers of the pose MLP of a bf16 net, two layers per launch (f16)
+ *  31     ws 256 x 128 tile 16-bit
  *  33     ws 256 x 128 tile bf16x3                   34 / 35 / 36  ws 64 x 256 four-multiply-wave tile bf16x3 / 16-bit / f32
  *  37 / 38 upconv_combine_kernel 16-bit / 4-byte storage                39  upconv_final_kernel
  *  40 / 41 conv_igemm_m32_kernel<T, 128, 64 / 128 / 256>: the 128-pixel tail and small-batch launches of rows 31 / 33 (16-bit / bf16x3;
@@ -520,7 +521,8 @@ int rgbm_crop_fingerprint(const float* img, int V, int n_words, uint64_t* keys_o
  * 134217728 implicit-GEMM request waves: 64-bit global addresses + zero page instead of buffer descriptors (the form before round 5)
  * 268435456 plane sweep of an f16 feature map (bf16 nets, sweep_f16 = 1; fp16 nets since round 6): one workgroup per tile instead of the
  *          persistent kernel            536870912  sparse tail: the round-3..5 point kernel instead of prob_sparse2_kernel
- * 1073741824 256-channel GEMM: tail and small launches on 256-channel x 128-pixel tiles / the 64 x 256 ws tile as in round 5 */
+ * 1073741824 256-channel GEMM: tail and small launches on 256-channel x 128-pixel tiles / the 64 x 256 ws tile as in round 5
+ *  524288  pose MLP of a bf16 net as per-layer launches: conversion, four 1x1 GEMMs, two mean kernels (default: pose_mlp1_kernel + pose_mlp2_kernel) */
 int rgbm_debug_flags(int flags);
 /* Kernel choice - tile shape, and with it the order of the fp32 sums - depends on a launch's GEMM rows, i.e. on the batch size: the
  * same pose in batches of different sizes agrees to the storage type's rounding (1e-6 .. 1e-5 relative in fp32 / bf16x3), not bit for

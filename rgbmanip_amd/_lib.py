@@ -41,9 +41,9 @@ PROF_KERNELS = [
     ("conv3d_tile_kernel<unsigned short, 16, 16, 4, 8, 8, 1, true, false> (conv11)", "bf16"),
 ] + [("conv_igemm_glds_kernel<bx3_t, ...> (all channel tiles)", "bf16x3"), ("conv3d_tile_kernel<bx3_t, ...> (conv1..conv11)", "bf16x3"),
      ("conv0 + fused plane sweep <bx3_t>", "bf16x3"), ("conv_igemm_ws_kernel<rgbm::bx3_t, false, false> (128 channels x 256 pixels)", "bf16x3"),
-     ("unused (conv_igemm_w256_kernel of rounds 2-5)", "bf16"),
+     ("pose_mlp1_kernel (pose_mlp1.0 + pose_mlp1.2 of a bf16 net in one launch)", "bf16"),
      ("conv_igemm_m32_kernel<unsigned short, 256, 256> (256 channels x 256 pixels, 32x32x16 MFMAs; gemm_kernel = 0: conv_igemm_ws_kernel<unsigned short, true, false>, 256 x 128)", "bf16"),
-     ("unused (row-halo ws tile of rounds 2-5)", "bf16"),
+     ("pose_mlp2_kernel (pose_mlp2.0 + pose_mlp2.2 + the sum over points of a bf16 net in one launch)", "bf16"),
      ("conv_igemm_m32_kernel<rgbm::bx3_t, 256, 256> (256 channels x 256 pixels, 32x32x16 MFMAs; gemm_kernel = 0: conv_igemm_ws_kernel<rgbm::bx3_t, true, false>, 256 x 128)", "bf16x3"),
      ("conv_igemm_ws_kernel<rgbm::bx3_t, false, false, true> (64 channels x 256 pixels, four multiply waves)", "bf16x3"),
      ("conv_igemm_ws_kernel<unsigned short, false, false, true> (64 channels x 256 pixels, four multiply waves)", "bf16"),

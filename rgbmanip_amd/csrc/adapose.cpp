@@ -697,21 +697,40 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
   // bf16 nets: the four big per-point layers of the pose MLP run in fp16 storage (fp32 they took 1.8 ms per 512 views at
   // 78 TFLOP/s on the fp32 matrix path); PF96 is produced in fp32 by its two writers and converted once
   const int pdt = pose_dtype();
-  const void* pf_in = bf.PF96;
-  if (pdt == F16) {
-    if (int rc = launch_f32_to_f16(bf.PF96, bf.PF96h, (long long)Vh * P * 96, s)) return rc;
-    pf_in = bf.PF96h;
-  } else if (pdt == BF16X3) {
-    if (int rc = launch_f32_to_bx3(bf.PF96, bf.PF96, (long long)Vh * P * 96, s)) return rc;      // in place: same 4-byte slots
+  // ... and since round 7 as two launches (pose_mlp.hip): neither PF96h, Q128a nor the two 256-channel per-point tensors reach memory;
+  // the slices' sums land where launch_mean_points_partial put them.  Debug flag 524288: the per-layer launches (also taken for a point
+  // count that is not a whole number of slabs per slice, and for layers of another shape)
+  auto pose_layer_ok = [](const ConvLayer& L, int cin, int cout) {
+    return L.dtype == F16 && L.packs.size() == 1 && L.packs[0].ntaps == 1 && L.Cin_pad == cin && L.Cout_pad == cout && L.g.act == ACT_RELU &&
+           L.packs[0].Kpad >= cin && L.bias != nullptr;
+  };
+  const bool pose_fused = pdt == F16 && !(g_debug_flags & DBG_POSE_MLP_R6) && pose_mlp_fits(P) && pose_layer_ok(pm1[0], 96, 128) &&
+                          pose_layer_ok(pm1[1], 128, 128) && pose_layer_ok(pm2[0], 128, 256) && pose_layer_ok(pm2[1], 256, 256);
+  if (pose_fused) {
+    PoseMlpDesc pd{};
+    const ConvLayer* L[4] = {&pm1[0], &pm1[1], &pm2[0], &pm2[1]};
+    for (int l = 0; l < 4; ++l) { pd.w[l] = L[l]->packs[0].w; pd.ldw[l] = L[l]->packs[0].Kpad; pd.bias[l] = L[l]->bias; }
+    pd.pf96 = bf.PF96; pd.vbias = bf.vbias; pd.q128 = bf.Q128b; pd.part128 = (float*)bf.Q128a; pd.part256 = (float*)bf.G256a; pd.V = Vh; pd.P = P;
+    if (int rc = launch_pose_mlp1(pd, s)) return rc;
+    if (int rc = launch_view_linear_mean((const float*)bf.Q128a, P, bf.glob, pm2_0_wfull, pm2_0_bias, bf.vbias, Vh, 128, 256, 256, 128, 0, s)) return rc;
+    if (int rc = launch_pose_mlp2(pd, s)) return rc;
+  } else {
+    const void* pf_in = bf.PF96;
+    if (pdt == F16) {
+      if (int rc = launch_f32_to_f16(bf.PF96, bf.PF96h, (long long)Vh * P * 96, s)) return rc;
+      pf_in = bf.PF96h;
+    } else if (pdt == BF16X3) {
+      if (int rc = launch_f32_to_bx3(bf.PF96, bf.PF96, (long long)Vh * P * 96, s)) return rc;      // in place: same 4-byte slots
+    }
+    if (int rc = pm1[0].run(pf_in, bf.Q128a, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = pm1[1].run(bf.Q128a, bf.Q128b, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
+    // the two means over a view's points are finished by their consumers (the slices' partial sums in Q128a / G256a: free at that point)
+    if (int rc = launch_mean_points_partial(pdt, bf.Q128b, (float*)bf.Q128a, Vh, P, 128, s)) return rc;
+    if (int rc = launch_view_linear_mean((const float*)bf.Q128a, P, bf.glob, pm2_0_wfull, pm2_0_bias, bf.vbias, Vh, 128, 256, 256, 128, 0, s)) return rc;
+    if (int rc = pm2[0].run(bf.Q128b, bf.G256a, Vh, 1, 1, P, 256, nullptr, 0, bf.vbias, 256, s)) return rc;
+    if (int rc = pm2[1].run(bf.G256a, bf.G256b, Vh, 1, 1, P, 256, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = launch_mean_points_partial(pdt, bf.G256b, (float*)bf.G256a, Vh, P, 256, s)) return rc;
   }
-  if (int rc = pm1[0].run(pf_in, bf.Q128a, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
-  if (int rc = pm1[1].run(bf.Q128a, bf.Q128b, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
-  // the two means over a view's points are finished by their consumers (the slices' partial sums in Q128a / G256a: free at that point)
-  if (int rc = launch_mean_points_partial(pdt, bf.Q128b, (float*)bf.Q128a, Vh, P, 128, s)) return rc;
-  if (int rc = launch_view_linear_mean((const float*)bf.Q128a, P, bf.glob, pm2_0_wfull, pm2_0_bias, bf.vbias, Vh, 128, 256, 256, 128, 0, s)) return rc;
-  if (int rc = pm2[0].run(bf.Q128b, bf.G256a, Vh, 1, 1, P, 256, nullptr, 0, bf.vbias, 256, s)) return rc;
-  if (int rc = pm2[1].run(bf.G256a, bf.G256b, Vh, 1, 1, P, 256, nullptr, 0, nullptr, 0, s)) return rc;
-  if (int rc = launch_mean_points_partial(pdt, bf.G256b, (float*)bf.G256a, Vh, P, 256, s)) return rc;
   float* hout[3] = {bf.r6, bf.tv, bf.sv};
   const int hdim[3] = {6, 3, 3};
   if (int rc = launch_pose_heads_mean((const float*)bf.G256a, P, bf.pf2, bf.R, head_w, head_b, hout, hdim, Vh, s)) return rc;      // + Ortho6d -> R

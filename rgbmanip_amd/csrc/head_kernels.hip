@@ -421,8 +421,7 @@ int launch_fuse_points(int dtype, const void* feat, const float* homog, const fl
 // Round 5: kMeanSplit workgroups per view (a slice of P / kMeanSplit points each, partial sums into `part`) and a second launch that adds
 // the slices in a fixed order - one workgroup per view read its 256-512 KB through one CU's latency (20 + 38 us of a 1.49 ms forward at
 // B = 1).  The split does not depend on the batch size, so neither does the order of the sums.
-constexpr int kMeanSplit = 8;
-template <typename TI>
+template <typename TI>      // kMeanSplit = 8: kernels.h
 __global__ __launch_bounds__(256) void mean_points_kernel(const TI* __restrict__ in, float* __restrict__ partial, int P, int C) {
   constexpr int E = 16 / sizeof(TI);
   __shared__ float part[256 * E];

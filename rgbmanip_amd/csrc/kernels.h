@@ -97,6 +97,25 @@ int launch_view_linear_mean(const float* partial, int P, float* mean_out, const 
                             int ldw, int i0, int relu, hipStream_t s);
 int launch_pose_heads_mean(const float* partial, int P, float* mean_out, float* R, float* const w[3][3], float* const b[3][3],
                            float* const out[3], const int odim[3], int V, hipStream_t s);
+constexpr int kMeanSplit = 8;      // slices of P / kMeanSplit points per view whose sums launch_mean_points_partial writes: [V][kMeanSplit][C]
+// pose_mlp.hip: the four per-point layers of the pose MLP of a bf16 net (f16 storage) in two launches.  launch_pose_mlp1: PF96 ->
+// pose_mlp1.0 -> pose_mlp1.2 -> q128 + its slices' column sums (part128); launch_pose_mlp2: q128 -> pose_mlp2.0 (+ vbias) -> pose_mlp2.2 ->
+// the slices' column sums of the f16-rounded result (part256) only.  Both sums in launch_mean_points_partial's layout.
+constexpr int kPoseMlpSlab = 128;      // points a workgroup carries through both layers at a time; a slab never straddles a slice
+struct PoseMlpDesc {
+  const float* pf96;       // [V * P][96] fp32
+  const void* w[4];        // f16 weights [Cout][ldw] of pose_mlp1.0 (96 -> 128), pose_mlp1.2 (128 -> 128), pose_mlp2.0's per-point half (128 -> 256), pose_mlp2.2 (256 -> 256)
+  int ldw[4];
+  const float* bias[4];    // fp32; bias[2] is not read (vbias holds pose_mlp2.0's)
+  const float* vbias;      // [V][256]
+  void* q128;              // [V * P][128] f16
+  float* part128;          // [V][kMeanSplit][128]
+  float* part256;          // [V][kMeanSplit][256]
+  int V, P;
+};
+bool pose_mlp_fits(int P);      // P is a whole number of slabs per slice
+int launch_pose_mlp1(const PoseMlpDesc& d, hipStream_t s);
+int launch_pose_mlp2(const PoseMlpDesc& d, hipStream_t s);
 // the three regression heads (3 x Linear + ReLU each) of every view in one launch; out[h] is [V][odim[h]]
 int launch_pose_heads(const float* pf2, float* const w[3][3], float* const b[3][3], float* const out[3], const int odim[3], int V,
                       hipStream_t s);
@@ -129,7 +148,7 @@ enum DebugFlag {
   DBG_PSP_STAGE_R5 = 1024, DBG_POINT_MLP_R5 = 2048, DBG_TILE_CONV0 = 4096, DBG_NO_KSPLIT = 16384, DBG_L2_SLIM_TILE = 32768,
   DBG_WS_128x256 = 65536, DBG_NO_SLIM64 = 262144, DBG_KORDER_TAPS_OUTER = 1 << 20, DBG_SWEEP_ALT_BLEND = 1 << 21, DBG_SWEEP_DOT2 = 1 << 22,
   DBG_PP_ONE_KERNEL = 1 << 23, DBG_NO_SLIM_SMALL = 1 << 24, DBG_PP_GENERIC_SELECT = 1 << 25, DBG_PP_GUARD = 1 << 26, DBG_GLOBAL_ADDR = 1 << 27,
-  DBG_SWEEP_PER_TILE = 1 << 28, DBG_SPARSE_TAIL_R5 = 1 << 29, DBG_M32_TAILS_R5 = 1 << 30,
+  DBG_SWEEP_PER_TILE = 1 << 28, DBG_SPARSE_TAIL_R5 = 1 << 29, DBG_M32_TAILS_R5 = 1 << 30, DBG_POSE_MLP_R6 = 1 << 19,
 };
 extern int g_debug_flags;
 extern long long g_ws_min_rows;
