@@ -183,6 +183,20 @@ int rgbm_prepare_inputs_ex(const float* rgb_dev, const uint8_t* mask_dev, const 
                            int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out, int32_t* choose_out,
                            float* pts2d_out, double* Kcrop_out, int32_t* window_out, int32_t* valid_out, uint8_t* scratch,
                            void* stream);
+/* rgbm_prepare_inputs_ex on 8-bit frames: rgb_dev [M,H,W,3] u8, a camera's bytes as they are (no float32 copy of the frames).
+ * Byte b means the float32 value fl32(b / 255), correctly rounded — numpy's float32(b) / float32(255); each tap is converted as
+ * (float)((double)b / 255.0), which equals it for all 256 values (b * (1 / 255.f) is one ulp off for 126 of them), and everything
+ * after the tap load is the float path's arithmetic.  Every output is therefore bit-identical to rgbm_prepare_inputs_ex on float32
+ * frames holding fl32(b / 255).  Same arguments, shape limits and error codes; frame_map_dev may be null, frame0 >= 0. */
+int rgbm_prepare_inputs_u8(const uint8_t* rgb_dev, const uint8_t* mask_dev, const double* K_dev, const int32_t* frame_map_dev,
+                           int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out, int32_t* choose_out,
+                           float* pts2d_out, double* Kcrop_out, int32_t* window_out, int32_t* valid_out, uint8_t* scratch,
+                           void* stream);
+/* Float frames -> 8-bit frames, the write side of a byte view queue whose environment hands over float frames:
+ * dst[i] = (uint8) min(max(rintf(src[i] * 255.f), 0), 255), rint = round half to even, NaN -> 0 (+inf -> 255, -inf -> 0).
+ * rintf(fl32(b / 255) * 255.f) == b for every byte b, so quantise -> rgbm_prepare_inputs_u8 is the identity on byte-valued frames.
+ * Any n > 0; src_dev 4-byte aligned, dst_dev any address (wide loads and stores between a scalar head and tail). */
+int rgbm_quantize_frames(const float* src_dev, uint8_t* dst_dev, size_t n, void* stream);
 
 /* Per-env mask extent for the controller's view queue.
  * Replaces: the np.nonzero / np.where loop of ControlInterface.add_view   models/controller/rl_pose.py:130-149

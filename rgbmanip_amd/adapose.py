@@ -431,12 +431,16 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     """Batched device-side `AdaPoseEstimator_v5.prepare_model_input` (`interface_v5.py:58-170`).
 
     rgb [N,H,W,3] float32 in [0,1], mask [N,H,W] (0/1), K [N,3,3]: torch CUDA tensors (or anything torch.as_tensor accepts).
+    A torch.uint8 rgb (a camera's bytes) is read as it is (`rgbm_prepare_inputs_u8`): byte b is the pixel fl32(b / 255), so every
+    output equals bit for bit what the float32 frames b / 255 give, without a float32 copy of the frames.
     With `frame_map` [N] int32, rgb / mask are a pool [M,H,W,..] (e.g. a view queue) and frame f reads entry frame_map[f]
     (negative: no view -> valid 0) — no gather of the selected frames is needed; K stays [N,3,3].
     Returns dict(img [N,3,S,S] f32, choose [N,P] i32, Kcrop [N,3,3] f64, window [N,4] i32, valid [N] i32[, pts2d])."""
     lib = _lib.load()
     dev = rgb.device if isinstance(rgb, torch.Tensor) and rgb.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    rgb = torch.as_tensor(rgb).to(device=dev, dtype=torch.float32).contiguous()
+    rgb = torch.as_tensor(rgb)
+    u8 = rgb.dtype == torch.uint8
+    rgb = rgb.to(device=dev, dtype=torch.uint8 if u8 else torch.float32).contiguous()
     mask = torch.as_tensor(mask).to(device=dev)
     if mask.dtype != torch.uint8:                       # the kernels test for non-zero, so a uint8 mask is used as it is
         mask = (mask != 0).to(torch.uint8)
@@ -459,7 +463,10 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     scratch = torch.empty(N * S * S, dtype=torch.uint8, device=dev)
     tail = (N, H, W, S, P, int(seed) & 0xFFFFFFFF, _lib.ptr(img), _lib.ptr(choose), _lib.ptr(pts2d), _lib.ptr(Kcrop), _lib.ptr(window),
             _lib.ptr(valid), _lib.ptr(scratch), _lib.stream_ptr(stream))
-    if frame0:          # a piece of a larger batch: frame f hashes as frame frame0 + f of the whole batch would
+    if u8:
+        _lib.check(lib.rgbm_prepare_inputs_u8(_lib.ptr(rgb), _lib.ptr(mask), _lib.ptr(K), _lib.ptr(frame_map), int(frame0), *tail),
+                   "rgbm_prepare_inputs_u8")
+    elif frame0:        # a piece of a larger batch: frame f hashes as frame frame0 + f of the whole batch would
         _lib.check(lib.rgbm_prepare_inputs_ex(_lib.ptr(rgb), _lib.ptr(mask), _lib.ptr(K), _lib.ptr(frame_map), int(frame0), *tail),
                    "rgbm_prepare_inputs_ex")
     elif frame_map is None:

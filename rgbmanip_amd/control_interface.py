@@ -4,7 +4,9 @@ Mirrors `ControlInterface` of `/root/reference/models/controller/rl_pose.py:14-4
 names and return values — with every per-step array kept on the GPU:
 
 * view queues (`reset_queue`, `add_view`, `add_bbox`, rl_pose.py:85-156): frames, masks and camera matrices stay CUDA
-  tensors (float32 frames instead of float64 host arrays); the per-env mask extent comes from `rgbm_mask_extent`;
+  tensors (float32 frames instead of float64 host arrays, or with cfg controller.hip_queue_dtype "uint8" the camera's 8-bit
+  pixels: a quarter of the queue's bytes, same estimates for byte-valued frames); the per-env mask extent comes from
+  `rgbm_mask_extent`;
 * policy encoders (`get_observation`, `get_state`, :158-187);
 * `get_estimation` (:189-223): the two most recent usable views per env are selected by index arithmetic instead of the
   O(max_steps * N) Python loop copying 480x640x3 images, and the estimator is entered through `estimate_device`;
@@ -65,7 +67,7 @@ class ControlInterface:
         self.pose_min = np.asarray(cfg["controller"]["pose_min"], dtype=np.float64)
         self.pose_max = np.asarray(cfg["controller"]["pose_max"], dtype=np.float64)
         self.pose_mid = (self.pose_min + self.pose_max) / 2
-        self._init_common(device)
+        self._init_common(device, cfg["controller"].get("hip_queue_dtype", "float32"))
         self.action_space = Box(low=-1.5, high=1.5, shape=(7 + self.max_steps,))
         self.state_space = Box(low=-1.5, high=1.5, shape=(self.max_steps * 15,))
         self.observation_space = Box(low=-1.5, high=1.5, shape=(self.max_steps * 12,))
@@ -80,17 +82,23 @@ class ControlInterface:
         self.reset_robot()
 
     @classmethod
-    def queue_only(cls, num_envs: int, pose_estimator, max_steps: int, device=None):
+    def queue_only(cls, num_envs: int, pose_estimator, max_steps: int, device=None, queue_dtype="float32"):
         """Only the view queue / encoders / `get_estimation` half, without a vec-env (`max_steps` as the reference's
-        attribute, i.e. cfg max_steps + 1)."""
+        attribute, i.e. cfg max_steps + 1; `queue_dtype` as cfg controller.hip_queue_dtype)."""
         self = cls.__new__(cls)
         self.env, self.estimator, self.manipulation, self.cfg = None, pose_estimator, None, None
         self.num_envs, self.max_steps = int(num_envs), int(max_steps)
-        self._init_common(device)
+        self._init_common(device, queue_dtype)
         self.reset_queue()
         return self
 
-    def _init_common(self, device):
+    def _init_common(self, device, queue_dtype="float32"):
+        # hip_queue_dtype: what a slot of image_queue holds.  "float32" (default): the frame as the env hands it over.  "uint8": the
+        # camera's 8-bit pixels, 921 600 bytes per slot and env instead of 3 686 400; byte b is the pixel fl32(b / 255) everywhere it is
+        # read (rgbm_prepare_inputs_u8, _save_data), a float frame is stored as rint(x * 255) (rgbm_quantize_frames)
+        if queue_dtype not in ("float32", "uint8"):
+            raise ValueError(f'controller.hip_queue_dtype is "float32" or "uint8", got {queue_dtype!r}')
+        self.queue_dtype = torch.uint8 if queue_dtype == "uint8" else torch.float32
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.H, self.W = CAMERA_INTRINSIC[-1], CAMERA_INTRINSIC[-2]
         self.lib = _lib.load()
@@ -109,7 +117,12 @@ class ControlInterface:
 
         def host(queue_name, k):
             if (queue_name, k) not in cache:
-                cache[(queue_name, k)] = getattr(self, queue_name)[k].to(torch.float64).cpu().numpy()
+                q = getattr(self, queue_name)[k]
+                if queue_name == "image_queue" and q.dtype == torch.uint8:
+                    # the value the float32 queue would have held: fl32(b / 255), correctly rounded (numpy's float32 division is)
+                    cache[(queue_name, k)] = (q.cpu().numpy().astype(np.float32) / np.float32(255)).astype(np.float64)
+                else:
+                    cache[(queue_name, k)] = q.to(torch.float64).cpu().numpy()
             return cache[(queue_name, k)]
 
         for e, obj_config in enumerate(current_obj_config):
@@ -130,7 +143,7 @@ class ControlInterface:
         z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=dev)
         if getattr(self, "image_queue", None) is None:
             # allocated (zeroed) once: a slot is only ever read while `available` marks it, and it is marked when written
-            self.image_queue = z(T, N, H, W, 3, dtype=torch.float32)
+            self.image_queue = z(T, N, H, W, 3, dtype=self.queue_dtype)
             self.mask_queue = z(T, N, H, W, dtype=torch.uint8)
         self.bbox_queue = z(T, N, 4)
         self.pose_queue = z(T, N, 7)
@@ -168,7 +181,14 @@ class ControlInterface:
         self._fresh_rows.append(k)
         cam = image["camera0"]
         mask = (self._dev(cam["Mask"], torch.uint8) != 0).to(torch.uint8).contiguous()
-        self.image_queue[k] = self._dev(cam["Color"], torch.float32)
+        color = torch.as_tensor(cam["Color"])
+        if self.queue_dtype == torch.float32 or color.dtype == torch.uint8:
+            self.image_queue[k] = color.to(device=self.device, dtype=self.queue_dtype)
+        else:                                    # a float frame into the byte queue: rint(x * 255), straight into the slot
+            color = color.to(device=self.device, dtype=torch.float32).contiguous()
+            assert color.numel() == self.image_queue[k].numel()
+            _lib.check(self.lib.rgbm_quantize_frames(_lib.ptr(color), _lib.ptr(self.image_queue[k]), color.numel(), _lib.stream_ptr()),
+                       "rgbm_quantize_frames")
         self.mask_queue[k] = mask
         self.pose_queue[k] = self._dev(cam_pose, torch.float64)
         self.intrinsic_queue[k] = self._dev(cam["Intrinsic"], torch.float64)

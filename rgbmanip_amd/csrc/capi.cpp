@@ -611,6 +611,19 @@ extern "C" int rgbm_prepare_inputs_ex(const float* rgb_dev, const uint8_t* mask_
                                Kcrop_out, window_out, valid_out, scratch, (hipStream_t)stream, frame0);
 }
 
+extern "C" int rgbm_prepare_inputs_u8(const uint8_t* rgb_dev, const uint8_t* mask_dev, const double* K_dev, const int32_t* frame_map_dev,
+                                      int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out, int32_t* choose_out,
+                                      float* pts2d_out, double* Kcrop_out, int32_t* window_out, int32_t* valid_out, uint8_t* scratch,
+                                      void* stream) {
+  RGBM_REQUIRE(frame0 >= 0, "prepare_inputs_u8 frame0");
+  return launch_prepare_inputs_u8(rgb_dev, mask_dev, K_dev, frame_map_dev, N, H, W, S, P, seed, img_out, choose_out, pts2d_out,
+                                  Kcrop_out, window_out, valid_out, scratch, (hipStream_t)stream, frame0);
+}
+
+extern "C" int rgbm_quantize_frames(const float* src_dev, uint8_t* dst_dev, size_t n, void* stream) {
+  return launch_quantize_frames(src_dev, dst_dev, n, (hipStream_t)stream);
+}
+
 extern "C" int rgbm_adapose_postprocess_pnp(int B, int P, uint32_t seed, const float* nocs1, const float* pts2d1, const float* nocs2,
                                             const float* pts2d2, const double* K, const double* E1, const double* E2, double* bbox_out,
                                             double* srt_out, int32_t* info_out, int32_t* valid_out, void* stream) {

@@ -186,6 +186,12 @@ void prob_sparse_pack(const float* w, const float* scale, std::vector<float>& pa
 int launch_prepare_inputs(const float* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W, int S, int P,
                           unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
                           unsigned char* small_scratch, hipStream_t s, int frame0 = 0);
+// the same on 8-bit frames [M,H,W,3]: byte b is the pixel value fl32(b / 255), everything after the tap load is the float path's
+int launch_prepare_inputs_u8(const unsigned char* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W,
+                             int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
+                             unsigned char* small_scratch, hipStream_t s, int frame0 = 0);
+// dst[i] = min(max(rint(src[i] * 255), 0), 255), NaN -> 0: float frames into an 8-bit view queue (any n, src 4-byte / dst 1-byte aligned)
+int launch_quantize_frames(const float* src, unsigned char* dst, size_t n, hipStream_t s);
 
 int launch_umeyama_ransac(const float* nocs, const float* depth, const int* choose, const double* Kc, const double* E1,
                           double* bbox, double* srt, int* valid, int B, int P, int img, unsigned seed, hipStream_t s);

@@ -78,7 +78,15 @@ __global__ __launch_bounds__(PRE_THREADS) void mask_window_kernel(const unsigned
 }
 
 // ---- 2. crop + resize: nearest mask, bilinear RGB, ToTensor + Normalize ---------------------------------------------
-__global__ void crop_resize_kernel(const float* __restrict__ rgb /*[N,H,W,3]*/, const unsigned char* __restrict__ mask,
+// A frame pixel as the float32 the arithmetic below takes.  float frames: the value itself.  8-bit frames (a camera's bytes): byte b
+// means fl32(b / 255), correctly rounded — numpy's float32(b) / float32(255) and what the upload path used to write as a float32
+// frame.  The fp64 quotient rounded to float32 equals the correctly rounded float32 quotient for every byte value, b * (1 / 255.f)
+// does not (126 of the 256 values are one ulp off, tools/check_div.py).
+__device__ inline float pixel_value(float v) { return v; }
+__device__ inline float pixel_value(unsigned char b) { return (float)((double)b / 255.0); }
+
+template <typename Px>
+__global__ void crop_resize_kernel(const Px* __restrict__ rgb /*[N,H,W,3]*/, const unsigned char* __restrict__ mask,
                                    const int* __restrict__ frame_map, const int* __restrict__ window, int N, int H, int W, int S,
                                    float* __restrict__ img /*[N,3,S,S]*/, unsigned char* __restrict__ small /*[N,S,S]*/) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -105,12 +113,12 @@ __global__ void crop_resize_kernel(const float* __restrict__ rgb /*[N,H,W,3]*/, 
   float ay, ax;
   taps(dy, h, S, y0, y1, ay);
   taps(dx, w, S, x0, x1, ax);
-  const float* base = rgb + (long long)sf * H * W * 3;
+  const Px* base = rgb + (long long)sf * H * W * 3;
   const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float p00 = base[((long long)(rmin + y0) * W + cmin + x0) * 3 + c], p01 = base[((long long)(rmin + y0) * W + cmin + x1) * 3 + c];
-    const float p10 = base[((long long)(rmin + y1) * W + cmin + x0) * 3 + c], p11 = base[((long long)(rmin + y1) * W + cmin + x1) * 3 + c];
+    const float p00 = pixel_value(base[((long long)(rmin + y0) * W + cmin + x0) * 3 + c]), p01 = pixel_value(base[((long long)(rmin + y0) * W + cmin + x1) * 3 + c]);
+    const float p10 = pixel_value(base[((long long)(rmin + y1) * W + cmin + x0) * 3 + c]), p11 = pixel_value(base[((long long)(rmin + y1) * W + cmin + x1) * 3 + c]);
     const float top = p00 * (1.f - ax) + p01 * ax;
     const float bot = p10 * (1.f - ax) + p11 * ax;
     const float v = top * (1.f - ay) + bot * ay;
@@ -205,6 +213,32 @@ __global__ __launch_bounds__(PRE_THREADS) void choose_kernel(const unsigned char
   }
 }
 
+// ---- float frames -> bytes: the write side of an 8-bit view queue whose environment hands over float frames -----------------
+// q(x) = min(max(rint(x * 255), 0), 255) with rint = round half to even, NaN -> 0 (every comparison with NaN is false).
+__device__ inline unsigned quantize_px(float x) {
+  const float r = rintf(x * 255.f);
+  return r > 0.f ? (r < 255.f ? (unsigned)r : 255u) : 0u;
+}
+
+// A streaming kernel, 4 bytes in and 1 byte out per pixel.  `head` (< 4) scalar pixels bring dst to a 4-byte boundary, then every
+// lane turns 4 consecutive floats into one 32-bit store (a wave: 1 KiB read, 256 B written, both contiguous), then `n - head - 4 *
+// quads` (< 4) scalar pixels.  src + head is only known to be 4-byte aligned: the copy below says so, and hipcc makes one 16-byte
+// load of it (global loads need dword alignment only).
+__global__ __launch_bounds__(256) void quantize_frames_kernel(const float* __restrict__ src, unsigned char* __restrict__ dst, size_t n,
+                                                              unsigned head, size_t quads) {
+  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+  if (gid < head) dst[gid] = (unsigned char)quantize_px(src[gid]);
+  const size_t tail0 = (size_t)head + 4 * quads;
+  if (gid < n - tail0) dst[tail0 + gid] = (unsigned char)quantize_px(src[tail0 + gid]);
+  const float* s4 = src + head;
+  unsigned* d4 = reinterpret_cast<unsigned*>(dst + head);
+  for (size_t q = gid; q < quads; q += step) {
+    float v[4];
+    __builtin_memcpy(v, __builtin_assume_aligned(s4 + 4 * q, 4), sizeof(v));
+    d4[q] = quantize_px(v[0]) | (quantize_px(v[1]) << 8) | (quantize_px(v[2]) << 16) | (quantize_px(v[3]) << 24);
+  }
+}
+
 // ---- ControlInterface.add_view (rl_pose.py:130-149): per-env mask extent, in rows (dim 1) and columns (dim 2) -----------
 __global__ __launch_bounds__(PRE_THREADS) void mask_extent_kernel(const unsigned char* __restrict__ mask, int H, int W,
                                                                    int* __restrict__ ext /*[N,4] rmin,cmin,rmax,cmax*/,
@@ -257,19 +291,46 @@ int launch_mask_extent(const unsigned char* mask, int N, int H, int W, int* ext,
 
 unsigned prepare_mix32(unsigned seed, unsigned frame, unsigned idx) { return mix32(seed, frame, idx); }
 
-int launch_prepare_inputs(const float* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W, int S, int P,
-                          unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
-                          unsigned char* small_scratch, hipStream_t s, int frame0) {
+namespace {
+template <typename Px>
+int prepare_inputs_impl(const Px* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W, int S, int P,
+                        unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
+                        unsigned char* small_scratch, hipStream_t s, int frame0) {
   RGBM_REQUIRE(rgb && mask && K && img && choose && Kcrop && window && valid && small_scratch, "prepare_inputs arguments");
   // the crop window is a square of up to 440 pixels shifted back into the frame (lib/utils.py:10-38 does it for 480 x 640): a
   // smaller frame could not hold it and the shifted window would start at a negative row / column
   RGBM_REQUIRE(N > 0 && H >= 440 && W >= 440 && S > 0 && P > 0 && S * S <= 65536, "prepare_inputs sizes (frames must be at least 440 x 440)");
   hipLaunchKernelGGL(mask_window_kernel, dim3(N), dim3(PRE_THREADS), 0, s, mask, K, frame_map, H, W, S, window, Kcrop, valid);
   const long long tot = (long long)N * S * S;
-  hipLaunchKernelGGL(crop_resize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, rgb, mask, frame_map, window, N, H, W, S, img, small_scratch);
+  hipLaunchKernelGGL(crop_resize_kernel<Px>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, rgb, mask, frame_map, window, N, H, W, S, img, small_scratch);
   const size_t lds = (size_t)S * S * sizeof(unsigned short);
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(choose_kernel), 150 * 1024)) return rc;
   hipLaunchKernelGGL(choose_kernel, dim3(N), dim3(PRE_THREADS), lds, s, small_scratch, window, S, P, seed, choose, pts2d, valid, frame0);
+  RGBM_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+int launch_prepare_inputs(const float* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W, int S, int P,
+                          unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
+                          unsigned char* small_scratch, hipStream_t s, int frame0) {
+  return prepare_inputs_impl(rgb, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
+}
+
+int launch_prepare_inputs_u8(const unsigned char* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W,
+                             int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
+                             unsigned char* small_scratch, hipStream_t s, int frame0) {
+  return prepare_inputs_impl(rgb, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
+}
+
+int launch_quantize_frames(const float* src, unsigned char* dst, size_t n, hipStream_t s) {
+  RGBM_REQUIRE(src && dst && n > 0, "quantize_frames arguments");
+  RGBM_REQUIRE(reinterpret_cast<uintptr_t>(src) % 4 == 0, "quantize_frames: src must be 4-byte aligned");
+  const unsigned head = (unsigned)std::min<size_t>(n, (4 - reinterpret_cast<uintptr_t>(dst) % 4) % 4);
+  const size_t quads = (n - head) / 4;
+  // a memory-bound stream: at most 8 blocks per CU's worth of blocks, the rest of the quads by grid stride
+  const unsigned blocks = (unsigned)std::min<size_t>(2048, std::max<size_t>(1, (quads + 255) / 256));
+  hipLaunchKernelGGL(quantize_frames_kernel, dim3(blocks), dim3(256), 0, s, src, dst, n, head, quads);
   RGBM_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -130,6 +130,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                                                                 graph_max_batch=int(cfg.get("hip_graph_max_batch", 32)),
                                                                 options={**options, "view2_heads": int(self.view2_heads)})
         self._plain_views = 0                 # views the PSPNet has run on in uncached forwards
+        self.frames_u8_native = 0             # frames the device paths have cropped straight from 8-bit pixels (rgbm_prepare_inputs_u8)
         self._slots = SlotFeatureCache(self.estimator)                   # estimate_device_indexed(..., fresh=...)
         self._content = ContentFeatureCache(self.estimator, records)     # estimate / estimate_device with "content"
         self._ring = self._pipe = None        # staging of _upload_frames / of the chunk pipeline, built by the first call that needs them
@@ -214,8 +215,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             S, wp = self.cfg["img_size"], self._pnp_branch()
 
             def prepare(a, b, d):
-                pa = prepare_inputs(self._upload_frames(d[0]), d[2], Kd[a:b], S, 1024, self.prepare_seed, want_pts2d=wp, frame0=a)
-                pb = prepare_inputs(self._upload_frames(d[1]), d[3], Kd[a:b], S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=a)
+                pa = self._prepare(self._upload_frames(d[0]), d[2], Kd[a:b], S, 1024, self.prepare_seed, want_pts2d=wp, frame0=a)
+                pb = self._prepare(self._upload_frames(d[1]), d[3], Kd[a:b], S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=a)
                 return a, b, self._content.keys(pa, pb)
 
             def network(p):
@@ -231,7 +232,14 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         return res
 
     def _upload_frames(self, frames):
-        out, self._ring = frames_to_device(frames, self.estimator.device, self._ring, self._CHUNK_BYTES)
+        out, self._ring = frames_to_device(frames, self.estimator.device, self._ring, self._CHUNK_BYTES, keep_u8=True)
+        return out
+
+    def _prepare(self, rgb, *args, **kw):
+        """`prepare_inputs`, counting the frames it crops straight from bytes (uint8 frames stay uint8 all the way into the kernel)."""
+        out = prepare_inputs(rgb, *args, **kw)
+        if getattr(rgb, "dtype", None) == torch.uint8:
+            self.frames_u8_native += int(out["img"].shape[0])
         return out
 
     def _upload_masks(self, masks):
@@ -239,15 +247,16 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
 
     # ------------------------------------------------------------------ the same pipeline without leaving the device
     def estimate_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0):
-        """`estimate` for frames that already live on the GPU (or get uploaded once): K [N,3,3], rgb [N,H,W,3] float32 in [0,1],
-        mask [N,H,W], E [N,4,4] world->camera.  Returns a CUDA tensor [N,8,3] float64; samples the reference would skip
+        """`estimate` for frames that already live on the GPU (or get uploaded once): K [N,3,3], rgb [N,H,W,3] float32 in [0,1] or
+        uint8 (byte b = the pixel fl32(b / 255); read as bytes, same boxes bit for bit), mask [N,H,W], E [N,4,4] world->camera.
+        Returns a CUDA tensor [N,8,3] float64; samples the reference would skip
         (empty mask) or reject (non-finite box) hold `default_bbox`."""
         S = self.cfg["img_size"]
         dev = self.estimator.device
         Kd = torch.as_tensor(K).to(dev)
         wp = self._pnp_branch()
-        a = prepare_inputs(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, S, 1024, self.prepare_seed, want_pts2d=wp, frame0=frame0)
-        b = prepare_inputs(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=frame0)
+        a = self._prepare(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, S, 1024, self.prepare_seed, want_pts2d=wp, frame0=frame0)
+        b = self._prepare(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=frame0)
         if self.feature_content:      # one host synchronisation per call: the keys must be on the host before the network can be enqueued
             self._content.reserve(int(Kd.shape[0]))
             return self._estimate_keyed(self._content.keys(a, b), E1, E2, Kd)
@@ -255,7 +264,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
 
     def estimate_device_indexed(self, K, rgb_pool, mask_pool, E1, E2, map1, map2, fresh=None):
         """`estimate_device` reading the two views of sample i from entries map1[i] / map2[i] of a frame pool
-        (rgb_pool [M,H,W,3] float32, mask_pool [M,H,W] uint8 — e.g. the controller's view queue) instead of from gathered
+        (rgb_pool [M,H,W,3] float32 or uint8, mask_pool [M,H,W] uint8 — e.g. the controller's view queue) instead of from gathered
         batches; a negative entry means "no such view" (the reference hands an all-zero frame over, which is skipped).
         K [N,3,3] (both views use it, interface_v5.py:213-227), E1 / E2 [N,4,4].
 
@@ -269,8 +278,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         cached = None
         if self.feature_cache and fresh is not None:
             cached = self._slots.update(rgb_pool, mask_pool, S, fresh, map1, map2, self.prepare_seed)
-        a = prepare_inputs(rgb_pool, mask_pool, K, S, 1024, self.prepare_seed, frame_map=map1, want_pts2d=wp)
-        b = prepare_inputs(rgb_pool, mask_pool, K, S, 1024, self.prepare_seed + 1, frame_map=map2, want_pts2d=wp)
+        a = self._prepare(rgb_pool, mask_pool, K, S, 1024, self.prepare_seed, frame_map=map1, want_pts2d=wp)
+        b = self._prepare(rgb_pool, mask_pool, K, S, 1024, self.prepare_seed + 1, frame_map=map2, want_pts2d=wp)
         return self._estimate_prepared(a, b, E1, E2, K, cached=cached)
 
     def invalidate_features(self):

@@ -105,12 +105,15 @@ class StagingRing:
         return [d[:rows] for d in self.dev[slot]]
 
 
-def frames_to_device(frames, device, ring, chunk_bytes):
-    """[N,H,W,3] host frames (float64 / float32 in [0,1], or uint8) -> CUDA float32 [N,H,W,3] in [0,1].  Frames that already are
-    CUDA tensors pass through.  A pool of host threads copies each chunk into one of two pinned staging buffers while the previous
-    chunk's copy is in flight; float frames are cast to float32 by that copy (3.8 GB of float64 frames arrive per call at N = 256 and
-    cross PCIe as 1.9 GB), uint8 frames cross as bytes and are scaled on the device.  Returns (frames, the ring to hand in next time)."""
+def frames_to_device(frames, device, ring, chunk_bytes, keep_u8=False):
+    """[N,H,W,3] host frames (float64 / float32 in [0,1], or uint8) -> CUDA float32 [N,H,W,3] in [0,1]; with `keep_u8`, uint8 frames
+    (host or CUDA) stay uint8 on the device — `prepare_inputs` reads bytes as the same pixel values (rgbm_prepare_inputs_u8), so the
+    float32 copy and its pass over the frames are not needed.  Frames that already are CUDA tensors pass through.  A pool of host
+    threads copies each chunk into one of two pinned staging buffers while the previous chunk's copy is in flight; float frames are cast to float32 by that copy (3.8 GB of float64 frames arrive per call at N = 256 and
+    cross PCIe as 1.9 GB), uint8 frames cross as bytes and are scaled on the device (or kept, `keep_u8`).  Returns (frames, the ring to hand in next time)."""
     if isinstance(frames, torch.Tensor) and frames.is_cuda:      # (device-side dtype conversion of an uploaded chunk)
+        if keep_u8 and frames.dtype == torch.uint8:
+            return frames, ring
         return (frames.to(torch.float32) if frames.dtype != torch.uint8 else (frames.to(torch.float64) / 255.0).to(torch.float32)), ring
     src = host_array(frames)
     tdt = _frame_dtype(src)                                # float frames: converted to float32 by the staging copy itself
@@ -118,14 +121,15 @@ def frames_to_device(frames, device, ring, chunk_bytes):
     per = max(1, int(np.prod(src.shape[1:]))) * (1 if src.dtype == np.uint8 else 4)
     rows = max(1, min(n, chunk_bytes // per))
     ring = StagingRing.matching(ring, rows, [src.shape[1:]], [tdt], device)
-    out = torch.empty(tuple(src.shape), dtype=torch.float32, device=device)
+    as_bytes = keep_u8 and src.dtype == np.uint8
+    out = torch.empty(tuple(src.shape), dtype=torch.uint8 if as_bytes else torch.float32, device=device)
     for i, a in enumerate(range(0, n, rows)):
         b, k = min(a + rows, n), i & 1
         ring.wait(k)
         ring.stage(k, [src], a, b, ["frame"])
         d, = ring.copy(k, b - a)
         # stream-ordered: this conversion runs before the copy that next overwrites the slot's device buffer (two chunks later)
-        if src.dtype == np.uint8:
+        if src.dtype == np.uint8 and not as_bytes:
             # x / 255 through float64: torch's float32 division on ROCm is not correctly rounded (126 of the 256 byte values
             # differ from numpy's float32(x) / float32(255) by one ulp, tools/check_div.py); the float64 quotient rounded to
             # float32 equals the correctly rounded float32 quotient for every byte value
