@@ -261,6 +261,15 @@ typedef struct rgbm_synth_scene {
 } rgbm_synth_scene;
 int rgbm_synth_camera(const rgbm_synth_scene* scene, double* K_dev, double* E_dev, double* rays_dev, void* stream);
 int rgbm_synth_render(const rgbm_synth_scene* scene, const double* rays_dev, float* color_dev, uint8_t* mask_dev, void* stream);
+/* The same camera delivering bytes, e.g. straight into a slot of an 8-bit view queue: one kernel instead of render -> quantise ->
+ * mask extent.  color_dev [N,H,W,3] u8 is bit for bit rgbm_quantize_frames of the frame rgbm_synth_render writes for this scene
+ * (per channel the same float64 expression, rounded to float32, then min(max(rintf(x * 255.f), 0), 255)); mask_dev [N,H,W] u8 is
+ * rgbm_synth_render's 0 / 1 mask.  extent_dev [N,4] i32 = (row min, col min, row max, col max) and count_dev [N] i32 are what
+ * rgbm_mask_extent returns on that mask ((2H, 2W, 0, 0) and 0 for an env without a hit); the entry point initialises them itself
+ * on `stream`.  Both may be NULL (colour and mask only); exactly one NULL is an argument error.  Any H, W and any output
+ * addresses: 32-bit stores when H*W % 4 == 0 and color_dev, mask_dev are 4-byte aligned, byte stores otherwise. */
+int rgbm_synth_render_u8(const rgbm_synth_scene* scene, const double* rays_dev, uint8_t* color_dev, uint8_t* mask_dev,
+                         int32_t* extent_dev, int32_t* count_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * PPO rollout storage.

@@ -165,6 +165,7 @@ SIGNATURES = {
     "rgbm_control_grasp_frame": (_i, [_vp, _i, _vp, _vp, _vp]),
     "rgbm_synth_camera": (_i, [C.POINTER(SynthScene), _vp, _vp, _vp, _vp]),
     "rgbm_synth_render": (_i, [C.POINTER(SynthScene), _vp, _vp, _vp, _vp]),
+    "rgbm_synth_render_u8": (_i, [C.POINTER(SynthScene), _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_debug_flags": (_i, [_i]),
     "rgbm_set_tuning": (_i, [C.c_char_p, _i64]),
     "rgbm_prof_rows": (_i, []),

@@ -6,7 +6,8 @@ names and return values — with every per-step array kept on the GPU:
 * view queues (`reset_queue`, `add_view`, `add_bbox`, rl_pose.py:85-156): frames, masks and camera matrices stay CUDA
   tensors (float32 frames instead of float64 host arrays, or with cfg controller.hip_queue_dtype "uint8" the camera's 8-bit
   pixels: a quarter of the queue's bytes, same estimates for byte-valued frames); the per-env mask extent comes from
-  `rgbm_mask_extent`;
+  `rgbm_mask_extent`, or with cfg controller.hip_render_to_queue the env renders colour bytes, mask, K, E and the extent
+  straight into the slot (`env.render_into`, one kernel, no intermediate frame);
 * policy encoders (`get_observation`, `get_state`, :158-187);
 * `get_estimation` (:189-223): the two most recent usable views per env are selected by index arithmetic instead of the
   O(max_steps * N) Python loop copying 480x640x3 images, and the estimator is entered through `estimate_device`;
@@ -68,6 +69,15 @@ class ControlInterface:
         self.pose_max = np.asarray(cfg["controller"]["pose_max"], dtype=np.float64)
         self.pose_mid = (self.pose_min + self.pose_max) / 2
         self._init_common(device, cfg["controller"].get("hip_queue_dtype", "float32"))
+        # hip_render_to_queue: the env renders every view straight into its slot of the byte queue (env.render_into: colour bytes, 0 / 1
+        # mask, K, E, mask extent and count from one kernel) instead of get_image() -> quantise -> mask pass -> copies -> rgbm_mask_extent
+        self.render_to_queue = bool(cfg["controller"].get("hip_render_to_queue", False))
+        if self.render_to_queue:
+            if self.queue_dtype != torch.uint8:
+                raise ValueError('controller.hip_render_to_queue needs the byte queue (controller.hip_queue_dtype: "uint8")')
+            if not callable(getattr(vec_env, "render_into", None)):
+                raise ValueError(f"controller.hip_render_to_queue needs an env with render_into(color, mask, intrinsic, extrinsic, "
+                                 f"extent, count); {type(vec_env).__name__} has none")
         self.action_space = Box(low=-1.5, high=1.5, shape=(7 + self.max_steps,))
         self.state_space = Box(low=-1.5, high=1.5, shape=(self.max_steps * 15,))
         self.observation_space = Box(low=-1.5, high=1.5, shape=(self.max_steps * 12,))
@@ -101,6 +111,7 @@ class ControlInterface:
         self.queue_dtype = torch.uint8 if queue_dtype == "uint8" else torch.float32
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.H, self.W = CAMERA_INTRINSIC[-1], CAMERA_INTRINSIC[-2]
+        self.render_to_queue = False                 # cfg controller.hip_render_to_queue (needs a vec-env: __init__)
         self.lib = _lib.load()
 
     # ------------------------------------------------------------------ rl_pose.py:56-83
@@ -171,14 +182,22 @@ class ControlInterface:
             self._reset_pose = np.concatenate((pos, ori), axis=-1)
         pose = self._reset_pose
         self.env.cam_move_to(pose, time=2, wait=1, planner="path", robot_frame=True, skip_move=True)
-        image = self.env.get_image()
-        self.add_view(image, self.env.camera_pose(robot_frame=True))
+        self._take_view()
         self.accumulate_steps += 1
+
+    def _take_view(self):
+        """The env's current view into queue slot `accumulate_steps % max_steps`."""
+        if not self.render_to_queue:
+            return self.add_view(self.env.get_image(), self.env.camera_pose(robot_frame=True))
+        k = self.accumulate_steps % self.max_steps
+        ext = torch.empty(self.num_envs, 4, dtype=torch.int32, device=self.device)
+        cnt = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        self.env.render_into(self.image_queue[k], self.mask_queue[k], self.intrinsic_queue[k], self.extrinsic_queue[k], ext, cnt)
+        self._view_added(k, self.env.camera_pose(robot_frame=True), ext, cnt)
 
     # ------------------------------------------------------------------ rl_pose.py:118-150
     def add_view(self, image, cam_pose):
         k = self.accumulate_steps % self.max_steps
-        self._fresh_rows.append(k)
         cam = image["camera0"]
         mask = (self._dev(cam["Mask"], torch.uint8) != 0).to(torch.uint8).contiguous()
         color = torch.as_tensor(cam["Color"])
@@ -190,13 +209,19 @@ class ControlInterface:
             _lib.check(self.lib.rgbm_quantize_frames(_lib.ptr(color), _lib.ptr(self.image_queue[k]), color.numel(), _lib.stream_ptr()),
                        "rgbm_quantize_frames")
         self.mask_queue[k] = mask
-        self.pose_queue[k] = self._dev(cam_pose, torch.float64)
         self.intrinsic_queue[k] = self._dev(cam["Intrinsic"], torch.float64)
         self.extrinsic_queue[k] = self._dev(cam["Extrinsic"], torch.float64)
         ext = torch.empty(self.num_envs, 4, dtype=torch.int32, device=self.device)
         cnt = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.rgbm_mask_extent(_lib.ptr(mask), self.num_envs, self.H, self.W, _lib.ptr(ext), _lib.ptr(cnt),
                                              _lib.stream_ptr()), "rgbm_mask_extent")
+        self._view_added(k, cam_pose, ext, cnt)
+
+    def _view_added(self, k, cam_pose, ext, cnt):
+        """Bookkeeping of a view whose frame, mask, K and E are in slot k (shared by `add_view` and the render-to-queue path): ext
+        [N,4] int32 / cnt [N] int32 = the mask's extent and pixel count per env."""
+        self._fresh_rows.append(k)
+        self.pose_queue[k] = self._dev(cam_pose, torch.float64)
         # the reference marks EVERY env available as soon as any env's mask has a pixel (rl_pose.py:132): kept as is
         anyone = (cnt.sum() > 0).to(torch.float64)
         self.available[k] = anyone
@@ -348,8 +373,7 @@ class ControlInterface:
         no_collision = self.cfg["task"]["name"] in ["cabinet", "drawer"]
         move_res = self.env.cam_move_to(env_action, time=2, wait=0.5, planner="path", robot_frame=True, skip_move=not eval,
                                         no_collision_with_front=no_collision)
-        image = self.env.get_image()
-        self.add_view(image, self.env.camera_pose(robot_frame=True))
+        self._take_view()
         pred_bbox = self.get_estimation()
         gt_bbox = self.env.get_observation(gt=True)["handle_bbox"]
         self.add_bbox(pred_bbox, gt_bbox)

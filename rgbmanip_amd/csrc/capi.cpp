@@ -665,6 +665,12 @@ extern "C" int rgbm_synth_render(const rgbm_synth_scene* scene, const double* ra
   return rgbm::launch_synth_render(*reinterpret_cast<const rgbm::SynthScene*>(scene), rays_dev, color_dev, mask_dev,
                                    (hipStream_t)stream);
 }
+extern "C" int rgbm_synth_render_u8(const rgbm_synth_scene* scene, const double* rays_dev, uint8_t* color_dev, uint8_t* mask_dev,
+                                    int32_t* extent_dev, int32_t* count_dev, void* stream) {
+  RGBM_REQUIRE(scene, "synth_render_u8 scene");
+  return rgbm::launch_synth_render_u8(*reinterpret_cast<const rgbm::SynthScene*>(scene), rays_dev, color_dev, mask_dev, extent_dev,
+                                      count_dev, (hipStream_t)stream);
+}
 
 extern "C" int rgbm_debug_flags(int flags) { rgbm::g_debug_flags = flags; ++rgbm::g_tuning_version; return 0; }
 

@@ -42,5 +42,8 @@ int launch_lookat_quat(const double* dir, double* quat, int N, int batch_zero, h
 int launch_control_grasp_frame(const double* est, double* center, double* direction, int N, hipStream_t s);
 int launch_synth_camera(const SynthScene& sc, double* K, double* E, double* rays, hipStream_t s);
 int launch_synth_render(const SynthScene& sc, const double* rays, float* color, unsigned char* mask, hipStream_t s);
+// the same frame as bytes (quantize_px of the float colour), the mask, and - both or neither - the mask's extent [N,4] / count [N]
+int launch_synth_render_u8(const SynthScene& sc, const double* rays, unsigned char* color, unsigned char* mask, int* ext, int* count,
+                           hipStream_t s);
 
 }  // namespace rgbm

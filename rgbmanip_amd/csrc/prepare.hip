@@ -12,6 +12,7 @@
 // Built with -ffp-contract=off: numpy rounds every elementwise op separately.
 #include "common.h"
 #include "kernels.h"
+#include "quantize.h"
 
 namespace rgbm {
 
@@ -214,11 +215,7 @@ __global__ __launch_bounds__(PRE_THREADS) void choose_kernel(const unsigned char
 }
 
 // ---- float frames -> bytes: the write side of an 8-bit view queue whose environment hands over float frames -----------------
-// q(x) = min(max(rint(x * 255), 0), 255) with rint = round half to even, NaN -> 0 (every comparison with NaN is false).
-__device__ inline unsigned quantize_px(float x) {
-  const float r = rintf(x * 255.f);
-  return r > 0.f ? (r < 255.f ? (unsigned)r : 255u) : 0u;
-}
+// q(x) = min(max(rint(x * 255), 0), 255) with rint = round half to even, NaN -> 0: quantize_px of quantize.h.
 
 // A streaming kernel, 4 bytes in and 1 byte out per pixel.  `head` (< 4) scalar pixels bring dst to a 4-byte boundary, then every
 // lane turns 4 consecutive floats into one 32-bit store (a wave: 1 KiB read, 256 B written, both contiguous), then `n - head - 4 *

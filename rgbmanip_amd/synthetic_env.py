@@ -126,9 +126,17 @@ class SyntheticMultiVecEnv:
     oriented handle box re-sampled at every `reset`.  `get_image` renders the 480x640 colour frame, handle mask,
     intrinsic and extrinsic of the hand camera with the HIP kernels of csrc/synth_env.hip; every returned array is a
     CUDA tensor.  `cam_move_to` is a reach model: targets farther than `reach` from the shoulder fail and leave the camera
-    half way; it returns `[success, period]` like `merge_obs` of the reference's per-env `(bool, int)` tuples."""
+    half way; it returns `[success, period]` like `merge_obs` of the reference's per-env `(bool, int)` tuples.
 
-    def __init__(self, num_envs: int, device, seed: int = 0, env_id_offset: int = 0, reach: float = 0.55, episodes: int = 32):
+    `color_dtype="uint8"`: the camera delivers bytes, as a real one does — `get_image()["Color"]` is the `torch.uint8` frame
+    `rgbm_synth_render_u8` writes, bit for bit `rgbm_quantize_frames` of the float32 frame.  `render_into` renders such a view
+    straight into caller-owned tensors (a slot of the controller's 8-bit view queue) together with the mask's extent and count."""
+
+    def __init__(self, num_envs: int, device, seed: int = 0, env_id_offset: int = 0, reach: float = 0.55, episodes: int = 32,
+                 color_dtype: str = "float32"):
+        if color_dtype not in ("float32", "uint8"):
+            raise ValueError(f'color_dtype is "float32" or "uint8", got {color_dtype!r}')
+        self.color_dtype = torch.uint8 if color_dtype == "uint8" else torch.float32
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
         self.env_ids = np.arange(env_id_offset, env_id_offset + self.num_envs) + 100000 * int(seed)
@@ -201,13 +209,39 @@ class SyntheticMultiVecEnv:
         K = torch.empty(n, 3, 3, dtype=torch.float64, device=dev)
         E = torch.empty(n, 4, 4, dtype=torch.float64, device=dev)
         rays = torch.empty(n, 12, dtype=torch.float64, device=dev)
-        color = torch.empty(n, CAM_H, CAM_W, 3, dtype=torch.float32, device=dev)
+        color = torch.empty(n, CAM_H, CAM_W, 3, dtype=self.color_dtype, device=dev)
         msk = torch.empty(n, CAM_H, CAM_W, dtype=torch.uint8, device=dev)
         sc = self._scene()
         _lib.check(self.lib.rgbm_synth_camera(_C.byref(sc), _lib.ptr(K), _lib.ptr(E), _lib.ptr(rays), _lib.stream_ptr()), "rgbm_synth_camera")
-        _lib.check(self.lib.rgbm_synth_render(_C.byref(sc), _lib.ptr(rays), _lib.ptr(color), _lib.ptr(msk), _lib.stream_ptr()),
-                   "rgbm_synth_render")
+        if self.color_dtype == torch.uint8:
+            _lib.check(self.lib.rgbm_synth_render_u8(_C.byref(sc), _lib.ptr(rays), _lib.ptr(color), _lib.ptr(msk), None, None,
+                                                     _lib.stream_ptr()), "rgbm_synth_render_u8")
+        else:
+            _lib.check(self.lib.rgbm_synth_render(_C.byref(sc), _lib.ptr(rays), _lib.ptr(color), _lib.ptr(msk), _lib.stream_ptr()),
+                       "rgbm_synth_render")
         return {"camera0": {"Color": color, "Mask": msk, "Intrinsic": K, "Extrinsic": E}}
+
+    def render_into(self, color, mask, intrinsic, extrinsic, extent, count):
+        """The view of `get_image()` as bytes, rendered straight into caller-owned CUDA tensors with no intermediate frame:
+        color [N,480,640,3] uint8, mask [N,480,640] uint8 (0 / 1), intrinsic [N,3,3] and extrinsic [N,4,4] float64, extent [N,4]
+        int32 = (row min, col min, row max, col max) of the mask ((960, 1280, 0, 0) without a hit) and count [N] int32 = its
+        number of pixels.  All must be contiguous and on this env's device; only the [N,12] ray scratch is allocated."""
+        n = self.num_envs
+        want = (("color", color, torch.uint8, (n, CAM_H, CAM_W, 3)), ("mask", mask, torch.uint8, (n, CAM_H, CAM_W)),
+                ("intrinsic", intrinsic, torch.float64, (n, 3, 3)), ("extrinsic", extrinsic, torch.float64, (n, 4, 4)),
+                ("extent", extent, torch.int32, (n, 4)), ("count", count, torch.int32, (n,)))
+        for name, t, dtype, shape in want:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self._cam.device and t.dtype == dtype
+                    and tuple(t.shape) == shape and t.is_contiguous()):
+                got = (t.device, t.dtype, tuple(t.shape), t.is_contiguous()) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"render_into: {name} must be a contiguous {dtype} CUDA tensor of shape {shape} on {self._cam.device}, "
+                                 f"got {got}")
+        rays = torch.empty(n, 12, dtype=torch.float64, device=self.device)
+        sc = self._scene()
+        _lib.check(self.lib.rgbm_synth_camera(_C.byref(sc), _lib.ptr(intrinsic), _lib.ptr(extrinsic), _lib.ptr(rays), _lib.stream_ptr()),
+                   "rgbm_synth_camera")
+        _lib.check(self.lib.rgbm_synth_render_u8(_C.byref(sc), _lib.ptr(rays), _lib.ptr(color), _lib.ptr(mask), _lib.ptr(extent),
+                                                 _lib.ptr(count), _lib.stream_ptr()), "rgbm_synth_render_u8")
 
     # ---- my_vec_env.py:281, open_cabinet.py:191-214
     def get_observation(self, gt=False):
