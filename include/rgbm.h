@@ -130,6 +130,16 @@ int rgbm_adapose_postprocess_ws(int B, int P, int img_size, const float* nocs1, 
                                 const int32_t* choose1, const double* Kcrop, const double* E1, double* bbox_world, double* ts,
                                 int32_t* valid, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The `direct_regression: True` tail of AdaPoseEstimator_v4.predict (interface_v4.py:322-325, 358-378): translation t1 and scale
+ * ||s1|| come from the network's own heads, so no pair median is searched.  half = max |nocs1| over the P points per axis, size = 2 half
+ * scale, get_3d_bbox corners, sRT = [r1 | t1] (r1 is not multiplied by the scale), world frame through inv(E1); the reference's dtypes:
+ * scale, size and the camera-frame box in float32, the world transform in float64.
+ * nocs1 [B,P,3] f32, r1 [B,3,3] f32, t1 [B,3] f32, s1 [B,3] f32, E1 [B,4,4] f64 (device) -> bbox_world [B,8,3] f64, ts [B,4] f64
+ * (t xyz, scale), valid [B] i32 (0 and the +10 default_bbox wherever the box or inv(E1) is non-finite; a NaN stays in its pose).
+ * Any B >= 1 and 1 <= P <= 1024; one launch of one workgroup per pose, no scratch. */
+int rgbm_adapose_postprocess_regressed(int B, int P, const float* nocs1, const float* r1, const float* t1, const float* s1,
+                                       const double* E1, double* bbox_world, double* ts, int32_t* valid, void* stream);
+
 /* The `direct_regression: False`, `use_depth: True` tail of predict: back-projected predicted depth vs
  * predicted NOCS, 128-hypothesis Umeyama RANSAC, final fit over the inliers, bbox to the world frame.
  * Replaces: interface_v5.py:322-339, 348-374; lib/align.py:10-104 (estimateSimilarityUmeyama / estimateSimilarityTransform)
@@ -192,6 +202,17 @@ int rgbm_prepare_inputs_u8(const uint8_t* rgb_dev, const uint8_t* mask_dev, cons
                            int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out, int32_t* choose_out,
                            float* pts2d_out, double* Kcrop_out, int32_t* window_out, int32_t* valid_out, uint8_t* scratch,
                            void* stream);
+/* rgbm_prepare_inputs_ex / rgbm_prepare_inputs_u8 behind one entry point, with the image transform as a switch.
+ * pixel_type 0: rgb_dev is [M,H,W,3] f32, 1: [M,H,W,3] u8 (byte b = fl32(b / 255), as above).
+ * normalize 1: ToTensor + ImageNet Normalize - exactly rgbm_prepare_inputs_ex (pixel_type 0) / rgbm_prepare_inputs_u8 (pixel_type 1), bit
+ *   for bit.  normalize 0: plain ToTensor, img_out holds the bilinear-resized crop itself - what AdaPoseEstimator_v4 feeds its network
+ *   for every task but "pots" (interface_v4.py:52-58).  The switch is a compile-time parameter of the crop kernel; window, mask resize,
+ *   choose, pts2d, Kcrop, valid, the subset hash, shape limits and error codes do not depend on it.
+ * A pixel_type or normalize outside {0, 1} is an argument error: nothing is launched. */
+int rgbm_prepare_inputs_opt(const void* rgb_dev, int pixel_type, int normalize, const uint8_t* mask_dev, const double* K_dev,
+                            const int32_t* frame_map_dev, int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out,
+                            int32_t* choose_out, float* pts2d_out, double* Kcrop_out, int32_t* window_out, int32_t* valid_out,
+                            uint8_t* scratch, void* stream);
 /* Float frames -> 8-bit frames, the write side of a byte view queue whose environment hands over float frames:
  * dst[i] = (uint8) min(max(rintf(src[i] * 255.f), 0), 255), rint = round half to even, NaN -> 0 (+inf -> 255, -inf -> 0).
  * rintf(fl32(b / 255) * 255.f) == b for every byte b, so quantise -> rgbm_prepare_inputs_u8 is the identity on byte-valued frames.

@@ -385,6 +385,26 @@ def postprocess(view1_nocs, view1_depth, view1_r, view1_choose, K_crop, E1, img_
     return bbox, ts, valid
 
 
+def postprocess_regressed(view1_nocs, view1_r, view1_t, view1_s, E1, stream=None):
+    """Device tail of `AdaPoseEstimator_v4.predict` for `direct_regression: True` (`interface_v4.py:322-325, 358-378`): translation
+    view1_t and scale ||view1_s|| from the network's own heads, no pair median.  Returns (bbox_world [B,8,3] f64, ts [B,4] f64 =
+    t xyz, scale, valid [B] i32) CUDA tensors; one launch for any B >= 1 and 1 <= P <= 1024, no scratch."""
+    lib = _lib.load()
+    dev = view1_nocs.device
+    B, P = view1_nocs.shape[:2]
+    f32 = lambda x: torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    nocs, r, t, s = f32(view1_nocs), f32(view1_r), f32(view1_t), f32(view1_s)
+    assert nocs.shape == (B, P, 3) and r.shape == (B, 3, 3) and t.shape == (B, 3) and s.shape == (B, 3), (nocs.shape, r.shape, t.shape, s.shape)
+    E = torch.as_tensor(E1).to(device=dev, dtype=torch.float64).contiguous()
+    assert E.shape == (B, 4, 4), E.shape
+    bbox = torch.empty(B, 8, 3, dtype=torch.float64, device=dev)
+    ts = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    valid = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.rgbm_adapose_postprocess_regressed(B, P, _lib.ptr(nocs), _lib.ptr(r), _lib.ptr(t), _lib.ptr(s), _lib.ptr(E), _lib.ptr(bbox),
+                                                      _lib.ptr(ts), _lib.ptr(valid), _lib.stream_ptr(stream)), "rgbm_adapose_postprocess_regressed")
+    return bbox, ts, valid
+
+
 def postprocess_ransac(view1_nocs, view1_depth, view1_choose, K_crop, E1, img_size: int = 224, seed: int = 0, stream=None):
     """Device tail of `predict` for `direct_regression: False`, `use_depth: True` (`interface_v5.py:322-339, 348-374`,
     `lib/align.py:10-104`): returns (bbox_world [B,8,3] f64, srt [B,13] f64 = scale, R, t, valid [B] i32) CUDA tensors."""
@@ -427,7 +447,7 @@ def postprocess_pnp(view1_nocs, view1_pts2d, view2_nocs, view2_pts2d, K, E1, E2,
 
 
 def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: int = 0, want_pts2d: bool = False, stream=None,
-                   frame_map=None, frame0: int = 0):
+                   frame_map=None, frame0: int = 0, normalize: bool = True):
     """Batched device-side `AdaPoseEstimator_v5.prepare_model_input` (`interface_v5.py:58-170`).
 
     rgb [N,H,W,3] float32 in [0,1], mask [N,H,W] (0/1), K [N,3,3]: torch CUDA tensors (or anything torch.as_tensor accepts).
@@ -435,6 +455,8 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     output equals bit for bit what the float32 frames b / 255 give, without a float32 copy of the frames.
     With `frame_map` [N] int32, rgb / mask are a pool [M,H,W,..] (e.g. a view queue) and frame f reads entry frame_map[f]
     (negative: no view -> valid 0) — no gather of the selected frames is needed; K stays [N,3,3].
+    `normalize=False` (`rgbm_prepare_inputs_opt`): img is the resized crop itself, without the ImageNet mean / std step — the plain
+    `ToTensor` transform of `AdaPoseEstimator_v4` for every task but "pots" (`interface_v4.py:52-58`); every other output is unchanged.
     Returns dict(img [N,3,S,S] f32, choose [N,P] i32, Kcrop [N,3,3] f64, window [N,4] i32, valid [N] i32[, pts2d])."""
     lib = _lib.load()
     dev = rgb.device if isinstance(rgb, torch.Tensor) and rgb.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -463,7 +485,10 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     scratch = torch.empty(N * S * S, dtype=torch.uint8, device=dev)
     tail = (N, H, W, S, P, int(seed) & 0xFFFFFFFF, _lib.ptr(img), _lib.ptr(choose), _lib.ptr(pts2d), _lib.ptr(Kcrop), _lib.ptr(window),
             _lib.ptr(valid), _lib.ptr(scratch), _lib.stream_ptr(stream))
-    if u8:
+    if not normalize:
+        _lib.check(lib.rgbm_prepare_inputs_opt(_lib.ptr(rgb), int(u8), 0, _lib.ptr(mask), _lib.ptr(K), _lib.ptr(frame_map), int(frame0), *tail),
+                   "rgbm_prepare_inputs_opt")
+    elif u8:
         _lib.check(lib.rgbm_prepare_inputs_u8(_lib.ptr(rgb), _lib.ptr(mask), _lib.ptr(K), _lib.ptr(frame_map), int(frame0), *tail),
                    "rgbm_prepare_inputs_u8")
     elif frame0:        # a piece of a larger batch: frame f hashes as frame frame0 + f of the whole batch would

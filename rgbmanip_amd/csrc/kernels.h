@@ -190,6 +190,10 @@ int launch_prepare_inputs(const float* rgb, const unsigned char* mask, const dou
 int launch_prepare_inputs_u8(const unsigned char* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W,
                              int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
                              unsigned char* small_scratch, hipStream_t s, int frame0 = 0);
+// either of the two above (pixel_type 0: float32 frames, 1: 8-bit frames), with (normalize 1) or without (0) the ImageNet mean / std step
+int launch_prepare_inputs_opt(const void* rgb, int pixel_type, int normalize, const unsigned char* mask, const double* K, const int* frame_map,
+                              int N, int H, int W, int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop,
+                              int* window, int* valid, unsigned char* small_scratch, hipStream_t s, int frame0 = 0);
 // dst[i] = min(max(rint(src[i] * 255), 0), 255), NaN -> 0: float frames into an 8-bit view queue (any n, src 4-byte / dst 1-byte aligned)
 int launch_quantize_frames(const float* src, unsigned char* dst, size_t n, hipStream_t s);
 
@@ -207,6 +211,9 @@ int launch_mask_extent(const unsigned char* mask, int N, int H, int W, int* ext,
 int launch_postprocess(const float* nocs, const float* depth, const float* rot, const int* choose, const double* Kc,
                        const double* E1, double* bbox, double* ts_out, int* valid, int B, int P, int img, hipStream_t s,
                        void* scratch = nullptr, size_t scratch_bytes = 0);
+// postproc_regressed.hip: the adapose_v4 direct-regression tail (translation and scale from the network's heads, no pair median)
+int launch_postprocess_regressed(const float* nocs, const float* rot, const float* tr, const float* sv, const double* E1, double* bbox,
+                                 double* ts_out, int* valid, int B, int P, hipStream_t s);
 // microbench.hip: achievable-peak probes for bench.py
 int launch_microbench_mfma(float* scratch, int iters, int random_operands, double* flops, hipStream_t s);
 int microbench_mfma_scratch_floats(int* n);

@@ -78,7 +78,9 @@ __global__ __launch_bounds__(PRE_THREADS) void mask_window_kernel(const unsigned
   valid[f] = 1;
 }
 
-// ---- 2. crop + resize: nearest mask, bilinear RGB, ToTensor + Normalize ---------------------------------------------
+// ---- 2. crop + resize: nearest mask, bilinear RGB, ToTensor [+ Normalize] -------------------------------------------
+// NORM: ImageNet mean / std (interface_v5.py:52-54; interface_v4.py:52-55 for task "pots"); without it the resized crop itself is
+// written (interface_v4.py:56-57: plain ToTensor for every other task).
 // A frame pixel as the float32 the arithmetic below takes.  float frames: the value itself.  8-bit frames (a camera's bytes): byte b
 // means fl32(b / 255), correctly rounded — numpy's float32(b) / float32(255) and what the upload path used to write as a float32
 // frame.  The fp64 quotient rounded to float32 equals the correctly rounded float32 quotient for every byte value, b * (1 / 255.f)
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(PRE_THREADS) void mask_window_kernel(const unsigned
 __device__ inline float pixel_value(float v) { return v; }
 __device__ inline float pixel_value(unsigned char b) { return (float)((double)b / 255.0); }
 
-template <typename Px>
+template <typename Px, bool NORM>
 __global__ void crop_resize_kernel(const Px* __restrict__ rgb /*[N,H,W,3]*/, const unsigned char* __restrict__ mask,
                                    const int* __restrict__ frame_map, const int* __restrict__ window, int N, int H, int W, int S,
                                    float* __restrict__ img /*[N,3,S,S]*/, unsigned char* __restrict__ small /*[N,S,S]*/) {
@@ -123,7 +125,8 @@ __global__ void crop_resize_kernel(const Px* __restrict__ rgb /*[N,H,W,3]*/, con
     const float top = p00 * (1.f - ax) + p01 * ax;
     const float bot = p10 * (1.f - ax) + p11 * ax;
     const float v = top * (1.f - ay) + bot * ay;
-    img[((long long)f * 3 + c) * S * S + p] = (v - mean[c]) / stdv[c];
+    if constexpr (NORM) img[((long long)f * 3 + c) * S * S + p] = (v - mean[c]) / stdv[c];
+    else img[((long long)f * 3 + c) * S * S + p] = v;
   }
 }
 
@@ -289,7 +292,7 @@ int launch_mask_extent(const unsigned char* mask, int N, int H, int W, int* ext,
 unsigned prepare_mix32(unsigned seed, unsigned frame, unsigned idx) { return mix32(seed, frame, idx); }
 
 namespace {
-template <typename Px>
+template <typename Px, bool NORM = true>
 int prepare_inputs_impl(const Px* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W, int S, int P,
                         unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
                         unsigned char* small_scratch, hipStream_t s, int frame0) {
@@ -299,7 +302,7 @@ int prepare_inputs_impl(const Px* rgb, const unsigned char* mask, const double* 
   RGBM_REQUIRE(N > 0 && H >= 440 && W >= 440 && S > 0 && P > 0 && S * S <= 65536, "prepare_inputs sizes (frames must be at least 440 x 440)");
   hipLaunchKernelGGL(mask_window_kernel, dim3(N), dim3(PRE_THREADS), 0, s, mask, K, frame_map, H, W, S, window, Kcrop, valid);
   const long long tot = (long long)N * S * S;
-  hipLaunchKernelGGL(crop_resize_kernel<Px>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, rgb, mask, frame_map, window, N, H, W, S, img, small_scratch);
+  hipLaunchKernelGGL((crop_resize_kernel<Px, NORM>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, rgb, mask, frame_map, window, N, H, W, S, img, small_scratch);
   const size_t lds = (size_t)S * S * sizeof(unsigned short);
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(choose_kernel), 150 * 1024)) return rc;
   hipLaunchKernelGGL(choose_kernel, dim3(N), dim3(PRE_THREADS), lds, s, small_scratch, window, S, P, seed, choose, pts2d, valid, frame0);
@@ -318,6 +321,20 @@ int launch_prepare_inputs_u8(const unsigned char* rgb, const unsigned char* mask
                              int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
                              unsigned char* small_scratch, hipStream_t s, int frame0) {
   return prepare_inputs_impl(rgb, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
+}
+
+// pixel_type 0: float32 frames, 1: 8-bit frames; normalize 1: the two entry points above, 0: the un-normalised crop
+int launch_prepare_inputs_opt(const void* rgb, int pixel_type, int normalize, const unsigned char* mask, const double* K, const int* frame_map,
+                              int N, int H, int W, int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop,
+                              int* window, int* valid, unsigned char* small_scratch, hipStream_t s, int frame0) {
+  RGBM_REQUIRE((pixel_type == 0 || pixel_type == 1) && (normalize == 0 || normalize == 1), "prepare_inputs_opt: pixel_type and normalize are 0 or 1");
+  const float* f32 = static_cast<const float*>(rgb);
+  const unsigned char* u8 = static_cast<const unsigned char*>(rgb);
+  if (normalize)
+    return pixel_type ? launch_prepare_inputs_u8(u8, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0)
+                      : launch_prepare_inputs(f32, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
+  return pixel_type ? prepare_inputs_impl<unsigned char, false>(u8, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0)
+                    : prepare_inputs_impl<float, false>(f32, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
 }
 
 int launch_quantize_frames(const float* src, unsigned char* dst, size_t n, hipStream_t s) {

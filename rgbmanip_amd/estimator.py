@@ -1,4 +1,4 @@
-"""`pose_estimator=adapose_*` plugin: AdaPoseEstimator_v5 on the HIP network.
+"""`pose_estimator=adapose_*` plugin: AdaPoseEstimator_v5 and AdaPoseEstimator_v4 on the HIP network.
 
 Mirrors `/root/reference/models/pose_estimator/AdaPose/interface_v5.py:37-374` and the base class
 `models/pose_estimator/base_estimator.py:5-20`: `AdaPoseEstimator_v5(env, cfg, logger)`,
@@ -11,6 +11,11 @@ batched post-processing launch on the device instead of N serial B=1 calls with 
 The crop/resize/sampling step runs on the host in numpy by default (the reference's arithmetic incl. its global-RNG
 subset) or, with cfg["hip_prepare"] == "device", batched on the GPU (`rgbm_prepare_inputs`; the 1024-subset
 is then a seeded hash, cfg["hip_prepare_seed"]); `estimate_device` takes device-resident frames and never leaves the GPU.
+
+`AdaPoseEstimator_v4` (`interface_v4.py:37-378`, `pose_estimator.name: adapose_v4`) is the same network (lib/network_v4.py is
+lib/network_v5.py bar one blank line) behind an interface that differs in two places, the two hooks of the class below: the crops are
+ImageNet-normalised only for task "pots" (`interface_v4.py:52-58`), and the `direct_regression: True` tail takes translation and scale
+from the network's own heads (`interface_v4.py:322-325`, `rgbm_adapose_postprocess_regressed`) instead of the pair median.
 """
 from __future__ import annotations
 
@@ -20,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, host_prepare
-from .adapose import AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, prepare_inputs
+from .adapose import AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs
 from .feature_cache import CachedViews, ContentFeatureCache, SlotFeatureCache
 from .host_prepare import _resize_linear, _resize_nearest, get_bbox      # noqa: F401  (part of this module's surface)
 from .upload import ChunkPipeline, _nonzero_into, _split, frames_to_device, host_array, masks_to_device      # noqa: F401
@@ -97,8 +102,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         # hip_graph (default off: measured, small batches are bound by their kernels, not by the ~100 launches): batches of at most
         # hip_graph_max_batch poses replay a captured hipGraph.
         # hip_view2_heads (default: only where the box tail reads view-2 outputs, i.e. the PnP branch): the reference network returns
-        # ten outputs and `predict` builds the box from view1_nocs / view1_depth / view1_r alone (interface_v5.py:318-374), so the
-        # cost volume, point heads and pose regression of the view-2 crops are skipped — the backbone still runs on both views
+        # ten outputs and `predict` builds the box from view1_nocs / view1_depth / view1_r alone (interface_v5.py:318-374; v4's regressed
+        # tail: view1_nocs / view1_r / view1_t / view1_s, interface_v4.py:322-325), so the cost volume, point heads and pose regression of
+        # the view-2 crops are skipped — the backbone still runs on both views, and all five view-1 outputs are computed in either mode
         self.view2_heads = bool(cfg.get("hip_view2_heads", self._pnp_branch()))
         # hip_dropout / hip_dropout_seed / hip_as_shipped (dropout_cfg): PSPNet's Dropout2d, seeded, fresh masks on every forward
         norm_mode, drop_p, drop_seed = dropout_cfg(cfg)
@@ -131,7 +137,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                                                                 options={**options, "view2_heads": int(self.view2_heads)})
         self._plain_views = 0                 # views the PSPNet has run on in uncached forwards
         self.frames_u8_native = 0             # frames the device paths have cropped straight from 8-bit pixels (rgbm_prepare_inputs_u8)
-        self._slots = SlotFeatureCache(self.estimator)                   # estimate_device_indexed(..., fresh=...)
+        self._slots = SlotFeatureCache(self.estimator, self._normalize)                 # estimate_device_indexed(..., fresh=...)
         self._content = ContentFeatureCache(self.estimator, records)     # estimate / estimate_device with "content"
         self._ring = self._pipe = None        # staging of _upload_frames / of the chunk pipeline, built by the first call that needs them
         self._dev_consts = None               # (DEFAULT_BBOX, _DEPTH_PLANES) on the device
@@ -153,9 +159,19 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     def feature_cache_bypassed(self):
         return self._content.bypassed
 
+    # ------------------------------------------------------------------ the two places where the v4 interface differs
+    @property
+    def _normalize(self) -> bool:
+        """ImageNet mean / std on the crops (interface_v5.py:52-54: always)."""
+        return True
+
+    def _regressed_tail(self, pred, choose, Kcrop, E1):
+        """The `direct_regression: True` box: scale = exact median over the point pairs, translation from it (interface_v5.py:318-321)."""
+        return postprocess(pred["view1_nocs"], pred["view1_depth"], pred["view1_r"], choose, Kcrop, E1, img_size=self.cfg["img_size"])[0]
+
     # ------------------------------------------------------------------ interface_v5.py:58-170
     def prepare_model_input(self, rgb, mask, intrinsic, resize_size):
-        return host_prepare.prepare_model_input(rgb, mask, intrinsic, resize_size, self.rng, self._frame)
+        return host_prepare.prepare_model_input(rgb, mask, intrinsic, resize_size, self.rng, self._frame, normalize=self._normalize)
 
     # ------------------------------------------------------------------ interface_v5.py:213-227
     def estimate(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
@@ -171,8 +187,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         # a user-set ("hash", s) means "hash subset"; its seeds are the device path's: prepare_seed for view 1, + 1 for view 2
         rng1, rng2 = (("hash", self.prepare_seed), ("hash", self.prepare_seed + 1)) if isinstance(self.rng, tuple) else (self.rng, self.rng)
         for i in range(n):
-            a = host_prepare.prepare_model_input(rgb1_batch[i], view1_mask_batch[i], camera_intrinsic_batch[i], S, rng1, i)
-            b = host_prepare.prepare_model_input(rgb2_batch[i], view2_mask_batch[i], camera_intrinsic_batch[i], S, rng2, i)
+            a = host_prepare.prepare_model_input(rgb1_batch[i], view1_mask_batch[i], camera_intrinsic_batch[i], S, rng1, i, normalize=self._normalize)
+            b = host_prepare.prepare_model_input(rgb2_batch[i], view2_mask_batch[i], camera_intrinsic_batch[i], S, rng2, i, normalize=self._normalize)
             if a[0] is None or b[0] is None:
                 continue
             p1, p2 = np.eye(4), np.eye(4)
@@ -237,7 +253,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
 
     def _prepare(self, rgb, *args, **kw):
         """`prepare_inputs`, counting the frames it crops straight from bytes (uint8 frames stay uint8 all the way into the kernel)."""
-        out = prepare_inputs(rgb, *args, **kw)
+        out = prepare_inputs(rgb, *args, normalize=self._normalize, **kw)
         if getattr(rgb, "dtype", None) == torch.uint8:
             self.frames_u8_native += int(out["img"].shape[0])
         return out
@@ -329,7 +345,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         or Umeyama-RANSAC between predicted NOCS and the back-projected predicted depth (`use_depth`), then the world box."""
         S = self.cfg["img_size"]
         if self.cfg.get("direct_regression", True):
-            return postprocess(pred["view1_nocs"], pred["view1_depth"], pred["view1_r"], choose, Kcrop, E1, img_size=S)[0]
+            return self._regressed_tail(pred, choose, Kcrop, E1)
         if self.cfg.get("use_depth", True):
             return postprocess_ransac(pred["view1_nocs"], pred["view1_depth"], choose, Kcrop, E1, img_size=S,
                                       seed=int(self.cfg.get("hip_ransac_seed", 0)))[0]
@@ -350,3 +366,18 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     def predict(self, camera_intrinsic, rgb1, view1_mask, view1_extrinsic, rgb2, view2_mask, view2_extrinsic):
         return self.estimate([camera_intrinsic], [rgb1], [view1_mask], [view1_extrinsic], [rgb2], [view2_mask],
                              [view2_extrinsic])[0]
+
+
+class AdaPoseEstimator_v4(AdaPoseEstimator_v5):
+    """`pose_estimator.name: adapose_v4` (`interface_v4.py:37-378`): the constructor, call surface and `hip_*` keys of
+    `AdaPoseEstimator_v5` on the same network and checkpoint; upload, device / host prepare, 8-bit frames, the feature caches and the
+    `direct_regression: False` tails are the code above."""
+
+    @property
+    def _normalize(self) -> bool:
+        """interface_v4.py:52-58: ToTensor + ImageNet Normalize for task "pots", plain ToTensor (the crop itself) for every other task."""
+        return self.cfg["task_name"] == "pots"
+
+    def _regressed_tail(self, pred, choose, Kcrop, E1):
+        """interface_v4.py:322-325: tt = view1_t, ts = ||view1_s|| — the network's own heads, no pair median."""
+        return postprocess_regressed(pred["view1_nocs"], pred["view1_r"], pred["view1_t"], pred["view1_s"], E1)[0]

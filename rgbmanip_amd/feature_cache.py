@@ -24,8 +24,9 @@ class CachedViews(NamedTuple):
 class SlotFeatureCache:
     """One record per frame-pool entry; nothing is allocated before the first `update`."""
 
-    def __init__(self, net):
+    def __init__(self, net, normalize=True):
         self.net = net
+        self.normalize = bool(normalize)  # the estimator's image transform: records must hold the maps of the crops its network is fed
         self.pool = None                  # [M + 1, feature_bytes]: one record per frame-pool entry; record M = the all-zero crop's map
         self.valid = None                 # [M + 1] bool on the device: record holds the map of the entry's current frame (M: always)
         self._fresh_dev = {}              # fresh tuple -> (entries, identity intrinsics) on the device
@@ -58,7 +59,7 @@ class SlotFeatureCache:
                 # the crop windows' intrinsics are not needed for the image: any K serves this preparation
                 fd = self._fresh_dev[key] = (torch.as_tensor(np.asarray(fresh, dtype=np.int32)).to(dev),
                                              torch.eye(3, dtype=torch.float64, device=dev).expand(len(fresh), 3, 3).contiguous())
-            img = prepare_inputs(rgb_pool, mask_pool, fd[1], S, 1024, prepare_seed, frame_map=fd[0])["img"]
+            img = prepare_inputs(rgb_pool, mask_pool, fd[1], S, 1024, prepare_seed, frame_map=fd[0], normalize=self.normalize)["img"]
             net.features(img, fd[0], self.pool)
             self.valid[fd[0].long()] = True
             self.views_computed += len(fresh)

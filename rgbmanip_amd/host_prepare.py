@@ -79,8 +79,9 @@ def _subset(choose, rng, frame):
     return choose[keep.nonzero()]
 
 
-def prepare_model_input(rgb, mask, intrinsic, resize_size, rng, frame=0):
-    """(view [3,S,S] tensor, choose [1024], pts2d [1024,2], K of the crop), or four Nones for an empty mask."""
+def prepare_model_input(rgb, mask, intrinsic, resize_size, rng, frame=0, normalize=True):
+    """(view [3,S,S] tensor, choose [1024], pts2d [1024,2], K of the crop), or four Nones for an empty mask.  `normalize=False`: the
+    view is the resized crop itself (plain `ToTensor`, `interface_v4.py:56-57`) instead of the ImageNet-normalised one."""
     rgb = np.asarray(rgb)
     if rgb.dtype == np.uint8:           # transforms.ToTensor scales uint8 images to [0, 1] (interface_v5.py:52-54,149); floats pass as they are
         rgb = rgb.astype(np.float32) / np.float32(255.0)
@@ -102,7 +103,9 @@ def prepare_model_input(rgb, mask, intrinsic, resize_size, rng, frame=0):
     pts2d = np.stack(((choose % resize_size).astype(np.float32) / ratio + cmin,
                       (choose // resize_size).astype(np.float32) / ratio + rmin), axis=-1)
     crop = _resize_linear(rgb[rmin:rmax, cmin:cmax, :], resize_size).astype(rgb.dtype)
-    view = (np.transpose(crop, (2, 0, 1)) - _MEAN.astype(rgb.dtype)[:, None, None]) / _STD.astype(rgb.dtype)[:, None, None]
+    view = np.transpose(crop, (2, 0, 1))
+    if normalize:
+        view = (view - _MEAN.astype(rgb.dtype)[:, None, None]) / _STD.astype(rgb.dtype)[:, None, None]
     K = np.eye(3)
     K[0, 0], K[1, 1] = intrinsic[0, 0] * ratio, intrinsic[1, 1] * ratio
     K[0, 2] = (intrinsic[0, 2] - (float(cmin + cmax) / 2 - float(cmax - cmin + 1) / 2)) * ratio

@@ -315,6 +315,22 @@ def control_view(num_envs: int, step: int, seed: int = 0, H: int = 480, W: int =
     return image, pose, gt
 
 
+def crop_frames(seed: int = 0, H: int = 480, W: int = 640):
+    """Two seeded 8-bit camera frames for the crop goldens and tests of the adapose_v4 transform (tests/golden/postproc_v4.npz):
+    (rgb [2,H,W,3] uint8, mask [2,H,W] uint8, K [2,3,3]).  Frame 0: a large ellipse (more than 1024 resized mask pixels, a 440
+    window); frame 1: a thin sliver at the right border (fewer than 1024: wrap padding, an 80 window shifted back into the frame)."""
+    rng = np.random.default_rng(seed * 1000 + 4004)
+    yy, xx = np.mgrid[0:H, 0:W]
+    base = 128.0 + 60.0 * np.cos(xx / 23.0)[None, :, :, None] + 40.0 * np.sin(yy / 17.0)[None, :, :, None]
+    rgb = np.clip(np.rint(base + rng.normal(0.0, 25.0, (2, H, W, 3))), 0, 255).astype(np.uint8)
+    mask = np.zeros((2, H, W), dtype=np.uint8)
+    mask[0] = (((yy - 250) / 120.0) ** 2 + ((xx - 300) / 170.0) ** 2) < 1.0
+    mask[1] = (((yy - 200) / 22.0) ** 2 + ((xx - 630) / 1.6) ** 2) < 1.0
+    K = np.tile(np.array([[439.31, 0, 320.0], [0, 439.31, 240.0], [0, 0, 1.0]]), (2, 1, 1))
+    K[1, 0, 2] += 1.5
+    return rgb, mask, K
+
+
 CONTROL_REWARD_CFG = {            # cfg/controller/rl.yaml:11-26, verbatim
     "diff_coef": -0.5, "move_success_coef": 8.0, "move_period_coef": -0.0, "far_coef": -2.5, "ori_coef": 0.25,
     "xyz_lookat_coef": -0.05, "bbox_coef": -1.0, "bbox_boundary_coef": -1.0, "have_bbox_coef": 2.0, "center_coef": 12.0,

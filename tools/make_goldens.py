@@ -320,6 +320,133 @@ def gen_postproc(out_dir, net_out, inp):
     np.savez_compressed(os.path.join(out_dir, "postproc.npz"), **cases)
 
 
+def gen_postproc_v4(out_dir):
+    """tests/golden/postproc_v4.npz: the `adapose_v4` interface where it differs from v5 (interface_v4.py:52-58, 322-325, 358-378).
+
+    Poses: the `direct_regression: True` tail on a dozen poses — glue = interface_v4.py:322-325, 358-378 around the reference's own
+    get_3d_bbox / transform_coordinates_3d and the numpy calls of the interface, in its dtypes (ts is a float32 scalar, so the box stays
+    float32 up to the world transform).  Poses 0, 1 are the golden forward's outputs (adapose_b2.npz), the rest seeded.
+    Crops: `AdaPoseEstimator_v4.prepare_model_input` of the reference class itself (built by its own constructor, which chooses the
+    transform from cfg["task_name"]) on the frames of rgbmanip_amd.synth.crop_frames: frame 0 for task one_door_cabinet (plain ToTensor:
+    the un-normalised crop, img_size 224), frame 1 for task pots (ToTensor + Normalize, img_size 112 — the file has to stay small).
+    The build image has neither OpenCV nor torchvision: `cv2.resize` is the documented INTER_NEAREST / INTER_LINEAR arithmetic of
+    oracle/postproc_ref.py (as everywhere in this repository, "parity unpinned" at that step), `transforms.ToTensor / Normalize /
+    Compose` are the stand-ins below, which follow torchvision's documented semantics."""
+    from oracle import postproc_ref
+    from rgbmanip_amd import synth
+
+    def cv2_resize(img, dsize, interpolation):
+        assert dsize[0] == dsize[1]
+        return (postproc_ref.resize_nearest if interpolation == 0 else postproc_ref.resize_linear)(img, dsize[0])
+
+    class ToTensor:
+        def __call__(self, pic):                    # HWC ndarray -> CHW tensor; uint8 is scaled to [0, 1], floats keep dtype and values
+            t = torch.from_numpy(np.ascontiguousarray(np.transpose(pic, (2, 0, 1))))
+            return t.to(torch.float32).div(255) if pic.dtype == np.uint8 else t
+
+    class Normalize:
+        def __init__(self, mean, std):
+            self.mean, self.std = mean, std
+
+        def __call__(self, t):
+            mean = torch.as_tensor(self.mean, dtype=t.dtype)[:, None, None]
+            std = torch.as_tensor(self.std, dtype=t.dtype)[:, None, None]
+            return t.clone().sub_(mean).div_(std)
+
+    class Compose:
+        def __init__(self, ts):
+            self.ts = ts
+
+        def __call__(self, x):
+            for t in self.ts:
+                x = t(x)
+            return x
+
+    sys.modules["cv2"].resize, sys.modules["cv2"].INTER_NEAREST, sys.modules["cv2"].INTER_LINEAR = cv2_resize, 0, 1
+    sys.modules["torchvision"].transforms = stub("torchvision.transforms", ToTensor=ToTensor, Normalize=Normalize, Compose=Compose)
+    stub("env.base_sapien_env", BaseEnv=object)
+    stub("env.sapien_envs.open_cabinet", OpenCabinetEnv=object)
+    stub("env.sapien_envs", open_cabinet=sys.modules["env.sapien_envs.open_cabinet"])
+    from models.pose_estimator.AdaPose.interface_v4 import AdaPoseEstimator_v4
+    from models.pose_estimator.AdaPose.lib import utils as U
+
+    default_bbox = np.asarray([[0, 0, 0], [0, 0, 1], [0, 1, 0], [0, 1, 1], [1, 0, 0], [1, 0, 1], [1, 1, 0], [1, 1, 1]]) + 10.0
+
+    def run_case(nocs, r, t, s, E1):
+        with np.errstate(all="ignore"):
+            tr, tt, ts = r, t, np.linalg.norm(s)                               # interface_v4.py:323-325
+            half_size = np.max(abs(nocs), axis=0)                              # :359-361
+            size = 2 * half_size * ts
+            bbox = U.get_3d_bbox(size)
+            sRT = np.eye(4).astype(np.float32)                                 # :363-366
+            sRT[:3, :3] = tr
+            sRT[:3, 3] = tt.flatten()
+            bbox = U.transform_coordinates_3d(bbox, sRT)
+            assert ts.dtype == np.float32 and bbox.dtype == np.float32, (ts.dtype, bbox.dtype)
+            ex_inv = np.linalg.inv(E1)                                         # :373-378
+            if np.isfinite(ex_inv).all() and np.isfinite(bbox).all():
+                return (ex_inv[:3, :3] @ bbox + ex_inv[:3, 3:4]).T, ts
+            return default_bbox, ts
+
+    g = np.random.default_rng(44)
+    net = np.load(os.path.join(out_dir, "adapose_b2.npz"))
+    inp = synth.adapose_inputs(2, seed=0)
+    cases = []
+    for b in range(2):
+        cases.append(("net", net["view1_nocs"][b], net["view1_r"][b], net["view1_t"][b], net["view1_s"][b], inp["E1"][b].astype(np.float64)))
+    for kind in ("rand", "rand", "rand", "rand", "far", "tiny", "nan_s", "inf_nocs", "nan_nocs", "nan_E"):
+        nocs = g.uniform(-0.45, 0.45, size=(1024, 3)).astype(np.float32)
+        r = np.linalg.qr(g.normal(size=(3, 3)))[0].astype(np.float32)
+        t = (np.array([0.0, 0.0, 0.8]) + g.normal(0, 0.2, 3)).astype(np.float32)
+        s = g.normal(0, 0.3, 3).astype(np.float32)
+        E = np.eye(4)
+        E[:3, :3] = np.linalg.qr(g.normal(size=(3, 3)))[0]
+        E[:3, 3] = g.normal(size=3)
+        if kind == "far":
+            t, s = t * np.float32(40), s * np.float32(25)
+        if kind == "tiny":
+            s = s * np.float32(1e-3)
+        if kind == "nan_s":
+            s[1] = np.nan
+        if kind == "inf_nocs":
+            nocs[700, 2] = np.inf
+        if kind == "nan_nocs":
+            nocs[5, 0] = np.nan
+        if kind == "nan_E":
+            E[1, 2] = np.nan
+        cases.append((kind, nocs, r, t, s, E))
+    save = {"kinds": np.array([c[0] for c in cases])}
+    boxes, scales = [], []
+    for i, (kind, nocs, r, t, s, E) in enumerate(cases):
+        bb, ts = run_case(nocs, r, t, s, E)
+        boxes.append(bb)
+        scales.append(ts)
+        print("postproc_v4 case", i, kind, "scale", ts, "bbox0", bb[0])
+    for j, name in enumerate(("nocs", "r", "t", "s", "E1")):
+        save[name] = np.stack([c[1 + j] for c in cases])
+    save["bbox"], save["scale"] = np.stack(boxes), np.array(scales, dtype=np.float32)
+
+    rgb8, mask, K = synth.crop_frames(seed=0)
+    rgb = rgb8.astype(np.float32) / np.float32(255.0)                           # float frames holding fl32(b / 255)
+    for f, (task, S) in enumerate((("one_door_cabinet", 224), ("pots", 112))):
+        cfg = {"name": "adapose_v4", "task_name": task, "load": False, "checkpoint_path": "", "img_size": S, "use_depth": True,
+               "n_pts": 1024, "direct_regression": True, "real_world": False}
+        est = AdaPoseEstimator_v4(None, cfg, None)
+        assert isinstance(est.transform, Compose) == (task == "pots")
+        np.random.seed(400 + f)
+        view, choose, pts2d, Kn = est.prepare_model_input(rgb[f], mask[f], K[f], S)
+        view = view.float().numpy()                                             # interface_v4.py:263
+        assert view.shape == (3, S, S) and choose.shape == (1024,)
+        save[f"crop{f}_task"], save[f"crop{f}_size"] = np.array(task), np.array(S)
+        save[f"crop{f}_img"], save[f"crop{f}_K"], save[f"crop{f}_n_distinct"] = view, Kn, np.array(len(np.unique(choose)))
+        if len(np.unique(choose)) < 1024:                                       # wrap padding: no random subset, the indices are pinned too
+            save[f"crop{f}_choose"], save[f"crop{f}_pts2d"] = choose, pts2d
+        print("postproc_v4 crop", f, task, S, "range", float(view.min()), float(view.max()), "distinct choose", len(np.unique(choose)))
+    path = os.path.join(out_dir, "postproc_v4.npz")
+    np.savez_compressed(path, **save)
+    print("postproc_v4.npz:", os.path.getsize(path), "bytes")
+
+
 def gen_ppo(out_dir):
     from algo.ppo.ppo import PPO, ActorCritic, RolloutStorage
     from rgbmanip_amd import synth
@@ -831,6 +958,8 @@ if __name__ == "__main__":
         gen_control_save(out_dir)
     if "align" in which:
         gen_align(out_dir)
+    if "postproc_v4" in which:            # on request only: it reads the committed adapose_b2.npz and replaces cv2.resize / transforms
+        gen_postproc_v4(out_dir)
     if "adapose_dropout" in which:        # last: its torch.manual_seed cannot reach the generators above
         gen_adapose_dropout(out_dir)
     print("done")
