@@ -213,6 +213,26 @@ int rgbm_prepare_inputs_opt(const void* rgb_dev, int pixel_type, int normalize, 
                             const int32_t* frame_map_dev, int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out,
                             int32_t* choose_out, float* pts2d_out, double* Kcrop_out, int32_t* window_out, int32_t* valid_out,
                             uint8_t* scratch, void* stream);
+/* rgbm_prepare_inputs_opt from crop windows the HOST has cut out of the frames (estimate() with cfg hip_upload: "windows"): only the
+ * pixels the crop kernel reads cross PCIe.  The caller derives frame f's window (rmin, rmax, cmin, cmax) = window_dev[f] from the mask
+ * with get_bbox's integer arithmetic (lib/utils.py:10-38 with H x W for 480 x 640; an empty mask: (0, 40, 0, 40) and valid_in_dev[f] = 0)
+ * and packs, with h = rmax - rmin and w = cmax - cmin:
+ *   pix_dev       the h*w*3 pixels of rows rmin..rmax-1 x columns cmin..cmax-1, row-major, at ELEMENT offset 3 * offset_dev[f];
+ *                 pixel_type 0: f32 elements, 1: u8 elements (byte b = fl32(b / 255), exactly as in rgbm_prepare_inputs_u8)
+ *   mask_pix_dev  the h*w mask bytes of the same window (non-zero = object) at mask_pix_dev + offset_dev[f]
+ *   offset_dev    [N] i64, the exclusive prefix sum of h*w over the frames of the call;  window_dev [N][4] i32;  valid_in_dev [N] i32
+ * H, W: the size of the frames the windows were cut from (Kcrop and pts2d are in frame coordinates; H, W >= 440 as above).
+ * img_out, choose_out, pts2d_out (may be NULL), Kcrop_out and valid_out are bit-identical to what rgbm_prepare_inputs_opt writes from the
+ * whole frames with the same pixel_type, normalize, frame0, seed, S and P (frame_map_dev NULL), whose window_out equals window_dev: the
+ * crop kernel runs the same interpolation body on the packed pixels, Kcrop comes from the same fp64 expressions, the choose stage is
+ * the same kernel.  That includes an empty mask (valid_in 0): pack the frame's 40 x 40 corner; Kcrop is the identity, valid_out 0.
+ * The windows are trusted: every tap is read at offset_dev[f] + y * w + x with y < h, x < w, so the packed buffers must hold
+ * offset_dev[N-1] + h*w pixels.  scratch: N*S*S bytes.  Argument errors (nothing is launched): pixel_type or normalize outside {0, 1},
+ * a null pointer other than pts2d_out, frame0 < 0 and the shape limits of rgbm_prepare_inputs. */
+int rgbm_prepare_inputs_windows(const void* pix_dev, int pixel_type, int normalize, const uint8_t* mask_pix_dev, const int64_t* offset_dev,
+                                const int32_t* window_dev, const int32_t* valid_in_dev, const double* K_dev, int frame0, int N, int H, int W,
+                                int S, int P, uint32_t seed, float* img_out, int32_t* choose_out, float* pts2d_out, double* Kcrop_out,
+                                int32_t* valid_out, uint8_t* scratch, void* stream);
 /* Float frames -> 8-bit frames, the write side of a byte view queue whose environment hands over float frames:
  * dst[i] = (uint8) min(max(rintf(src[i] * 255.f), 0), 255), rint = round half to even, NaN -> 0 (+inf -> 255, -inf -> 0).
  * rintf(fl32(b / 255) * 255.f) == b for every byte b, so quantise -> rgbm_prepare_inputs_u8 is the identity on byte-valued frames.

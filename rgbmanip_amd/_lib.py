@@ -158,6 +158,7 @@ SIGNATURES = {
     "rgbm_prepare_inputs_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_prepare_inputs_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_prepare_inputs_opt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rgbm_prepare_inputs_windows": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_quantize_frames": (_i, [_vp, _vp, C.c_size_t, _vp]),
     "rgbm_projection": (_i, [_vp, _vp, _vp, _i, _vp]),
     "rgbm_mask_extent": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),

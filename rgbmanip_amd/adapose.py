@@ -505,6 +505,41 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     return out
 
 
+def prepare_inputs_windows(pix, mask_pix, offset, window, valid_in, K, H: int, W: int, img_size: int = 224, n_pts: int = 1024, seed: int = 0,
+                           want_pts2d: bool = False, stream=None, frame0: int = 0, normalize: bool = True):
+    """`prepare_inputs` from crop windows the host has cut out of the frames and packed (`rgbm_prepare_inputs_windows`, cfg hip_upload:
+    "windows"; upload.mask_windows / pack_windows): pix flat float32 or uint8 (3 elements per pixel), mask_pix flat uint8, offset [N]
+    int64 (pixel offset of frame f's window in both), window [N,4] int32, valid_in [N] int32 (0: empty mask) — CUDA tensors; K [N,3,3];
+    H, W: the size of the frames the windows were cut from.  Returns the dict of `prepare_inputs`, bit for bit what it returns for the
+    whole frames (its "window" is the tensor handed in)."""
+    lib = _lib.load()
+    dev = pix.device
+    if pix.dtype not in (torch.uint8, torch.float32) or mask_pix.dtype != torch.uint8:
+        raise TypeError(f"prepare_inputs_windows: pix float32 or uint8 and mask_pix uint8, got {pix.dtype} / {mask_pix.dtype}")
+    N = int(window.shape[0])
+    K = torch.as_tensor(K).to(device=dev, dtype=torch.float64).contiguous()
+    offset = offset.to(device=dev, dtype=torch.int64).contiguous()
+    window = window.to(device=dev, dtype=torch.int32).contiguous()
+    valid_in = valid_in.to(device=dev, dtype=torch.int32).contiguous()
+    assert K.shape[0] == N and offset.shape == (N,) and window.shape == (N, 4) and valid_in.shape == (N,)
+    assert pix.is_contiguous() and mask_pix.is_contiguous() and pix.numel() == 3 * mask_pix.numel()
+    S, P = int(img_size), int(n_pts)
+    img = torch.empty(N, 3, S, S, dtype=torch.float32, device=dev)
+    choose = torch.empty(N, P, dtype=torch.int32, device=dev)
+    pts2d = torch.empty(N, P, 2, dtype=torch.float32, device=dev) if want_pts2d else None
+    Kcrop = torch.empty(N, 3, 3, dtype=torch.float64, device=dev)
+    valid = torch.empty(N, dtype=torch.int32, device=dev)
+    scratch = torch.empty(N * S * S, dtype=torch.uint8, device=dev)
+    _lib.check(lib.rgbm_prepare_inputs_windows(_lib.ptr(pix), int(pix.dtype == torch.uint8), int(bool(normalize)), _lib.ptr(mask_pix), _lib.ptr(offset),
+                                               _lib.ptr(window), _lib.ptr(valid_in), _lib.ptr(K), int(frame0), N, int(H), int(W), S, P,
+                                               int(seed) & 0xFFFFFFFF, _lib.ptr(img), _lib.ptr(choose), _lib.ptr(pts2d), _lib.ptr(Kcrop), _lib.ptr(valid),
+                                               _lib.ptr(scratch), _lib.stream_ptr(stream)), "rgbm_prepare_inputs_windows")
+    out = {"img": img, "choose": choose, "Kcrop": Kcrop, "window": window, "valid": valid}
+    if want_pts2d:
+        out["pts2d"] = pts2d
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Host mirror of the device's dependency cone (csrc/prob_sparse.hip::cone_of), for reporting and capacity planning: which part of
 # the plane-sweep volume the network needs for a given set of chosen pixels (option "sparse_dec"; network_v5.py:260-291, 449-455).

@@ -22,7 +22,7 @@ RL_CONTROLLER_CFG = {
 
 
 # Keys the HIP estimator reads on top of the reference's (INTEGRATION.md section 2 lists them with defaults): hip_dtype, hip_prepare,
-# hip_prepare_seed, hip_ransac_seed, hip_upload_chunk, hip_view2_heads, hip_graph, hip_graph_max_batch, hip_options, hip_norm_mode,
+# hip_prepare_seed, hip_ransac_seed, hip_upload_chunk, hip_upload ("frames" / "windows": upload whole frames or only their crop windows), hip_view2_heads, hip_graph, hip_graph_max_batch, hip_options, hip_norm_mode,
 # hip_dropout, hip_dropout_seed, hip_as_shipped, hip_feature_cache (default False: keep the PSPNet feature map of every frame of the
 # controller's view queue across steps; refused together with hip_dropout / hip_as_shipped; "content": the same for estimate() /
 # estimate_device(), crops recognised by a device-side fingerprint), hip_feature_cache_records (default 0: two records per pose)

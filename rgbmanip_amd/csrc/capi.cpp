@@ -629,6 +629,16 @@ extern "C" int rgbm_prepare_inputs_opt(const void* rgb_dev, int pixel_type, int 
                                    pts2d_out, Kcrop_out, window_out, valid_out, scratch, (hipStream_t)stream, frame0);
 }
 
+extern "C" int rgbm_prepare_inputs_windows(const void* pix_dev, int pixel_type, int normalize, const uint8_t* mask_pix_dev,
+                                           const int64_t* offset_dev, const int32_t* window_dev, const int32_t* valid_in_dev, const double* K_dev,
+                                           int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out, int32_t* choose_out,
+                                           float* pts2d_out, double* Kcrop_out, int32_t* valid_out, uint8_t* scratch, void* stream) {
+  static_assert(sizeof(int64_t) == sizeof(long long), "offset table");
+  return launch_prepare_inputs_windows(pix_dev, pixel_type, normalize, mask_pix_dev, reinterpret_cast<const long long*>(offset_dev), window_dev,
+                                       valid_in_dev, K_dev, frame0, N, H, W, S, P, seed, img_out, choose_out, pts2d_out, Kcrop_out, valid_out,
+                                       scratch, (hipStream_t)stream);
+}
+
 extern "C" int rgbm_adapose_postprocess_regressed(int B, int P, const float* nocs1, const float* r1, const float* t1, const float* s1,
                                                   const double* E1, double* bbox_out, double* ts_out, int32_t* valid_out, void* stream) {
   return launch_postprocess_regressed(nocs1, r1, t1, s1, E1, bbox_out, ts_out, valid_out, B, P, (hipStream_t)stream);

@@ -194,6 +194,12 @@ int launch_prepare_inputs_u8(const unsigned char* rgb, const unsigned char* mask
 int launch_prepare_inputs_opt(const void* rgb, int pixel_type, int normalize, const unsigned char* mask, const double* K, const int* frame_map,
                               int N, int H, int W, int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop,
                               int* window, int* valid, unsigned char* small_scratch, hipStream_t s, int frame0 = 0);
+// launch_prepare_inputs_opt from crop windows the host has cut out and packed back to back (pix / mask_pix at the element offsets `offset`,
+// `window` = the windows mask_window_kernel would derive, valid_in 0 = an empty mask); same img / choose / pts2d / Kcrop / valid, bit for bit
+int launch_prepare_inputs_windows(const void* pix, int pixel_type, int normalize, const unsigned char* mask_pix, const long long* offset,
+                                  const int* window, const int* valid_in, const double* K, int frame0, int N, int H, int W, int S, int P,
+                                  unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* valid, unsigned char* small_scratch,
+                                  hipStream_t s);
 // dst[i] = min(max(rint(src[i] * 255), 0), 255), NaN -> 0: float frames into an 8-bit view queue (any n, src 4-byte / dst 1-byte aligned)
 int launch_quantize_frames(const float* src, unsigned char* dst, size_t n, hipStream_t s);
 

@@ -26,6 +26,20 @@ __host__ __device__ inline unsigned mix32(unsigned seed, unsigned frame, unsigne
   return h;
 }
 
+// ---- cropped intrinsics of a window: interface_v5.py:153-168 (python floats = fp64), shared by the two kernels that write Kcrop ----
+__device__ inline void crop_intrinsics(const double* __restrict__ Ki, int rmin, int rmax, int cmin, int cmax, int S, double* __restrict__ Ko) {
+  const double ratio = (double)S / (double)(rmax - rmin);
+  const double ccx = (double)(cmin + cmax) / 2.0, ccy = (double)(rmin + rmax) / 2.0;
+  const double csx = (double)(cmax - cmin + 1), csy = (double)(rmax - rmin + 1);
+  Ko[0] = Ki[0] * ratio; Ko[1] = 0.0; Ko[2] = (Ki[2] - (ccx - csx / 2.0)) * ratio;
+  Ko[3] = 0.0; Ko[4] = Ki[4] * ratio; Ko[5] = (Ki[5] - (ccy - csy / 2.0)) * ratio;
+  Ko[6] = 0.0; Ko[7] = 0.0; Ko[8] = 1.0;
+}
+// an empty mask (the reference returns None -> default bbox): the identity, so that what is computed from it stays finite
+__device__ inline void identity_intrinsics(double* __restrict__ Ko) {
+  for (int i = 0; i < 9; ++i) Ko[i] = (i % 4 == 0) ? 1.0 : 0.0;
+}
+
 // ---- 1. mask bounding box -> crop window (get_bbox) -> cropped intrinsics ------------------------------------------
 // frame_map (optional): frame f reads image / mask number frame_map[f] of the arrays it is given (a view queue); a negative
 // entry is a missing view and behaves like an all-zero mask.  K, the outputs and the subset hash stay indexed by f.
@@ -53,7 +67,7 @@ __global__ __launch_bounds__(PRE_THREADS) void mask_window_kernel(const unsigned
   double* Ko = Kcrop + f * 9;
   if (s_y2 < 0) {                                   // empty mask: the reference returns None -> default bbox
     w[0] = 0; w[1] = 40; w[2] = 0; w[3] = 40;
-    for (int i = 0; i < 9; ++i) Ko[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    identity_intrinsics(Ko);
     valid[f] = 0;
     return;
   }
@@ -67,14 +81,7 @@ __global__ __launch_bounds__(PRE_THREADS) void mask_window_kernel(const unsigned
   if (rmax > H) { rmin = rmin - (rmax - H); rmax = H; }
   if (cmax > W) { cmin = cmin - (cmax - W); cmax = W; }
   w[0] = rmin; w[1] = rmax; w[2] = cmin; w[3] = cmax;
-  // interface_v5.py:153-168 (python floats = fp64)
-  const double ratio = (double)S / (double)(rmax - rmin);
-  const double* Ki = K + f * 9;
-  const double ccx = (double)(cmin + cmax) / 2.0, ccy = (double)(rmin + rmax) / 2.0;
-  const double csx = (double)(cmax - cmin + 1), csy = (double)(rmax - rmin + 1);
-  Ko[0] = Ki[0] * ratio; Ko[1] = 0.0; Ko[2] = (Ki[2] - (ccx - csx / 2.0)) * ratio;
-  Ko[3] = 0.0; Ko[4] = Ki[4] * ratio; Ko[5] = (Ki[5] - (ccy - csy / 2.0)) * ratio;
-  Ko[6] = 0.0; Ko[7] = 0.0; Ko[8] = 1.0;
+  crop_intrinsics(K + f * 9, rmin, rmax, cmin, cmax, S, Ko);
   valid[f] = 1;
 }
 
@@ -88,22 +95,14 @@ __global__ __launch_bounds__(PRE_THREADS) void mask_window_kernel(const unsigned
 __device__ inline float pixel_value(float v) { return v; }
 __device__ inline float pixel_value(unsigned char b) { return (float)((double)b / 255.0); }
 
+// INTER_LINEAR on a float image, one output pixel (dy, dx) of an h x w source window resized to S x S, all three channels: f = (d + 0.5) *
+// scale - 0.5, clamp at both edges, weights in fp32.  The window's pixel (y, x) is base[((row0 + y) * pitch + col0 + x) * 3 + c]: a window
+// inside a whole frame (crop_resize_kernel: row0 / col0 = the window's corner, pitch = W) or a packed window (crop_resize_windows_kernel:
+// row0 = col0 = 0, pitch = w).  The ONE body both crop kernels run, so that what they write cannot drift apart.
 template <typename Px, bool NORM>
-__global__ void crop_resize_kernel(const Px* __restrict__ rgb /*[N,H,W,3]*/, const unsigned char* __restrict__ mask,
-                                   const int* __restrict__ frame_map, const int* __restrict__ window, int N, int H, int W, int S,
-                                   float* __restrict__ img /*[N,3,S,S]*/, unsigned char* __restrict__ small /*[N,S,S]*/) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)N * S * S) return;
-  const int f = (int)(i / (S * S)), p = (int)(i - (long long)f * S * S), dy = p / S, dx = p - dy * S;
-  const int rmin = window[f * 4 + 0], rmax = window[f * 4 + 1], cmin = window[f * 4 + 2], cmax = window[f * 4 + 3];
-  const int h = rmax - rmin, w = cmax - cmin;
-  // INTER_NEAREST: sx = min(floor(dx * (src/dst)), src-1), fp64 like numpy's python-float scale
-  const int ny = min((int)floor((double)dy * ((double)h / (double)S)), h - 1);
-  const int nx = min((int)floor((double)dx * ((double)w / (double)S)), w - 1);
-  const int mf = frame_map ? frame_map[f] : f;
-  const int sf = mf < 0 ? 0 : mf;
-  small[i] = (mf >= 0 && mask[((long long)sf * H + rmin + ny) * W + cmin + nx]) ? 1 : 0;
-  // INTER_LINEAR on a float image: f = (d + 0.5) * scale - 0.5, clamp at both edges, weights in fp32
+__device__ inline void crop_bilinear(const Px* __restrict__ base, int row0, int col0, int pitch, int h, int w, int S, int dy, int dx,
+                                     float* __restrict__ img /*[N,3,S,S]*/, int f, int p) {
+  const int rmin = row0, cmin = col0, W = pitch;
   auto taps = [](int d, int n_src, int n_dst, int& i0, int& i1, float& a) {
     const double fl = ((double)d + 0.5) * ((double)n_src / (double)n_dst) - 0.5;
     int j = (int)floor(fl);
@@ -116,7 +115,6 @@ __global__ void crop_resize_kernel(const Px* __restrict__ rgb /*[N,H,W,3]*/, con
   float ay, ax;
   taps(dy, h, S, y0, y1, ay);
   taps(dx, w, S, x0, x1, ax);
-  const Px* base = rgb + (long long)sf * H * W * 3;
   const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -128,6 +126,65 @@ __global__ void crop_resize_kernel(const Px* __restrict__ rgb /*[N,H,W,3]*/, con
     if constexpr (NORM) img[((long long)f * 3 + c) * S * S + p] = (v - mean[c]) / stdv[c];
     else img[((long long)f * 3 + c) * S * S + p] = v;
   }
+}
+
+// INTER_NEAREST: sx = min(floor(dx * (src/dst)), src-1), fp64 like numpy's python-float scale
+__device__ inline int nearest_tap(int d, int n_src, int n_dst) { return min((int)floor((double)d * ((double)n_src / (double)n_dst)), n_src - 1); }
+
+template <typename Px, bool NORM>
+__global__ void crop_resize_kernel(const Px* __restrict__ rgb /*[N,H,W,3]*/, const unsigned char* __restrict__ mask,
+                                   const int* __restrict__ frame_map, const int* __restrict__ window, int N, int H, int W, int S,
+                                   float* __restrict__ img /*[N,3,S,S]*/, unsigned char* __restrict__ small /*[N,S,S]*/) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)N * S * S) return;
+  const int f = (int)(i / (S * S)), p = (int)(i - (long long)f * S * S), dy = p / S, dx = p - dy * S;
+  const int rmin = window[f * 4 + 0], rmax = window[f * 4 + 1], cmin = window[f * 4 + 2], cmax = window[f * 4 + 3];
+  const int h = rmax - rmin, w = cmax - cmin;
+  const int ny = nearest_tap(dy, h, S), nx = nearest_tap(dx, w, S);
+  const int mf = frame_map ? frame_map[f] : f;
+  const int sf = mf < 0 ? 0 : mf;
+  small[i] = (mf >= 0 && mask[((long long)sf * H + rmin + ny) * W + cmin + nx]) ? 1 : 0;
+  crop_bilinear<Px, NORM>(rgb + (long long)sf * H * W * 3, rmin, cmin, W, h, w, S, dy, dx, img, f, p);
+}
+
+// ---- 2b. the same from packed windows (estimate() with hip_upload: "windows") ------------------------------------------
+// The host has cut every frame's crop window out of the frame and of the mask and stored the windows back to back: frame f's h x w x 3
+// pixels row-major at element 3 * offset[f] of pix, its h x w mask bytes at mask_pix + offset[f]; window[f] is what mask_window_kernel
+// derives from the whole mask (the host restates its integer arithmetic, upload.mask_windows).  Same taps, same values, same arithmetic as
+// crop_resize_kernel on the whole frames: img and small are bit-identical.  A window with no pixels (h or w <= 0: not what the host
+// packs) is written as zeros instead of being read.
+template <typename Px, bool NORM>
+__global__ void crop_resize_windows_kernel(const Px* __restrict__ pix, const unsigned char* __restrict__ mask_pix,
+                                           const long long* __restrict__ offset /*[N]*/, const int* __restrict__ window /*[N,4]*/, int N, int S,
+                                           float* __restrict__ img /*[N,3,S,S]*/, unsigned char* __restrict__ small /*[N,S,S]*/) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)N * S * S) return;
+  const int f = (int)(i / (S * S)), p = (int)(i - (long long)f * S * S), dy = p / S, dx = p - dy * S;
+  const int h = window[f * 4 + 1] - window[f * 4 + 0], w = window[f * 4 + 3] - window[f * 4 + 2];
+  if (h <= 0 || w <= 0) {
+    small[i] = 0;
+    for (int c = 0; c < 3; ++c) img[((long long)f * 3 + c) * S * S + p] = 0.f;
+    return;
+  }
+  const long long off = offset[f];
+  const int ny = nearest_tap(dy, h, S), nx = nearest_tap(dx, w, S);
+  small[i] = mask_pix[off + (long long)ny * w + nx] ? 1 : 0;
+  crop_bilinear<Px, NORM>(pix + off * 3, 0, 0, w, h, w, S, dy, dx, img, f, p);
+}
+
+// Kcrop and valid of packed windows: what mask_window_kernel writes once it has found the window.  valid_in 0 = an empty mask.
+__global__ void window_intrinsics_kernel(const int* __restrict__ window, const int* __restrict__ valid_in, const double* __restrict__ K, int N,
+                                         int S, double* __restrict__ Kcrop /*[N,9]*/, int* __restrict__ valid) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= N) return;
+  const int* w = window + f * 4;
+  if (!valid_in[f] || w[1] <= w[0] || w[3] <= w[2]) {
+    identity_intrinsics(Kcrop + f * 9);
+    valid[f] = 0;
+    return;
+  }
+  crop_intrinsics(K + f * 9, w[0], w[1], w[2], w[3], S, Kcrop + f * 9);
+  valid[f] = 1;
 }
 
 // ---- 3. choose: nonzero indices of the resized mask, ordered random P-subset or wrap padding -------------------------
@@ -335,6 +392,41 @@ int launch_prepare_inputs_opt(const void* rgb, int pixel_type, int normalize, co
                       : launch_prepare_inputs(f32, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
   return pixel_type ? prepare_inputs_impl<unsigned char, false>(u8, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0)
                     : prepare_inputs_impl<float, false>(f32, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
+}
+
+namespace {
+template <typename Px, bool NORM>
+void launch_crop_windows(const void* pix, const unsigned char* mask_pix, const long long* offset, const int* window, int N, int S, float* img,
+                         unsigned char* small, hipStream_t s) {
+  const long long tot = (long long)N * S * S;
+  hipLaunchKernelGGL((crop_resize_windows_kernel<Px, NORM>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, static_cast<const Px*>(pix),
+                     mask_pix, offset, window, N, S, img, small);
+}
+}  // namespace
+
+// prepare_inputs_opt from packed crop windows (include/rgbm.h: rgbm_prepare_inputs_windows)
+int launch_prepare_inputs_windows(const void* pix, int pixel_type, int normalize, const unsigned char* mask_pix, const long long* offset,
+                                  const int* window, const int* valid_in, const double* K, int frame0, int N, int H, int W, int S, int P,
+                                  unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* valid, unsigned char* small_scratch,
+                                  hipStream_t s) {
+  RGBM_REQUIRE((pixel_type == 0 || pixel_type == 1) && (normalize == 0 || normalize == 1), "prepare_inputs_windows: pixel_type and normalize are 0 or 1");
+  RGBM_REQUIRE(pix && mask_pix && offset && window && valid_in && K && img && choose && Kcrop && valid && small_scratch,
+               "prepare_inputs_windows arguments");
+  RGBM_REQUIRE(frame0 >= 0 && N > 0 && H >= 440 && W >= 440 && S > 0 && P > 0 && S * S <= 65536,
+               "prepare_inputs_windows sizes (the windows' frames must be at least 440 x 440)");
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(choose_kernel), 150 * 1024)) return rc;
+  hipLaunchKernelGGL(window_intrinsics_kernel, dim3((N + 127) / 128), dim3(128), 0, s, window, valid_in, K, N, S, Kcrop, valid);
+  if (normalize) {
+    if (pixel_type) launch_crop_windows<unsigned char, true>(pix, mask_pix, offset, window, N, S, img, small_scratch, s);
+    else launch_crop_windows<float, true>(pix, mask_pix, offset, window, N, S, img, small_scratch, s);
+  } else {
+    if (pixel_type) launch_crop_windows<unsigned char, false>(pix, mask_pix, offset, window, N, S, img, small_scratch, s);
+    else launch_crop_windows<float, false>(pix, mask_pix, offset, window, N, S, img, small_scratch, s);
+  }
+  hipLaunchKernelGGL(choose_kernel, dim3(N), dim3(PRE_THREADS), (size_t)S * S * sizeof(unsigned short), s, small_scratch, window, S, P, seed, choose,
+                     pts2d, valid, frame0);
+  RGBM_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 int launch_quantize_frames(const float* src, unsigned char* dst, size_t n, hipStream_t s) {

@@ -25,10 +25,12 @@ import numpy as np
 import torch
 
 from . import _lib, host_prepare
-from .adapose import AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs
+from .adapose import (AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
+                      prepare_inputs_windows)
 from .feature_cache import CachedViews, ContentFeatureCache, SlotFeatureCache
 from .host_prepare import _resize_linear, _resize_nearest, get_bbox      # noqa: F401  (part of this module's surface)
-from .upload import ChunkPipeline, _nonzero_into, _split, frames_to_device, host_array, masks_to_device      # noqa: F401
+from .upload import (ChunkPipeline, WindowRing, _nonzero_into, _split, frames_payload_bytes, frames_to_device, host_array,      # noqa: F401
+                     masks_to_device)
 
 DEFAULT_BBOX = np.asarray([[0, 0, 0], [0, 0, 1], [0, 1, 0], [0, 1, 1], [1, 0, 0], [1, 0, 1], [1, 1, 0], [1, 1, 1]],
                           dtype=np.float64) + 10.0
@@ -88,6 +90,17 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     def __init__(self, env, cfg, logger, state_dict=None, dtype=None, device=0, net=None):
         """`net`: an already built `AdaPoseNet` to share (weights + workspace) instead of building one from `state_dict`."""
         super().__init__(env, cfg, logger)
+        # hip_upload (estimate() with host arrays and hip_prepare: device): "frames" (default) stages and uploads every pixel of every
+        # frame; "windows" derives each frame's crop window from its mask on the host and uploads only that part of the frame and of the
+        # mask (upload.WindowRing, rgbm_prepare_inputs_windows) — the same boxes bit for bit, 22 % of the bytes on the crop test frames
+        self.upload_mode = cfg.get("hip_upload", "frames")
+        if self.upload_mode not in ("frames", "windows"):
+            raise ValueError(f'AdaPoseEstimator_v5: hip_upload is "frames" or "windows", got {self.upload_mode!r}')
+        if self.upload_mode == "windows" and cfg.get("hip_prepare", "device") != "device":
+            raise ValueError('AdaPoseEstimator_v5: hip_upload: "windows" packs the crop windows for the device-side preparation; it needs '
+                             f'hip_prepare: "device", got {cfg.get("hip_prepare")!r}')
+        self.upload_bytes_last_call = 0       # payload the last estimate() handed to the copy engine: frames and masks, or their windows
+        self.upload_table_bytes_last_call = 0         # ... and the offset / window / valid tables on top of it (hip_upload: "windows")
         if net is not None:
             state_dict = {}
         elif state_dict is None:
@@ -140,6 +153,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         self._slots = SlotFeatureCache(self.estimator, self._normalize)                 # estimate_device_indexed(..., fresh=...)
         self._content = ContentFeatureCache(self.estimator, records)     # estimate / estimate_device with "content"
         self._ring = self._pipe = None        # staging of _upload_frames / of the chunk pipeline, built by the first call that needs them
+        self._wring = None                    # one-slot WindowRing of an unchunked hip_upload: "windows" call
         self._dev_consts = None               # (DEFAULT_BBOX, _DEPTH_PLANES) on the device
         self._pnp_warned = False
         self.rng = np.random          # the reference shuffles with the global numpy RNG (interface_v5.py:129)
@@ -216,7 +230,11 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         chunk pipeline (upload.ChunkPipeline), whose per-chunk work is defined here."""
         n = len(rgb1)
         chunk = int(self.cfg.get("hip_upload_chunk", 32))
-        on_dev = any(isinstance(x, torch.Tensor) and x.is_cuda for x in (rgb1, rgb2))
+        cuda = [isinstance(x, torch.Tensor) and x.is_cuda for x in (rgb1, rgb2, mask1, mask2)]
+        if self.upload_mode == "windows" and not any(cuda):
+            return self._estimate_host_windows(K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk)
+        self.upload_bytes_last_call, self.upload_table_bytes_last_call = frames_payload_bytes(rgb1, rgb2, mask1, mask2), 0
+        on_dev = cuda[0] or cuda[1]
         if on_dev or n <= chunk or chunk <= 0:
             return self.estimate_device(np.asarray(K), self._upload_frames(rgb1), self._upload_masks(mask1), np.asarray(E1),
                                         self._upload_frames(rgb2), self._upload_masks(mask2), np.asarray(E2)).cpu().numpy()
@@ -244,8 +262,66 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                 out[a:b] = self.estimate_device(Kd[a:b], self._upload_frames(d[0]), d[2], E1d[a:b], self._upload_frames(d[1]), d[3], E2d[a:b], frame0=a)
             pipe.run(srcs, n, network)
         res = out.cpu().numpy()
-        pipe.trace.report()
+        pipe.trace.report(self.upload_bytes_last_call)
         return res
+
+    def _estimate_host_windows(self, K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk):
+        """`_estimate_host_frames` with hip_upload: "windows": the host derives every frame's crop window from its mask, packs that part of
+        the frame and of the mask into pinned staging and uploads the packed buffers (upload.WindowRing); `rgbm_prepare_inputs_windows`
+        writes img / choose / pts2d / Kcrop / valid from them and everything behind is the code of the whole-frame path.  At most
+        `hip_upload_chunk` poses (or chunk 0): the whole call is packed at once; more: the chunk pipeline with a window ring."""
+        dev = self.estimator.device
+        srcs = [host_array(x) for x in (rgb1, rgb2, mask1, mask2)]
+        Kd = torch.as_tensor(np.asarray(K)).to(dev)
+        E1d, E2d = torch.as_tensor(np.asarray(E1)).to(dev), torch.as_tensor(np.asarray(E2)).to(dev)
+        S, wp = self.cfg["img_size"], self._pnp_branch()
+
+        def prep(a, b, d):
+            return [self._prepare_windows(d, v, Kd[a:b], S, 1024, self.prepare_seed + v, want_pts2d=wp, frame0=a) for v in (0, 1)]
+        if n <= chunk or chunk <= 0:
+            ring = self._wring = WindowRing.matching(self._wring, n, srcs, dev, slots=1, grow=True)
+            ring.payload_bytes = ring.table_bytes = 0
+            ring.wait(0)
+            ring.stage(0, srcs, 0, n)
+            pa, pb = prep(0, n, ring.copy(0, n))
+            if self.feature_content:
+                self._content.reserve(n)
+                out = self._estimate_keyed(self._content.keys(pa, pb), E1d, E2d, Kd)
+            else:
+                out = self._estimate_prepared(pa, pb, E1d, E2d, Kd)
+            res = out.cpu().numpy()
+            self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
+            return res
+        pipe = self._pipe = ChunkPipeline.matching(self._pipe, chunk, srcs, dev, windows=True)
+        ring = pipe.ring
+        ring.payload_bytes = ring.table_bytes = 0
+        out = torch.empty(n, 8, 3, dtype=torch.float64, device=dev)
+        if self.feature_content:
+            self._content.reserve(n)
+
+            def prepare(a, b, d):
+                return a, b, self._content.keys(*prep(a, b, d))
+
+            def network(p):
+                a, b, keys = p
+                out[a:b] = self._estimate_keyed(keys, E1d[a:b], E2d[a:b], Kd[a:b])
+            pipe.run_keyed(srcs, n, prepare, network)
+        else:
+            def network(a, b, d):
+                pa, pb = prep(a, b, d)
+                out[a:b] = self._estimate_prepared(pa, pb, E1d[a:b], E2d[a:b], Kd[a:b])
+            pipe.run(srcs, n, network)
+        res = out.cpu().numpy()
+        self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
+        pipe.trace.report(self.upload_bytes_last_call)
+        return res
+
+    def _prepare_windows(self, d, v, K, *args, **kw):
+        """`prepare_inputs_windows` on view v of a `PackedViews`, counting the frames cropped straight from bytes like `_prepare`."""
+        out = prepare_inputs_windows(d.pix[v], d.mask[v], d.offset[v], d.window[v], d.valid[v], K, d.H, d.W, *args, normalize=self._normalize, **kw)
+        if d.pix[v].dtype == torch.uint8:
+            self.frames_u8_native += int(out["img"].shape[0])
+        return out
 
     def _upload_frames(self, frames):
         out, self._ring = frames_to_device(frames, self.estimator.device, self._ring, self._CHUNK_BYTES, keep_u8=True)
