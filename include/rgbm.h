@@ -112,6 +112,29 @@ int rgbm_adapose_forward(rgbm_adapose_t* h, int B, const float* img1, const floa
                          const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
                          size_t workspace_bytes, const rgbm_adapose_out* out, void* stream);
 
+/* Dense depth and confidence maps of the crops (what lib/network_v3.py:406-408 returns as view1_depth: softmax over the D planes of the
+ * regularised cost volume, then the expectation with the depth values), beside the ten point outputs.
+ * rgbm_adapose_forward_dense: the arguments of rgbm_adapose_forward plus two caller-owned fp32 device buffers [V'][224][224],
+ *   V' = 2B (rows: the view-1 crops, then the view-2 crops) or, with option view2_heads = 0, B (view-1 maps only; the cost volume of the
+ *   view-2 crops is not built, as in rgbm_adapose_forward).  depth_map[v][y][x] = sum_d p[d] depths[v % B][d], conf_map[v][y][x] =
+ *   max_d p[d], p = softmax_d of the prob conv (Conv3d 8 -> 1, 3^3, zero padding, network_v5.py:280,290) evaluated at every pixel; fp32
+ *   sums in the order of the point head, so depth_map read at choose1[b][p] is view1_depth[b][p].  conf_map may be NULL, depth_map not.
+ *   For this one call the network runs with a dense cost regularisation and the dense tail — the effect of options sparse_dec = 0 and
+ *   sparse_tail = 0 — without changing the handle's options: the ten outputs in `out` are bit for bit those of a handle built with
+ *   these two options, and can differ from the default sparse-tail outputs by the rounding between the two tails (16-bit and split-pair
+ *   storage; the bound of tests/test_gpu_adapose.py::test_prob_sparse_kernels_agree).  Works with Dropout2d on (the masks are drawn
+ *   upstream of the cost volume).  There is no hipGraph and no feature-cache form of this call.
+ * rgbm_adapose_dense_workspace_bytes: the workspace of such a call (256-byte aligned, as for rgbm_adapose_forward).
+ * rgbm_depth_to_points: depth_map [n][S][S] fp32, Kcrop [n][3][3] fp64 (cropped intrinsics), E [n][4][4] fp64 (world -> camera) ->
+ *   points [n][S][S][3] fp32 in the world frame: inv(E) (depth Kcrop^-1 (x, y, 1)^T), the per-pixel form of the back-projection of
+ *   interface_v5.py:329-336 followed by ex_inv of :369-372 (fp64 arithmetic, rounded once).  A pixel whose depth is not finite yields
+ *   NaN; nothing is clamped.  n <= 65535. */
+int rgbm_adapose_dense_workspace_bytes(rgbm_adapose_t* h, int B, size_t* bytes);
+int rgbm_adapose_forward_dense(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
+                               const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
+                               size_t workspace_bytes, const rgbm_adapose_out* out, float* depth_map, float* conf_map, void* stream);
+int rgbm_depth_to_points(const float* depth_map, const double* Kcrop, const double* E, int n, int S, float* points, void* stream);
+
 /* Post-processing of one batch of network outputs into world-frame handle boxes.
  * Replaces: compute_scale_and_translation / get_3d_bbox / transform_coordinates_3d and the tail of predict()
  *   models/pose_estimator/AdaPose/lib/utils.py:40-119, models/pose_estimator/AdaPose/interface_v5.py:318-321,354-374

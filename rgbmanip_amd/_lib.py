@@ -114,6 +114,9 @@ SIGNATURES = {
     "rgbm_adapose_forward_ex": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _i, _vp]),
     "rgbm_adapose_forward_graph": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32)]),
+    "rgbm_adapose_dense_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),
+    "rgbm_adapose_forward_dense": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp, _vp, _vp]),
+    "rgbm_depth_to_points": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "rgbm_adapose_graph_clear": (_i, [_vp]),
     "rgbm_adapose_feature_bytes": (_i, [_vp, C.POINTER(_sz)]),
     "rgbm_adapose_features_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),

@@ -208,7 +208,14 @@ class AdaPoseNet:
         return {k: v.clone() for k, v in out.items()}      # the static outputs are overwritten by the next replay
 
     def forward(self, view1_img, view1_choose, view2_img, view2_choose, view1_proj, view2_proj, depth_values,
-                stop_after: int = 0, stream=None):
+                stop_after: int = 0, stream=None, dense_depth: bool = False):
+        """The reference network's call.  `dense_depth=True` (rgbm_adapose_forward_dense): the same dict plus `view1_depth_map` /
+        `view1_depth_conf` and, with the view-2 heads, `view2_depth_map` / `view2_depth_conf` — [B, 224, 224] float32 each: the expected
+        depth and the largest probability over the 24 planes at every pixel of the crop.  That call runs the dense cost regularisation
+        and the dense tail whatever the net's options say (and leaves them as they are), always eagerly on one stream."""
+        if dense_depth:
+            assert stop_after == 0, "dense_depth: the whole forward"
+            return self._forward_dense((view1_img, view2_img, view1_choose, view2_choose, view1_proj, view2_proj, depth_values), stream)
         if self.graph and stop_after == 0 and stream is None and len(view1_img) <= self.graph_max_batch:
             self._last_graph = True
             return self._forward_graph((view1_img, view1_choose, view2_img, view2_choose, view1_proj, view2_proj, depth_values))
@@ -240,6 +247,35 @@ class AdaPoseNet:
                                                     _lib.ptr(P1), _lib.ptr(P2), _lib.ptr(dep), C.c_void_p(ws_ptr), ws_bytes,
                                                     C.byref(o), stop_after, _lib.stream_ptr(stream)), "rgbm_adapose_forward")
         self._last = (img1, img2, ch1, ch2, P1, P2, dep)     # keep inputs alive until the stream has consumed them
+        return out
+
+    def dense_workspace_bytes(self, B: int) -> int:
+        n = C.c_size_t()
+        _lib.check(self.lib.rgbm_adapose_dense_workspace_bytes(self._h, B, C.byref(n)), "rgbm_adapose_dense_workspace_bytes")
+        return n.value
+
+    def _forward_dense(self, args, stream):
+        dts = (torch.float32, torch.float32, torch.int32, torch.int32, torch.float32, torch.float32, torch.float32)
+        img1, img2, ch1, ch2, P1, P2, dep = t = tuple(self._prep(a, d) for a, d in zip(args, dts))
+        B = img1.shape[0]
+        assert img1.shape == (B, 3, 224, 224) and img2.shape == img1.shape, img1.shape
+        assert ch1.shape == (B, 1024) and ch2.shape == ch1.shape
+        assert P1.shape == (B, 4, 4) and P2.shape == (B, 4, 4) and dep.shape == (B, 24)
+        out = self._empty_outputs(B)
+        views = 2 if self.options.get("view2_heads", 1) else 1
+        maps = torch.empty(2, views * B, 224, 224, dtype=torch.float32, device=self.device)      # depth, confidence
+        o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
+        ws_ptr, ws_bytes = self._workspace_at_least(self.dense_workspace_bytes(B))       # grows on first use
+        self._poison(self._ws, stream)
+        self._drop_explicit = False
+        _lib.check(self.lib.rgbm_adapose_forward_dense(self._h, B, *[_lib.ptr(x) for x in t], C.c_void_p(ws_ptr), ws_bytes, C.byref(o),
+                                                       _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.stream_ptr(stream)),
+                   "rgbm_adapose_forward_dense")
+        self._last_split = self._last_graph = False
+        self._last = t                                        # keep inputs alive until the stream has consumed them
+        for v in range(views):
+            out[f"view{v + 1}_depth_map"] = maps[0, v * B:(v + 1) * B]
+            out[f"view{v + 1}_depth_conf"] = maps[1, v * B:(v + 1) * B]
         return out
 
     def _forward_split(self, B, args, out, stream):
@@ -383,6 +419,42 @@ def postprocess(view1_nocs, view1_depth, view1_r, view1_choose, K_crop, E1, img_
                                                _lib.ptr(K), _lib.ptr(E), _lib.ptr(bbox), _lib.ptr(ts), _lib.ptr(valid),
                                                _lib.ptr(scratch), nb.value, _lib.stream_ptr(stream)), "rgbm_adapose_postprocess_ws")
     return bbox, ts, valid
+
+
+def depth_to_points(depth_map, K_crop, E, stream=None):
+    """World-frame points of a crop's depth map (rgbm_depth_to_points): depth_map [n,S,S] float32, K_crop [n,3,3] (cropped intrinsics),
+    E [n,4,4] (world -> camera) -> [n,S,S,3] float32 CUDA: inv(E) applied to the back-projection of interface_v5.py:329-336 at every
+    pixel — the per-pixel `Position` image of the simulator camera.  A pixel whose depth is not finite yields NaN."""
+    lib = _lib.load()
+    d = torch.as_tensor(depth_map)
+    dev = d.device if d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    d = d.to(device=dev, dtype=torch.float32).contiguous()
+    n, S = d.shape[0], d.shape[1]
+    assert d.shape == (n, S, S), d.shape
+    K = torch.as_tensor(K_crop).to(device=dev, dtype=torch.float64).contiguous()
+    Ed = torch.as_tensor(E).to(device=dev, dtype=torch.float64).contiguous()
+    assert K.shape == (n, 3, 3) and Ed.shape == (n, 4, 4), (K.shape, Ed.shape)
+    pts = torch.empty(n, S, S, 3, dtype=torch.float32, device=dev)
+    if n:
+        _lib.check(lib.rgbm_depth_to_points(_lib.ptr(d), _lib.ptr(K), _lib.ptr(Ed), n, S, _lib.ptr(pts), _lib.stream_ptr(stream)),
+                   "rgbm_depth_to_points")
+    return pts
+
+
+def depth_to_points_ref(depth_map, K_crop, E):
+    """float64 numpy twin of `depth_to_points` (tests, documentation): the arithmetic of interface_v5.py:329-336, 369-372 per pixel."""
+    d = np.asarray(depth_map, dtype=np.float64)
+    K, E = np.asarray(K_crop, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    n, S = d.shape[0], d.shape[1]
+    y, x = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64), indexing="ij")
+    out = np.empty((n, S, S, 3))
+    for i in range(n):
+        ex_inv = np.linalg.inv(E[i])
+        with np.errstate(invalid="ignore"):                   # a non-finite depth: NaN below
+            cam = np.stack([(x - K[i, 0, 2]) * d[i] / K[i, 0, 0], (y - K[i, 1, 2]) * d[i] / K[i, 1, 1], d[i]], axis=-1)
+            out[i] = cam @ ex_inv[:3, :3].T + ex_inv[:3, 3]
+        out[i][~np.isfinite(d[i])] = np.nan
+    return out
 
 
 def postprocess_regressed(view1_nocs, view1_r, view1_t, view1_s, E1, stream=None):

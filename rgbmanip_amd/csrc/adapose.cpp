@@ -537,6 +537,11 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, h
   // other tiles, the depth-sweeping conv0 walks the list of needed ones.  conv6 stays dense (a 0.3 ms GEMM): what it computes from
   // unwritten input tiles is never read by anything that is read.
   const bool sparse_ok = sparse_active();
+  // forward_dense(): the dense head on the u11 of every chunk, beside the point kernel (rows v0 .. v0 + Vc - 1 of the maps)
+  auto dense = [&](int v0, int Vc, int classmajor) -> int {
+    if (dense_depth_map == nullptr) return 0;
+    return launch_dense_depth(dtype, bf.u11, wprob, depths, dense_depth_map, dense_conf_map, v0, Vc, B, D, S, S, classmajor, s);
+  };
   for (int v0 = 0; norm_mode == 0 && cost_impl >= 1 && v0 < Vh; v0 += Vc0) {
     const int Vc = Vh - v0 < Vc0 ? Vh - v0 : Vc0;
     const unsigned char* mk[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -578,6 +583,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, h
     }
     if (int rc = tile(9, bf.u9, bf.u11, bf.c[0], Vc, D / 2, S / 2, S / 2, D, S, S, true, v0)) return rc;
     if (int rc = launch_prob_softmax_depth(dtype, bf.u11, wprob, bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, 1, s)) return rc;
+    if (int rc = dense(v0, Vc, 1)) return rc;
   }
   // norm_mode 1: every layer = un-normalised conv (generic implicit GEMM) -> per-view batch statistics -> normalise + ReLU (+ skip)
   for (int v0 = 0; norm_mode == 1 && v0 < Vh; v0 += Vc0) {
@@ -601,6 +607,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, h
     if (int rc = layer(8, bf.u7, bf.u9, bf.c[2], D / 4, S / 4, S / 4, 16)) return rc;
     if (int rc = layer(9, bf.u9, bf.u11, bf.c[0], D / 2, S / 2, S / 2, 8)) return rc;
     if (int rc = launch_prob_softmax_depth(dtype, bf.u11, wprob, bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, 0, s)) return rc;
+    if (int rc = dense(v0, Vc, 0)) return rc;
   }
   if (norm_mode == 1) return 0;
   for (int v0 = 0; cost_impl == 0 && v0 < Vh; v0 += Vc0) {
@@ -618,6 +625,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, h
     if (int rc = dc[1].run(bf.u7, bf.u9, Vc, D / 4, S / 4, S / 4, 16, bf.c[2], RES_POST_ACT, nullptr, 0, s)) return rc;
     if (int rc = dc[2].run(bf.u9, bf.u11, Vc, D / 2, S / 2, S / 2, 8, bf.c[0], RES_POST_ACT, nullptr, 0, s)) return rc;
     if (int rc = launch_prob_softmax_depth(dtype, bf.u11, wprob, bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, 0, s)) return rc;
+    if (int rc = dense(v0, Vc, 0)) return rc;
   }
   return 0;
 }
@@ -660,6 +668,30 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   if (stop_after == 1) return 0;
   (void)VP; (void)P; (void)D;
   return heads(bf, B, depths, out, s, stop_after);
+}
+
+size_t AdaPose::dense_workspace_bytes(int B) {
+  const int sd = sparse_dec, st = sparse_tail;
+  sparse_dec = 0; sparse_tail = 0;
+  const size_t n = workspace_bytes(B);
+  sparse_dec = sd; sparse_tail = st;
+  return n;
+}
+
+int AdaPose::forward_dense(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
+                           const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
+                           float* depth_map, float* conf_map, hipStream_t s) {
+  RGBM_REQUIRE(depth_map != nullptr, "forward_dense: depth_map is null");
+  RGBM_REQUIRE(B > 0, "batch");
+  const size_t need = dense_workspace_bytes(B);
+  RGBM_REQUIRE(workspace_size >= need, "forward_dense: workspace too small: need " + std::to_string(need) + " (rgbm_adapose_dense_workspace_bytes)");
+  const int sd = sparse_dec, st = sparse_tail;
+  sparse_dec = 0; sparse_tail = 0;
+  dense_depth_map = depth_map; dense_conf_map = conf_map;
+  const int rc = forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_size, out, s, 0);
+  dense_depth_map = nullptr; dense_conf_map = nullptr;
+  sparse_dec = sd; sparse_tail = st;
+  return rc;
 }
 
 // Everything behind the PSPNet: reads the feature map(s) in bf.feat / bf.featf, bf.homog, bf.choose (forward() and forward_cached() fill them)

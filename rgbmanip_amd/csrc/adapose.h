@@ -112,6 +112,16 @@ struct AdaPose {
   int forward(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
               const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
               hipStream_t s, int stop_after = 0) const;
+  // forward() with a dense cost regularisation and the dense tail for this one call (sparse_dec = 0, sparse_tail = 0; the handle's
+  // options are restored before it returns), plus the dense head (dense_depth.hip) on every chunk's u11: depth_map / conf_map
+  // [Vh][img][img] fp32, Vh = 2B or, with view2_heads = 0, B.  conf_map may be null.  The ten point outputs are those of a handle built
+  // with the two options.  dense_workspace_bytes(B): the workspace of such a call (the plan holds u11 whatever the options say).
+  size_t dense_workspace_bytes(int B);
+  int forward_dense(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
+                    const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
+                    float* depth_map, float* conf_map, hipStream_t s);
+  float* dense_depth_map = nullptr;      // set for the duration of forward_dense: cost_volume() runs the dense head behind every u11
+  float* dense_conf_map = nullptr;
   // Feature cache: the forward split at the PSPNet's output.  features() runs the PSPNet on V >= 1 views of one image array
   // [V][3][img][img] and writes view v's record (feature_bytes() long) to pool + slots[v] * feature_bytes(); forward_cached() is
   // forward() with the PSPNet replaced by reading records slot1[b] / slot2[b].  Both refuse a net with Dropout2d on.  A slot outside

@@ -186,6 +186,27 @@ int rgbm_adapose_forward(rgbm_adapose_t* h, int B, const float* img1, const floa
   return rgbm_adapose_forward_ex(h, B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, out, 0, stream);
 }
 
+int rgbm_adapose_dense_workspace_bytes(rgbm_adapose_t* h, int B, size_t* bytes) {
+  RGBM_REQUIRE(h && bytes && B > 0, "dense_workspace_bytes arguments");
+  *bytes = h->net.dense_workspace_bytes(B);
+  return 0;
+}
+
+int rgbm_adapose_forward_dense(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
+                               const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
+                               size_t workspace_bytes, const rgbm_adapose_out* out, float* depth_map, float* conf_map, void* stream) {
+  RGBM_REQUIRE(depth_map != nullptr, "forward_dense: depth_map is NULL (conf_map may be, depth_map may not)");
+  RGBM_REQUIRE(h && img1 && img2 && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward_dense arguments");
+  if (h->net.drop_p > 0.f && B > 0)
+    if (int rc = ensure_dropout_capacity(h, B)) return rc;
+  return h->net.forward_dense(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), depth_map,
+                              conf_map, (hipStream_t)stream);
+}
+
+int rgbm_depth_to_points(const float* depth_map, const double* Kcrop, const double* E, int n, int S, float* points, void* stream) {
+  return rgbm::launch_depth_to_points(depth_map, Kcrop, E, n, S, points, (hipStream_t)stream);
+}
+
 int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes) {
   RGBM_REQUIRE(h && bytes, "feature_bytes arguments");
   *bytes = h->net.feature_bytes();

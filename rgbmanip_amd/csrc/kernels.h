@@ -51,6 +51,12 @@ int launch_gather_points(int dtype, const void* feat, const int* choose, float* 
 int launch_prob_softmax_depth(int dtype, const void* u11, const float* wprob, const int* choose, const float* depths,
                               float* prob, float* depth_out, int v0, int Vc, int B, int P, int D, int H, int W, int classmajor,
                               hipStream_t s);
+// dense_depth.hip: the same prob conv + softmax + expected depth at EVERY pixel of views v0 .. v0 + Vc - 1 (u11 of that chunk, either
+// layout) -> depth_map / conf_map [views][H][W] fp32 (conf = max_d p; conf_map may be null); depths [B][D], view v reads row v % B
+int launch_dense_depth(int dtype, const void* u11, const float* wprob, const float* depths, float* depth_map, float* conf_map,
+                       int v0, int Vc, int B, int D, int H, int W, int classmajor, hipStream_t s);
+// depth_points.hip: depth [n][S][S] fp32, Kcrop [n][3][3] / E [n][4][4] fp64 -> world-frame points [n][S][S][3] fp32
+int launch_depth_to_points(const float* depth, const double* Kc, const double* E, int n, int S, float* points, hipStream_t s);
 int launch_fuse_points(int dtype, const void* feat, const float* homog, const float* depths, const int* choose,
                        const float* prob, float* out, int V, int B, int P, int D, int H, int W, int ldo, int ch_off,
                        hipStream_t s, int Vn = -1);      // Vn: views 0 .. Vn - 1 only (default: all V)

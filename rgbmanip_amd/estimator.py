@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, host_prepare
-from .adapose import (AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
+from .adapose import (AdaPoseNet, depth_to_points, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
                       prepare_inputs_windows)
 from .feature_cache import CachedViews, ContentFeatureCache, SlotFeatureCache
 from .host_prepare import _resize_linear, _resize_nearest, get_bbox      # noqa: F401  (part of this module's surface)
@@ -35,6 +35,19 @@ from .upload import (ChunkPipeline, WindowRing, _nonzero_into, _split, frames_pa
 DEFAULT_BBOX = np.asarray([[0, 0, 0], [0, 0, 1], [0, 1, 0], [0, 1, 1], [1, 0, 0], [1, 0, 1], [1, 1, 0], [1, 1, 1]],
                           dtype=np.float64) + 10.0
 _DEPTH_PLANES = np.arange(0.1, 0.1 * (24 - 0.5) + 0.1, 0.1, dtype=np.float32)      # the 24 sweep depths (interface_v5.py:259-262)
+
+
+def _put(out, a, b, res):
+    """Rows a .. b - 1 of a pipelined call's result: the boxes, or every tensor of `estimate_depth`'s dict."""
+    if isinstance(out, dict):
+        for k, v in out.items():
+            v[a:b] = res[k]
+    else:
+        out[a:b] = res
+
+
+def _to_host(out):
+    return {k: v.cpu().numpy() for k, v in out.items()} if isinstance(out, dict) else out.cpu().numpy()
 
 
 class BasePoseEstimator:
@@ -225,26 +238,28 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         return out
 
     # ------------------------------------------------------------------ host frames -> HBM (upload.py)
-    def _estimate_host_frames(self, K, rgb1, mask1, E1, rgb2, mask2, E2):
+    def _estimate_host_frames(self, K, rgb1, mask1, E1, rgb2, mask2, E2, dense=False):
         """`estimate` with `hip_prepare: device`: one `estimate_device` call, or for more than `hip_upload_chunk` host poses the
-        chunk pipeline (upload.ChunkPipeline), whose per-chunk work is defined here."""
+        chunk pipeline (upload.ChunkPipeline), whose per-chunk work is defined here.  `dense`: the dict of `estimate_depth` instead of
+        the boxes (plain path: no content cache)."""
         n = len(rgb1)
         chunk = int(self.cfg.get("hip_upload_chunk", 32))
         cuda = [isinstance(x, torch.Tensor) and x.is_cuda for x in (rgb1, rgb2, mask1, mask2)]
         if self.upload_mode == "windows" and not any(cuda):
-            return self._estimate_host_windows(K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk)
+            return self._estimate_host_windows(K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk, dense)
         self.upload_bytes_last_call, self.upload_table_bytes_last_call = frames_payload_bytes(rgb1, rgb2, mask1, mask2), 0
         on_dev = cuda[0] or cuda[1]
+        on_device = self.estimate_depth_device if dense else self.estimate_device
         if on_dev or n <= chunk or chunk <= 0:
-            return self.estimate_device(np.asarray(K), self._upload_frames(rgb1), self._upload_masks(mask1), np.asarray(E1),
-                                        self._upload_frames(rgb2), self._upload_masks(mask2), np.asarray(E2)).cpu().numpy()
+            return _to_host(on_device(np.asarray(K), self._upload_frames(rgb1), self._upload_masks(mask1), np.asarray(E1),
+                                      self._upload_frames(rgb2), self._upload_masks(mask2), np.asarray(E2)))
         dev = self.estimator.device
         srcs = [host_array(x) for x in (rgb1, rgb2, mask1, mask2)]
         pipe = self._pipe = ChunkPipeline.matching(self._pipe, chunk, srcs, dev)
         Kd = torch.as_tensor(np.asarray(K)).to(dev)
         E1d, E2d = torch.as_tensor(np.asarray(E1)).to(dev), torch.as_tensor(np.asarray(E2)).to(dev)
-        out = torch.empty(n, 8, 3, dtype=torch.float64, device=dev)
-        if self.feature_content:
+        out = self._alloc_out(n, dev, dense)
+        if self.feature_content and not dense:
             self._content.reserve(n)
             S, wp = self.cfg["img_size"], self._pnp_branch()
 
@@ -259,13 +274,13 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             pipe.run_keyed(srcs, n, prepare, network)
         else:
             def network(a, b, d):
-                out[a:b] = self.estimate_device(Kd[a:b], self._upload_frames(d[0]), d[2], E1d[a:b], self._upload_frames(d[1]), d[3], E2d[a:b], frame0=a)
+                _put(out, a, b, on_device(Kd[a:b], self._upload_frames(d[0]), d[2], E1d[a:b], self._upload_frames(d[1]), d[3], E2d[a:b], frame0=a))
             pipe.run(srcs, n, network)
-        res = out.cpu().numpy()
+        res = _to_host(out)
         pipe.trace.report(self.upload_bytes_last_call)
         return res
 
-    def _estimate_host_windows(self, K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk):
+    def _estimate_host_windows(self, K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk, dense=False):
         """`_estimate_host_frames` with hip_upload: "windows": the host derives every frame's crop window from its mask, packs that part of
         the frame and of the mask into pinned staging and uploads the packed buffers (upload.WindowRing); `rgbm_prepare_inputs_windows`
         writes img / choose / pts2d / Kcrop / valid from them and everything behind is the code of the whole-frame path.  At most
@@ -275,6 +290,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         Kd = torch.as_tensor(np.asarray(K)).to(dev)
         E1d, E2d = torch.as_tensor(np.asarray(E1)).to(dev), torch.as_tensor(np.asarray(E2)).to(dev)
         S, wp = self.cfg["img_size"], self._pnp_branch()
+        kw = {"dense": True} if dense else {}
 
         def prep(a, b, d):
             return [self._prepare_windows(d, v, Kd[a:b], S, 1024, self.prepare_seed + v, want_pts2d=wp, frame0=a) for v in (0, 1)]
@@ -284,19 +300,19 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             ring.wait(0)
             ring.stage(0, srcs, 0, n)
             pa, pb = prep(0, n, ring.copy(0, n))
-            if self.feature_content:
+            if self.feature_content and not dense:
                 self._content.reserve(n)
                 out = self._estimate_keyed(self._content.keys(pa, pb), E1d, E2d, Kd)
             else:
-                out = self._estimate_prepared(pa, pb, E1d, E2d, Kd)
-            res = out.cpu().numpy()
+                out = self._estimate_prepared(pa, pb, E1d, E2d, Kd, **kw)
+            res = _to_host(out)
             self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
             return res
         pipe = self._pipe = ChunkPipeline.matching(self._pipe, chunk, srcs, dev, windows=True)
         ring = pipe.ring
         ring.payload_bytes = ring.table_bytes = 0
-        out = torch.empty(n, 8, 3, dtype=torch.float64, device=dev)
-        if self.feature_content:
+        out = self._alloc_out(n, dev, dense)
+        if self.feature_content and not dense:
             self._content.reserve(n)
 
             def prepare(a, b, d):
@@ -309,9 +325,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         else:
             def network(a, b, d):
                 pa, pb = prep(a, b, d)
-                out[a:b] = self._estimate_prepared(pa, pb, E1d[a:b], E2d[a:b], Kd[a:b])
+                _put(out, a, b, self._estimate_prepared(pa, pb, E1d[a:b], E2d[a:b], Kd[a:b], **kw))
             pipe.run(srcs, n, network)
-        res = out.cpu().numpy()
+        res = _to_host(out)
         self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
         pipe.trace.report(self.upload_bytes_last_call)
         return res
@@ -343,16 +359,49 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         uint8 (byte b = the pixel fl32(b / 255); read as bytes, same boxes bit for bit), mask [N,H,W], E [N,4,4] world->camera.
         Returns a CUDA tensor [N,8,3] float64; samples the reference would skip
         (empty mask) or reject (non-finite box) hold `default_bbox`."""
+        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0)
+
+    def _estimate_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0, dense: bool = False):
         S = self.cfg["img_size"]
         dev = self.estimator.device
         Kd = torch.as_tensor(K).to(dev)
         wp = self._pnp_branch()
         a = self._prepare(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, S, 1024, self.prepare_seed, want_pts2d=wp, frame0=frame0)
         b = self._prepare(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=frame0)
-        if self.feature_content:      # one host synchronisation per call: the keys must be on the host before the network can be enqueued
+        if self.feature_content and not dense:      # one host synchronisation per call: the keys must be on the host before the network can be enqueued
             self._content.reserve(int(Kd.shape[0]))
             return self._estimate_keyed(self._content.keys(a, b), E1, E2, Kd)
-        return self._estimate_prepared(a, b, E1, E2, Kd)
+        return self._estimate_prepared(a, b, E1, E2, Kd, **({"dense": True} if dense else {}))
+
+    # ------------------------------------------------------------------ dense depth of the view-1 crops (DESIGN.md "Dense depth maps")
+    def estimate_depth(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
+                       view2_mask_batch, view2_extrinsic_batch):
+        """`estimate` (same arguments, frame dtypes, hip_upload modes and chunk pipeline) returning what the cost volume holds for the
+        view-1 crop of every sample, as a dict of numpy arrays: `bbox` [n,8,3] f64 (the box `estimate` builds from the dense-tail
+        outputs), `depth` / `conf` [n,S,S] f32 (expected depth and largest plane probability at every pixel of the crop), `points`
+        [n,S,S,3] f32 (the depth map back-projected into the world frame), `window` [n,4] i32 (rmin, rmax, cmin, cmax: where the crop
+        lies in the frame), `Kcrop` [n,3,3] f64 (the crop's intrinsics), `valid` [n] i32.  A sample with an empty mask has valid 0, NaN
+        maps and the +10 cube.  The network runs densely and on the plain path: cfg hip_feature_cache is bypassed for this call
+        (counted in `feature_cache_bypassed`), hip_graph is ignored."""
+        if self.prepare_mode != "device":
+            raise ValueError(f'estimate_depth crops on the device: it needs hip_prepare: "device", got {self.prepare_mode!r}')
+        return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
+                                          view2_mask_batch, view2_extrinsic_batch, dense=True)
+
+    def estimate_depth_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0):
+        """`estimate_depth` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
+        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=True)
+
+    def _alloc_out(self, n, dev, dense):
+        """What the chunks of a pipelined call are written into: the boxes, or the tensors of `estimate_depth`."""
+        if not dense:
+            return torch.empty(n, 8, 3, dtype=torch.float64, device=dev)
+        S = self.cfg["img_size"]
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"bbox": torch.empty(n, 8, 3, dtype=torch.float64, device=dev), "depth": torch.empty(n, S, S, **f32),
+                "conf": torch.empty(n, S, S, **f32), "points": torch.empty(n, S, S, 3, **f32),
+                "window": torch.empty(n, 4, dtype=torch.int32, device=dev), "Kcrop": torch.empty(n, 3, 3, dtype=torch.float64, device=dev),
+                "valid": torch.empty(n, dtype=torch.int32, device=dev)}
 
     def estimate_device_indexed(self, K, rgb_pool, mask_pool, E1, E2, map1, map2, fresh=None):
         """`estimate_device` reading the two views of sample i from entries map1[i] / map2[i] of a frame pool
@@ -387,7 +436,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     def _pnp_branch(self):
         return not self.cfg.get("direct_regression", True) and not self.cfg.get("use_depth", True)
 
-    def _estimate_prepared(self, a, b, E1, E2, K=None, cached: CachedViews | None = None):
+    def _estimate_prepared(self, a, b, E1, E2, K=None, cached: CachedViews | None = None, dense: bool = False):
         dev = self.estimator.device
         E1d = torch.as_tensor(E1).to(device=dev, dtype=torch.float64)
         E2d = torch.as_tensor(E2).to(device=dev, dtype=torch.float64)
@@ -404,7 +453,13 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         if consts is None or consts[0].device != dev:
             consts = self._dev_consts = (torch.from_numpy(DEFAULT_BBOX).to(dev), torch.from_numpy(_DEPTH_PLANES).to(dev))
         depths = consts[1][None].expand(n, 24).contiguous()
-        if cached is None:
+        if dense:
+            assert cached is None
+            pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], proj(a["Kcrop"], E1d), proj(b["Kcrop"], E2d), depths,
+                                  dense_depth=True)
+            self._plain_views += 2 * n
+            self._content.bypassed += int(self.feature_cache)      # a call / chunk the cache was set for and did not serve
+        elif cached is None:
             pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], proj(a["Kcrop"], E1d), proj(b["Kcrop"], E2d), depths)
             self._plain_views += 2 * n
         else:
@@ -414,7 +469,14 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         ok = (a["valid"] != 0) & (b["valid"] != 0)
         if cached is not None and cached.ok is not None:
             ok = ok & cached.ok
-        return torch.where(ok.view(n, 1, 1), bbox, consts[0].expand(n, 8, 3))
+        box = torch.where(ok.view(n, 1, 1), bbox, consts[0].expand(n, 8, 3))
+        if not dense:
+            return box
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+        depth = torch.where(ok.view(n, 1, 1), pred["view1_depth_map"], nan)
+        conf = torch.where(ok.view(n, 1, 1), pred["view1_depth_conf"], nan)
+        return {"bbox": box, "depth": depth, "conf": conf, "points": depth_to_points(depth, a["Kcrop"], E1d),      # NaN depth -> NaN points
+                "window": a["window"], "Kcrop": a["Kcrop"], "valid": ok.to(torch.int32)}
 
     def _bbox_tail(self, pred, choose, Kcrop, E1, pts2d=None, E2=None, K=None):
         """interface_v5.py:318-374: scale / translation from the regressed rotation (`direct_regression`, the shipped configs)
