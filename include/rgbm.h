@@ -135,6 +135,32 @@ int rgbm_adapose_forward_dense(rgbm_adapose_t* h, int B, const float* img1, cons
                                size_t workspace_bytes, const rgbm_adapose_out* out, float* depth_map, float* conf_map, void* stream);
 int rgbm_depth_to_points(const float* depth_map, const double* Kcrop, const double* E, int n, int S, float* points, void* stream);
 
+/* Two-view geometric consistency of dense depth maps, and the packed point cloud of the pixels that pass it.
+ * rgbm_depth_consistency: depth_a / depth_b [n][S][S] fp32 (camera z of the crops of views a and b), Kcrop_* [n][3][3] fp64 (fx, fy, cx,
+ *   cy are read), E_* [n][4][4] fp64 (world -> camera); conf_a [n][S][S] fp32 and mask_a [n][S][S] uint8 may be NULL.  Per pixel (x, y)
+ *   of view a with depth d, in fp64, rounded once into the fp32 results:
+ *     1. d not finite or <= 0, or an E without a finite inverse: keep 0, fused / reproj / rel NaN;
+ *     2. X = inv(E_a) (d Kcrop_a^-1 (x, y, 1)^T), (u, v, z) its projection through Kcrop_b E_b[:3]; z <= 0 or u, v outside
+ *        [0, S - 1]: as 1;
+ *     3. depth_b sampled bilinearly at (u, v) (taps floor(u) and min(floor(u) + 1, S - 1), v alike); a tap that is not finite or <= 0:
+ *        as 1;
+ *     4. (u, v) at the sampled depth back-projected through view b and projected into view a: (x', y', d'); reproj = hypot(x' - x,
+ *        y' - y) in pixels, rel = |d' - d| / d — written whatever step 5 decides (diagnostic maps; reproj and rel may be NULL);
+ *     5. keep = reproj < px_max && rel < rel_max && (conf_a == NULL || conf >= conf_min) && (mask_a == NULL || mask != 0);
+ *        fused = keep ? (d + d') / 2 : NaN.
+ *   px_max, rel_max, conf_min: finite and >= 0.  n <= 65535, S <= 4096.
+ * rgbm_cloud_pack: ordered compaction.  For pose i the pixels of view 1 with keep1 != 0 in row-major order, then those of view 2, each
+ *   back-projected to the world frame with the arithmetic of rgbm_depth_to_points (same bits): cloud [n][cap][3] fp32, index [n][cap]
+ *   int32 = view * S * S + pixel (view 0 or 1), count [n][2] int32 = the pixels kept per view — the full counts even when their sum
+ *   exceeds cap.  Only the first cap rows are written; rows min(cap, total) .. cap - 1 hold NaN / -1.  fused2, keep2, Kcrop2 and E2 may
+ *   be NULL together (a one-view cloud).  The order does not depend on scheduling (no atomics); cap >= 0. */
+int rgbm_depth_consistency(const float* depth_a, const float* conf_a, const uint8_t* mask_a, const double* Kcrop_a, const double* E_a,
+                           const float* depth_b, const double* Kcrop_b, const double* E_b, int n, int S, double px_max, double rel_max,
+                           float conf_min, float* fused, float* reproj, float* rel, uint8_t* keep, void* stream);
+int rgbm_cloud_pack(const float* fused1, const uint8_t* keep1, const double* Kcrop1, const double* E1, const float* fused2,
+                    const uint8_t* keep2, const double* Kcrop2, const double* E2, int n, int S, int cap, float* cloud, int32_t* index,
+                    int32_t* count, void* stream);
+
 /* Post-processing of one batch of network outputs into world-frame handle boxes.
  * Replaces: compute_scale_and_translation / get_3d_bbox / transform_coordinates_3d and the tail of predict()
  *   models/pose_estimator/AdaPose/lib/utils.py:40-119, models/pose_estimator/AdaPose/interface_v5.py:318-321,354-374

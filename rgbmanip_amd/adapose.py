@@ -457,6 +457,141 @@ def depth_to_points_ref(depth_map, K_crop, E):
     return out
 
 
+def _view_args(depth, K_crop, E, dev=None):
+    d = torch.as_tensor(depth)
+    if dev is None:
+        dev = d.device if d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    d = d.to(device=dev, dtype=torch.float32).contiguous()
+    n, S = d.shape[0], d.shape[1]
+    assert d.shape == (n, S, S), d.shape
+    K = torch.as_tensor(K_crop).to(device=dev, dtype=torch.float64).contiguous()
+    Ed = torch.as_tensor(E).to(device=dev, dtype=torch.float64).contiguous()
+    assert K.shape == (n, 3, 3) and Ed.shape == (n, 4, 4), (K.shape, Ed.shape)
+    return d, K, Ed, dev
+
+
+def depth_consistency(depth_a, Kcrop_a, E_a, depth_b, Kcrop_b, E_b, conf_a=None, mask_a=None, px_max: float = 1.0, rel_max: float = 0.01,
+                      conf_min: float = 0.0, stream=None, want_diagnostics: bool = True):
+    """Two-view geometric consistency of view a's depth map against view b's (rgbm_depth_consistency): every pixel
+    of depth_a [n,S,S] is back-projected, projected into view b, depth_b is sampled there bilinearly, back-projected and projected back
+    into view a; the pixel is kept when it lands within `px_max` pixels of where it started at a depth within `rel_max` (relative), its
+    confidence (conf_a [n,S,S], optional) is at least `conf_min` and its mask byte (mask_a [n,S,S], optional) is set.  Kcrop_* [n,3,3],
+    E_* [n,4,4] world -> camera.  Returns a dict of CUDA tensors [n,S,S]: `fused` f32 (mean of the two depths where kept, NaN elsewhere),
+    `reproj` f32 (pixels) and `rel` f32 (NaN where the pixel could not be sampled; None with want_diagnostics=False), `keep` uint8."""
+    lib = _lib.load()
+    da, Ka, Ea, dev = _view_args(depth_a, Kcrop_a, E_a)
+    db, Kb, Eb, _ = _view_args(depth_b, Kcrop_b, E_b, dev)
+    n, S = da.shape[0], da.shape[1]
+    assert db.shape == da.shape, (da.shape, db.shape)
+    conf = None if conf_a is None else torch.as_tensor(conf_a).to(device=dev, dtype=torch.float32).contiguous()
+    mask = None
+    if mask_a is not None:
+        mask = torch.as_tensor(mask_a).to(device=dev)
+        mask = (mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)).contiguous()
+    assert (conf is None or conf.shape == da.shape) and (mask is None or mask.shape == da.shape)
+    fused = torch.empty(n, S, S, dtype=torch.float32, device=dev)
+    reproj = torch.empty_like(fused) if want_diagnostics else None
+    rel = torch.empty_like(fused) if want_diagnostics else None
+    keep = torch.empty(n, S, S, dtype=torch.uint8, device=dev)
+    if n:
+        _lib.check(lib.rgbm_depth_consistency(_lib.ptr(da), _lib.ptr(conf), _lib.ptr(mask), _lib.ptr(Ka), _lib.ptr(Ea), _lib.ptr(db), _lib.ptr(Kb),
+                                              _lib.ptr(Eb), n, S, float(px_max), float(rel_max), float(conf_min), _lib.ptr(fused),
+                                              _lib.ptr(reproj), _lib.ptr(rel), _lib.ptr(keep), _lib.stream_ptr(stream)), "rgbm_depth_consistency")
+    return {"fused": fused, "reproj": reproj, "rel": rel, "keep": keep}
+
+
+def depth_consistency_ref(depth_a, Kcrop_a, E_a, depth_b, Kcrop_b, E_b, conf_a=None, mask_a=None, px_max: float = 1.0, rel_max: float = 0.01,
+                          conf_min: float = 0.0):
+    """float64 numpy twin of `depth_consistency` (tests, documentation): rules 1-5 of DESIGN.md section 5k.  Returns dict(fused, reproj,
+    rel [n,S,S] float64, keep [n,S,S] bool).  Also returns `sampled` (bool: the pixel passed rules 1-3, i.e. reproj / rel are numbers)."""
+    da, db = np.asarray(depth_a, dtype=np.float64), np.asarray(depth_b, dtype=np.float64)
+    Ka, Kb = np.asarray(Kcrop_a, dtype=np.float64), np.asarray(Kcrop_b, dtype=np.float64)
+    Ea, Eb = np.asarray(E_a, dtype=np.float64), np.asarray(E_b, dtype=np.float64)
+    n, S = da.shape[0], da.shape[1]
+    yy, xx = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64), indexing="ij")
+    out = {k: np.full((n, S, S), np.nan) for k in ("fused", "reproj", "rel")}
+    out["keep"] = np.zeros((n, S, S), dtype=bool)
+    out["sampled"] = np.zeros((n, S, S), dtype=bool)
+
+    def back(inv, K, x, y, z):                             # pixel at depth z -> world
+        cam = np.stack([(x - K[0, 2]) * z / K[0, 0], (y - K[1, 2]) * z / K[1, 1], z], axis=-1)
+        return cam @ inv[:3, :3].T + inv[:3, 3]
+
+    def project(E, K, X):                                  # world -> (u, v, z)
+        c = X @ E[:3, :3].T + E[:3, 3]
+        return K[0, 0] * c[..., 0] / c[..., 2] + K[0, 2], K[1, 1] * c[..., 1] / c[..., 2] + K[1, 2], c[..., 2]
+
+    for i in range(n):
+        try:
+            inv_a, inv_b = np.linalg.inv(Ea[i]), np.linalg.inv(Eb[i])
+        except np.linalg.LinAlgError:
+            continue
+        if not (np.isfinite(inv_a).all() and np.isfinite(inv_b).all()):
+            continue
+        with np.errstate(all="ignore"):
+            d = da[i]
+            ok = np.isfinite(d) & (d > 0)                                                                   # rule 1
+            dz = np.where(ok, d, 1.0)
+            u, v, z = project(Eb[i], Kb[i], back(inv_a, Ka[i], xx, yy, dz))
+            ok &= (z > 0) & (u >= 0) & (u <= S - 1) & (v >= 0) & (v <= S - 1)                               # rule 2
+            us, vs = np.where(ok, u, 0.0), np.where(ok, v, 0.0)
+            x0, y0 = np.floor(us).astype(np.int64), np.floor(vs).astype(np.int64)
+            x1, y1 = np.minimum(x0 + 1, S - 1), np.minimum(y0 + 1, S - 1)
+            t00, t01, t10, t11 = db[i][y0, x0], db[i][y0, x1], db[i][y1, x0], db[i][y1, x1]
+            for t in (t00, t01, t10, t11):
+                ok &= np.isfinite(t) & (t > 0)                                                              # rule 3
+            ax, ay = us - x0, vs - y0
+            samp = (t00 * (1 - ax) + t01 * ax) * (1 - ay) + (t10 * (1 - ax) + t11 * ax) * ay
+            xr, yr, dr = project(Ea[i], Ka[i], back(inv_b, Kb[i], us, vs, samp))                           # rule 4
+            reproj, rel = np.hypot(xr - xx, yr - yy), np.abs(dr - d) / d
+            keep = ok & (reproj < px_max) & (rel < rel_max)                                                 # rule 5
+            if conf_a is not None:
+                keep &= np.asarray(conf_a[i], dtype=np.float32) >= np.float32(conf_min)
+            if mask_a is not None:
+                keep &= np.asarray(mask_a[i]) != 0
+        out["reproj"][i][ok], out["rel"][i][ok] = reproj[ok], rel[ok]
+        out["fused"][i][keep] = ((d + dr) / 2)[keep]
+        out["keep"][i], out["sampled"][i] = keep, ok
+    return out
+
+
+def cloud_pack(fused1, keep1, Kcrop1, E1, fused2=None, keep2=None, Kcrop2=None, E2=None, max_points=None, stream=None):
+    """Packed world-frame point cloud of the kept pixels (rgbm_cloud_pack): for pose i the pixels of view 1 with
+    keep1 != 0 in row-major order, then those of view 2 (all four view-2 arguments, or none for a one-view cloud), each back-projected
+    exactly as `depth_to_points` does.  Returns CUDA tensors (cloud [n,cap,3] f32, index [n,cap] i32 = view * S * S + pixel, count [n,2]
+    i32 = pixels kept per view, whatever cap is); rows past the kept pixels hold NaN / -1.  cap = max_points, default the worst case
+    (2 S S, or S S for one view).  The order is fixed: two calls give the same bytes."""
+    lib = _lib.load()
+    f1, K1, E1d, dev = _view_args(fused1, Kcrop1, E1)
+    n, S = f1.shape[0], f1.shape[1]
+    two = [x is not None for x in (fused2, keep2, Kcrop2, E2)]
+    if any(two) != all(two):
+        raise ValueError("cloud_pack: fused2, keep2, Kcrop2 and E2 are given together or not at all")
+
+    def keep_of(k):
+        k = torch.as_tensor(k).to(device=dev)
+        k = (k if k.dtype == torch.uint8 else (k != 0).to(torch.uint8)).contiguous()
+        assert k.shape == (n, S, S), k.shape
+        return k
+    k1 = keep_of(keep1)
+    f2 = K2 = E2d = k2 = None
+    if all(two):
+        f2, K2, E2d, _ = _view_args(fused2, Kcrop2, E2, dev)
+        assert f2.shape == f1.shape, (f1.shape, f2.shape)
+        k2 = keep_of(keep2)
+    cap = (2 if all(two) else 1) * S * S if max_points is None else int(max_points)
+    if cap < 0:
+        raise ValueError(f"cloud_pack: max_points >= 0, got {max_points}")
+    cloud = torch.empty(n, cap, 3, dtype=torch.float32, device=dev)
+    index = torch.empty(n, cap, dtype=torch.int32, device=dev)
+    count = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    if n:
+        _lib.check(lib.rgbm_cloud_pack(_lib.ptr(f1), _lib.ptr(k1), _lib.ptr(K1), _lib.ptr(E1d), _lib.ptr(f2), _lib.ptr(k2), _lib.ptr(K2),
+                                       _lib.ptr(E2d), n, S, cap, _lib.ptr(cloud), _lib.ptr(index), _lib.ptr(count), _lib.stream_ptr(stream)),
+                   "rgbm_cloud_pack")
+    return cloud, index, count
+
+
 def postprocess_regressed(view1_nocs, view1_r, view1_t, view1_s, E1, stream=None):
     """Device tail of `AdaPoseEstimator_v4.predict` for `direct_regression: True` (`interface_v4.py:322-325, 358-378`): translation
     view1_t and scale ||view1_s|| from the network's own heads, no pair median.  Returns (bbox_world [B,8,3] f64, ts [B,4] f64 =
@@ -519,7 +654,7 @@ def postprocess_pnp(view1_nocs, view1_pts2d, view2_nocs, view2_pts2d, K, E1, E2,
 
 
 def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: int = 0, want_pts2d: bool = False, stream=None,
-                   frame_map=None, frame0: int = 0, normalize: bool = True):
+                   frame_map=None, frame0: int = 0, normalize: bool = True, want_mask: bool = False):
     """Batched device-side `AdaPoseEstimator_v5.prepare_model_input` (`interface_v5.py:58-170`).
 
     rgb [N,H,W,3] float32 in [0,1], mask [N,H,W] (0/1), K [N,3,3]: torch CUDA tensors (or anything torch.as_tensor accepts).
@@ -529,7 +664,8 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     (negative: no view -> valid 0) — no gather of the selected frames is needed; K stays [N,3,3].
     `normalize=False` (`rgbm_prepare_inputs_opt`): img is the resized crop itself, without the ImageNet mean / std step — the plain
     `ToTensor` transform of `AdaPoseEstimator_v4` for every task but "pots" (`interface_v4.py:52-58`); every other output is unchanged.
-    Returns dict(img [N,3,S,S] f32, choose [N,P] i32, Kcrop [N,3,3] f64, window [N,4] i32, valid [N] i32[, pts2d])."""
+    `want_mask=True` adds `mask` [N,S,S] uint8: the nearest-neighbour resize of the frame mask's crop window that `choose` is drawn from.
+    Returns dict(img [N,3,S,S] f32, choose [N,P] i32, Kcrop [N,3,3] f64, window [N,4] i32, valid [N] i32[, pts2d][, mask])."""
     lib = _lib.load()
     dev = rgb.device if isinstance(rgb, torch.Tensor) and rgb.is_cuda else torch.device("cuda", torch.cuda.current_device())
     rgb = torch.as_tensor(rgb)
@@ -574,16 +710,18 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     out = {"img": img, "choose": choose, "Kcrop": Kcrop, "window": window, "valid": valid}
     if want_pts2d:
         out["pts2d"] = pts2d
+    if want_mask:
+        out["mask"] = scratch.view(N, S, S)
     return out
 
 
 def prepare_inputs_windows(pix, mask_pix, offset, window, valid_in, K, H: int, W: int, img_size: int = 224, n_pts: int = 1024, seed: int = 0,
-                           want_pts2d: bool = False, stream=None, frame0: int = 0, normalize: bool = True):
+                           want_pts2d: bool = False, stream=None, frame0: int = 0, normalize: bool = True, want_mask: bool = False):
     """`prepare_inputs` from crop windows the host has cut out of the frames and packed (`rgbm_prepare_inputs_windows`, cfg hip_upload:
     "windows"; upload.mask_windows / pack_windows): pix flat float32 or uint8 (3 elements per pixel), mask_pix flat uint8, offset [N]
     int64 (pixel offset of frame f's window in both), window [N,4] int32, valid_in [N] int32 (0: empty mask) — CUDA tensors; K [N,3,3];
     H, W: the size of the frames the windows were cut from.  Returns the dict of `prepare_inputs`, bit for bit what it returns for the
-    whole frames (its "window" is the tensor handed in)."""
+    whole frames (its "window" is the tensor handed in; `want_mask` as there)."""
     lib = _lib.load()
     dev = pix.device
     if pix.dtype not in (torch.uint8, torch.float32) or mask_pix.dtype != torch.uint8:
@@ -609,6 +747,8 @@ def prepare_inputs_windows(pix, mask_pix, offset, window, valid_in, K, H: int, W
     out = {"img": img, "choose": choose, "Kcrop": Kcrop, "window": window, "valid": valid}
     if want_pts2d:
         out["pts2d"] = pts2d
+    if want_mask:
+        out["mask"] = scratch.view(N, S, S)
     return out
 
 

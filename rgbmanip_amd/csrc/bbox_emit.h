@@ -31,6 +31,25 @@ __device__ inline bool invert_extrinsic(long long b, const double* __restrict__ 
   return ok;
 }
 
+// inv(E) of view b as the 3 x 4 matrix [R | t] (row-major, 12 doubles) the back-projection below applies; false: no finite inverse
+__device__ inline bool invert_extrinsic_rows(long long b, const double* __restrict__ E, double* inv /*[12]*/) {
+  double a[4][8];
+  const bool ok = invert_extrinsic(b, E, a);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) inv[i * 4 + j] = a[i][4 + j];
+  return ok;
+}
+
+// pixel (x, y) of a crop at camera depth z -> world frame: cam = ((x - cx) z / fx, (y - cy) z / fy, z), world = inv[:, :3] cam + inv[:, 3]
+// (interface_v5.py:329-336, 369-372).  The ONE expression depth_points.hip and depth_consistency.hip evaluate (both built without
+// contraction), so that a packed cloud point equals the point image's bit for bit.
+__device__ inline void backproject_world(const double* inv /*[12]*/, double x, double y, double z, double fx, double fy, double cx, double cy,
+                                         double out[3]) {
+  const double c0 = (x - cx) * z / fx, c1 = (y - cy) * z / fy;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) out[r] = inv[r * 4 + 0] * c0 + inv[r * 4 + 1] * c1 + inv[r * 4 + 2] * z + inv[r * 4 + 3];
+}
+
 // camera-frame corners -> world frame through `a` (invert_extrinsic), or default_bbox (+10 cube) and valid = 0 when !ok or a corner is
 // non-finite
 __device__ inline void emit_corners_world(long long b, const double cam[8][3], bool ok, const double a[4][8], double* __restrict__ bbox,

@@ -207,6 +207,19 @@ int rgbm_depth_to_points(const float* depth_map, const double* Kcrop, const doub
   return rgbm::launch_depth_to_points(depth_map, Kcrop, E, n, S, points, (hipStream_t)stream);
 }
 
+int rgbm_depth_consistency(const float* depth_a, const float* conf_a, const uint8_t* mask_a, const double* Kcrop_a, const double* E_a,
+                           const float* depth_b, const double* Kcrop_b, const double* E_b, int n, int S, double px_max, double rel_max,
+                           float conf_min, float* fused, float* reproj, float* rel, uint8_t* keep, void* stream) {
+  return rgbm::launch_depth_consistency(depth_a, conf_a, mask_a, Kcrop_a, E_a, depth_b, Kcrop_b, E_b, n, S, px_max, rel_max, conf_min, fused,
+                                        reproj, rel, keep, (hipStream_t)stream);
+}
+
+int rgbm_cloud_pack(const float* fused1, const uint8_t* keep1, const double* Kcrop1, const double* E1, const float* fused2,
+                    const uint8_t* keep2, const double* Kcrop2, const double* E2, int n, int S, int cap, float* cloud, int32_t* index,
+                    int32_t* count, void* stream) {
+  return rgbm::launch_cloud_pack(fused1, keep1, Kcrop1, E1, fused2, keep2, Kcrop2, E2, n, S, cap, cloud, index, count, (hipStream_t)stream);
+}
+
 int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes) {
   RGBM_REQUIRE(h && bytes, "feature_bytes arguments");
   *bytes = h->net.feature_bytes();

@@ -16,12 +16,7 @@ __global__ __launch_bounds__(256) void depth_to_points_kernel(const float* __res
   __shared__ double inv[12];
   __shared__ int inv_ok;
   const long long v = blockIdx.y;
-  if (threadIdx.x == 0) {
-    double a[4][8];
-    inv_ok = invert_extrinsic(v, E, a) ? 1 : 0;
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 4; ++j) inv[i * 4 + j] = a[i][4 + j];
-  }
+  if (threadIdx.x == 0) inv_ok = invert_extrinsic_rows(v, E, inv) ? 1 : 0;
   __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S * S) return;
@@ -34,10 +29,10 @@ __global__ __launch_bounds__(256) void depth_to_points_kernel(const float* __res
     o[0] = qnan; o[1] = qnan; o[2] = qnan;
     return;
   }
-  const double z = (double)zf;
-  const double c0 = ((double)x - cx) * z / fx, c1 = ((double)y - cy) * z / fy;
+  double w[3];
+  backproject_world(inv, (double)x, (double)y, (double)zf, fx, fy, cx, cy, w);
 #pragma unroll
-  for (int r = 0; r < 3; ++r) o[r] = (float)(inv[r * 4 + 0] * c0 + inv[r * 4 + 1] * c1 + inv[r * 4 + 2] * z + inv[r * 4 + 3]);
+  for (int r = 0; r < 3; ++r) o[r] = (float)w[r];
 }
 
 int launch_depth_to_points(const float* depth, const double* Kc, const double* E, int n, int S, float* points, hipStream_t s) {

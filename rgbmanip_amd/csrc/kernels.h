@@ -57,6 +57,15 @@ int launch_dense_depth(int dtype, const void* u11, const float* wprob, const flo
                        int v0, int Vc, int B, int D, int H, int W, int classmajor, hipStream_t s);
 // depth_points.hip: depth [n][S][S] fp32, Kcrop [n][3][3] / E [n][4][4] fp64 -> world-frame points [n][S][S][3] fp32
 int launch_depth_to_points(const float* depth, const double* Kc, const double* E, int n, int S, float* points, hipStream_t s);
+// depth_consistency.hip: the two-view check of view a's map [n][S][S] against view b's (conf_a fp32 / mask_a uint8 / reproj / rel may be
+// null) -> fused / reproj / rel fp32, keep uint8; and the ordered compaction of the kept pixels of view 1, then view 2 (the view-2
+// arguments null together: one view) into cloud [n][cap][3] fp32, index [n][cap] i32 (view * S * S + pixel), count [n][2] i32
+int launch_depth_consistency(const float* depth_a, const float* conf_a, const unsigned char* mask_a, const double* Ka, const double* Ea,
+                             const float* depth_b, const double* Kb, const double* Eb, int n, int S, double px_max, double rel_max,
+                             float conf_min, float* fused, float* reproj, float* rel, unsigned char* keep, hipStream_t s);
+int launch_cloud_pack(const float* fused1, const unsigned char* keep1, const double* K1, const double* E1, const float* fused2,
+                      const unsigned char* keep2, const double* K2, const double* E2, int n, int S, int cap, float* cloud, int* index,
+                      int* count, hipStream_t s);
 int launch_fuse_points(int dtype, const void* feat, const float* homog, const float* depths, const int* choose,
                        const float* prob, float* out, int V, int B, int P, int D, int H, int W, int ldo, int ch_off,
                        hipStream_t s, int Vn = -1);      // Vn: views 0 .. Vn - 1 only (default: all V)

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, host_prepare
-from .adapose import (AdaPoseNet, depth_to_points, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
+from .adapose import (AdaPoseNet, cloud_pack, depth_consistency, depth_to_points, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
                       prepare_inputs_windows)
 from .feature_cache import CachedViews, ContentFeatureCache, SlotFeatureCache
 from .host_prepare import _resize_linear, _resize_nearest, get_bbox      # noqa: F401  (part of this module's surface)
@@ -44,6 +44,13 @@ def _put(out, a, b, res):
             v[a:b] = res[k]
     else:
         out[a:b] = res
+
+
+class _Cloud(dict):
+    """The options of `estimate_cloud` (px_max, rel_max, conf_min, masked, cap) on their way through the chunk pipeline, in the place of
+    `dense=True`: the third output shape beside the boxes and the dict of `estimate_depth`."""
+    def __bool__(self):
+        return True
 
 
 def _to_host(out):
@@ -240,8 +247,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     # ------------------------------------------------------------------ host frames -> HBM (upload.py)
     def _estimate_host_frames(self, K, rgb1, mask1, E1, rgb2, mask2, E2, dense=False):
         """`estimate` with `hip_prepare: device`: one `estimate_device` call, or for more than `hip_upload_chunk` host poses the
-        chunk pipeline (upload.ChunkPipeline), whose per-chunk work is defined here.  `dense`: the dict of `estimate_depth` instead of
-        the boxes (plain path: no content cache)."""
+        chunk pipeline (upload.ChunkPipeline), whose per-chunk work is defined here.  `dense`: the dict of `estimate_depth` (True) or of
+        `estimate_cloud` (a `_Cloud`) instead of the boxes (plain path: no content cache)."""
         n = len(rgb1)
         chunk = int(self.cfg.get("hip_upload_chunk", 32))
         cuda = [isinstance(x, torch.Tensor) and x.is_cuda for x in (rgb1, rgb2, mask1, mask2)]
@@ -250,6 +257,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         self.upload_bytes_last_call, self.upload_table_bytes_last_call = frames_payload_bytes(rgb1, rgb2, mask1, mask2), 0
         on_dev = cuda[0] or cuda[1]
         on_device = self.estimate_depth_device if dense else self.estimate_device
+        if isinstance(dense, _Cloud):
+            def on_device(*args, frame0=0):
+                return self._estimate_device(*args, frame0=frame0, dense=dense)
         if on_dev or n <= chunk or chunk <= 0:
             return _to_host(on_device(np.asarray(K), self._upload_frames(rgb1), self._upload_masks(mask1), np.asarray(E1),
                                       self._upload_frames(rgb2), self._upload_masks(mask2), np.asarray(E2)))
@@ -290,10 +300,11 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         Kd = torch.as_tensor(np.asarray(K)).to(dev)
         E1d, E2d = torch.as_tensor(np.asarray(E1)).to(dev), torch.as_tensor(np.asarray(E2)).to(dev)
         S, wp = self.cfg["img_size"], self._pnp_branch()
-        kw = {"dense": True} if dense else {}
+        kw = {"dense": dense} if dense else {}
+        mk = {"want_mask": True} if isinstance(dense, _Cloud) else {}
 
         def prep(a, b, d):
-            return [self._prepare_windows(d, v, Kd[a:b], S, 1024, self.prepare_seed + v, want_pts2d=wp, frame0=a) for v in (0, 1)]
+            return [self._prepare_windows(d, v, Kd[a:b], S, 1024, self.prepare_seed + v, want_pts2d=wp, frame0=a, **mk) for v in (0, 1)]
         if n <= chunk or chunk <= 0:
             ring = self._wring = WindowRing.matching(self._wring, n, srcs, dev, slots=1, grow=True)
             ring.payload_bytes = ring.table_bytes = 0
@@ -366,12 +377,13 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         dev = self.estimator.device
         Kd = torch.as_tensor(K).to(dev)
         wp = self._pnp_branch()
-        a = self._prepare(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, S, 1024, self.prepare_seed, want_pts2d=wp, frame0=frame0)
-        b = self._prepare(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=frame0)
+        mk = {"want_mask": True} if isinstance(dense, _Cloud) else {}
+        a = self._prepare(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, S, 1024, self.prepare_seed, want_pts2d=wp, frame0=frame0, **mk)
+        b = self._prepare(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=frame0, **mk)
         if self.feature_content and not dense:      # one host synchronisation per call: the keys must be on the host before the network can be enqueued
             self._content.reserve(int(Kd.shape[0]))
             return self._estimate_keyed(self._content.keys(a, b), E1, E2, Kd)
-        return self._estimate_prepared(a, b, E1, E2, Kd, **({"dense": True} if dense else {}))
+        return self._estimate_prepared(a, b, E1, E2, Kd, **({"dense": dense} if dense else {}))
 
     # ------------------------------------------------------------------ dense depth of the view-1 crops (DESIGN.md "Dense depth maps")
     def estimate_depth(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
@@ -392,8 +404,71 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         """`estimate_depth` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
         return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=True)
 
+    # ------------------------------------------------------------------ consistent two-view point cloud (DESIGN.md section 5k)
+    def _cloud_options(self, px_max, rel_max, conf_min, masked, max_points):
+        if self.prepare_mode != "device":
+            raise ValueError(f'estimate_cloud crops on the device: it needs hip_prepare: "device", got {self.prepare_mode!r}')
+        if not self.view2_heads:
+            raise ValueError("estimate_cloud checks the view-1 depth map against the view-2 map: it needs a net that runs the view-2 heads "
+                             "(cfg hip_view2_heads: True; the default for the regression tail is False)")
+        S = self.cfg["img_size"]
+        cap = 2 * S * S if max_points is None else int(max_points)
+        if cap < 0:
+            raise ValueError(f"estimate_cloud: max_points >= 0, got {max_points}")
+        return _Cloud(px_max=float(px_max), rel_max=float(rel_max), conf_min=float(conf_min), masked=bool(masked), cap=cap)
+
+    def estimate_cloud(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
+                       view2_extrinsic_batch, *, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True, max_points=None):
+        """`estimate_depth` (same arguments, frame types, upload modes and chunk pipeline) followed by the two-view geometric consistency
+        check and the packed point cloud of the pixels that pass it, as a dict of numpy arrays.  Everything `estimate_depth` returns,
+        unchanged, plus `depth2` / `conf2` [n,S,S] f32, `window2` [n,4] i32, `Kcrop2` [n,3,3] f64 (the same for the view-2 crop), `mask1` /
+        `mask2` [n,S,S] u8 (the crop-resolution masks `choose` is drawn from), `fused1` / `reproj1` / `rel1` [n,S,S] f32 and `keep1`
+        [n,S,S] u8 (`depth_consistency` of view 1 against view 2; `...2`: view 2 against view 1), `cloud` [n,cap,3] f32, `cloud_index`
+        [n,cap] i32 and `count` [n,2] i32 (`cloud_pack`: view 1's kept pixels in row-major order, then view 2's; cap = max_points, default
+        2 S S).  A pixel is kept when it comes back within `px_max` pixels at a depth within `rel_max`, with confidence >= `conf_min`
+        and, with `masked`, inside its crop mask.  A sample with valid 0 has keep 0, count [0, 0] and NaN maps and cloud rows.  Needs the
+        view-2 maps, i.e. cfg hip_view2_heads: True, and hip_prepare: "device"; the feature cache is bypassed as in `estimate_depth`."""
+        opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points)
+        return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
+                                          view2_mask_batch, view2_extrinsic_batch, dense=opts)
+
+    def estimate_cloud_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0, *, px_max=1.0, rel_max=0.01, conf_min=0.0,
+                              masked=True, max_points=None):
+        """`estimate_cloud` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
+        opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points)
+        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=opts)
+
+    def _cloud_tail(self, r, pred, a, b, E1d, E2d, ok, o: _Cloud):
+        """The dict of `estimate_depth` (r, left as it is) extended by the view-2 maps, the two checks and the packed cloud."""
+        n = E1d.shape[0]
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=E1d.device)
+        d2 = torch.where(ok.view(n, 1, 1), pred["view2_depth_map"], nan)
+        c2 = torch.where(ok.view(n, 1, 1), pred["view2_depth_conf"], nan)
+        th = dict(px_max=o["px_max"], rel_max=o["rel_max"], conf_min=o["conf_min"])
+        m1, m2 = (a["mask"], b["mask"]) if o["masked"] else (None, None)
+        v1 = depth_consistency(r["depth"], a["Kcrop"], E1d, d2, b["Kcrop"], E2d, conf_a=r["conf"], mask_a=m1, **th)
+        v2 = depth_consistency(d2, b["Kcrop"], E2d, r["depth"], a["Kcrop"], E1d, conf_a=c2, mask_a=m2, **th)
+        cloud, index, count = cloud_pack(v1["fused"], v1["keep"], a["Kcrop"], E1d, v2["fused"], v2["keep"], b["Kcrop"], E2d, max_points=o["cap"])
+        r.update(depth2=d2, conf2=c2, window2=b["window"], Kcrop2=b["Kcrop"], mask1=a["mask"], mask2=b["mask"], cloud=cloud,
+                 cloud_index=index, count=count)
+        for v, res in ((1, v1), (2, v2)):
+            for k in ("fused", "keep", "reproj", "rel"):
+                r[f"{k}{v}"] = res[k]
+        return r
+
     def _alloc_out(self, n, dev, dense):
-        """What the chunks of a pipelined call are written into: the boxes, or the tensors of `estimate_depth`."""
+        """What the chunks of a pipelined call are written into: the boxes, the tensors of `estimate_depth`, or those of `estimate_cloud`."""
+        if isinstance(dense, _Cloud):
+            S, cap = self.cfg["img_size"], dense["cap"]
+            out = self._alloc_out(n, dev, True)
+            m = lambda dt: torch.empty(n, S, S, dtype=dt, device=dev)      # noqa: E731
+            out.update(depth2=m(torch.float32), conf2=m(torch.float32), window2=torch.empty(n, 4, dtype=torch.int32, device=dev),
+                       Kcrop2=torch.empty(n, 3, 3, dtype=torch.float64, device=dev), mask1=m(torch.uint8), mask2=m(torch.uint8),
+                       cloud=torch.empty(n, cap, 3, dtype=torch.float32, device=dev),
+                       cloud_index=torch.empty(n, cap, dtype=torch.int32, device=dev), count=torch.empty(n, 2, dtype=torch.int32, device=dev))
+            for v in (1, 2):
+                out.update({f"fused{v}": m(torch.float32), f"keep{v}": m(torch.uint8), f"reproj{v}": m(torch.float32), f"rel{v}": m(torch.float32)})
+            return out
         if not dense:
             return torch.empty(n, 8, 3, dtype=torch.float64, device=dev)
         S = self.cfg["img_size"]
@@ -475,8 +550,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
         depth = torch.where(ok.view(n, 1, 1), pred["view1_depth_map"], nan)
         conf = torch.where(ok.view(n, 1, 1), pred["view1_depth_conf"], nan)
-        return {"bbox": box, "depth": depth, "conf": conf, "points": depth_to_points(depth, a["Kcrop"], E1d),      # NaN depth -> NaN points
-                "window": a["window"], "Kcrop": a["Kcrop"], "valid": ok.to(torch.int32)}
+        res = {"bbox": box, "depth": depth, "conf": conf, "points": depth_to_points(depth, a["Kcrop"], E1d),      # NaN depth -> NaN points
+               "window": a["window"], "Kcrop": a["Kcrop"], "valid": ok.to(torch.int32)}
+        return self._cloud_tail(res, pred, a, b, E1d, E2d, ok, dense) if isinstance(dense, _Cloud) else res
 
     def _bbox_tail(self, pred, choose, Kcrop, E1, pts2d=None, E2=None, K=None):
         """interface_v5.py:318-374: scale / translation from the regressed rotation (`direct_regression`, the shipped configs)

@@ -222,6 +222,25 @@ def adapose_inputs(B: int, seed: int = 0, img: int = IMG, n_pts: int = N_PTS):
 # --------------------------------------------------------------------------------------
 # PPO
 # --------------------------------------------------------------------------------------
+def sphere_depth(K_crop, E, center=(0.0, 0.0, 0.5), radius: float = 0.12, img: int = IMG):
+    """Depth maps of a sphere ray-cast into cameras: K_crop [n,3,3], E [n,4,4] (world -> camera) -> [n,img,img] float32, the camera z of
+    the first intersection of every pixel's ray, NaN off the sphere.  The scene of the two-view consistency tests."""
+    K, E = np.asarray(K_crop, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    n = K.shape[0]
+    y, x = np.meshgrid(np.arange(img, dtype=np.float64), np.arange(img, dtype=np.float64), indexing="ij")
+    out = np.full((n, img, img), np.nan, dtype=np.float32)
+    for i in range(n):
+        c = E[i, :3, :3] @ np.asarray(center, dtype=np.float64) + E[i, :3, 3]          # the centre in the camera frame
+        r = np.stack([(x - K[i, 0, 2]) / K[i, 0, 0], (y - K[i, 1, 2]) / K[i, 1, 1], np.ones_like(x)], axis=-1)      # rays with z = 1
+        a, b = (r * r).sum(-1), r @ c
+        disc = b * b - a * (c @ c - radius * radius)
+        with np.errstate(invalid="ignore"):
+            z = (b - np.sqrt(disc)) / a                                                   # ray parameter = camera z
+        hit = (disc >= 0) & (z > 0)
+        out[i][hit] = z[hit].astype(np.float32)
+    return out
+
+
 def policy_state_dict(seed: int = 0, obs=60, act=12, hid=(96, 96, 32), init_std=0.6):
     """ActorCritic state_dict in the reference's key order (`module.py:24-54`)."""
     sd = OrderedDict()
