@@ -161,6 +161,45 @@ int rgbm_cloud_pack(const float* fused1, const uint8_t* keep1, const double* Kcr
                     const uint8_t* keep2, const double* Kcrop2, const double* E2, int n, int S, int cap, float* cloud, int32_t* index,
                     int32_t* count, void* stream);
 
+/* Dense NOCS maps, and a box fitted to the two-view cloud.
+ * rgbm_adapose_forward_maps: the arguments of rgbm_adapose_forward_dense plus nocs_map [V'][224][224][3] fp32 (V' as for depth_map): the
+ *   network's per-pixel NOCS branch (gather -> instance_color -> nocs_head -> tanh, network_v5.py:432-438) evaluated at every pixel of
+ *   the feature map with the arithmetic of the point branch, so nocs_map read at choose1[b][p] is view1_nocs[b][p] bit for bit.
+ *   depth_map != NULL: rgbm_adapose_forward_dense plus the NOCS map (nocs_map may then be NULL).  depth_map == NULL (conf_map must be NULL
+ *   too): the plain rgbm_adapose_forward plus the NOCS map — the handle's sparse_dec / sparse_tail stay in force, the workspace is that of
+ *   rgbm_adapose_workspace_bytes, the ten outputs are bit for bit those of rgbm_adapose_forward.  All three NULL: an argument error.
+ *   There is no hipGraph and no feature-cache form of this call.
+ * rgbm_nocs_map: the kernel alone, with the handle's weights, on a plain fp32 feature array feat_f32 [V][HW][32] -> nocs_map [V][HW][3];
+ *   V * HW must be a multiple of 64.  A NaN feature gives NaN in its own pixel and nowhere else.
+ * rgbm_cloud_gather: rows of per-pixel maps at a packed cloud's indices.  map1 / map2 [n][S2][C] fp32 (map2 may be NULL), index [n][cap]
+ *   int32 as rgbm_cloud_pack writes it -> out [n][cap][C] fp32, out[i][r] = map{1 + index / S2}[i][index % S2].  Rows with index < 0,
+ *   index >= 2 S2, or index >= S2 while map2 == NULL hold NaN.  1 <= C <= 4, cap >= 0.
+ * rgbm_cloud_similarity: the reference's similarity RANSAC (lib/align.py:10-104) between the cloud's object-space rows nocs [n][cap][3]
+ *   and its world-frame rows cloud [n][cap][3] (both fp32, arithmetic in fp64), count [n][2] as rgbm_cloud_pack writes it.  For pose b
+ *   with m = min(cap, count[b][0] + count[b][1]), over rows 0 .. m - 1:
+ *     1. m < 5, or a NaN among the m rows of either array: invalid;
+ *     2. threshold 2 max ||s - mean s|| / 10; 128 five-point Umeyama hypotheses, sample k of hypothesis i = mix32(seed, 128 b + i, k) mod m
+ *        (the hash of rgbm_adapose_postprocess_ransac); inlier counts of every hypothesis over all m rows against scale * threshold; the
+ *        reference's sequential scan over the counts (a strictly better ratio wins, confidence break, best ratio < 0.1: no consensus);
+ *        Umeyama over the kept hypothesis's inliers;
+ *     3. the box: half = max |nocs| over the m rows per axis, size = 2 half scale, get_3d_bbox corners through [R | t] rounded to float32
+ *        (interface_v5.py:348-367); no world transform, the cloud is in the world frame already.
+ *   bbox [n][8][3] fp64, srt [n][13] fp64 (scale, R row-major, t), valid [n] int32, info [n][4] int32 = (m, the kept hypothesis or -1,
+ *   its inlier count, the hypotheses the scan examined; -1, 0, 0 behind m for an invalid pose).  Invalid, no-consensus and non-finite
+ *   poses: valid 0, the +10 default_bbox, srt[0] NaN.  A pose's rows are cut into slices of whole workgroups whose integer counts and fp64
+ *   partial sums are combined in slice order (no floating-point atomics): results are bit-identical from run to run.
+ *   scratch: rgbm_cloud_similarity_scratch_bytes(n, cap) bytes of device memory, 8-byte aligned, contents irrelevant.  cap >= 1,
+ *   n <= 65535. */
+int rgbm_adapose_forward_maps(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
+                              const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
+                              size_t workspace_bytes, const rgbm_adapose_out* out, float* depth_map, float* conf_map, float* nocs_map,
+                              void* stream);
+int rgbm_nocs_map(rgbm_adapose_t* h, const float* feat_f32, int V, int HW, float* nocs_map, void* stream);
+int rgbm_cloud_gather(const float* map1, const float* map2, const int32_t* index, int n, int S2, int C, int cap, float* out, void* stream);
+int rgbm_cloud_similarity_scratch_bytes(int n, int cap, size_t* bytes);
+int rgbm_cloud_similarity(const float* nocs, const float* cloud, const int32_t* count, int n, int cap, uint32_t seed, double* bbox, double* srt,
+                          int32_t* info, int32_t* valid, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Post-processing of one batch of network outputs into world-frame handle boxes.
  * Replaces: compute_scale_and_translation / get_3d_bbox / transform_coordinates_3d and the tail of predict()
  *   models/pose_estimator/AdaPose/lib/utils.py:40-119, models/pose_estimator/AdaPose/interface_v5.py:318-321,354-374

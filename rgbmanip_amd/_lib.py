@@ -116,6 +116,11 @@ SIGNATURES = {
                                         C.POINTER(C.c_int32)]),
     "rgbm_adapose_dense_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),
     "rgbm_adapose_forward_dense": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp, _vp, _vp]),
+    "rgbm_adapose_forward_maps": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp, _vp, _vp, _vp]),
+    "rgbm_nocs_map": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "rgbm_cloud_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "rgbm_cloud_similarity_scratch_bytes": (_i, [_i, _i, C.POINTER(_sz)]),
+    "rgbm_cloud_similarity": (_i, [_vp, _vp, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rgbm_depth_to_points": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "rgbm_depth_consistency": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _d, _f, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_cloud_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

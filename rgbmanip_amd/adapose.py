@@ -208,14 +208,18 @@ class AdaPoseNet:
         return {k: v.clone() for k, v in out.items()}      # the static outputs are overwritten by the next replay
 
     def forward(self, view1_img, view1_choose, view2_img, view2_choose, view1_proj, view2_proj, depth_values,
-                stop_after: int = 0, stream=None, dense_depth: bool = False):
+                stop_after: int = 0, stream=None, dense_depth: bool = False, dense_nocs: bool = False):
         """The reference network's call.  `dense_depth=True` (rgbm_adapose_forward_dense): the same dict plus `view1_depth_map` /
         `view1_depth_conf` and, with the view-2 heads, `view2_depth_map` / `view2_depth_conf` — [B, 224, 224] float32 each: the expected
         depth and the largest probability over the 24 planes at every pixel of the crop.  That call runs the dense cost regularisation
-        and the dense tail whatever the net's options say (and leaves them as they are), always eagerly on one stream."""
-        if dense_depth:
-            assert stop_after == 0, "dense_depth: the whole forward"
-            return self._forward_dense((view1_img, view2_img, view1_choose, view2_choose, view1_proj, view2_proj, depth_values), stream)
+        and the dense tail whatever the net's options say (and leaves them as they are), always eagerly on one stream.
+        `dense_nocs=True` (rgbm_adapose_forward_maps), alone or with `dense_depth`: plus `view1_nocs_map` (and `view2_nocs_map` with the
+        view-2 heads) [B, 224, 224, 3] float32, the NOCS branch at every pixel; the map read at `choose` is `view*_nocs` bit for bit.
+        Alone it leaves the ten outputs those of the plain forward (the net's own options, eagerly on one stream)."""
+        if dense_depth or dense_nocs:
+            assert stop_after == 0, "dense_depth / dense_nocs: the whole forward"
+            return self._forward_dense((view1_img, view2_img, view1_choose, view2_choose, view1_proj, view2_proj, depth_values), stream,
+                                       depth=bool(dense_depth), nocs=bool(dense_nocs))
         if self.graph and stop_after == 0 and stream is None and len(view1_img) <= self.graph_max_batch:
             self._last_graph = True
             return self._forward_graph((view1_img, view1_choose, view2_img, view2_choose, view1_proj, view2_proj, depth_values))
@@ -254,7 +258,7 @@ class AdaPoseNet:
         _lib.check(self.lib.rgbm_adapose_dense_workspace_bytes(self._h, B, C.byref(n)), "rgbm_adapose_dense_workspace_bytes")
         return n.value
 
-    def _forward_dense(self, args, stream):
+    def _forward_dense(self, args, stream, depth: bool = True, nocs: bool = False):
         dts = (torch.float32, torch.float32, torch.int32, torch.int32, torch.float32, torch.float32, torch.float32)
         img1, img2, ch1, ch2, P1, P2, dep = t = tuple(self._prep(a, d) for a, d in zip(args, dts))
         B = img1.shape[0]
@@ -263,19 +267,39 @@ class AdaPoseNet:
         assert P1.shape == (B, 4, 4) and P2.shape == (B, 4, 4) and dep.shape == (B, 24)
         out = self._empty_outputs(B)
         views = 2 if self.options.get("view2_heads", 1) else 1
-        maps = torch.empty(2, views * B, 224, 224, dtype=torch.float32, device=self.device)      # depth, confidence
+        maps = torch.empty(2, views * B, 224, 224, dtype=torch.float32, device=self.device) if depth else None      # depth, confidence
+        nmap = torch.empty(views * B, 224, 224, 3, dtype=torch.float32, device=self.device) if nocs else None
         o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
-        ws_ptr, ws_bytes = self._workspace_at_least(self.dense_workspace_bytes(B))       # grows on first use
+        ws_ptr, ws_bytes = self._workspace_at_least(self.dense_workspace_bytes(B) if depth else self.workspace_bytes(B))       # grows on first use
         self._poison(self._ws, stream)
         self._drop_explicit = False
-        _lib.check(self.lib.rgbm_adapose_forward_dense(self._h, B, *[_lib.ptr(x) for x in t], C.c_void_p(ws_ptr), ws_bytes, C.byref(o),
-                                                       _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.stream_ptr(stream)),
-                   "rgbm_adapose_forward_dense")
+        if nocs:
+            _lib.check(self.lib.rgbm_adapose_forward_maps(self._h, B, *[_lib.ptr(x) for x in t], C.c_void_p(ws_ptr), ws_bytes, C.byref(o),
+                                                          _lib.ptr(maps[0]) if depth else None, _lib.ptr(maps[1]) if depth else None,
+                                                          _lib.ptr(nmap), _lib.stream_ptr(stream)), "rgbm_adapose_forward_maps")
+        else:
+            _lib.check(self.lib.rgbm_adapose_forward_dense(self._h, B, *[_lib.ptr(x) for x in t], C.c_void_p(ws_ptr), ws_bytes, C.byref(o),
+                                                           _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.stream_ptr(stream)),
+                       "rgbm_adapose_forward_dense")
         self._last_split = self._last_graph = False
         self._last = t                                        # keep inputs alive until the stream has consumed them
         for v in range(views):
-            out[f"view{v + 1}_depth_map"] = maps[0, v * B:(v + 1) * B]
-            out[f"view{v + 1}_depth_conf"] = maps[1, v * B:(v + 1) * B]
+            if depth:
+                out[f"view{v + 1}_depth_map"] = maps[0, v * B:(v + 1) * B]
+                out[f"view{v + 1}_depth_conf"] = maps[1, v * B:(v + 1) * B]
+            if nocs:
+                out[f"view{v + 1}_nocs_map"] = nmap[v * B:(v + 1) * B]
+        return out
+
+    def nocs_map(self, feat, stream=None):
+        """The dense NOCS kernel alone (rgbm_nocs_map) with this net's weights: feat [V, HW, 32] (any float type; read as float32) ->
+        [V, HW, 3] float32 CUDA, V * HW a multiple of 64."""
+        f = torch.as_tensor(feat).to(device=self.device, dtype=torch.float32).contiguous()
+        if f.dim() != 3 or f.shape[2] != 32 or f.shape[0] * f.shape[1] == 0 or (f.shape[0] * f.shape[1]) % 64:
+            raise ValueError(f"nocs_map: feat [V, HW, 32] with V * HW a positive multiple of 64, got {tuple(f.shape)}")
+        out = torch.empty(f.shape[0], f.shape[1], 3, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.rgbm_nocs_map(self._h, _lib.ptr(f), int(f.shape[0]), int(f.shape[1]), _lib.ptr(out), _lib.stream_ptr(stream)),
+                   "rgbm_nocs_map")
         return out
 
     def _forward_split(self, B, args, out, stream):
@@ -590,6 +614,168 @@ def cloud_pack(fused1, keep1, Kcrop1, E1, fused2=None, keep2=None, Kcrop2=None, 
                                        _lib.ptr(E2d), n, S, cap, _lib.ptr(cloud), _lib.ptr(index), _lib.ptr(count), _lib.stream_ptr(stream)),
                    "rgbm_cloud_pack")
     return cloud, index, count
+
+
+def nocs_map(net, feat, stream=None):
+    """`AdaPoseNet.nocs_map`: the NOCS branch of `net` at every row of feat [V, HW, 32] -> [V, HW, 3] float32 CUDA."""
+    return net.nocs_map(feat, stream=stream)
+
+
+def cloud_gather(map1, map2, index, stream=None):
+    """Rows of per-pixel maps at a packed cloud's indices (rgbm_cloud_gather): map1 / map2 [n, S2, C] or [n, S, S, C] float32 (map2 may
+    be None), index [n, cap] int32 as `cloud_pack` returns it -> [n, cap, C] float32 CUDA, out[i, r] = map{1 + index // S2}[i, index % S2].
+    Rows with index < 0, index >= 2 S2, or a view-2 index without map2 hold NaN.  1 <= C <= 4."""
+    lib = _lib.load()
+    m1 = torch.as_tensor(map1)
+    dev = m1.device if m1.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    m1 = m1.to(device=dev, dtype=torch.float32).contiguous()
+    if m1.dim() not in (3, 4):
+        raise ValueError(f"cloud_gather: map1 [n, S2, C] or [n, S, S, C], got {tuple(m1.shape)}")
+    n, Cc = int(m1.shape[0]), int(m1.shape[-1])
+    S2 = int(m1.shape[1]) if m1.dim() == 3 else int(m1.shape[1] * m1.shape[2])
+    if not 1 <= Cc <= 4 or S2 < 1:
+        raise ValueError(f"cloud_gather: 1 <= C <= 4 and S2 >= 1, got C = {Cc}, S2 = {S2}")
+    m2 = None
+    if map2 is not None:
+        m2 = torch.as_tensor(map2).to(device=dev, dtype=torch.float32).contiguous()
+        if m2.shape != m1.shape:
+            raise ValueError(f"cloud_gather: map2 has map1's shape, got {tuple(m2.shape)} and {tuple(m1.shape)}")
+    ix = torch.as_tensor(index).to(device=dev, dtype=torch.int32).contiguous()
+    if ix.dim() != 2 or ix.shape[0] != n:
+        raise ValueError(f"cloud_gather: index [n, cap], got {tuple(ix.shape)} for n = {n}")
+    cap = int(ix.shape[1])
+    out = torch.empty(n, cap, Cc, dtype=torch.float32, device=dev)
+    if n and cap:
+        _lib.check(lib.rgbm_cloud_gather(_lib.ptr(m1), _lib.ptr(m2), _lib.ptr(ix), n, S2, Cc, cap, _lib.ptr(out), _lib.stream_ptr(stream)),
+                   "rgbm_cloud_gather")
+    return out
+
+
+_DEFAULT_BBOX = np.asarray([[0, 0, 0], [0, 0, 1], [0, 1, 0], [0, 1, 1], [1, 0, 0], [1, 0, 1], [1, 1, 0], [1, 1, 1]], dtype=np.float64) + 10.0
+_BBOX_SIGNS = np.asarray([[1, 1, 1], [1, 1, -1], [-1, 1, 1], [-1, 1, -1], [1, -1, 1], [1, -1, -1], [-1, -1, 1], [-1, -1, -1]], dtype=np.float64)
+
+
+def _fit_shapes(nocs, cloud, count):
+    if nocs.ndim != 3 or nocs.shape[2] != 3 or tuple(cloud.shape) != tuple(nocs.shape):
+        raise ValueError(f"cloud_similarity: nocs and cloud [n, cap, 3], got {tuple(nocs.shape)} and {tuple(cloud.shape)}")
+    if tuple(count.shape) != (nocs.shape[0], 2):
+        raise ValueError(f"cloud_similarity: count [n, 2], got {tuple(count.shape)}")
+    return int(nocs.shape[0]), int(nocs.shape[1])
+
+
+def cloud_similarity(nocs, cloud, count, seed: int = 0, stream=None):
+    """The reference's similarity RANSAC (lib/align.py:10-104) between a packed cloud's object-space rows nocs [n, cap, 3] and its
+    world-frame rows cloud [n, cap, 3] (rgbm_cloud_similarity): over the first m = min(cap, count.sum(1)) rows of
+    pose b, 128 five-point hypotheses drawn by the seeded hash (sample k of hypothesis i = mix32(seed, 128 b + i, k) % m), the reference's
+    scan and the final Umeyama fit over the kept hypothesis's inliers, then the box of `bbox_from_srt` without a world transform.  Returns
+    CUDA tensors (bbox [n,8,3] f64, srt [n,13] f64 = scale, R, t, info [n,4] i32 = m, kept hypothesis or -1, its inliers, hypotheses
+    examined, valid [n] i32).  m < 5, a NaN row, no consensus: valid 0, the +10 cube, srt[:, 0] NaN.  Two calls give the same bytes."""
+    lib = _lib.load()
+    nc = torch.as_tensor(nocs)
+    dev = nc.device if nc.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    nc = nc.to(device=dev, dtype=torch.float32).contiguous()
+    cl = torch.as_tensor(cloud).to(device=dev, dtype=torch.float32).contiguous()
+    ct = torch.as_tensor(count).to(device=dev, dtype=torch.int32).contiguous()
+    n, cap = _fit_shapes(nc, cl, ct)
+    bbox = torch.from_numpy(_DEFAULT_BBOX).to(dev).expand(n, 8, 3).contiguous()
+    srt = torch.zeros(n, 13, dtype=torch.float64, device=dev)
+    info = torch.zeros(n, 4, dtype=torch.int32, device=dev)
+    valid = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n and cap:
+        nb = C.c_size_t()
+        _lib.check(lib.rgbm_cloud_similarity_scratch_bytes(n, cap, C.byref(nb)), "rgbm_cloud_similarity_scratch_bytes")
+        scratch = torch.empty(max(nb.value // 8, 1), dtype=torch.int64, device=dev)
+        if stream is not None:
+            scratch.record_stream(stream)
+        _lib.check(lib.rgbm_cloud_similarity(_lib.ptr(nc), _lib.ptr(cl), _lib.ptr(ct), n, cap, int(seed) & 0xFFFFFFFF, _lib.ptr(bbox), _lib.ptr(srt),
+                                             _lib.ptr(info), _lib.ptr(valid), _lib.ptr(scratch), nb.value, _lib.stream_ptr(stream)),
+                   "rgbm_cloud_similarity")
+    elif n:                                                   # no rows at all: every pose is invalid
+        srt[:, 0] = float("nan")
+        srt[:, 1] = srt[:, 5] = srt[:, 9] = 1.0
+        info[:, 1] = -1
+    return bbox, srt, info, valid
+
+
+def _mix32(seed: int, frame: int, idx: int) -> int:
+    M = 0xFFFFFFFF
+    h = (seed ^ ((frame * 0x9E3779B9) & M) ^ ((idx * 0x85EBCA6B) & M)) & M
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & M
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & M
+    h ^= h >> 16
+    return h
+
+
+def _umeyama_ref(src, tgt):
+    """lib/align.py:10-41 on rows src / tgt [k, 3] float64 -> (scale, R, t)."""
+    ms, mt = src.mean(axis=0), tgt.mean(axis=0)
+    cs, ct = src - ms, tgt - mt
+    cov = ct.T @ cs / src.shape[0]
+    if np.isnan(cov).any():
+        raise RuntimeError("NaN covariance")
+    U, D, Vh = np.linalg.svd(cov, full_matrices=True)
+    if np.linalg.det(U) * np.linalg.det(Vh) < 0.0:
+        D[-1] = -D[-1]
+        U[:, -1] = -U[:, -1]
+    R = U @ Vh
+    with np.errstate(all="ignore"):
+        scale = 1 / np.var(src, axis=0).sum() * np.sum(D)
+    return scale, R, mt - ms.dot(scale * R.T)
+
+
+def cloud_similarity_ref(nocs, cloud, count, seed: int = 0):
+    """float64 numpy twin of `cloud_similarity` (tests, documentation): the semantics of include/rgbm.h restated per pose.  Returns numpy
+    arrays (bbox [n,8,3] f64, srt [n,13] f64, info [n,4] i32, valid [n] i32)."""
+    nocs, cloud, count = np.asarray(nocs, dtype=np.float32), np.asarray(cloud, dtype=np.float32), np.asarray(count)
+    n, cap = _fit_shapes(nocs, cloud, count)
+    bbox = np.tile(_DEFAULT_BBOX, (n, 1, 1))
+    srt = np.zeros((n, 13))
+    srt[:, 0], srt[:, 1], srt[:, 5], srt[:, 9] = np.nan, 1.0, 1.0, 1.0
+    info, valid = np.zeros((n, 4), dtype=np.int32), np.zeros(n, dtype=np.int32)
+    seed = int(seed) & 0xFFFFFFFF
+    for b in range(n):
+        m = int(min(cap, max(0, int(count[b, 0]) + int(count[b, 1]))))
+        info[b] = (m, -1, 0, 0)
+        s, t = nocs[b, :m].astype(np.float64), cloud[b, :m].astype(np.float64)
+        if m < 5 or np.isnan(s).any() or np.isnan(t).any():
+            continue
+        thr = 2 * np.sqrt(((s - s.mean(axis=0)) ** 2).sum(axis=1)).max() / 10.0
+        best, best_h, best_inl, examined, failed = 0.0, -1, None, 0, False
+        for i in range(128):
+            idx = [_mix32(seed, 128 * b + i, k) % m for k in range(5)]
+            try:
+                sc, R, tr = _umeyama_ref(s[idx], t[idx])
+            except RuntimeError:
+                failed = True
+                break
+            examined = i + 1
+            with np.errstate(all="ignore"):
+                inl = np.sqrt(((t - (s @ (sc * R).T + tr)) ** 2).sum(axis=1)) < sc * thr
+            ratio = int(inl.sum()) / m
+            if ratio > best:
+                best, best_h, best_inl = ratio, i, inl
+            b5 = (best * best) * (best * best) * best
+            if (1 - (1 - b5) ** i) > 0.99:
+                break
+        if failed:
+            continue
+        if best < 0.1:
+            info[b] = (m, -1, 0, examined)
+            continue
+        info[b] = (m, best_h, int(best_inl.sum()), examined)
+        try:
+            sc, R, tr = _umeyama_ref(s[best_inl], t[best_inl])
+        except RuntimeError:
+            continue
+        srt[b, 1:10], srt[b, 10:13] = R.reshape(9), tr
+        with np.errstate(all="ignore"):
+            size = 2 * np.abs(s).max(axis=0) * sc
+            corners = (_BBOX_SIGNS * (size[None, :] / 2)) @ R.astype(np.float32).astype(np.float64).T + tr.astype(np.float32).astype(np.float64)
+        if np.isfinite(corners).all():
+            bbox[b], srt[b, 0], valid[b] = corners, sc, 1
+    return bbox, srt, info, valid
 
 
 def postprocess_regressed(view1_nocs, view1_r, view1_t, view1_s, E1, stream=None):

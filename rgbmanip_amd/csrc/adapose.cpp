@@ -694,6 +694,25 @@ int AdaPose::forward_dense(int B, const float* img1, const float* img2, const in
   return rc;
 }
 
+int AdaPose::forward_maps(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
+                          const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
+                          float* depth_map, float* conf_map, float* nocs_map, hipStream_t s) {
+  RGBM_REQUIRE(depth_map != nullptr || nocs_map != nullptr, "forward_maps: depth_map and nocs_map are both null");
+  RGBM_REQUIRE(depth_map != nullptr || conf_map == nullptr, "forward_maps: conf_map without depth_map");
+  RGBM_REQUIRE(nocs_map == nullptr || pmlp_table != nullptr, "forward_maps: no point MLP table");
+  dense_nocs_map = nocs_map;
+  const int rc = depth_map != nullptr
+      ? forward_dense(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_size, out, depth_map, conf_map, s)
+      : forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_size, out, s, 0);
+  dense_nocs_map = nullptr;
+  return rc;
+}
+
+int AdaPose::nocs_map_of(const float* feat_f32, long long pixels, float* nocs_map, hipStream_t s) const {
+  RGBM_REQUIRE(pmlp_table != nullptr, "nocs_map: no point MLP table");
+  return launch_dense_nocs(F32, pmlp_table, feat_f32, nocs_map, pixels, s);
+}
+
 // Everything behind the PSPNet: reads the feature map(s) in bf.feat / bf.featf, bf.homog, bf.choose (forward() and forward_cached() fill them)
 int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs& out, hipStream_t s, int stop_after) const {
   const int V = 2 * B, P = n_pts, S = img, D = n_depth;
@@ -719,6 +738,10 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
     if (int rc = npm[0].run(bf.nocs4, bf.N32, Vh, 1, 1, P, 32, nullptr, 0, nullptr, 0, s)) return rc;
     if (int rc = npm[1].run(bf.N32, bf.PF96 + 32, Vh, 1, 1, P, 96, nullptr, 0, nullptr, 0, s)) return rc;
   }
+
+  // forward_maps(): the same branch's layers 0..3 on every pixel of the Vh feature maps (the dense NOCS map)
+  if (dense_nocs_map != nullptr)
+    if (int rc = launch_dense_nocs(fdt, pmlp_table, featg, dense_nocs_map, (long long)Vh * S * S, s)) return rc;
 
   // ---- plane-sweep cost volume -> probability at the sampled pixels -> depth ----
   if (int rc = cost_volume(bf, V, B, depths, s)) return rc;

@@ -122,6 +122,15 @@ struct AdaPose {
                     float* depth_map, float* conf_map, hipStream_t s);
   float* dense_depth_map = nullptr;      // set for the duration of forward_dense: cost_volume() runs the dense head behind every u11
   float* dense_conf_map = nullptr;
+  // forward_maps(): forward_dense() (depth_map != null) or the plain forward() (depth_map == null: the handle's sparse_dec / sparse_tail and
+  // the workspace_bytes(B) workspace; the ten outputs are forward()'s bit for bit), plus the dense NOCS map nocs_map [Vh][img][img][3] fp32
+  // when it is not null: layers 0..3 of the point MLP table on every pixel (head_kernels.hip: dense_nocs_kernel), launched behind the
+  // per-point branch in heads(), so that nocs_map read at choose is the point NOCS bit for bit.
+  int forward_maps(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
+                   const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
+                   float* depth_map, float* conf_map, float* nocs_map, hipStream_t s);
+  int nocs_map_of(const float* feat_f32, long long pixels, float* nocs_map, hipStream_t s) const;      // the kernel alone on an fp32 feature array
+  float* dense_nocs_map = nullptr;       // set for the duration of forward_maps
   // Feature cache: the forward split at the PSPNet's output.  features() runs the PSPNet on V >= 1 views of one image array
   // [V][3][img][img] and writes view v's record (feature_bytes() long) to pool + slots[v] * feature_bytes(); forward_cached() is
   // forward() with the PSPNet replaced by reading records slot1[b] / slot2[b].  Both refuse a net with Dropout2d on.  A slot outside

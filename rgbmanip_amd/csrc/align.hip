@@ -14,6 +14,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "bbox_emit.h"
+#include "align_math.h"
 
 #pragma clang fp contract(off)
 
@@ -24,84 +25,6 @@ namespace {
 constexpr int AL_THREADS = 256;
 constexpr int AL_MAXP = 1024;
 constexpr int AL_ITERS = 128;
-
-__device__ __forceinline__ unsigned al_mix32(unsigned seed, unsigned frame, unsigned idx) {      // = mix32 of prepare.hip
-  unsigned h = seed ^ (frame * 0x9E3779B9u) ^ (idx * 0x85EBCA6Bu);
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return h;
-}
-
-__device__ inline double det3(const double* m) {
-  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-}
-
-// A (row-major 3x3) = U diag(S) V^T, S descending, by one-sided Jacobi on the columns of A.
-__device__ void svd3(const double* A, double* U, double* S, double* V) {
-  double W[9], Vm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  for (int i = 0; i < 9; ++i) W[i] = A[i];
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double alpha = 0, beta = 0, gamma = 0;
-        for (int r = 0; r < 3; ++r) { alpha += W[r * 3 + p] * W[r * 3 + p]; beta += W[r * 3 + q] * W[r * 3 + q]; gamma += W[r * 3 + p] * W[r * 3 + q]; }
-        if (gamma == 0.0 || fabs(gamma) <= 1e-300) continue;
-        off = fmax(off, fabs(gamma) / sqrt(alpha * beta));
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
-        for (int r = 0; r < 3; ++r) {
-          const double wp = W[r * 3 + p], wq = W[r * 3 + q];
-          W[r * 3 + p] = c * wp - s * wq; W[r * 3 + q] = s * wp + c * wq;
-          const double vp = Vm[r * 3 + p], vq = Vm[r * 3 + q];
-          Vm[r * 3 + p] = c * vp - s * vq; Vm[r * 3 + q] = s * vp + c * vq;
-        }
-      }
-    if (off < 1e-15) break;
-  }
-  double sv[3];
-  for (int j = 0; j < 3; ++j) sv[j] = sqrt(W[j] * W[j] + W[3 + j] * W[3 + j] + W[6 + j] * W[6 + j]);
-  int ord[3] = {0, 1, 2};
-  for (int a = 0; a < 2; ++a)
-    for (int b = a + 1; b < 3; ++b)
-      if (sv[ord[b]] > sv[ord[a]]) { const int tmp = ord[a]; ord[a] = ord[b]; ord[b] = tmp; }
-  const double tiny = 1e-14 * fmax(sv[ord[0]], 1e-300);
-  for (int j = 0; j < 3; ++j) {
-    const int o = ord[j];
-    S[j] = sv[o];
-    for (int r = 0; r < 3; ++r) { V[r * 3 + j] = Vm[r * 3 + o]; U[r * 3 + j] = sv[o] > tiny ? W[r * 3 + o] / sv[o] : 0.0; }
-  }
-  // columns of U that belong to (numerically) zero singular values: complete to an orthonormal basis
-  if (!(S[0] > tiny)) { U[0] = 1; U[3] = 0; U[6] = 0; }
-  if (!(S[1] > tiny)) {
-    const double ax = fabs(U[0]), ay = fabs(U[3]), az = fabs(U[6]);
-    double e[3] = {0, 0, 0};
-    e[(ax <= ay && ax <= az) ? 0 : (ay <= az ? 1 : 2)] = 1.0;
-    const double d = e[0] * U[0] + e[1] * U[3] + e[2] * U[6];
-    double v[3] = {e[0] - d * U[0], e[1] - d * U[3], e[2] - d * U[6]};
-    const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    U[1] = v[0] / n; U[4] = v[1] / n; U[7] = v[2] / n;
-  }
-  if (!(S[2] > tiny)) {
-    U[2] = U[3] * U[7] - U[6] * U[4]; U[5] = U[6] * U[1] - U[0] * U[7]; U[8] = U[0] * U[4] - U[3] * U[1];
-  }
-}
-
-// Umeyama from sufficient statistics: n, centroids ms / mt, Cov = sum (t - mt)(s - ms)^T / n, varP = sum_axis var(source).
-// -> scale, R (row-major), t.  Returns false for a NaN covariance.
-__device__ bool umeyama_from_stats(const double* cov, const double* ms, const double* mt, double varP, double& scale, double* R, double* t) {
-  for (int i = 0; i < 9; ++i) if (cov[i] != cov[i]) return false;
-  double U[9], S[3], V[9];
-  svd3(cov, U, S, V);
-  double Vh[9];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Vh[i * 3 + j] = V[j * 3 + i];
-  if (det3(U) * det3(Vh) < 0.0) { S[2] = -S[2]; U[2] = -U[2]; U[5] = -U[5]; U[8] = -U[8]; }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R[i * 3 + j] = U[i * 3] * Vh[j] + U[i * 3 + 1] * Vh[3 + j] + U[i * 3 + 2] * Vh[6 + j];
-  scale = 1 / varP * ((S[0] + S[1]) + S[2]);
-  for (int j = 0; j < 3; ++j) t[j] = mt[j] - ((ms[0] * (scale * R[j * 3]) + ms[1] * (scale * R[j * 3 + 1])) + ms[2] * (scale * R[j * 3 + 2]));
-  return true;
-}
 
 __device__ double al_block_sum(double v, double* red) {
   const int t = threadIdx.x;

@@ -203,6 +203,40 @@ int rgbm_adapose_forward_dense(rgbm_adapose_t* h, int B, const float* img1, cons
                               conf_map, (hipStream_t)stream);
 }
 
+int rgbm_adapose_forward_maps(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
+                              const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
+                              size_t workspace_bytes, const rgbm_adapose_out* out, float* depth_map, float* conf_map, float* nocs_map,
+                              void* stream) {
+  RGBM_REQUIRE(depth_map != nullptr || nocs_map != nullptr, "forward_maps: depth_map, conf_map and nocs_map are all NULL (or conf_map alone is given)");
+  RGBM_REQUIRE(depth_map != nullptr || conf_map == nullptr, "forward_maps: conf_map needs depth_map");
+  RGBM_REQUIRE(h && img1 && img2 && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward_maps arguments");
+  if (h->net.drop_p > 0.f && B > 0)
+    if (int rc = ensure_dropout_capacity(h, B)) return rc;
+  return h->net.forward_maps(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), depth_map, conf_map,
+                             nocs_map, (hipStream_t)stream);
+}
+
+int rgbm_nocs_map(rgbm_adapose_t* h, const float* feat_f32, int V, int HW, float* nocs_map, void* stream) {
+  RGBM_REQUIRE(h && feat_f32 && nocs_map && V > 0 && HW > 0, "nocs_map arguments");
+  RGBM_REQUIRE(((long long)V * HW) % 64 == 0, "nocs_map: V * HW must be a multiple of 64");
+  return h->net.nocs_map_of(feat_f32, (long long)V * HW, nocs_map, (hipStream_t)stream);
+}
+
+int rgbm_cloud_gather(const float* map1, const float* map2, const int32_t* index, int n, int S2, int C, int cap, float* out, void* stream) {
+  return rgbm::launch_cloud_gather(map1, map2, index, n, S2, C, cap, out, (hipStream_t)stream);
+}
+
+int rgbm_cloud_similarity_scratch_bytes(int n, int cap, size_t* bytes) {
+  RGBM_REQUIRE(bytes && n >= 0 && cap >= 1, "cloud_similarity_scratch_bytes arguments");
+  *bytes = rgbm::cloud_similarity_scratch_bytes(n, cap);
+  return 0;
+}
+
+int rgbm_cloud_similarity(const float* nocs, const float* cloud, const int32_t* count, int n, int cap, uint32_t seed, double* bbox, double* srt,
+                          int32_t* info, int32_t* valid, void* scratch, size_t scratch_bytes, void* stream) {
+  return rgbm::launch_cloud_similarity(nocs, cloud, count, n, cap, seed, bbox, srt, info, valid, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 int rgbm_depth_to_points(const float* depth_map, const double* Kcrop, const double* E, int n, int S, float* points, void* stream) {
   return rgbm::launch_depth_to_points(depth_map, Kcrop, E, n, S, points, (hipStream_t)stream);
 }

@@ -70,7 +70,7 @@ constexpr int ACT_A = 128 * 16, ACT_B = 64 * 16;          // floats of a wave's 
 constexpr size_t LDS_BYTES = (size_t)(W_FLOATS + B_FLOATS + 4 * (ACT_A + ACT_B)) * sizeof(float);
 }  // namespace pmlp
 
-template <int L>
+template <int L, bool G4 = true>      // G4 = false (dense_nocs_kernel): layer 3 keeps its tile in LDS only, the caller stores it
 __device__ __forceinline__ void pmlp_layer(const float* __restrict__ wl, const float* __restrict__ bl, const float* __restrict__ xin,
                                            float* __restrict__ xout, int lane, float* __restrict__ gout4, float* __restrict__ gout64, int ldg) {
   using namespace pmlp;
@@ -106,7 +106,7 @@ __device__ __forceinline__ void pmlp_layer(const float* __restrict__ wl, const f
         const float r = acc[g][i] + bv[i];
         v[i] = AC == ACT_RELU ? (r < 0.f ? 0.f : r) : AC == ACT_TANH ? tanhf(r) : r;      // NaN propagates like torch
       }
-      if (L == 3) {
+      if (L == 3 && G4) {
         if (lane < 16) *reinterpret_cast<float4*>(gout4 + (long long)lane * 4) = make_float4(v[0], v[1], v[2], v[3]);      // nocs4: channels 0..3 of the tile
       }
       if (L == NL - 1) {
@@ -197,6 +197,79 @@ int launch_point_mlp(int feat_dtype, const PointMlpDesc& d, hipStream_t s) {
     hipLaunchKernelGGL(point_mlp_kernel<bx3_t>, dim3(grid), dim3(256), pmlp::LDS_BYTES, s, d);
   else
     hipLaunchKernelGGL(point_mlp_kernel<float>, dim3(grid), dim3(256), pmlp::LDS_BYTES, s, d);
+  RGBM_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------- the NOCS branch on every pixel (dense NOCS map)
+// The branch is per pixel (network_v5.py:432-438: gather -> instance_color -> nocs_head -> tanh), so the map over all S x S pixels is
+// layers 0..3 of the point kernel without the gather: same table, same pmlp_layer chains (fp32 MFMA sums over ascending K, bias behind
+// them), hence map[choose[p]] == nocs[p] bit for bit.  A wave carries 16 CONSECUTIVE pixels: its input is one contiguous 1 KB (16-bit) or
+// 2 KB (fp32 / split-pair copy) run read as 16-byte chunks, all of a lane's loads in flight before the first LDS write; its 16 x 3 output
+// floats are 192 contiguous bytes, staged through the activation buffer and stored as 48 consecutive dwords.  LDS: layers 0..3 of the
+// table (78 KB) + their biases + the four waves' buffers = 125 KB: one workgroup per CU, which walks 64-pixel tiles.
+namespace pmlp {
+constexpr int DN_W = w_off(4), DN_B = b_off(4);
+constexpr size_t DN_LDS_BYTES = (size_t)(DN_W + DN_B + 4 * (ACT_A + ACT_B)) * sizeof(float);
+}  // namespace pmlp
+
+template <typename TF>
+__global__ __launch_bounds__(256) void dense_nocs_kernel(const float* __restrict__ table, const TF* __restrict__ feat, float* __restrict__ out,
+                                                         long long N) {
+  using namespace pmlp;
+  extern __shared__ __attribute__((aligned(16))) float dn_lds[];
+  float* wl = dn_lds;
+  float* bl = wl + DN_W;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* xa = bl + DN_B + wave * (ACT_A + ACT_B);
+  float* xb = xa + ACT_A;
+  for (int i = tid; i < DN_W / 4; i += 256) reinterpret_cast<float4*>(wl)[i] = reinterpret_cast<const float4*>(table)[i];
+  for (int i = tid; i < DN_B / 4; i += 256) reinterpret_cast<float4*>(bl)[i] = reinterpret_cast<const float4*>(table + W_FLOATS)[i];
+  __syncthreads();
+  constexpr int EPC = Elem<TF>::kPerChunk;            // elements of a 16-byte chunk: 4 (fp32) or 8 (16-bit storage)
+  constexpr int NCH = 16 * 32 / EPC / 64;             // chunks per lane: 2 or 1
+  const long long ntile = N / 64;
+  for (long long tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const long long p0 = tile * 64 + wave * 16;       // this wave's 16 pixels
+    const uint4* src = reinterpret_cast<const uint4*>(feat + p0 * 32);
+    uint4 c[NCH];
+#pragma unroll
+    for (int r = 0; r < NCH; ++r) c[r] = src[lane + 64 * r];
+#pragma unroll
+    for (int r = 0; r < NCH; ++r) {
+      const int e0 = (lane + 64 * r) * EPC, pt = e0 >> 5, ch0 = e0 & 31;
+      float x[EPC];
+      unpack_chunk(c[r], x, TF());
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) xa[(ch0 + e) * 16 + pt] = x[e];
+    }
+    pmlp_layer<0>(wl, bl, xa, xb, lane, nullptr, nullptr, 0);
+    pmlp_layer<1>(wl, bl, xb, xa, lane, nullptr, nullptr, 0);
+    pmlp_layer<2>(wl, bl, xa, xb, lane, nullptr, nullptr, 0);
+    pmlp_layer<3, false>(wl, bl, xb, xa, lane, nullptr, nullptr, 0);      // xa[c * 16 + pixel], c = 0..2 real
+    if (lane < 48) out[p0 * 3 + lane] = xa[(lane % 3) * 16 + lane / 3];
+  }
+}
+
+int launch_dense_nocs(int feat_dtype, const float* table, const void* feat, float* out, long long N, hipStream_t s) {
+  RGBM_REQUIRE(table && feat && out && N > 0 && N % 64 == 0, "dense NOCS map: V * H * W must be a multiple of 64");
+  RGBM_REQUIRE(feat_dtype == BF16 || feat_dtype == F16 || feat_dtype == F32, "dense NOCS map: feature storage bf16, f16 or fp32");
+  static_assert(pmlp::DN_W % 4 == 0 && pmlp::DN_B % 4 == 0 && pmlp::W_FLOATS % 4 == 0, "the table is copied in 16-byte pieces");
+  static_assert(pmlp::DN_LDS_BYTES <= 160 * 1024, "dense NOCS map: weights + four waves' activations must fit the LDS");
+  int n_cu = 0;
+  if (int rc = persistent_grid_cus(&n_cu)) return rc;
+  const long long ntile = N / 64;
+  const unsigned grid = (unsigned)(ntile < n_cu ? ntile : n_cu);
+  const void* fn = feat_dtype == BF16 ? reinterpret_cast<const void*>(dense_nocs_kernel<unsigned short>)
+                   : feat_dtype == F16 ? reinterpret_cast<const void*>(dense_nocs_kernel<f16_t>)
+                                       : reinterpret_cast<const void*>(dense_nocs_kernel<float>);
+  if (int rc = ensure_dynamic_lds(fn, (int)pmlp::DN_LDS_BYTES)) return rc;
+  if (feat_dtype == BF16)
+    hipLaunchKernelGGL(dense_nocs_kernel<unsigned short>, dim3(grid), dim3(256), pmlp::DN_LDS_BYTES, s, table, (const unsigned short*)feat, out, N);
+  else if (feat_dtype == F16)
+    hipLaunchKernelGGL(dense_nocs_kernel<f16_t>, dim3(grid), dim3(256), pmlp::DN_LDS_BYTES, s, table, (const f16_t*)feat, out, N);
+  else
+    hipLaunchKernelGGL(dense_nocs_kernel<float>, dim3(grid), dim3(256), pmlp::DN_LDS_BYTES, s, table, (const float*)feat, out, N);
   RGBM_CHECK_HIP(hipGetLastError());
   return 0;
 }

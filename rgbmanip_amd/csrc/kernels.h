@@ -105,6 +105,8 @@ struct PointMlpDesc {
 int point_mlp_table_floats();
 void point_mlp_pack(const float* const w[6], const float* const b[6], float* table);      // host; w[l]: [Cout][Cin] row-major fp32 of instance_color.0, nocs_head.0/2/4, nocs_pts_mlp.0/2
 int launch_point_mlp(int feat_dtype, const PointMlpDesc& d, hipStream_t s);
+// the same table's layers 0..3 on every pixel: feat [N][32] (bf16 / f16 / fp32) -> out [N][3] fp32, N % 64 == 0
+int launch_dense_nocs(int feat_dtype, const float* table, const void* feat, float* out, long long N, hipStream_t s);
 int launch_ortho6d(const float* r6, float* R, int V, hipStream_t s);
 // consumers that finish a mean over points themselves (one launch less per mean): launch_mean_points_partial writes the slices' sums
 int launch_mean_points_partial(int dtype, const void* in, float* scratch, int V, int P, int C, hipStream_t s);
@@ -220,6 +222,12 @@ int launch_quantize_frames(const float* src, unsigned char* dst, size_t n, hipSt
 
 int launch_umeyama_ransac(const float* nocs, const float* depth, const int* choose, const double* Kc, const double* E1,
                           double* bbox, double* srt, int* valid, int B, int P, int img, unsigned seed, hipStream_t s);
+
+// cloud_fit.hip — per-pixel map look-ups of the packed cloud's rows, and the similarity RANSAC over them (include/rgbm.h)
+int launch_cloud_gather(const float* map1, const float* map2, const int* index, int n, int S2, int C, int cap, float* out, hipStream_t s);
+size_t cloud_similarity_scratch_bytes(int n, int cap);
+int launch_cloud_similarity(const float* nocs, const float* cloud, const int* count, int n, int cap, unsigned seed, double* bbox, double* srt,
+                            int* info, int* valid, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 int launch_projection(const double* Kc, const double* E, float* P, int n, hipStream_t s);      // prepare.hip
 // pnp.hip — the use_depth: False tail of predict (NOCS matches -> triangulation -> scale -> EPnP-RANSAC -> VVS -> world bbox)

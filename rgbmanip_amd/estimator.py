@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, host_prepare
-from .adapose import (AdaPoseNet, cloud_pack, depth_consistency, depth_to_points, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
+from .adapose import (AdaPoseNet, cloud_gather, cloud_pack, cloud_similarity, depth_consistency, depth_to_points, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
                       prepare_inputs_windows)
 from .feature_cache import CachedViews, ContentFeatureCache, SlotFeatureCache
 from .host_prepare import _resize_linear, _resize_nearest, get_bbox      # noqa: F401  (part of this module's surface)
@@ -261,8 +261,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             def on_device(*args, frame0=0):
                 return self._estimate_device(*args, frame0=frame0, dense=dense)
         if on_dev or n <= chunk or chunk <= 0:
-            return _to_host(on_device(np.asarray(K), self._upload_frames(rgb1), self._upload_masks(mask1), np.asarray(E1),
-                                      self._upload_frames(rgb2), self._upload_masks(mask2), np.asarray(E2)))
+            return _to_host(self._cloud_fit(on_device(np.asarray(K), self._upload_frames(rgb1), self._upload_masks(mask1), np.asarray(E1),
+                                                      self._upload_frames(rgb2), self._upload_masks(mask2), np.asarray(E2)), dense))
         dev = self.estimator.device
         srcs = [host_array(x) for x in (rgb1, rgb2, mask1, mask2)]
         pipe = self._pipe = ChunkPipeline.matching(self._pipe, chunk, srcs, dev)
@@ -286,7 +286,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             def network(a, b, d):
                 _put(out, a, b, on_device(Kd[a:b], self._upload_frames(d[0]), d[2], E1d[a:b], self._upload_frames(d[1]), d[3], E2d[a:b], frame0=a))
             pipe.run(srcs, n, network)
-        res = _to_host(out)
+        res = _to_host(self._cloud_fit(out, dense))
         pipe.trace.report(self.upload_bytes_last_call)
         return res
 
@@ -316,7 +316,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                 out = self._estimate_keyed(self._content.keys(pa, pb), E1d, E2d, Kd)
             else:
                 out = self._estimate_prepared(pa, pb, E1d, E2d, Kd, **kw)
-            res = _to_host(out)
+            res = _to_host(self._cloud_fit(out, dense))
             self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
             return res
         pipe = self._pipe = ChunkPipeline.matching(self._pipe, chunk, srcs, dev, windows=True)
@@ -338,7 +338,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                 pa, pb = prep(a, b, d)
                 _put(out, a, b, self._estimate_prepared(pa, pb, E1d[a:b], E2d[a:b], Kd[a:b], **kw))
             pipe.run(srcs, n, network)
-        res = _to_host(out)
+        res = _to_host(self._cloud_fit(out, dense))
         self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
         pipe.trace.report(self.upload_bytes_last_call)
         return res
@@ -405,7 +405,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=True)
 
     # ------------------------------------------------------------------ consistent two-view point cloud
-    def _cloud_options(self, px_max, rel_max, conf_min, masked, max_points):
+    def _cloud_options(self, px_max, rel_max, conf_min, masked, max_points, **fit):
         if self.prepare_mode != "device":
             raise ValueError(f'estimate_cloud crops on the device: it needs hip_prepare: "device", got {self.prepare_mode!r}')
         if not self.view2_heads:
@@ -415,7 +415,11 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         cap = 2 * S * S if max_points is None else int(max_points)
         if cap < 0:
             raise ValueError(f"estimate_cloud: max_points >= 0, got {max_points}")
-        return _Cloud(px_max=float(px_max), rel_max=float(rel_max), conf_min=float(conf_min), masked=bool(masked), cap=cap)
+        o = _Cloud(px_max=float(px_max), rel_max=float(rel_max), conf_min=float(conf_min), masked=bool(masked), cap=cap)
+        if fit:                                               # estimate_cloud_pose: the seed of the fit, an int from here on
+            seed = fit["fit_seed"]
+            o["fit_seed"] = int(self.cfg.get("hip_ransac_seed", 0) if seed is None else seed)
+        return o
 
     def estimate_cloud(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
                        view2_extrinsic_batch, *, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True, max_points=None):
@@ -438,6 +442,38 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points)
         return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=opts)
 
+    # ------------------------------------------------------------------ a box fitted to the two-view cloud
+    def estimate_cloud_pose(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
+                            view2_extrinsic_batch, *, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True, max_points=None, fit_seed=None):
+        """`estimate_cloud` (same arguments, keywords, frame types, upload modes, chunk pipeline and errors) plus the object-space
+        coordinate of every cloud row and a second, independent box per pose fitted to them.  Everything `estimate_cloud` returns,
+        unchanged, plus `nocs1` / `nocs2` [n,S,S,3] f32 (the network's NOCS branch at every pixel of the two crops; read at `choose` they
+        are the point NOCS), `cloud_nocs` [n,cap,3] f32 (the maps at `cloud_index`), and the similarity RANSAC of the reference's
+        `direct_regression: False` tail between `cloud_nocs` and `cloud` (`cloud_similarity`, seed `fit_seed`, default cfg
+        hip_ransac_seed; pose b of the call draws stream b, whatever the chunking): `bbox_cloud` [n,8,3] f64 (world frame), `srt_cloud`
+        [n,13] f64 (scale, R, t), `fit_info` [n,4] i32 (rows used, kept hypothesis or -1, its inliers, hypotheses examined) and
+        `valid_cloud` [n] i32.  A sample with valid 0, fewer than 5 rows or no consensus has valid_cloud 0 and the +10 cube; a sample with
+        valid 0 has NaN NOCS maps."""
+        opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points, fit_seed=fit_seed)
+        return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
+                                          view2_mask_batch, view2_extrinsic_batch, dense=opts)
+
+    def estimate_cloud_pose_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0, *, px_max=1.0, rel_max=0.01, conf_min=0.0,
+                                   masked=True, max_points=None, fit_seed=None):
+        """`estimate_cloud_pose` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
+        opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points, fit_seed=fit_seed)
+        return self._cloud_fit(self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=opts), opts)
+
+    def _cloud_fit(self, out, o):
+        """The fit of `estimate_cloud_pose` over all poses of a call at once (so that pose b draws sample stream b however the call was
+        chunked); every other result passes through untouched."""
+        if not (isinstance(o, _Cloud) and "fit_seed" in o):
+            return out
+        bbox, srt, info, valid = cloud_similarity(out["cloud_nocs"], out["cloud"], out["count"], seed=o["fit_seed"])
+        out = dict(out)
+        out.update(bbox_cloud=bbox, srt_cloud=srt, fit_info=info, valid_cloud=valid)
+        return out
+
     def _cloud_tail(self, r, pred, a, b, E1d, E2d, ok, o: _Cloud):
         """The dict of `estimate_depth` (r, left as it is) extended by the view-2 maps, the two checks and the packed cloud."""
         n = E1d.shape[0]
@@ -454,6 +490,10 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         for v, res in ((1, v1), (2, v2)):
             for k in ("fused", "keep", "reproj", "rel"):
                 r[f"{k}{v}"] = res[k]
+        if "fit_seed" in o:
+            n1 = torch.where(ok.view(n, 1, 1, 1), pred["view1_nocs_map"], nan)
+            n2 = torch.where(ok.view(n, 1, 1, 1), pred["view2_nocs_map"], nan)
+            r.update(nocs1=n1, nocs2=n2, cloud_nocs=cloud_gather(n1, n2, index))
         return r
 
     def _alloc_out(self, n, dev, dense):
@@ -468,6 +508,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
                        cloud_index=torch.empty(n, cap, dtype=torch.int32, device=dev), count=torch.empty(n, 2, dtype=torch.int32, device=dev))
             for v in (1, 2):
                 out.update({f"fused{v}": m(torch.float32), f"keep{v}": m(torch.uint8), f"reproj{v}": m(torch.float32), f"rel{v}": m(torch.float32)})
+            if "fit_seed" in dense:
+                out.update(nocs1=torch.empty(n, S, S, 3, dtype=torch.float32, device=dev), nocs2=torch.empty(n, S, S, 3, dtype=torch.float32, device=dev),
+                           cloud_nocs=torch.empty(n, cap, 3, dtype=torch.float32, device=dev))
             return out
         if not dense:
             return torch.empty(n, 8, 3, dtype=torch.float64, device=dev)
@@ -530,8 +573,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         depths = consts[1][None].expand(n, 24).contiguous()
         if dense:
             assert cached is None
+            nk = {"dense_nocs": True} if isinstance(dense, _Cloud) and "fit_seed" in dense else {}
             pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], proj(a["Kcrop"], E1d), proj(b["Kcrop"], E2d), depths,
-                                  dense_depth=True)
+                                  dense_depth=True, **nk)
             self._plain_views += 2 * n
             self._content.bypassed += int(self.feature_cache)      # a call / chunk the cache was set for and did not serve
         elif cached is None:

@@ -1,0 +1,173 @@
+"""-m gpu: `cloud_similarity` (csrc/cloud_fit.hip) against the oracle's similarity RANSAC fed the same hash sample stream, and
+`AdaPoseEstimator_v5.estimate_cloud_pose` end to end."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from cloud_fit_cases import CASES, SEED, oracle_fit, planted  # noqa: E402
+from rgbmanip_amd.adapose import cloud_similarity  # noqa: E402
+
+S = 224
+
+
+def _host(ts):
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in ts)
+
+
+def _against_oracle(got, j, nocs, cloud, count, seed, tag):
+    """Pose j of a device call against the oracle at tests/test_gpu_align.py's tolerances; info exactly."""
+    bbox, srt, info, valid = got
+    want, s, R, t, margin, scan = oracle_fit(nocs, cloud, count, seed, j)
+    assert info[j, 0] == min(nocs.shape[0], int(count.sum())) and tuple(info[j, 1:]) == scan, (tag, info[j], scan)
+    if s is None:
+        assert valid[j] == 0 and np.isnan(srt[j, 0]), tag
+        np.testing.assert_array_equal(bbox[j], want)
+        return False
+    assert valid[j] == 1, tag
+    np.testing.assert_allclose(srt[j, 0], s, rtol=1e-10, err_msg=tag)
+    np.testing.assert_allclose(srt[j, 1:10].reshape(3, 3), R, rtol=0, atol=1e-10, err_msg=tag)
+    np.testing.assert_allclose(srt[j, 10:], t, rtol=0, atol=1e-10, err_msg=tag)
+    np.testing.assert_allclose(bbox[j], want, rtol=0, atol=1e-9, err_msg=tag)
+    return True
+
+
+def test_cloud_similarity_matches_the_oracle_on_the_host_cases():
+    """The cases of tests/test_cloud_fit_host.py (whose margin condition is verified there), grouped by cap into device calls, so that
+    the pose index of the sample stream varies too."""
+    caps = sorted({c[2] for c in CASES})
+    n_valid = 0
+    for cap in caps:
+        group = [(k, c) for k, c in enumerate(CASES) if c[2] == cap]
+        data = [planted(k, c[1], c[2], c[3], c[4], c[5]) for k, c in group]
+        got = _host(cloud_similarity(np.stack([d[0] for d in data]), np.stack([d[1] for d in data]), np.stack([d[2] for d in data]), seed=SEED))
+        assert got[0].dtype == np.float64 and got[1].shape == (len(group), 13) and got[2].dtype == np.int32 and got[3].dtype == np.int32
+        for j, ((k, c), d) in enumerate(zip(group, data)):
+            n_valid += _against_oracle(got, j, *d, SEED, c[0])
+    assert n_valid == 9
+
+
+def test_cloud_similarity_at_the_full_cap_and_twice():
+    """cap = m = 2 S S = 100 352 rows, n = 2 (25 slices per pose), 20 % and 45 % outliers; two calls give identical bytes."""
+    cap = 2 * S * S
+    data = [planted(100 + i, cap, cap, o, False) for i, o in enumerate((0.2, 0.45))]
+    args = [torch.from_numpy(np.stack([d[i] for d in data])).cuda() for i in range(3)]
+    a = _host(cloud_similarity(*args, seed=5))
+    b = _host(cloud_similarity(*args, seed=5))
+    for x, y in zip(a, b):
+        assert x.tobytes() == y.tobytes()
+    for j, d in enumerate(data):
+        want, s, R, t, margin, scan = oracle_fit(*d, 5, j)
+        print(f"pose {j}: margin {margin:.3e}, scan {scan}")
+        assert margin > 1e-9                                 # the condition on the inputs, as in the host test
+        assert _against_oracle(a, j, *d, 5, f"full cap, pose {j}")
+    assert a[2][:, 0].tolist() == [cap, cap]
+
+
+def test_cloud_similarity_without_rows():
+    bbox, srt, info, valid = _host(cloud_similarity(np.zeros((2, 0, 3), np.float32), np.zeros((2, 0, 3), np.float32), np.zeros((2, 2), np.int32)))
+    assert valid.tolist() == [0, 0] and np.isnan(srt[:, 0]).all() and (bbox >= 10).all() and info.tolist() == [[0, -1, 0, 0]] * 2
+
+
+# ------------------------------------------------------------------------------------------------------------------ end to end
+def _scene():
+    from test_gpu_cloud import _scene as scene
+    return scene()
+
+
+def _estimator(**kw):
+    from test_gpu_cloud import _estimator as estimator, _net
+    return estimator(_net(view2_heads=1), hip_view2_heads=True, **kw)
+
+
+LOOSE = dict(px_max=60.0, rel_max=0.5, conf_min=0.05)       # tests/test_gpu_cloud.py: lets a share of a synthetic net's pixels through
+FIT_KEYS = ["nocs1", "nocs2", "cloud_nocs", "bbox_cloud", "srt_cloud", "fit_info", "valid_cloud"]
+
+
+def _check_fit(r, seed):
+    """The fit keys of a result dict (numpy) against the maps, the cloud and the oracle fit of the returned rows."""
+    n, cap = r["cloud"].shape[:2]
+    assert r["nocs1"].shape == (n, S, S, 3) and r["nocs1"].dtype == np.float32 and r["nocs2"].shape == (n, S, S, 3)
+    assert r["cloud_nocs"].shape == (n, cap, 3) and r["cloud_nocs"].dtype == np.float32
+    assert r["bbox_cloud"].shape == (n, 8, 3) and r["bbox_cloud"].dtype == np.float64 and r["srt_cloud"].shape == (n, 13)
+    assert r["fit_info"].shape == (n, 4) and r["fit_info"].dtype == np.int32 and r["valid_cloud"].shape == (n,)
+    both = np.concatenate([r["nocs1"].reshape(n, S * S, 3), r["nocs2"].reshape(n, S * S, 3)], axis=1)
+    for i in range(n):
+        ix = r["cloud_index"][i]
+        want = np.full((cap, 3), np.nan, dtype=np.float32)
+        want[ix >= 0] = both[i][ix[ix >= 0]]
+        assert np.array_equal(r["cloud_nocs"][i], want, equal_nan=True), i
+        _against_oracle((r["bbox_cloud"], r["srt_cloud"], r["fit_info"], r["valid_cloud"]), i, r["cloud_nocs"][i], r["cloud"][i], r["count"][i],
+                        seed, f"pose {i}")
+    # the pose with the empty mask
+    assert np.isnan(r["nocs1"][1]).all() and np.isnan(r["nocs2"][1]).all() and r["valid_cloud"][1] == 0 and (r["bbox_cloud"][1] >= 10).all()
+    assert np.isfinite(r["nocs1"][[0, 2]]).all()
+
+
+@pytest.mark.parametrize("mode,chunk", [("frames", 32), ("frames", 2), ("windows", 32), ("windows", 2)])
+@pytest.mark.parametrize("frames", ["f", "u"])
+def test_estimate_cloud_pose(frames, mode, chunk):
+    """n = 3 (pose 1 has an empty mask), float and 8-bit frames, whole-frame and window upload, one call and the chunk pipeline."""
+    s = _scene()
+    est = _estimator(hip_upload=mode, hip_upload_chunk=chunk, hip_ransac_seed=5)
+    args = (s["K"], s[frames + "1"], s["m1"], s["E1"], s[frames + "2"], s["m2"], s["E2"])
+    kw = dict(max_points=6000, **LOOSE)
+    base = est.estimate_cloud(*args, **kw)
+    r = est.estimate_cloud_pose(*args, **kw)
+    assert sorted(r) == sorted(list(base) + FIT_KEYS) and all(isinstance(v, np.ndarray) for v in r.values())
+    for k in base:
+        assert np.array_equal(r[k], base[k], equal_nan=True), k
+    _check_fit(r, 5)
+    print("fit_info", r["fit_info"].tolist(), "valid_cloud", r["valid_cloud"].tolist())
+    # the device call on the whole batch: estimate_cloud_device's tensors, the fit of its own rows; the host call's bytes when that ran
+    # as one chunk too (the network's small-batch paths make the chunked maps differ in the last bits, as for estimate_cloud)
+    u8 = frames == "u"
+    dev = [torch.from_numpy(s["u1"] if u8 else s["f1"].astype(np.float32)).cuda(), torch.from_numpy(s["m1"]).cuda(),
+           torch.from_numpy(s["u2"] if u8 else s["f2"].astype(np.float32)).cuda(), torch.from_numpy(s["m2"]).cuda()]
+    dargs = (s["K"], dev[0], dev[1], s["E1"], dev[2], dev[3], s["E2"])
+    dbase = est.estimate_cloud_device(*dargs, **kw)
+    d = est.estimate_cloud_pose_device(*dargs, **kw)
+    assert sorted(d) == sorted(r) and all(isinstance(v, torch.Tensor) and v.is_cuda for v in d.values())
+    for k in dbase:
+        assert torch.equal(d[k].view(torch.uint8), dbase[k].view(torch.uint8)), k
+    dh = {k: v.cpu().numpy() for k, v in d.items()}
+    _check_fit(dh, 5)
+    if chunk >= 3:
+        for k in r:
+            assert np.array_equal(dh[k], r[k], equal_nan=True), k
+
+
+def test_estimate_cloud_pose_options_and_what_it_leaves_alone():
+    """fit_seed; the full default cap; the errors of estimate_cloud; estimate / estimate_depth / estimate_cloud before and after;
+    AdaPoseEstimator_v4 inherits the call."""
+    from rgbmanip_amd.config import adapose_cfg
+    from rgbmanip_amd.estimator import AdaPoseEstimator_v4
+    from test_gpu_cloud import _estimator as estimator, _net
+    s = _scene()
+    args = (s["K"], s["u1"], s["m1"], s["E1"], s["u2"], s["m2"], s["E2"])
+    est = _estimator(hip_ransac_seed=5)
+    box0, depth0, cloud0 = est.estimate(*args), est.estimate_depth(*args), est.estimate_cloud(*args, **LOOSE)
+    r = est.estimate_cloud_pose(*args, **LOOSE)                                    # cap = 2 S S
+    assert r["cloud_nocs"].shape == (3, 2 * S * S, 3)
+    _check_fit(r, 5)
+    q = est.estimate_cloud_pose(*args, fit_seed=77, max_points=6000, **LOOSE)
+    _check_fit(q, 77)
+    box1, depth1, cloud1 = est.estimate(*args), est.estimate_depth(*args), est.estimate_cloud(*args, **LOOSE)
+    assert np.array_equal(box0, box1)
+    for a, b in ((depth0, depth1), (cloud0, cloud1)):
+        assert sorted(a) == sorted(b)
+        for k in a:
+            assert np.array_equal(a[k], b[k], equal_nan=True), k
+    for k in cloud0:
+        assert np.array_equal(r[k], cloud0[k], equal_nan=True), k
+    with pytest.raises(ValueError, match="hip_view2_heads"):
+        estimator(_net(view2_heads=0)).estimate_cloud_pose(*args)
+    with pytest.raises(ValueError, match="hip_view2_heads"):
+        estimator(_net(view2_heads=0)).estimate_cloud_pose_device(*args)
+    v4 = AdaPoseEstimator_v4(None, dict(adapose_cfg("one_door_cabinet", load=False, name="adapose_v4"), hip_dtype="bf16", hip_prepare="device",
+                                        hip_prepare_seed=9, hip_view2_heads=True, hip_ransac_seed=5), None, net=_net(view2_heads=1))
+    w = v4.estimate_cloud_pose(*args, max_points=6000, **LOOSE)
+    assert sorted(w) == sorted(q) and w["valid"].tolist() == [1, 0, 1]
+    _check_fit(w, 5)
