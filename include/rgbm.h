@@ -124,7 +124,8 @@ int rgbm_adapose_forward(rgbm_adapose_t* h, int B, const float* img1, const floa
  *   these two options, and can differ from the default sparse-tail outputs by the rounding between the two tails (16-bit and split-pair
  *   storage; the bound of tests/test_gpu_adapose.py::test_prob_sparse_kernels_agree).  Works with Dropout2d on (the masks are drawn
  *   upstream of the cost volume).  There is no hipGraph and no feature-cache form of this call.
- * rgbm_adapose_dense_workspace_bytes: the workspace of such a call (256-byte aligned, as for rgbm_adapose_forward).
+ * rgbm_adapose_dense_workspace_bytes: the workspace of such a call (256-byte aligned, as for rgbm_adapose_forward).  The workspace plan
+ *   holds conv11's output whatever the options and the call say, so this is rgbm_adapose_workspace_bytes(B); the query reads the handle only.
  * rgbm_depth_to_points: depth_map [n][S][S] fp32, Kcrop [n][3][3] fp64 (cropped intrinsics), E [n][4][4] fp64 (world -> camera) ->
  *   points [n][S][S][3] fp32 in the world frame: inv(E) (depth Kcrop^-1 (x, y, 1)^T), the per-pixel form of the back-projection of
  *   interface_v5.py:329-336 followed by ex_inv of :369-372 (fp64 arithmetic, rounded once).  A pixel whose depth is not finite yields
@@ -579,13 +580,14 @@ int rgbm_adapose_forward_ex(rgbm_adapose_t* h, int B, const float* img1, const f
                             size_t workspace_bytes, const rgbm_adapose_out* out, int stop_after, void* stream);
 /* rgbm_adapose_forward replayed from a hipGraph (small batches — the reference calls the network at batch 1 per env,
  * interface_v5.py:213-227,259-280, and ships num_envs: 8 — are launch-bound: ~150 launches per forward).  The first call with a
- * given (B, every device pointer, workspace, outputs) runs the forward once eagerly, captures its launch sequence on `stream` and
+ * given (B, every device pointer, workspace, outputs, stream) runs the forward once eagerly, captures its launch sequence on `stream` and
  * keeps the instantiated graph (up to 8 per handle, least recently used evicted; dropped when an option changes); later calls with the
  * same arguments replay it with one hipGraphLaunch.  The caller keeps every buffer alive and at the same address.  `stream` must be
  * a created (non-null) stream.  *n_nodes (optional) = graph nodes (kernel launches + copies) of this batch size; *captured
  * (optional) = 1 when this call did the capture, 0 on a replay, -1 when it ran eagerly because rgbm_prof_start is active.
- * Pass the same `stream` for every call on one set of buffers: the captured launches of a small batch use the K-split scratch of the stream
- * they were captured on (rgbm_debug_flags 16384), which other streams' forwards do not share. */
+ * The capture stream is part of the key: the captured launches of a small batch use the K-split scratch of the stream they were captured on
+ * (rgbm_debug_flags 16384), which other streams' forwards do not share, so a call with the same buffers on another stream warms up and
+ * captures a graph of its own (*captured = 1, the same limit of 8) instead of replaying the first stream's. */
 int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
                                const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
                                size_t workspace_bytes, const rgbm_adapose_out* out, void* stream, int32_t* n_nodes, int32_t* captured);

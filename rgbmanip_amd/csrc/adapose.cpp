@@ -262,7 +262,7 @@ void AdaPose::destroy() {
   up1c.destroy(); up2c.destroy(); tail.destroy();
   if (drop_masks) (void)hipFree(drop_masks);
   if (drop_state) (void)hipFree(drop_state);
-  drop_masks = nullptr; drop_state = nullptr; drop_cap_views = 0; drop_p = 0.f; drop_explicit = 0; drop_last_B = 0;
+  drop_masks = nullptr; drop_state = nullptr; drop_cap_views = 0; drop_p = 0.f;
   for (auto& l : c3d) l.destroy();
   for (auto& l : dc) l.destroy();
   for (auto& l : c3d_raw) l.destroy();
@@ -301,10 +301,13 @@ bool AdaPose::feat_f16() const {
          tail.ready() && tail.f16_ready();
 }
 
-bool AdaPose::sparse_active() const {
+bool AdaPose::sparse_tail_active(bool dense) const {
   const bool b16 = dtype_size(dtype) == 2;
-  return sparse_dec != 0 && norm_mode == 0 && cost_impl == 3 && (b16 || (dtype == BF16X3 && w11_x3)) && sparse_tail && sweep_w != nullptr &&
-         !(g_debug_flags & DBG_TILE_CONV0);
+  return !dense && sparse_tail && norm_mode == 0 && cost_impl == 3 && (b16 || (dtype == BF16X3 && w11_x3));
+}
+
+bool AdaPose::sparse_active(bool dense) const {
+  return sparse_dec != 0 && sparse_tail_active(dense) && sweep_w != nullptr && !(g_debug_flags & DBG_TILE_CONV0);
 }
 
 int AdaPose::chunk_views(int V) const {
@@ -392,8 +395,10 @@ size_t AdaPose::workspace_bytes(int B) const {
   return A.peak + 256;
 }
 
-int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* img2, hipStream_t s, const float* drop) const {
+int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* img2, const Call& call) const {
   const int S = img;
+  hipStream_t s = call.stream;
+  const float* drop = call.dropout != Dropout::None ? drop_masks : nullptr;      // factors [V][kDropoutPerView]
   int H = S / 2, W = S / 2;
   if (stem && stem_w) {
     // NCHW fp32 images -> conv1 + ReLU + max-pool in one kernel (no padded copy, no 112 x 112 x 64 tensor)
@@ -429,8 +434,7 @@ int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* im
     H = Ho; W = Wo;
     xi = (xi + 3) & 3;
   }
-  const void* f = bf.lb[xi];                    // [V][H][W][512], H = W = S/8
-  last_f_index = xi;
+  const void* f = bf.lb[xi];                    // [V][H][W][512], H = W = S/8; xi == layer4_index()
   RGBM_REQUIRE(H == S / 8 && W == S / 8, "feature stride");
   if (g_debug_flags & DBG_PSP_STAGE_R5) {      // the PSP stage as rounds 1-5 ran it: copy, pooling, four GEMM launches, four resizes
     if (int rc = launch_copy_channels(dtype, f, bf.cat, (long long)V * H * W, 512, 1024, 0, s)) return rc;
@@ -465,7 +469,7 @@ int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* im
   }
   // up_1 / up_2: 1x1 GEMM at the low resolution (nine taps stacked on the output channels, z in `ups`: 9/16 of the up-sampled
   // tensor it replaces) + tap combination; or, for A/B, the x2 resize followed by the 3x3 conv on the up-sampled grid
-  // Dropout2d (drop: factors [V][kDropoutPerView]) is applied in the tap combination's epilogue only: the A/B paths refuse it
+  // Dropout2d is applied in the tap combination's epilogue only: the A/B paths refuse it
   RGBM_REQUIRE(drop == nullptr || (upconv & 3) == 3, "dropout needs option upconv bits 0 and 1 (up_1 / up_2 through the tap combination)");
   if (upconv & 1) {
     if (int rc = up1c.run(bf.cat, bf.ups, bf.u1, V, H, W, 256, s, drop)) return rc;
@@ -479,19 +483,18 @@ int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* im
     if (int rc = launch_resize_bilinear_ac(dtype, bf.u1, bf.ups, V, 2 * H, 2 * W, 256, 4 * H, 4 * W, 256, 0, s)) return rc;
     if (int rc = up2.run(bf.ups, bf.u2, V, 1, 4 * H, 4 * W, 64, nullptr, 0, nullptr, 0, s)) return rc;
   }
-  fin.out_plain_f32 = feat_f32_only();
+  const bool plain_f32 = feat_f32_only();
   if ((upconv & 4) && tail.ready())       // up_3 + final from the half-resolution tensor in one kernel: no up-sampled tensor, no z, no u3
-    return tail.run(bf.u2, fin.out_plain_f32 ? (void*)bf.featf : bf.feat, fin.out_plain_f32 ? 1 : feat_f16() ? 2 : 0, V, 4 * H, 4 * W, s);
+    return tail.run(bf.u2, plain_f32 ? (void*)bf.featf : bf.feat, plain_f32 ? 1 : feat_f16() ? 2 : 0, V, 4 * H, 4 * W, s);
   if (int rc = launch_resize_bilinear_ac(dtype, bf.u2, bf.ups, V, 4 * H, 4 * W, 64, 8 * H, 8 * W, 64, 0, s)) return rc;
   // up_3 + final: one launch on the bf16 path (the 64-channel up_3 output then never reaches HBM: `u3` is not written)
   // bf16x3, default path: `final` writes the plain-fp32 feature map directly (no split-pair copy, no 6.6 GB conversion pass)
-  fin.out_plain_f32 = feat_f32_only();
-  if (int rc = up3.run_then_1x1(fin, bf.ups, bf.u3, 64, fin.out_plain_f32 ? (void*)bf.featf : bf.feat, 32, V, 1, 8 * H, 8 * W, fuse_final != 0, nullptr, s)) return rc;
-  return 0;
+  return up3.run_then_1x1(fin, bf.ups, bf.u3, 64, plain_f32 ? (void*)bf.featf : bf.feat, 32, V, 1, 8 * H, 8 * W, fuse_final != 0, nullptr, s, plain_f32);
 }
 
-int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, hipStream_t s) const {
+int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, const Call& call) const {
   const int S = img, D = n_depth, P = n_pts;
+  hipStream_t s = call.stream;
   const int Vh = view2_heads ? V : B;      // views whose probability volume is computed (partners are looked up among all V)
   const int Vc0 = chunk_views(V);
   const bool b16 = dtype_size(dtype) == 2;      // 16-bit storage: the depth-sweeping conv0, implicit-GEMM conv6 and the sparse tail exist for these
@@ -536,176 +539,120 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, h
   // layer is needed only inside their dependency cones (prob_sparse.hip: sparse_mask_kernel) — conv1 .. conv5, conv7 / conv9 skip the
   // other tiles, the depth-sweeping conv0 walks the list of needed ones.  conv6 stays dense (a 0.3 ms GEMM): what it computes from
   // unwritten input tiles is never read by anything that is read.
-  const bool sparse_ok = sparse_active();
-  // forward_dense(): the dense head on the u11 of every chunk, beside the point kernel (rows v0 .. v0 + Vc - 1 of the maps)
-  auto dense = [&](int v0, int Vc, int classmajor) -> int {
-    if (dense_depth_map == nullptr) return 0;
-    return launch_dense_depth(dtype, bf.u11, wprob, depths, dense_depth_map, dense_conf_map, v0, Vc, B, D, S, S, classmajor, s);
-  };
-  for (int v0 = 0; norm_mode == 0 && cost_impl >= 1 && v0 < Vh; v0 += Vc0) {
+  const bool sparse_ok = sparse_active(call.dense);
+  // the ten 3-D layers as the two generic bodies walk them: input, output, skip tensor, down-sampling of the input grid, output channels
+  struct Layer3d { const void* in; void* out; const void* res; int div, C; };
+  const Layer3d l3d[10] = {{bf.vol, bf.c[0], nullptr, 1, 8}, {bf.c[0], bf.c[1], nullptr, 1, 16}, {bf.c[1], bf.c[2], nullptr, 2, 16},
+                           {bf.c[2], bf.c[3], nullptr, 2, 32}, {bf.c[3], bf.c[4], nullptr, 4, 32}, {bf.c[4], bf.c[5], nullptr, 4, 64},
+                           {bf.c[5], bf.c[6], nullptr, 8, 64}, {bf.c[6], bf.u7, bf.c[4], 8, 32}, {bf.u7, bf.u9, bf.c[2], 4, 16},
+                           {bf.u9, bf.u11, bf.c[0], 2, 8}};
+  for (int v0 = 0; v0 < Vh; v0 += Vc0) {
     const int Vc = Vh - v0 < Vc0 ? Vh - v0 : Vc0;
-    const unsigned char* mk[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    sweep_sparse = false;
-    if (sparse_ok) {
-      int td, th, tw;
-      for (int L : {1, 2, 3, 4, 5, 7, 8}) RGBM_REQUIRE(!conv3d_tile_dims(L, dtype, &td, &th, &tw) && th == 8 && tw == 8, "sparse cost regularisation: 8 x 8 tiles expected");
-      if (int rc = launch_sparse_masks(bf.choose, v0, Vc, P, S, bf.masks, bf.sweep_list, bf.sweep_count, s)) return rc;
-      for (int L : {7, 8}) mk[L] = bf.masks + sparse_mask_offset(S, L);
-      if (sparse_dec >= 2) {
-        for (int L : {1, 2, 3, 4, 5}) mk[L] = bf.masks + sparse_mask_offset(S, L);
-        sweep_sparse = true;
-      }
-    }
-    if (cost_impl == 1) {
+    int classmajor = 0;      // layout of the u11 the chunk body leaves behind
+    if (norm_mode == 1) {
+      // per-sample BatchNorm3d: every layer = un-normalised conv (generic implicit GEMM) -> per-view batch statistics -> normalise + ReLU (+ skip)
       if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
-      if (int rc = tile(0, bf.vol, bf.c[0], nullptr, Vc, D, S, S, D, S, S, false, v0)) return rc;
+      for (int i = 0; i < 10; ++i) {
+        const Layer3d& l = l3d[i];
+        const ConvLayer& L = i >= 7 ? dc_raw[i - 7] : c3d_raw[i];
+        int Do, Ho, Wo;
+        L.out_dims(D / l.div, S / l.div, S / l.div, Do, Ho, Wo);
+        if (int rc = L.run(l.in, l.out, Vc, D / l.div, S / l.div, S / l.div, l.C, nullptr, RES_NONE, nullptr, 0, s)) return rc;
+        if (int rc = launch_bn_per_sample(dtype, l.out, l.res, bn_gamma[i], bn_beta[i], bf.bn_scratch, Vc, (long long)Do * Ho * Wo, l.C, 1, s)) return rc;
+      }
+    } else if (cost_impl == 0) {
+      // generic implicit GEMM on the materialised volume; the skip adds of conv7 / 9 / 11 are post-ReLU (network_v5.py:287-289)
+      if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
+      for (int i = 0; i < 10; ++i) {
+        const Layer3d& l = l3d[i];
+        const ConvLayer& L = i >= 7 ? dc[i - 7] : c3d[i];
+        if (int rc = L.run(l.in, l.out, Vc, D / l.div, S / l.div, S / l.div, l.C, l.res, RES_POST_ACT, nullptr, 0, s)) return rc;
+      }
     } else {
-      if (int rc = tile(10, nullptr, bf.c[0], nullptr, Vc, D, S, S, D, S, S, false, v0)) return rc;
+      // halo-tiled layers; conv0 on the materialised volume (cost_impl 1) or with the plane sweep fused in
+      const unsigned char* mk[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+      sweep_sparse = false;
+      if (sparse_ok) {
+        int td, th, tw;
+        for (int L : {1, 2, 3, 4, 5, 7, 8}) RGBM_REQUIRE(!conv3d_tile_dims(L, dtype, &td, &th, &tw) && th == 8 && tw == 8, "sparse cost regularisation: 8 x 8 tiles expected");
+        if (int rc = launch_sparse_masks(bf.choose, v0, Vc, P, S, bf.masks, bf.sweep_list, bf.sweep_count, s)) return rc;
+        for (int L : {7, 8}) mk[L] = bf.masks + sparse_mask_offset(S, L);
+        if (sparse_dec >= 2) {
+          for (int L : {1, 2, 3, 4, 5}) mk[L] = bf.masks + sparse_mask_offset(S, L);
+          sweep_sparse = true;
+        }
+      }
+      if (cost_impl == 1) {
+        if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
+        if (int rc = tile(0, bf.vol, bf.c[0], nullptr, Vc, D, S, S, D, S, S, false, v0)) return rc;
+      } else {
+        if (int rc = tile(10, nullptr, bf.c[0], nullptr, Vc, D, S, S, D, S, S, false, v0)) return rc;
+      }
+      if (int rc = tile(1, bf.c[0], bf.c[1], nullptr, Vc, D, S, S, D / 2, S / 2, S / 2, false, v0, mk[1])) return rc;
+      if (int rc = tile(2, bf.c[1], bf.c[2], nullptr, Vc, D / 2, S / 2, S / 2, D / 2, S / 2, S / 2, false, v0, mk[2])) return rc;
+      if (int rc = tile(3, bf.c[2], bf.c[3], nullptr, Vc, D / 2, S / 2, S / 2, D / 4, S / 4, S / 4, false, v0, mk[3])) return rc;
+      if (int rc = tile(4, bf.c[3], bf.c[4], nullptr, Vc, D / 4, S / 4, S / 4, D / 4, S / 4, S / 4, false, v0, mk[4])) return rc;
+      if (int rc = tile(5, bf.c[4], bf.c[5], nullptr, Vc, D / 4, S / 4, S / 4, D / 8, S / 8, S / 8, false, v0, mk[5])) return rc;
+      if (cost_impl == 3 && (b16 || dtype == BF16X3) && igemm_conv6) {
+        // conv6 (64 -> 64, K = 27 x 64): a plain GEMM shape, 2.7x faster on the role-specialised implicit-GEMM kernel
+        if (int rc = c3d[6].run(bf.c[5], bf.c[6], Vc, D / 8, S / 8, S / 8, 64, nullptr, RES_NONE, nullptr, 0, s)) return rc;
+      } else {
+        if (int rc = tile(6, bf.c[5], bf.c[6], nullptr, Vc, D / 8, S / 8, S / 8, D / 8, S / 8, S / 8, false, v0)) return rc;
+      }
+      if (int rc = tile(7, bf.c[6], bf.u7, bf.c[4], Vc, D / 8, S / 8, S / 8, D / 4, S / 4, S / 4, true, v0, mk[7])) return rc;
+      if (int rc = tile(8, bf.u7, bf.u9, bf.c[2], Vc, D / 4, S / 4, S / 4, D / 2, S / 2, S / 2, true, v0, mk[8])) return rc;
+      if (sparse_tail_active(call.dense)) {
+        // conv11 + skip + prob conv + softmax + depth only on the 3x3 neighbourhoods of the chosen pixels (prob_sparse.hip)
+        if (int rc = launch_prob_sparse(bf.u9, bf.c[0], dtype == BF16X3 ? w11_x3 : t3d[9].w, t3d[9].bias, wprob, bf.choose, depths, bf.prob,
+                                        bf.depth, v0, Vc, B, P, D, S, S, dtype, s, w11_taps)) return rc;
+        continue;
+      }
+      if (int rc = tile(9, bf.u9, bf.u11, bf.c[0], Vc, D / 2, S / 2, S / 2, D, S, S, true, v0)) return rc;
+      classmajor = 1;      // u11 is only gathered: conv11's halo-tile kernel writes it class-major
     }
-    if (int rc = tile(1, bf.c[0], bf.c[1], nullptr, Vc, D, S, S, D / 2, S / 2, S / 2, false, v0, mk[1])) return rc;
-    if (int rc = tile(2, bf.c[1], bf.c[2], nullptr, Vc, D / 2, S / 2, S / 2, D / 2, S / 2, S / 2, false, v0, mk[2])) return rc;
-    if (int rc = tile(3, bf.c[2], bf.c[3], nullptr, Vc, D / 2, S / 2, S / 2, D / 4, S / 4, S / 4, false, v0, mk[3])) return rc;
-    if (int rc = tile(4, bf.c[3], bf.c[4], nullptr, Vc, D / 4, S / 4, S / 4, D / 4, S / 4, S / 4, false, v0, mk[4])) return rc;
-    if (int rc = tile(5, bf.c[4], bf.c[5], nullptr, Vc, D / 4, S / 4, S / 4, D / 8, S / 8, S / 8, false, v0, mk[5])) return rc;
-    if (cost_impl == 3 && (b16 || dtype == BF16X3) && igemm_conv6) {
-      // conv6 (64 -> 64, K = 27 x 64): a plain GEMM shape, 2.7x faster on the role-specialised implicit-GEMM kernel
-      if (int rc = c3d[6].run(bf.c[5], bf.c[6], Vc, D / 8, S / 8, S / 8, 64, nullptr, RES_NONE, nullptr, 0, s)) return rc;
-    } else {
-      if (int rc = tile(6, bf.c[5], bf.c[6], nullptr, Vc, D / 8, S / 8, S / 8, D / 8, S / 8, S / 8, false, v0)) return rc;
-    }
-    if (int rc = tile(7, bf.c[6], bf.u7, bf.c[4], Vc, D / 8, S / 8, S / 8, D / 4, S / 4, S / 4, true, v0, mk[7])) return rc;
-    if (int rc = tile(8, bf.u7, bf.u9, bf.c[2], Vc, D / 4, S / 4, S / 4, D / 2, S / 2, S / 2, true, v0, mk[8])) return rc;
-    if (cost_impl == 3 && (b16 || (dtype == BF16X3 && w11_x3)) && sparse_tail) {
-      // conv11 + skip + prob conv + softmax + depth only on the 3x3 neighbourhoods of the chosen pixels (prob_sparse.hip)
-      if (int rc = launch_prob_sparse(bf.u9, bf.c[0], dtype == BF16X3 ? w11_x3 : t3d[9].w, t3d[9].bias, wprob, bf.choose, depths, bf.prob,
-                                      bf.depth, v0, Vc, B, P, D, S, S, dtype, s, w11_taps)) return rc;
-      continue;
-    }
-    if (int rc = tile(9, bf.u9, bf.u11, bf.c[0], Vc, D / 2, S / 2, S / 2, D, S, S, true, v0)) return rc;
-    if (int rc = launch_prob_softmax_depth(dtype, bf.u11, wprob, bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, 1, s)) return rc;
-    if (int rc = dense(v0, Vc, 1)) return rc;
-  }
-  // norm_mode 1: every layer = un-normalised conv (generic implicit GEMM) -> per-view batch statistics -> normalise + ReLU (+ skip)
-  for (int v0 = 0; norm_mode == 1 && v0 < Vh; v0 += Vc0) {
-    const int Vc = Vh - v0 < Vc0 ? Vh - v0 : Vc0;
-    if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
-    auto layer = [&](int i, const void* in, void* out, const void* res, int Di, int Hi, int Wi, int C) -> int {
-      const ConvLayer& L = i >= 7 ? dc_raw[i - 7] : c3d_raw[i];
-      int Do, Ho, Wo;
-      L.out_dims(Di, Hi, Wi, Do, Ho, Wo);
-      if (int rc = L.run(in, out, Vc, Di, Hi, Wi, C, nullptr, RES_NONE, nullptr, 0, s)) return rc;
-      return launch_bn_per_sample(dtype, out, res, bn_gamma[i], bn_beta[i], bf.bn_scratch, Vc, (long long)Do * Ho * Wo, C, 1, s);
-    };
-    if (int rc = layer(0, bf.vol, bf.c[0], nullptr, D, S, S, 8)) return rc;
-    if (int rc = layer(1, bf.c[0], bf.c[1], nullptr, D, S, S, 16)) return rc;
-    if (int rc = layer(2, bf.c[1], bf.c[2], nullptr, D / 2, S / 2, S / 2, 16)) return rc;
-    if (int rc = layer(3, bf.c[2], bf.c[3], nullptr, D / 2, S / 2, S / 2, 32)) return rc;
-    if (int rc = layer(4, bf.c[3], bf.c[4], nullptr, D / 4, S / 4, S / 4, 32)) return rc;
-    if (int rc = layer(5, bf.c[4], bf.c[5], nullptr, D / 4, S / 4, S / 4, 64)) return rc;
-    if (int rc = layer(6, bf.c[5], bf.c[6], nullptr, D / 8, S / 8, S / 8, 64)) return rc;
-    if (int rc = layer(7, bf.c[6], bf.u7, bf.c[4], D / 8, S / 8, S / 8, 32)) return rc;
-    if (int rc = layer(8, bf.u7, bf.u9, bf.c[2], D / 4, S / 4, S / 4, 16)) return rc;
-    if (int rc = layer(9, bf.u9, bf.u11, bf.c[0], D / 2, S / 2, S / 2, 8)) return rc;
-    if (int rc = launch_prob_softmax_depth(dtype, bf.u11, wprob, bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, 0, s)) return rc;
-    if (int rc = dense(v0, Vc, 0)) return rc;
-  }
-  if (norm_mode == 1) return 0;
-  for (int v0 = 0; cost_impl == 0 && v0 < Vh; v0 += Vc0) {
-    const int Vc = Vh - v0 < Vc0 ? Vh - v0 : Vc0;
-    if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
-    if (int rc = c3d[0].run(bf.vol, bf.c[0], Vc, D, S, S, 8, nullptr, 0, nullptr, 0, s)) return rc;
-    if (int rc = c3d[1].run(bf.c[0], bf.c[1], Vc, D, S, S, 16, nullptr, 0, nullptr, 0, s)) return rc;
-    if (int rc = c3d[2].run(bf.c[1], bf.c[2], Vc, D / 2, S / 2, S / 2, 16, nullptr, 0, nullptr, 0, s)) return rc;
-    if (int rc = c3d[3].run(bf.c[2], bf.c[3], Vc, D / 2, S / 2, S / 2, 32, nullptr, 0, nullptr, 0, s)) return rc;
-    if (int rc = c3d[4].run(bf.c[3], bf.c[4], Vc, D / 4, S / 4, S / 4, 32, nullptr, 0, nullptr, 0, s)) return rc;
-    if (int rc = c3d[5].run(bf.c[4], bf.c[5], Vc, D / 4, S / 4, S / 4, 64, nullptr, 0, nullptr, 0, s)) return rc;
-    if (int rc = c3d[6].run(bf.c[5], bf.c[6], Vc, D / 8, S / 8, S / 8, 64, nullptr, 0, nullptr, 0, s)) return rc;
-    // skip adds are post-ReLU (network_v5.py:287-289)
-    if (int rc = dc[0].run(bf.c[6], bf.u7, Vc, D / 8, S / 8, S / 8, 32, bf.c[4], RES_POST_ACT, nullptr, 0, s)) return rc;
-    if (int rc = dc[1].run(bf.u7, bf.u9, Vc, D / 4, S / 4, S / 4, 16, bf.c[2], RES_POST_ACT, nullptr, 0, s)) return rc;
-    if (int rc = dc[2].run(bf.u9, bf.u11, Vc, D / 2, S / 2, S / 2, 8, bf.c[0], RES_POST_ACT, nullptr, 0, s)) return rc;
-    if (int rc = launch_prob_softmax_depth(dtype, bf.u11, wprob, bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, 0, s)) return rc;
-    if (int rc = dense(v0, Vc, 0)) return rc;
+    if (int rc = launch_prob_softmax_depth(dtype, bf.u11, wprob, bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, classmajor, s)) return rc;
+    // the dense head on the u11 of every chunk, beside the point kernel (rows v0 .. v0 + Vc - 1 of the maps)
+    if (call.depth_map != nullptr)
+      if (int rc = launch_dense_depth(dtype, bf.u11, wprob, depths, call.depth_map, call.conf_map, v0, Vc, B, D, S, S, classmajor, s)) return rc;
   }
   return 0;
 }
 
 int AdaPose::forward(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
                      const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
-                     hipStream_t s, int stop_after) const {
+                     const Call& call) const {
+  RGBM_REQUIRE(call.depth_map == nullptr || call.dense, "forward: depth_map needs a dense call");
+  RGBM_REQUIRE(call.depth_map != nullptr || call.conf_map == nullptr, "forward_maps: conf_map without depth_map");
+  RGBM_REQUIRE(call.nocs_map == nullptr || pmlp_table != nullptr, "forward_maps: no point MLP table");
   RGBM_REQUIRE(B > 0, "batch");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
   const size_t need = workspace_bytes(B);
-  RGBM_REQUIRE(workspace_size >= need, "workspace too small: need " + std::to_string(need));
+  RGBM_REQUIRE(workspace_size >= need, call.dense ? "forward_dense: workspace too small: need " + std::to_string(need) + " (rgbm_adapose_dense_workspace_bytes)"
+                                                  : "workspace too small: need " + std::to_string(need));
   Arena A(workspace, workspace_size);
   Buffers bf;
   plan(B, A, bf);
-  const int V = 2 * B, P = n_pts, S = img, D = n_depth;
-  const size_t VP = (size_t)V * P;
+  const int V = 2 * B, S = img;
+  hipStream_t s = call.stream;
 
   // ---- stage inputs: views = [view1 batch ; view2 batch] ----
-  if (int rc = launch_stage_in(P1, P2, choose1, choose2, bf.Pviews, bf.choose, B, P, s)) return rc;
+  if (int rc = launch_stage_in(P1, P2, choose1, choose2, bf.Pviews, bf.choose, B, n_pts, s)) return rc;
   // Dropout2d: masks loaded for this forward (rgbm_adapose_set_dropout_masks), or drawn for poses counter .. counter + B - 1
-  const float* drop = nullptr;
-  if (drop_active()) {
-    RGBM_REQUIRE(V <= drop_cap_views && drop_masks && (drop_explicit || drop_state), "dropout: mask buffer smaller than the batch");
+  if (call.dropout != Dropout::None) {
+    const bool loaded = call.dropout == Dropout::Loaded;
+    RGBM_REQUIRE(V <= drop_cap_views && drop_masks && (loaded || drop_state), "dropout: mask buffer smaller than the batch");
     RGBM_REQUIRE((upconv & 3) == 3, "dropout needs option upconv bits 0 and 1 (up_1 / up_2 through the tap combination)");
-    if (drop_explicit) {
-      RGBM_REQUIRE(drop_explicit == B, "dropout: the masks set for the next forward are for batch " + std::to_string(drop_explicit));
-      drop_explicit = 0;
-    } else {
-      if (int rc = launch_dropout_masks(drop_masks, drop_state, B, drop_p, drop_seed, drop_no_advance ? 0 : 1, s)) return rc;
-    }
-    drop = drop_masks;
-    drop_last_B = B;
+    if (!loaded)
+      if (int rc = launch_dropout_masks(drop_masks, drop_state, B, drop_p, drop_seed, call.dropout == Dropout::Draw ? 1 : 0, s)) return rc;
   }
-  if (int rc = pspnet(bf, V, img1, img2, s, drop)) return rc;
+  if (int rc = pspnet(bf, V, img1, img2, call)) return rc;
   if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
   // bf16x3 nets: everything that GATHERS from the feature map (plane sweep, point heads) reads a plain fp32 copy of it
   if (dtype == BF16X3 && !feat_f32_only())
     if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * S * S * 32, s)) return rc;
-  if (stop_after == 1) return 0;
-  (void)VP; (void)P; (void)D;
-  return heads(bf, B, depths, out, s, stop_after);
-}
-
-size_t AdaPose::dense_workspace_bytes(int B) {
-  const int sd = sparse_dec, st = sparse_tail;
-  sparse_dec = 0; sparse_tail = 0;
-  const size_t n = workspace_bytes(B);
-  sparse_dec = sd; sparse_tail = st;
-  return n;
-}
-
-int AdaPose::forward_dense(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
-                           const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
-                           float* depth_map, float* conf_map, hipStream_t s) {
-  RGBM_REQUIRE(depth_map != nullptr, "forward_dense: depth_map is null");
-  RGBM_REQUIRE(B > 0, "batch");
-  const size_t need = dense_workspace_bytes(B);
-  RGBM_REQUIRE(workspace_size >= need, "forward_dense: workspace too small: need " + std::to_string(need) + " (rgbm_adapose_dense_workspace_bytes)");
-  const int sd = sparse_dec, st = sparse_tail;
-  sparse_dec = 0; sparse_tail = 0;
-  dense_depth_map = depth_map; dense_conf_map = conf_map;
-  const int rc = forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_size, out, s, 0);
-  dense_depth_map = nullptr; dense_conf_map = nullptr;
-  sparse_dec = sd; sparse_tail = st;
-  return rc;
-}
-
-int AdaPose::forward_maps(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
-                          const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
-                          float* depth_map, float* conf_map, float* nocs_map, hipStream_t s) {
-  RGBM_REQUIRE(depth_map != nullptr || nocs_map != nullptr, "forward_maps: depth_map and nocs_map are both null");
-  RGBM_REQUIRE(depth_map != nullptr || conf_map == nullptr, "forward_maps: conf_map without depth_map");
-  RGBM_REQUIRE(nocs_map == nullptr || pmlp_table != nullptr, "forward_maps: no point MLP table");
-  dense_nocs_map = nocs_map;
-  const int rc = depth_map != nullptr
-      ? forward_dense(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_size, out, depth_map, conf_map, s)
-      : forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_size, out, s, 0);
-  dense_nocs_map = nullptr;
-  return rc;
+  if (call.stop_after == 1) return 0;
+  return heads(bf, B, depths, out, call);
 }
 
 int AdaPose::nocs_map_of(const float* feat_f32, long long pixels, float* nocs_map, hipStream_t s) const {
@@ -714,8 +661,9 @@ int AdaPose::nocs_map_of(const float* feat_f32, long long pixels, float* nocs_ma
 }
 
 // Everything behind the PSPNet: reads the feature map(s) in bf.feat / bf.featf, bf.homog, bf.choose (forward() and forward_cached() fill them)
-int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs& out, hipStream_t s, int stop_after) const {
+int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call) const {
   const int V = 2 * B, P = n_pts, S = img, D = n_depth;
+  hipStream_t s = call.stream;
   const void* featg = bf.feat;
   int fdt = dtype;
   if (dtype == BF16X3) { featg = bf.featf; fdt = F32; }
@@ -739,13 +687,13 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
     if (int rc = npm[1].run(bf.N32, bf.PF96 + 32, Vh, 1, 1, P, 96, nullptr, 0, nullptr, 0, s)) return rc;
   }
 
-  // forward_maps(): the same branch's layers 0..3 on every pixel of the Vh feature maps (the dense NOCS map)
-  if (dense_nocs_map != nullptr)
-    if (int rc = launch_dense_nocs(fdt, pmlp_table, featg, dense_nocs_map, (long long)Vh * S * S, s)) return rc;
+  // the same branch's layers 0..3 on every pixel of the Vh feature maps (the dense NOCS map)
+  if (call.nocs_map != nullptr)
+    if (int rc = launch_dense_nocs(fdt, pmlp_table, featg, call.nocs_map, (long long)Vh * S * S, s)) return rc;
 
   // ---- plane-sweep cost volume -> probability at the sampled pixels -> depth ----
-  if (int rc = cost_volume(bf, V, B, depths, s)) return rc;
-  if (stop_after == 2) return 0;
+  if (int rc = cost_volume(bf, V, B, depths, call)) return rc;
+  if (call.stop_after == 2) return 0;
 
   // ---- depth-guided fusion + pose regression (network_v5.py:457-508) ----
   if (int rc = launch_fuse_points(fdt, featg, bf.homog, depths, bf.choose, bf.prob, bf.PF96, V, B, P, D, S, S, 96, 0, s, Vh)) return rc;
@@ -825,9 +773,10 @@ size_t AdaPose::feature_bytes() const {
 size_t AdaPose::features_workspace_bytes(int V) const { return workspace_bytes((V + 1) / 2); }
 
 int AdaPose::features(int V, const float* images, const int* slots, void* pool, int pool_records, void* workspace, size_t workspace_size,
-                      hipStream_t s) const {
+                      const Call& call) const {
+  hipStream_t s = call.stream;
   RGBM_REQUIRE(V > 0 && pool_records > 0, "features: views and pool records");
-  RGBM_REQUIRE(!drop_active(), "features: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would change "
+  RGBM_REQUIRE(call.dropout == Dropout::None, "features: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would change "
                "what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "features: workspace must be 256-byte, pool 16-byte aligned");
   const size_t need = features_workspace_bytes(V);
@@ -835,7 +784,7 @@ int AdaPose::features(int V, const float* images, const int* slots, void* pool, 
   Arena A(workspace, workspace_size);
   Buffers bf;
   plan((V + 1) / 2, A, bf);
-  if (int rc = pspnet(bf, V, images, nullptr, s, nullptr)) return rc;
+  if (int rc = pspnet(bf, V, images, nullptr, call)) return rc;
   if (dtype == BF16X3 && !feat_f32_only())
     if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * img * img * 32, s)) return rc;
   FeaturePart parts[2];
@@ -848,9 +797,10 @@ int AdaPose::features(int V, const float* images, const int* slots, void* pool, 
 
 int AdaPose::forward_cached(int B, const void* pool, int pool_records, const int* slot1, const int* slot2, const int* choose1,
                             const int* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
-                            size_t workspace_size, const Outputs& out, hipStream_t s) const {
+                            size_t workspace_size, const Outputs& out, const Call& call) const {
+  hipStream_t s = call.stream;
   RGBM_REQUIRE(B > 0 && pool_records > 0, "forward_cached: batch and pool records");
-  RGBM_REQUIRE(!drop_active(), "forward_cached: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would "
+  RGBM_REQUIRE(call.dropout == Dropout::None, "forward_cached: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would "
                "change what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "forward_cached: workspace must be 256-byte, pool 16-byte aligned");
   RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
@@ -867,7 +817,7 @@ int AdaPose::forward_cached(int B, const void* pool, int pool_records, const int
   for (int i = 0; i < np; ++i)
     if (int rc = launch_feature_gather(pool, parts[i].buf, slot1, slot2, B, pool_records, parts[i].off, parts[i].bytes, rec, s)) return rc;
   if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
-  if (int rc = heads(bf, B, depths, out, s, 0)) return rc;
+  if (int rc = heads(bf, B, depths, out, call)) return rc;
   // a slot outside the pool: that pose's ten outputs are NaN (nothing was read for it; every other pose is what a clean call gives)
   float* const o[10] = {out.nocs1, out.nocs2, out.depth1, out.depth2, out.r1, out.r2, out.t1, out.t2, out.s1, out.s2};
   const int per[10] = {3 * P, 3 * P, P, P, 9, 9, 3, 3, 3, 3};

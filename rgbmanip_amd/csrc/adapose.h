@@ -74,18 +74,35 @@ struct AdaPose {
   float* head_b[3][3] = {{nullptr}};
 
   // Seeded Dropout2d of PSPNet (dropout.hip; set through rgbm_adapose_set_dropout): p = 0 is off.  drop_masks [drop_cap_views][kDropoutPerView]
-  // holds the factors of the last forward, drop_state the device pose counter (+ the mask kernel's ticket).  drop_explicit: B of masks
-  // loaded by rgbm_adapose_set_dropout_masks, used by the next forward instead of drawing; drop_no_advance: draw without advancing the
-  // counter (the eager warm-up in front of a graph capture, which the replay draws again)
+  // holds the factors of the last forward, drop_state the device pose counter (+ the mask kernel's ticket).  Which masks a forward uses
+  // is the call's business (Call::dropout); which call comes next and what the last one drew is the handle's (capi.cpp).
   float drop_p = 0.f;
   unsigned long long drop_seed = 0;
   float* drop_masks = nullptr;
   unsigned long long* drop_state = nullptr;
   int drop_cap_views = 0;
-  mutable int drop_explicit = 0;
-  mutable int drop_last_B = 0;
-  int drop_no_advance = 0;
-  bool drop_active() const { return drop_p > 0.f || drop_explicit > 0; }
+
+  // What one call wants beyond the network's inputs and outputs.  The entry point (capi.cpp) fills it; forward() / forward_cached() pass
+  // it down pspnet() / heads() / cost_volume(), none of which writes the net.
+  enum class Dropout {
+    None,            // no Dropout2d
+    Loaded,          // the factors rgbm_adapose_set_dropout_masks put into drop_masks
+    Draw,            // draw for poses counter .. counter + B - 1 and advance the counter
+    DrawNoAdvance    // draw without advancing (the eager warm-up in front of a graph capture, which the replay draws again)
+  };
+  struct Call {
+    hipStream_t stream = nullptr;
+    int stop_after = 0;
+    // a dense cost regularisation and the dense tail for this call: what options sparse_dec = 0, sparse_tail = 0 give.  The ten point
+    // outputs are those of a handle built with the two options.
+    bool dense = false;
+    // depth_map / conf_map [Vh][img][img] fp32, Vh = 2B or, with view2_heads = 0, B: the dense head (dense_depth.hip) on every chunk's
+    // u11 (needs `dense`; conf_map may be null alone).  nocs_map [Vh][img][img][3] fp32: layers 0..3 of the point MLP table on every pixel
+    // (head_kernels.hip: dense_nocs_kernel), launched behind the per-point branch in heads(), so that nocs_map read at choose is the
+    // point NOCS bit for bit; it needs nothing dense, and the ten outputs are the plain forward's bit for bit.
+    float *depth_map = nullptr, *conf_map = nullptr, *nocs_map = nullptr;
+    Dropout dropout = Dropout::None;
+  };
 
   struct Buffers {
     float *Pviews, *homog; int* choose; void* feat;
@@ -109,56 +126,42 @@ struct AdaPose {
   int create(const StateDict& sd, int dtype, int norm_mode = 0);
   void destroy();
   size_t workspace_bytes(int B) const;
+  // the map rules of a call (depth_map needs dense, conf_map needs depth_map, nocs_map needs the point MLP table) are checked here
   int forward(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
-              const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
-              hipStream_t s, int stop_after = 0) const;
-  // forward() with a dense cost regularisation and the dense tail for this one call (sparse_dec = 0, sparse_tail = 0; the handle's
-  // options are restored before it returns), plus the dense head (dense_depth.hip) on every chunk's u11: depth_map / conf_map
-  // [Vh][img][img] fp32, Vh = 2B or, with view2_heads = 0, B.  conf_map may be null.  The ten point outputs are those of a handle built
-  // with the two options.  dense_workspace_bytes(B): the workspace of such a call (the plan holds u11 whatever the options say).
-  size_t dense_workspace_bytes(int B);
-  int forward_dense(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
-                    const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
-                    float* depth_map, float* conf_map, hipStream_t s);
-  float* dense_depth_map = nullptr;      // set for the duration of forward_dense: cost_volume() runs the dense head behind every u11
-  float* dense_conf_map = nullptr;
-  // forward_maps(): forward_dense() (depth_map != null) or the plain forward() (depth_map == null: the handle's sparse_dec / sparse_tail and
-  // the workspace_bytes(B) workspace; the ten outputs are forward()'s bit for bit), plus the dense NOCS map nocs_map [Vh][img][img][3] fp32
-  // when it is not null: layers 0..3 of the point MLP table on every pixel (head_kernels.hip: dense_nocs_kernel), launched behind the
-  // per-point branch in heads(), so that nocs_map read at choose is the point NOCS bit for bit.
-  int forward_maps(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
-                   const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
-                   float* depth_map, float* conf_map, float* nocs_map, hipStream_t s);
+              const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out, const Call& call) const;
+  // the workspace of a dense call: the plan holds u11 whatever the options and the call say
+  size_t dense_workspace_bytes(int B) const { return workspace_bytes(B); }
   int nocs_map_of(const float* feat_f32, long long pixels, float* nocs_map, hipStream_t s) const;      // the kernel alone on an fp32 feature array
-  float* dense_nocs_map = nullptr;       // set for the duration of forward_maps
   // Feature cache: the forward split at the PSPNet's output.  features() runs the PSPNet on V >= 1 views of one image array
   // [V][3][img][img] and writes view v's record (feature_bytes() long) to pool + slots[v] * feature_bytes(); forward_cached() is
-  // forward() with the PSPNet replaced by reading records slot1[b] / slot2[b].  Both refuse a net with Dropout2d on.  A slot outside
-  // [0, pool_records) is neither written nor read; forward_cached() returns NaN outputs for such a pose.
+  // forward() with the PSPNet replaced by reading records slot1[b] / slot2[b].  Both refuse a call with Dropout2d (call.dropout != None).
+  // A slot outside [0, pool_records) is neither written nor read; forward_cached() returns NaN outputs for such a pose.
   size_t feature_bytes() const;
   size_t features_workspace_bytes(int V) const;
   int features(int V, const float* images, const int* slots, void* pool, int pool_records, void* workspace, size_t workspace_size,
-               hipStream_t s) const;
+               const Call& call) const;
   int forward_cached(int B, const void* pool, int pool_records, const int* slot1, const int* slot2, const int* choose1, const int* choose2,
                      const float* P1, const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
-                     hipStream_t s) const;
+                     const Call& call) const;
   struct FeaturePart { void* buf; size_t off, bytes; };      // a feature buffer of the workspace and its place inside a record
   int feature_parts(const Buffers& bf, FeaturePart parts[2]) const;
-  int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, hipStream_t s, int stop_after) const;
-  mutable int last_f_index = 0;   // which rotating buffer holds the layer4 output (debug fetch)
+  int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call) const;
+  int layer4_index() const { return (3 * n_blocks) & 3; }      // which of the rotating buffers bf.lb holds the layer4 output (debug fetch)
 
   // exposed for layer-level tests
   int plan(int B, Arena& A, Buffers& bf) const;
   // img2 == nullptr: all V views (any V >= 1) lie in img1
-  int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, hipStream_t s, const float* drop = nullptr) const;
-  int cost_volume(const Buffers& bf, int V, int B, const float* depths, hipStream_t s) const;
+  int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, const Call& call) const;
+  int cost_volume(const Buffers& bf, int V, int B, const float* depths, const Call& call) const;
   int chunk_views(int V) const;
   // bf16x3 on the default path: nothing reads the split-pair feature map (the sweep and the point heads gather from plain fp32), so
   // `final` writes fp32 directly; the A/B paths (materialised volume, halo-tile conv0, per-sample BN) still want split pairs
   bool feat_f32_only() const;
   bool feat_f16() const;        // bf16 nets: the feature map (bf.feat) holds f16 in this forward (option sweep_f16 and the paths that can produce / consume it)
-  // the conditions under which cost_volume() skips tiles outside the chosen pixels' dependency cones (option sparse_dec)
-  bool sparse_active() const;
+  // the sparse tail (conv11 + prob only where prob is gathered: option sparse_tail) runs in a call that is not dense, and with it
+  // cost_volume() skips tiles outside the chosen pixels' dependency cones (option sparse_dec)
+  bool sparse_tail_active(bool dense) const;
+  bool sparse_active(bool dense = false) const;
 };
 
 const char* last_error_cstr();

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -16,9 +17,12 @@
 using namespace rgbm;
 
 // One captured forward: the launch sequence of AdaPose::forward for a fixed batch size and fixed device pointers, replayed with a
-// single hipGraphLaunch (small batches are launch-bound: ~150 launches of a few microseconds each per forward).
+// single hipGraphLaunch (small batches are launch-bound: ~150 launches of a few microseconds each per forward).  The capture stream is part
+// of the key: the K-split scratch and its arrival counters belong to the capture stream (m32_ksplit_buffers), so a replay on another stream
+// would share them with whatever runs on the first.
 struct ForwardGraph {
   int B = 0;
+  hipStream_t stream = nullptr;
   const void* in[7] = {nullptr};
   void* ws = nullptr;
   size_t ws_bytes = 0;
@@ -37,6 +41,8 @@ struct rgbm_adapose {
   int opt_version = 0;                 // bumped by set_option / set_chunk: captured graphs of older settings are dropped
   unsigned long long tick = 0;
   std::vector<ForwardGraph> graphs;    // at most kMaxGraphs, least recently used evicted
+  int drop_explicit = 0;               // B of the masks loaded by rgbm_adapose_set_dropout_masks: the next forward uses them instead of drawing
+  int drop_last_B = 0;                 // batch of the last forward with Dropout2d (what rgbm_adapose_dropout_masks reads back)
 };
 static const size_t kMaxGraphs = 8;
 
@@ -63,6 +69,42 @@ static void drop_graph(ForwardGraph& g) {
   g.exec = nullptr; g.graph = nullptr;
 }
 
+static AdaPose::Outputs to_out(const rgbm_adapose_out* o) {
+  AdaPose::Outputs r;
+  r.nocs1 = o->view1_nocs; r.nocs2 = o->view2_nocs; r.depth1 = o->view1_depth; r.depth2 = o->view2_depth;
+  r.r1 = o->view1_r; r.r2 = o->view2_r; r.t1 = o->view1_t; r.t2 = o->view2_t; r.s1 = o->view1_s; r.s2 = o->view2_s;
+  return r;
+}
+
+// What every forward entry point does before it runs the net: the null checks (`name` arguments), the Dropout2d buffer for this batch, and
+// the call's stream and dropout instruction - masks loaded for one forward win over drawing.  finish_call() books what a forward that ran
+// did to the handle's dropout state.
+static int prepare_call(rgbm_adapose* h, const char* name, int B, std::initializer_list<const void*> pointers, void* stream, AdaPose::Call* call) {
+  bool ok = h != nullptr;
+  for (const void* p : pointers) ok = ok && p != nullptr;
+  RGBM_REQUIRE(ok, std::string(name) + " arguments");
+  if (h->net.drop_p > 0.f && B > 0)
+    if (int rc = ensure_dropout_capacity(h, B)) return rc;
+  call->stream = (hipStream_t)stream;
+  call->dropout = h->drop_explicit ? AdaPose::Dropout::Loaded : h->net.drop_p > 0.f ? AdaPose::Dropout::Draw : AdaPose::Dropout::None;
+  return 0;
+}
+
+static int finish_call(rgbm_adapose* h, int B, const AdaPose::Call& call, int rc) {
+  if (rc == 0 && call.dropout != AdaPose::Dropout::None) {
+    h->drop_last_B = B;
+    if (call.dropout == AdaPose::Dropout::Loaded) h->drop_explicit = 0;      // masks set for one forward are used once
+  }
+  return rc;
+}
+
+static int forward_call(rgbm_adapose* h, const char* name, int B, const float* img1, const float* img2, const int32_t* choose1,
+                        const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace, size_t workspace_bytes,
+                        const rgbm_adapose_out* out, void* stream, AdaPose::Call call) {
+  if (int rc = prepare_call(h, name, B, {img1, img2, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
+  RGBM_REQUIRE(h->drop_explicit == 0 || h->drop_explicit == B, "dropout: the masks set for the next forward are for batch " + std::to_string(h->drop_explicit));
+  return finish_call(h, B, call, h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), call));
+}
 
 extern "C" {
 
@@ -139,8 +181,8 @@ int rgbm_adapose_set_dropout(rgbm_adapose_t* h, float p, uint64_t seed) {
 
 int rgbm_adapose_dropout_masks(rgbm_adapose_t* h, int B, float* out_dev) {
   RGBM_REQUIRE(h && out_dev && B > 0, "dropout_masks arguments");
-  RGBM_REQUIRE(h->net.drop_last_B == B && h->net.drop_masks, "dropout_masks: the last forward with dropout had batch " +
-               std::to_string(h->net.drop_last_B) + ", not " + std::to_string(B));
+  RGBM_REQUIRE(h->drop_last_B == B && h->net.drop_masks, "dropout_masks: the last forward with dropout had batch " +
+               std::to_string(h->drop_last_B) + ", not " + std::to_string(B));
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   RGBM_CHECK_HIP(hipDeviceSynchronize());
   RGBM_CHECK_HIP(hipMemcpy(out_dev, h->net.drop_masks, (size_t)2 * B * kDropoutPerView * sizeof(float), hipMemcpyDeviceToDevice));
@@ -153,7 +195,7 @@ int rgbm_adapose_set_dropout_masks(rgbm_adapose_t* h, int B, const float* masks_
   if (int rc = ensure_dropout_capacity(h, B)) return rc;
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // no forward in flight reads the buffer any more
   RGBM_CHECK_HIP(hipMemcpy(h->net.drop_masks, masks_dev, (size_t)2 * B * kDropoutPerView * sizeof(float), hipMemcpyDeviceToDevice));
-  h->net.drop_explicit = B;
+  h->drop_explicit = B;
   return 0;
 }
 
@@ -163,21 +205,12 @@ int rgbm_adapose_workspace_bytes(rgbm_adapose_t* h, int B, size_t* bytes) {
   return 0;
 }
 
-static AdaPose::Outputs to_out(const rgbm_adapose_out* o) {
-  AdaPose::Outputs r;
-  r.nocs1 = o->view1_nocs; r.nocs2 = o->view2_nocs; r.depth1 = o->view1_depth; r.depth2 = o->view2_depth;
-  r.r1 = o->view1_r; r.r2 = o->view2_r; r.t1 = o->view1_t; r.t2 = o->view2_t; r.s1 = o->view1_s; r.s2 = o->view2_s;
-  return r;
-}
-
 int rgbm_adapose_forward_ex(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
                             const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
                             size_t workspace_bytes, const rgbm_adapose_out* out, int stop_after, void* stream) {
-  RGBM_REQUIRE(h && img1 && img2 && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward arguments");
-  if (h->net.drop_p > 0.f && B > 0)
-    if (int rc = ensure_dropout_capacity(h, B)) return rc;
-  return h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out),
-                        (hipStream_t)stream, stop_after);
+  AdaPose::Call call;
+  call.stop_after = stop_after;
+  return forward_call(h, "forward", B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, out, stream, call);
 }
 
 int rgbm_adapose_forward(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
@@ -196,11 +229,9 @@ int rgbm_adapose_forward_dense(rgbm_adapose_t* h, int B, const float* img1, cons
                                const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
                                size_t workspace_bytes, const rgbm_adapose_out* out, float* depth_map, float* conf_map, void* stream) {
   RGBM_REQUIRE(depth_map != nullptr, "forward_dense: depth_map is NULL (conf_map may be, depth_map may not)");
-  RGBM_REQUIRE(h && img1 && img2 && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward_dense arguments");
-  if (h->net.drop_p > 0.f && B > 0)
-    if (int rc = ensure_dropout_capacity(h, B)) return rc;
-  return h->net.forward_dense(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), depth_map,
-                              conf_map, (hipStream_t)stream);
+  AdaPose::Call call;
+  call.dense = true; call.depth_map = depth_map; call.conf_map = conf_map;
+  return forward_call(h, "forward_dense", B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, out, stream, call);
 }
 
 int rgbm_adapose_forward_maps(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
@@ -209,11 +240,9 @@ int rgbm_adapose_forward_maps(rgbm_adapose_t* h, int B, const float* img1, const
                               void* stream) {
   RGBM_REQUIRE(depth_map != nullptr || nocs_map != nullptr, "forward_maps: depth_map, conf_map and nocs_map are all NULL (or conf_map alone is given)");
   RGBM_REQUIRE(depth_map != nullptr || conf_map == nullptr, "forward_maps: conf_map needs depth_map");
-  RGBM_REQUIRE(h && img1 && img2 && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward_maps arguments");
-  if (h->net.drop_p > 0.f && B > 0)
-    if (int rc = ensure_dropout_capacity(h, B)) return rc;
-  return h->net.forward_maps(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), depth_map, conf_map,
-                             nocs_map, (hipStream_t)stream);
+  AdaPose::Call call;
+  call.dense = depth_map != nullptr; call.depth_map = depth_map; call.conf_map = conf_map; call.nocs_map = nocs_map;
+  return forward_call(h, "forward_maps", B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, out, stream, call);
 }
 
 int rgbm_nocs_map(rgbm_adapose_t* h, const float* feat_f32, int V, int HW, float* nocs_map, void* stream) {
@@ -268,8 +297,9 @@ int rgbm_adapose_features_workspace_bytes(rgbm_adapose_t* h, int V, size_t* byte
 
 int rgbm_adapose_features(rgbm_adapose_t* h, int V, const float* img, const int32_t* slots_dev, void* pool, int pool_records,
                           void* workspace, size_t workspace_bytes, void* stream) {
-  RGBM_REQUIRE(h && img && slots_dev && pool && workspace, "features arguments");
-  return h->net.features(V, img, slots_dev, pool, pool_records, workspace, workspace_bytes, (hipStream_t)stream);
+  AdaPose::Call call;      // a handle with Dropout2d on (or masks loaded) is refused by the net
+  if (int rc = prepare_call(h, "features", 0, {img, slots_dev, pool, workspace}, stream, &call)) return rc;
+  return h->net.features(V, img, slots_dev, pool, pool_records, workspace, workspace_bytes, call);
 }
 
 int rgbm_crop_fingerprint(const float* img, int V, int n_words, uint64_t* keys_out, void* stream) {
@@ -279,9 +309,10 @@ int rgbm_crop_fingerprint(const float* img, int V, int n_words, uint64_t* keys_o
 int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int pool_records, const int32_t* slot1_dev,
                                 const int32_t* slot2_dev, const int32_t* choose1, const int32_t* choose2, const float* P1, const float* P2,
                                 const float* depths, void* workspace, size_t workspace_bytes, const rgbm_adapose_out* out, void* stream) {
-  RGBM_REQUIRE(h && pool && slot1_dev && slot2_dev && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward_cached arguments");
+  AdaPose::Call call;
+  if (int rc = prepare_call(h, "forward_cached", B, {pool, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
   return h->net.forward_cached(B, pool, pool_records, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, workspace_bytes,
-                               to_out(out), (hipStream_t)stream);
+                               to_out(out), call);      // refuses a call with Dropout2d
 }
 
 int rgbm_adapose_graph_clear(rgbm_adapose_t* h) {
@@ -294,19 +325,21 @@ int rgbm_adapose_graph_clear(rgbm_adapose_t* h) {
 int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1,
                                const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
                                size_t workspace_bytes, const rgbm_adapose_out* out, void* stream, int32_t* n_nodes, int32_t* captured) {
-  RGBM_REQUIRE(h && img1 && img2 && choose1 && choose2 && P1 && P2 && depths && workspace && out, "forward_graph arguments");
-  hipStream_t s = (hipStream_t)stream;
   if (n_nodes) *n_nodes = 0;
   if (captured) *captured = 0;
+  AdaPose::Call call;
   // the in-library profiler records events around launches: not capturable, and a timing run wants the launches themselves
-  if (h->net.drop_p > 0.f && B > 0)
-    if (int rc = ensure_dropout_capacity(h, B)) return rc;
   // masks loaded by rgbm_adapose_set_dropout_masks are for one forward: not captured
-  if (prof_enabled() || h->net.drop_explicit) {
+  if (prof_enabled() || (h && h->drop_explicit)) {
     if (captured) *captured = -1;
-    return h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), s, 0);
+    return forward_call(h, "forward_graph", B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, out, stream, call);
   }
+  if (int rc = prepare_call(h, "forward_graph", B, {img1, img2, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
+  hipStream_t s = call.stream;
   RGBM_REQUIRE(s != nullptr, "forward_graph: stream capture is not allowed on the default (null) stream; pass a created stream");
+  auto forward = [&](const AdaPose::Call& c) {
+    return h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), c);
+  };
   const void* in[7] = {img1, img2, choose1, choose2, P1, P2, depths};
   ForwardGraph* hit = nullptr;
   for (size_t i = 0; i < h->graphs.size();) {
@@ -316,23 +349,21 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
       h->graphs.erase(h->graphs.begin() + i);
       continue;
     }
-    if (g.B == B && !memcmp(g.in, in, sizeof(in)) && g.ws == workspace && g.ws_bytes == workspace_bytes &&
+    if (g.B == B && g.stream == s && !memcmp(g.in, in, sizeof(in)) && g.ws == workspace && g.ws_bytes == workspace_bytes &&
         !memcmp(&g.out, out, sizeof(*out))) hit = &g;
     ++i;
   }
   if (!hit) {
     // an eager forward first: it sets the dynamic-LDS attributes of the kernels this shape uses and loads their code objects (neither
     // may happen inside a capture), and reports argument errors with their own messages
-    // with dropout the warm-up draws the masks the replay draws again: the pose counter advances once
-    h->net.drop_no_advance = 1;
-    const int rw = h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), s, 0);
-    h->net.drop_no_advance = 0;
-    if (rw) return rw;
+    AdaPose::Call warm = call;      // with dropout the warm-up draws the masks the replay draws again: the pose counter advances once
+    if (call.dropout == AdaPose::Dropout::Draw) warm.dropout = AdaPose::Dropout::DrawNoAdvance;
+    if (int rw = forward(warm)) return rw;
     ForwardGraph g;
-    g.B = B; memcpy(g.in, in, sizeof(in)); g.ws = workspace; g.ws_bytes = workspace_bytes; g.out = *out;
+    g.B = B; g.stream = s; memcpy(g.in, in, sizeof(in)); g.ws = workspace; g.ws_bytes = workspace_bytes; g.out = *out;
     g.opt_version = h->opt_version; g.tuning_version = g_tuning_version;
     RGBM_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), s, 0);
+    const int rc = forward(call);
     const hipError_t ee = hipStreamEndCapture(s, &g.graph);
     if (rc) { if (g.graph) (void)hipGraphDestroy(g.graph); return rc; }
     if (ee != hipSuccess || !g.graph) { set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(ee)); return -2; }
@@ -352,7 +383,7 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
   hit->last_use = ++h->tick;
   if (n_nodes) *n_nodes = (int32_t)hit->nodes;
   RGBM_CHECK_HIP(hipGraphLaunch(hit->exec, s));
-  return 0;
+  return finish_call(h, B, call, 0);
 }
 
 int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* name, float* out_dev, size_t capacity,
@@ -368,7 +399,7 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   const void* src = nullptr; size_t cnt = 0; int dt = n.dtype;
   if (nm == "imgpad") { src = bf.imgpad; cnt = V * S * S * n.img_cpad; }
   else if (nm == "conv1") { src = bf.c1; cnt = V * (S / 2) * (S / 2) * 64; }
-  else if (nm == "layer4") { src = bf.lb[n.last_f_index]; cnt = V * (S / 8) * (S / 8) * 512; }
+  else if (nm == "layer4") { src = bf.lb[n.layer4_index()]; cnt = V * (S / 8) * (S / 8) * 512; }
   else if (nm == "cat") { src = bf.cat; cnt = V * (S / 8) * (S / 8) * 1024; }
   else if (nm == "u1") { src = bf.u1; cnt = V * (S / 4) * (S / 4) * 256; }
   else if (nm == "u2") { src = bf.u2; cnt = V * (S / 2) * (S / 2) * 64; }

@@ -248,7 +248,7 @@ void conv_desc_geom(ConvDesc& d, const ConvGeom& g, const PackedConv& pc, int Ci
 }
 
 int ConvLayer::build_desc(ConvDesc& d, const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res,
-                          int res_mode, const float* bias_override, int bias_stride, int cls) const {
+                          int res_mode, const float* bias_override, int bias_stride, int cls, bool out_plain_f32) const {
   RGBM_REQUIRE(!packs.empty(), "conv layer not initialised");
   const PackedConv& pc = packs[cls];
   conv_desc_geom(d, g, pc, Cin_pad, Cout_pad, N, Di, Hi, Wi, ldo, cls);
@@ -266,18 +266,18 @@ int ConvLayer::build_desc(ConvDesc& d, const void* in, void* out, int N, int Di,
 }
 
 int ConvLayer::run(const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res, int res_mode,
-                   const float* bias_override, int bias_stride, hipStream_t s) const {
+                   const float* bias_override, int bias_stride, hipStream_t s, bool out_plain_f32) const {
   const int nclass = g.transposed ? 8 : 1;
   for (int cls = 0; cls < nclass; ++cls) {
     ConvDesc d;
-    if (int rc = build_desc(d, in, out, N, Di, Hi, Wi, ldo, res, res_mode, bias_override, bias_stride, cls)) return rc;
+    if (int rc = build_desc(d, in, out, N, Di, Hi, Wi, ldo, res, res_mode, bias_override, bias_stride, cls, out_plain_f32)) return rc;
     if (int rc = launch_conv(d, dtype, s)) return rc;
   }
   return 0;
 }
 
 int ConvLayer::run_then_1x1(const ConvLayer& next, const void* in, void* mid, int ldmid, void* out2, int ldo2, int N, int Di, int Hi,
-                            int Wi, bool allow_fuse, bool* fused, hipStream_t s) const {
+                            int Wi, bool allow_fuse, bool* fused, hipStream_t s, bool out2_plain_f32) const {
   if (fused) *fused = false;
   const ConvGeom& ng = next.g;
   const bool is1x1 = !ng.transposed && ng.KD == 1 && ng.KH == 1 && ng.KW == 1 && ng.sd == 1 && ng.sh == 1 && ng.sw == 1 &&
@@ -298,7 +298,7 @@ int ConvLayer::run_then_1x1(const ConvLayer& next, const void* in, void* mid, in
   if (int rc = run(in, mid, N, Di, Hi, Wi, ldmid, nullptr, RES_NONE, nullptr, 0, s)) return rc;
   int Do, Ho, Wo;
   out_dims(Di, Hi, Wi, Do, Ho, Wo);
-  return next.run(mid, out2, N, Do, Ho, Wo, ldo2, nullptr, RES_NONE, nullptr, 0, s);
+  return next.run(mid, out2, N, Do, Ho, Wo, ldo2, nullptr, RES_NONE, nullptr, 0, s, out2_plain_f32);
 }
 
 int UpConvLayer::init(int dtype, int Cin, int Cout_, const float* w, const float* bias_h, int act_, float slope_) {

@@ -48,7 +48,6 @@ struct ConvLayer {
   float* bias = nullptr;         // [Cout_pad] fp32 or null
   std::vector<PackedConv> packs; // 1, or 8 for transposed
   std::vector<void*> owned;      // device allocations to free
-  mutable bool out_plain_f32 = false;    // (set per run by the owner) bf16x3 layers only: the output tensor is plain fp32 (for what gathers from it), see ConvDesc::out_f32
 
   // weights: [Cout][Cin][KD][KH][KW] (or [Cin][Cout][3][3][3] when transposed), optional per-Cout scale/shift
   // (folded BN) and bias.  Cin_pad: physical channel count of the input tensor.
@@ -58,15 +57,17 @@ struct ConvLayer {
 
   // Run on input [N][Di][Hi][Wi][Cin_pad] -> output [N][Do][Ho][Wo][ldo] (+ch offset via out pointer).
   // res: optional residual with the output's layout.  bias_override/bias_stride: per-sample bias.
+  // out_plain_f32 (bf16x3 layers only): the output tensor is plain fp32 (for what gathers from it), see ConvDesc::out_f32
   int run(const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res, int res_mode,
-          const float* bias_override, int bias_stride, hipStream_t s) const;
+          const float* bias_override, int bias_stride, hipStream_t s, bool out_plain_f32 = false) const;
   void out_dims(int Di, int Hi, int Wi, int& Do, int& Ho, int& Wo) const;
   // this conv followed by `next` (a 1x1, stride 1): one fused launch writing only out2 when the kernel selection allows it
-  // (*fused = true; `mid` is then NOT written), otherwise the two layers one after the other through `mid`.
+  // (*fused = true; `mid` is then NOT written), otherwise the two layers one after the other through `mid`.  out2_plain_f32: `next`'s
+  // out_plain_f32.
   int run_then_1x1(const ConvLayer& next, const void* in, void* mid, int ldmid, void* out2, int ldo2, int N, int Di, int Hi, int Wi,
-                   bool allow_fuse, bool* fused, hipStream_t s) const;
+                   bool allow_fuse, bool* fused, hipStream_t s, bool out2_plain_f32 = false) const;
   int build_desc(ConvDesc& d, const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res, int res_mode,
-                 const float* bias_override, int bias_stride, int cls) const;
+                 const float* bias_override, int bias_stride, int cls, bool out_plain_f32 = false) const;
 };
 
 // PSPUpsample (x2 bilinear align_corners -> conv3x3 pad 1 + bias -> activation; pspnet.py:100-107) as a 1x1 GEMM at the low

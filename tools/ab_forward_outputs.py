@@ -1,0 +1,105 @@
+"""Every output array of a fixed list of AdaPoseNet calls on the golden inputs and seeded weights, written to an .npz: run it in two trees
+(each run its own process with its own built librgbm_hip.so) and compare bit for bit.
+
+usage: ab_forward_outputs.py out.npz            (in each tree)
+       ab_forward_outputs.py --compare a.npz b.npz
+
+Only the Python names both trees have are used.  Arrays are compared as bytes (view2_heads = 0 fills the view-2 outputs with NaN)."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def compare(a, b):
+    A, B = np.load(a), np.load(b)
+    if sorted(A.files) != sorted(B.files):
+        print("different call lists:", sorted(set(A.files) ^ set(B.files)))
+        return 1
+    for k in A.files:
+        if A[k].shape != B[k].shape or A[k].dtype != B[k].dtype or A[k].tobytes() != B[k].tobytes():
+            print(f"FIRST DIFFERENCE at {k}: shapes {A[k].shape} {B[k].shape}")
+            return 1
+    calls = sorted({k.rsplit(" | ", 1)[0] for k in A.files})
+    print(f"all equal: {len(A.files)} arrays of {len(calls)} calls\n" + "\n".join(calls))
+    return 0
+
+
+def main(path):
+    import torch
+    from rgbmanip_amd import synth
+    from rgbmanip_amd.adapose import AdaPoseNet
+    out = {}
+    sd = synth.adapose_state_dict(seed=0, prefix="module.")
+    inputs = {B: synth.adapose_inputs(B, seed=0) for B in (1, 2, 4)}      # B = 2: the batch of tests/golden/adapose_b2*.npz
+
+    def put(name, pred):
+        torch.cuda.synchronize()
+        for k, v in pred.items():
+            out[f"{name} | {k}"] = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+    def call(net, B, **kw):
+        i = inputs[B]
+        return net(i["img1"], i["choose1"], i["img2"], i["choose2"], i["P1"], i["P2"], i["depths"], **kw)
+
+    variants = (("plain", {}), ("dense_depth", dict(dense_depth=True)), ("dense_nocs", dict(dense_nocs=True)),
+                ("dense_depth+dense_nocs", dict(dense_depth=True, dense_nocs=True)))
+    for dt in ("bf16", "bf16x3", "fp32"):
+        for v2h in (1, 0):
+            net = AdaPoseNet(sd, dtype=dt, max_chunk_views=2, options={"view2_heads": v2h})
+            for B in (1, 2):
+                for vn, kw in variants:
+                    put(f"{dt} view2_heads={v2h} B={B} {vn}", call(net, B, **kw))
+                put(f"{dt} view2_heads={v2h} B={B} plain again", call(net, B))
+            # the forward split at the PSPNet's output
+            i = inputs[2]
+            pool = net.feature_pool(4)
+            net.features(np.concatenate([i["img1"], i["img2"]]), np.arange(4), pool)
+            put(f"{dt} view2_heads={v2h} B=2 features + forward_cached",
+                net.forward_cached(pool, [0, 1], [2, 3], i["choose1"], i["choose2"], i["P1"], i["P2"], i["depths"]))
+        net = AdaPoseNet(sd, dtype=dt, graph=True)
+        for rep in range(3):
+            put(f"{dt} graph B=1 run {rep}", call(net, 1))
+    net = AdaPoseNet(sd, dtype="bf16", split_streams=True, split_min_batch=4)
+    for rep in range(2):
+        put(f"bf16 split_streams B=4 run {rep}", call(net, 4))
+    # Dropout2d: drawn masks (two eager forwards; capture + two replays), then explicit masks, then the sequence goes on
+    for graph in (False, True):
+        net = AdaPoseNet(sd, dtype="bf16", dropout=0.1, dropout_seed=3, graph=graph)
+        for rep in range(3 if graph else 2):
+            put(f"bf16 dropout 0.1 seed 3 graph={graph} B=2 run {rep}", call(net, 2))
+            put(f"bf16 dropout 0.1 seed 3 graph={graph} B=2 run {rep} masks", {"masks": net.dropout_masks(2)})
+        masks = (np.random.default_rng(7).random((4, 320)) > 0.1).astype(np.float32) / np.float32(0.9)
+        net.set_dropout_masks(masks)
+        put(f"bf16 dropout graph={graph} explicit masks B=2", call(net, 2))
+        put(f"bf16 dropout graph={graph} explicit masks B=2 masks", {"masks": net.dropout_masks(2)})
+        put(f"bf16 dropout graph={graph} after explicit masks B=2", call(net, 2))
+        put(f"bf16 dropout graph={graph} after explicit masks B=2 masks", {"masks": net.dropout_masks(2)})
+    net = AdaPoseNet(sd, dtype="bf16")
+    net.set_dropout_masks(masks)
+    put("bf16 explicit masks on a net without dropout B=2", call(net, 2, dense_depth=True))
+    put("bf16 explicit masks on a net without dropout B=2, next forward", call(net, 2))
+    # the other chunk bodies of cost_volume(), two chunks each
+    for name, dt, kw in (("norm_mode=1", "fp32", dict(norm_mode=1)), ("norm_mode=1", "bf16x3", dict(norm_mode=1)), ("cost_impl=0", "bf16", dict(cost_impl=0)),
+                         ("cost_impl=1", "bf16", dict(cost_impl=1)), ("cost_impl=2", "bf16", dict(cost_impl=2)), ("cost_impl=2", "fp32", dict(cost_impl=2))):
+        net = AdaPoseNet(sd, dtype=dt, max_chunk_views=2, **kw)
+        put(f"{dt} {name} B=2 plain", call(net, 2))
+        put(f"{dt} {name} B=2 dense_depth", call(net, 2, dense_depth=True))
+    # stop_after through the taps it leaves behind
+    for dt in ("bf16", "bf16x3"):
+        net = AdaPoseNet(sd, dtype=dt)
+        call(net, 2, stop_after=1)
+        put(f"{dt} stop_after=1 B=2", {"feat": net.fetch(2, "feat", 4 * 224 * 224 * 32), "layer4": net.fetch(2, "layer4", 4 * 28 * 28 * 512)})
+        call(net, 2, stop_after=2)
+        put(f"{dt} stop_after=2 B=2", {"prob": net.fetch(2, "prob", 4 * 1024 * 24)})
+    torch.cuda.synchronize()
+    np.savez(path, **out)
+    print(f"{len(out)} arrays -> {path}")
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    main(sys.argv[1])
