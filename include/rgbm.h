@@ -63,6 +63,32 @@ typedef struct rgbm_adapose_out {   /* device fp32, shapes of the reference's ou
  *                kernels, materialised volume. */
 int rgbm_adapose_create(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype, int norm_mode);
 int rgbm_adapose_destroy(rgbm_adapose_t* h);
+
+/* The baseline network, StereoPoseNet_with_depth_baseline (lib/network_baseline.py:523-669; interface_baseline.py builds it): v5's PSPNet
+ * and point heads, with the plane-sweep cost volume and the depth-guided fusion replaced by ViewFusion(32, 4 heads, depth 4)
+ * (lib/fusion.py) between the two views' gathered rows and a per-point depth_head (32 -> 64 -> 32 -> 1, ReLUs).  DESIGN.md section 5m.
+ * rgbm_adapose_create_baseline: the same handle type from a baseline state dict (img_extractor.*, instance_color, nocs_head,
+ *   view_fusion.blocks.{0..3}.fusion{1,2}.linears.{0..3}.{weight,bias}, depth_head.{0,2,4} and, with regress_pose = 1, nocs_pts_mlp,
+ *   pose_mlp1 / pose_mlp2 and the three estimators); a missing weight is reported by name.  dtype is the PSPNet's storage type; the
+ *   attention stack, depth_head and the point heads are fp32 whatever it is.
+ *   On such a handle rgbm_adapose_workspace_bytes, rgbm_adapose_forward(_ex) and rgbm_adapose_fetch work: the arguments are unchanged,
+ *   P1 / P2 / depths are not read (the reference ignores them) and may be NULL; with regress_pose = 0 the six r / t / s outputs are NaN.
+ *   Options view2_heads (0: view 2's nocs_head, depth_head, pose branch and the last block's fusion2 are skipped and its five outputs
+ *   are NaN; its rows still feed every block's keys), max_chunk (the attention stack runs max_chunk / 2 poses at a time), stem, upconv
+ *   and fuse_final are honoured; the cost-volume options (cost_impl, sparse_tail, sparse_dec, sweep_f16, igemm_conv6) are errors.
+ *   rgbm_adapose_fetch also serves "fused1" / "fused2" [B][P][32].  Refused, with nothing launched: rgbm_adapose_forward_dense /
+ *   _forward_maps, rgbm_adapose_set_dropout with p > 0 and _set_dropout_masks, the feature-cache calls, rgbm_adapose_forward_graph.
+ * rgbm_view_fusion: the attention stack alone with the handle's weights.  x1 / x2 [B][P][32] fp32 (the two views' rows, point-major) ->
+ *   y1 / y2 [B][P][32]; P a multiple of 32 in [32, 4096], 1 <= B <= 65535, 16-byte aligned buffers, outputs distinct from inputs.  All
+ *   arithmetic is fp32 (q k^T on the fp32 matrix pipe, the rest FMAs); keys are walked in tiles with a running maximum and sum, so no score
+ *   reaches memory and scores of +-200 are exact to fp32.  A pose's result does not depend on B and is the same bytes on every call.
+ *   scratch: rgbm_view_fusion_scratch_bytes(B, P) bytes (ten [B][P][32] fp32 buffers), 16-byte aligned, contents irrelevant.
+ * rgbm_depth_head: x [n_rows][32] fp32 -> out [n_rows] fp32 with the handle's depth_head. */
+int rgbm_adapose_create_baseline(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype, int regress_pose);
+int rgbm_view_fusion(rgbm_adapose_t* h, const float* x1, const float* x2, int B, int P, float* y1, float* y2, void* scratch,
+                     size_t scratch_bytes, void* stream);
+int rgbm_view_fusion_scratch_bytes(int B, int P, size_t* bytes);
+int rgbm_depth_head(rgbm_adapose_t* h, const float* x, int64_t n_rows, float* out, void* stream);
 /* views per cost-volume chunk (default 512 = batch 256 in one chunk); bounds the workspace */
 int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views);
 /* options: "max_chunk" (views per cost-volume chunk), "fuse_final" (bf16 only; 1 [default] = PSPNet's final 1x1 runs inside

@@ -103,6 +103,10 @@ SIGNATURES = {
     "rgbm_version": (_i, []),
     "rgbm_last_error": (C.c_char_p, []),
     "rgbm_adapose_create": (_i, [C.POINTER(_vp), _i, C.POINTER(WeightDesc), _i, _i, _i]),
+    "rgbm_adapose_create_baseline": (_i, [C.POINTER(_vp), _i, C.POINTER(WeightDesc), _i, _i, _i]),
+    "rgbm_view_fusion": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "rgbm_view_fusion_scratch_bytes": (_i, [_i, _i, C.POINTER(_sz)]),
+    "rgbm_depth_head": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "rgbm_adapose_destroy": (_i, [_vp]),
     "rgbm_adapose_set_chunk": (_i, [_vp, _i]),
     "rgbm_adapose_set_option": (_i, [_vp, C.c_char_p, _i]),

@@ -26,8 +26,24 @@ class AdaPoseNet:
     def __init__(self, state_dict, dtype: str = "fp32", device: int = 0, max_chunk_views: int | None = None,
                  cost_impl: int | None = None, sparse_tail: int | None = None, options: dict | None = None,
                  norm_mode: int | str = 0, poison_workspace: bool = False, graph: bool = False, graph_max_batch: int = 32,
-                 split_streams: bool | int = False, split_min_batch: int = 128, dropout: float = 0.0, dropout_seed: int = 0):
+                 split_streams: bool | int = False, split_min_batch: int = 128, dropout: float = 0.0, dropout_seed: int = 0,
+                 arch: str = "v5", regress_pose: bool = True):
         self.lib = _lib.load()
+        # arch "baseline": the reference's StereoPoseNet_with_depth_baseline (lib/network_baseline.py:523-669) from its state dict - v5's
+        # PSPNet and point heads, the cost volume replaced by the cross-view attention stack and depth_head.
+        # regress_pose=False (baseline only): no pose branch; forward returns the reference's four keys.  hipGraph replay, Dropout2d,
+        # per-sample BatchNorm3d, the dense maps and the feature cache are not implemented for it.
+        if arch not in ("v5", "baseline"):
+            raise ValueError(f"arch must be 'v5' or 'baseline', got {arch!r}")
+        self.arch = arch
+        self.regress_pose = bool(regress_pose)
+        if arch == "baseline":
+            for key, on in (("graph", graph), ("dropout", dropout), ("norm_mode", norm_mode not in (0, "eval")), ("cost_impl", cost_impl is not None),
+                            ("sparse_tail", sparse_tail is not None)):
+                if on:
+                    raise _lib.RgbmError(f"AdaPoseNet(arch='baseline'): {key} is not implemented for the baseline network")
+        elif not regress_pose:
+            raise ValueError("regress_pose=False exists for arch='baseline' only")
         # graph: forwards of at most `graph_max_batch` poses are replayed from a hipGraph captured per batch size
         # (rgbm_adapose_forward_graph): static input / output / workspace buffers per batch size, one hipGraphLaunch instead of ~150
         # launches — the small-batch deployment path (interface_v5.py:213-227 calls the network per env; cfg/task/open_cabinet.yaml
@@ -75,8 +91,12 @@ class AdaPoseNet:
         # norm_mode: 0 / "eval" = BatchNorm3d with running statistics (default); 1 / "per_sample" = the reference's as-shipped
         # train-mode statistics at batch 1 (every view normalised with its own volume's mean / variance)
         self.norm_mode = {"eval": 0, "per_sample": 1}.get(norm_mode, norm_mode)
-        _lib.check(self.lib.rgbm_adapose_create(C.byref(self._h), device, arr, len(descs), self.dtype, int(self.norm_mode)),
-                   "rgbm_adapose_create")
+        if arch == "baseline":
+            _lib.check(self.lib.rgbm_adapose_create_baseline(C.byref(self._h), device, arr, len(descs), self.dtype, int(self.regress_pose)),
+                       "rgbm_adapose_create_baseline")
+        else:
+            _lib.check(self.lib.rgbm_adapose_create(C.byref(self._h), device, arr, len(descs), self.dtype, int(self.norm_mode)),
+                       "rgbm_adapose_create")
         if max_chunk_views:
             _lib.check(self.lib.rgbm_adapose_set_chunk(self._h, int(max_chunk_views)), "rgbm_adapose_set_chunk")
         if cost_impl is not None:
@@ -251,6 +271,39 @@ class AdaPoseNet:
                                                     _lib.ptr(P1), _lib.ptr(P2), _lib.ptr(dep), C.c_void_p(ws_ptr), ws_bytes,
                                                     C.byref(o), stop_after, _lib.stream_ptr(stream)), "rgbm_adapose_forward")
         self._last = (img1, img2, ch1, ch2, P1, P2, dep)     # keep inputs alive until the stream has consumed them
+        if self.arch == "baseline" and not self.regress_pose:      # the reference's four keys (network_baseline.py:667-670)
+            return {k: out[k] for k in ("view1_nocs", "view2_nocs", "view1_depth", "view2_depth")}
+        return out
+
+    def view_fusion(self, x1, x2, stream=None):
+        """The attention stack alone (rgbm_view_fusion) with this net's weights: rows x1 / x2 [B, P, 32] (point-major; read as float32),
+        P a multiple of 32 in [32, 4096] -> (y1, y2) [B, P, 32] float32 CUDA."""
+        a = torch.as_tensor(x1).to(device=self.device, dtype=torch.float32).contiguous()
+        b = torch.as_tensor(x2).to(device=self.device, dtype=torch.float32).contiguous()
+        if a.dim() != 3 or a.shape[2] != 32 or b.shape != a.shape or a.shape[0] < 1 or a.shape[1] % 32 or not 32 <= a.shape[1] <= 4096:
+            raise ValueError(f"view_fusion: x1 / x2 [B, P, 32] with P a multiple of 32 in [32, 4096], got {tuple(a.shape)} and {tuple(b.shape)}")
+        B, P = int(a.shape[0]), int(a.shape[1])
+        nb = C.c_size_t()
+        _lib.check(self.lib.rgbm_view_fusion_scratch_bytes(B, P, C.byref(nb)), "rgbm_view_fusion_scratch_bytes")
+        scratch = torch.empty(nb.value // 4, dtype=torch.float32, device=self.device)
+        y1, y2 = torch.empty_like(a), torch.empty_like(a)
+        if stream is not None:
+            for t in (scratch, y1, y2, a, b):
+                t.record_stream(stream)
+        _lib.check(self.lib.rgbm_view_fusion(self._h, _lib.ptr(a), _lib.ptr(b), B, P, _lib.ptr(y1), _lib.ptr(y2), _lib.ptr(scratch), nb.value,
+                                             _lib.stream_ptr(stream)), "rgbm_view_fusion")
+        return y1, y2
+
+    def depth_head(self, x, stream=None):
+        """depth_head alone (rgbm_depth_head) with this net's weights: rows x [..., 32] -> [...] float32 CUDA."""
+        t = torch.as_tensor(x).to(device=self.device, dtype=torch.float32).contiguous()
+        if t.dim() < 2 or t.shape[-1] != 32 or t.numel() == 0:
+            raise ValueError(f"depth_head: x [..., 32], got {tuple(t.shape)}")
+        out = torch.empty(t.shape[:-1], dtype=torch.float32, device=self.device)
+        if stream is not None:
+            t.record_stream(stream)
+            out.record_stream(stream)
+        _lib.check(self.lib.rgbm_depth_head(self._h, _lib.ptr(t), t.numel() // 32, _lib.ptr(out), _lib.stream_ptr(stream)), "rgbm_depth_head")
         return out
 
     def dense_workspace_bytes(self, B: int) -> int:
@@ -614,6 +667,48 @@ def cloud_pack(fused1, keep1, Kcrop1, E1, fused2=None, keep2=None, Kcrop2=None, 
                                        _lib.ptr(E2d), n, S, cap, _lib.ptr(cloud), _lib.ptr(index), _lib.ptr(count), _lib.stream_ptr(stream)),
                    "rgbm_cloud_pack")
     return cloud, index, count
+
+
+def view_fusion(net, x1, x2, stream=None):
+    """`AdaPoseNet.view_fusion`: the attention stack of a baseline `net` on rows x1 / x2 [B, P, 32] -> (y1, y2) float32 CUDA."""
+    return net.view_fusion(x1, x2, stream=stream)
+
+
+def depth_head(net, x, stream=None):
+    """`AdaPoseNet.depth_head`: depth_head of a baseline `net` on rows x [..., 32] -> [...] float32 CUDA."""
+    return net.depth_head(x, stream=stream)
+
+
+def view_fusion_ref(state_dict, x1, x2, prefix: str = "view_fusion.", stats: dict | None = None):
+    """float64 numpy twin of `view_fusion` (tests, documentation): lib/fusion.py:11-82 as network_baseline.py:631 calls it (no mask, no
+    position embedding, no dropout).  state_dict: the baseline net's (numpy or torch values, optional `module.` prefix); rows x1 / x2
+    [B, P, 32] -> (y1, y2) [B, P, 32] float64.  Both attentions of a block read the block's inputs.  stats (optional dict) receives
+    `rowmax` (mean largest probability per row), `score_absmax`, `score_min` and `score_max` per attention, fusion1 then fusion2 of every block."""
+    sd = {}
+    for k, v in state_dict.items():
+        k = k[7:] if k.startswith("module.") else k
+        if k.startswith(prefix):
+            sd[k[len(prefix):]] = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+    x1, x2 = np.asarray(x1, dtype=np.float64), np.asarray(x2, dtype=np.float64)
+    B, P, _ = x1.shape
+
+    def attend(xq, xkv, p):
+        lin = lambda i, x: x @ sd[f"{p}.linears.{i}.weight"].T + sd[f"{p}.linears.{i}.bias"]
+        q, k, v = (lin(i, x).reshape(B, P, 4, 8).transpose(0, 2, 1, 3) for i, x in ((0, xq), (1, xkv), (2, xkv)))
+        s = q @ k.transpose(0, 1, 3, 2) / np.sqrt(8.0)                     # [B, 4, P, P]
+        e = np.exp(s - s.max(axis=-1, keepdims=True))
+        pr = e / e.sum(axis=-1, keepdims=True)
+        if stats is not None:
+            stats.setdefault("rowmax", []).append(float(pr.max(axis=-1).mean()))
+            stats.setdefault("score_absmax", []).append(float(np.abs(s).max()))
+            stats.setdefault("score_min", []).append(float(s.min()))
+            stats.setdefault("score_max", []).append(float(s.max()))
+        return lin(3, (pr @ v).transpose(0, 2, 1, 3).reshape(B, P, 32))
+    for blk in range(4):
+        y1 = attend(x1, x2, f"blocks.{blk}.fusion1") + x1
+        y2 = attend(x2, x1, f"blocks.{blk}.fusion2") + x2
+        x1, x2 = y1, y2
+    return x1, x2
 
 
 def nocs_map(net, feat, stream=None):

@@ -26,7 +26,10 @@ RL_CONTROLLER_CFG = {
 # hip_dropout, hip_dropout_seed, hip_as_shipped, hip_feature_cache (default False: keep the PSPNet feature map of every frame of the
 # controller's view queue across steps; refused together with hip_dropout / hip_as_shipped; "content": the same for estimate() /
 # estimate_device(), crops recognised by a device-side fingerprint), hip_feature_cache_records (default 0: two records per pose)
-# `name`: "adapose_v5" (every shipped cfg/pose_estimator/*.yaml) or "adapose_v4" (train.py:234-236 dispatches it to AdaPoseEstimator_v4)
+# `name`: "adapose_v5" (every shipped cfg/pose_estimator/*.yaml), "adapose_v4" (train.py:234-236 dispatches it to AdaPoseEstimator_v4) or
+# "adapose_baseline" (train.py:242-244: AdaPoseEstimator_baseline, the attention network of lib/network_baseline.py; its checkpoint is a
+# StereoPoseNet_with_depth_baseline state dict, with the pose branch only when direct_regression is true; hip_feature_cache, hip_dropout,
+# hip_as_shipped and hip_graph are refused for it)
 def adapose_cfg(task_name="one_door_cabinet", checkpoint_path="downloads/pose_estimator/one_door_cabinet.pth", load=True, name="adapose_v5"):
     return {"name": name, "task_name": task_name, "load": load, "checkpoint_path": checkpoint_path, "img_size": 224,
             "use_depth": True, "n_pts": 1024, "direct_regression": True, "real_world": False}

@@ -5,6 +5,7 @@
 // so its footprint is bounded, the second half of pose_mlp2's first layer (global feature) turned into a
 // per-view bias.  Views are ordered v = side*B + b (all view-1 images, then all view-2 images).
 #include "adapose.h"
+#include "view_fusion.h"
 
 #include <math.h>
 #include <string.h>
@@ -75,6 +76,51 @@ static int init_linear(ConvLayer& L, const StateDict& sd, const std::string& p, 
 int AdaPose::create(const StateDict& sd, int dtype_, int norm_mode_) {
   dtype = dtype_;
   norm_mode = norm_mode_;
+  if (int rc = create_backbone(sd)) return rc;
+  if (int rc = create_cost(sd)) return rc;
+  if (int rc = create_point_heads(sd, true)) return rc;
+  return create_pose(sd);
+}
+
+// The baseline network (lib/network_baseline.py:523-669): the same PSPNet and point heads, the cost volume and the depth-guided fusion
+// replaced by the cross-view attention stack and depth_head (view_fusion.hip); the pose branch only with regress_pose.
+int AdaPose::create_baseline(const StateDict& sd, int dtype_, int regress_pose_) {
+  dtype = dtype_;
+  norm_mode = 0;
+  arch = ARCH_BASELINE;
+  regress_pose = regress_pose_;
+  if (int rc = create_backbone(sd)) return rc;
+  if (int rc = create_point_heads(sd, regress_pose != 0)) return rc;
+  {
+    std::vector<float> wv((size_t)kVfWeightFloats);
+    for (int blk = 0; blk < kVfBlocks; ++blk)
+      for (int dir = 0; dir < 2; ++dir)
+        for (int l = 0; l < 4; ++l) {
+          const std::string p = "view_fusion.blocks." + std::to_string(blk) + ".fusion" + std::to_string(dir + 1) + ".linears." + std::to_string(l);
+          GET(w, p + ".weight"); GET(b, p + ".bias");
+          RGBM_REQUIRE(w->numel() == kVfDim * kVfDim && b->numel() == kVfDim, "view_fusion weight shape " + p);
+          float* dst = wv.data() + (size_t)((blk * 2 + dir) * 4 + l) * kVfLinearFloats;
+          memcpy(dst, w->data, sizeof(float) * kVfDim * kVfDim);
+          memcpy(dst + kVfDim * kVfDim, b->data, sizeof(float) * kVfDim);
+        }
+    if (upload_f32(wv.data(), wv.size(), &vf_w)) return -2;
+  }
+  {
+    std::vector<float> wd((size_t)kDepthHeadFloats);
+    static const char* const names[3] = {"depth_head.0", "depth_head.2", "depth_head.4"};
+    static const int cin[3] = {32, 64, 32}, cout[3] = {64, 32, 1}, woff[3] = {kDhW0, kDhW1, kDhW2}, boff[3] = {kDhB0, kDhB1, kDhB2};
+    for (int l = 0; l < 3; ++l) {
+      GET(w, std::string(names[l]) + ".weight"); GET(b, std::string(names[l]) + ".bias");
+      RGBM_REQUIRE(w->numel() == (long long)cin[l] * cout[l] && b->numel() == cout[l], std::string("depth_head weight shape ") + names[l]);
+      memcpy(wd.data() + woff[l], w->data, sizeof(float) * cin[l] * cout[l]);
+      memcpy(wd.data() + boff[l], b->data, sizeof(float) * cout[l]);
+    }
+    if (upload_f32(wd.data(), wd.size(), &dh_w)) return -2;
+  }
+  return regress_pose ? create_pose(sd) : 0;
+}
+
+int AdaPose::create_backbone(const StateDict& sd) {
   const int E = dtype_chunk(dtype);
   img_cpad = E;                              // RGB padded to one 16-byte chunk
   const std::string fe = "img_extractor.feats.";
@@ -128,8 +174,10 @@ int AdaPose::create(const StateDict& sd, int dtype_, int norm_mode_) {
     GET(wf, "img_extractor.final.weight"); GET(bfin, "img_extractor.final.bias");
     if (int rc = tail.init(dtype, w3->data, b3->data, s3->data[0], wf->data, bfin->data)) return rc;
   }
+  return 0;
+}
 
-
+int AdaPose::create_cost(const StateDict& sd) {
   const std::string cr = "cost_regularization.";
   const int crc[8] = {32, 8, 16, 16, 32, 32, 64, 64};
   const int crs[7] = {1, 2, 1, 2, 1, 2, 1};
@@ -203,19 +251,28 @@ int AdaPose::create(const StateDict& sd, int dtype_, int norm_mode_) {
     for (int c = 0; c < 8; ++c) for (int t = 0; t < 27; ++t) wp[t * 8 + c] = w->data[c * 27 + t];
     if (upload_f32(wp.data(), wp.size(), &wprob)) return -2;
   }
+  return 0;
+}
+
+// pts_mlp = false (the baseline network without its pose branch has no nocs_pts_mlp): layers 4 / 5 of the point kernel's table are zero
+int AdaPose::create_point_heads(const StateDict& sd, bool pts_mlp) {
   // fp32 point heads as 1x1 convs
   if (int rc = init_linear(inst, sd, "instance_color.0", 32, 64, ACT_RELU, 32, 64)) return rc;
   if (int rc = init_linear(nh[0], sd, "nocs_head.0", 64, 128, ACT_RELU, 64, 128)) return rc;
   if (int rc = init_linear(nh[1], sd, "nocs_head.2", 128, 64, ACT_RELU, 128, 64)) return rc;
   if (int rc = init_linear(nh[2], sd, "nocs_head.4", 64, 3, ACT_TANH, 64, 4)) return rc;
-  if (int rc = init_linear(npm[0], sd, "nocs_pts_mlp.0", 3, 32, ACT_RELU, 4, 32)) return rc;
-  if (int rc = init_linear(npm[1], sd, "nocs_pts_mlp.2", 32, 64, ACT_RELU, 32, 64)) return rc;
+  if (pts_mlp) {
+    if (int rc = init_linear(npm[0], sd, "nocs_pts_mlp.0", 3, 32, ACT_RELU, 4, 32)) return rc;
+    if (int rc = init_linear(npm[1], sd, "nocs_pts_mlp.2", 32, 64, ACT_RELU, 32, 64)) return rc;
+  }
   {
     // the same six layers as one LDS image for point_mlp_kernel (head_kernels.hip)
     static const char* const names[6] = {"instance_color.0", "nocs_head.0", "nocs_head.2", "nocs_head.4", "nocs_pts_mlp.0", "nocs_pts_mlp.2"};
     static const int cin[6] = {32, 64, 128, 64, 3, 32}, cout[6] = {64, 128, 64, 3, 32, 64};
     const float* w[6]; const float* b[6];
+    const std::vector<float> zeros(32 * 64, 0.f);
     for (int l = 0; l < 6; ++l) {
+      if (l >= 4 && !pts_mlp) { w[l] = b[l] = zeros.data(); continue; }
       GET(wt, std::string(names[l]) + ".weight"); GET(bt, std::string(names[l]) + ".bias");
       RGBM_REQUIRE(wt->numel() == (long long)cin[l] * cout[l] && bt->numel() == cout[l], std::string("point MLP shape ") + names[l]);
       w[l] = wt->data; b[l] = bt->data;
@@ -224,6 +281,10 @@ int AdaPose::create(const StateDict& sd, int dtype_, int norm_mode_) {
     point_mlp_pack(w, b, table.data());
     if (upload_f32(table.data(), table.size(), &pmlp_table)) return -2;
   }
+  return 0;
+}
+
+int AdaPose::create_pose(const StateDict& sd) {
   if (int rc = init_linear(pm1[0], sd, "pose_mlp1.0", 96, 128, ACT_RELU, 96, 128, nullptr, pose_dtype())) return rc;
   if (int rc = init_linear(pm1[1], sd, "pose_mlp1.2", 128, 128, ACT_RELU, 128, 128, nullptr, pose_dtype())) return rc;
   {
@@ -286,6 +347,8 @@ void AdaPose::destroy() {
   if (pm2_0_wfull) (void)hipFree(pm2_0_wfull);
   if (pmlp_table) { (void)hipFree(pmlp_table); pmlp_table = nullptr; }
   if (pm2_0_bias) (void)hipFree(pm2_0_bias);
+  if (vf_w) { (void)hipFree(vf_w); vf_w = nullptr; }
+  if (dh_w) { (void)hipFree(dh_w); dh_w = nullptr; }
   for (int h = 0; h < 3; ++h) for (int l = 0; l < 3; ++l) { if (head_w[h][l]) (void)hipFree(head_w[h][l]); if (head_b[h][l]) (void)hipFree(head_b[h][l]); }
 }
 
@@ -308,6 +371,11 @@ bool AdaPose::sparse_tail_active(bool dense) const {
 
 bool AdaPose::sparse_active(bool dense) const {
   return sparse_dec != 0 && sparse_tail_active(dense) && sweep_w != nullptr && !(g_debug_flags & DBG_TILE_CONV0);
+}
+
+int AdaPose::chunk_poses(int B) const {
+  const int cap = max_chunk / 2 > 0 ? max_chunk / 2 : 1;
+  return B < cap ? B : cap;
 }
 
 int AdaPose::chunk_views(int V) const {
@@ -368,6 +436,16 @@ int AdaPose::plan(int B, Arena& A, Buffers& bf) const {
   bf.u2 = A.alloc((size_t)V * f2 * 64 * es);
   bf.u3 = A.alloc((size_t)V * f1 * 64 * es);
   A.release(m0);
+  bf.fused = nullptr; bf.vf_scratch = nullptr;
+  if (arch == ARCH_BASELINE) {
+    // ---- phase B of the baseline network: the fused rows of both views and the attention stack's scratch for one chunk of poses ----
+    bf.fused = (float*)A.alloc(VP * 32 * 4);
+    bf.vf_scratch = A.alloc(view_fusion_scratch_bytes(chunk_poses(B), P));
+    bf.vol = bf.bn_scratch = bf.u7 = bf.u9 = bf.u11 = nullptr;
+    for (auto& c : bf.c) c = nullptr;
+    A.release(m0);
+    return 0;
+  }
   // ---- phase B: cost volume, per chunk of views ----
   const int Vc = chunk_views(V);
   const int D = n_depth;
@@ -625,6 +703,9 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   RGBM_REQUIRE(call.depth_map != nullptr || call.conf_map == nullptr, "forward_maps: conf_map without depth_map");
   RGBM_REQUIRE(call.nocs_map == nullptr || pmlp_table != nullptr, "forward_maps: no point MLP table");
   RGBM_REQUIRE(B > 0, "batch");
+  RGBM_REQUIRE(arch != ARCH_BASELINE || !(call.dense || call.depth_map || call.conf_map || call.nocs_map),
+               "baseline network: the dense / maps forwards are not implemented (they read the cost volume this network does not have)");
+  RGBM_REQUIRE(arch != ARCH_BASELINE || call.dropout == Dropout::None, "baseline network: Dropout2d is not implemented");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
   const size_t need = workspace_bytes(B);
@@ -637,7 +718,11 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   hipStream_t s = call.stream;
 
   // ---- stage inputs: views = [view1 batch ; view2 batch] ----
-  if (int rc = launch_stage_in(P1, P2, choose1, choose2, bf.Pviews, bf.choose, B, n_pts, s)) return rc;
+  // the baseline network ignores the projections and the depth planes (network_baseline.py:609-669 never reads them): they may be null
+  if (arch == ARCH_BASELINE) {
+    RGBM_CHECK_HIP(hipMemcpyAsync(bf.choose, choose1, (size_t)B * n_pts * sizeof(int), hipMemcpyDeviceToDevice, s));
+    RGBM_CHECK_HIP(hipMemcpyAsync(bf.choose + (size_t)B * n_pts, choose2, (size_t)B * n_pts * sizeof(int), hipMemcpyDeviceToDevice, s));
+  } else if (int rc = launch_stage_in(P1, P2, choose1, choose2, bf.Pviews, bf.choose, B, n_pts, s)) return rc;
   // Dropout2d: masks loaded for this forward (rgbm_adapose_set_dropout_masks), or drawn for poses counter .. counter + B - 1
   if (call.dropout != Dropout::None) {
     const bool loaded = call.dropout == Dropout::Loaded;
@@ -647,12 +732,60 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
       if (int rc = launch_dropout_masks(drop_masks, drop_state, B, drop_p, drop_seed, call.dropout == Dropout::Draw ? 1 : 0, s)) return rc;
   }
   if (int rc = pspnet(bf, V, img1, img2, call)) return rc;
-  if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
+  if (arch != ARCH_BASELINE)
+    if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
   // bf16x3 nets: everything that GATHERS from the feature map (plane sweep, point heads) reads a plain fp32 copy of it
   if (dtype == BF16X3 && !feat_f32_only())
     if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * S * S * 32, s)) return rc;
   if (call.stop_after == 1) return 0;
+  if (arch == ARCH_BASELINE) return heads_baseline(bf, B, out, call);
   return heads(bf, B, depths, out, call);
+}
+
+// Everything behind the PSPNet of the baseline network (network_baseline.py:617-669): the gathered rows feed the NOCS branch as in v5 and,
+// untouched, the attention stack; depth_head and the pose branch read the fused rows.
+int AdaPose::heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call) const {
+  const int V = 2 * B, P = n_pts, S = img;
+  hipStream_t s = call.stream;
+  const void* featg = bf.feat;
+  int fdt = dtype;
+  if (dtype == BF16X3) { featg = bf.featf; fdt = F32; }
+  if (feat_f16()) fdt = F16;
+  const int Vh = view2_heads ? V : B;
+  RGBM_REQUIRE(pmlp_table != nullptr && ((long long)Vh * P) % 64 == 0, "baseline network: the point MLP kernel needs a multiple of 64 points");
+  // both views' rows: view 2's are every block's keys even without its heads
+  if (int rc = launch_gather_points(fdt, featg, bf.choose, bf.X0, V, P, S * S, 32, s)) return rc;
+  PointMlpDesc pd{};
+  pd.table = pmlp_table; pd.feat = featg; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = P; pd.HW = S * S;
+  pd.N = (long long)Vh * P;
+  if (int rc = launch_point_mlp(fdt, pd, s)) return rc;
+  // the attention stack, a chunk of poses at a time (max_chunk views = max_chunk / 2 poses): a pose's rows do not depend on its chunk
+  const size_t view2 = (size_t)B * P * 32;
+  const int Bc0 = chunk_poses(B);
+  for (int b0 = 0; b0 < B; b0 += Bc0) {
+    const int Bc = B - b0 < Bc0 ? B - b0 : Bc0;
+    const size_t o = (size_t)b0 * P * 32;
+    if (int rc = launch_view_fusion(vf_w, bf.X0 + o, bf.X0 + view2 + o, Bc, P, bf.fused + o, bf.fused + view2 + o, bf.vf_scratch,
+                                    view_fusion_scratch_bytes(Bc0, P), view2_heads ? 2 : 1, s)) return rc;
+  }
+  if (call.stop_after == 2) return 0;
+  // depth_head on the fused rows; the same rows are channels 0..31 of the pose feature (network_baseline.py:633-641)
+  if (int rc = launch_depth_head(dh_w, bf.fused, (long long)Vh * P, bf.depth, regress_pose ? bf.PF96 : nullptr, 96, s)) return rc;
+  if (regress_pose)
+    if (int rc = pose_branch(bf, Vh, call)) return rc;
+  float* const on[2] = {out.nocs1, out.nocs2};
+  float* const od[2] = {out.depth1, out.depth2};
+  float* const orr[2] = {out.r1, out.r2};
+  float* const ot[2] = {out.t1, out.t2};
+  float* const os[2] = {out.s1, out.s2};
+  if (int rc = launch_stage_out(bf.nocs4, bf.depth, bf.R, bf.tv, bf.sv, on, od, orr, ot, os, B, P, view2_heads, s)) return rc;
+  if (!regress_pose)      // no pose branch: the six r / t / s outputs are NaN
+    for (int v = 0; v < 2; ++v) {
+      if (int rc = launch_fill_nan(orr[v], (long long)B * 9, s)) return rc;
+      if (int rc = launch_fill_nan(ot[v], (long long)B * 3, s)) return rc;
+      if (int rc = launch_fill_nan(os[v], (long long)B * 3, s)) return rc;
+    }
+  return 0;
 }
 
 int AdaPose::nocs_map_of(const float* feat_f32, long long pixels, float* nocs_map, hipStream_t s) const {
@@ -697,6 +830,26 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
 
   // ---- depth-guided fusion + pose regression (network_v5.py:457-508) ----
   if (int rc = launch_fuse_points(fdt, featg, bf.homog, depths, bf.choose, bf.prob, bf.PF96, V, B, P, D, S, S, 96, 0, s, Vh)) return rc;
+  if (int rc = pose_branch(bf, Vh, call)) return rc;
+
+  // ---- outputs (fp32, reference shapes); view2_heads = 0: the view-2 outputs are filled with NaN, so that a consumer of one fails
+  // loudly instead of reading stale numbers ----
+  {
+    float* const on[2] = {out.nocs1, out.nocs2};
+    float* const od[2] = {out.depth1, out.depth2};
+    float* const orr[2] = {out.r1, out.r2};
+    float* const ot[2] = {out.t1, out.t2};
+    float* const os[2] = {out.s1, out.s2};
+    if (int rc = launch_stage_out(bf.nocs4, bf.depth, bf.R, bf.tv, bf.sv, on, od, orr, ot, os, B, P, view2_heads, s)) return rc;
+  }
+  return 0;
+}
+
+// pose_mlp1 -> mean -> pose_mlp2 -> mean -> the three heads + Ortho6d on the pose features PF96 of views 0 .. Vh - 1 (network_v5.py:470-508;
+// network_baseline.py:643-659 is the same code)
+int AdaPose::pose_branch(const Buffers& bf, int Vh, const Call& call) const {
+  const int P = n_pts;
+  hipStream_t s = call.stream;
   // bf16 nets: the four big per-point layers of the pose MLP run in fp16 storage (fp32 they took 1.8 ms per 512 views at
   // 78 TFLOP/s on the fp32 matrix path); PF96 is produced in fp32 by its two writers and converted once
   const int pdt = pose_dtype();
@@ -736,19 +889,7 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
   }
   float* hout[3] = {bf.r6, bf.tv, bf.sv};
   const int hdim[3] = {6, 3, 3};
-  if (int rc = launch_pose_heads_mean((const float*)bf.G256a, P, bf.pf2, bf.R, head_w, head_b, hout, hdim, Vh, s)) return rc;      // + Ortho6d -> R
-
-  // ---- outputs (fp32, reference shapes); view2_heads = 0: the view-2 outputs are filled with NaN, so that a consumer of one fails
-  // loudly instead of reading stale numbers ----
-  {
-    float* const on[2] = {out.nocs1, out.nocs2};
-    float* const od[2] = {out.depth1, out.depth2};
-    float* const orr[2] = {out.r1, out.r2};
-    float* const ot[2] = {out.t1, out.t2};
-    float* const os[2] = {out.s1, out.s2};
-    if (int rc = launch_stage_out(bf.nocs4, bf.depth, bf.R, bf.tv, bf.sv, on, od, orr, ot, os, B, P, view2_heads, s)) return rc;
-  }
-  return 0;
+  return launch_pose_heads_mean((const float*)bf.G256a, P, bf.pf2, bf.R, head_w, head_b, hout, hdim, Vh, s);      // + Ortho6d -> R
 }
 
 // ---- feature cache (feature_cache.hip, DESIGN.md "Feature cache") ----
@@ -776,6 +917,7 @@ int AdaPose::features(int V, const float* images, const int* slots, void* pool, 
                       const Call& call) const {
   hipStream_t s = call.stream;
   RGBM_REQUIRE(V > 0 && pool_records > 0, "features: views and pool records");
+  RGBM_REQUIRE(arch != ARCH_BASELINE, "baseline network: the feature cache is not implemented");
   RGBM_REQUIRE(call.dropout == Dropout::None, "features: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would change "
                "what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "features: workspace must be 256-byte, pool 16-byte aligned");
@@ -800,6 +942,7 @@ int AdaPose::forward_cached(int B, const void* pool, int pool_records, const int
                             size_t workspace_size, const Outputs& out, const Call& call) const {
   hipStream_t s = call.stream;
   RGBM_REQUIRE(B > 0 && pool_records > 0, "forward_cached: batch and pool records");
+  RGBM_REQUIRE(arch != ARCH_BASELINE, "baseline network: the feature cache is not implemented");
   RGBM_REQUIRE(call.dropout == Dropout::None, "forward_cached: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would "
                "change what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "forward_cached: workspace must be 256-byte, pool 16-byte aligned");

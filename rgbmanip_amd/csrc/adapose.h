@@ -19,6 +19,13 @@ struct Arena {
 };
 
 struct AdaPose {
+  // which network the handle holds: network_v5.py's StereoPoseNet_with_depth, or network_baseline.py's StereoPoseNet_with_depth_baseline
+  // (the cost volume and the depth-guided fusion replaced by the cross-view attention stack and depth_head: view_fusion.hip)
+  enum { ARCH_V5 = 0, ARCH_BASELINE = 1 };
+  int arch = ARCH_V5;
+  int regress_pose = 1;           // baseline only: 0 = no pose branch (the six r / t / s outputs are NaN)
+  float* vf_w = nullptr;          // baseline: the attention stack's 32 linears (view_fusion.h: kVfWeightFloats)
+  float* dh_w = nullptr;          // baseline: depth_head (kDepthHeadFloats)
   int dtype = F32;
   // storage type of the pose MLP (pose_mlp1 / pose_mlp2, network_v5.py:470-494): fp16 for the bf16 throughput mode (its
   // activations are O(1); fp16 per-point features keep 11 mantissa bits, the means over points stay fp32, and the rotation
@@ -115,6 +122,8 @@ struct AdaPose {
     void *imgpad, *c1, *lb[4], *pooled[4], *stage[4], *cat, *ups, *u1, *u2, *u3;
     void *vol, *c[7], *u7, *u9, *u11;
     void* bn_scratch;
+    float* fused;                      // baseline: the attention stack's output rows [V][P][32]
+    void* vf_scratch;                  // ... and its scratch for one chunk of poses
   };
   struct Outputs {   // device fp32, reference shapes (network_v5.py:510-515)
     float *nocs1, *nocs2;   // [B,P,3]
@@ -124,6 +133,12 @@ struct AdaPose {
   };
 
   int create(const StateDict& sd, int dtype, int norm_mode = 0);
+  int create_baseline(const StateDict& sd, int dtype, int regress_pose);
+  // the parts of a network create() / create_baseline() put together (dtype is set before)
+  int create_backbone(const StateDict& sd);
+  int create_cost(const StateDict& sd);
+  int create_point_heads(const StateDict& sd, bool pts_mlp);
+  int create_pose(const StateDict& sd);
   void destroy();
   size_t workspace_bytes(int B) const;
   // the map rules of a call (depth_map needs dense, conf_map needs depth_map, nocs_map needs the point MLP table) are checked here
@@ -146,6 +161,9 @@ struct AdaPose {
   struct FeaturePart { void* buf; size_t off, bytes; };      // a feature buffer of the workspace and its place inside a record
   int feature_parts(const Buffers& bf, FeaturePart parts[2]) const;
   int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call) const;
+  int heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call) const;
+  int pose_branch(const Buffers& bf, int Vh, const Call& call) const;
+  int chunk_poses(int B) const;      // baseline: poses per launch of the attention stack (max_chunk views)
   int layer4_index() const { return (3 * n_blocks) & 3; }      // which of the rotating buffers bf.lb holds the layer4 output (debug fetch)
 
   // exposed for layer-level tests

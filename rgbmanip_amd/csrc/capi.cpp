@@ -13,6 +13,7 @@
 #include "control.h"
 #include "conv_plan.h"
 #include "prof.h"
+#include "view_fusion.h"
 
 using namespace rgbm;
 
@@ -98,9 +99,17 @@ static int finish_call(rgbm_adapose* h, int B, const AdaPose::Call& call, int rc
   return rc;
 }
 
+static bool is_baseline(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_BASELINE; }
+
 static int forward_call(rgbm_adapose* h, const char* name, int B, const float* img1, const float* img2, const int32_t* choose1,
                         const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace, size_t workspace_bytes,
                         const rgbm_adapose_out* out, void* stream, AdaPose::Call call) {
+  if (is_baseline(h)) {      // the projections and the depth planes are not read and may be null
+    RGBM_REQUIRE(!(call.dense || call.depth_map || call.conf_map || call.nocs_map), std::string(name) + ": not implemented for the baseline network "
+                 "(the dense maps come from the cost volume, which this network does not have)");
+    if (int rc = prepare_call(h, name, B, {img1, img2, choose1, choose2, workspace, out}, stream, &call)) return rc;
+    return h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), call);
+  }
   if (int rc = prepare_call(h, name, B, {img1, img2, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
   RGBM_REQUIRE(h->drop_explicit == 0 || h->drop_explicit == B, "dropout: the masks set for the next forward are for batch " + std::to_string(h->drop_explicit));
   return finish_call(h, B, call, h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), call));
@@ -133,6 +142,47 @@ int rgbm_adapose_create(rgbm_adapose_t** h, int device, const rgbm_weight_desc* 
   return 0;
 }
 
+int rgbm_adapose_create_baseline(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype, int regress_pose) {
+  RGBM_REQUIRE(h != nullptr && w != nullptr && n_w > 0, "create_baseline arguments");
+  RGBM_REQUIRE(dtype == RGBM_F32 || dtype == RGBM_BF16 || dtype == RGBM_F16 || dtype == RGBM_BF16X3, "dtype must be 0 (fp32), 1 (bf16), 2 (fp16) or 3 (bf16x3)");
+  RGBM_REQUIRE(regress_pose == 0 || regress_pose == 1, "regress_pose: 0 or 1");
+  RGBM_CHECK_HIP(hipSetDevice(device));
+  StateDict sd;
+  for (int i = 0; i < n_w; ++i) {
+    std::string name = w[i].name;
+    if (name.rfind("module.", 0) == 0) name = name.substr(7);
+    HostTensor t;
+    t.data = w[i].data;
+    for (int d = 0; d < w[i].ndim; ++d) t.shape.push_back(w[i].shape[d]);
+    sd[name] = t;
+  }
+  rgbm_adapose* obj = new rgbm_adapose();
+  obj->device = device;
+  int rc = obj->net.create_baseline(sd, dtype, regress_pose);
+  if (rc) { obj->net.destroy(); delete obj; return rc; }
+  *h = obj;
+  return 0;
+}
+
+int rgbm_view_fusion_scratch_bytes(int B, int P, size_t* bytes) {
+  RGBM_REQUIRE(bytes && B >= 1 && P >= kVfMinPoints && P <= kVfMaxPoints && P % 32 == 0, "view_fusion_scratch_bytes: B >= 1, P a multiple of 32 in [32, 4096]");
+  *bytes = view_fusion_scratch_bytes(B, P);
+  return 0;
+}
+
+int rgbm_view_fusion(rgbm_adapose_t* h, const float* x1, const float* x2, int B, int P, float* y1, float* y2, void* scratch,
+                     size_t scratch_bytes, void* stream) {
+  RGBM_REQUIRE(h && x1 && x2 && y1 && y2 && scratch, "view_fusion arguments");
+  RGBM_REQUIRE(h->net.vf_w != nullptr, "view_fusion: the handle holds no attention stack (rgbm_adapose_create_baseline builds one)");
+  return launch_view_fusion(h->net.vf_w, x1, x2, B, P, y1, y2, scratch, scratch_bytes, 2, (hipStream_t)stream);
+}
+
+int rgbm_depth_head(rgbm_adapose_t* h, const float* x, int64_t n_rows, float* out, void* stream) {
+  RGBM_REQUIRE(h && x && out && n_rows > 0, "depth_head arguments");
+  RGBM_REQUIRE(h->net.dh_w != nullptr, "depth_head: the handle holds no depth_head (rgbm_adapose_create_baseline builds one)");
+  return launch_depth_head(h->net.dh_w, x, (long long)n_rows, out, nullptr, 0, (hipStream_t)stream);
+}
+
 int rgbm_adapose_destroy(rgbm_adapose_t* h) {
   if (!h) return 0;
   for (auto& g : h->graphs) drop_graph(g);
@@ -151,6 +201,9 @@ int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views) {
 int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value) {
   RGBM_REQUIRE(h && key, "set_option arguments");
   const std::string k = key;
+  if (is_baseline(h))
+    for (const char* cv : {"cost_impl", "sparse_tail", "sparse_dec", "sweep_f16", "igemm_conv6"})
+      RGBM_REQUIRE(k != cv, "option " + k + " belongs to the cost volume, which the baseline network does not have");
   if (k == "max_chunk") { RGBM_REQUIRE(value > 0, "max_chunk"); h->net.max_chunk = value; }
   else if (k == "igemm_conv6") { RGBM_REQUIRE(value == 0 || value == 1, "igemm_conv6"); h->net.igemm_conv6 = value; }
   else if (k == "fuse_final") { RGBM_REQUIRE(value == 0 || value == 1, "fuse_final"); h->net.fuse_final = value; }
@@ -168,6 +221,7 @@ int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value) {
 
 int rgbm_adapose_set_dropout(rgbm_adapose_t* h, float p, uint64_t seed) {
   RGBM_REQUIRE(h && (p == 0.f || (p > 0.f && p < 1.f)), "set_dropout: p must be 0 (off) or lie in (0, 1)");
+  RGBM_REQUIRE(!(is_baseline(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the baseline network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (!h->net.drop_state) RGBM_CHECK_HIP(hipMalloc(&h->net.drop_state, 2 * sizeof(unsigned long long)));
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // every forward issued before this call has drawn its masks
@@ -191,6 +245,7 @@ int rgbm_adapose_dropout_masks(rgbm_adapose_t* h, int B, float* out_dev) {
 
 int rgbm_adapose_set_dropout_masks(rgbm_adapose_t* h, int B, const float* masks_dev) {
   RGBM_REQUIRE(h && masks_dev && B > 0, "set_dropout_masks arguments");
+  RGBM_REQUIRE(!is_baseline(h), "set_dropout_masks: Dropout2d is not implemented for the baseline network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (int rc = ensure_dropout_capacity(h, B)) return rc;
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // no forward in flight reads the buffer any more
@@ -285,18 +340,21 @@ int rgbm_cloud_pack(const float* fused1, const uint8_t* keep1, const double* Kcr
 
 int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes) {
   RGBM_REQUIRE(h && bytes, "feature_bytes arguments");
+  RGBM_REQUIRE(!is_baseline(h), "feature_bytes: the feature cache is not implemented for the baseline network");
   *bytes = h->net.feature_bytes();
   return 0;
 }
 
 int rgbm_adapose_features_workspace_bytes(rgbm_adapose_t* h, int V, size_t* bytes) {
   RGBM_REQUIRE(h && bytes && V > 0, "features_workspace_bytes arguments");
+  RGBM_REQUIRE(!is_baseline(h), "features_workspace_bytes: the feature cache is not implemented for the baseline network");
   *bytes = h->net.features_workspace_bytes(V);
   return 0;
 }
 
 int rgbm_adapose_features(rgbm_adapose_t* h, int V, const float* img, const int32_t* slots_dev, void* pool, int pool_records,
                           void* workspace, size_t workspace_bytes, void* stream) {
+  RGBM_REQUIRE(!is_baseline(h), "features: the feature cache is not implemented for the baseline network");
   AdaPose::Call call;      // a handle with Dropout2d on (or masks loaded) is refused by the net
   if (int rc = prepare_call(h, "features", 0, {img, slots_dev, pool, workspace}, stream, &call)) return rc;
   return h->net.features(V, img, slots_dev, pool, pool_records, workspace, workspace_bytes, call);
@@ -309,6 +367,7 @@ int rgbm_crop_fingerprint(const float* img, int V, int n_words, uint64_t* keys_o
 int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int pool_records, const int32_t* slot1_dev,
                                 const int32_t* slot2_dev, const int32_t* choose1, const int32_t* choose2, const float* P1, const float* P2,
                                 const float* depths, void* workspace, size_t workspace_bytes, const rgbm_adapose_out* out, void* stream) {
+  RGBM_REQUIRE(!is_baseline(h), "forward_cached: the feature cache is not implemented for the baseline network");
   AdaPose::Call call;
   if (int rc = prepare_call(h, "forward_cached", B, {pool, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
   return h->net.forward_cached(B, pool, pool_records, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, workspace_bytes,
@@ -327,6 +386,7 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
                                size_t workspace_bytes, const rgbm_adapose_out* out, void* stream, int32_t* n_nodes, int32_t* captured) {
   if (n_nodes) *n_nodes = 0;
   if (captured) *captured = 0;
+  RGBM_REQUIRE(!is_baseline(h), "forward_graph: hipGraph replay is not implemented for the baseline network");
   AdaPose::Call call;
   // the in-library profiler records events around launches: not capturable, and a timing run wants the launches themselves
   // masks loaded by rgbm_adapose_set_dropout_masks are for one forward: not captured
@@ -419,6 +479,11 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   else if (nm == "pf96") { src = bf.PF96; cnt = V * P * 96; dt = n.pose_dtype() == BF16X3 ? BF16X3 : F32; }
   else if (nm == "pf2") { src = bf.pf2; cnt = V * 256; dt = F32; }
   else if (nm == "r6") { src = bf.r6; cnt = V * 6; dt = F32; }
+  else if (nm == "fused1" && bf.fused) { src = bf.fused; cnt = (size_t)B * P * 32; dt = F32; }
+  else if (nm == "fused2" && bf.fused) { src = bf.fused + (size_t)B * P * 32; cnt = (size_t)B * P * 32; dt = F32; }
+  if (is_baseline(h))      // the cost-volume buffers do not exist in this handle's workspace
+    RGBM_REQUIRE(nm == "feat" || nm == "fused1" || nm == "fused2" || nm == "pf96" || nm == "pf2" || nm == "r6" || nm == "layer4" || nm == "cat" ||
+                 nm == "u1" || nm == "u2", "tap '" + nm + "' does not exist in the baseline network");
   RGBM_REQUIRE(src != nullptr, "unknown intermediate name: " + nm);
   // with sparse cost regularisation c0..c5 / u7 / u9 are written only inside the chosen pixels' dependency cones (and c6 is computed
   // from them): the rest of these tensors is whatever the workspace held, so a tap of them is refused instead of returned partly stale

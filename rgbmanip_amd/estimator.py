@@ -127,10 +127,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             if cfg.get("load", False):
                 state_dict = torch.load(cfg["checkpoint_path"], map_location="cpu")      # DataParallel keys ("module.")
             else:
-                from . import synth
-                state_dict = synth.adapose_state_dict(seed=0)
+                state_dict = self._synthetic_state_dict()
                 if logger is not None:
-                    logger.warning("AdaPoseEstimator_v5: cfg.load is False -> synthetic (seeded) weights")
+                    logger.warning(f"{type(self).__name__}: cfg.load is False -> synthetic (seeded) weights")
         self.dtype = dtype or cfg.get("hip_dtype", "bf16x3")      # the fastest mode inside north_star's 1e-4 (fp32: 4x slower, bf16: 2.4x faster at 1e-2)
         # hip_graph (default off: measured, small batches are bound by their kernels, not by the ~100 launches): batches of at most
         # hip_graph_max_batch poses replay a captured hipGraph.
@@ -163,11 +162,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         options = {str(k): int(v) for k, v in dict(cfg.get("hip_options", {}) or {}).items()}
         if net is not None:
             self.view2_heads = _check_shared_net(net, self.view2_heads, drop_p, drop_seed, options)      # report what the net computes
-        self.estimator = net if net is not None else AdaPoseNet(state_dict, dtype=self.dtype, device=device,
-                                                                norm_mode=norm_mode, dropout=drop_p, dropout_seed=drop_seed,
-                                                                graph=bool(cfg.get("hip_graph", False)),
-                                                                graph_max_batch=int(cfg.get("hip_graph_max_batch", 32)),
-                                                                options={**options, "view2_heads": int(self.view2_heads)})
+        self.estimator = net if net is not None else self._build_net(state_dict, device, norm_mode, drop_p, drop_seed,
+                                                                     {**options, "view2_heads": int(self.view2_heads)})
         self._plain_views = 0                 # views the PSPNet has run on in uncached forwards
         self.frames_u8_native = 0             # frames the device paths have cropped straight from 8-bit pixels (rgbm_prepare_inputs_u8)
         self._slots = SlotFeatureCache(self.estimator, self._normalize)                 # estimate_device_indexed(..., fresh=...)
@@ -192,6 +188,16 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     @property
     def feature_cache_bypassed(self):
         return self._content.bypassed
+
+    # ------------------------------------------------------------------ the network construction (what the baseline interface overrides)
+    def _synthetic_state_dict(self):
+        from . import synth
+        return synth.adapose_state_dict(seed=0)
+
+    def _build_net(self, state_dict, device, norm_mode, drop_p, drop_seed, options):
+        return AdaPoseNet(state_dict, dtype=self.dtype, device=device, norm_mode=norm_mode, dropout=drop_p, dropout_seed=drop_seed,
+                          graph=bool(self.cfg.get("hip_graph", False)), graph_max_batch=int(self.cfg.get("hip_graph_max_batch", 32)),
+                          options=options)
 
     # ------------------------------------------------------------------ the two places where the v4 interface differs
     @property
@@ -639,3 +645,53 @@ class AdaPoseEstimator_v4(AdaPoseEstimator_v5):
     def _regressed_tail(self, pred, choose, Kcrop, E1):
         """interface_v4.py:322-325: tt = view1_t, ts = ||view1_s|| — the network's own heads, no pair median."""
         return postprocess_regressed(pred["view1_nocs"], pred["view1_r"], pred["view1_t"], pred["view1_s"], E1)[0]
+
+
+class AdaPoseEstimator_baseline(AdaPoseEstimator_v5):
+    """`pose_estimator.name: adapose_baseline` (`interface_baseline.py`, which is `interface_v5.py` with the network class changed):
+    `StereoPoseNet_with_depth_baseline(regress_pose=cfg["direct_regression"])` — v5's PSPNet and point heads, the plane-sweep cost
+    volume replaced by attention between the two views' chosen points.  Crop, upload, 8-bit frames, windows, the
+    three box tails and `hip_dtype` / `hip_prepare` / `hip_upload` / `hip_view2_heads` / `hip_options` are the code above.  What reads the
+    cost volume or is not implemented for this network raises, naming the key."""
+
+    _UNSUPPORTED = ("hip_feature_cache", "hip_dropout", "hip_as_shipped", "hip_graph")
+
+    def __init__(self, env, cfg, logger, state_dict=None, dtype=None, device=0, net=None):
+        for key in self._UNSUPPORTED:
+            if cfg.get(key, False):
+                raise ValueError(f"AdaPoseEstimator_baseline: cfg key {key} is not implemented for the baseline network")
+        if cfg.get("hip_norm_mode", "eval") not in ("eval", 0):
+            raise ValueError("AdaPoseEstimator_baseline: cfg key hip_norm_mode: the baseline network has no BatchNorm3d")
+        if net is not None and getattr(net, "arch", "v5") != "baseline":
+            raise ValueError("AdaPoseEstimator_baseline: the shared net must be an AdaPoseNet(arch='baseline')")
+        super().__init__(env, cfg, logger, state_dict=state_dict, dtype=dtype, device=device, net=net)
+
+    def _synthetic_state_dict(self):
+        from . import synth
+        return synth.baseline_state_dict(seed=0, regress_pose=bool(self.cfg["direct_regression"]))
+
+    def _build_net(self, state_dict, device, norm_mode, drop_p, drop_seed, options):
+        return AdaPoseNet(state_dict, dtype=self.dtype, device=device, options=options, arch="baseline",
+                          regress_pose=bool(self.cfg["direct_regression"]))
+
+    def _no_cost_volume(self, name):
+        raise NotImplementedError(f"AdaPoseEstimator_baseline.{name}: the dense maps come from the cost volume, which the baseline network "
+                                  "does not have")
+
+    def estimate_depth(self, *a, **k):
+        self._no_cost_volume("estimate_depth")
+
+    def estimate_depth_device(self, *a, **k):
+        self._no_cost_volume("estimate_depth_device")
+
+    def estimate_cloud(self, *a, **k):
+        self._no_cost_volume("estimate_cloud")
+
+    def estimate_cloud_device(self, *a, **k):
+        self._no_cost_volume("estimate_cloud_device")
+
+    def estimate_cloud_pose(self, *a, **k):
+        self._no_cost_volume("estimate_cloud_pose")
+
+    def estimate_cloud_pose_device(self, *a, **k):
+        self._no_cost_volume("estimate_cloud_pose_device")

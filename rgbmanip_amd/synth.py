@@ -93,8 +93,55 @@ def adapose_schema():
 
 def adapose_state_dict(seed: int = 0, prefix: str = "") -> "OrderedDict[str, np.ndarray]":
     """Synthetic checkpoint: name -> fp32 ndarray (int64 for num_batches_tracked)."""
+    return _draw_state_dict(adapose_schema(), seed, prefix)
+
+
+# Gain on the query and key projections (linears.0 / linears.1) of the baseline network's attention stack.  At torch's default init the
+# softmax rows are all but uniform (mean largest probability 0.003 against 0.001 for uniform attention at 1024 keys), which cannot tell a
+# correct softmax from none; the golden generator (tools/make_goldens.py: gen_adapose_baseline) asserts on the golden batch that the mean
+# row maximum of every block lies in [0.2, 0.9] with this constant.
+BASELINE_QK_GAIN = 4.0
+BASELINE_DEPTH_BIAS = 0.5      # added to depth_head.4.bias: depths of the golden batch around 0.5, a few rows still zeroed by the ReLU
+
+
+def baseline_schema(regress_pose: bool = True):
+    """(name, shape, kind) of StereoPoseNet_with_depth_baseline (lib/network_baseline.py:523-607) in its state_dict order: v5's PSPNet,
+    instance_color and nocs_head, then view_fusion, depth_head and - with regress_pose - the pose branch."""
+    v5 = adapose_schema()
+    by_prefix = lambda *pre: [e for e in v5 if e[0].startswith(pre)]
+    s = by_prefix("img_extractor.", "instance_color.", "nocs_head.")
+    for blk in range(4):
+        for f in (1, 2):
+            for l in range(4):
+                p = f"view_fusion.blocks.{blk}.fusion{f}.linears.{l}"
+                s.append((p + ".weight", (32, 32), "qk" if l < 2 else "w"))
+                s.append((p + ".bias", (32,), "b:32"))
+    for i, (a, b) in zip((0, 2, 4), ((32, 64), (64, 32), (32, 1))):
+        s.append((f"depth_head.{i}.weight", (b, a, 1), "w"))
+        # the last bias is shifted up: at the default draw the final ReLU zeroes every depth of the golden batch
+        s.append((f"depth_head.{i}.bias", (b,), "b:%d" % a if i < 4 else "b+:%d" % a))
+    if regress_pose:
+        s += by_prefix("nocs_pts_mlp.", "pose_mlp1.", "pose_mlp2.", "rotation_estimator.", "translation_estimator.", "size_estimator.")
+    return s
+
+
+def baseline_state_dict(seed: int = 0, regress_pose: bool = True, prefix: str = "") -> "OrderedDict[str, np.ndarray]":
+    """Synthetic checkpoint of the baseline network.  Every tensor it shares with `adapose_state_dict` is the same draw (the generator
+    is keyed by the tensor's name), so the PSPNet goldens' distribution carries over; the attention stack's query / key weights are the
+    default draw times BASELINE_QK_GAIN."""
+    return _draw_state_dict(baseline_schema(regress_pose), seed, prefix)
+
+
+def view_fusion_inputs(B: int, P: int, seed: int = 0):
+    """Rows for the attention stack alone: (x1, x2) [B, P, 32] float32, N(0, 1)."""
+    g = _rng(f"view_fusion_inputs.{B}.{P}", seed)
+    return (np.ascontiguousarray(g.normal(size=(B, P, 32)), dtype=np.float32),
+            np.ascontiguousarray(g.normal(size=(B, P, 32)), dtype=np.float32))
+
+
+def _draw_state_dict(schema, seed: int, prefix: str):
     sd = OrderedDict()
-    for name, shape, kind in adapose_schema():
+    for name, shape, kind in schema:
         g = _rng(name, seed)
         if kind == "bb":
             n = shape[2] * shape[3] * shape[0]
@@ -103,6 +150,9 @@ def adapose_state_dict(seed: int = 0, prefix: str = "") -> "OrderedDict[str, np.
             fan_in = int(np.prod(shape[1:]))
             bound = 1.0 / np.sqrt(fan_in)
             v = g.uniform(-bound, bound, size=shape)
+        elif kind == "qk":
+            bound = BASELINE_QK_GAIN / np.sqrt(shape[1])
+            v = g.uniform(-bound, bound, size=shape)
         elif kind == "wT":
             fan_in = int(shape[1] * np.prod(shape[2:]))
             bound = 1.0 / np.sqrt(fan_in)
@@ -110,6 +160,9 @@ def adapose_state_dict(seed: int = 0, prefix: str = "") -> "OrderedDict[str, np.
         elif kind.startswith("b:"):
             bound = 1.0 / np.sqrt(int(kind[2:]))
             v = g.uniform(-bound, bound, size=shape)
+        elif kind.startswith("b+:"):
+            bound = 1.0 / np.sqrt(int(kind[3:]))
+            v = g.uniform(-bound, bound, size=shape) + BASELINE_DEPTH_BIAS
         elif kind == "prelu":
             v = np.full(shape, 0.25)
         elif kind == "bn_g":

@@ -157,6 +157,82 @@ def gen_adapose(out_dir):
     return out, inp
 
 
+def gen_adapose_baseline(out_dir):
+    """The baseline network (lib/network_baseline.py) on the golden batch, and the attention stack alone on two small shapes."""
+    from models.pose_estimator.AdaPose.lib.network_baseline import StereoPoseNet_with_depth_baseline
+    from models.pose_estimator.AdaPose.lib.fusion import ViewFusion
+    from rgbmanip_amd import synth
+
+    net = StereoPoseNet_with_depth_baseline(n_cat=1, nv_pts=1024, regress_pose=True).eval()
+    sd = synth.baseline_state_dict(seed=0)
+    print("load_state_dict:", net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True))
+    B = 2
+    inp = synth.adapose_inputs(B, seed=0)
+    tin = {k: torch.from_numpy(v) for k, v in inp.items()}
+    inter = {}
+
+    def hook(name):
+        def f(mod, i, o):
+            inter.setdefault(name, o.detach())
+        return f
+    ie = net.img_extractor
+    hs = [ie.feats.conv1.register_forward_hook(hook("v1_conv1_raw")), ie.feats.maxpool.register_forward_hook(hook("v1_pool")),
+          ie.feats.layer1.register_forward_hook(hook("v1_layer1")), ie.feats.layer2.register_forward_hook(hook("v1_layer2")),
+          ie.feats.layer3.register_forward_hook(hook("v1_layer3")), ie.feats.layer4.register_forward_hook(hook("v1_layer4")),
+          ie.psp.register_forward_hook(hook("v1_psp")), ie.up_1.register_forward_hook(hook("v1_up_1")),
+          ie.up_2.register_forward_hook(hook("v1_up_2")), ie.up_3.register_forward_hook(hook("v1_up_3")),
+          ie.register_forward_hook(hook("feat1"))]
+    fused = {}
+    hs.append(net.view_fusion.register_forward_hook(lambda mod, i, o: fused.update(fused1=o[0].detach(), fused2=o[1].detach())))
+
+    def rowmax():      # mean largest probability per softmax row: fusion1 then fusion2 of every block
+        return np.array([float(f.attn.max(dim=-1).values.mean()) for blk in net.view_fusion.blocks for f in (blk.fusion1, blk.fusion2)])
+    args = (tin["img1"], tin["choose1"], tin["img2"], tin["choose2"], tin["P1"], tin["P2"], tin["depths"])
+    with torch.no_grad():
+        out = net(*args)
+        rm = rowmax()
+        out2 = net(*args)
+    for h in hs:
+        h.remove()
+    for k in out:
+        assert torch.equal(out[k], out2[k]), k
+    print("row-maximum means per attention:", rm)
+    assert (rm >= 0.2).all() and (rm <= 0.9).all(), "adjust synth.BASELINE_QK_GAIN: the golden batch's attention is too flat or too peaked"
+    save = {k: v.numpy() for k, v in out.items()}
+    save["fused1"] = fused["fused1"].transpose(1, 2).contiguous().numpy()       # [B, P, 32], point-major
+    save["fused2"] = fused["fused2"].transpose(1, 2).contiguous().numpy()
+    save["rowmax_mean"] = rm
+    for k, v in inter.items():
+        save["slice_" + k] = strided(v)
+        save["absmean_" + k] = np.array(v.abs().mean().item(), dtype=np.float64)
+    for tag, rp in (("", True), ("_nopose", False)):
+        ref_sd = StereoPoseNet_with_depth_baseline(n_cat=1, nv_pts=1024, regress_pose=rp).state_dict()
+        save["sd_keys" + tag] = np.array(list(ref_sd.keys()))
+        save["sd_shapes" + tag] = np.array(["x".join(str(d) for d in v.shape) for v in ref_sd.values()])
+    np.savez_compressed(os.path.join(out_dir, "adapose_baseline_b2.npz"), **save)
+    for k, v in out.items():
+        print(k, tuple(v.shape), float(v.abs().mean()), bool(torch.isfinite(v).all()))
+
+    # the attention stack alone: the reference module with the same constructed weights on two small shapes
+    vf = ViewFusion(embed_dim=32, num_heads=4, depth=4).eval()
+    vf.load_state_dict({k[len("view_fusion."):]: torch.from_numpy(v) for k, v in sd.items() if k.startswith("view_fusion.")}, strict=True)
+    small = {}
+    for Bs, Ps in ((3, 96), (1, 32)):
+        x1, x2 = synth.view_fusion_inputs(Bs, Ps, seed=0)
+        blocks = []
+        hb = [blk.register_forward_hook(lambda mod, i, o: blocks.append(o)) for blk in vf.blocks]
+        with torch.no_grad():
+            y1, y2 = vf(torch.from_numpy(x1).transpose(1, 2).contiguous(), torch.from_numpy(x2).transpose(1, 2).contiguous())
+        for h in hb:
+            h.remove()
+        t = f"b{Bs}_p{Ps}_"
+        small[t + "x1"], small[t + "x2"] = x1, x2
+        small[t + "y1"], small[t + "y2"] = y1.transpose(1, 2).contiguous().numpy(), y2.transpose(1, 2).contiguous().numpy()
+        for i, (o1, o2) in enumerate(blocks):
+            small[t + f"blk{i}_y1"], small[t + f"blk{i}_y2"] = o1.transpose(1, 2).contiguous().numpy(), o2.transpose(1, 2).contiguous().numpy()
+    np.savez_compressed(os.path.join(out_dir, "view_fusion_small.npz"), **small)
+
+
 def gen_adapose_trainbn(out_dir):
     """The as-shipped normalisation (interface_v5.py:39-56 never calls .eval()): the reference module in .train()
     with only its Dropout2d modules in .eval() (their masks are random), run the way the estimator runs it — ONE pose per call —
@@ -960,6 +1036,8 @@ if __name__ == "__main__":
         gen_align(out_dir)
     if "postproc_v4" in which:            # on request only: it reads the committed adapose_b2.npz and replaces cv2.resize / transforms
         gen_postproc_v4(out_dir)
+    if "adapose_baseline" in which:       # on request only
+        gen_adapose_baseline(out_dir)
     if "adapose_dropout" in which:        # last: its torch.manual_seed cannot reach the generators above
         gen_adapose_dropout(out_dir)
     print("done")
