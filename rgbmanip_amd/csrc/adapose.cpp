@@ -5,6 +5,7 @@
 // so its footprint is bounded, the second half of pose_mlp2's first layer (global feature) turned into a
 // per-view bias.  Views are ordered v = side*B + b (all view-1 images, then all view-2 images).
 #include "adapose.h"
+#include "cost3d.h"
 #include "view_fusion.h"
 
 #include <math.h>
@@ -53,16 +54,12 @@ static int bn_fold(const StateDict& sd, const std::string& p, int C, std::vector
   return 0;
 }
 
-static int init_conv3d_bn(ConvLayer& L, int dtype, const StateDict& sd, const std::string& p, int Cin, int Cout, int stride,
-                          bool transposed) {
-  GET(w, p + "conv.weight");
-  RGBM_REQUIRE(w->numel() == (long long)Cout * Cin * 27, "weight shape " + p);
-  std::vector<float> scale, shift;
-  if (int rc = bn_fold(sd, p + "bn.", Cout, scale, shift)) return rc;
+// a row of kCost3d as the generic implicit-GEMM layer sees it (k3 p1)
+static ConvGeom cost3d_geom(const Cost3dLayer& L, int act) {
   ConvGeom g;
-  g.Cin = Cin; g.Cout = Cout; g.KD = g.KH = g.KW = 3; g.sd = g.sh = g.sw = stride; g.pd = g.ph = g.pw = 1;
-  g.transposed = transposed; g.act = ACT_RELU;
-  return L.init(dtype, g, w->data, nullptr, scale.data(), shift.data(), Cin, Cout);
+  g.Cin = L.cin; g.Cout = L.cout; g.KD = g.KH = g.KW = 3; g.sd = g.sh = g.sw = L.stride; g.pd = g.ph = g.pw = 1;
+  g.transposed = L.transposed; g.act = act;
+  return g;
 }
 
 static int init_linear(ConvLayer& L, const StateDict& sd, const std::string& p, int Cin, int Cout, int act, int Cin_pad,
@@ -103,7 +100,7 @@ int AdaPose::create_baseline(const StateDict& sd, int dtype_, int regress_pose_)
           memcpy(dst, w->data, sizeof(float) * kVfDim * kVfDim);
           memcpy(dst + kVfDim * kVfDim, b->data, sizeof(float) * kVfDim);
         }
-    if (upload_f32(wv.data(), wv.size(), &vf_w)) return -2;
+    if (upload_f32(wv.data(), wv.size(), vf_w)) return -2;
   }
   {
     std::vector<float> wd((size_t)kDepthHeadFloats);
@@ -115,7 +112,7 @@ int AdaPose::create_baseline(const StateDict& sd, int dtype_, int regress_pose_)
       memcpy(wd.data() + woff[l], w->data, sizeof(float) * cin[l] * cout[l]);
       memcpy(wd.data() + boff[l], b->data, sizeof(float) * cout[l]);
     }
-    if (upload_f32(wd.data(), wd.size(), &dh_w)) return -2;
+    if (upload_f32(wd.data(), wd.size(), dh_w)) return -2;
   }
   return regress_pose ? create_pose(sd) : 0;
 }
@@ -130,7 +127,7 @@ int AdaPose::create_backbone(const StateDict& sd) {
     RGBM_REQUIRE(w1->numel() == 64 * 3 * 7 * 7, "conv1 shape");
     std::vector<float> pk;
     stem_pack(w1->data, pk);
-    if (int rc = upload_packed(pk, dtype, &stem_w)) return rc;
+    if (int rc = upload_packed(pk, dtype, stem_w)) return rc;
     // same-box A/B at batch 256 (tools/ab_option.py <dtype> stem 0 1): bf16 forward 56.58 -> 55.62 ms; split pairs 125.06 -> 124.68 ms
     // with 4-row tiles (8-row tiles: 79 KB of staging, 122.63 -> 122.91 ms)
     stem = 1;
@@ -179,69 +176,49 @@ int AdaPose::create_backbone(const StateDict& sd) {
 
 int AdaPose::create_cost(const StateDict& sd) {
   const std::string cr = "cost_regularization.";
-  const int crc[8] = {32, 8, 16, 16, 32, 32, 64, 64};
-  const int crs[7] = {1, 2, 1, 2, 1, 2, 1};
-  for (int i = 0; i < 7; ++i)
-    if (int rc = init_conv3d_bn(c3d[i], dtype, sd, cr + "conv" + std::to_string(i) + ".", crc[i], crc[i + 1], crs[i], false)) return rc;
-  if (int rc = init_conv3d_bn(dc[0], dtype, sd, cr + "conv7.", 64, 32, 2, true)) return rc;
-  if (int rc = init_conv3d_bn(dc[1], dtype, sd, cr + "conv9.", 32, 16, 2, true)) return rc;
-  if (int rc = init_conv3d_bn(dc[2], dtype, sd, cr + "conv11.", 16, 8, 2, true)) return rc;
-  if (norm_mode == 1) {
-    const char* nm[10] = {"conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11"};
-    for (int i = 0; i < 10; ++i) {
-      const bool tr = i >= 7;
-      const int cin = tr ? (i == 7 ? 64 : i == 8 ? 32 : 16) : crc[i], cout = tr ? cin / 2 : crc[i + 1];
-      const std::string p = cr + nm[i] + ".";
-      GET(w, p + "conv.weight"); GET(gm, p + "bn.weight"); GET(bt, p + "bn.bias");
-      RGBM_REQUIRE(w->numel() == (long long)cout * cin * 27 && gm->numel() == cout && bt->numel() == cout, "weight shape " + p);
-      ConvGeom g;
-      g.Cin = cin; g.Cout = cout; g.KD = g.KH = g.KW = 3; g.sd = g.sh = g.sw = tr ? 2 : crs[i]; g.pd = g.ph = g.pw = 1;
-      g.transposed = tr; g.act = ACT_NONE;
-      ConvLayer& L = tr ? dc_raw[i - 7] : c3d_raw[i];
-      if (int rc = L.init(dtype, g, w->data, nullptr, nullptr, nullptr, cin, cout)) return rc;
-      if (upload_f32(gm->data, cout, &bn_gamma[i])) return -2;
-      if (upload_f32(bt->data, cout, &bn_beta[i])) return -2;
+  // every row of kCost3d in its three forms: the generic layer with BatchNorm folded in, with norm_mode 1 the raw layer and its gamma /
+  // beta, and the halo-tile pack (conv3d_tile.hip); conv0 and conv11 have further packs of their own
+  for (int i = 0; i < kCost3dLayers; ++i) {
+    const Cost3dLayer& L = kCost3d[i];
+    const std::string p = cr + L.name + ".";
+    GET(w, p + "conv.weight");
+    RGBM_REQUIRE(w->numel() == (long long)L.cout * L.cin * 27, "weight shape " + p);
+    std::vector<float> scale, shift, packed;
+    if (int rc = bn_fold(sd, p + "bn.", L.cout, scale, shift)) return rc;
+    if (int rc = c3d[i].init(dtype, cost3d_geom(L, ACT_RELU), w->data, nullptr, scale.data(), shift.data(), L.cin, L.cout)) return rc;
+    if (norm_mode == 1) {
+      GET(gm, p + "bn.weight"); GET(bt, p + "bn.bias");
+      if (int rc = c3d_raw[i].init(dtype, cost3d_geom(L, ACT_NONE), w->data, nullptr, nullptr, nullptr, L.cin, L.cout)) return rc;
+      if (upload_f32(gm->data, L.cout, bn_gamma[i])) return -2;
+      if (upload_f32(bt->data, L.cout, bn_beta[i])) return -2;
     }
-  }
-  {
-    // halo-tiled versions of the same ten layers (conv3d_tile.hip)
-    const char* nm[10] = {"conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11"};
-    const int cin[10] = {32, 8, 16, 16, 32, 32, 64, 64, 32, 16};
-    const int cout[10] = {8, 16, 16, 32, 32, 64, 64, 32, 16, 8};
-    for (int i = 0; i < 10; ++i) {
-      const std::string p = cr + nm[i] + ".";
-      GET(w, p + "conv.weight");
-      std::vector<float> scale, shift, packed;
-      if (int rc = bn_fold(sd, p + "bn.", cout[i], scale, shift)) return rc;
-      const int coutp = cout[i] < 16 ? 16 : cout[i];
-      conv3d_tile_pack(w->data, scale.data(), cin[i], cout[i], coutp, i >= 7, dtype, packed);
-      t3d[i].Cin = cin[i]; t3d[i].Cout = cout[i];
-      if (upload_packed(packed, dtype, &t3d[i].w)) return -2;
-      std::vector<float> bpad(coutp, 0.f);
-      for (int o = 0; o < cout[i]; ++o) bpad[o] = shift[o];
-      if (upload_f32(bpad.data(), bpad.size(), &t3d[i].bias)) return -2;
-      if (i == 9 && dtype != F32) {
-        // conv11 for the sparse tail (prob_sparse2_kernel): one operand per in-plane tap, both depth parities on the 16 MFMA rows
-        std::vector<float> pt;
-        prob_sparse_pack(w->data, scale.data(), pt);
-        if (dtype == BF16X3) { if (conv0_sweep_x3_upload(pt, &w11_taps)) return -2; }
-        else if (upload_packed(pt, dtype, &w11_taps)) return -2;
-      }
-      if (i == 9 && dtype == BF16X3) {
-        // conv11 for the sparse tail (prob_sparse.hip): its step structure is the 16-bit kernels' (two taps x 16 channels per
-        // MFMA), so the weights are packed in that geometry and split into hi / lo operand arrays
-        std::vector<float> p16;
-        conv3d_tile_pack(w->data, scale.data(), cin[i], cout[i], coutp, true, BF16, p16);
-        if (conv0_sweep_x3_upload(p16, &w11_x3)) return -2;
-      }
-      if (i == 0 && dtype != F32) {
-        // the same conv0 weights in the depth-sweeping kernel's paired-tap fragment order (conv0_sweep.hip / conv0_sweep_x3.hip)
-        conv0_sweep_pack(w->data, scale.data(), packed);
-        if (dtype == BF16X3) { if (conv0_sweep_x3_upload(packed, &sweep_w)) return -2; }
-        else if (upload_packed(packed, dtype, &sweep_w)) return -2;
-        // the f16 form of the sweep (sweep_f16) only for weights that f16 can hold: otherwise sweep_w_f16 stays null and feat_f16() is false
-        if (dtype == BF16 && weights_fit_f16(packed) && upload_packed(packed, F16, &sweep_w_f16)) return -2;
-      }
+    const int coutp = cost3d_coutp(i);
+    conv3d_tile_pack(w->data, scale.data(), L.cin, L.cout, coutp, L.transposed, dtype, packed);
+    if (upload_packed(packed, dtype, t3d[i].w)) return -2;
+    std::vector<float> bpad(coutp, 0.f);
+    for (int o = 0; o < L.cout; ++o) bpad[o] = shift[o];
+    if (upload_f32(bpad.data(), bpad.size(), t3d[i].bias)) return -2;
+    if (i == 9 && dtype != F32) {
+      // conv11 for the sparse tail (prob_sparse2_kernel): one operand per in-plane tap, both depth parities on the 16 MFMA rows
+      std::vector<float> pt;
+      prob_sparse_pack(w->data, scale.data(), pt);
+      if (dtype == BF16X3) { if (conv0_sweep_x3_upload(pt, w11_taps.out())) return -2; }
+      else if (upload_packed(pt, dtype, w11_taps)) return -2;
+    }
+    if (i == 9 && dtype == BF16X3) {
+      // conv11 for the sparse tail (prob_sparse.hip): its step structure is the 16-bit kernels' (two taps x 16 channels per
+      // MFMA), so the weights are packed in that geometry and split into hi / lo operand arrays
+      std::vector<float> p16;
+      conv3d_tile_pack(w->data, scale.data(), L.cin, L.cout, coutp, true, BF16, p16);
+      if (conv0_sweep_x3_upload(p16, w11_x3.out())) return -2;
+    }
+    if (i == 0 && dtype != F32) {
+      // the same conv0 weights in the depth-sweeping kernel's paired-tap fragment order (conv0_sweep.hip / conv0_sweep_x3.hip)
+      conv0_sweep_pack(w->data, scale.data(), packed);
+      if (dtype == BF16X3) { if (conv0_sweep_x3_upload(packed, sweep_w.out())) return -2; }
+      else if (upload_packed(packed, dtype, sweep_w)) return -2;
+      // the f16 form of the sweep (sweep_f16) only for weights that f16 can hold: otherwise sweep_w_f16 stays null and feat_f16() is false
+      if (dtype == BF16 && weights_fit_f16(packed) && upload_packed(packed, F16, sweep_w_f16)) return -2;
     }
   }
   {
@@ -249,7 +226,7 @@ int AdaPose::create_cost(const StateDict& sd) {
     RGBM_REQUIRE(w->numel() == 8 * 27, "prob weight shape");
     std::vector<float> wp(27 * 8);
     for (int c = 0; c < 8; ++c) for (int t = 0; t < 27; ++t) wp[t * 8 + c] = w->data[c * 27 + t];
-    if (upload_f32(wp.data(), wp.size(), &wprob)) return -2;
+    if (upload_f32(wp.data(), wp.size(), wprob)) return -2;
   }
   return 0;
 }
@@ -279,7 +256,7 @@ int AdaPose::create_point_heads(const StateDict& sd, bool pts_mlp) {
     }
     std::vector<float> table((size_t)point_mlp_table_floats());
     point_mlp_pack(w, b, table.data());
-    if (upload_f32(table.data(), table.size(), &pmlp_table)) return -2;
+    if (upload_f32(table.data(), table.size(), pmlp_table)) return -2;
   }
   return 0;
 }
@@ -294,8 +271,8 @@ int AdaPose::create_pose(const StateDict& sd) {
     std::vector<float> wl(256 * 128);
     for (int o = 0; o < 256; ++o) for (int i = 0; i < 128; ++i) wl[o * 128 + i] = w->data[o * 256 + i];
     if (int rc = init_linear(pm2[0], sd, "pose_mlp2.0", 128, 256, ACT_RELU, 128, 256, wl.data(), pose_dtype())) return rc;
-    if (upload_f32(w->data, 256 * 256, &pm2_0_wfull)) return -2;
-    if (upload_f32(b->data, 256, &pm2_0_bias)) return -2;
+    if (upload_f32(w->data, 256 * 256, pm2_0_wfull)) return -2;
+    if (upload_f32(b->data, 256, pm2_0_bias)) return -2;
   }
   if (int rc = init_linear(pm2[1], sd, "pose_mlp2.2", 256, 256, ACT_RELU, 256, 256, nullptr, pose_dtype())) return rc;
   const char* hn[3] = {"rotation_estimator", "translation_estimator", "size_estimator"};
@@ -306,61 +283,22 @@ int AdaPose::create_pose(const StateDict& sd) {
       GET(w, std::string(hn[h]) + "." + std::to_string(2 * l) + ".weight");
       GET(b, std::string(hn[h]) + "." + std::to_string(2 * l) + ".bias");
       RGBM_REQUIRE(w->numel() == (long long)dims[l] * dims[l + 1], "head weight shape");
-      if (upload_f32(w->data, w->numel(), &head_w[h][l])) return -2;
-      if (upload_f32(b->data, b->numel(), &head_b[h][l])) return -2;
+      if (upload_f32(w->data, w->numel(), head_w[h][l])) return -2;
+      if (upload_f32(b->data, b->numel(), head_b[h][l])) return -2;
     }
   }
   return 0;
 }
 
-void AdaPose::destroy() {
-  conv1.destroy();
-  if (stem_w) (void)hipFree(stem_w);
-  stem_w = nullptr;
-  for (int i = 0; i < n_blocks; ++i) { blocks[i].c1.destroy(); blocks[i].c2.destroy(); if (blocks[i].has_ds) blocks[i].ds.destroy(); }
-  for (auto& l : psp) l.destroy();
-  up1.destroy(); up2.destroy(); up3.destroy(); fin.destroy();
-  up1c.destroy(); up2c.destroy(); tail.destroy();
-  if (drop_masks) (void)hipFree(drop_masks);
-  if (drop_state) (void)hipFree(drop_state);
-  drop_masks = nullptr; drop_state = nullptr; drop_cap_views = 0; drop_p = 0.f;
-  for (auto& l : c3d) l.destroy();
-  for (auto& l : dc) l.destroy();
-  for (auto& l : c3d_raw) l.destroy();
-  for (auto& l : dc_raw) l.destroy();
-  for (int i = 0; i < 10; ++i) { if (bn_gamma[i]) (void)hipFree(bn_gamma[i]); if (bn_beta[i]) (void)hipFree(bn_beta[i]); bn_gamma[i] = bn_beta[i] = nullptr; }
-  inst.destroy();
-  for (auto& l : nh) l.destroy();
-  for (auto& l : npm) l.destroy();
-  for (auto& l : pm1) l.destroy();
-  for (auto& l : pm2) l.destroy();
-  for (auto& t : t3d) { if (t.w) (void)hipFree(t.w); if (t.bias) (void)hipFree(t.bias); t.w = nullptr; t.bias = nullptr; }
-  if (sweep_w) (void)hipFree(sweep_w);
-  sweep_w = nullptr;
-  if (sweep_w_f16) (void)hipFree(sweep_w_f16);
-  sweep_w_f16 = nullptr;
-  if (w11_x3) (void)hipFree(w11_x3);
-  w11_x3 = nullptr;
-  if (w11_taps) (void)hipFree(w11_taps);
-  w11_taps = nullptr;
-  if (wprob) (void)hipFree(wprob);
-  if (pm2_0_wfull) (void)hipFree(pm2_0_wfull);
-  if (pmlp_table) { (void)hipFree(pmlp_table); pmlp_table = nullptr; }
-  if (pm2_0_bias) (void)hipFree(pm2_0_bias);
-  if (vf_w) { (void)hipFree(vf_w); vf_w = nullptr; }
-  if (dh_w) { (void)hipFree(dh_w); dh_w = nullptr; }
-  for (int h = 0; h < 3; ++h) for (int l = 0; l < 3; ++l) { if (head_w[h][l]) (void)hipFree(head_w[h][l]); if (head_b[h][l]) (void)hipFree(head_b[h][l]); }
-}
-
 bool AdaPose::feat_f32_only() const {
-  return dtype == BF16X3 && cost_impl == 3 && sweep_w != nullptr && norm_mode == 0 && !(g_debug_flags & DBG_TILE_CONV0);
+  return dtype == BF16X3 && cost_impl == 3 && sweep_w && norm_mode == 0 && !(g_debug_flags & DBG_TILE_CONV0);
 }
 
 // bf16 nets: what `final` writes and what the plane sweep and the point heads read is f16 - same bytes, three more mantissa bits, and the
 // sweep's blend becomes four v_pk_fma_f16 per dword.  Needs the one-kernel up_3 + final (its epilogue knows the f16 form) and the
 // depth-sweeping conv0 (the halo-tile / volume paths read the storage type).
 bool AdaPose::feat_f16() const {
-  return dtype == BF16 && sweep_f16 != 0 && cost_impl == 3 && sweep_w_f16 != nullptr && norm_mode == 0 && !(g_debug_flags & DBG_TILE_CONV0) && (upconv & 4) &&
+  return dtype == BF16 && sweep_f16 != 0 && cost_impl == 3 && sweep_w_f16 && norm_mode == 0 && !(g_debug_flags & DBG_TILE_CONV0) && (upconv & 4) &&
          tail.ready() && tail.f16_ready();
 }
 
@@ -370,7 +308,7 @@ bool AdaPose::sparse_tail_active(bool dense) const {
 }
 
 bool AdaPose::sparse_active(bool dense) const {
-  return sparse_dec != 0 && sparse_tail_active(dense) && sweep_w != nullptr && !(g_debug_flags & DBG_TILE_CONV0);
+  return sparse_dec != 0 && sparse_tail_active(dense) && sweep_w && !(g_debug_flags & DBG_TILE_CONV0);
 }
 
 int AdaPose::chunk_poses(int B) const {
@@ -441,8 +379,8 @@ int AdaPose::plan(int B, Arena& A, Buffers& bf) const {
     // ---- phase B of the baseline network: the fused rows of both views and the attention stack's scratch for one chunk of poses ----
     bf.fused = (float*)A.alloc(VP * 32 * 4);
     bf.vf_scratch = A.alloc(view_fusion_scratch_bytes(chunk_poses(B), P));
-    bf.vol = bf.bn_scratch = bf.u7 = bf.u9 = bf.u11 = nullptr;
-    for (auto& c : bf.c) c = nullptr;
+    bf.vol = bf.bn_scratch = nullptr;
+    for (auto& c : bf.c3) c = nullptr;
     A.release(m0);
     return 0;
   }
@@ -452,16 +390,7 @@ int AdaPose::plan(int B, Arena& A, Buffers& bf) const {
   const size_t vox = (size_t)D * S * S;
   bf.vol = (cost_impl >= 2 && norm_mode == 0) ? nullptr : A.alloc((size_t)Vc * vox * 32 * es);   // fused-warp conv0 never materialises it
   bf.bn_scratch = norm_mode == 1 ? A.alloc(bn_scratch_bytes(Vc)) : nullptr;
-  bf.c[0] = A.alloc((size_t)Vc * vox * 8 * es);
-  bf.c[1] = A.alloc((size_t)Vc * (vox / 8) * 16 * es);
-  bf.c[2] = A.alloc((size_t)Vc * (vox / 8) * 16 * es);
-  bf.c[3] = A.alloc((size_t)Vc * (vox / 64) * 32 * es);
-  bf.c[4] = A.alloc((size_t)Vc * (vox / 64) * 32 * es);
-  bf.c[5] = A.alloc((size_t)Vc * (vox / 512) * 64 * es);
-  bf.c[6] = A.alloc((size_t)Vc * (vox / 512) * 64 * es);
-  bf.u7 = A.alloc((size_t)Vc * (vox / 64) * 32 * es);
-  bf.u9 = A.alloc((size_t)Vc * (vox / 8) * 16 * es);
-  bf.u11 = A.alloc((size_t)Vc * vox * 8 * es);
+  for (int l = 0; l < kCost3dLayers; ++l) bf.c3[l] = A.alloc(cost3d_out_elems(l, Vc, D, S) * es);
   A.release(m0);
   return 0;
 }
@@ -476,13 +405,13 @@ size_t AdaPose::workspace_bytes(int B) const {
 int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* img2, const Call& call) const {
   const int S = img;
   hipStream_t s = call.stream;
-  const float* drop = call.dropout != Dropout::None ? drop_masks : nullptr;      // factors [V][kDropoutPerView]
+  const float* drop = call.dropout != Dropout::None ? drop_masks.get<float>() : nullptr;      // factors [V][kDropoutPerView]
   int H = S / 2, W = S / 2;
   if (stem && stem_w) {
     // NCHW fp32 images -> conv1 + ReLU + max-pool in one kernel (no padded copy, no 112 x 112 x 64 tensor)
     // img2 == nullptr (features()): all V views, any V >= 1, lie in img1
-    if (img2 == nullptr) { if (int rc = launch_stem_views(dtype, img1, stem_w, bf.lb[0], V, S, s)) return rc; }
-    else if (int rc = launch_stem(dtype, img1, img2, stem_w, bf.lb[0], V / 2, V, S, s)) return rc;
+    if (img2 == nullptr) { if (int rc = launch_stem_views(dtype, img1, stem_w.get(), bf.lb[0], V, S, s)) return rc; }
+    else if (int rc = launch_stem(dtype, img1, img2, stem_w.get(), bf.lb[0], V / 2, V, S, s)) return rc;
   } else {
     const size_t es = dtype_size(dtype);
     const int B = img2 == nullptr ? V : V / 2;
@@ -531,9 +460,9 @@ int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* im
     // implicit GEMMs.  The concat (backbone channels + the four resized stages) is one launch at any size.
     bool small = V <= kPspSmallViews;
     for (int i = 0; i < 4; ++i)
-      small = small && psp[i].packs.size() == 1 && psp[i].packs[0].Kpad == 512 && psp[i].Cout_pad == 128 && psp[i].bias == nullptr;
+      small = small && psp[i].packs.size() == 1 && psp[i].packs[0].Kpad == 512 && psp[i].Cout_pad == 128 && !psp[i].bias;
     if (small) {
-      const void* w[4] = {psp[0].packs[0].w, psp[1].packs[0].w, psp[2].packs[0].w, psp[3].packs[0].w};
+      const void* w[4] = {psp[0].packs[0].w.get(), psp[1].packs[0].w.get(), psp[2].packs[0].w.get(), psp[3].packs[0].w.get()};
       void* outs[4] = {bf.stage[0], bf.stage[1], bf.stage[2], bf.stage[3]};
       if (int rc = launch_psp_pool_conv(dtype, f, 512, w, outs, kPspBins, V, H, W, psp[0].g.act, psp[0].g.slope, s)) return rc;
     } else {
@@ -576,17 +505,28 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
   const int Vh = view2_heads ? V : B;      // views whose probability volume is computed (partners are looked up among all V)
   const int Vc0 = chunk_views(V);
   const bool b16 = dtype_size(dtype) == 2;      // 16-bit storage: the depth-sweeping conv0, implicit-GEMM conv6 and the sparse tail exist for these
+  // the rows of kCost3d on this forward's buffers, as the three chunk bodies walk them: input, output, skip tensor, down-sampling of the
+  // input grid, output channels
+  struct Layer3d { const void* in; void* out; const void* res; int div, C; };
+  Layer3d l3d[kCost3dLayers];
+  for (int i = 0; i < kCost3dLayers; ++i)
+    l3d[i] = {i == 0 ? bf.vol : bf.c3[i - 1], bf.c3[i], kCost3d[i].skip >= 0 ? bf.c3[kCost3d[i].skip] : nullptr, kCost3d[i].in_div, kCost3d[i].cout};
+  void* const u11 = bf.c3[kCost3dLayers - 1];
   // halo-tiled path (cost_impl >= 1): one launch per layer; conv0 optionally builds its input on the fly
-  bool sweep_sparse = false;      // set per chunk below: the depth-sweeping conv0 walks the list of needed tiles
-  auto tile = [&](int layer, const void* in, void* out, const void* res, int Vc, int Di, int Hi, int Wi, int Do, int Ho,
-                  int Wo, bool transposed, int v0, const unsigned char* tmask = nullptr) -> int {
+  bool sweep_sparse = false;     // set per chunk below: the depth-sweeping conv0 walks the list of needed tiles
+  // layer: the kernel's id, a row of kCost3d or 10 = row 0 with the plane sweep fused in (no input tensor); grids and channels come from the row
+  auto tile = [&](int layer, const Layer3d& l, int Vc, int v0, const unsigned char* tmask) -> int {
     const int li = layer == 10 ? 0 : layer;
+    const int Cin = kCost3d[li].cin, Cout = kCost3d[li].cout, qi = l.div, qo = cost3d_out_div(li);
+    const bool transposed = kCost3d[li].transposed;
+    const int Di = D / qi, Hi = S / qi, Wi = S / qi, Do = D / qo, Ho = S / qo, Wo = S / qo;
+    const void* res = l.res;
     Conv3dTileDesc d;
     memset(&d, 0, sizeof(d));
-    d.in = in; d.wgt = t3d[li].w; d.out = out; d.bias = t3d[li].bias; d.res = res;
+    d.in = layer == 10 ? nullptr : l.in; d.wgt = t3d[li].w.get(); d.out = l.out; d.bias = t3d[li].bias.get<float>(); d.res = res;
     d.N = Vc; d.Di = Di; d.Hi = Hi; d.Wi = Wi; d.Do = Do; d.Ho = Ho; d.Wo = Wo;
     d.Dq = transposed ? Di : Do; d.Hq = transposed ? Hi : Ho; d.Wq = transposed ? Wi : Wo;
-    d.Cout = t3d[li].Cout; d.relu = 1;
+    d.Cout = Cout; d.relu = 1;
     d.feat = bf.feat; d.homog = bf.homog; d.depths = depths; d.v0 = v0; d.V = V; d.B = B;
     d.out_classmajor = layer == 9 ? 1 : 0;      // u11 is only gathered sparsely by the prob kernel
     d.tile_mask = tmask;
@@ -594,20 +534,20 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
     if (layer == 10 && sweep_sparse) { d.tile_list = bf.sweep_list; d.tile_count = bf.sweep_count; }
     // profiler rows (prof.h): conv0 + fused warp on its own; bf16 layers one row each, f32 layers aggregated
     d.prof_variant = dtype == BF16X3 ? (layer == 10 ? 28 : 27) : layer == 10 ? 10 + (dtype != F32 ? 1 : 0) : (dtype != F32 ? 16 + layer : 8);
-    d.algo_flops = 2.0 * Vc * (double)(transposed ? Di * Hi * Wi : Do * Ho * Wo) * t3d[li].Cout * 27.0 * t3d[li].Cin;
+    d.algo_flops = 2.0 * Vc * (double)(transposed ? Di * Hi * Wi : Do * Ho * Wo) * Cout * 27.0 * Cin;
     // layer 10 (conv0 with the plane sweep fused in) reads the two feature maps of a pair, not the 32 x D x H x W volume it
     // never materialises: algorithmic bytes = features in + c0 out
-    d.algo_bytes = ((layer == 10 ? (double)Vc * Hi * Wi * t3d[li].Cin : (double)Vc * Di * Hi * Wi * t3d[li].Cin) +
-                    (double)Vc * Do * Ho * Wo * t3d[li].Cout * (res ? 2 : 1)) * (double)dtype_size(dtype);
+    d.algo_bytes = ((layer == 10 ? (double)Vc * Hi * Wi * Cin : (double)Vc * Di * Hi * Wi * Cin) +
+                    (double)Vc * Do * Ho * Wo * Cout * (res ? 2 : 1)) * (double)dtype_size(dtype);
     // debug flag 4096: the halo-tile conv0 instead of either depth-sweeping kernel, in every storage type (the runtime way out
     // should a compiler update bring the sweep kernels' hand-counted asm gathers out of step)
     if (layer == 10 && cost_impl == 3 && b16 && sweep_w && !(g_debug_flags & DBG_TILE_CONV0)) {
-      d.wgt = sweep_w;
-      if (feat_f16()) { d.wgt = sweep_w_f16; d.feat_f16 = 1; }
+      d.wgt = sweep_w.get();
+      if (feat_f16()) { d.wgt = sweep_w_f16.get(); d.feat_f16 = 1; }
       return launch_conv0_sweep(d, dtype, s);
     }
     if (layer == 10 && cost_impl == 3 && dtype == BF16X3 && sweep_w && !(g_debug_flags & DBG_TILE_CONV0)) {
-      d.wgt = sweep_w;
+      d.wgt = sweep_w.get();
       d.feat = bf.featf;
       return launch_conv0_sweep_x3(d, s);
     }
@@ -618,12 +558,6 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
   // other tiles, the depth-sweeping conv0 walks the list of needed ones.  conv6 stays dense (a 0.3 ms GEMM): what it computes from
   // unwritten input tiles is never read by anything that is read.
   const bool sparse_ok = sparse_active(call.dense);
-  // the ten 3-D layers as the two generic bodies walk them: input, output, skip tensor, down-sampling of the input grid, output channels
-  struct Layer3d { const void* in; void* out; const void* res; int div, C; };
-  const Layer3d l3d[10] = {{bf.vol, bf.c[0], nullptr, 1, 8}, {bf.c[0], bf.c[1], nullptr, 1, 16}, {bf.c[1], bf.c[2], nullptr, 2, 16},
-                           {bf.c[2], bf.c[3], nullptr, 2, 32}, {bf.c[3], bf.c[4], nullptr, 4, 32}, {bf.c[4], bf.c[5], nullptr, 4, 64},
-                           {bf.c[5], bf.c[6], nullptr, 8, 64}, {bf.c[6], bf.u7, bf.c[4], 8, 32}, {bf.u7, bf.u9, bf.c[2], 4, 16},
-                           {bf.u9, bf.u11, bf.c[0], 2, 8}};
   for (int v0 = 0; v0 < Vh; v0 += Vc0) {
     const int Vc = Vh - v0 < Vc0 ? Vh - v0 : Vc0;
     int classmajor = 0;      // layout of the u11 the chunk body leaves behind
@@ -632,19 +566,19 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
       if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
       for (int i = 0; i < 10; ++i) {
         const Layer3d& l = l3d[i];
-        const ConvLayer& L = i >= 7 ? dc_raw[i - 7] : c3d_raw[i];
+        const ConvLayer& L = c3d_raw[i];
         int Do, Ho, Wo;
         L.out_dims(D / l.div, S / l.div, S / l.div, Do, Ho, Wo);
         if (int rc = L.run(l.in, l.out, Vc, D / l.div, S / l.div, S / l.div, l.C, nullptr, RES_NONE, nullptr, 0, s)) return rc;
-        if (int rc = launch_bn_per_sample(dtype, l.out, l.res, bn_gamma[i], bn_beta[i], bf.bn_scratch, Vc, (long long)Do * Ho * Wo, l.C, 1, s)) return rc;
+        if (int rc = launch_bn_per_sample(dtype, l.out, l.res, bn_gamma[i].get<float>(), bn_beta[i].get<float>(), bf.bn_scratch, Vc,
+                                          (long long)Do * Ho * Wo, l.C, 1, s)) return rc;
       }
     } else if (cost_impl == 0) {
       // generic implicit GEMM on the materialised volume; the skip adds of conv7 / 9 / 11 are post-ReLU (network_v5.py:287-289)
       if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
       for (int i = 0; i < 10; ++i) {
         const Layer3d& l = l3d[i];
-        const ConvLayer& L = i >= 7 ? dc[i - 7] : c3d[i];
-        if (int rc = L.run(l.in, l.out, Vc, D / l.div, S / l.div, S / l.div, l.C, l.res, RES_POST_ACT, nullptr, 0, s)) return rc;
+        if (int rc = c3d[i].run(l.in, l.out, Vc, D / l.div, S / l.div, S / l.div, l.C, l.res, RES_POST_ACT, nullptr, 0, s)) return rc;
       }
     } else {
       // halo-tiled layers; conv0 on the materialised volume (cost_impl 1) or with the plane sweep fused in
@@ -660,38 +594,34 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
           sweep_sparse = true;
         }
       }
-      if (cost_impl == 1) {
-        if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
-        if (int rc = tile(0, bf.vol, bf.c[0], nullptr, Vc, D, S, S, D, S, S, false, v0)) return rc;
-      } else {
-        if (int rc = tile(10, nullptr, bf.c[0], nullptr, Vc, D, S, S, D, S, S, false, v0)) return rc;
+      // one launch per row; the rows that are not simply their halo-tile kernel say so
+      const bool tail_sparse = sparse_tail_active(call.dense);
+      for (int i = 0; i < (tail_sparse ? 9 : kCost3dLayers); ++i) {
+        const Layer3d& l = l3d[i];
+        if (i == 0 && cost_impl == 1) {
+          if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
+          if (int rc = tile(0, l, Vc, v0, nullptr)) return rc;
+        } else if (i == 0) {
+          if (int rc = tile(10, l, Vc, v0, nullptr)) return rc;
+        } else if (i == 6 && cost_impl == 3 && (b16 || dtype == BF16X3) && igemm_conv6) {
+          // conv6 (64 -> 64, K = 27 x 64): a plain GEMM shape, 2.7x faster on the role-specialised implicit-GEMM kernel
+          if (int rc = c3d[6].run(l.in, l.out, Vc, D / l.div, S / l.div, S / l.div, l.C, nullptr, RES_NONE, nullptr, 0, s)) return rc;
+        } else {
+          if (int rc = tile(i, l, Vc, v0, mk[i])) return rc;      // masks: rows 1-5, 7 and 8 (above)
+        }
       }
-      if (int rc = tile(1, bf.c[0], bf.c[1], nullptr, Vc, D, S, S, D / 2, S / 2, S / 2, false, v0, mk[1])) return rc;
-      if (int rc = tile(2, bf.c[1], bf.c[2], nullptr, Vc, D / 2, S / 2, S / 2, D / 2, S / 2, S / 2, false, v0, mk[2])) return rc;
-      if (int rc = tile(3, bf.c[2], bf.c[3], nullptr, Vc, D / 2, S / 2, S / 2, D / 4, S / 4, S / 4, false, v0, mk[3])) return rc;
-      if (int rc = tile(4, bf.c[3], bf.c[4], nullptr, Vc, D / 4, S / 4, S / 4, D / 4, S / 4, S / 4, false, v0, mk[4])) return rc;
-      if (int rc = tile(5, bf.c[4], bf.c[5], nullptr, Vc, D / 4, S / 4, S / 4, D / 8, S / 8, S / 8, false, v0, mk[5])) return rc;
-      if (cost_impl == 3 && (b16 || dtype == BF16X3) && igemm_conv6) {
-        // conv6 (64 -> 64, K = 27 x 64): a plain GEMM shape, 2.7x faster on the role-specialised implicit-GEMM kernel
-        if (int rc = c3d[6].run(bf.c[5], bf.c[6], Vc, D / 8, S / 8, S / 8, 64, nullptr, RES_NONE, nullptr, 0, s)) return rc;
-      } else {
-        if (int rc = tile(6, bf.c[5], bf.c[6], nullptr, Vc, D / 8, S / 8, S / 8, D / 8, S / 8, S / 8, false, v0)) return rc;
-      }
-      if (int rc = tile(7, bf.c[6], bf.u7, bf.c[4], Vc, D / 8, S / 8, S / 8, D / 4, S / 4, S / 4, true, v0, mk[7])) return rc;
-      if (int rc = tile(8, bf.u7, bf.u9, bf.c[2], Vc, D / 4, S / 4, S / 4, D / 2, S / 2, S / 2, true, v0, mk[8])) return rc;
-      if (sparse_tail_active(call.dense)) {
+      if (tail_sparse) {
         // conv11 + skip + prob conv + softmax + depth only on the 3x3 neighbourhoods of the chosen pixels (prob_sparse.hip)
-        if (int rc = launch_prob_sparse(bf.u9, bf.c[0], dtype == BF16X3 ? w11_x3 : t3d[9].w, t3d[9].bias, wprob, bf.choose, depths, bf.prob,
-                                        bf.depth, v0, Vc, B, P, D, S, S, dtype, s, w11_taps)) return rc;
+        if (int rc = launch_prob_sparse(l3d[9].in, l3d[9].res, dtype == BF16X3 ? w11_x3.get() : t3d[9].w.get(), t3d[9].bias.get<float>(),
+                                        wprob.get<float>(), bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, dtype, s, w11_taps.get())) return rc;
         continue;
       }
-      if (int rc = tile(9, bf.u9, bf.u11, bf.c[0], Vc, D / 2, S / 2, S / 2, D, S, S, true, v0)) return rc;
       classmajor = 1;      // u11 is only gathered: conv11's halo-tile kernel writes it class-major
     }
-    if (int rc = launch_prob_softmax_depth(dtype, bf.u11, wprob, bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, classmajor, s)) return rc;
+    if (int rc = launch_prob_softmax_depth(dtype, u11, wprob.get<float>(), bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, classmajor, s)) return rc;
     // the dense head on the u11 of every chunk, beside the point kernel (rows v0 .. v0 + Vc - 1 of the maps)
     if (call.depth_map != nullptr)
-      if (int rc = launch_dense_depth(dtype, bf.u11, wprob, depths, call.depth_map, call.conf_map, v0, Vc, B, D, S, S, classmajor, s)) return rc;
+      if (int rc = launch_dense_depth(dtype, u11, wprob.get<float>(), depths, call.depth_map, call.conf_map, v0, Vc, B, D, S, S, classmajor, s)) return rc;
   }
   return 0;
 }
@@ -701,7 +631,7 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
                      const Call& call) const {
   RGBM_REQUIRE(call.depth_map == nullptr || call.dense, "forward: depth_map needs a dense call");
   RGBM_REQUIRE(call.depth_map != nullptr || call.conf_map == nullptr, "forward_maps: conf_map without depth_map");
-  RGBM_REQUIRE(call.nocs_map == nullptr || pmlp_table != nullptr, "forward_maps: no point MLP table");
+  RGBM_REQUIRE(call.nocs_map == nullptr || pmlp_table, "forward_maps: no point MLP table");
   RGBM_REQUIRE(B > 0, "batch");
   RGBM_REQUIRE(arch != ARCH_BASELINE || !(call.dense || call.depth_map || call.conf_map || call.nocs_map),
                "baseline network: the dense / maps forwards are not implemented (they read the cost volume this network does not have)");
@@ -729,7 +659,7 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
     RGBM_REQUIRE(V <= drop_cap_views && drop_masks && (loaded || drop_state), "dropout: mask buffer smaller than the batch");
     RGBM_REQUIRE((upconv & 3) == 3, "dropout needs option upconv bits 0 and 1 (up_1 / up_2 through the tap combination)");
     if (!loaded)
-      if (int rc = launch_dropout_masks(drop_masks, drop_state, B, drop_p, drop_seed, call.dropout == Dropout::Draw ? 1 : 0, s)) return rc;
+      if (int rc = launch_dropout_masks(drop_masks.get<float>(), drop_state.get<unsigned long long>(), B, drop_p, drop_seed, call.dropout == Dropout::Draw ? 1 : 0, s)) return rc;
   }
   if (int rc = pspnet(bf, V, img1, img2, call)) return rc;
   if (arch != ARCH_BASELINE)
@@ -744,74 +674,77 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
 
 // Everything behind the PSPNet of the baseline network (network_baseline.py:617-669): the gathered rows feed the NOCS branch as in v5 and,
 // untouched, the attention stack; depth_head and the pose branch read the fused rows.
+AdaPose::FeatSource AdaPose::gather_source(const Buffers& bf) const {
+  if (dtype == BF16X3) return {bf.featf, F32};
+  return {bf.feat, feat_f16() ? (int)F16 : dtype};
+}
+
+// view2_heads = 0: the view-2 outputs are filled with NaN, so that a consumer of one fails loudly instead of reading stale numbers
+int AdaPose::stage_out(const Buffers& bf, int B, const Outputs& out, hipStream_t s) const {
+  float* const on[2] = {out.nocs1, out.nocs2};
+  float* const od[2] = {out.depth1, out.depth2};
+  float* const orr[2] = {out.r1, out.r2};
+  float* const ot[2] = {out.t1, out.t2};
+  float* const os[2] = {out.s1, out.s2};
+  return launch_stage_out(bf.nocs4, bf.depth, bf.R, bf.tv, bf.sv, on, od, orr, ot, os, B, n_pts, view2_heads, s);
+}
+
 int AdaPose::heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call) const {
   const int V = 2 * B, P = n_pts, S = img;
   hipStream_t s = call.stream;
-  const void* featg = bf.feat;
-  int fdt = dtype;
-  if (dtype == BF16X3) { featg = bf.featf; fdt = F32; }
-  if (feat_f16()) fdt = F16;
+  const FeatSource src = gather_source(bf);
   const int Vh = view2_heads ? V : B;
-  RGBM_REQUIRE(pmlp_table != nullptr && ((long long)Vh * P) % 64 == 0, "baseline network: the point MLP kernel needs a multiple of 64 points");
+  RGBM_REQUIRE(pmlp_table && ((long long)Vh * P) % 64 == 0, "baseline network: the point MLP kernel needs a multiple of 64 points");
   // both views' rows: view 2's are every block's keys even without its heads
-  if (int rc = launch_gather_points(fdt, featg, bf.choose, bf.X0, V, P, S * S, 32, s)) return rc;
+  if (int rc = launch_gather_points(src.dtype, src.feat, bf.choose, bf.X0, V, P, S * S, 32, s)) return rc;
   PointMlpDesc pd{};
-  pd.table = pmlp_table; pd.feat = featg; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = P; pd.HW = S * S;
+  pd.table = pmlp_table.get<float>(); pd.feat = src.feat; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = P; pd.HW = S * S;
   pd.N = (long long)Vh * P;
-  if (int rc = launch_point_mlp(fdt, pd, s)) return rc;
+  if (int rc = launch_point_mlp(src.dtype, pd, s)) return rc;
   // the attention stack, a chunk of poses at a time (max_chunk views = max_chunk / 2 poses): a pose's rows do not depend on its chunk
   const size_t view2 = (size_t)B * P * 32;
   const int Bc0 = chunk_poses(B);
   for (int b0 = 0; b0 < B; b0 += Bc0) {
     const int Bc = B - b0 < Bc0 ? B - b0 : Bc0;
     const size_t o = (size_t)b0 * P * 32;
-    if (int rc = launch_view_fusion(vf_w, bf.X0 + o, bf.X0 + view2 + o, Bc, P, bf.fused + o, bf.fused + view2 + o, bf.vf_scratch,
+    if (int rc = launch_view_fusion(vf_w.get<float>(), bf.X0 + o, bf.X0 + view2 + o, Bc, P, bf.fused + o, bf.fused + view2 + o, bf.vf_scratch,
                                     view_fusion_scratch_bytes(Bc0, P), view2_heads ? 2 : 1, s)) return rc;
   }
   if (call.stop_after == 2) return 0;
   // depth_head on the fused rows; the same rows are channels 0..31 of the pose feature (network_baseline.py:633-641)
-  if (int rc = launch_depth_head(dh_w, bf.fused, (long long)Vh * P, bf.depth, regress_pose ? bf.PF96 : nullptr, 96, s)) return rc;
+  if (int rc = launch_depth_head(dh_w.get<float>(), bf.fused, (long long)Vh * P, bf.depth, regress_pose ? bf.PF96 : nullptr, 96, s)) return rc;
   if (regress_pose)
     if (int rc = pose_branch(bf, Vh, call)) return rc;
-  float* const on[2] = {out.nocs1, out.nocs2};
-  float* const od[2] = {out.depth1, out.depth2};
-  float* const orr[2] = {out.r1, out.r2};
-  float* const ot[2] = {out.t1, out.t2};
-  float* const os[2] = {out.s1, out.s2};
-  if (int rc = launch_stage_out(bf.nocs4, bf.depth, bf.R, bf.tv, bf.sv, on, od, orr, ot, os, B, P, view2_heads, s)) return rc;
-  if (!regress_pose)      // no pose branch: the six r / t / s outputs are NaN
-    for (int v = 0; v < 2; ++v) {
-      if (int rc = launch_fill_nan(orr[v], (long long)B * 9, s)) return rc;
-      if (int rc = launch_fill_nan(ot[v], (long long)B * 3, s)) return rc;
-      if (int rc = launch_fill_nan(os[v], (long long)B * 3, s)) return rc;
-    }
+  if (int rc = stage_out(bf, B, out, s)) return rc;
+  if (!regress_pose) {      // no pose branch: the six r / t / s outputs are NaN
+    float* const rts[6] = {out.r1, out.t1, out.s1, out.r2, out.t2, out.s2};
+    for (int i = 0; i < 6; ++i)
+      if (int rc = launch_fill_nan(rts[i], (long long)B * (i % 3 == 0 ? 9 : 3), s)) return rc;
+  }
   return 0;
 }
 
 int AdaPose::nocs_map_of(const float* feat_f32, long long pixels, float* nocs_map, hipStream_t s) const {
-  RGBM_REQUIRE(pmlp_table != nullptr, "nocs_map: no point MLP table");
-  return launch_dense_nocs(F32, pmlp_table, feat_f32, nocs_map, pixels, s);
+  RGBM_REQUIRE(pmlp_table, "nocs_map: no point MLP table");
+  return launch_dense_nocs(F32, pmlp_table.get<float>(), feat_f32, nocs_map, pixels, s);
 }
 
 // Everything behind the PSPNet: reads the feature map(s) in bf.feat / bf.featf, bf.homog, bf.choose (forward() and forward_cached() fill them)
 int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call) const {
   const int V = 2 * B, P = n_pts, S = img, D = n_depth;
   hipStream_t s = call.stream;
-  const void* featg = bf.feat;
-  int fdt = dtype;
-  if (dtype == BF16X3) { featg = bf.featf; fdt = F32; }
-  if (feat_f16()) fdt = F16;
+  const FeatSource src = gather_source(bf);
 
   const int Vh = view2_heads ? V : B;      // views that get heads: both crops of every pose, or the view-1 crops only (option view2_heads)
   // ---- per-point NOCS branch (network_v5.py:432-444) ----
-  if (pmlp_table != nullptr && !(g_debug_flags & DBG_POINT_MLP_R5) && ((long long)Vh * P) % 64 == 0) {
+  if (pmlp_table && !(g_debug_flags & DBG_POINT_MLP_R5) && ((long long)Vh * P) % 64 == 0) {
     // gather + the six layers in one launch (head_kernels.hip): a wave carries 16 points through the whole branch, weights and activations in LDS
     PointMlpDesc pd{};
-    pd.table = pmlp_table; pd.feat = featg; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = P; pd.HW = S * S;
+    pd.table = pmlp_table.get<float>(); pd.feat = src.feat; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = P; pd.HW = S * S;
     pd.N = (long long)Vh * P;
-    if (int rc = launch_point_mlp(fdt, pd, s)) return rc;
+    if (int rc = launch_point_mlp(src.dtype, pd, s)) return rc;
   } else {
-    if (int rc = launch_gather_points(fdt, featg, bf.choose, bf.X0, Vh, P, S * S, 32, s)) return rc;
+    if (int rc = launch_gather_points(src.dtype, src.feat, bf.choose, bf.X0, Vh, P, S * S, 32, s)) return rc;
     if (int rc = inst.run(bf.X0, bf.X1, Vh, 1, 1, P, 64, nullptr, 0, nullptr, 0, s)) return rc;
     if (int rc = nh[0].run(bf.X1, bf.H128, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
     if (int rc = nh[1].run(bf.H128, bf.H64, Vh, 1, 1, P, 64, nullptr, 0, nullptr, 0, s)) return rc;
@@ -822,27 +755,18 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
 
   // the same branch's layers 0..3 on every pixel of the Vh feature maps (the dense NOCS map)
   if (call.nocs_map != nullptr)
-    if (int rc = launch_dense_nocs(fdt, pmlp_table, featg, call.nocs_map, (long long)Vh * S * S, s)) return rc;
+    if (int rc = launch_dense_nocs(src.dtype, pmlp_table.get<float>(), src.feat, call.nocs_map, (long long)Vh * S * S, s)) return rc;
 
   // ---- plane-sweep cost volume -> probability at the sampled pixels -> depth ----
   if (int rc = cost_volume(bf, V, B, depths, call)) return rc;
   if (call.stop_after == 2) return 0;
 
   // ---- depth-guided fusion + pose regression (network_v5.py:457-508) ----
-  if (int rc = launch_fuse_points(fdt, featg, bf.homog, depths, bf.choose, bf.prob, bf.PF96, V, B, P, D, S, S, 96, 0, s, Vh)) return rc;
+  if (int rc = launch_fuse_points(src.dtype, src.feat, bf.homog, depths, bf.choose, bf.prob, bf.PF96, V, B, P, D, S, S, 96, 0, s, Vh)) return rc;
   if (int rc = pose_branch(bf, Vh, call)) return rc;
 
-  // ---- outputs (fp32, reference shapes); view2_heads = 0: the view-2 outputs are filled with NaN, so that a consumer of one fails
-  // loudly instead of reading stale numbers ----
-  {
-    float* const on[2] = {out.nocs1, out.nocs2};
-    float* const od[2] = {out.depth1, out.depth2};
-    float* const orr[2] = {out.r1, out.r2};
-    float* const ot[2] = {out.t1, out.t2};
-    float* const os[2] = {out.s1, out.s2};
-    if (int rc = launch_stage_out(bf.nocs4, bf.depth, bf.R, bf.tv, bf.sv, on, od, orr, ot, os, B, P, view2_heads, s)) return rc;
-  }
-  return 0;
+  // ---- outputs (fp32, reference shapes) ----
+  return stage_out(bf, B, out, s);
 }
 
 // pose_mlp1 -> mean -> pose_mlp2 -> mean -> the three heads + Ortho6d on the pose features PF96 of views 0 .. Vh - 1 (network_v5.py:470-508;
@@ -858,17 +782,17 @@ int AdaPose::pose_branch(const Buffers& bf, int Vh, const Call& call) const {
   // count that is not a whole number of slabs per slice, and for layers of another shape)
   auto pose_layer_ok = [](const ConvLayer& L, int cin, int cout) {
     return L.dtype == F16 && L.packs.size() == 1 && L.packs[0].ntaps == 1 && L.Cin_pad == cin && L.Cout_pad == cout && L.g.act == ACT_RELU &&
-           L.packs[0].Kpad >= cin && L.bias != nullptr;
+           L.packs[0].Kpad >= cin && L.bias;
   };
   const bool pose_fused = pdt == F16 && !(g_debug_flags & DBG_POSE_MLP_R6) && pose_mlp_fits(P) && pose_layer_ok(pm1[0], 96, 128) &&
                           pose_layer_ok(pm1[1], 128, 128) && pose_layer_ok(pm2[0], 128, 256) && pose_layer_ok(pm2[1], 256, 256);
   if (pose_fused) {
     PoseMlpDesc pd{};
     const ConvLayer* L[4] = {&pm1[0], &pm1[1], &pm2[0], &pm2[1]};
-    for (int l = 0; l < 4; ++l) { pd.w[l] = L[l]->packs[0].w; pd.ldw[l] = L[l]->packs[0].Kpad; pd.bias[l] = L[l]->bias; }
+    for (int l = 0; l < 4; ++l) { pd.w[l] = L[l]->packs[0].w.get(); pd.ldw[l] = L[l]->packs[0].Kpad; pd.bias[l] = L[l]->bias.get<float>(); }
     pd.pf96 = bf.PF96; pd.vbias = bf.vbias; pd.q128 = bf.Q128b; pd.part128 = (float*)bf.Q128a; pd.part256 = (float*)bf.G256a; pd.V = Vh; pd.P = P;
     if (int rc = launch_pose_mlp1(pd, s)) return rc;
-    if (int rc = launch_view_linear_mean((const float*)bf.Q128a, P, bf.glob, pm2_0_wfull, pm2_0_bias, bf.vbias, Vh, 128, 256, 256, 128, 0, s)) return rc;
+    if (int rc = launch_view_linear_mean((const float*)bf.Q128a, P, bf.glob, pm2_0_wfull.get<float>(), pm2_0_bias.get<float>(), bf.vbias, Vh, 128, 256, 256, 128, 0, s)) return rc;
     if (int rc = launch_pose_mlp2(pd, s)) return rc;
   } else {
     const void* pf_in = bf.PF96;
@@ -882,14 +806,17 @@ int AdaPose::pose_branch(const Buffers& bf, int Vh, const Call& call) const {
     if (int rc = pm1[1].run(bf.Q128a, bf.Q128b, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
     // the two means over a view's points are finished by their consumers (the slices' partial sums in Q128a / G256a: free at that point)
     if (int rc = launch_mean_points_partial(pdt, bf.Q128b, (float*)bf.Q128a, Vh, P, 128, s)) return rc;
-    if (int rc = launch_view_linear_mean((const float*)bf.Q128a, P, bf.glob, pm2_0_wfull, pm2_0_bias, bf.vbias, Vh, 128, 256, 256, 128, 0, s)) return rc;
+    if (int rc = launch_view_linear_mean((const float*)bf.Q128a, P, bf.glob, pm2_0_wfull.get<float>(), pm2_0_bias.get<float>(), bf.vbias, Vh, 128, 256, 256, 128, 0, s)) return rc;
     if (int rc = pm2[0].run(bf.Q128b, bf.G256a, Vh, 1, 1, P, 256, nullptr, 0, bf.vbias, 256, s)) return rc;
     if (int rc = pm2[1].run(bf.G256a, bf.G256b, Vh, 1, 1, P, 256, nullptr, 0, nullptr, 0, s)) return rc;
     if (int rc = launch_mean_points_partial(pdt, bf.G256b, (float*)bf.G256a, Vh, P, 256, s)) return rc;
   }
   float* hout[3] = {bf.r6, bf.tv, bf.sv};
   const int hdim[3] = {6, 3, 3};
-  return launch_pose_heads_mean((const float*)bf.G256a, P, bf.pf2, bf.R, head_w, head_b, hout, hdim, Vh, s);      // + Ortho6d -> R
+  float *hw[3][3], *hb[3][3];
+  for (int h = 0; h < 3; ++h)
+    for (int l = 0; l < 3; ++l) { hw[h][l] = head_w[h][l].get<float>(); hb[h][l] = head_b[h][l].get<float>(); }
+  return launch_pose_heads_mean((const float*)bf.G256a, P, bf.pf2, bf.R, hw, hb, hout, hdim, Vh, s);      // + Ortho6d -> R
 }
 
 // ---- feature cache (feature_cache.hip, DESIGN.md "Feature cache") ----

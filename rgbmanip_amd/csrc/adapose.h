@@ -24,8 +24,8 @@ struct AdaPose {
   enum { ARCH_V5 = 0, ARCH_BASELINE = 1 };
   int arch = ARCH_V5;
   int regress_pose = 1;           // baseline only: 0 = no pose branch (the six r / t / s outputs are NaN)
-  float* vf_w = nullptr;          // baseline: the attention stack's 32 linears (view_fusion.h: kVfWeightFloats)
-  float* dh_w = nullptr;          // baseline: depth_head (kDepthHeadFloats)
+  DevBuf vf_w;                    // baseline: the attention stack's 32 linears (view_fusion.h: kVfWeightFloats)
+  DevBuf dh_w;                    // baseline: depth_head (kDepthHeadFloats)
   int dtype = F32;
   // storage type of the pose MLP (pose_mlp1 / pose_mlp2, network_v5.py:470-494): fp16 for the bf16 throughput mode (its
   // activations are O(1); fp16 per-point features keep 11 mantissa bits, the means over points stay fp32, and the rotation
@@ -46,19 +46,19 @@ struct AdaPose {
   ConvLayer psp[4], up1, up2, up3, fin;
   UpConvLayer up1c, up2c;       // up_1 / up_2 as a low-resolution 1x1 GEMM + tap combination (upconv.hip)
   int sparse_dec = 2;           // with the sparse tail: 2 = every 3-D layer (and the plane sweep) only on the tiles inside the chosen pixels' dependency cones, 1 = conv7 / conv9 only, 0 = dense (A/B, and the c0 .. u9 taps)
-  void* stem_w = nullptr;       // conv1 packed for the one-kernel stem (stem.hip; 16-bit and split-pair storage)
+  DevBuf stem_w;                // conv1 packed for the one-kernel stem (stem.hip; 16-bit and split-pair storage)
   int stem = 0;                 // 1: NCHW images -> conv1 7x7 + ReLU + max-pool in one kernel (default for 16-bit and split-pair storage, set in create()); 0: copy, implicit-GEMM conv, pool (materialises `conv1`)
   UpConvFinal tail;             // up_3 + final in one kernel (upconv_final.hip; 16-bit and split-pair storage)
   int upconv = 7;               // bit 0: up_1, bit 1: up_2 through UpConvLayer, bit 2: up_3 + final through UpConvFinal (16-bit / split pairs); 0 = x2 resize + 3x3 conv on the up-sampled grid, for A/B and tests
-  ConvLayer c3d[7], dc[3];      // generic implicit-GEMM versions (kept for A/B: cost_impl = 0)
+  // The ten layers of the cost regularisation, indexed as the rows of kCost3d (cost3d.h: 0..6 conv0..6, 7..9 conv7/9/11), in three forms:
+  ConvLayer c3d[10];            // generic implicit-GEMM versions (kept for A/B: cost_impl = 0; conv6 of the default path)
   // norm_mode 1 (per-sample BatchNorm3d: the as-shipped train-mode behaviour at batch 1): the same ten layers without
   // BN / activation, their gamma / beta, and the in-place normalisation of bn_kernels.hip behind each of them
   int norm_mode = 0;
-  ConvLayer c3d_raw[7], dc_raw[3];
-  float* bn_gamma[10] = {nullptr};
-  float* bn_beta[10] = {nullptr};
-  struct Tile3d { void* w = nullptr; float* bias = nullptr; int Cin = 0, Cout = 0; };
-  Tile3d t3d[10];               // halo-tiled versions: 0..6 conv0..6, 7..9 conv7/9/11
+  ConvLayer c3d_raw[10];
+  DevBuf bn_gamma[10], bn_beta[10];
+  struct Tile3d { DevBuf w, bias; };
+  Tile3d t3d[10];               // halo-tiled versions
   int igemm_conv6 = 1;          // bf16 + cost_impl 3: conv6 through the implicit-GEMM path instead of the halo-tile kernel
   int fuse_final = 1;           // bf16: PSPNet `final` 1x1 fused into up_3's kernel (0 = two launches; `u3` is then materialised)
   int view2_heads = 1;          // 0: the cost volume, the point heads and the pose regression run for the view-1 crops only (the view-2 outputs are
@@ -66,27 +66,26 @@ struct AdaPose {
                                 // view1_nocs / view1_depth / view1_r and drops the rest — at ~3/4 of the time; the backbone still runs on both views
   int sparse_tail = 1;          // cost_impl 3: evaluate conv11 + prob only where prob is gathered (0 = dense conv11, for A/B and tests)
   int sweep_f16 = 1;            // bf16 nets: `final` writes the feature map as f16 and the plane sweep blends it with packed f16 FMAs (conv0_sweep.hip; 0 = bf16 feature map, fp32 blend)
-  void* w11_taps = nullptr;     // conv11 for the sparse tail's round-6 kernel: prob_sparse_pack's nine in-plane-tap operands (bf16x3: hi operands, then lo)
-  void* sweep_w_f16 = nullptr;  // bf16 nets: the same conv0 weights as f16 (sweep_f16)
-  void* sweep_w = nullptr;      // conv0 weights in conv0_sweep.hip fragment order (16-bit nets; bf16x3 nets: hi + lo operand arrays of conv0_sweep_x3.hip)
+  DevBuf w11_taps;              // conv11 for the sparse tail's round-6 kernel: prob_sparse_pack's nine in-plane-tap operands (bf16x3: hi operands, then lo)
+  DevBuf sweep_w_f16;           // bf16 nets: the same conv0 weights as f16 (sweep_f16)
+  DevBuf sweep_w;               // conv0 weights in conv0_sweep.hip fragment order (16-bit nets; bf16x3 nets: hi + lo operand arrays of conv0_sweep_x3.hip)
   int cost_impl = 3;            // 0 generic igemm + materialised volume, 1 tiled + materialised volume, 2 tiled + fused warp,
                                 // 3 = 2 with the depth-sweeping conv0 kernel (bf16; fp32 nets run 2)
-  void* w11_x3 = nullptr;       // bf16x3 nets: conv11 weights for prob_sparse (16-bit step geometry, hi operands then lo operands)
-  float* wprob = nullptr;
+  DevBuf w11_x3;                // bf16x3 nets: conv11 weights for prob_sparse (16-bit step geometry, hi operands then lo operands)
+  DevBuf wprob;
   ConvLayer inst, nh[3], npm[2], pm1[2], pm2[2];
-  float* pm2_0_wfull = nullptr;
-  float* pmlp_table = nullptr;    // the per-point NOCS branch's six layers as point_mlp_kernel's LDS image (kernels.h: point_mlp_pack)
-  float* pm2_0_bias = nullptr;
-  float* head_w[3][3] = {{nullptr}};
-  float* head_b[3][3] = {{nullptr}};
+  DevBuf pm2_0_wfull;
+  DevBuf pmlp_table;            // the per-point NOCS branch's six layers as point_mlp_kernel's LDS image (kernels.h: point_mlp_pack)
+  DevBuf pm2_0_bias;
+  DevBuf head_w[3][3], head_b[3][3];
 
   // Seeded Dropout2d of PSPNet (dropout.hip; set through rgbm_adapose_set_dropout): p = 0 is off.  drop_masks [drop_cap_views][kDropoutPerView]
   // holds the factors of the last forward, drop_state the device pose counter (+ the mask kernel's ticket).  Which masks a forward uses
   // is the call's business (Call::dropout); which call comes next and what the last one drew is the handle's (capi.cpp).
   float drop_p = 0.f;
   unsigned long long drop_seed = 0;
-  float* drop_masks = nullptr;
-  unsigned long long* drop_state = nullptr;
+  DevBuf drop_masks;
+  DevBuf drop_state;
   int drop_cap_views = 0;
 
   // What one call wants beyond the network's inputs and outputs.  The entry point (capi.cpp) fills it; forward() / forward_cached() pass
@@ -120,7 +119,7 @@ struct AdaPose {
     void* PF96h;                       // fp16 copy of PF96 (pose MLP input of 16-bit nets)
     float *glob, *vbias, *pf2, *h1, *h2, *r6, *R, *tv, *sv;
     void *imgpad, *c1, *lb[4], *pooled[4], *stage[4], *cat, *ups, *u1, *u2, *u3;
-    void *vol, *c[7], *u7, *u9, *u11;
+    void *vol, *c3[10];                // the plane-sweep volume (where it is materialised) and the outputs of the ten rows of kCost3d
     void* bn_scratch;
     float* fused;                      // baseline: the attention stack's output rows [V][P][32]
     void* vf_scratch;                  // ... and its scratch for one chunk of poses
@@ -139,7 +138,6 @@ struct AdaPose {
   int create_cost(const StateDict& sd);
   int create_point_heads(const StateDict& sd, bool pts_mlp);
   int create_pose(const StateDict& sd);
-  void destroy();
   size_t workspace_bytes(int B) const;
   // the map rules of a call (depth_map needs dense, conf_map needs depth_map, nocs_map needs the point MLP table) are checked here
   int forward(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
@@ -162,6 +160,10 @@ struct AdaPose {
   int feature_parts(const Buffers& bf, FeaturePart parts[2]) const;
   int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call) const;
   int heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call) const;
+  // what the point heads gather from: the feature map of this forward and its element type (fp32 copy for split pairs, f16 with feat_f16())
+  struct FeatSource { const void* feat; int dtype; };
+  FeatSource gather_source(const Buffers& bf) const;
+  int stage_out(const Buffers& bf, int B, const Outputs& out, hipStream_t s) const;      // the staged point / pose results -> the ten outputs
   int pose_branch(const Buffers& bf, int Vh, const Call& call) const;
   int chunk_poses(int B) const;      // baseline: poses per launch of the attention stack (max_chunk views)
   int layer4_index() const { return (3 * n_blocks) & 3; }      // which of the rotating buffers bf.lb holds the layer4 output (debug fetch)

@@ -6,11 +6,14 @@
 
 #include <algorithm>
 #include <initializer_list>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "adapose.h"
 #include "control.h"
+#include "cost3d.h"
 #include "conv_plan.h"
 #include "prof.h"
 #include "view_fusion.h"
@@ -36,7 +39,15 @@ struct ForwardGraph {
   unsigned long long last_use = 0;
 };
 
+static void drop_graph(ForwardGraph& g) {
+  if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  if (g.graph) (void)hipGraphDestroy(g.graph);
+  g.exec = nullptr; g.graph = nullptr;
+}
+
+// Owns everything the handle holds on the device: the net's weights and buffers free themselves (layers.h: DevBuf), the captured graphs here.
 struct rgbm_adapose {
+  ~rgbm_adapose() { for (auto& g : graphs) drop_graph(g); }
   AdaPose net;
   int device;
   int opt_version = 0;                 // bumped by set_option / set_chunk: captured graphs of older settings are dropped
@@ -52,22 +63,13 @@ static int ensure_dropout_capacity(rgbm_adapose* h, int B) {
   AdaPose& n = h->net;
   if (2 * B <= n.drop_cap_views) return 0;
   const int views = std::max(2 * B, 2 * n.drop_cap_views);
-  float* m = nullptr;
-  RGBM_CHECK_HIP(hipMalloc(&m, (size_t)views * kDropoutPerView * sizeof(float)));
-  if (n.drop_masks) {
-    (void)hipDeviceSynchronize();      // a forward in flight may still read the old buffer
-    (void)hipFree(n.drop_masks);
-  }
-  n.drop_masks = m;
+  DevBuf m;
+  RGBM_CHECK_HIP(hipMalloc(m.out(), (size_t)views * kDropoutPerView * sizeof(float)));
+  if (n.drop_masks) (void)hipDeviceSynchronize();      // a forward in flight may still read the old buffer
+  n.drop_masks = std::move(m);                         // frees the old one
   n.drop_cap_views = views;
   ++h->opt_version;
   return 0;
-}
-
-static void drop_graph(ForwardGraph& g) {
-  if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  if (g.graph) (void)hipGraphDestroy(g.graph);
-  g.exec = nullptr; g.graph = nullptr;
 }
 
 static AdaPose::Outputs to_out(const rgbm_adapose_out* o) {
@@ -115,53 +117,51 @@ static int forward_call(rgbm_adapose* h, const char* name, int B, const float* i
   return finish_call(h, B, call, h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), call));
 }
 
+// The tail of the one-shot entry points (tests): wait for what was launched and report a device error in the library's way.  Their
+// temporary weights are locals that free themselves behind this, whatever `rc` is.
+static int finish_one_shot(int rc, void* stream) {
+  if (rc) return rc;
+  const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+  if (e == hipSuccess) return 0;
+  set_error(hipGetErrorString(e));
+  return -2;
+}
+
+// Both create entry points: the state dict from the weight descriptors, then a handle around the net `arch` names.  mode: create()'s
+// norm_mode or create_baseline()'s regress_pose.  A net that fails half built frees what it had uploaded when the handle goes.
+static int create_handle(rgbm_adapose_t** h, const char* name, int device, const rgbm_weight_desc* w, int n_w, int dtype, int arch, int mode) {
+  RGBM_REQUIRE(h != nullptr && w != nullptr && n_w > 0, std::string(name) + " arguments");
+  RGBM_REQUIRE(dtype == RGBM_F32 || dtype == RGBM_BF16 || dtype == RGBM_F16 || dtype == RGBM_BF16X3, "dtype must be 0 (fp32), 1 (bf16), 2 (fp16) or 3 (bf16x3)");
+  RGBM_CHECK_HIP(hipSetDevice(device));
+  StateDict sd;
+  for (int i = 0; i < n_w; ++i) {
+    std::string key = w[i].name;
+    if (key.rfind("module.", 0) == 0) key = key.substr(7);
+    HostTensor t;
+    t.data = w[i].data;
+    for (int d = 0; d < w[i].ndim; ++d) t.shape.push_back(w[i].shape[d]);
+    sd[key] = t;
+  }
+  std::unique_ptr<rgbm_adapose> obj(new rgbm_adapose());
+  obj->device = device;
+  if (int rc = arch == AdaPose::ARCH_BASELINE ? obj->net.create_baseline(sd, dtype, mode) : obj->net.create(sd, dtype, mode)) return rc;
+  *h = obj.release();
+  return 0;
+}
+
 extern "C" {
 
 int rgbm_version(void) { return RGBM_VERSION; }
 const char* rgbm_last_error(void) { return last_error_cstr(); }
 
 int rgbm_adapose_create(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype, int norm_mode) {
-  RGBM_REQUIRE(h != nullptr && w != nullptr && n_w > 0, "create arguments");
-  RGBM_REQUIRE(dtype == RGBM_F32 || dtype == RGBM_BF16 || dtype == RGBM_F16 || dtype == RGBM_BF16X3, "dtype must be 0 (fp32), 1 (bf16), 2 (fp16) or 3 (bf16x3)");
   RGBM_REQUIRE(norm_mode == 0 || norm_mode == 1, "norm_mode: 0 = eval-mode (folded) BatchNorm3d, 1 = per-sample statistics");
-  RGBM_CHECK_HIP(hipSetDevice(device));
-  StateDict sd;
-  for (int i = 0; i < n_w; ++i) {
-    std::string name = w[i].name;
-    if (name.rfind("module.", 0) == 0) name = name.substr(7);
-    HostTensor t;
-    t.data = w[i].data;
-    for (int d = 0; d < w[i].ndim; ++d) t.shape.push_back(w[i].shape[d]);
-    sd[name] = t;
-  }
-  rgbm_adapose* obj = new rgbm_adapose();
-  obj->device = device;
-  int rc = obj->net.create(sd, dtype, norm_mode);
-  if (rc) { obj->net.destroy(); delete obj; return rc; }
-  *h = obj;
-  return 0;
+  return create_handle(h, "create", device, w, n_w, dtype, AdaPose::ARCH_V5, norm_mode);
 }
 
 int rgbm_adapose_create_baseline(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype, int regress_pose) {
-  RGBM_REQUIRE(h != nullptr && w != nullptr && n_w > 0, "create_baseline arguments");
-  RGBM_REQUIRE(dtype == RGBM_F32 || dtype == RGBM_BF16 || dtype == RGBM_F16 || dtype == RGBM_BF16X3, "dtype must be 0 (fp32), 1 (bf16), 2 (fp16) or 3 (bf16x3)");
   RGBM_REQUIRE(regress_pose == 0 || regress_pose == 1, "regress_pose: 0 or 1");
-  RGBM_CHECK_HIP(hipSetDevice(device));
-  StateDict sd;
-  for (int i = 0; i < n_w; ++i) {
-    std::string name = w[i].name;
-    if (name.rfind("module.", 0) == 0) name = name.substr(7);
-    HostTensor t;
-    t.data = w[i].data;
-    for (int d = 0; d < w[i].ndim; ++d) t.shape.push_back(w[i].shape[d]);
-    sd[name] = t;
-  }
-  rgbm_adapose* obj = new rgbm_adapose();
-  obj->device = device;
-  int rc = obj->net.create_baseline(sd, dtype, regress_pose);
-  if (rc) { obj->net.destroy(); delete obj; return rc; }
-  *h = obj;
-  return 0;
+  return create_handle(h, "create_baseline", device, w, n_w, dtype, AdaPose::ARCH_BASELINE, regress_pose);
 }
 
 int rgbm_view_fusion_scratch_bytes(int B, int P, size_t* bytes) {
@@ -173,20 +173,17 @@ int rgbm_view_fusion_scratch_bytes(int B, int P, size_t* bytes) {
 int rgbm_view_fusion(rgbm_adapose_t* h, const float* x1, const float* x2, int B, int P, float* y1, float* y2, void* scratch,
                      size_t scratch_bytes, void* stream) {
   RGBM_REQUIRE(h && x1 && x2 && y1 && y2 && scratch, "view_fusion arguments");
-  RGBM_REQUIRE(h->net.vf_w != nullptr, "view_fusion: the handle holds no attention stack (rgbm_adapose_create_baseline builds one)");
-  return launch_view_fusion(h->net.vf_w, x1, x2, B, P, y1, y2, scratch, scratch_bytes, 2, (hipStream_t)stream);
+  RGBM_REQUIRE(h->net.vf_w, "view_fusion: the handle holds no attention stack (rgbm_adapose_create_baseline builds one)");
+  return launch_view_fusion(h->net.vf_w.get<float>(), x1, x2, B, P, y1, y2, scratch, scratch_bytes, 2, (hipStream_t)stream);
 }
 
 int rgbm_depth_head(rgbm_adapose_t* h, const float* x, int64_t n_rows, float* out, void* stream) {
   RGBM_REQUIRE(h && x && out && n_rows > 0, "depth_head arguments");
-  RGBM_REQUIRE(h->net.dh_w != nullptr, "depth_head: the handle holds no depth_head (rgbm_adapose_create_baseline builds one)");
-  return launch_depth_head(h->net.dh_w, x, (long long)n_rows, out, nullptr, 0, (hipStream_t)stream);
+  RGBM_REQUIRE(h->net.dh_w, "depth_head: the handle holds no depth_head (rgbm_adapose_create_baseline builds one)");
+  return launch_depth_head(h->net.dh_w.get<float>(), x, (long long)n_rows, out, nullptr, 0, (hipStream_t)stream);
 }
 
 int rgbm_adapose_destroy(rgbm_adapose_t* h) {
-  if (!h) return 0;
-  for (auto& g : h->graphs) drop_graph(g);
-  h->net.destroy();
   delete h;
   return 0;
 }
@@ -223,9 +220,9 @@ int rgbm_adapose_set_dropout(rgbm_adapose_t* h, float p, uint64_t seed) {
   RGBM_REQUIRE(h && (p == 0.f || (p > 0.f && p < 1.f)), "set_dropout: p must be 0 (off) or lie in (0, 1)");
   RGBM_REQUIRE(!(is_baseline(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the baseline network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
-  if (!h->net.drop_state) RGBM_CHECK_HIP(hipMalloc(&h->net.drop_state, 2 * sizeof(unsigned long long)));
+  if (!h->net.drop_state) RGBM_CHECK_HIP(hipMalloc(h->net.drop_state.out(), 2 * sizeof(unsigned long long)));
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // every forward issued before this call has drawn its masks
-  RGBM_CHECK_HIP(hipMemset(h->net.drop_state, 0, 2 * sizeof(unsigned long long)));
+  RGBM_CHECK_HIP(hipMemset(h->net.drop_state.get(), 0, 2 * sizeof(unsigned long long)));
   RGBM_CHECK_HIP(hipDeviceSynchronize());
   h->net.drop_p = p;
   h->net.drop_seed = (unsigned long long)seed;
@@ -239,7 +236,7 @@ int rgbm_adapose_dropout_masks(rgbm_adapose_t* h, int B, float* out_dev) {
                std::to_string(h->drop_last_B) + ", not " + std::to_string(B));
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   RGBM_CHECK_HIP(hipDeviceSynchronize());
-  RGBM_CHECK_HIP(hipMemcpy(out_dev, h->net.drop_masks, (size_t)2 * B * kDropoutPerView * sizeof(float), hipMemcpyDeviceToDevice));
+  RGBM_CHECK_HIP(hipMemcpy(out_dev, h->net.drop_masks.get(), (size_t)2 * B * kDropoutPerView * sizeof(float), hipMemcpyDeviceToDevice));
   return 0;
 }
 
@@ -249,7 +246,7 @@ int rgbm_adapose_set_dropout_masks(rgbm_adapose_t* h, int B, const float* masks_
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (int rc = ensure_dropout_capacity(h, B)) return rc;
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // no forward in flight reads the buffer any more
-  RGBM_CHECK_HIP(hipMemcpy(h->net.drop_masks, masks_dev, (size_t)2 * B * kDropoutPerView * sizeof(float), hipMemcpyDeviceToDevice));
+  RGBM_CHECK_HIP(hipMemcpy(h->net.drop_masks.get(), masks_dev, (size_t)2 * B * kDropoutPerView * sizeof(float), hipMemcpyDeviceToDevice));
   h->drop_explicit = B;
   return 0;
 }
@@ -466,13 +463,6 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   else if (nm == "u3") { src = bf.u3; cnt = V * S * S * 64; }
   else if (nm == "feat") { src = bf.feat; cnt = V * S * S * 32; if (n.feat_f32_only()) { src = bf.featf; dt = F32; } else if (n.feat_f16()) dt = F16; }
   else if (nm == "vol") { src = bf.vol; cnt = Vc * D * S * S * 32; }
-  else if (nm == "c0") { src = bf.c[0]; cnt = Vc * D * S * S * 8; }
-  else if (nm == "c2") { src = bf.c[2]; cnt = Vc * (D / 2) * (S / 2) * (S / 2) * 16; }
-  else if (nm == "c4") { src = bf.c[4]; cnt = Vc * (D / 4) * (S / 4) * (S / 4) * 32; }
-  else if (nm == "c6") { src = bf.c[6]; cnt = Vc * (D / 8) * (S / 8) * (S / 8) * 64; }
-  else if (nm == "u7") { src = bf.u7; cnt = Vc * (D / 4) * (S / 4) * (S / 4) * 32; }
-  else if (nm == "u9") { src = bf.u9; cnt = Vc * (D / 2) * (S / 2) * (S / 2) * 16; }
-  else if (nm == "u11") { src = bf.u11; cnt = Vc * D * S * S * 8; }
   else if (nm == "homog") { src = bf.homog; cnt = V * 12; dt = F32; }
   else if (nm == "prob") { src = bf.prob; cnt = V * P * D; dt = F32; }
   // pf96: after a forward of a split-pair net the buffer holds hi / lo pairs (adapose.cpp converts it in place for the pose MLP)
@@ -481,13 +471,18 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   else if (nm == "r6") { src = bf.r6; cnt = V * 6; dt = F32; }
   else if (nm == "fused1" && bf.fused) { src = bf.fused; cnt = (size_t)B * P * 32; dt = F32; }
   else if (nm == "fused2" && bf.fused) { src = bf.fused + (size_t)B * P * 32; cnt = (size_t)B * P * 32; dt = F32; }
+  // the taps of the cost regularisation: the outputs of these rows of kCost3d
+  static const struct { const char* name; int row; } taps3d[] = {{"c0", 0}, {"c2", 2}, {"c4", 4}, {"c6", 6}, {"u7", 7}, {"u9", 8}, {"u11", 9}};
+  int row3d = -1;
+  for (const auto& t : taps3d)
+    if (nm == t.name) { row3d = t.row; src = bf.c3[row3d]; cnt = cost3d_out_elems(row3d, (int)Vc, (int)D, (int)S); }
   if (is_baseline(h))      // the cost-volume buffers do not exist in this handle's workspace
     RGBM_REQUIRE(nm == "feat" || nm == "fused1" || nm == "fused2" || nm == "pf96" || nm == "pf2" || nm == "r6" || nm == "layer4" || nm == "cat" ||
                  nm == "u1" || nm == "u2", "tap '" + nm + "' does not exist in the baseline network");
   RGBM_REQUIRE(src != nullptr, "unknown intermediate name: " + nm);
   // with sparse cost regularisation c0..c5 / u7 / u9 are written only inside the chosen pixels' dependency cones (and c6 is computed
   // from them): the rest of these tensors is whatever the workspace held, so a tap of them is refused instead of returned partly stale
-  const bool tap3d = nm == "c0" || nm == "c2" || nm == "c4" || nm == "c6" || nm == "u7" || nm == "u9";
+  const bool tap3d = row3d >= 0 && row3d < 9;      // u11 exists only with the dense tail, which computes all of it
   RGBM_REQUIRE(!(tap3d && n.sparse_active()), "tap '" + nm + "' needs a dense cost regularisation: set option sparse_dec = 0 before the forward "
                "(the default computes it only inside the chosen pixels' dependency cones)");
   *n_elems = cnt;
@@ -549,11 +544,8 @@ int rgbm_conv_nd(int dtype, const void* in_dev, int N, int D, int H, int W, int 
   RGBM_REQUIRE(in_dev && w_host && out_dev, "conv arguments");
   const ConvGeom g = conv_nd_geom(Cin, Cout, KD, KH, KW, stride_d, stride_hw, pad_d, pad_hw, dil_hw, transposed, act, slope);
   ConvLayer L;
-  int rc = L.init(dtype, g, w_host, bias_host, bn_scale_host, bn_shift_host, Cin_pad, Cout_pad);
-  if (!rc) rc = L.run(in_dev, out_dev, N, D, H, W, Cout_pad, res_dev, res_mode, nullptr, 0, (hipStream_t)stream);
-  if (!rc) { hipError_t e = hipStreamSynchronize((hipStream_t)stream); if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = -2; } }
-  L.destroy();
-  return rc;
+  if (int rc = L.init(dtype, g, w_host, bias_host, bn_scale_host, bn_shift_host, Cin_pad, Cout_pad)) return rc;
+  return finish_one_shot(L.run(in_dev, out_dev, N, D, H, W, Cout_pad, res_dev, res_mode, nullptr, 0, (hipStream_t)stream), stream);
 }
 
 int rgbm_conv_plan(int dtype, int N, int D, int H, int W, int Cin, int Cin_pad, int Cout, int Cout_pad, int KD, int KH, int KW,
@@ -583,34 +575,25 @@ int rgbm_upsample_conv3x3(int dtype, const void* in_dev, int V, int h, int w, in
                           const float* bias_host, int act, float slope, void* z_scratch_dev, void* out_dev, void* stream) {
   RGBM_REQUIRE(in_dev && w_host && z_scratch_dev && out_dev, "upsample_conv3x3 arguments");
   UpConvLayer L;
-  int rc = L.init(dtype, Cin, Cout, w_host, bias_host, act, slope);
-  if (!rc) rc = L.run(in_dev, z_scratch_dev, out_dev, V, h, w, Cout, (hipStream_t)stream);
-  if (!rc) { hipError_t e = hipStreamSynchronize((hipStream_t)stream); if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = -2; } }
-  L.destroy();
-  return rc;
+  if (int rc = L.init(dtype, Cin, Cout, w_host, bias_host, act, slope)) return rc;
+  return finish_one_shot(L.run(in_dev, z_scratch_dev, out_dev, V, h, w, Cout, (hipStream_t)stream), stream);
 }
 
 int rgbm_upsample_conv3x3_final(int dtype, const void* in_dev, int V, int h, int w, const float* w3_host, const float* b3_host,
                                 float slope, const float* wf_host, const float* bf_host, void* out_dev, int out_f32, void* stream) {
   RGBM_REQUIRE(in_dev && w3_host && b3_host && wf_host && bf_host && out_dev, "upsample_conv3x3_final arguments");
   UpConvFinal L;
-  int rc = L.init(dtype, w3_host, b3_host, slope, wf_host, bf_host);
-  if (!rc) rc = L.run(in_dev, out_dev, out_f32, V, h, w, (hipStream_t)stream);
-  if (!rc) { hipError_t e = hipStreamSynchronize((hipStream_t)stream); if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = -2; } }
-  L.destroy();
-  return rc;
+  if (int rc = L.init(dtype, w3_host, b3_host, slope, wf_host, bf_host)) return rc;
+  return finish_one_shot(L.run(in_dev, out_dev, out_f32, V, h, w, (hipStream_t)stream), stream);
 }
 
 int rgbm_stem(int dtype, const float* img1_dev, const float* img2_dev, const float* w_host, void* out_dev, int B, int S, void* stream) {
   RGBM_REQUIRE(img1_dev && img2_dev && w_host && out_dev && B > 0, "stem arguments");
   std::vector<float> pk;
   stem_pack(w_host, pk);
-  void* wd = nullptr;
-  int rc = upload_packed(pk, dtype, &wd);
-  if (!rc) rc = launch_stem(dtype, img1_dev, img2_dev, wd, out_dev, B, 2 * B, S, (hipStream_t)stream);
-  if (!rc) { hipError_t e = hipStreamSynchronize((hipStream_t)stream); if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = -2; } }
-  if (wd) (void)hipFree(wd);
-  return rc;
+  DevBuf wd;
+  if (int rc = upload_packed(pk, dtype, wd)) return rc;
+  return finish_one_shot(launch_stem(dtype, img1_dev, img2_dev, wd.get(), out_dev, B, 2 * B, S, (hipStream_t)stream), stream);
 }
 
 int rgbm_bn_per_sample_scratch_bytes(int V, size_t* bytes) {
@@ -669,34 +652,28 @@ int rgbm_prof_stop(double* stats) {
 extern "C" int rgbm_conv3d_tile(int layer, int dtype, const void* in_dev, int N, int D, int H, int W, const float* w_host,
                                 const float* bn_scale_host, const float* bn_shift_host, const void* res_dev, void* out_dev,
                                 void* stream) {
-  static const int cin[10] = {32, 8, 16, 16, 32, 32, 64, 64, 32, 16};
-  static const int cout[10] = {8, 16, 16, 32, 32, 64, 64, 32, 16, 8};
-  static const int stride[10] = {1, 2, 1, 2, 1, 2, 1, 1, 1, 1};
-  RGBM_REQUIRE(layer >= 0 && layer < 10 && in_dev && w_host && bn_scale_host && bn_shift_host && out_dev, "conv3d_tile arguments");
-  const bool tr = layer >= 7;
-  const int coutp = cout[layer] < 16 ? 16 : cout[layer];
+  RGBM_REQUIRE(layer >= 0 && layer < kCost3dLayers && in_dev && w_host && bn_scale_host && bn_shift_host && out_dev, "conv3d_tile arguments");
+  const Cost3dLayer& L = kCost3d[layer];
+  const int coutp = cost3d_coutp(layer);
   std::vector<float> packed;
-  conv3d_tile_pack(w_host, bn_scale_host, cin[layer], cout[layer], coutp, tr, dtype, packed);
-  void* wdev = nullptr; float* bdev = nullptr;
-  if (upload_packed(packed, dtype, &wdev)) return -2;
+  conv3d_tile_pack(w_host, bn_scale_host, L.cin, L.cout, coutp, L.transposed, dtype, packed);
+  DevBuf wdev, bdev;
+  if (upload_packed(packed, dtype, wdev)) return -2;
   std::vector<float> bpad(coutp, 0.f);
-  for (int o = 0; o < cout[layer]; ++o) bpad[o] = bn_shift_host[o];
-  if (upload_f32(bpad.data(), bpad.size(), &bdev)) return -2;
+  for (int o = 0; o < L.cout; ++o) bpad[o] = bn_shift_host[o];
+  if (upload_f32(bpad.data(), bpad.size(), bdev)) return -2;
   Conv3dTileDesc d;
   memset(&d, 0, sizeof(d));
-  d.in = in_dev; d.wgt = wdev; d.out = out_dev; d.bias = bdev; d.res = res_dev;
+  d.in = in_dev; d.wgt = wdev.get(); d.out = out_dev; d.bias = bdev.get<float>(); d.res = res_dev;
   d.N = N; d.Di = D; d.Hi = H; d.Wi = W;
-  if (tr) { d.Do = 2 * D; d.Ho = 2 * H; d.Wo = 2 * W; d.Dq = D; d.Hq = H; d.Wq = W; }
+  if (L.transposed) { d.Do = 2 * D; d.Ho = 2 * H; d.Wo = 2 * W; d.Dq = D; d.Hq = H; d.Wq = W; }
   else {
-    const int s = stride[layer];
+    const int s = L.stride;
     d.Do = (D + 2 - 3) / s + 1; d.Ho = (H + 2 - 3) / s + 1; d.Wo = (W + 2 - 3) / s + 1;
     d.Dq = d.Do; d.Hq = d.Ho; d.Wq = d.Wo;
   }
-  d.Cout = cout[layer]; d.relu = 1; d.prof_variant = -1;
-  int rc = launch_conv3d_tile(layer, dtype, d, (hipStream_t)stream);
-  if (!rc) { hipError_t e = hipStreamSynchronize((hipStream_t)stream); if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = -2; } }
-  (void)hipFree(wdev); (void)hipFree(bdev);
-  return rc;
+  d.Cout = L.cout; d.relu = 1; d.prof_variant = -1;
+  return finish_one_shot(launch_conv3d_tile(layer, dtype, d, (hipStream_t)stream), stream);
 }
 
 // Kernel-level entry for the depth-sweeping conv0 + fused plane sweep (tests): bf16 features [V][H][W][32] -> [V][D][H][W][8].
@@ -709,23 +686,20 @@ static int conv0_sweep_entry(int dtype, int feat_f16, const void* feat_dev, cons
   if (int rc = launch_homography(P_views_dev, homog_scratch, V, B, (hipStream_t)stream)) return rc;
   std::vector<float> packed;
   conv0_sweep_pack(w_host, bn_scale_host, packed);
-  void* wdev = nullptr; float* bdev = nullptr;
-  if (dtype == BF16X3) { if (conv0_sweep_x3_upload(packed, &wdev)) return -2; }
-  else if (upload_packed(packed, feat_f16 ? (int)F16 : dtype, &wdev)) return -2;
-  std::vector<float> bpad(16, 0.f);
-  for (int o = 0; o < 8; ++o) bpad[o] = bn_shift_host[o];
-  if (upload_f32(bpad.data(), bpad.size(), &bdev)) return -2;
+  DevBuf wdev, bdev;
+  if (dtype == BF16X3) { if (conv0_sweep_x3_upload(packed, wdev.out())) return -2; }
+  else if (upload_packed(packed, feat_f16 ? (int)F16 : dtype, wdev)) return -2;
+  std::vector<float> bpad(cost3d_coutp(0), 0.f);
+  for (int o = 0; o < kCost3d[0].cout; ++o) bpad[o] = bn_shift_host[o];
+  if (upload_f32(bpad.data(), bpad.size(), bdev)) return -2;
   Conv3dTileDesc d;
   memset(&d, 0, sizeof(d));
-  d.wgt = wdev; d.out = out_dev; d.bias = bdev;
+  d.wgt = wdev.get(); d.out = out_dev; d.bias = bdev.get<float>();
   d.N = V; d.Di = D; d.Hi = H; d.Wi = W; d.Do = D; d.Ho = H; d.Wo = W; d.Dq = D; d.Hq = H; d.Wq = W;
-  d.Cout = 8; d.relu = 1; d.prof_variant = -1;
+  d.Cout = kCost3d[0].cout; d.relu = 1; d.prof_variant = -1;
   d.feat = feat_dev; d.homog = homog_scratch; d.depths = depths_dev; d.v0 = 0; d.V = V; d.B = B;
   d.feat_f16 = feat_f16;
-  int rc = dtype == BF16X3 ? launch_conv0_sweep_x3(d, (hipStream_t)stream) : launch_conv0_sweep(d, dtype, (hipStream_t)stream);
-  if (!rc) { hipError_t e = hipStreamSynchronize((hipStream_t)stream); if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = -2; } }
-  (void)hipFree(wdev); (void)hipFree(bdev);
-  return rc;
+  return finish_one_shot(dtype == BF16X3 ? launch_conv0_sweep_x3(d, (hipStream_t)stream) : launch_conv0_sweep(d, dtype, (hipStream_t)stream), stream);
 }
 
 extern "C" int rgbm_conv0_sweep_dt(int dtype, const void* feat_dev, const float* P_views_dev, const float* depths_dev,

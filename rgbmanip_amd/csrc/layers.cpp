@@ -56,11 +56,13 @@ int persistent_grid_cus(int* n_cu) {
   return 0;
 }
 
-int upload_f32(const float* host, size_t n, float** dev) {
-  RGBM_CHECK_HIP(hipMalloc((void**)dev, n * sizeof(float)));
-  RGBM_CHECK_HIP(hipMemcpy(*dev, host, n * sizeof(float), hipMemcpyHostToDevice));
+static int upload_bytes(const void* host, size_t bytes, DevBuf& dev) {
+  RGBM_CHECK_HIP(hipMalloc(dev.out(), bytes));
+  RGBM_CHECK_HIP(hipMemcpy(dev.get(), host, bytes, hipMemcpyHostToDevice));
   return 0;
 }
+
+int upload_f32(const float* host, size_t n, DevBuf& dev) { return upload_bytes(host, n * sizeof(float), dev); }
 
 static inline unsigned short host_f32_to_f16(float f) {
   const _Float16 h = (_Float16)(f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f));      // round to nearest even, saturating
@@ -85,13 +87,13 @@ bool weights_fit_f16(const std::vector<float>& w) {
 }
 
 // host fp32 values -> device array in the storage type `dtype`
-int upload_packed(const std::vector<float>& w, int dtype, void** dev) {
+int upload_packed(const std::vector<float>& w, int dtype, DevBuf& dev) {
   if (dtype == BF16 || dtype == F16) {
     std::vector<unsigned short> h(w.size());
     for (size_t i = 0; i < w.size(); ++i) h[i] = dtype == BF16 ? host_f32_to_bf16(w[i]) : host_f32_to_f16(w[i]);
-    RGBM_CHECK_HIP(hipMalloc(dev, h.size() * 2));
-    RGBM_CHECK_HIP(hipMemcpy(*dev, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-  } else if (dtype == BF16X3) {
+    return upload_bytes(h.data(), h.size() * 2, dev);
+  }
+  if (dtype == BF16X3) {
     // split-pair chunks (common.h, bx3_t): every 4 consecutive values become {hi01, hi23, lo01, lo23}
     RGBM_REQUIRE(w.size() % 4 == 0, "bf16x3 weights: element count must be a multiple of 4");
     std::vector<unsigned> h(w.size());
@@ -107,13 +109,9 @@ int upload_packed(const std::vector<float>& w, int dtype, void** dev) {
       h[i] = hi[0] | ((unsigned)hi[1] << 16); h[i + 1] = hi[2] | ((unsigned)hi[3] << 16);
       h[i + 2] = lo[0] | ((unsigned)lo[1] << 16); h[i + 3] = lo[2] | ((unsigned)lo[3] << 16);
     }
-    RGBM_CHECK_HIP(hipMalloc(dev, h.size() * 4));
-    RGBM_CHECK_HIP(hipMemcpy(*dev, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-  } else {
-    RGBM_CHECK_HIP(hipMalloc(dev, w.size() * 4));
-    RGBM_CHECK_HIP(hipMemcpy(*dev, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    return upload_bytes(h.data(), h.size() * 4, dev);
   }
-  return 0;
+  return upload_bytes(w.data(), w.size() * 4, dev);
 }
 
 int conv_pack_geom(const ConvGeom& g, int dtype, int Cin_pad, int Cout_pad, int cls, PackedConv* pc) {
@@ -158,14 +156,12 @@ int ConvLayer::init(int dtype_, const ConvGeom& g_, const float* w, const float*
       if (bn_shift) v += bn_shift[o];
       b[o] = v;
     }
-    if (upload_f32(b.data(), b.size(), &bias)) return -2;
-    owned.push_back(bias);
+    if (upload_f32(b.data(), b.size(), bias)) return -2;
   }
 
   auto finish = [&](PackedConv& pc, std::vector<float>& packed) -> int {
-    if (upload_packed(packed, dtype, &pc.w)) return -2;
-    owned.push_back(pc.w);
-    packs.push_back(pc);
+    if (upload_packed(packed, dtype, pc.w)) return -2;
+    packs.push_back(std::move(pc));
     return 0;
   };
 
@@ -202,13 +198,6 @@ int ConvLayer::init(int dtype_, const ConvGeom& g_, const float* w, const float*
     if (finish(pc, packed)) return -2;
   }
   return 0;
-}
-
-void ConvLayer::destroy() {
-  for (void* p : owned) (void)hipFree(p);
-  owned.clear();
-  packs.clear();
-  bias = nullptr;
 }
 
 void conv_out_dims(const ConvGeom& g, int Di, int Hi, int Wi, int& Do, int& Ho, int& Wo) {
@@ -252,8 +241,8 @@ int ConvLayer::build_desc(ConvDesc& d, const void* in, void* out, int N, int Di,
   RGBM_REQUIRE(!packs.empty(), "conv layer not initialised");
   const PackedConv& pc = packs[cls];
   conv_desc_geom(d, g, pc, Cin_pad, Cout_pad, N, Di, Hi, Wi, ldo, cls);
-  d.in = in; d.out = out; d.res = res; d.wgt = pc.w;
-  d.bias = bias_override ? bias_override : bias;
+  d.in = in; d.out = out; d.res = res; d.wgt = pc.w.get();
+  d.bias = bias_override ? bias_override : bias.get<float>();
   d.bias_stride = bias_override ? bias_stride : 0;
   d.res_mode = res ? res_mode : RES_NONE;
   d.out_f32 = (out_plain_f32 && dtype == BF16X3) ? 1 : 0;
@@ -285,7 +274,7 @@ int ConvLayer::run_then_1x1(const ConvLayer& next, const void* in, void* mid, in
   if (allow_fuse && is1x1 && !g.transposed && dtype_size(dtype) == 2 && next.dtype == dtype && next.Cin_pad == Cout_pad) {
     ConvDesc d;
     if (int rc = build_desc(d, in, mid, N, Di, Hi, Wi, ldmid, nullptr, RES_NONE, nullptr, 0, 0)) return rc;
-    d.w2 = next.packs[0].w; d.bias2 = next.bias; d.out2 = out2; d.ldo2 = ldo2; d.cout2 = next.Cout_pad;
+    d.w2 = next.packs[0].w.get(); d.bias2 = next.bias.get<float>(); d.out2 = out2; d.ldo2 = ldo2; d.cout2 = next.Cout_pad;
     d.kpad2 = next.packs[0].Kpad; d.act2 = ng.act; d.slope2 = ng.slope;
     if (conv_ws64_eligible(d, dtype)) {
       d.algo_flops += 2.0 * (double)d.M * ng.Cout * ng.Cin;
@@ -323,23 +312,15 @@ int UpConvLayer::init(int dtype, int Cin, int Cout_, const float* w, const float
   } else {
     if (int rc = gemm.init(dtype, g, wz.data(), nullptr, nullptr, nullptr, Cin, 9 * Cout)) return rc;
   }
-  if (bias_h) { if (upload_f32(bias_h, Cout, &bias)) return -2; }
+  if (bias_h) { if (upload_f32(bias_h, Cout, bias)) return -2; }
   return 0;
-}
-
-void UpConvLayer::destroy() {
-  gemm.destroy();
-  gemm2.destroy();
-  split = 0;
-  if (bias) (void)hipFree(bias);
-  bias = nullptr;
 }
 
 int UpConvLayer::run(const void* in, void* z, void* out, int V, int h, int w, int ldo, hipStream_t s, const float* drop) const {
   if (int rc = gemm.run(in, z, V, 1, h, w, 9 * Cout, nullptr, RES_NONE, nullptr, 0, s)) return rc;
   if (split)
     if (int rc = gemm2.run(in, reinterpret_cast<char*>(z) + (size_t)split * dtype_size(gemm.dtype), V, 1, h, w, 9 * Cout, nullptr, RES_NONE, nullptr, 0, s)) return rc;
-  return launch_upconv_combine(gemm.dtype, z, bias, out, V, h, w, Cout, ldo, act, slope, s, drop);
+  return launch_upconv_combine(gemm.dtype, z, bias.get<float>(), out, V, h, w, Cout, ldo, act, slope, s, drop);
 }
 
 int UpConvFinal::init(int dtype_, const float* w3, const float* b3, float slope_, const float* wfin, const float* bfin) {
@@ -349,25 +330,15 @@ int UpConvFinal::init(int dtype_, const float* w3, const float* b3, float slope_
   for (int t = 0; t < 9; ++t)
     for (int o = 0; o < 64; ++o)
       for (int c = 0; c < 64; ++c) z[((size_t)t * 64 + o) * 64 + c] = w3[((size_t)o * 64 + c) * 9 + t];
-  if (int rc = upload_packed(z, dtype, &wz)) return rc;
-  if (int rc = upload_packed(f, dtype, &wf)) return rc;
-  if (dtype == BF16 && weights_fit_f16(f)) if (int rc = upload_packed(f, F16, &wf_h)) return rc;      // else: no f16 tail (AdaPose::feat_f16)
-  if (upload_f32(b3, 64, &bias) || upload_f32(bfin, 32, &biasf)) return -2;
+  if (int rc = upload_packed(z, dtype, wz)) return rc;
+  if (int rc = upload_packed(f, dtype, wf)) return rc;
+  if (dtype == BF16 && weights_fit_f16(f)) if (int rc = upload_packed(f, F16, wf_h)) return rc;      // else: no f16 tail (AdaPose::feat_f16)
+  if (upload_f32(b3, 64, bias) || upload_f32(bfin, 32, biasf)) return -2;
   return 0;
 }
 
-void UpConvFinal::destroy() {
-  if (wz) (void)hipFree(wz);
-  if (wf) (void)hipFree(wf);
-  if (wf_h) (void)hipFree(wf_h);
-  wf_h = nullptr;
-  if (bias) (void)hipFree(bias);
-  if (biasf) (void)hipFree(biasf);
-  wz = wf = nullptr; bias = biasf = nullptr;
-}
-
 int UpConvFinal::run(const void* in, void* out, int out_kind, int V, int h, int w, hipStream_t s) const {
-  return launch_upconv_final(dtype, in, wz, bias, slope, wf, biasf, out, out_kind, V, h, w, s, wf_h);
+  return launch_upconv_final(dtype, in, wz.get(), bias.get<float>(), slope, wf.get(), biasf.get<float>(), out, out_kind, V, h, w, s, wf_h.get());
 }
 
 }  // namespace rgbm

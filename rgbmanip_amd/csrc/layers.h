@@ -16,6 +16,31 @@ struct HostTensor {
 };
 typedef std::map<std::string, HostTensor> StateDict;
 
+// One device allocation that frees itself.  Move-only: whatever holds one cannot be copied, and nothing is shared or counted.  The upload
+// helpers below fill it; out() hands its slot to hipMalloc or to a launcher that returns an allocation through void**.
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+  }
+  void** out() { reset(); return &p_; }
+  template <class T = void> T* get() const { return static_cast<T*>(p_); }
+  explicit operator bool() const { return p_ != nullptr; }
+
+ private:
+  void* p_ = nullptr;
+};
+
 struct ConvGeom {
   int Cin = 0, Cout = 0;         // logical channels
   int KD = 1, KH = 1, KW = 1;
@@ -29,7 +54,7 @@ struct ConvGeom {
 
 // One packed weight set (a transposed conv owns 8, one per output parity class).
 struct PackedConv {
-  void* w = nullptr;             // [Cout_pad][Kpad] in the layer dtype
+  DevBuf w;                      // [Cout_pad][Kpad] in the layer dtype
   int KD = 1, KH = 1, KW = 1, ntaps = 1, Kpad = 0, KT = 0;
 };
 
@@ -45,15 +70,13 @@ struct ConvLayer {
   int dtype = F32;
   int Cin_pad = 0;               // physical input channels (>= Cin, multiple of the 16-byte chunk)
   int Cout_pad = 0;              // physical output channels written (multiple of 4)
-  float* bias = nullptr;         // [Cout_pad] fp32 or null
+  DevBuf bias;                   // [Cout_pad] fp32 or null
   std::vector<PackedConv> packs; // 1, or 8 for transposed
-  std::vector<void*> owned;      // device allocations to free
 
   // weights: [Cout][Cin][KD][KH][KW] (or [Cin][Cout][3][3][3] when transposed), optional per-Cout scale/shift
   // (folded BN) and bias.  Cin_pad: physical channel count of the input tensor.
   int init(int dtype, const ConvGeom& g, const float* w, const float* bias, const float* bn_scale, const float* bn_shift,
            int Cin_pad, int Cout_pad);
-  void destroy();
 
   // Run on input [N][Di][Hi][Wi][Cin_pad] -> output [N][Do][Ho][Wo][ldo] (+ch offset via out pointer).
   // res: optional residual with the output's layout.  bias_override/bias_stride: per-sample bias.
@@ -76,12 +99,11 @@ struct UpConvLayer {
   ConvLayer gemm;                // 1x1: Cin -> 9*Cout rows in (tap, channel) order, no bias, no activation
   ConvLayer gemm2;               // round 6: the stacked rows behind the last multiple of 256 (up_2: 576 = 512 + 64), see init()
   int split = 0;                 // rows of `gemm` when the product runs as two launches (0: one launch)
-  float* bias = nullptr;         // [Cout] fp32 or null
+  DevBuf bias;                   // [Cout] fp32 or null
   int Cout = 0, act = ACT_NONE;
   float slope = 0.f;
   // w: [Cout][Cin][3][3] (nn.Conv2d layout)
   int init(int dtype, int Cin, int Cout, const float* w, const float* bias_h, int act, float slope);
-  void destroy();
   size_t scratch_elems(int V, int h, int w) const { return (size_t)V * h * w * 9 * Cout; }
   // in [V][h][w][Cin] -> z scratch [V][h][w][9*Cout] -> out [V][2h][2w][ldo]
   // drop (optional): Dropout2d factors, drop[v * kDropoutPerView + channel] (kernels.h)
@@ -91,25 +113,24 @@ struct UpConvLayer {
 // PSPNet tail: up_3 (x2 bilinear -> conv3x3 64 -> 64 + bias -> PReLU) and `final` (conv1x1 64 -> 32 + bias) in ONE kernel
 // (upconv_final.hip): neither the up-sampled tensor, nor the tap-stacked z, nor up_3's output reach memory.  16-bit / split pairs.
 struct UpConvFinal {
-  void* wz = nullptr;            // [9 * 64][64] storage type, rows in (tap, channel) order
-  void* wf = nullptr;            // [32][64] storage type
-  void* wf_h = nullptr;          // bf16 nets: the same in f16 (out_kind 2: the f16 tail)
-  float* bias = nullptr;         // [64] up_3 bias
-  float* biasf = nullptr;        // [32] final bias
+  DevBuf wz;                     // [9 * 64][64] storage type, rows in (tap, channel) order
+  DevBuf wf;                     // [32][64] storage type
+  DevBuf wf_h;                   // bf16 nets: the same in f16 (out_kind 2: the f16 tail)
+  DevBuf bias;                   // [64] up_3 bias
+  DevBuf biasf;                  // [32] final bias
   float slope = 0.f;
   int dtype = 0;
-  bool ready() const { return wz != nullptr; }
-  bool f16_ready() const { return wf_h != nullptr; }      // `final`'s weights are representable in f16 (weights_fit_f16): the f16 tail exists
+  bool ready() const { return (bool)wz; }
+  bool f16_ready() const { return (bool)wf_h; }      // `final`'s weights are representable in f16 (weights_fit_f16): the f16 tail exists
   // w3 [64][64][3][3], b3 [64], wfin [32][64], bfin [32] (nn.Conv2d layouts)
   int init(int dtype, const float* w3, const float* b3, float slope, const float* wfin, const float* bfin);
-  void destroy();
   // in [V][h][w][64] -> out [V][2h][2w][32] (storage type; plain fp32: split-pair path only; f16: bf16 path only)
   int run(const void* in, void* out, int out_kind, int V, int h, int w, hipStream_t s) const;      // out_kind: launch_upconv_final's out_f32 (0 storage type, 1 plain fp32, 2 f16)
 };
 
 // device upload helpers
 bool weights_fit_f16(const std::vector<float>& w);      // no value saturates in IEEE f16, no appreciable weight mass below its smallest normal
-int upload_packed(const std::vector<float>& w, int dtype, void** dev);      // host fp32 -> device array in storage type dtype
-int upload_f32(const float* host, size_t n, float** dev);
+int upload_packed(const std::vector<float>& w, int dtype, DevBuf& dev);      // host fp32 -> device array in storage type dtype
+int upload_f32(const float* host, size_t n, DevBuf& dev);
 
 }  // namespace rgbm

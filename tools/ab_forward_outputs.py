@@ -4,7 +4,11 @@
 usage: ab_forward_outputs.py out.npz            (in each tree)
        ab_forward_outputs.py --compare a.npz b.npz
 
-Only the Python names both trees have are used.  Arrays are compared as bytes (view2_heads = 0 fills the view-2 outputs with NaN)."""
+Only the Python names both trees have are used.  Arrays are compared as bytes (view2_heads = 0 fills the view-2 outputs with NaN).
+Besides the forwards of the v5 and the baseline network the list holds the 3-D taps of a dense cost regularisation (element count and
+SHA-256 each), and under "sizes" the node counts of the captured graphs, workspace_bytes(B) for B = 1, 2, 3, 256 and feature_bytes
+(the baseline network has no feature cache, so only its workspace sizes are listed)."""
+import hashlib
 import os
 import sys
 
@@ -31,7 +35,7 @@ def main(path):
     import torch
     from rgbmanip_amd import synth
     from rgbmanip_amd.adapose import AdaPoseNet
-    out = {}
+    out, sizes = {}, {}
     sd = synth.adapose_state_dict(seed=0, prefix="module.")
     inputs = {B: synth.adapose_inputs(B, seed=0) for B in (1, 2, 4)}      # B = 2: the batch of tests/golden/adapose_b2*.npz
 
@@ -94,6 +98,32 @@ def main(path):
         put(f"{dt} stop_after=1 B=2", {"feat": net.fetch(2, "feat", 4 * 224 * 224 * 32), "layer4": net.fetch(2, "layer4", 4 * 28 * 28 * 512)})
         call(net, 2, stop_after=2)
         put(f"{dt} stop_after=2 B=2", {"prob": net.fetch(2, "prob", 4 * 1024 * 24)})
+    # the baseline network (no cost volume): two chunks of poses
+    for dt in ("bf16", "fp32"):
+        for rp in (True, False):
+            bsd = synth.baseline_state_dict(seed=0, regress_pose=rp)
+            for v2h in ((1, 0) if dt == "bf16" else (1,)):
+                net = AdaPoseNet(bsd, dtype=dt, arch="baseline", regress_pose=rp, max_chunk_views=2, options={"view2_heads": v2h})
+                put(f"{dt} baseline regress_pose={rp} view2_heads={v2h} B=2", call(net, 2))
+                sizes[f"baseline {dt} regress_pose={rp} view2_heads={v2h}"] = [net.workspace_bytes(B) for B in (1, 2, 3, 256)]
+    # the 3-D taps of a dense cost regularisation, B = 1: element count and SHA-256 of the bytes (c0 alone is 77 MB)
+    for dt in ("bf16", "fp32"):
+        for taps, kw in ((("c0", "c2", "c4", "c6", "u7", "u9"), {}), (("u11",), dict(sparse_tail=0))):
+            net = AdaPoseNet(sd, dtype=dt, options={"sparse_dec": 0}, **kw)
+            call(net, 1)
+            torch.cuda.synchronize()
+            for t in taps:
+                a = net.fetch(1, t, 2 * 24 * 224 * 224 * 8).cpu().numpy()
+                put(f"{dt} sparse_dec=0 B=1 tap {t}", {"count": a.size, "sha256": np.frombuffer(hashlib.sha256(a.tobytes()).digest(), np.uint8)})
+    # what a captured forward consists of, and what the plan asks for
+    for dt in ("bf16", "bf16x3", "fp32"):
+        net = AdaPoseNet(sd, dtype=dt, graph=True)
+        for rep in range(2):
+            call(net, 1)
+        sizes[f"{dt} last_graph_nodes"] = [net.last_graph_nodes]
+        sizes[f"{dt} workspace_bytes"] = [net.workspace_bytes(B) for B in (1, 2, 3, 256)]
+        sizes[f"{dt} feature_bytes"] = [net.feature_bytes]
+    put("sizes", {k: np.asarray(v, np.int64) for k, v in sizes.items()})
     torch.cuda.synchronize()
     np.savez(path, **out)
     print(f"{len(out)} arrays -> {path}")
