@@ -27,6 +27,9 @@ import numpy as np
 from .postproc_ref import DEFAULT_BBOX, compute_scale, mix32
 
 RANSAC_ITERS, RANSAC_CONF, REPROJ_ERR, MODEL_POINTS = 100, 0.99, 3.0, 5
+# Test knob, 0 in every normal use: turns the basis that `epnp` gets for the null space of a five-point system by this angle.  A case
+# whose RANSAC scan changes under it cannot be compared hypothesis by hypothesis with another eigen-solver (tests/pnp_cases.py).
+NULL_BASIS_ANGLE = 0.0
 
 
 # ------------------------------------------------------------------------------------------------ lib/utils.py:121-195
@@ -66,21 +69,70 @@ def nocs_matches(left_pts2d, left_nocs, right_pts2d, right_nocs, left_pose, righ
     return ml[ok], mr[ok]
 
 
-def left_scale_from_matches(left_pts2d, left_nocs, left_proj, left_pose, right_pts2d, right_nocs, right_proj, right_pose, K):
-    """utils.py:121-195 -> (left_scale, n_matches); left_scale is NaN without a valid pair (np.median of an empty list)."""
+def pairs_kept(cam_pts, nocs_pts):
+    """How many i < j pairs pass both gates of compute_scale (nocs distance > 0.01, real distance < 0.3): half of what the
+    reference's full n x n list keeps (the diagonal fails the first gate), and the length of the list whose median csrc/pnp.hip
+    takes."""
+    i, j = np.triu_indices(cam_pts.shape[0], 1)
+    with np.errstate(all="ignore"):
+        real = np.linalg.norm(cam_pts[i] - cam_pts[j], axis=-1)
+        nocs = np.linalg.norm(nocs_pts[i] - nocs_pts[j], axis=-1)
+        return int(((nocs > 0.01) & (real < 0.3)).sum())
+
+
+def left_scale_from_matches(left_pts2d, left_nocs, left_proj, left_pose, right_pts2d, right_nocs, right_proj, right_pose, K, info=None):
+    """utils.py:121-195 -> (left_scale, n_matches); left_scale is NaN without a valid pair (np.median of an empty list).
+    `info` (a dict) receives n_pairs_kept."""
     ml, mr = nocs_matches(left_pts2d, left_nocs, right_pts2d, right_nocs, left_pose, right_pose, K)
+    if info is not None:
+        info["n_pairs_kept"] = 0
     if len(ml) == 0:
         return float("nan"), 0
     X = triangulate_points(left_proj[:3], right_proj[:3], left_pts2d[ml].T.astype(np.float64), right_pts2d[mr].T.astype(np.float64))
-    X = X / X[3]
-    left_pts = (left_pose @ X)[:3].T
     with np.errstate(all="ignore"):
+        X = X / X[3]
+        left_pts = (left_pose @ X)[:3].T
+        if info is not None:
+            info["n_pairs_kept"] = pairs_kept(left_pts, left_nocs[ml])
         return float(compute_scale(left_pts, left_nocs[ml])), len(ml)
 
 
 # ------------------------------------------------------------------------------------------------ EPnP (OpenCV epnp.cpp)
 def _solve_ls(A, b):
     return np.linalg.lstsq(A, b, rcond=None)[0]
+
+
+def jacobi_eigh(A):
+    """Cyclic Jacobi on a small symmetric matrix, rotation by rotation as `eig_sym` of csrc/pnp.hip: (eigenvalues ascending,
+    eigenvectors in the columns).  Used for the SIGNS of the eigenvectors only (see epnp): they are what the rotations, each by at
+    most 45 degrees from the identity, and the final selection sort leave."""
+    A = np.array(A, dtype=np.float64)
+    n = A.shape[0]
+    V = np.eye(n)
+    for _ in range(64):
+        off = sum(A[i, j] * A[i, j] for i in range(n) for j in range(i + 1, n))
+        diag = sum(A[i, i] * A[i, i] for i in range(n))
+        if not off > 1e-60 * (diag + off):
+            break
+        for p in range(n - 1):
+            for q in range(p + 1, n):
+                apq = A[p, q]
+                if apq == 0.0:
+                    continue
+                theta = (A[q, q] - A[p, p]) / (2.0 * apq)
+                t = (1.0 if theta >= 0 else -1.0) / (abs(theta) + np.sqrt(theta * theta + 1.0))
+                c = 1.0 / np.sqrt(t * t + 1.0)
+                s = t * c
+                A[:, p], A[:, q] = c * A[:, p] - s * A[:, q], s * A[:, p] + c * A[:, q]
+                A[p, :], A[q, :] = c * A[p, :] - s * A[q, :], s * A[p, :] + c * A[q, :]
+                V[:, p], V[:, q] = c * V[:, p] - s * V[:, q], s * V[:, p] + c * V[:, q]
+    ev = np.diag(A).copy()
+    for i in range(n - 1):                                   # selection sort, as the kernel's: a stable sort may order equals otherwise
+        m = i + int(np.argmin(ev[i:]))
+        if m != i:
+            ev[[i, m]] = ev[[m, i]]
+            V[:, [i, m]] = V[:, [m, i]]
+    return ev, V
 
 
 def epnp(pw, uv, K):
@@ -93,6 +145,14 @@ def epnp(pw, uv, K):
     pw0 = pw - cws[0]
     dc, uct = np.linalg.eigh(pw0.T @ pw0)                   # ascending; OpenCV's SVD gives them descending
     dc, uct = dc[::-1], uct[:, ::-1].T
+    # The sign of a principal axis is its solver's accident (LAPACK here, cyclic Jacobi in csrc/pnp.hip, OpenCV's Jacobi SVD in the
+    # reference), and it matters: a flipped axis mirrors a control point, and on noisy points EPnP then returns another pose (up to
+    # 1e-2 in R on the cases of tests/pnp_cases.py, 2e-5 after VVS).  A sign says nothing about right or wrong, so the axes (LAPACK's
+    # values) take the signs of the kernel's solver, restated in jacobi_eigh.  OpenCV's own signs are unpinned like the rest of this file.
+    _, vj = jacobi_eigh(pw0.T @ pw0)
+    for i in range(3):
+        if uct[i] @ vj[:, 2 - i] < 0:
+            uct[i] = -uct[i]
     for i in range(1, 4):
         cws[i] = cws[0] + np.sqrt(max(dc[i - 1], 0.0) / n) * uct[i - 1]
     CC = (cws[1:] - cws[0]).T                               # columns = control axes
@@ -106,6 +166,11 @@ def epnp(pw, uv, K):
         M[1::2, 3 * j + 1] = al[:, j] * fv
         M[1::2, 3 * j + 2] = al[:, j] * (vc - uv[:, 1])
     w, V = np.linalg.eigh(M.T @ M)                           # ascending: V[:, 0] is OpenCV's ut[11]
+    if 2 * n < 12 and NULL_BASIS_ANGLE:
+        # five points: M has 10 rows, so M^T M has an exact two-dimensional null space and V[:, 0], V[:, 1] are WHATEVER basis of
+        # it the solver returns.  The beta approximations below start from that basis, and now and then end in another pose.
+        c, s = np.cos(NULL_BASIS_ANGLE), np.sin(NULL_BASIS_ANGLE)
+        V[:, 0], V[:, 1] = c * V[:, 0] - s * V[:, 1], s * V[:, 0] + c * V[:, 1]
     v = [V[:, k] for k in range(4)]                          # v[0] = smallest eigenvalue
     pairs = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
     dv = [[v[i][3 * a:3 * a + 3] - v[i][3 * b:3 * b + 3] for (a, b) in pairs] for i in range(4)]
@@ -202,21 +267,31 @@ def hash_subset(seed, pose, it, n):
     return np.array(out)
 
 
-def solve_pnp_ransac(pw, uv, K, seed=0, pose=0):
-    """cv2.solvePnPRansac(flags=SOLVEPNP_EPNP, reprojectionError=3.0): (ok, R, t, inlier mask)."""
+def solve_pnp_ransac(pw, uv, K, seed=0, pose=0, info=None):
+    """cv2.solvePnPRansac(flags=SOLVEPNP_EPNP, reprojectionError=3.0): (ok, R, t, inlier mask).
+    `info` (a dict) receives what the scan did: n_examined (the value of `it` when the scan ends, info[:, 3] of csrc/pnp.hip),
+    n_failed_hyp (examined hypotheses whose EPnP was non-finite) and, when a hypothesis was kept, kept_sq_err (the squared
+    reprojection error of every point under it).
+    A non-finite final EPnP over the inliers gives ok = False: that is the KERNEL's convention (`if (!ok) s_best = -1` in
+    csrc/pnp.hip), restated here so that both sides agree; what OpenCV itself does there is unpinned, like the rest of this file."""
     n = pw.shape[0]
     thr = REPROJ_ERR * REPROJ_ERR
-    best, best_mask, niters, it = 0, None, RANSAC_ITERS, 0
+    best, best_mask, niters, it, n_failed, kept_err = 0, None, RANSAC_ITERS, 0, 0, None
     while it < niters:
         sub = hash_subset(seed, pose, it, n)
         it += 1
-        R, t = epnp(pw[sub], uv[sub], K)
+        try:
+            R, t = epnp(pw[sub], uv[sub], K)
+        except np.linalg.LinAlgError:                      # LAPACK refuses a non-finite matrix: a failed hypothesis all the same
+            R = t = np.full(3, np.nan)
         if not (np.isfinite(R).all() and np.isfinite(t).all()):
+            n_failed += 1
             continue
-        mask = reproj_sq_err(pw, uv, K, R, t) <= thr
+        sq = reproj_sq_err(pw, uv, K, R, t)
+        mask = sq <= thr
         good = int(mask.sum())
         if good > max(best, MODEL_POINTS - 1):
-            best, best_mask = good, mask
+            best, best_mask, kept_err = good, mask, sq
             ep = (n - good) / n
             num, den = max(1.0 - RANSAC_CONF, np.finfo(float).tiny), 1.0 - (1.0 - ep) ** MODEL_POINTS
             if den < np.finfo(float).tiny:
@@ -224,9 +299,15 @@ def solve_pnp_ransac(pw, uv, K, seed=0, pose=0):
             else:
                 num, den = np.log(num), np.log(den)
                 niters = niters if (den >= 0 or -num >= niters * (-den)) else int(np.rint(num / den))
+    if info is not None:
+        info.update(n_examined=it, n_failed_hyp=n_failed)
     if best_mask is None:
         return False, None, None, None
+    if info is not None:
+        info["kept_sq_err"] = kept_err
     R, t = epnp(pw[best_mask], uv[best_mask], K)
+    if not (np.isfinite(R).all() and np.isfinite(t).all()):
+        return False, None, None, None
     return True, R, t, best_mask
 
 
@@ -239,9 +320,10 @@ def rodrigues_to_R(r):
     return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
 
 
-def refine_vvs(pw, uv, K, R, t, iters=20, eps=1e-6, lam=1.0):
+def refine_vvs(pw, uv, K, R, t, iters=20, eps=1e-6, lam=1.0, trace=None):
     """cv2.solvePnPRefineVVS: Gauss-Newton on SE(3) over the normalised image coordinates, update cMo <- exp(-dq)^-1 ... written as
-    the left-multiplied inverse exponential of the velocity twist dq = -lambda pinv(L) e."""
+    the left-multiplied inverse exponential of the velocity twist dq = -lambda pinv(L) e.
+    `trace` (a list) receives |err - prev| of every iteration, the quantity the stop rule compares with eps (inf in the first)."""
     xd = (uv[:, 0] - K[0, 2]) / K[0, 0]
     yd = (uv[:, 1] - K[1, 2]) / K[1, 1]
     prev = np.inf
@@ -252,6 +334,13 @@ def refine_vvs(pw, uv, K, R, t, iters=20, eps=1e-6, lam=1.0):
         e = np.empty(2 * len(x))
         e[0::2], e[1::2] = x - xd, y - yd
         err = np.sqrt(e @ e / len(x))
+        if trace is not None:
+            trace.append(abs(err - prev))
+        if not np.isfinite(err):
+            # a non-finite pixel or pose: the NaN reaches every entry of the pose within two updates (dq, then Rodrigues of it), after
+            # which LAPACK's SVD raises where OpenCV's would go on returning NaN.  NaN in, NaN out — the caller's finiteness check
+            # (interface_v5.py:368-374) turns that into the default box.  Unpinned against OpenCV like the rest of this file.
+            return np.full((3, 3), np.nan), np.full(3, np.nan)
         if abs(err - prev) < eps:
             break
         prev = err
@@ -281,18 +370,20 @@ def pnp_bbox_world(nocs1, pts2d1, nocs2, pts2d2, K, E1, E2, seed=0, pose=0):
     pixels of view 1, the ORIGINAL intrinsics) -> box in the world frame.  Returns (bbox [8,3], dict of intermediates)."""
     P1, P2 = np.eye(4), np.eye(4)
     P1[:3], P2[:3] = K @ E1[:3], K @ E2[:3]
-    scale, nm = left_scale_from_matches(pts2d1, nocs1, P1, E1, pts2d2, nocs2, P2, E2, K)
-    info = {"scale": scale, "n_matches": nm}
+    info = {}
+    scale, nm = left_scale_from_matches(pts2d1, nocs1, P1, E1, pts2d2, nocs2, P2, E2, K, info)
+    info.update(scale=scale, n_matches=nm)
     if not np.isfinite(scale):
         return DEFAULT_BBOX.copy(), info
     pw = (nocs1.astype(np.float32) * np.float32(scale)).astype(np.float64)      # align.py:105 on float32 nocs
     uv = pts2d1.astype(np.float32).astype(np.float64)
-    ok, R, t, mask = solve_pnp_ransac(pw, uv, K, seed, pose)
+    info.update(pw=pw, uv=uv)                                                    # what enters solve_pnp_ransac and refine_vvs
+    ok, R, t, mask = solve_pnp_ransac(pw, uv, K, seed, pose, info)
     info["ransac_ok"] = ok
     if not ok:
         return DEFAULT_BBOX.copy(), info
-    info["n_inliers"] = int(mask.sum())
-    R, t = refine_vvs(pw, uv, K, R, t)
+    info.update(n_inliers=int(mask.sum()), inliers=mask, R0=R, t0=t, vvs_trace=[])
+    R, t = refine_vvs(pw, uv, K, R, t, trace=info["vvs_trace"])
     info.update(R=R, t=t)
     from .align_ref import bbox_from_srt
     return bbox_from_srt(nocs1, scale, R, t, E1), info

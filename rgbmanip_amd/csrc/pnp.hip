@@ -163,6 +163,8 @@ __device__ bool epnp(const PnpData& D, const int* idx, int n, double* R, double*
   }
   double dc[3], uc3[9];
   eig_sym(C, 3, dc, uc3);                                  // ascending; control axis i uses the i-th LARGEST
+  // On noisy points the pose depends on the SIGN of these axes (a flipped axis mirrors a control point): it is the one eig_sym's
+  // rotations from the identity leave, and oracle/pnp_ref.py::jacobi_eigh restates them to sign its own axes alike.
   for (int i = 1; i < 4; ++i) {
     const int col = 3 - i;
     const double k = sqrt(fmax(dc[col], 0.0) / n);
@@ -349,17 +351,18 @@ __global__ __launch_bounds__(PN_T) void pnp_ransac_kernel(
     for (int k = 0; k < 3; ++k) atomicMax((int*)&hmax[k], __float_as_int(fabsf(n1[p][k])));
   }
   __syncthreads();
-  // ---- mutual nearest neighbours in NOCS space (utils.py:124-137): float32 distances, first minimum like np.argmin ----
+  // ---- mutual nearest neighbours in NOCS space (utils.py:124-137): float32 distances, first minimum like np.argmin, which also
+  //      takes the FIRST NaN for the minimum (once `best` is NaN neither test below holds again) ----
   for (int p = t; p < P; p += PN_T) {
     float best = INFINITY; int bi = 0;
     float best2 = INFINITY; int bi2 = 0;
     for (int q = 0; q < P; ++q) {
       const float dx = n1[p][0] - n2[q][0], dy = n1[p][1] - n2[q][1], dz = n1[p][2] - n2[q][2];
       const float d = sqrtf((dx * dx + dy * dy) + dz * dz);
-      if (d < best) { best = d; bi = q; }
+      if (d < best || (d != d && best == best)) { best = d; bi = q; }
       const float ex = n1[q][0] - n2[p][0], ey = n1[q][1] - n2[p][1], ez = n1[q][2] - n2[p][2];
       const float e = sqrtf((ex * ex + ey * ey) + ez * ez);
-      if (e < best2) { best2 = e; bi2 = q; }
+      if (e < best2 || (e != e && best2 == best2)) { best2 = e; bi2 = q; }
     }
     l2r[p] = bi; r2l[p] = bi2;
   }
@@ -618,7 +621,12 @@ __global__ __launch_bounds__(PN_T) void pnp_ransac_kernel(
     __syncthreads();
   }
   if (t == 0) {
-    const bool ok = have_scale && ransac_ok;
+    // a NaN pixel of view 1 leaves RANSAC standing (the point is no inlier) but reaches the refined pose through the residual: like
+    // every other failure that is the default box AND the identity in srt, not a box refused below with half a pose reported here
+    bool pose_finite = true;
+    for (int i = 0; i < 9; ++i) pose_finite = pose_finite && isfinite(s_R[i]);
+    for (int i = 0; i < 3; ++i) pose_finite = pose_finite && isfinite(s_t[i]);
+    const bool ok = have_scale && ransac_ok && pose_finite;
     double* o = srt + (long long)b * 13;
     o[0] = scale;
     for (int i = 0; i < 9; ++i) o[1 + i] = ok ? s_R[i] : (i % 4 == 0 ? 1.0 : 0.0);

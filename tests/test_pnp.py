@@ -93,6 +93,7 @@ def test_device_pnp_branch_matches_the_restatement():
             continue
         assert abs(srt[k, 0] - ei["scale"]) <= 1e-12 * ei["scale"], (k, srt[k, 0], ei["scale"])
         assert info[k, 1] == int(ei["ransac_ok"]) and valid[k] == 1
+        assert info[k, 3] == ei["n_examined"], (k, info[k], ei["n_examined"])
         assert abs(int(info[k, 2]) - ei["n_inliers"]) <= 2, (k, info[k], ei["n_inliers"])        # points on the 3-pixel edge may flip
         assert np.abs(srt[k, 1:10].reshape(3, 3) - ei["R"]).max() < 5e-6, (k, np.abs(srt[k, 1:10].reshape(3, 3) - ei["R"]).max())
         assert np.abs(srt[k, 10:13] - ei["t"]).max() < 5e-6
