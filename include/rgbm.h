@@ -227,6 +227,35 @@ int rgbm_cloud_similarity_scratch_bytes(int n, int cap, size_t* bytes);
 int rgbm_cloud_similarity(const float* nocs, const float* cloud, const int32_t* count, int n, int cap, uint32_t seed, double* bbox, double* srt,
                           int32_t* info, int32_t* valid, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Multi-view depth fusion: the consistency check over V views of a pose, and the cloud of all of them.
+ * rgbm_depth_fusion: depth [n][V][S][S] fp32 (camera z of the V crops of pose i), conf [n][V][S][S] fp32 and mask [n][V][S][S] uint8 (may
+ *   be NULL), Kcrop [n][V][3][3] fp64, E [n][V][4][4] fp64 (world -> camera).  Per pixel (x, y) of view a with depth d, in fp64, rounded
+ *   once:
+ *     0. d not finite or <= 0, or E_a without a finite inverse: keep 0, fused NaN, nviews 0, agree 0;
+ *     1. the sources b = 0 .. V - 1, b != a, in increasing order: a source whose E_b has no finite inverse does not agree; otherwise rules
+ *        2-4 of rgbm_depth_consistency (same taps, same clamp of the second tap, same NaN / <= 0 tap rule) give (x', y', d'_b), and b
+ *        agrees iff hypot(x' - x, y' - y) < px_max && |d'_b - d| / d < rel_max;
+ *     2. c = the number of agreeing sources: nviews = c, agree = the bit set of the agreeing b — written whatever 3 decides (agree may
+ *        be NULL);
+ *     3. keep = c >= n_min && (conf == NULL || conf >= conf_min) && (mask == NULL || mask != 0);
+ *        fused = keep ? (d + sum of d'_b over the agreeing b, added in increasing b) / (1 + c) : NaN.
+ *   2 <= V <= 16, 1 <= n_min <= V - 1, n >= 1, n V <= 65535, S <= 4096; px_max, rel_max, conf_min finite and >= 0.  No atomics: results
+ *   are bit-identical from run to run.  At V = 2, n_min = 1, fused and keep of view 0 are the bits rgbm_depth_consistency(a = view 0, b =
+ *   view 1) writes, and those of view 1 the bits of the opposite direction.
+ * rgbm_cloud_pack_views: rgbm_cloud_pack's ordered compaction over V views.  fused [n][V][S][S] fp32, keep [n][V][S][S] uint8, Kcrop
+ *   [n][V][3][3], E [n][V][4][4] -> for pose i the kept pixels of view 0 in row-major order, then view 1's, ...: cloud [n][cap][3] fp32
+ *   (the back-projection of rgbm_depth_to_points, same bits), index [n][cap] int32 = view * S * S + pixel, count [n][V] int32 = the
+ *   pixels kept per view, whatever cap is.  Rows min(cap, total) .. cap - 1 hold NaN / -1.  1 <= V <= 16, n <= 65535, S <= 4096, cap >=
+ *   0; no atomics.  At V = 2 the three outputs are byte for byte those of rgbm_cloud_pack, at V = 1 those of its one-view form.
+ * rgbm_cloud_gather_views: maps [n][V][S2][C] fp32, index [n][cap] int32 as rgbm_cloud_pack_views writes it -> out [n][cap][C] fp32,
+ *   out[i][r] = maps[i][index / S2][index % S2].  Rows with an index outside [0, V S2) hold NaN.  1 <= V <= 16, 1 <= C <= 4, cap >= 0. */
+int rgbm_depth_fusion(const float* depth, const float* conf, const uint8_t* mask, const double* Kcrop, const double* E, int n, int V, int S,
+                      double px_max, double rel_max, float conf_min, int n_min, float* fused, uint8_t* keep, uint8_t* nviews, uint16_t* agree,
+                      void* stream);
+int rgbm_cloud_pack_views(const float* fused, const uint8_t* keep, const double* Kcrop, const double* E, int n, int V, int S, int cap,
+                          float* cloud, int32_t* index, int32_t* count, void* stream);
+int rgbm_cloud_gather_views(const float* maps, const int32_t* index, int n, int V, int S2, int C, int cap, float* out, void* stream);
+
 /* Post-processing of one batch of network outputs into world-frame handle boxes.
  * Replaces: compute_scale_and_translation / get_3d_bbox / transform_coordinates_3d and the tail of predict()
  *   models/pose_estimator/AdaPose/lib/utils.py:40-119, models/pose_estimator/AdaPose/interface_v5.py:318-321,354-374

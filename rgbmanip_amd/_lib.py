@@ -128,6 +128,9 @@ SIGNATURES = {
     "rgbm_depth_to_points": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "rgbm_depth_consistency": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _d, _f, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_cloud_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "rgbm_depth_fusion": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "rgbm_cloud_pack_views": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "rgbm_cloud_gather_views": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "rgbm_adapose_graph_clear": (_i, [_vp]),
     "rgbm_adapose_feature_bytes": (_i, [_vp, C.POINTER(_sz)]),
     "rgbm_adapose_features_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),

@@ -577,6 +577,47 @@ def depth_consistency(depth_a, Kcrop_a, E_a, depth_b, Kcrop_b, E_b, conf_a=None,
     return {"fused": fused, "reproj": reproj, "rel": rel, "keep": keep}
 
 
+def _consistency_pair_ref(d, Ka, Ea, inv_a, db, Kb, Eb, inv_b, xx, yy):
+    """Rules 1-4 of DESIGN.md section 5k for one pose and one direction, in float64: view a's map d [S,S] against view b's db, inv_* the
+    inverses of E_*.  Returns (ok, reproj, rel, dr): ok = the pixel passed rules 1-3 (the other three are numbers there), dr = d'.  The
+    arithmetic `depth_consistency_ref` and `depth_fusion_ref` share."""
+    S = d.shape[0]
+
+    def back(inv, K, x, y, z):                             # pixel at depth z -> world
+        cam = np.stack([(x - K[0, 2]) * z / K[0, 0], (y - K[1, 2]) * z / K[1, 1], z], axis=-1)
+        return cam @ inv[:3, :3].T + inv[:3, 3]
+
+    def project(E, K, X):                                  # world -> (u, v, z)
+        c = X @ E[:3, :3].T + E[:3, 3]
+        return K[0, 0] * c[..., 0] / c[..., 2] + K[0, 2], K[1, 1] * c[..., 1] / c[..., 2] + K[1, 2], c[..., 2]
+
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(d) & (d > 0)                                                                   # rule 1
+        dz = np.where(ok, d, 1.0)
+        u, v, z = project(Eb, Kb, back(inv_a, Ka, xx, yy, dz))
+        ok &= (z > 0) & (u >= 0) & (u <= S - 1) & (v >= 0) & (v <= S - 1)                               # rule 2
+        us, vs = np.where(ok, u, 0.0), np.where(ok, v, 0.0)
+        x0, y0 = np.floor(us).astype(np.int64), np.floor(vs).astype(np.int64)
+        x1, y1 = np.minimum(x0 + 1, S - 1), np.minimum(y0 + 1, S - 1)
+        t00, t01, t10, t11 = db[y0, x0], db[y0, x1], db[y1, x0], db[y1, x1]
+        for t in (t00, t01, t10, t11):
+            ok &= np.isfinite(t) & (t > 0)                                                              # rule 3
+        ax, ay = us - x0, vs - y0
+        samp = (t00 * (1 - ax) + t01 * ax) * (1 - ay) + (t10 * (1 - ax) + t11 * ax) * ay
+        xr, yr, dr = project(Ea, Ka, back(inv_b, Kb, us, vs, samp))                                    # rule 4
+        reproj, rel = np.hypot(xr - xx, yr - yy), np.abs(dr - d) / d
+    return ok, reproj, rel, dr
+
+
+def _finite_inverse(E):
+    """inv(E), or None where E has no finite inverse."""
+    try:
+        inv = np.linalg.inv(E)
+    except np.linalg.LinAlgError:
+        return None
+    return inv if np.isfinite(inv).all() else None
+
+
 def depth_consistency_ref(depth_a, Kcrop_a, E_a, depth_b, Kcrop_b, E_b, conf_a=None, mask_a=None, px_max: float = 1.0, rel_max: float = 0.01,
                           conf_min: float = 0.0):
     """float64 numpy twin of `depth_consistency` (tests, documentation): rules 1-5 of DESIGN.md section 5k.  Returns dict(fused, reproj,
@@ -589,47 +630,137 @@ def depth_consistency_ref(depth_a, Kcrop_a, E_a, depth_b, Kcrop_b, E_b, conf_a=N
     out = {k: np.full((n, S, S), np.nan) for k in ("fused", "reproj", "rel")}
     out["keep"] = np.zeros((n, S, S), dtype=bool)
     out["sampled"] = np.zeros((n, S, S), dtype=bool)
-
-    def back(inv, K, x, y, z):                             # pixel at depth z -> world
-        cam = np.stack([(x - K[0, 2]) * z / K[0, 0], (y - K[1, 2]) * z / K[1, 1], z], axis=-1)
-        return cam @ inv[:3, :3].T + inv[:3, 3]
-
-    def project(E, K, X):                                  # world -> (u, v, z)
-        c = X @ E[:3, :3].T + E[:3, 3]
-        return K[0, 0] * c[..., 0] / c[..., 2] + K[0, 2], K[1, 1] * c[..., 1] / c[..., 2] + K[1, 2], c[..., 2]
-
     for i in range(n):
-        try:
-            inv_a, inv_b = np.linalg.inv(Ea[i]), np.linalg.inv(Eb[i])
-        except np.linalg.LinAlgError:
+        inv_a, inv_b = _finite_inverse(Ea[i]), _finite_inverse(Eb[i])
+        if inv_a is None or inv_b is None:
             continue
-        if not (np.isfinite(inv_a).all() and np.isfinite(inv_b).all()):
-            continue
+        d = da[i]
+        ok, reproj, rel, dr = _consistency_pair_ref(d, Ka[i], Ea[i], inv_a, db[i], Kb[i], Eb[i], inv_b, xx, yy)
         with np.errstate(all="ignore"):
-            d = da[i]
-            ok = np.isfinite(d) & (d > 0)                                                                   # rule 1
-            dz = np.where(ok, d, 1.0)
-            u, v, z = project(Eb[i], Kb[i], back(inv_a, Ka[i], xx, yy, dz))
-            ok &= (z > 0) & (u >= 0) & (u <= S - 1) & (v >= 0) & (v <= S - 1)                               # rule 2
-            us, vs = np.where(ok, u, 0.0), np.where(ok, v, 0.0)
-            x0, y0 = np.floor(us).astype(np.int64), np.floor(vs).astype(np.int64)
-            x1, y1 = np.minimum(x0 + 1, S - 1), np.minimum(y0 + 1, S - 1)
-            t00, t01, t10, t11 = db[i][y0, x0], db[i][y0, x1], db[i][y1, x0], db[i][y1, x1]
-            for t in (t00, t01, t10, t11):
-                ok &= np.isfinite(t) & (t > 0)                                                              # rule 3
-            ax, ay = us - x0, vs - y0
-            samp = (t00 * (1 - ax) + t01 * ax) * (1 - ay) + (t10 * (1 - ax) + t11 * ax) * ay
-            xr, yr, dr = project(Ea[i], Ka[i], back(inv_b, Kb[i], us, vs, samp))                           # rule 4
-            reproj, rel = np.hypot(xr - xx, yr - yy), np.abs(dr - d) / d
-            keep = ok & (reproj < px_max) & (rel < rel_max)                                                 # rule 5
+            keep = ok & (reproj < px_max) & (rel < rel_max)                                             # rule 5
             if conf_a is not None:
                 keep &= np.asarray(conf_a[i], dtype=np.float32) >= np.float32(conf_min)
             if mask_a is not None:
                 keep &= np.asarray(mask_a[i]) != 0
         out["reproj"][i][ok], out["rel"][i][ok] = reproj[ok], rel[ok]
-        out["fused"][i][keep] = ((d + dr) / 2)[keep]
+        with np.errstate(all="ignore"):
+            out["fused"][i][keep] = ((d + dr) / 2)[keep]
         out["keep"][i], out["sampled"][i] = keep, ok
     return out
+
+
+def _views_args(depth, Kcrop, E, name):
+    d = torch.as_tensor(depth)
+    dev = d.device if d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    d = d.to(device=dev, dtype=torch.float32).contiguous()
+    if d.dim() != 4 or d.shape[2] != d.shape[3]:
+        raise ValueError(f"{name}: maps [n, V, S, S], got {tuple(d.shape)}")
+    n, V = int(d.shape[0]), int(d.shape[1])
+    K = torch.as_tensor(Kcrop).to(device=dev, dtype=torch.float64).contiguous()
+    Ed = torch.as_tensor(E).to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(K.shape) != (n, V, 3, 3) or tuple(Ed.shape) != (n, V, 4, 4):
+        raise ValueError(f"{name}: Kcrop [n, V, 3, 3] and E [n, V, 4, 4], got {tuple(K.shape)} and {tuple(Ed.shape)} for n, V = {n}, {V}")
+    return d, K, Ed, dev
+
+
+def _u8_on(x, dev, shape, name):
+    x = torch.as_tensor(x).to(device=dev)
+    x = (x if x.dtype == torch.uint8 else (x != 0).to(torch.uint8)).contiguous()
+    if x.shape != shape:
+        raise ValueError(f"{name} has the maps' shape, got {tuple(x.shape)} and {tuple(shape)}")
+    return x
+
+
+def depth_fusion(depth, Kcrop, E, conf=None, mask=None, px_max: float = 1.0, rel_max: float = 0.01, conf_min: float = 0.0, n_min: int = 1,
+                 stream=None, want_agree: bool = True):
+    """Multi-view fusion of the V depth maps of every pose (rgbm_depth_fusion): every pixel of every view of depth
+    [n,V,S,S] is checked against each of the other V - 1 views with the arithmetic of `depth_consistency`; a source agrees when the pixel
+    comes back within `px_max` pixels at a depth within `rel_max` (relative).  A pixel is kept when at least `n_min` sources agree, its
+    confidence (conf [n,V,S,S], optional) is at least `conf_min` and its mask byte (mask [n,V,S,S], optional) is set; its fused depth is
+    the mean of its own depth and the agreeing sources' depths.  Kcrop [n,V,3,3], E [n,V,4,4] world -> camera; 2 <= V <= 16, 1 <= n_min
+    <= V - 1.  Returns a dict of CUDA tensors [n,V,S,S]: `fused` f32 (NaN where not kept), `keep` uint8, `nviews` uint8 (agreeing sources,
+    whatever `keep` says) and `agree` int16 (the bit set of the agreeing views: bit b = view b; None with want_agree=False).  At V = 2,
+    n_min = 1 `fused` / `keep` are the bits of the two directions of `depth_consistency`."""
+    lib = _lib.load()
+    d, K, Ed, dev = _views_args(depth, Kcrop, E, "depth_fusion")
+    n, V, S = int(d.shape[0]), int(d.shape[1]), int(d.shape[2])
+    c = None if conf is None else torch.as_tensor(conf).to(device=dev, dtype=torch.float32).contiguous()
+    if c is not None and c.shape != d.shape:
+        raise ValueError(f"depth_fusion: conf has the maps' shape, got {tuple(c.shape)} and {tuple(d.shape)}")
+    m = None if mask is None else _u8_on(mask, dev, d.shape, "depth_fusion: mask")
+    fused = torch.empty(n, V, S, S, dtype=torch.float32, device=dev)
+    keep = torch.empty(n, V, S, S, dtype=torch.uint8, device=dev)
+    nviews = torch.empty(n, V, S, S, dtype=torch.uint8, device=dev)
+    agree = torch.empty(n, V, S, S, dtype=torch.int16, device=dev) if want_agree else None      # 16 bits, V <= 16: bit 15 is the sign
+    if n:
+        _lib.check(lib.rgbm_depth_fusion(_lib.ptr(d), _lib.ptr(c), _lib.ptr(m), _lib.ptr(K), _lib.ptr(Ed), n, V, S, float(px_max), float(rel_max),
+                                         float(conf_min), int(n_min), _lib.ptr(fused), _lib.ptr(keep), _lib.ptr(nviews), _lib.ptr(agree),
+                                         _lib.stream_ptr(stream)), "rgbm_depth_fusion")
+    return {"fused": fused, "keep": keep, "nviews": nviews, "agree": agree}
+
+
+def depth_fusion_ref(depth, Kcrop, E, conf=None, mask=None, px_max: float = 1.0, rel_max: float = 0.01, conf_min: float = 0.0, n_min: int = 1):
+    """float64 numpy twin of `depth_fusion` (tests, documentation): rules 0-3 of DESIGN.md section 5n on the per-source arithmetic of
+    `depth_consistency_ref`.  Returns dict(fused [n,V,S,S] float64, keep bool, nviews uint8, agree uint16) and `margin` [n,V,V,S,S,2]
+    float64: margin[i, a, b, y, x] = (|reproj - px_max| in pixels, |rel - rel_max|) of pixel (x, y) of reference view a against source
+    b, i.e. how far that pair's decision is from flipping; NaN where the pair was not sampled (rules 1-3 of section 5k, b = a, a view
+    without a finite inverse).  Tests assert on it that no pair sits on a threshold."""
+    dd = np.asarray(depth, dtype=np.float64)
+    K, Ev = np.asarray(Kcrop, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    n, V, S = dd.shape[0], dd.shape[1], dd.shape[2]
+    if not 2 <= V <= 16 or not 1 <= n_min <= V - 1:
+        raise ValueError(f"depth_fusion_ref: 2 <= V <= 16 and 1 <= n_min <= V - 1, got V = {V}, n_min = {n_min}")
+    yy, xx = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64), indexing="ij")
+    out = {"fused": np.full((n, V, S, S), np.nan), "keep": np.zeros((n, V, S, S), dtype=bool), "nviews": np.zeros((n, V, S, S), dtype=np.uint8),
+           "agree": np.zeros((n, V, S, S), dtype=np.uint16), "margin": np.full((n, V, V, S, S, 2), np.nan)}
+    for i in range(n):
+        inv = [_finite_inverse(Ev[i, v]) for v in range(V)]
+        for a in range(V):
+            if inv[a] is None:
+                continue                                                                                # rule 0
+            d = dd[i, a]
+            total, c, bits = d.copy(), np.zeros((S, S), dtype=np.int64), np.zeros((S, S), dtype=np.uint16)
+            for b in range(V):                                                                          # rule 1, in increasing b
+                if b == a or inv[b] is None:
+                    continue
+                ok, reproj, rel, dr = _consistency_pair_ref(d, K[i, a], Ev[i, a], inv[a], dd[i, b], K[i, b], Ev[i, b], inv[b], xx, yy)
+                with np.errstate(all="ignore"):
+                    yes = ok & (reproj < px_max) & (rel < rel_max)
+                    total = np.where(yes, total + dr, total)
+                out["margin"][i, a, b][ok] = np.stack([np.abs(reproj - px_max), np.abs(rel - rel_max)], axis=-1)[ok]
+                c += yes
+                bits |= (yes.astype(np.uint16) << np.uint16(b))
+            keep = c >= n_min                                                                           # rules 2, 3
+            if conf is not None:
+                keep &= np.asarray(conf[i][a], dtype=np.float32) >= np.float32(conf_min)
+            if mask is not None:
+                keep &= np.asarray(mask[i][a]) != 0
+            with np.errstate(all="ignore"):
+                out["fused"][i, a][keep] = (total / (1 + c))[keep]
+            out["keep"][i, a], out["nviews"][i, a], out["agree"][i, a] = keep, c, bits
+    return out
+
+
+def cloud_pack_views(fused, keep, Kcrop, E, max_points=None, stream=None):
+    """Packed world-frame point cloud of the kept pixels of V views (rgbm_cloud_pack_views): `cloud_pack` for fused
+    / keep [n,V,S,S], Kcrop [n,V,3,3], E [n,V,4,4] — for pose i the kept pixels of view 0 in row-major order, then view 1's, and so on, each
+    back-projected exactly as `depth_to_points` does.  Returns CUDA tensors (cloud [n,cap,3] f32, index [n,cap] i32 = view * S * S +
+    pixel, count [n,V] i32 = pixels kept per view, whatever cap is); rows past the kept pixels hold NaN / -1.  cap = max_points, default
+    the worst case V S S.  1 <= V <= 16.  At V = 2 (V = 1) the outputs are byte for byte those of `cloud_pack` (of its one-view form)."""
+    lib = _lib.load()
+    f, K, Ed, dev = _views_args(fused, Kcrop, E, "cloud_pack_views")
+    n, V, S = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
+    k = _u8_on(keep, dev, f.shape, "cloud_pack_views: keep")
+    cap = V * S * S if max_points is None else int(max_points)
+    if cap < 0:
+        raise ValueError(f"cloud_pack_views: max_points >= 0, got {max_points}")
+    cloud = torch.empty(n, cap, 3, dtype=torch.float32, device=dev)
+    index = torch.empty(n, cap, dtype=torch.int32, device=dev)
+    count = torch.empty(n, V, dtype=torch.int32, device=dev)
+    if n:
+        _lib.check(lib.rgbm_cloud_pack_views(_lib.ptr(f), _lib.ptr(k), _lib.ptr(K), _lib.ptr(Ed), n, V, S, cap, _lib.ptr(cloud), _lib.ptr(index),
+                                             _lib.ptr(count), _lib.stream_ptr(stream)), "rgbm_cloud_pack_views")
+    return cloud, index, count
 
 
 def cloud_pack(fused1, keep1, Kcrop1, E1, fused2=None, keep2=None, Kcrop2=None, E2=None, max_points=None, stream=None):
@@ -743,6 +874,31 @@ def cloud_gather(map1, map2, index, stream=None):
     if n and cap:
         _lib.check(lib.rgbm_cloud_gather(_lib.ptr(m1), _lib.ptr(m2), _lib.ptr(ix), n, S2, Cc, cap, _lib.ptr(out), _lib.stream_ptr(stream)),
                    "rgbm_cloud_gather")
+    return out
+
+
+def cloud_gather_views(maps, index, stream=None):
+    """Rows of the per-pixel maps of V views at a packed cloud's indices (rgbm_cloud_gather_views): maps [n, V, S2, C] or [n, V, S, S, C]
+    float32, index [n, cap] int32 as `cloud_pack_views` returns it -> [n, cap, C] float32 CUDA, out[i, r] = maps[i, index // S2, index %
+    S2].  Rows with an index outside [0, V S2) hold NaN.  1 <= V <= 16, 1 <= C <= 4."""
+    lib = _lib.load()
+    m = torch.as_tensor(maps)
+    dev = m.device if m.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    m = m.to(device=dev, dtype=torch.float32).contiguous()
+    if m.dim() not in (4, 5):
+        raise ValueError(f"cloud_gather_views: maps [n, V, S2, C] or [n, V, S, S, C], got {tuple(m.shape)}")
+    n, V, Cc = int(m.shape[0]), int(m.shape[1]), int(m.shape[-1])
+    S2 = int(m.shape[2]) if m.dim() == 4 else int(m.shape[2] * m.shape[3])
+    if not 1 <= Cc <= 4 or S2 < 1 or not 1 <= V <= 16:
+        raise ValueError(f"cloud_gather_views: 1 <= C <= 4, S2 >= 1 and 1 <= V <= 16, got C = {Cc}, S2 = {S2}, V = {V}")
+    ix = torch.as_tensor(index).to(device=dev, dtype=torch.int32).contiguous()
+    if ix.dim() != 2 or ix.shape[0] != n:
+        raise ValueError(f"cloud_gather_views: index [n, cap], got {tuple(ix.shape)} for n = {n}")
+    cap = int(ix.shape[1])
+    out = torch.empty(n, cap, Cc, dtype=torch.float32, device=dev)
+    if n and cap:
+        _lib.check(lib.rgbm_cloud_gather_views(_lib.ptr(m), _lib.ptr(ix), n, V, S2, Cc, cap, _lib.ptr(out), _lib.stream_ptr(stream)),
+                   "rgbm_cloud_gather_views")
     return out
 
 

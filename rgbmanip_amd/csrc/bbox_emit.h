@@ -50,6 +50,17 @@ __device__ inline void backproject_world(const double* inv /*[12]*/, double x, d
   for (int r = 0; r < 3; ++r) out[r] = inv[r * 4 + 0] * c0 + inv[r * 4 + 1] * c1 + inv[r * 4 + 2] * z + inv[r * 4 + 3];
 }
 
+// world X -> (u, v, z) of a view with rows E[0..11] of its extrinsic and fx, fy, cx, cy of its cropped intrinsics: the ONE projection of
+// depth_consistency.hip and depth_fusion.hip (both built without contraction), whose V = 2 results are the same bits
+__device__ inline void project_view(const double* E /*[12]*/, const double X[3], double fx, double fy, double cx, double cy, double& u,
+                                    double& v, double& z) {
+  const double c0 = E[0] * X[0] + E[1] * X[1] + E[2] * X[2] + E[3];
+  const double c1 = E[4] * X[0] + E[5] * X[1] + E[6] * X[2] + E[7];
+  z = E[8] * X[0] + E[9] * X[1] + E[10] * X[2] + E[11];
+  u = fx * c0 / z + cx;
+  v = fy * c1 / z + cy;
+}
+
 // camera-frame corners -> world frame through `a` (invert_extrinsic), or default_bbox (+10 cube) and valid = 0 when !ok or a corner is
 // non-finite
 __device__ inline void emit_corners_world(long long b, const double cam[8][3], bool ok, const double a[4][8], double* __restrict__ bbox,

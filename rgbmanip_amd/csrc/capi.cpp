@@ -335,6 +335,22 @@ int rgbm_cloud_pack(const float* fused1, const uint8_t* keep1, const double* Kcr
   return rgbm::launch_cloud_pack(fused1, keep1, Kcrop1, E1, fused2, keep2, Kcrop2, E2, n, S, cap, cloud, index, count, (hipStream_t)stream);
 }
 
+int rgbm_depth_fusion(const float* depth, const float* conf, const uint8_t* mask, const double* Kcrop, const double* E, int n, int V, int S,
+                      double px_max, double rel_max, float conf_min, int n_min, float* fused, uint8_t* keep, uint8_t* nviews, uint16_t* agree,
+                      void* stream) {
+  return rgbm::launch_depth_fusion(depth, conf, mask, Kcrop, E, n, V, S, px_max, rel_max, conf_min, n_min, fused, keep, nviews, agree,
+                                   (hipStream_t)stream);
+}
+
+int rgbm_cloud_pack_views(const float* fused, const uint8_t* keep, const double* Kcrop, const double* E, int n, int V, int S, int cap,
+                          float* cloud, int32_t* index, int32_t* count, void* stream) {
+  return rgbm::launch_cloud_pack_views(fused, keep, Kcrop, E, n, V, S, cap, cloud, index, count, (hipStream_t)stream);
+}
+
+int rgbm_cloud_gather_views(const float* maps, const int32_t* index, int n, int V, int S2, int C, int cap, float* out, void* stream) {
+  return rgbm::launch_cloud_gather_views(maps, index, n, V, S2, C, cap, out, (hipStream_t)stream);
+}
+
 int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes) {
   RGBM_REQUIRE(h && bytes, "feature_bytes arguments");
   RGBM_REQUIRE(!is_baseline(h), "feature_bytes: the feature cache is not implemented for the baseline network");

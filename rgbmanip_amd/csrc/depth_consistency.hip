@@ -32,17 +32,7 @@ namespace {
 constexpr int PACK_THREADS = 1024;      // 16 waves
 constexpr int PACK_BLOCKS = 8;          // workgroups per pose
 constexpr int PACK_WAVES = PACK_THREADS / 64;
-
-// world X -> (u, v, z) of a view with rows E[0..11] of its extrinsic and fx, fy, cx, cy of its cropped intrinsics
-__device__ inline void project_view(const double* E /*[12]*/, const double X[3], double fx, double fy, double cx, double cy, double& u,
-                                    double& v, double& z) {
-  const double c0 = E[0] * X[0] + E[1] * X[1] + E[2] * X[2] + E[3];
-  const double c1 = E[4] * X[0] + E[5] * X[1] + E[6] * X[2] + E[7];
-  z = E[8] * X[0] + E[9] * X[1] + E[10] * X[2] + E[11];
-  u = fx * c0 / z + cx;
-  v = fy * c1 / z + cy;
-}
-}  // namespace
+}  // namespace                         // project_view: bbox_emit.h, shared with depth_fusion.hip
 
 __global__ __launch_bounds__(256) void depth_consistency_kernel(const float* __restrict__ depth_a, const float* __restrict__ conf_a,
                                                                 const unsigned char* __restrict__ mask_a, const double* __restrict__ Ka,

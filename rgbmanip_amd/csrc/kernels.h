@@ -66,6 +66,15 @@ int launch_depth_consistency(const float* depth_a, const float* conf_a, const un
 int launch_cloud_pack(const float* fused1, const unsigned char* keep1, const double* K1, const double* E1, const float* fused2,
                       const unsigned char* keep2, const double* K2, const double* E2, int n, int S, int cap, float* cloud, int* index,
                       int* count, hipStream_t s);
+// depth_fusion.hip: the check over V views of a pose (depth / conf / mask [n][V][S][S], Kcrop [n][V][3][3], E [n][V][4][4]; conf, mask,
+// agree may be null) -> fused fp32, keep / nviews uint8, agree uint16; the ordered compaction of the kept pixels of views 0 .. V - 1 into
+// cloud [n][cap][3], index [n][cap] (view * S * S + pixel), count [n][V]; and the rows of maps [n][V][S2][C] at such indices
+int launch_depth_fusion(const float* depth, const float* conf, const unsigned char* mask, const double* Kc, const double* E, int n, int V,
+                        int S, double px_max, double rel_max, float conf_min, int n_min, float* fused, unsigned char* keep,
+                        unsigned char* nviews, unsigned short* agree, hipStream_t s);
+int launch_cloud_pack_views(const float* fused, const unsigned char* keep, const double* Kc, const double* E, int n, int V, int S, int cap,
+                            float* cloud, int* index, int* count, hipStream_t s);
+int launch_cloud_gather_views(const float* maps, const int* index, int n, int V, int S2, int C, int cap, float* out, hipStream_t s);
 int launch_fuse_points(int dtype, const void* feat, const float* homog, const float* depths, const int* choose,
                        const float* prob, float* out, int V, int B, int P, int D, int H, int W, int ldo, int ch_off,
                        hipStream_t s, int Vn = -1);      // Vn: views 0 .. Vn - 1 only (default: all V)

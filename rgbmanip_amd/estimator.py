@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, host_prepare
-from .adapose import (AdaPoseNet, cloud_gather, cloud_pack, cloud_similarity, depth_consistency, depth_to_points, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
+from .adapose import (AdaPoseNet, cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity, depth_consistency, depth_fusion, depth_to_points, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
                       prepare_inputs_windows)
 from .feature_cache import CachedViews, ContentFeatureCache, SlotFeatureCache
 from .host_prepare import _resize_linear, _resize_nearest, get_bbox      # noqa: F401  (part of this module's surface)
@@ -502,6 +502,118 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             r.update(nocs1=n1, nocs2=n2, cloud_nocs=cloud_gather(n1, n2, index))
         return r
 
+    # ------------------------------------------------------------------ V views of a pose: fused maps, one cloud, one box
+    _VIEWS_CHUNK = 64                 # network poses per dense forward of estimate_cloud_views
+
+    def _views_options(self, n_min, px_max, rel_max, conf_min, masked, max_points, fit, fit_seed):
+        if self.prepare_mode != "device":
+            raise ValueError(f'estimate_cloud_views crops on the device: it needs hip_prepare: "device", got {self.prepare_mode!r}')
+        if self.upload_mode == "windows":
+            raise ValueError('estimate_cloud_views uploads whole frames: cfg hip_upload: "windows" is not implemented for it (use "frames")')
+        if max_points is not None and int(max_points) < 0:
+            raise ValueError(f"estimate_cloud_views: max_points >= 0, got {max_points}")
+        o = dict(n_min=int(n_min), px_max=float(px_max), rel_max=float(rel_max), conf_min=float(conf_min), masked=bool(masked),
+                 cap=None if max_points is None else int(max_points))
+        if fit:
+            o["fit_seed"] = int(self.cfg.get("hip_ransac_seed", 0) if fit_seed is None else fit_seed)
+        return o
+
+    def estimate_cloud_views(self, K, frames, masks, E, *, n_min=1, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True, max_points=None,
+                             fit=False, fit_seed=None):
+        """One cloud (and, with `fit`, one box) per pose from V >= 2 frames of it: K [n,3,3], frames [n,V,H,W,3] (float64 / float32 in
+        [0,1] or uint8), masks [n,V,H,W], E [n,V,4,4] world -> camera.  Every frame is uploaded and cropped once; frame k then runs
+        through the dense forward of `estimate_depth` as view 1 of a network pose whose view 2 is its neighbour p(k) (p(k) = k + 1, and
+        p(V - 1) = V - 2); the n V view-1 maps go through `depth_fusion` (every pixel checked against the other V - 1 views, kept when at
+        least `n_min` agree within `px_max` pixels / `rel_max` relative depth, with confidence >= `conf_min` and, with `masked`, inside
+        its crop mask) and `cloud_pack_views`.  Returns a dict of numpy arrays: `depth` / `conf` / `fused` [n,V,S,S] f32, `mask` / `keep`
+        / `nviews` [n,V,S,S] u8, `agree` [n,V,S,S] int16 (bit b: view b agrees), `window` [n,V,4] i32, `Kcrop` [n,V,3,3] f64, `valid`
+        [n,V] i32, `cloud` [n,cap,3] f32, `cloud_index` [n,cap] i32 (view * S * S + pixel), `count` [n,V] i32; cap = max_points, default
+        V S S.  With `fit`: `nocs` [n,V,S,S,3] f32, `cloud_nocs` [n,cap,3] f32 and `bbox_cloud` / `srt_cloud` / `fit_info` / `valid_cloud`
+        of `cloud_similarity` (seed `fit_seed`, default cfg hip_ransac_seed) on the cloud with its counts folded to [total, 0].  A frame
+        whose own mask or whose neighbour's mask is empty has valid 0, NaN maps and keep 0, and agrees with nobody as a source.  Needs
+        hip_prepare: "device" and whole-frame upload (hip_upload: "windows" is refused); the view-2 heads are not needed; the feature
+        cache is bypassed and counted as in `estimate_depth`."""
+        o = self._views_options(n_min, px_max, rel_max, conf_min, masked, max_points, fit, fit_seed)
+        cuda = isinstance(frames, torch.Tensor) and frames.is_cuda
+        fr = frames if cuda else host_array(frames)
+        mk = masks if isinstance(masks, torch.Tensor) and masks.is_cuda else host_array(masks)
+        if fr.ndim != 5 or mk.ndim != 4:
+            raise ValueError(f"estimate_cloud_views: frames [n,V,H,W,3] and masks [n,V,H,W], got {tuple(fr.shape)} and {tuple(mk.shape)}")
+        n, V = int(fr.shape[0]), int(fr.shape[1])
+        flat_f, flat_m = fr.reshape((n * V,) + tuple(fr.shape[2:])), mk.reshape((n * V,) + tuple(mk.shape[2:]))
+        self.upload_bytes_last_call, self.upload_table_bytes_last_call = frames_payload_bytes(flat_f, flat_f[:0], flat_m, flat_m[:0]), 0      # one stack of each
+        fd, md = self._upload_frames(flat_f), self._upload_masks(flat_m)
+        return _to_host(self._estimate_views(np.asarray(K), fd.view((n, V) + tuple(fd.shape[1:])), md.view((n, V) + tuple(md.shape[1:])),
+                                             np.asarray(E), o))
+
+    def estimate_cloud_views_device(self, K, frames, masks, E, *, n_min=1, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True,
+                                    max_points=None, fit=False, fit_seed=None):
+        """`estimate_cloud_views` for frames that live on the GPU (float32 or uint8 [n,V,H,W,3]): the same dict, as CUDA tensors."""
+        return self._estimate_views(K, frames, masks, E, self._views_options(n_min, px_max, rel_max, conf_min, masked, max_points, fit, fit_seed))
+
+    def _estimate_views(self, K, frames, masks, E, o):
+        dev, S = self.estimator.device, self.cfg["img_size"]
+        frames, masks = torch.as_tensor(frames).to(dev), torch.as_tensor(masks).to(dev)
+        if frames.dim() != 5 or masks.dim() != 4 or masks.shape[:2] != frames.shape[:2]:
+            raise ValueError(f"estimate_cloud_views: frames [n,V,H,W,3] and masks [n,V,H,W], got {tuple(frames.shape)} and {tuple(masks.shape)}")
+        n, V = int(frames.shape[0]), int(frames.shape[1])
+        if not 2 <= V <= 16 or not 1 <= o["n_min"] <= V - 1:
+            raise ValueError(f"estimate_cloud_views: 2 <= V <= 16 and 1 <= n_min <= V - 1, got V = {V}, n_min = {o['n_min']}")
+        Kd = torch.as_tensor(K).to(device=dev, dtype=torch.float64)
+        Ed = torch.as_tensor(E).to(device=dev, dtype=torch.float64)
+        if tuple(Kd.shape) != (n, 3, 3) or tuple(Ed.shape) != (n, V, 4, 4):
+            raise ValueError(f"estimate_cloud_views: K [n,3,3] and E [n,V,4,4], got {tuple(Kd.shape)} and {tuple(Ed.shape)}")
+        N = n * V
+        E1 = Ed.reshape(N, 4, 4)
+        # every frame is cropped once, as a view 1 (its choose subset is drawn with the view-1 seed, also where it serves as a view 2)
+        a = self._prepare(frames.reshape((N,) + tuple(frames.shape[2:])), masks.reshape((N,) + tuple(masks.shape[2:])),
+                          Kd.repeat_interleave(V, dim=0), S, 1024, self.prepare_seed, want_mask=True)
+        nb = torch.arange(N, device=dev).view(n, V)
+        nb = torch.cat([nb[:, 1:], nb[:, V - 2:V - 1]], dim=1).reshape(N)      # p(k) = k + 1, p(V - 1) = V - 2
+        b = {k: a[k].index_select(0, nb) for k in ("img", "choose", "Kcrop", "valid")}
+        E2 = E1.index_select(0, nb)
+        consts = self._dev_consts
+        if consts is None or consts[0].device != dev:
+            consts = self._dev_consts = (torch.from_numpy(DEFAULT_BBOX).to(dev), torch.from_numpy(_DEPTH_PLANES).to(dev))
+        fit = "fit_seed" in o
+        depth = torch.empty(N, S, S, dtype=torch.float32, device=dev)
+        conf = torch.empty_like(depth)
+        nocs = torch.empty(N, S, S, 3, dtype=torch.float32, device=dev) if fit else None
+        lib = _lib.load()
+        for lo in range(0, N, self._VIEWS_CHUNK):
+            hi = min(lo + self._VIEWS_CHUNK, N)
+            P = []
+            for Kc, Ev in ((a["Kcrop"][lo:hi], E1[lo:hi]), (b["Kcrop"][lo:hi], E2[lo:hi])):
+                Pm = torch.empty(hi - lo, 4, 4, dtype=torch.float32, device=dev)
+                _lib.check(lib.rgbm_projection(_lib.ptr(Kc.contiguous()), _lib.ptr(Ev.contiguous()), _lib.ptr(Pm), hi - lo, _lib.stream_ptr()),
+                           "rgbm_projection")
+                P.append(Pm)
+            pred = self.estimator(a["img"][lo:hi], a["choose"][lo:hi], b["img"][lo:hi], b["choose"][lo:hi], P[0], P[1],
+                                  consts[1][None].expand(hi - lo, 24).contiguous(), dense_depth=True, **({"dense_nocs": True} if fit else {}))
+            depth[lo:hi], conf[lo:hi] = pred["view1_depth_map"], pred["view1_depth_conf"]
+            if fit:
+                nocs[lo:hi] = pred["view1_nocs_map"]
+            self._plain_views += 2 * (hi - lo)
+            self._content.bypassed += int(self.feature_cache)      # a chunk the cache was set for and did not serve
+        ok = (a["valid"] != 0) & (b["valid"] != 0)
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+        depth = torch.where(ok.view(N, 1, 1), depth, nan).view(n, V, S, S)
+        conf = torch.where(ok.view(N, 1, 1), conf, nan).view(n, V, S, S)
+        Kc, mask = a["Kcrop"].view(n, V, 3, 3), a["mask"].view(n, V, S, S)
+        f = depth_fusion(depth, Kc, Ed, conf=conf, mask=mask if o["masked"] else None, px_max=o["px_max"], rel_max=o["rel_max"],
+                         conf_min=o["conf_min"], n_min=o["n_min"])
+        cloud, index, count = cloud_pack_views(f["fused"], f["keep"], Kc, Ed, max_points=o["cap"])
+        r = {"depth": depth, "conf": conf, "fused": f["fused"], "mask": mask, "keep": f["keep"], "nviews": f["nviews"], "agree": f["agree"],
+             "window": a["window"].view(n, V, 4), "Kcrop": Kc, "valid": ok.to(torch.int32).view(n, V), "cloud": cloud, "cloud_index": index,
+             "count": count}
+        if fit:
+            nocs = torch.where(ok.view(N, 1, 1, 1), nocs, nan).view(n, V, S, S, 3)
+            cn = cloud_gather_views(nocs, index)
+            folded = torch.stack([count.sum(dim=1, dtype=torch.int32), torch.zeros(n, dtype=torch.int32, device=dev)], dim=1)
+            bbox, srt, info, valid = cloud_similarity(cn, cloud, folded, seed=o["fit_seed"])
+            r.update(nocs=nocs, cloud_nocs=cn, bbox_cloud=bbox, srt_cloud=srt, fit_info=info, valid_cloud=valid)
+        return r
+
     def _alloc_out(self, n, dev, dense):
         """What the chunks of a pipelined call are written into: the boxes, the tensors of `estimate_depth`, or those of `estimate_cloud`."""
         if isinstance(dense, _Cloud):
@@ -695,3 +807,9 @@ class AdaPoseEstimator_baseline(AdaPoseEstimator_v5):
 
     def estimate_cloud_pose_device(self, *a, **k):
         self._no_cost_volume("estimate_cloud_pose_device")
+
+    def estimate_cloud_views(self, *a, **k):
+        self._no_cost_volume("estimate_cloud_views")
+
+    def estimate_cloud_views_device(self, *a, **k):
+        self._no_cost_volume("estimate_cloud_views_device")

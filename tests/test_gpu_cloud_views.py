@@ -1,0 +1,404 @@
+"""-m gpu: the multi-view fusion `depth_fusion` (csrc/depth_fusion.hip) against its float64 twin and against the two-view kernel at V = 2,
+`cloud_pack_views` / `cloud_gather_views` against `depth_to_points` / torch indexing and their two-view forms, and
+`AdaPoseEstimator_v5.estimate_cloud_views` end to end."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from cloud_views_cases import assert_scene_preconditions, conf_and_mask, sphere_ref, sphere_views  # noqa: E402
+from rgbmanip_amd import synth  # noqa: E402
+from rgbmanip_amd.adapose import (AdaPoseNet, cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity,  # noqa: E402
+                                  depth_consistency, depth_fusion, depth_fusion_ref, depth_to_points)
+
+S = 224
+H, W = 480, 640
+_CACHE = {}
+
+
+def _host(r):
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in r.items() if v is not None}
+
+
+def _against_twin(got, want):
+    assert got["keep"].dtype == np.uint8 and np.array_equal(got["keep"] != 0, want["keep"])
+    assert got["nviews"].dtype == np.uint8 and np.array_equal(got["nviews"], want["nviews"])
+    assert got["agree"].dtype == np.int16 and np.array_equal(got["agree"].view(np.uint16), want["agree"])
+    assert got["fused"].dtype == np.float32 and np.array_equal(np.isnan(got["fused"]), np.isnan(want["fused"]))
+    err = np.abs(got["fused"].astype(np.float64) - want["fused"])
+    print(f"fused: largest |kernel - twin| {np.nanmax(err) if np.isfinite(err).any() else 0:.3e}")
+    np.testing.assert_allclose(got["fused"], want["fused"], rtol=1e-6, atol=1e-7, equal_nan=True)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 1. kernel against twin
+@pytest.mark.parametrize("V", [4, 6])
+def test_depth_fusion_against_the_float64_twin_on_the_sphere_scenes(V):
+    """n = 2, S = 224, n_min 1, 2 and V - 1, without and with conf (conf_min 0.5) and mask.  No sampled pair lies within 1e-6 px / 1e-8 of
+    a threshold in float64 (asserted: a property of the inputs), so keep / nviews / agree must be the twin's exactly."""
+    assert_scene_preconditions(V)
+    depth, K, E = sphere_views(V)
+    conf, mask = conf_and_mask(V)
+    for n_min in sorted({1, 2, V - 1}):
+        for with_conf in (False, True):
+            kw = dict(conf=conf, mask=mask, conf_min=0.5) if with_conf else {}
+            want = sphere_ref(V, n_min, with_conf)
+            if with_conf and n_min == 1:
+                assert 0.2 < want["keep"].sum() / (want["nviews"] >= 1).sum() < 0.6      # both filters bite
+            _against_twin(_host(depth_fusion(depth, K, E, n_min=n_min, **kw)), want)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 2. V = 2
+def test_depth_fusion_of_two_views_is_the_two_view_kernel():
+    inp = synth.adapose_inputs(3, seed=5)
+    d = [synth.sphere_depth(inp["K1"], inp["E1"]), synth.sphere_depth(inp["K2"], inp["E2"])]
+    Kv, Ev = [inp["K1"], inp["K2"]], [inp["E1"], inp["E2"]]
+    depth, K, E = np.stack(d, 1), np.stack(Kv, 1), np.stack(Ev, 1)
+    g = np.random.default_rng(23)
+    conf = g.random(depth.shape, dtype=np.float32)
+    yy, xx = np.mgrid[0:S, 0:S]
+    mask = np.broadcast_to((((yy - 110) / 75.0) ** 2 + ((xx - 118) / 95.0) ** 2 <= 1).astype(np.uint8), depth.shape).copy()
+    for with_conf in (False, True):
+        got = _host(depth_fusion(depth, K, E, n_min=1, **(dict(conf=conf, mask=mask, conf_min=0.5) if with_conf else {})))
+        for a, b in ((0, 1), (1, 0)):
+            kw = dict(conf_a=conf[:, a], mask_a=mask[:, a], conf_min=0.5) if with_conf else {}
+            two = _host(depth_consistency(d[a], Kv[a], Ev[a], d[b], Kv[b], Ev[b], **kw))
+            assert two["keep"].sum() > 2000
+            assert np.array_equal(got["keep"][:, a], two["keep"])
+            assert np.array_equal(got["fused"][:, a].view(np.uint32), two["fused"].view(np.uint32))
+            agrees = (two["reproj"] < 1.0) & (two["rel"] < 0.01)
+            assert np.array_equal(got["nviews"][:, a], agrees.astype(np.uint8)) and np.array_equal(got["agree"][:, a], agrees.astype(np.int16) << b)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 3. edges
+def _exact_rig(n, V, size):
+    """E = identity, power-of-two focal length: ((x - cx) d / f) f / d is x itself, so u and v land on the integers 0 .. size - 1."""
+    K = np.tile(np.array([[256.0, 0, size / 2], [0, 256.0, size / 2], [0, 0, 1.0]])[None, None], (n, V, 1, 1))
+    return K, np.tile(np.eye(4)[None, None], (n, V, 1, 1))
+
+
+def _guarded(maps):
+    """maps [1, V, s, s] on the device between two NaN guard maps."""
+    V, s = maps.shape[1], maps.shape[2]
+    guard = torch.full((V + 2, s, s), float("nan"), dtype=torch.float32, device="cuda")
+    guard[1:V + 1] = torch.from_numpy(maps[0])
+    return guard[1:V + 1][None]
+
+
+def test_depth_fusion_edges_of_a_small_map():
+    """S = 8, n = 1, V = 3 identical cameras on the exact rig, the same depth ramp in all views: u, v are the integers 0 .. 7 and at 7 the
+    second tap must stay inside the map.  Then one NaN tap in view 2, then view 1's principal point moved by 2^-20 px."""
+    s, V = 8, 3
+    K, E = _exact_rig(1, V, s)
+    y, x = np.mgrid[0:s, 0:s]
+    ramp = (0.5 + 0.03 * x + 0.02 * y).astype(np.float32)
+    d = np.tile(ramp[None, None], (1, V, 1, 1))
+    others = np.array([0b110, 0b101, 0b011], dtype=np.int16)
+    for n_min in (1, 2):
+        got = _host(depth_fusion(_guarded(d), K, E, n_min=n_min))
+        assert got["keep"].all() and (got["nviews"] == 2).all() and np.array_equal(got["fused"], d)      # (3 d) / 3 is exact in fp64
+        assert all((got["agree"][0, a] == others[a]).all() for a in range(V))
+    # one NaN tap in view 2: the four pixels of views 0 and 1 that read it lose that witness
+    dn = d.copy()
+    dn[0, 2, 3, 5] = np.nan
+    reads = np.zeros((s, s), dtype=bool)
+    reads[2:4, 4:6] = True
+    for n_min in (1, 2):
+        got = _host(depth_fusion(_guarded(dn), K, E, n_min=n_min))
+        for a in (0, 1):
+            assert np.array_equal(got["nviews"][0, a], np.where(reads, 1, 2))
+            assert np.array_equal(got["agree"][0, a], np.where(reads, others[a] & 0b011, others[a]))
+            assert np.array_equal(got["keep"][0, a] != 0, ~reads if n_min == 2 else np.ones_like(reads))
+            kept = got["keep"][0, a] != 0
+            assert np.array_equal(got["fused"][0, a][kept], ramp[kept]) and np.isnan(got["fused"][0, a][~kept]).all()
+        # view 2 itself: its NaN pixel follows rule 0, every other pixel is untouched
+        hole = np.zeros((s, s), dtype=bool)
+        hole[3, 5] = True
+        assert np.array_equal(got["nviews"][0, 2], np.where(hole, 0, 2)) and np.array_equal(got["agree"][0, 2], np.where(hole, 0, others[2]))
+        assert np.array_equal(got["keep"][0, 2] != 0, ~hole) and np.array_equal(got["fused"][0, 2][~hole], ramp[~hole]) and np.isnan(got["fused"][0, 2, 3, 5])
+        _against_twin(got, depth_fusion_ref(dn, K, E, n_min=n_min))
+    # view 1's principal point moved by 2^-20 px: column 7 of views 0 and 2 projects just outside [0, 7] of view 1 (rule 2)
+    Kb = K.copy()
+    Kb[0, 1, 0, 2] += 2.0 ** -20
+    base = _host(depth_fusion(_guarded(d), K, E, n_min=1))
+    got = _host(depth_fusion(_guarded(d), Kb, E, n_min=1))
+    want = depth_fusion_ref(d, Kb, E, n_min=1)
+    for a in (0, 2):
+        assert (want["nviews"][0, a, :, 7] == 1).all() and (want["agree"][0, a, :, 7] == (others[a] & 0b101)).all()
+        assert (want["nviews"][0, a, :, :7] == 2).all() and want["keep"][0, a].all()
+        assert np.array_equal(got["keep"][0, a], base["keep"][0, a])                      # n_min = 1 keeps everything
+    # ... and the mirror image in view 1 itself: its column 0 projects to u = -2^-20 in both other views and has no witness left
+    assert (want["nviews"][0, 1, :, 0] == 0).all() and not want["keep"][0, 1, :, 0].any()
+    assert (want["nviews"][0, 1, :, 1:] == 2).all() and want["keep"][0, 1, :, 1:].all()
+    _against_twin(got, want)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 4. invalid input
+def test_depth_fusion_invalid_pixels_and_singular_extrinsics():
+    V = 4
+    depth, K, E = sphere_views(V)
+    da = depth.copy()
+    ys, xs = np.nonzero(np.isfinite(da[0, 1]))
+    bad = [(0, 1, ys[100 + j], xs[100 + j]) for j in range(4)]
+    for at, val in zip(bad, (np.inf, -np.inf, 0.0, -0.4)):
+        da[at] = val
+    got = _host(depth_fusion(da, K, E, n_min=1))
+    for at in bad:                                          # rule 0
+        assert got["keep"][at] == 0 and np.isnan(got["fused"][at]) and got["nviews"][at] == 0 and got["agree"][at] == 0
+    _against_twin(got, depth_fusion_ref(da, K, E, n_min=1))
+    # a singular E for source 2 of pose 1: it agrees nowhere, the other sources' bits are those of the call with it
+    full = _host(depth_fusion(depth, K, E, n_min=1))
+    Es = E.copy()
+    Es[1, 2, 1] = 0.0
+    got = _host(depth_fusion(depth, K, Es, n_min=1))
+    for a in (0, 1, 3):
+        assert np.array_equal(got["agree"][1, a], full["agree"][1, a] & ~np.int16(1 << 2))
+    assert (full["agree"][1, [0, 1, 3]] & 4).any()
+    # ... and as a reference view (rule 0): the whole view has keep 0, NaN
+    assert not got["keep"][1, 2].any() and np.isnan(got["fused"][1, 2]).all() and not got["nviews"][1, 2].any() and not got["agree"][1, 2].any()
+    for k in ("fused", "keep", "nviews", "agree"):
+        assert np.array_equal(got[k][0], full[k][0], equal_nan=True), k     # pose 0 is untouched
+    _against_twin(got, depth_fusion_ref(depth, K, Es, n_min=1))
+
+
+# ------------------------------------------------------------------------------------------------------------------ 5. determinism
+def test_depth_fusion_is_deterministic_and_agree_is_optional():
+    depth, K, E = sphere_views(6)
+    conf, mask = conf_and_mask(6)
+    kw = dict(conf=conf, mask=mask, conf_min=0.5, n_min=2)
+    a, b = _host(depth_fusion(depth, K, E, **kw)), _host(depth_fusion(depth, K, E, **kw))
+    lean = depth_fusion(depth, K, E, want_agree=False, **kw)
+    assert lean["agree"] is None
+    lean = _host(lean)
+    assert a["keep"].sum() > 10000
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes(), k
+        if k != "agree":
+            assert a[k].tobytes() == lean[k].tobytes(), k
+
+
+# ------------------------------------------------------------------------------------------------------------------ 6. cloud_pack_views
+def _patterns():
+    g = np.random.default_rng(41)
+    z = np.zeros(S * S, dtype=np.uint8)
+    first, last, stride = z.copy(), z.copy(), z.copy()
+    first[0], last[-1] = 1, 1
+    stride[::1023] = 1
+    return {"ones": np.ones(S * S, dtype=np.uint8), "zeros": z, "first": first, "last": last, "every 1023rd": stride,
+            "bernoulli": (g.random(S * S) < 0.5).astype(np.uint8)}
+
+
+def _pack_inputs():
+    if "pack" not in _CACHE:
+        g = np.random.default_rng(7)
+        inp = synth.adapose_inputs(3, seed=5)
+        K = np.stack([inp["K1"], inp["K2"], inp["K1"]], 1).astype(np.float64)
+        E = np.stack([inp["E1"], inp["E2"], inp["E2"]], 1).astype(np.float64)
+        fused = g.uniform(0.2, 2.0, (3, 3, S, S)).astype(np.float32)
+        pts = depth_to_points(fused.reshape(9, S, S), K.reshape(9, 3, 3), E.reshape(9, 4, 4)).cpu().numpy().reshape(3, 3, S * S, 3)
+        _CACHE["pack"] = (fused, K, E, pts)
+    return _CACHE["pack"]
+
+
+def _check_pack_views(fused, keep, K, E, pts, cap=None):
+    cloud, index, count = (t.cpu().numpy() for t in cloud_pack_views(fused, keep, K, E, max_points=cap))
+    n, V = keep.shape[:2]
+    cap = V * S * S if cap is None else cap
+    assert cloud.shape == (n, cap, 3) and cloud.dtype == np.float32 and index.shape == (n, cap) and index.dtype == np.int32
+    assert count.shape == (n, V) and count.dtype == np.int32
+    for i in range(n):
+        idx = [np.flatnonzero(keep[i, v].reshape(-1) != 0) for v in range(V)]
+        want_pts = np.concatenate([pts[i, v][j] for v, j in enumerate(idx)])
+        want_idx = np.concatenate([j + v * S * S for v, j in enumerate(idx)]).astype(np.int32)
+        m = min(len(want_idx), cap)
+        assert count[i].tolist() == [len(j) for j in idx], i     # the full counts, whatever cap is
+        assert np.array_equal(index[i, :m], want_idx[:m]), i
+        assert np.array_equal(cloud[i, :m].view(np.uint32), want_pts[:m].view(np.uint32)), i
+        assert (index[i, m:] == -1).all() and np.isnan(cloud[i, m:]).all(), i
+    return cloud, index, count
+
+
+@pytest.mark.parametrize("name", ["ones", "zeros", "first", "last", "every 1023rd", "bernoulli"])
+def test_cloud_pack_views_synthetic_keep_patterns(name):
+    """n = 3, V = 3 with an all-zero pose in the middle; views 1 and 2 carry the pattern reversed (7 where view 0 has 1: any non-zero byte
+    keeps) and rolled.  Kept pixels sit on both sides of every boundary of the scan: the 1024-pixel chunks, the four pieces of a view
+    (12 544 pixels each at S = 224) and the seams between the views."""
+    fused, K, E, pts = _pack_inputs()
+    p = _patterns()[name]
+    z = np.zeros_like(p)
+    keep = np.stack([np.stack([p, p[::-1] * 7, np.roll(p, 517)]), np.stack([z, z, z]), np.stack([np.roll(p, 517), p, p[::-1]])]).reshape(3, 3, S, S)
+    a = _check_pack_views(fused, keep, K, E, pts)
+    b = _check_pack_views(fused, keep, K, E, pts)
+    for x, y in zip(a, b):                                   # two calls: identical bytes
+        assert x.tobytes() == y.tobytes()
+    total = int(p.sum()) * 3
+    for cap in sorted({0, 1, total // 2, max(total - 1, 0), total + 5}):
+        _check_pack_views(fused, keep, K, E, pts, cap)
+    # V = 2 and V = 1: the bytes of cloud_pack and of its one-view form
+    for cap in (None, total // 2, 3):
+        two = cloud_pack(fused[:, 0], keep[:, 0], K[:, 0], E[:, 0], fused[:, 1], keep[:, 1], K[:, 1], E[:, 1], max_points=cap)
+        got = cloud_pack_views(fused[:, :2], keep[:, :2], K[:, :2], E[:, :2], max_points=cap)
+        one = cloud_pack(fused[:, 2], keep[:, 2], K[:, 2], E[:, 2], max_points=cap)
+        got1 = cloud_pack_views(fused[:, 2:], keep[:, 2:], K[:, 2:], E[:, 2:], max_points=cap)
+        for x, y in zip(two, got):
+            assert x.cpu().numpy().tobytes() == y.cpu().numpy().tobytes(), cap
+        assert one[0].cpu().numpy().tobytes() == got1[0].cpu().numpy().tobytes() and torch.equal(one[1], got1[1])
+        assert torch.equal(one[2][:, :1], got1[2]) and not one[2][:, 1].any()      # cloud_pack's count is [n, 2], the second column 0
+
+
+# ------------------------------------------------------------------------------------------------------------------ 7. cloud_gather_views
+@pytest.mark.parametrize("C_", [1, 3, 4])
+def test_cloud_gather_views_against_torch_indexing(C_):
+    g = torch.Generator().manual_seed(5 + C_)
+    n, V, S2, cap = 3, 3, 100, 257
+    maps = torch.randn(n, V, S2, C_, generator=g).cuda()
+    index = torch.randint(0, V * S2, (n, cap), generator=g, dtype=torch.int32)
+    index[0, 3], index[1, 0], index[2, -1], index[2, 5] = -1, V * S2, V * S2 + 7, -5
+    index[1, 1], index[1, 2] = 0, V * S2 - 1
+    index = index.cuda()
+    inside = (index >= 0) & (index < V * S2)
+    want = maps.reshape(n, V * S2, C_).gather(1, index.clamp(0, V * S2 - 1).long()[..., None].expand(n, cap, C_))
+    want = torch.where(inside[..., None], want, torch.full_like(want, float("nan")))
+    got = cloud_gather_views(maps, index)
+    assert got.shape == (n, cap, C_) and got.dtype == torch.float32
+    assert np.array_equal(got.cpu().numpy(), want.cpu().numpy(), equal_nan=True) and int((~inside).sum()) == 4
+    assert np.array_equal(cloud_gather_views(maps.reshape(n, V, 10, 10, C_), index).cpu().numpy(), want.cpu().numpy(), equal_nan=True)
+    two = cloud_gather(maps[:, 0], maps[:, 1], index)        # V = 2: cloud_gather (indices >= 2 S2: NaN in both)
+    assert np.array_equal(cloud_gather_views(maps[:, :2], index).cpu().numpy(), two.cpu().numpy(), equal_nan=True)
+    assert cloud_gather_views(maps, index[:, :0]).shape == (n, 0, C_)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 8. the estimator
+def _scene():
+    """Three poses x V = 3 host frames built like tests/test_gpu_cloud.py::_scene (float64 and uint8, elliptical masks); frame 1 of pose
+    1 has an empty mask."""
+    if "scene" not in _CACHE:
+        g = np.random.default_rng(3)
+        n, V = 3, 3
+        yy, xx = np.mgrid[0:H, 0:W]
+        K = np.tile(np.array([[439.31, 0, 320.0], [0, 439.31, 240.0], [0, 0, 1.0]])[None], (n, 1, 1))
+        base, more = synth.adapose_inputs(n, seed=0), synth.adapose_inputs(n, seed=5)
+        E = np.stack([base["E1"], base["E2"], more["E1"]], 1).astype(np.float64)
+        wave = (np.cos(xx / 37.0), np.sin(yy / 29.0), np.cos((xx + yy) / 41.0))
+        f = np.stack([np.clip(0.5 + 0.25 * wave[v][None, :, :, None] + 0.2 * g.random((n, H, W, 3)), 0, 1) for v in range(V)], 1)
+        m = np.stack([np.stack([((yy - 240 - 5 * v) / (60.0 + 5 * v)) ** 2 + ((xx - 300 - 10 * i - 20 * v) / (90.0 - 5 * v)) ** 2 <= 1
+                                for v in range(V)]) for i in range(n)])
+        m[1, 1] = False
+        _CACHE["scene"] = dict(K=K, E=E, f=f, u=np.rint(f * 255.0).astype(np.uint8), m=m)
+    return _CACHE["scene"]
+
+
+def _net(**options):
+    key = ("net", tuple(sorted(options.items())))
+    if key not in _CACHE:
+        _CACHE[key] = AdaPoseNet(synth.adapose_state_dict(seed=0, prefix="module."), dtype="bf16", options=options)
+    return _CACHE[key]
+
+
+def _estimator(net, **kw):
+    from rgbmanip_amd.config import ADAPOSE_CFGS
+    from rgbmanip_amd.estimator import AdaPoseEstimator_v5
+    cfg = dict(ADAPOSE_CFGS["adapose_cabinet"], load=False, hip_dtype="bf16", hip_prepare="device", hip_prepare_seed=9, **kw)
+    return AdaPoseEstimator_v5(None, cfg, None, net=net)
+
+
+VIEWS_KEYS = sorted(["depth", "conf", "fused", "mask", "keep", "nviews", "agree", "window", "Kcrop", "valid", "cloud", "cloud_index", "count"])
+FIT_KEYS = sorted(VIEWS_KEYS + ["nocs", "cloud_nocs", "bbox_cloud", "srt_cloud", "fit_info", "valid_cloud"])
+# a synthetic net's maps are unrelated, so the default thresholds keep next to nothing; these let a share of the pixels through
+LOOSE = dict(px_max=60.0, rel_max=0.5, conf_min=0.05)
+NEIGHBOUR = [1, 2, 1]                                         # p(k) at V = 3
+
+
+@pytest.mark.parametrize("frames", ["f", "u"])
+def test_estimate_cloud_views(frames):
+    s = _scene()
+    n, V = 3, 3
+    est = _estimator(_net(view2_heads=0))                    # the view-2 heads are not needed
+    r = est.estimate_cloud_views(s["K"], s[frames], s["m"], s["E"], **LOOSE)
+    assert sorted(r) == VIEWS_KEYS and all(isinstance(v, np.ndarray) for v in r.values())
+    assert all(r[k].shape == (n, V, S, S) and r[k].dtype == np.float32 for k in ("depth", "conf", "fused"))
+    assert all(r[k].shape == (n, V, S, S) and r[k].dtype == np.uint8 for k in ("mask", "keep", "nviews"))
+    assert r["agree"].shape == (n, V, S, S) and r["agree"].dtype == np.int16
+    assert r["window"].shape == (n, V, 4) and r["window"].dtype == np.int32 and r["Kcrop"].shape == (n, V, 3, 3) and r["Kcrop"].dtype == np.float64
+    assert r["cloud"].shape == (n, V * S * S, 3) and r["cloud"].dtype == np.float32
+    assert r["cloud_index"].shape == (n, V * S * S) and r["cloud_index"].dtype == np.int32 and r["count"].shape == (n, V) and r["count"].dtype == np.int32
+    # frame 1 of pose 1 has an empty mask; it is the neighbour of frames 0 and 2 of that pose
+    assert r["valid"].dtype == np.int32 and r["valid"].tolist() == [[1, 1, 1], [0, 0, 0], [1, 1, 1]]
+    assert all(np.isnan(r[k][1]).all() for k in ("depth", "conf", "fused")) and not r["keep"][1].any() and not r["nviews"][1].any()
+    assert r["count"][1].tolist() == [0, 0, 0] and np.isnan(r["cloud"][1]).all() and (r["cloud_index"][1] == -1).all()
+    assert (r["count"][[0, 2]].sum(1) > 5000).all(), r["count"]      # seeded weights: which views agree is arbitrary, that some do is not
+    assert (r["keep"] <= r["mask"]).all()
+    # the maps of frame k: estimate_depth_device's for the pair (k, p(k)), bit for bit
+    u8 = frames == "u"
+    fd = torch.from_numpy(s["u"] if u8 else s["f"].astype(np.float32)).cuda()
+    md = torch.from_numpy(s["m"]).cuda()
+    flat = lambda t: t.reshape((n * V,) + tuple(t.shape[2:]))      # noqa: E731
+    d = est.estimate_depth_device(np.repeat(s["K"], V, axis=0), flat(fd), flat(md), flat(s["E"]), flat(fd[:, NEIGHBOUR]), flat(md[:, NEIGHBOUR]),
+                                  flat(s["E"][:, NEIGHBOUR]))
+    for k in ("depth", "conf", "window", "Kcrop"):
+        assert np.array_equal(flat(r[k]), d[k].cpu().numpy(), equal_nan=True), k
+    assert flat(r["valid"]).tolist() == d["valid"].tolist()
+    # fusion and cloud: the public functions on the returned maps
+    f = _host(depth_fusion(r["depth"], r["Kcrop"], s["E"], conf=r["conf"], mask=r["mask"], **LOOSE))
+    for k in ("fused", "keep", "nviews", "agree"):
+        assert np.array_equal(r[k], f[k], equal_nan=True), k
+    cloud, index, count = (t.cpu().numpy() for t in cloud_pack_views(r["fused"], r["keep"], r["Kcrop"], s["E"]))
+    assert np.array_equal(r["cloud"], cloud, equal_nan=True) and np.array_equal(r["cloud_index"], index) and np.array_equal(r["count"], count)
+    assert count.tolist() == [[int(r["keep"][i, v].sum()) for v in range(V)] for i in range(n)]
+    # the device form
+    q = est.estimate_cloud_views_device(s["K"], fd, md, s["E"], **LOOSE)
+    assert sorted(q) == VIEWS_KEYS and all(isinstance(v, torch.Tensor) and v.is_cuda for v in q.values())
+    for k in r:
+        assert np.array_equal(q[k].cpu().numpy(), r[k], equal_nan=True), k
+
+
+def test_estimate_cloud_views_fit_options_and_what_it_leaves_alone():
+    from rgbmanip_amd.config import adapose_cfg
+    from rgbmanip_amd.estimator import AdaPoseEstimator_baseline, AdaPoseEstimator_v4
+    s = _scene()
+    n, V = 3, 3
+    net = _net(view2_heads=1)
+    est = _estimator(net, hip_view2_heads=True, hip_feature_cache="content")
+    pair = (s["K"], s["u"][:, 0], s["m"][:, 0], s["E"][:, 0], s["u"][:, 2], s["m"][:, 2], s["E"][:, 2])
+    box0, cloud0 = est.estimate(*pair), est.estimate_cloud(*pair, **LOOSE)
+    bypassed = est.feature_cache_bypassed
+    plain = est.estimate_cloud_views(s["K"], s["u"], s["m"], s["E"], **LOOSE)
+    assert est.feature_cache_bypassed == bypassed + 1
+    r = est.estimate_cloud_views(s["K"], s["u"], s["m"], s["E"], fit=True, fit_seed=77, max_points=6000, n_min=2, **LOOSE)
+    assert sorted(r) == FIT_KEYS
+    assert r["nocs"].shape == (n, V, S, S, 3) and r["nocs"].dtype == np.float32 and np.isnan(r["nocs"][1]).all() and np.isfinite(r["nocs"][[0, 2]]).all()
+    assert r["cloud"].shape == (n, 6000, 3) and r["cloud_nocs"].shape == (n, 6000, 3) and r["cloud_nocs"].dtype == np.float32
+    assert r["bbox_cloud"].shape == (n, 8, 3) and r["bbox_cloud"].dtype == np.float64 and r["srt_cloud"].shape == (n, 13)
+    assert r["fit_info"].shape == (n, 4) and r["fit_info"].dtype == np.int32 and r["valid_cloud"].shape == (n,) and r["valid_cloud"].dtype == np.int32
+    for k in ("depth", "conf", "mask", "nviews", "agree", "window", "Kcrop", "valid"):      # n_min changes neither the maps nor the votes
+        assert np.array_equal(r[k], plain[k], equal_nan=True), k
+    assert (r["keep"] <= plain["keep"]).all() and r["keep"].sum() < plain["keep"].sum() and np.array_equal(r["keep"] != 0, (plain["keep"] != 0) & (r["nviews"] >= 2))
+    assert np.array_equal(r["cloud_nocs"], cloud_gather_views(r["nocs"], r["cloud_index"]).cpu().numpy(), equal_nan=True)
+    folded = np.stack([r["count"].sum(1), np.zeros(n)], 1).astype(np.int32)
+    bbox, srt, info, valid = (t.cpu().numpy() for t in cloud_similarity(r["cloud_nocs"], r["cloud"], folded, seed=77))
+    assert np.array_equal(r["bbox_cloud"], bbox) and np.array_equal(r["srt_cloud"], srt, equal_nan=True)
+    assert np.array_equal(r["fit_info"], info) and np.array_equal(r["valid_cloud"], valid)
+    assert r["valid_cloud"][1] == 0 and r["fit_info"][[0, 2], 0].tolist() == np.minimum(r["count"][[0, 2]].sum(1), 6000).tolist()
+    free = est.estimate_cloud_views(s["K"], s["u"], s["m"], s["E"], masked=False, **LOOSE)
+    assert (free["keep"] >= plain["keep"]).all() and not (free["keep"] <= free["mask"]).all()
+    # estimate() and estimate_cloud() return the same bytes after the views calls
+    box1, cloud1 = est.estimate(*pair), est.estimate_cloud(*pair, **LOOSE)
+    assert np.array_equal(box0, box1) and sorted(cloud0) == sorted(cloud1)
+    for k in cloud0:
+        assert np.array_equal(cloud0[k], cloud1[k], equal_nan=True), k
+    # refusals
+    with pytest.raises(ValueError, match="hip_upload"):
+        _estimator(net, hip_view2_heads=True, hip_upload="windows").estimate_cloud_views(s["K"], s["u"], s["m"], s["E"])
+    for kw in (dict(n_min=0), dict(n_min=3)):
+        with pytest.raises(ValueError, match="n_min"):
+            est.estimate_cloud_views(s["K"], s["u"], s["m"], s["E"], **kw)
+    with pytest.raises(ValueError, match="V"):
+        est.estimate_cloud_views(s["K"], s["u"][:, :1], s["m"][:, :1], s["E"][:, :1])
+    base = AdaPoseEstimator_baseline.__new__(AdaPoseEstimator_baseline)
+    with pytest.raises(NotImplementedError, match="estimate_cloud_views"):
+        base.estimate_cloud_views(s["K"], s["u"], s["m"], s["E"])
+    v4 = AdaPoseEstimator_v4(None, dict(adapose_cfg("one_door_cabinet", load=False, name="adapose_v4"), hip_dtype="bf16", hip_prepare="device",
+                                        hip_prepare_seed=9, hip_view2_heads=True), None, net=net)
+    q = v4.estimate_cloud_views(s["K"], s["u"], s["m"], s["E"], **LOOSE)
+    assert sorted(q) == VIEWS_KEYS and q["valid"].tolist() == [[1, 1, 1], [0, 0, 0], [1, 1, 1]]
