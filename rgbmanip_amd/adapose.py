@@ -15,6 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from .cloud import (cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity, cloud_similarity_ref,      # noqa: F401  (part of this module's surface)
+                    depth_consistency, depth_consistency_ref, depth_fusion, depth_fusion_ref, depth_to_points, depth_to_points_ref)
 
 _DTYPES = {"fp32": _lib.F32, "f32": _lib.F32, "float32": _lib.F32, "bf16": _lib.BF16, "bfloat16": _lib.BF16,
            "fp16": _lib.F16, "f16": _lib.F16, "float16": _lib.F16, "bf16x3": _lib.BF16X3}
@@ -498,308 +500,6 @@ def postprocess(view1_nocs, view1_depth, view1_r, view1_choose, K_crop, E1, img_
     return bbox, ts, valid
 
 
-def depth_to_points(depth_map, K_crop, E, stream=None):
-    """World-frame points of a crop's depth map (rgbm_depth_to_points): depth_map [n,S,S] float32, K_crop [n,3,3] (cropped intrinsics),
-    E [n,4,4] (world -> camera) -> [n,S,S,3] float32 CUDA: inv(E) applied to the back-projection of interface_v5.py:329-336 at every
-    pixel — the per-pixel `Position` image of the simulator camera.  A pixel whose depth is not finite yields NaN."""
-    lib = _lib.load()
-    d = torch.as_tensor(depth_map)
-    dev = d.device if d.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    d = d.to(device=dev, dtype=torch.float32).contiguous()
-    n, S = d.shape[0], d.shape[1]
-    assert d.shape == (n, S, S), d.shape
-    K = torch.as_tensor(K_crop).to(device=dev, dtype=torch.float64).contiguous()
-    Ed = torch.as_tensor(E).to(device=dev, dtype=torch.float64).contiguous()
-    assert K.shape == (n, 3, 3) and Ed.shape == (n, 4, 4), (K.shape, Ed.shape)
-    pts = torch.empty(n, S, S, 3, dtype=torch.float32, device=dev)
-    if n:
-        _lib.check(lib.rgbm_depth_to_points(_lib.ptr(d), _lib.ptr(K), _lib.ptr(Ed), n, S, _lib.ptr(pts), _lib.stream_ptr(stream)),
-                   "rgbm_depth_to_points")
-    return pts
-
-
-def depth_to_points_ref(depth_map, K_crop, E):
-    """float64 numpy twin of `depth_to_points` (tests, documentation): the arithmetic of interface_v5.py:329-336, 369-372 per pixel."""
-    d = np.asarray(depth_map, dtype=np.float64)
-    K, E = np.asarray(K_crop, dtype=np.float64), np.asarray(E, dtype=np.float64)
-    n, S = d.shape[0], d.shape[1]
-    y, x = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64), indexing="ij")
-    out = np.empty((n, S, S, 3))
-    for i in range(n):
-        ex_inv = np.linalg.inv(E[i])
-        with np.errstate(invalid="ignore"):                   # a non-finite depth: NaN below
-            cam = np.stack([(x - K[i, 0, 2]) * d[i] / K[i, 0, 0], (y - K[i, 1, 2]) * d[i] / K[i, 1, 1], d[i]], axis=-1)
-            out[i] = cam @ ex_inv[:3, :3].T + ex_inv[:3, 3]
-        out[i][~np.isfinite(d[i])] = np.nan
-    return out
-
-
-def _view_args(depth, K_crop, E, dev=None):
-    d = torch.as_tensor(depth)
-    if dev is None:
-        dev = d.device if d.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    d = d.to(device=dev, dtype=torch.float32).contiguous()
-    n, S = d.shape[0], d.shape[1]
-    assert d.shape == (n, S, S), d.shape
-    K = torch.as_tensor(K_crop).to(device=dev, dtype=torch.float64).contiguous()
-    Ed = torch.as_tensor(E).to(device=dev, dtype=torch.float64).contiguous()
-    assert K.shape == (n, 3, 3) and Ed.shape == (n, 4, 4), (K.shape, Ed.shape)
-    return d, K, Ed, dev
-
-
-def depth_consistency(depth_a, Kcrop_a, E_a, depth_b, Kcrop_b, E_b, conf_a=None, mask_a=None, px_max: float = 1.0, rel_max: float = 0.01,
-                      conf_min: float = 0.0, stream=None, want_diagnostics: bool = True):
-    """Two-view geometric consistency of view a's depth map against view b's (rgbm_depth_consistency): every pixel
-    of depth_a [n,S,S] is back-projected, projected into view b, depth_b is sampled there bilinearly, back-projected and projected back
-    into view a; the pixel is kept when it lands within `px_max` pixels of where it started at a depth within `rel_max` (relative), its
-    confidence (conf_a [n,S,S], optional) is at least `conf_min` and its mask byte (mask_a [n,S,S], optional) is set.  Kcrop_* [n,3,3],
-    E_* [n,4,4] world -> camera.  Returns a dict of CUDA tensors [n,S,S]: `fused` f32 (mean of the two depths where kept, NaN elsewhere),
-    `reproj` f32 (pixels) and `rel` f32 (NaN where the pixel could not be sampled; None with want_diagnostics=False), `keep` uint8."""
-    lib = _lib.load()
-    da, Ka, Ea, dev = _view_args(depth_a, Kcrop_a, E_a)
-    db, Kb, Eb, _ = _view_args(depth_b, Kcrop_b, E_b, dev)
-    n, S = da.shape[0], da.shape[1]
-    assert db.shape == da.shape, (da.shape, db.shape)
-    conf = None if conf_a is None else torch.as_tensor(conf_a).to(device=dev, dtype=torch.float32).contiguous()
-    mask = None
-    if mask_a is not None:
-        mask = torch.as_tensor(mask_a).to(device=dev)
-        mask = (mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)).contiguous()
-    assert (conf is None or conf.shape == da.shape) and (mask is None or mask.shape == da.shape)
-    fused = torch.empty(n, S, S, dtype=torch.float32, device=dev)
-    reproj = torch.empty_like(fused) if want_diagnostics else None
-    rel = torch.empty_like(fused) if want_diagnostics else None
-    keep = torch.empty(n, S, S, dtype=torch.uint8, device=dev)
-    if n:
-        _lib.check(lib.rgbm_depth_consistency(_lib.ptr(da), _lib.ptr(conf), _lib.ptr(mask), _lib.ptr(Ka), _lib.ptr(Ea), _lib.ptr(db), _lib.ptr(Kb),
-                                              _lib.ptr(Eb), n, S, float(px_max), float(rel_max), float(conf_min), _lib.ptr(fused),
-                                              _lib.ptr(reproj), _lib.ptr(rel), _lib.ptr(keep), _lib.stream_ptr(stream)), "rgbm_depth_consistency")
-    return {"fused": fused, "reproj": reproj, "rel": rel, "keep": keep}
-
-
-def _consistency_pair_ref(d, Ka, Ea, inv_a, db, Kb, Eb, inv_b, xx, yy):
-    """Rules 1-4 of DESIGN.md section 5k for one pose and one direction, in float64: view a's map d [S,S] against view b's db, inv_* the
-    inverses of E_*.  Returns (ok, reproj, rel, dr): ok = the pixel passed rules 1-3 (the other three are numbers there), dr = d'.  The
-    arithmetic `depth_consistency_ref` and `depth_fusion_ref` share."""
-    S = d.shape[0]
-
-    def back(inv, K, x, y, z):                             # pixel at depth z -> world
-        cam = np.stack([(x - K[0, 2]) * z / K[0, 0], (y - K[1, 2]) * z / K[1, 1], z], axis=-1)
-        return cam @ inv[:3, :3].T + inv[:3, 3]
-
-    def project(E, K, X):                                  # world -> (u, v, z)
-        c = X @ E[:3, :3].T + E[:3, 3]
-        return K[0, 0] * c[..., 0] / c[..., 2] + K[0, 2], K[1, 1] * c[..., 1] / c[..., 2] + K[1, 2], c[..., 2]
-
-    with np.errstate(all="ignore"):
-        ok = np.isfinite(d) & (d > 0)                                                                   # rule 1
-        dz = np.where(ok, d, 1.0)
-        u, v, z = project(Eb, Kb, back(inv_a, Ka, xx, yy, dz))
-        ok &= (z > 0) & (u >= 0) & (u <= S - 1) & (v >= 0) & (v <= S - 1)                               # rule 2
-        us, vs = np.where(ok, u, 0.0), np.where(ok, v, 0.0)
-        x0, y0 = np.floor(us).astype(np.int64), np.floor(vs).astype(np.int64)
-        x1, y1 = np.minimum(x0 + 1, S - 1), np.minimum(y0 + 1, S - 1)
-        t00, t01, t10, t11 = db[y0, x0], db[y0, x1], db[y1, x0], db[y1, x1]
-        for t in (t00, t01, t10, t11):
-            ok &= np.isfinite(t) & (t > 0)                                                              # rule 3
-        ax, ay = us - x0, vs - y0
-        samp = (t00 * (1 - ax) + t01 * ax) * (1 - ay) + (t10 * (1 - ax) + t11 * ax) * ay
-        xr, yr, dr = project(Ea, Ka, back(inv_b, Kb, us, vs, samp))                                    # rule 4
-        reproj, rel = np.hypot(xr - xx, yr - yy), np.abs(dr - d) / d
-    return ok, reproj, rel, dr
-
-
-def _finite_inverse(E):
-    """inv(E), or None where E has no finite inverse."""
-    try:
-        inv = np.linalg.inv(E)
-    except np.linalg.LinAlgError:
-        return None
-    return inv if np.isfinite(inv).all() else None
-
-
-def depth_consistency_ref(depth_a, Kcrop_a, E_a, depth_b, Kcrop_b, E_b, conf_a=None, mask_a=None, px_max: float = 1.0, rel_max: float = 0.01,
-                          conf_min: float = 0.0):
-    """float64 numpy twin of `depth_consistency` (tests, documentation): rules 1-5 of DESIGN.md section 5k.  Returns dict(fused, reproj,
-    rel [n,S,S] float64, keep [n,S,S] bool).  Also returns `sampled` (bool: the pixel passed rules 1-3, i.e. reproj / rel are numbers)."""
-    da, db = np.asarray(depth_a, dtype=np.float64), np.asarray(depth_b, dtype=np.float64)
-    Ka, Kb = np.asarray(Kcrop_a, dtype=np.float64), np.asarray(Kcrop_b, dtype=np.float64)
-    Ea, Eb = np.asarray(E_a, dtype=np.float64), np.asarray(E_b, dtype=np.float64)
-    n, S = da.shape[0], da.shape[1]
-    yy, xx = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64), indexing="ij")
-    out = {k: np.full((n, S, S), np.nan) for k in ("fused", "reproj", "rel")}
-    out["keep"] = np.zeros((n, S, S), dtype=bool)
-    out["sampled"] = np.zeros((n, S, S), dtype=bool)
-    for i in range(n):
-        inv_a, inv_b = _finite_inverse(Ea[i]), _finite_inverse(Eb[i])
-        if inv_a is None or inv_b is None:
-            continue
-        d = da[i]
-        ok, reproj, rel, dr = _consistency_pair_ref(d, Ka[i], Ea[i], inv_a, db[i], Kb[i], Eb[i], inv_b, xx, yy)
-        with np.errstate(all="ignore"):
-            keep = ok & (reproj < px_max) & (rel < rel_max)                                             # rule 5
-            if conf_a is not None:
-                keep &= np.asarray(conf_a[i], dtype=np.float32) >= np.float32(conf_min)
-            if mask_a is not None:
-                keep &= np.asarray(mask_a[i]) != 0
-        out["reproj"][i][ok], out["rel"][i][ok] = reproj[ok], rel[ok]
-        with np.errstate(all="ignore"):
-            out["fused"][i][keep] = ((d + dr) / 2)[keep]
-        out["keep"][i], out["sampled"][i] = keep, ok
-    return out
-
-
-def _views_args(depth, Kcrop, E, name):
-    d = torch.as_tensor(depth)
-    dev = d.device if d.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    d = d.to(device=dev, dtype=torch.float32).contiguous()
-    if d.dim() != 4 or d.shape[2] != d.shape[3]:
-        raise ValueError(f"{name}: maps [n, V, S, S], got {tuple(d.shape)}")
-    n, V = int(d.shape[0]), int(d.shape[1])
-    K = torch.as_tensor(Kcrop).to(device=dev, dtype=torch.float64).contiguous()
-    Ed = torch.as_tensor(E).to(device=dev, dtype=torch.float64).contiguous()
-    if tuple(K.shape) != (n, V, 3, 3) or tuple(Ed.shape) != (n, V, 4, 4):
-        raise ValueError(f"{name}: Kcrop [n, V, 3, 3] and E [n, V, 4, 4], got {tuple(K.shape)} and {tuple(Ed.shape)} for n, V = {n}, {V}")
-    return d, K, Ed, dev
-
-
-def _u8_on(x, dev, shape, name):
-    x = torch.as_tensor(x).to(device=dev)
-    x = (x if x.dtype == torch.uint8 else (x != 0).to(torch.uint8)).contiguous()
-    if x.shape != shape:
-        raise ValueError(f"{name} has the maps' shape, got {tuple(x.shape)} and {tuple(shape)}")
-    return x
-
-
-def depth_fusion(depth, Kcrop, E, conf=None, mask=None, px_max: float = 1.0, rel_max: float = 0.01, conf_min: float = 0.0, n_min: int = 1,
-                 stream=None, want_agree: bool = True):
-    """Multi-view fusion of the V depth maps of every pose (rgbm_depth_fusion): every pixel of every view of depth
-    [n,V,S,S] is checked against each of the other V - 1 views with the arithmetic of `depth_consistency`; a source agrees when the pixel
-    comes back within `px_max` pixels at a depth within `rel_max` (relative).  A pixel is kept when at least `n_min` sources agree, its
-    confidence (conf [n,V,S,S], optional) is at least `conf_min` and its mask byte (mask [n,V,S,S], optional) is set; its fused depth is
-    the mean of its own depth and the agreeing sources' depths.  Kcrop [n,V,3,3], E [n,V,4,4] world -> camera; 2 <= V <= 16, 1 <= n_min
-    <= V - 1.  Returns a dict of CUDA tensors [n,V,S,S]: `fused` f32 (NaN where not kept), `keep` uint8, `nviews` uint8 (agreeing sources,
-    whatever `keep` says) and `agree` int16 (the bit set of the agreeing views: bit b = view b; None with want_agree=False).  At V = 2,
-    n_min = 1 `fused` / `keep` are the bits of the two directions of `depth_consistency`."""
-    lib = _lib.load()
-    d, K, Ed, dev = _views_args(depth, Kcrop, E, "depth_fusion")
-    n, V, S = int(d.shape[0]), int(d.shape[1]), int(d.shape[2])
-    c = None if conf is None else torch.as_tensor(conf).to(device=dev, dtype=torch.float32).contiguous()
-    if c is not None and c.shape != d.shape:
-        raise ValueError(f"depth_fusion: conf has the maps' shape, got {tuple(c.shape)} and {tuple(d.shape)}")
-    m = None if mask is None else _u8_on(mask, dev, d.shape, "depth_fusion: mask")
-    fused = torch.empty(n, V, S, S, dtype=torch.float32, device=dev)
-    keep = torch.empty(n, V, S, S, dtype=torch.uint8, device=dev)
-    nviews = torch.empty(n, V, S, S, dtype=torch.uint8, device=dev)
-    agree = torch.empty(n, V, S, S, dtype=torch.int16, device=dev) if want_agree else None      # 16 bits, V <= 16: bit 15 is the sign
-    if n:
-        _lib.check(lib.rgbm_depth_fusion(_lib.ptr(d), _lib.ptr(c), _lib.ptr(m), _lib.ptr(K), _lib.ptr(Ed), n, V, S, float(px_max), float(rel_max),
-                                         float(conf_min), int(n_min), _lib.ptr(fused), _lib.ptr(keep), _lib.ptr(nviews), _lib.ptr(agree),
-                                         _lib.stream_ptr(stream)), "rgbm_depth_fusion")
-    return {"fused": fused, "keep": keep, "nviews": nviews, "agree": agree}
-
-
-def depth_fusion_ref(depth, Kcrop, E, conf=None, mask=None, px_max: float = 1.0, rel_max: float = 0.01, conf_min: float = 0.0, n_min: int = 1):
-    """float64 numpy twin of `depth_fusion` (tests, documentation): rules 0-3 of DESIGN.md section 5n on the per-source arithmetic of
-    `depth_consistency_ref`.  Returns dict(fused [n,V,S,S] float64, keep bool, nviews uint8, agree uint16) and `margin` [n,V,V,S,S,2]
-    float64: margin[i, a, b, y, x] = (|reproj - px_max| in pixels, |rel - rel_max|) of pixel (x, y) of reference view a against source
-    b, i.e. how far that pair's decision is from flipping; NaN where the pair was not sampled (rules 1-3 of section 5k, b = a, a view
-    without a finite inverse).  Tests assert on it that no pair sits on a threshold."""
-    dd = np.asarray(depth, dtype=np.float64)
-    K, Ev = np.asarray(Kcrop, dtype=np.float64), np.asarray(E, dtype=np.float64)
-    n, V, S = dd.shape[0], dd.shape[1], dd.shape[2]
-    if not 2 <= V <= 16 or not 1 <= n_min <= V - 1:
-        raise ValueError(f"depth_fusion_ref: 2 <= V <= 16 and 1 <= n_min <= V - 1, got V = {V}, n_min = {n_min}")
-    yy, xx = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64), indexing="ij")
-    out = {"fused": np.full((n, V, S, S), np.nan), "keep": np.zeros((n, V, S, S), dtype=bool), "nviews": np.zeros((n, V, S, S), dtype=np.uint8),
-           "agree": np.zeros((n, V, S, S), dtype=np.uint16), "margin": np.full((n, V, V, S, S, 2), np.nan)}
-    for i in range(n):
-        inv = [_finite_inverse(Ev[i, v]) for v in range(V)]
-        for a in range(V):
-            if inv[a] is None:
-                continue                                                                                # rule 0
-            d = dd[i, a]
-            total, c, bits = d.copy(), np.zeros((S, S), dtype=np.int64), np.zeros((S, S), dtype=np.uint16)
-            for b in range(V):                                                                          # rule 1, in increasing b
-                if b == a or inv[b] is None:
-                    continue
-                ok, reproj, rel, dr = _consistency_pair_ref(d, K[i, a], Ev[i, a], inv[a], dd[i, b], K[i, b], Ev[i, b], inv[b], xx, yy)
-                with np.errstate(all="ignore"):
-                    yes = ok & (reproj < px_max) & (rel < rel_max)
-                    total = np.where(yes, total + dr, total)
-                out["margin"][i, a, b][ok] = np.stack([np.abs(reproj - px_max), np.abs(rel - rel_max)], axis=-1)[ok]
-                c += yes
-                bits |= (yes.astype(np.uint16) << np.uint16(b))
-            keep = c >= n_min                                                                           # rules 2, 3
-            if conf is not None:
-                keep &= np.asarray(conf[i][a], dtype=np.float32) >= np.float32(conf_min)
-            if mask is not None:
-                keep &= np.asarray(mask[i][a]) != 0
-            with np.errstate(all="ignore"):
-                out["fused"][i, a][keep] = (total / (1 + c))[keep]
-            out["keep"][i, a], out["nviews"][i, a], out["agree"][i, a] = keep, c, bits
-    return out
-
-
-def cloud_pack_views(fused, keep, Kcrop, E, max_points=None, stream=None):
-    """Packed world-frame point cloud of the kept pixels of V views (rgbm_cloud_pack_views): `cloud_pack` for fused
-    / keep [n,V,S,S], Kcrop [n,V,3,3], E [n,V,4,4] — for pose i the kept pixels of view 0 in row-major order, then view 1's, and so on, each
-    back-projected exactly as `depth_to_points` does.  Returns CUDA tensors (cloud [n,cap,3] f32, index [n,cap] i32 = view * S * S +
-    pixel, count [n,V] i32 = pixels kept per view, whatever cap is); rows past the kept pixels hold NaN / -1.  cap = max_points, default
-    the worst case V S S.  1 <= V <= 16.  At V = 2 (V = 1) the outputs are byte for byte those of `cloud_pack` (of its one-view form)."""
-    lib = _lib.load()
-    f, K, Ed, dev = _views_args(fused, Kcrop, E, "cloud_pack_views")
-    n, V, S = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
-    k = _u8_on(keep, dev, f.shape, "cloud_pack_views: keep")
-    cap = V * S * S if max_points is None else int(max_points)
-    if cap < 0:
-        raise ValueError(f"cloud_pack_views: max_points >= 0, got {max_points}")
-    cloud = torch.empty(n, cap, 3, dtype=torch.float32, device=dev)
-    index = torch.empty(n, cap, dtype=torch.int32, device=dev)
-    count = torch.empty(n, V, dtype=torch.int32, device=dev)
-    if n:
-        _lib.check(lib.rgbm_cloud_pack_views(_lib.ptr(f), _lib.ptr(k), _lib.ptr(K), _lib.ptr(Ed), n, V, S, cap, _lib.ptr(cloud), _lib.ptr(index),
-                                             _lib.ptr(count), _lib.stream_ptr(stream)), "rgbm_cloud_pack_views")
-    return cloud, index, count
-
-
-def cloud_pack(fused1, keep1, Kcrop1, E1, fused2=None, keep2=None, Kcrop2=None, E2=None, max_points=None, stream=None):
-    """Packed world-frame point cloud of the kept pixels (rgbm_cloud_pack): for pose i the pixels of view 1 with
-    keep1 != 0 in row-major order, then those of view 2 (all four view-2 arguments, or none for a one-view cloud), each back-projected
-    exactly as `depth_to_points` does.  Returns CUDA tensors (cloud [n,cap,3] f32, index [n,cap] i32 = view * S * S + pixel, count [n,2]
-    i32 = pixels kept per view, whatever cap is); rows past the kept pixels hold NaN / -1.  cap = max_points, default the worst case
-    (2 S S, or S S for one view).  The order is fixed: two calls give the same bytes."""
-    lib = _lib.load()
-    f1, K1, E1d, dev = _view_args(fused1, Kcrop1, E1)
-    n, S = f1.shape[0], f1.shape[1]
-    two = [x is not None for x in (fused2, keep2, Kcrop2, E2)]
-    if any(two) != all(two):
-        raise ValueError("cloud_pack: fused2, keep2, Kcrop2 and E2 are given together or not at all")
-
-    def keep_of(k):
-        k = torch.as_tensor(k).to(device=dev)
-        k = (k if k.dtype == torch.uint8 else (k != 0).to(torch.uint8)).contiguous()
-        assert k.shape == (n, S, S), k.shape
-        return k
-    k1 = keep_of(keep1)
-    f2 = K2 = E2d = k2 = None
-    if all(two):
-        f2, K2, E2d, _ = _view_args(fused2, Kcrop2, E2, dev)
-        assert f2.shape == f1.shape, (f1.shape, f2.shape)
-        k2 = keep_of(keep2)
-    cap = (2 if all(two) else 1) * S * S if max_points is None else int(max_points)
-    if cap < 0:
-        raise ValueError(f"cloud_pack: max_points >= 0, got {max_points}")
-    cloud = torch.empty(n, cap, 3, dtype=torch.float32, device=dev)
-    index = torch.empty(n, cap, dtype=torch.int32, device=dev)
-    count = torch.empty(n, 2, dtype=torch.int32, device=dev)
-    if n:
-        _lib.check(lib.rgbm_cloud_pack(_lib.ptr(f1), _lib.ptr(k1), _lib.ptr(K1), _lib.ptr(E1d), _lib.ptr(f2), _lib.ptr(k2), _lib.ptr(K2),
-                                       _lib.ptr(E2d), n, S, cap, _lib.ptr(cloud), _lib.ptr(index), _lib.ptr(count), _lib.stream_ptr(stream)),
-                   "rgbm_cloud_pack")
-    return cloud, index, count
-
-
 def view_fusion(net, x1, x2, stream=None):
     """`AdaPoseNet.view_fusion`: the attention stack of a baseline `net` on rows x1 / x2 [B, P, 32] -> (y1, y2) float32 CUDA."""
     return net.view_fusion(x1, x2, stream=stream)
@@ -845,188 +545,6 @@ def view_fusion_ref(state_dict, x1, x2, prefix: str = "view_fusion.", stats: dic
 def nocs_map(net, feat, stream=None):
     """`AdaPoseNet.nocs_map`: the NOCS branch of `net` at every row of feat [V, HW, 32] -> [V, HW, 3] float32 CUDA."""
     return net.nocs_map(feat, stream=stream)
-
-
-def cloud_gather(map1, map2, index, stream=None):
-    """Rows of per-pixel maps at a packed cloud's indices (rgbm_cloud_gather): map1 / map2 [n, S2, C] or [n, S, S, C] float32 (map2 may
-    be None), index [n, cap] int32 as `cloud_pack` returns it -> [n, cap, C] float32 CUDA, out[i, r] = map{1 + index // S2}[i, index % S2].
-    Rows with index < 0, index >= 2 S2, or a view-2 index without map2 hold NaN.  1 <= C <= 4."""
-    lib = _lib.load()
-    m1 = torch.as_tensor(map1)
-    dev = m1.device if m1.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    m1 = m1.to(device=dev, dtype=torch.float32).contiguous()
-    if m1.dim() not in (3, 4):
-        raise ValueError(f"cloud_gather: map1 [n, S2, C] or [n, S, S, C], got {tuple(m1.shape)}")
-    n, Cc = int(m1.shape[0]), int(m1.shape[-1])
-    S2 = int(m1.shape[1]) if m1.dim() == 3 else int(m1.shape[1] * m1.shape[2])
-    if not 1 <= Cc <= 4 or S2 < 1:
-        raise ValueError(f"cloud_gather: 1 <= C <= 4 and S2 >= 1, got C = {Cc}, S2 = {S2}")
-    m2 = None
-    if map2 is not None:
-        m2 = torch.as_tensor(map2).to(device=dev, dtype=torch.float32).contiguous()
-        if m2.shape != m1.shape:
-            raise ValueError(f"cloud_gather: map2 has map1's shape, got {tuple(m2.shape)} and {tuple(m1.shape)}")
-    ix = torch.as_tensor(index).to(device=dev, dtype=torch.int32).contiguous()
-    if ix.dim() != 2 or ix.shape[0] != n:
-        raise ValueError(f"cloud_gather: index [n, cap], got {tuple(ix.shape)} for n = {n}")
-    cap = int(ix.shape[1])
-    out = torch.empty(n, cap, Cc, dtype=torch.float32, device=dev)
-    if n and cap:
-        _lib.check(lib.rgbm_cloud_gather(_lib.ptr(m1), _lib.ptr(m2), _lib.ptr(ix), n, S2, Cc, cap, _lib.ptr(out), _lib.stream_ptr(stream)),
-                   "rgbm_cloud_gather")
-    return out
-
-
-def cloud_gather_views(maps, index, stream=None):
-    """Rows of the per-pixel maps of V views at a packed cloud's indices (rgbm_cloud_gather_views): maps [n, V, S2, C] or [n, V, S, S, C]
-    float32, index [n, cap] int32 as `cloud_pack_views` returns it -> [n, cap, C] float32 CUDA, out[i, r] = maps[i, index // S2, index %
-    S2].  Rows with an index outside [0, V S2) hold NaN.  1 <= V <= 16, 1 <= C <= 4."""
-    lib = _lib.load()
-    m = torch.as_tensor(maps)
-    dev = m.device if m.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    m = m.to(device=dev, dtype=torch.float32).contiguous()
-    if m.dim() not in (4, 5):
-        raise ValueError(f"cloud_gather_views: maps [n, V, S2, C] or [n, V, S, S, C], got {tuple(m.shape)}")
-    n, V, Cc = int(m.shape[0]), int(m.shape[1]), int(m.shape[-1])
-    S2 = int(m.shape[2]) if m.dim() == 4 else int(m.shape[2] * m.shape[3])
-    if not 1 <= Cc <= 4 or S2 < 1 or not 1 <= V <= 16:
-        raise ValueError(f"cloud_gather_views: 1 <= C <= 4, S2 >= 1 and 1 <= V <= 16, got C = {Cc}, S2 = {S2}, V = {V}")
-    ix = torch.as_tensor(index).to(device=dev, dtype=torch.int32).contiguous()
-    if ix.dim() != 2 or ix.shape[0] != n:
-        raise ValueError(f"cloud_gather_views: index [n, cap], got {tuple(ix.shape)} for n = {n}")
-    cap = int(ix.shape[1])
-    out = torch.empty(n, cap, Cc, dtype=torch.float32, device=dev)
-    if n and cap:
-        _lib.check(lib.rgbm_cloud_gather_views(_lib.ptr(m), _lib.ptr(ix), n, V, S2, Cc, cap, _lib.ptr(out), _lib.stream_ptr(stream)),
-                   "rgbm_cloud_gather_views")
-    return out
-
-
-_DEFAULT_BBOX = np.asarray([[0, 0, 0], [0, 0, 1], [0, 1, 0], [0, 1, 1], [1, 0, 0], [1, 0, 1], [1, 1, 0], [1, 1, 1]], dtype=np.float64) + 10.0
-_BBOX_SIGNS = np.asarray([[1, 1, 1], [1, 1, -1], [-1, 1, 1], [-1, 1, -1], [1, -1, 1], [1, -1, -1], [-1, -1, 1], [-1, -1, -1]], dtype=np.float64)
-
-
-def _fit_shapes(nocs, cloud, count):
-    if nocs.ndim != 3 or nocs.shape[2] != 3 or tuple(cloud.shape) != tuple(nocs.shape):
-        raise ValueError(f"cloud_similarity: nocs and cloud [n, cap, 3], got {tuple(nocs.shape)} and {tuple(cloud.shape)}")
-    if tuple(count.shape) != (nocs.shape[0], 2):
-        raise ValueError(f"cloud_similarity: count [n, 2], got {tuple(count.shape)}")
-    return int(nocs.shape[0]), int(nocs.shape[1])
-
-
-def cloud_similarity(nocs, cloud, count, seed: int = 0, stream=None):
-    """The reference's similarity RANSAC (lib/align.py:10-104) between a packed cloud's object-space rows nocs [n, cap, 3] and its
-    world-frame rows cloud [n, cap, 3] (rgbm_cloud_similarity): over the first m = min(cap, count.sum(1)) rows of
-    pose b, 128 five-point hypotheses drawn by the seeded hash (sample k of hypothesis i = mix32(seed, 128 b + i, k) % m), the reference's
-    scan and the final Umeyama fit over the kept hypothesis's inliers, then the box of `bbox_from_srt` without a world transform.  Returns
-    CUDA tensors (bbox [n,8,3] f64, srt [n,13] f64 = scale, R, t, info [n,4] i32 = m, kept hypothesis or -1, its inliers, hypotheses
-    examined, valid [n] i32).  m < 5, a NaN row, no consensus: valid 0, the +10 cube, srt[:, 0] NaN.  Two calls give the same bytes."""
-    lib = _lib.load()
-    nc = torch.as_tensor(nocs)
-    dev = nc.device if nc.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    nc = nc.to(device=dev, dtype=torch.float32).contiguous()
-    cl = torch.as_tensor(cloud).to(device=dev, dtype=torch.float32).contiguous()
-    ct = torch.as_tensor(count).to(device=dev, dtype=torch.int32).contiguous()
-    n, cap = _fit_shapes(nc, cl, ct)
-    bbox = torch.from_numpy(_DEFAULT_BBOX).to(dev).expand(n, 8, 3).contiguous()
-    srt = torch.zeros(n, 13, dtype=torch.float64, device=dev)
-    info = torch.zeros(n, 4, dtype=torch.int32, device=dev)
-    valid = torch.zeros(n, dtype=torch.int32, device=dev)
-    if n and cap:
-        nb = C.c_size_t()
-        _lib.check(lib.rgbm_cloud_similarity_scratch_bytes(n, cap, C.byref(nb)), "rgbm_cloud_similarity_scratch_bytes")
-        scratch = torch.empty(max(nb.value // 8, 1), dtype=torch.int64, device=dev)
-        if stream is not None:
-            scratch.record_stream(stream)
-        _lib.check(lib.rgbm_cloud_similarity(_lib.ptr(nc), _lib.ptr(cl), _lib.ptr(ct), n, cap, int(seed) & 0xFFFFFFFF, _lib.ptr(bbox), _lib.ptr(srt),
-                                             _lib.ptr(info), _lib.ptr(valid), _lib.ptr(scratch), nb.value, _lib.stream_ptr(stream)),
-                   "rgbm_cloud_similarity")
-    elif n:                                                   # no rows at all: every pose is invalid
-        srt[:, 0] = float("nan")
-        srt[:, 1] = srt[:, 5] = srt[:, 9] = 1.0
-        info[:, 1] = -1
-    return bbox, srt, info, valid
-
-
-def _mix32(seed: int, frame: int, idx: int) -> int:
-    M = 0xFFFFFFFF
-    h = (seed ^ ((frame * 0x9E3779B9) & M) ^ ((idx * 0x85EBCA6B) & M)) & M
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & M
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & M
-    h ^= h >> 16
-    return h
-
-
-def _umeyama_ref(src, tgt):
-    """lib/align.py:10-41 on rows src / tgt [k, 3] float64 -> (scale, R, t)."""
-    ms, mt = src.mean(axis=0), tgt.mean(axis=0)
-    cs, ct = src - ms, tgt - mt
-    cov = ct.T @ cs / src.shape[0]
-    if np.isnan(cov).any():
-        raise RuntimeError("NaN covariance")
-    U, D, Vh = np.linalg.svd(cov, full_matrices=True)
-    if np.linalg.det(U) * np.linalg.det(Vh) < 0.0:
-        D[-1] = -D[-1]
-        U[:, -1] = -U[:, -1]
-    R = U @ Vh
-    with np.errstate(all="ignore"):
-        scale = 1 / np.var(src, axis=0).sum() * np.sum(D)
-    return scale, R, mt - ms.dot(scale * R.T)
-
-
-def cloud_similarity_ref(nocs, cloud, count, seed: int = 0):
-    """float64 numpy twin of `cloud_similarity` (tests, documentation): the semantics of include/rgbm.h restated per pose.  Returns numpy
-    arrays (bbox [n,8,3] f64, srt [n,13] f64, info [n,4] i32, valid [n] i32)."""
-    nocs, cloud, count = np.asarray(nocs, dtype=np.float32), np.asarray(cloud, dtype=np.float32), np.asarray(count)
-    n, cap = _fit_shapes(nocs, cloud, count)
-    bbox = np.tile(_DEFAULT_BBOX, (n, 1, 1))
-    srt = np.zeros((n, 13))
-    srt[:, 0], srt[:, 1], srt[:, 5], srt[:, 9] = np.nan, 1.0, 1.0, 1.0
-    info, valid = np.zeros((n, 4), dtype=np.int32), np.zeros(n, dtype=np.int32)
-    seed = int(seed) & 0xFFFFFFFF
-    for b in range(n):
-        m = int(min(cap, max(0, int(count[b, 0]) + int(count[b, 1]))))
-        info[b] = (m, -1, 0, 0)
-        s, t = nocs[b, :m].astype(np.float64), cloud[b, :m].astype(np.float64)
-        if m < 5 or np.isnan(s).any() or np.isnan(t).any():
-            continue
-        thr = 2 * np.sqrt(((s - s.mean(axis=0)) ** 2).sum(axis=1)).max() / 10.0
-        best, best_h, best_inl, examined, failed = 0.0, -1, None, 0, False
-        for i in range(128):
-            idx = [_mix32(seed, 128 * b + i, k) % m for k in range(5)]
-            try:
-                sc, R, tr = _umeyama_ref(s[idx], t[idx])
-            except RuntimeError:
-                failed = True
-                break
-            examined = i + 1
-            with np.errstate(all="ignore"):
-                inl = np.sqrt(((t - (s @ (sc * R).T + tr)) ** 2).sum(axis=1)) < sc * thr
-            ratio = int(inl.sum()) / m
-            if ratio > best:
-                best, best_h, best_inl = ratio, i, inl
-            b5 = (best * best) * (best * best) * best
-            if (1 - (1 - b5) ** i) > 0.99:
-                break
-        if failed:
-            continue
-        if best < 0.1:
-            info[b] = (m, -1, 0, examined)
-            continue
-        info[b] = (m, best_h, int(best_inl.sum()), examined)
-        try:
-            sc, R, tr = _umeyama_ref(s[best_inl], t[best_inl])
-        except RuntimeError:
-            continue
-        srt[b, 1:10], srt[b, 10:13] = R.reshape(9), tr
-        with np.errstate(all="ignore"):
-            size = 2 * np.abs(s).max(axis=0) * sc
-            corners = (_BBOX_SIGNS * (size[None, :] / 2)) @ R.astype(np.float32).astype(np.float64).T + tr.astype(np.float32).astype(np.float64)
-        if np.isfinite(corners).all():
-            bbox[b], srt[b, 0], valid[b] = corners, sc, 1
-    return bbox, srt, info, valid
 
 
 def postprocess_regressed(view1_nocs, view1_r, view1_t, view1_s, E1, stream=None):

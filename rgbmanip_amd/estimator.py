@@ -20,20 +20,21 @@ from the network's own heads (`interface_v4.py:322-325`, `rgbm_adapose_postproce
 from __future__ import annotations
 
 import warnings
+from dataclasses import dataclass
+from functools import partial
 
 import numpy as np
 import torch
 
 from . import _lib, host_prepare
-from .adapose import (AdaPoseNet, cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity, depth_consistency, depth_fusion, depth_to_points, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs,
-                      prepare_inputs_windows)
+from .adapose import AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs, prepare_inputs_windows
+from .cloud import (DEFAULT_BBOX, cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity, depth_consistency, depth_fusion,
+                    depth_to_points)
 from .feature_cache import CachedViews, ContentFeatureCache, SlotFeatureCache
 from .host_prepare import _resize_linear, _resize_nearest, get_bbox      # noqa: F401  (part of this module's surface)
 from .upload import (ChunkPipeline, WindowRing, _nonzero_into, _split, frames_payload_bytes, frames_to_device, host_array,      # noqa: F401
                      masks_to_device)
 
-DEFAULT_BBOX = np.asarray([[0, 0, 0], [0, 0, 1], [0, 1, 0], [0, 1, 1], [1, 0, 0], [1, 0, 1], [1, 1, 0], [1, 1, 1]],
-                          dtype=np.float64) + 10.0
 _DEPTH_PLANES = np.arange(0.1, 0.1 * (24 - 0.5) + 0.1, 0.1, dtype=np.float32)      # the 24 sweep depths (interface_v5.py:259-262)
 
 
@@ -46,11 +47,46 @@ def _put(out, a, b, res):
         out[a:b] = res
 
 
-class _Cloud(dict):
-    """The options of `estimate_cloud` (px_max, rel_max, conf_min, masked, cap) on their way through the chunk pipeline, in the place of
-    `dense=True`: the third output shape beside the boxes and the dict of `estimate_depth`."""
-    def __bool__(self):
-        return True
+@dataclass(frozen=True)
+class ResultPlan:
+    """What a two-view call returns, on its way through upload, chunk pipeline, network and tails (`want=`): the boxes of `estimate` (the
+    default instance), the dict of `estimate_depth` (`maps`), that dict extended by `estimate_cloud` (`maps` and `cloud`, under the
+    thresholds and the capacity below), and with a `fit_seed` the fit of `estimate_cloud_pose` on top."""
+    maps: bool = False                 # the dense maps: the network runs densely and on the plain path (the content cache is bypassed)
+    cloud: bool = False                # ... checked against each other and packed (with maps only)
+    px_max: float = 1.0
+    rel_max: float = 0.01
+    conf_min: float = 0.0
+    masked: bool = True
+    cap: int | None = 0                # rows of the packed cloud
+    fit_seed: int | None = None        # seed of the similarity fit; None: no fit
+
+    @property
+    def fit(self) -> bool:
+        """`cloud_similarity` runs on the cloud's NOCS rows, after the chunks."""
+        return self.fit_seed is not None
+
+    @property
+    def prepare_kw(self) -> dict:
+        """Extra keywords of `_prepare` / `_prepare_windows`."""
+        return {"want_mask": True} if self.cloud else {}
+
+    @property
+    def network_kw(self) -> dict:
+        """Extra keywords of the network call."""
+        if not self.maps:
+            return {}
+        return {"dense_depth": True, "dense_nocs": True} if self.fit else {"dense_depth": True}
+
+
+@dataclass(frozen=True)
+class ViewsPlan(ResultPlan):
+    """The plan of `estimate_cloud_views`: every frame's maps, fused where `n_min` sources agree; cap None: V S S."""
+    maps: bool = True
+    n_min: int = 1
+
+
+BOXES = ResultPlan()
 
 
 def _to_host(out):
@@ -220,7 +256,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         n = len(rgb1_batch)
         if self.prepare_mode == "device":
             return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
-                                              view2_mask_batch, view2_extrinsic_batch)
+                                              view2_mask_batch, view2_extrinsic_batch, want=BOXES)
         out = np.repeat(DEFAULT_BBOX[None], n, axis=0)
         rows, img1, img2, ch1, ch2, P1, P2, K1, E1 = [], [], [], [], [], [], [], [], []
         pt1, pt2, E2, K0 = [], [], [], []                    # the PnP branch also needs the pixels, the second extrinsic and the original K
@@ -251,31 +287,28 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         return out
 
     # ------------------------------------------------------------------ host frames -> HBM (upload.py)
-    def _estimate_host_frames(self, K, rgb1, mask1, E1, rgb2, mask2, E2, dense=False):
+    def _estimate_host_frames(self, K, rgb1, mask1, E1, rgb2, mask2, E2, want: ResultPlan):
         """`estimate` with `hip_prepare: device`: one `estimate_device` call, or for more than `hip_upload_chunk` host poses the
-        chunk pipeline (upload.ChunkPipeline), whose per-chunk work is defined here.  `dense`: the dict of `estimate_depth` (True) or of
-        `estimate_cloud` (a `_Cloud`) instead of the boxes (plain path: no content cache)."""
+        chunk pipeline (upload.ChunkPipeline), whose per-chunk work is defined here.  `want`: the boxes, or the dict of `estimate_depth`
+        / `estimate_cloud` instead (plain path: no content cache)."""
         n = len(rgb1)
         chunk = int(self.cfg.get("hip_upload_chunk", 32))
         cuda = [isinstance(x, torch.Tensor) and x.is_cuda for x in (rgb1, rgb2, mask1, mask2)]
         if self.upload_mode == "windows" and not any(cuda):
-            return self._estimate_host_windows(K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk, dense)
+            return self._estimate_host_windows(K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk, want=want)
         self.upload_bytes_last_call, self.upload_table_bytes_last_call = frames_payload_bytes(rgb1, rgb2, mask1, mask2), 0
-        on_dev = cuda[0] or cuda[1]
-        on_device = self.estimate_depth_device if dense else self.estimate_device
-        if isinstance(dense, _Cloud):
-            def on_device(*args, frame0=0):
-                return self._estimate_device(*args, frame0=frame0, dense=dense)
-        if on_dev or n <= chunk or chunk <= 0:
+        # boxes: the public entry point, so that what a subclass or a test puts in its place is what runs
+        on_device = partial(self._estimate_device, want=want) if want.maps else self.estimate_device
+        if cuda[0] or cuda[1] or n <= chunk or chunk <= 0:
             return _to_host(self._cloud_fit(on_device(np.asarray(K), self._upload_frames(rgb1), self._upload_masks(mask1), np.asarray(E1),
-                                                      self._upload_frames(rgb2), self._upload_masks(mask2), np.asarray(E2)), dense))
+                                                      self._upload_frames(rgb2), self._upload_masks(mask2), np.asarray(E2)), want=want))
         dev = self.estimator.device
         srcs = [host_array(x) for x in (rgb1, rgb2, mask1, mask2)]
         pipe = self._pipe = ChunkPipeline.matching(self._pipe, chunk, srcs, dev)
         Kd = torch.as_tensor(np.asarray(K)).to(dev)
         E1d, E2d = torch.as_tensor(np.asarray(E1)).to(dev), torch.as_tensor(np.asarray(E2)).to(dev)
-        out = self._alloc_out(n, dev, dense)
-        if self.feature_content and not dense:
+        out = self._alloc_out(n=n, dev=dev, want=want)
+        if self.feature_content and not want.maps:
             self._content.reserve(n)
             S, wp = self.cfg["img_size"], self._pnp_branch()
 
@@ -292,11 +325,11 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             def network(a, b, d):
                 _put(out, a, b, on_device(Kd[a:b], self._upload_frames(d[0]), d[2], E1d[a:b], self._upload_frames(d[1]), d[3], E2d[a:b], frame0=a))
             pipe.run(srcs, n, network)
-        res = _to_host(self._cloud_fit(out, dense))
+        res = _to_host(self._cloud_fit(out, want=want))
         pipe.trace.report(self.upload_bytes_last_call)
         return res
 
-    def _estimate_host_windows(self, K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk, dense=False):
+    def _estimate_host_windows(self, K, rgb1, mask1, E1, rgb2, mask2, E2, n, chunk, want: ResultPlan):
         """`_estimate_host_frames` with hip_upload: "windows": the host derives every frame's crop window from its mask, packs that part of
         the frame and of the mask into pinned staging and uploads the packed buffers (upload.WindowRing); `rgbm_prepare_inputs_windows`
         writes img / choose / pts2d / Kcrop / valid from them and everything behind is the code of the whole-frame path.  At most
@@ -306,30 +339,29 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         Kd = torch.as_tensor(np.asarray(K)).to(dev)
         E1d, E2d = torch.as_tensor(np.asarray(E1)).to(dev), torch.as_tensor(np.asarray(E2)).to(dev)
         S, wp = self.cfg["img_size"], self._pnp_branch()
-        kw = {"dense": dense} if dense else {}
-        mk = {"want_mask": True} if isinstance(dense, _Cloud) else {}
+        cached = self.feature_content and not want.maps
 
         def prep(a, b, d):
-            return [self._prepare_windows(d, v, Kd[a:b], S, 1024, self.prepare_seed + v, want_pts2d=wp, frame0=a, **mk) for v in (0, 1)]
+            return [self._prepare_windows(d, v, Kd[a:b], S, 1024, self.prepare_seed + v, want_pts2d=wp, frame0=a, **want.prepare_kw) for v in (0, 1)]
         if n <= chunk or chunk <= 0:
             ring = self._wring = WindowRing.matching(self._wring, n, srcs, dev, slots=1, grow=True)
             ring.payload_bytes = ring.table_bytes = 0
             ring.wait(0)
             ring.stage(0, srcs, 0, n)
             pa, pb = prep(0, n, ring.copy(0, n))
-            if self.feature_content and not dense:
+            if cached:
                 self._content.reserve(n)
                 out = self._estimate_keyed(self._content.keys(pa, pb), E1d, E2d, Kd)
             else:
-                out = self._estimate_prepared(pa, pb, E1d, E2d, Kd, **kw)
-            res = _to_host(self._cloud_fit(out, dense))
+                out = self._estimate_prepared(pa, pb, E1d, E2d, Kd, want=want)
+            res = _to_host(self._cloud_fit(out, want=want))
             self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
             return res
         pipe = self._pipe = ChunkPipeline.matching(self._pipe, chunk, srcs, dev, windows=True)
         ring = pipe.ring
         ring.payload_bytes = ring.table_bytes = 0
-        out = self._alloc_out(n, dev, dense)
-        if self.feature_content and not dense:
+        out = self._alloc_out(n=n, dev=dev, want=want)
+        if cached:
             self._content.reserve(n)
 
             def prepare(a, b, d):
@@ -342,9 +374,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         else:
             def network(a, b, d):
                 pa, pb = prep(a, b, d)
-                _put(out, a, b, self._estimate_prepared(pa, pb, E1d[a:b], E2d[a:b], Kd[a:b], **kw))
+                _put(out, a, b, self._estimate_prepared(pa, pb, E1d[a:b], E2d[a:b], Kd[a:b], want=want))
             pipe.run(srcs, n, network)
-        res = _to_host(self._cloud_fit(out, dense))
+        res = _to_host(self._cloud_fit(out, want=want))
         self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
         pipe.trace.report(self.upload_bytes_last_call)
         return res
@@ -376,20 +408,18 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         uint8 (byte b = the pixel fl32(b / 255); read as bytes, same boxes bit for bit), mask [N,H,W], E [N,4,4] world->camera.
         Returns a CUDA tensor [N,8,3] float64; samples the reference would skip
         (empty mask) or reject (non-finite box) hold `default_bbox`."""
-        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0)
+        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, want=BOXES)
 
-    def _estimate_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0, dense: bool = False):
-        S = self.cfg["img_size"]
-        dev = self.estimator.device
+    def _estimate_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0, *, want: ResultPlan):
+        S, dev = self.cfg["img_size"], self.estimator.device
         Kd = torch.as_tensor(K).to(dev)
-        wp = self._pnp_branch()
-        mk = {"want_mask": True} if isinstance(dense, _Cloud) else {}
-        a = self._prepare(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, S, 1024, self.prepare_seed, want_pts2d=wp, frame0=frame0, **mk)
-        b = self._prepare(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, want_pts2d=wp, frame0=frame0, **mk)
-        if self.feature_content and not dense:      # one host synchronisation per call: the keys must be on the host before the network can be enqueued
+        kw = dict(want_pts2d=self._pnp_branch(), frame0=frame0, **want.prepare_kw)
+        a = self._prepare(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, S, 1024, self.prepare_seed, **kw)
+        b = self._prepare(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, S, 1024, self.prepare_seed + 1, **kw)
+        if self.feature_content and not want.maps:      # one host synchronisation per call: the keys must be on the host before the network can be enqueued
             self._content.reserve(int(Kd.shape[0]))
             return self._estimate_keyed(self._content.keys(a, b), E1, E2, Kd)
-        return self._estimate_prepared(a, b, E1, E2, Kd, **({"dense": dense} if dense else {}))
+        return self._estimate_prepared(a, b, E1, E2, Kd, want=want)
 
     # ------------------------------------------------------------------ dense depth of the view-1 crops (DESIGN.md "Dense depth maps")
     def estimate_depth(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
@@ -404,28 +434,24 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         if self.prepare_mode != "device":
             raise ValueError(f'estimate_depth crops on the device: it needs hip_prepare: "device", got {self.prepare_mode!r}')
         return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
-                                          view2_mask_batch, view2_extrinsic_batch, dense=True)
+                                          view2_mask_batch, view2_extrinsic_batch, want=ResultPlan(maps=True))
 
     def estimate_depth_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0):
         """`estimate_depth` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
-        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=True)
+        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, want=ResultPlan(maps=True))
 
     # ------------------------------------------------------------------ consistent two-view point cloud (DESIGN.md section 5k)
-    def _cloud_options(self, px_max, rel_max, conf_min, masked, max_points, **fit):
+    def _cloud_options(self, px_max, rel_max, conf_min, masked, max_points, **fit) -> ResultPlan:
         if self.prepare_mode != "device":
             raise ValueError(f'estimate_cloud crops on the device: it needs hip_prepare: "device", got {self.prepare_mode!r}')
         if not self.view2_heads:
             raise ValueError("estimate_cloud checks the view-1 depth map against the view-2 map: it needs a net that runs the view-2 heads "
                              "(cfg hip_view2_heads: True; the default for the regression tail is False)")
-        S = self.cfg["img_size"]
-        cap = 2 * S * S if max_points is None else int(max_points)
+        cap = 2 * self.cfg["img_size"] ** 2 if max_points is None else int(max_points)
         if cap < 0:
             raise ValueError(f"estimate_cloud: max_points >= 0, got {max_points}")
-        o = _Cloud(px_max=float(px_max), rel_max=float(rel_max), conf_min=float(conf_min), masked=bool(masked), cap=cap)
-        if fit:                                               # estimate_cloud_pose: the seed of the fit, an int from here on
-            seed = fit["fit_seed"]
-            o["fit_seed"] = int(self.cfg.get("hip_ransac_seed", 0) if seed is None else seed)
-        return o
+        seed = int(self.cfg.get("hip_ransac_seed", 0) if fit["fit_seed"] is None else fit["fit_seed"]) if fit else None      # estimate_cloud_pose
+        return ResultPlan(True, True, float(px_max), float(rel_max), float(conf_min), bool(masked), cap, seed)
 
     def estimate_cloud(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
                        view2_extrinsic_batch, *, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True, max_points=None):
@@ -438,15 +464,14 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         2 S S).  A pixel is kept when it comes back within `px_max` pixels at a depth within `rel_max`, with confidence >= `conf_min`
         and, with `masked`, inside its crop mask.  A sample with valid 0 has keep 0, count [0, 0] and NaN maps and cloud rows.  Needs the
         view-2 maps, i.e. cfg hip_view2_heads: True, and hip_prepare: "device"; the feature cache is bypassed as in `estimate_depth`."""
-        opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points)
-        return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
-                                          view2_mask_batch, view2_extrinsic_batch, dense=opts)
+        return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
+                                          view2_extrinsic_batch, want=self._cloud_options(px_max, rel_max, conf_min, masked, max_points))
 
     def estimate_cloud_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0, *, px_max=1.0, rel_max=0.01, conf_min=0.0,
                               masked=True, max_points=None):
         """`estimate_cloud` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
-        opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points)
-        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=opts)
+        return self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0,
+                                     want=self._cloud_options(px_max, rel_max, conf_min, masked, max_points))
 
     # ------------------------------------------------------------------ a box fitted to the two-view cloud (DESIGN.md section 5l)
     def estimate_cloud_pose(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
@@ -460,43 +485,42 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         [n,13] f64 (scale, R, t), `fit_info` [n,4] i32 (rows used, kept hypothesis or -1, its inliers, hypotheses examined) and
         `valid_cloud` [n] i32.  A sample with valid 0, fewer than 5 rows or no consensus has valid_cloud 0 and the +10 cube; a sample with
         valid 0 has NaN NOCS maps."""
-        opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points, fit_seed=fit_seed)
-        return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch,
-                                          view2_mask_batch, view2_extrinsic_batch, dense=opts)
+        return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
+                                          view2_extrinsic_batch, want=self._cloud_options(px_max, rel_max, conf_min, masked, max_points, fit_seed=fit_seed))
 
     def estimate_cloud_pose_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0, *, px_max=1.0, rel_max=0.01, conf_min=0.0,
                                    masked=True, max_points=None, fit_seed=None):
         """`estimate_cloud_pose` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
         opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points, fit_seed=fit_seed)
-        return self._cloud_fit(self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, dense=opts), opts)
+        return self._cloud_fit(self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, want=opts), want=opts)
 
-    def _cloud_fit(self, out, o):
+    def _cloud_fit(self, out, want: ResultPlan):
         """The fit of `estimate_cloud_pose` over all poses of a call at once (so that pose b draws sample stream b however the call was
         chunked); every other result passes through untouched."""
-        if not (isinstance(o, _Cloud) and "fit_seed" in o):
+        if not want.fit:
             return out
-        bbox, srt, info, valid = cloud_similarity(out["cloud_nocs"], out["cloud"], out["count"], seed=o["fit_seed"])
+        bbox, srt, info, valid = cloud_similarity(out["cloud_nocs"], out["cloud"], out["count"], seed=want.fit_seed)
         out = dict(out)
         out.update(bbox_cloud=bbox, srt_cloud=srt, fit_info=info, valid_cloud=valid)
         return out
 
-    def _cloud_tail(self, r, pred, a, b, E1d, E2d, ok, o: _Cloud):
+    def _cloud_tail(self, r, pred, a, b, E1d, E2d, ok, o: ResultPlan):
         """The dict of `estimate_depth` (r, left as it is) extended by the view-2 maps, the two checks and the packed cloud."""
         n = E1d.shape[0]
         nan = torch.full((), float("nan"), dtype=torch.float32, device=E1d.device)
         d2 = torch.where(ok.view(n, 1, 1), pred["view2_depth_map"], nan)
         c2 = torch.where(ok.view(n, 1, 1), pred["view2_depth_conf"], nan)
-        th = dict(px_max=o["px_max"], rel_max=o["rel_max"], conf_min=o["conf_min"])
-        m1, m2 = (a["mask"], b["mask"]) if o["masked"] else (None, None)
+        th = dict(px_max=o.px_max, rel_max=o.rel_max, conf_min=o.conf_min)
+        m1, m2 = (a["mask"], b["mask"]) if o.masked else (None, None)
         v1 = depth_consistency(r["depth"], a["Kcrop"], E1d, d2, b["Kcrop"], E2d, conf_a=r["conf"], mask_a=m1, **th)
         v2 = depth_consistency(d2, b["Kcrop"], E2d, r["depth"], a["Kcrop"], E1d, conf_a=c2, mask_a=m2, **th)
-        cloud, index, count = cloud_pack(v1["fused"], v1["keep"], a["Kcrop"], E1d, v2["fused"], v2["keep"], b["Kcrop"], E2d, max_points=o["cap"])
+        cloud, index, count = cloud_pack(v1["fused"], v1["keep"], a["Kcrop"], E1d, v2["fused"], v2["keep"], b["Kcrop"], E2d, max_points=o.cap)
         r.update(depth2=d2, conf2=c2, window2=b["window"], Kcrop2=b["Kcrop"], mask1=a["mask"], mask2=b["mask"], cloud=cloud,
                  cloud_index=index, count=count)
         for v, res in ((1, v1), (2, v2)):
             for k in ("fused", "keep", "reproj", "rel"):
                 r[f"{k}{v}"] = res[k]
-        if "fit_seed" in o:
+        if o.fit:
             n1 = torch.where(ok.view(n, 1, 1, 1), pred["view1_nocs_map"], nan)
             n2 = torch.where(ok.view(n, 1, 1, 1), pred["view2_nocs_map"], nan)
             r.update(nocs1=n1, nocs2=n2, cloud_nocs=cloud_gather(n1, n2, index))
@@ -512,11 +536,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             raise ValueError('estimate_cloud_views uploads whole frames: cfg hip_upload: "windows" is not implemented for it (use "frames")')
         if max_points is not None and int(max_points) < 0:
             raise ValueError(f"estimate_cloud_views: max_points >= 0, got {max_points}")
-        o = dict(n_min=int(n_min), px_max=float(px_max), rel_max=float(rel_max), conf_min=float(conf_min), masked=bool(masked),
-                 cap=None if max_points is None else int(max_points))
-        if fit:
-            o["fit_seed"] = int(self.cfg.get("hip_ransac_seed", 0) if fit_seed is None else fit_seed)
-        return o
+        seed = int(self.cfg.get("hip_ransac_seed", 0) if fit_seed is None else fit_seed) if fit else None
+        return ViewsPlan(px_max=float(px_max), rel_max=float(rel_max), conf_min=float(conf_min), masked=bool(masked),
+                         cap=None if max_points is None else int(max_points), fit_seed=seed, n_min=int(n_min))
 
     def estimate_cloud_views(self, K, frames, masks, E, *, n_min=1, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True, max_points=None,
                              fit=False, fit_seed=None):
@@ -557,8 +579,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         if frames.dim() != 5 or masks.dim() != 4 or masks.shape[:2] != frames.shape[:2]:
             raise ValueError(f"estimate_cloud_views: frames [n,V,H,W,3] and masks [n,V,H,W], got {tuple(frames.shape)} and {tuple(masks.shape)}")
         n, V = int(frames.shape[0]), int(frames.shape[1])
-        if not 2 <= V <= 16 or not 1 <= o["n_min"] <= V - 1:
-            raise ValueError(f"estimate_cloud_views: 2 <= V <= 16 and 1 <= n_min <= V - 1, got V = {V}, n_min = {o['n_min']}")
+        if not 2 <= V <= 16 or not 1 <= o.n_min <= V - 1:
+            raise ValueError(f"estimate_cloud_views: 2 <= V <= 16 and 1 <= n_min <= V - 1, got V = {V}, n_min = {o.n_min}")
         Kd = torch.as_tensor(K).to(device=dev, dtype=torch.float64)
         Ed = torch.as_tensor(E).to(device=dev, dtype=torch.float64)
         if tuple(Kd.shape) != (n, 3, 3) or tuple(Ed.shape) != (n, V, 4, 4):
@@ -572,72 +594,52 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         nb = torch.cat([nb[:, 1:], nb[:, V - 2:V - 1]], dim=1).reshape(N)      # p(k) = k + 1, p(V - 1) = V - 2
         b = {k: a[k].index_select(0, nb) for k in ("img", "choose", "Kcrop", "valid")}
         E2 = E1.index_select(0, nb)
-        consts = self._dev_consts
-        if consts is None or consts[0].device != dev:
-            consts = self._dev_consts = (torch.from_numpy(DEFAULT_BBOX).to(dev), torch.from_numpy(_DEPTH_PLANES).to(dev))
-        fit = "fit_seed" in o
         depth = torch.empty(N, S, S, dtype=torch.float32, device=dev)
         conf = torch.empty_like(depth)
-        nocs = torch.empty(N, S, S, 3, dtype=torch.float32, device=dev) if fit else None
-        lib = _lib.load()
+        nocs = torch.empty(N, S, S, 3, dtype=torch.float32, device=dev) if o.fit else None
         for lo in range(0, N, self._VIEWS_CHUNK):
             hi = min(lo + self._VIEWS_CHUNK, N)
-            P = []
-            for Kc, Ev in ((a["Kcrop"][lo:hi], E1[lo:hi]), (b["Kcrop"][lo:hi], E2[lo:hi])):
-                Pm = torch.empty(hi - lo, 4, 4, dtype=torch.float32, device=dev)
-                _lib.check(lib.rgbm_projection(_lib.ptr(Kc.contiguous()), _lib.ptr(Ev.contiguous()), _lib.ptr(Pm), hi - lo, _lib.stream_ptr()),
-                           "rgbm_projection")
-                P.append(Pm)
-            pred = self.estimator(a["img"][lo:hi], a["choose"][lo:hi], b["img"][lo:hi], b["choose"][lo:hi], P[0], P[1],
-                                  consts[1][None].expand(hi - lo, 24).contiguous(), dense_depth=True, **({"dense_nocs": True} if fit else {}))
+            rows = lambda d: {k: d[k][lo:hi] for k in ("img", "choose", "Kcrop")}      # noqa: E731
+            pred = self._forward(rows(a), rows(b), E1[lo:hi], E2[lo:hi], o)
             depth[lo:hi], conf[lo:hi] = pred["view1_depth_map"], pred["view1_depth_conf"]
-            if fit:
+            if o.fit:
                 nocs[lo:hi] = pred["view1_nocs_map"]
-            self._plain_views += 2 * (hi - lo)
-            self._content.bypassed += int(self.feature_cache)      # a chunk the cache was set for and did not serve
         ok = (a["valid"] != 0) & (b["valid"] != 0)
         nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
         depth = torch.where(ok.view(N, 1, 1), depth, nan).view(n, V, S, S)
         conf = torch.where(ok.view(N, 1, 1), conf, nan).view(n, V, S, S)
         Kc, mask = a["Kcrop"].view(n, V, 3, 3), a["mask"].view(n, V, S, S)
-        f = depth_fusion(depth, Kc, Ed, conf=conf, mask=mask if o["masked"] else None, px_max=o["px_max"], rel_max=o["rel_max"],
-                         conf_min=o["conf_min"], n_min=o["n_min"])
-        cloud, index, count = cloud_pack_views(f["fused"], f["keep"], Kc, Ed, max_points=o["cap"])
+        f = depth_fusion(depth, Kc, Ed, conf=conf, mask=mask if o.masked else None, px_max=o.px_max, rel_max=o.rel_max,
+                         conf_min=o.conf_min, n_min=o.n_min)
+        cloud, index, count = cloud_pack_views(f["fused"], f["keep"], Kc, Ed, max_points=o.cap)
         r = {"depth": depth, "conf": conf, "fused": f["fused"], "mask": mask, "keep": f["keep"], "nviews": f["nviews"], "agree": f["agree"],
              "window": a["window"].view(n, V, 4), "Kcrop": Kc, "valid": ok.to(torch.int32).view(n, V), "cloud": cloud, "cloud_index": index,
              "count": count}
-        if fit:
+        if o.fit:
             nocs = torch.where(ok.view(N, 1, 1, 1), nocs, nan).view(n, V, S, S, 3)
             cn = cloud_gather_views(nocs, index)
             folded = torch.stack([count.sum(dim=1, dtype=torch.int32), torch.zeros(n, dtype=torch.int32, device=dev)], dim=1)
-            bbox, srt, info, valid = cloud_similarity(cn, cloud, folded, seed=o["fit_seed"])
+            bbox, srt, info, valid = cloud_similarity(cn, cloud, folded, seed=o.fit_seed)
             r.update(nocs=nocs, cloud_nocs=cn, bbox_cloud=bbox, srt_cloud=srt, fit_info=info, valid_cloud=valid)
         return r
 
-    def _alloc_out(self, n, dev, dense):
+    def _alloc_out(self, n, dev, want: ResultPlan):
         """What the chunks of a pipelined call are written into: the boxes, the tensors of `estimate_depth`, or those of `estimate_cloud`."""
-        if isinstance(dense, _Cloud):
-            S, cap = self.cfg["img_size"], dense["cap"]
-            out = self._alloc_out(n, dev, True)
-            m = lambda dt: torch.empty(n, S, S, dtype=dt, device=dev)      # noqa: E731
-            out.update(depth2=m(torch.float32), conf2=m(torch.float32), window2=torch.empty(n, 4, dtype=torch.int32, device=dev),
-                       Kcrop2=torch.empty(n, 3, 3, dtype=torch.float64, device=dev), mask1=m(torch.uint8), mask2=m(torch.uint8),
-                       cloud=torch.empty(n, cap, 3, dtype=torch.float32, device=dev),
-                       cloud_index=torch.empty(n, cap, dtype=torch.int32, device=dev), count=torch.empty(n, 2, dtype=torch.int32, device=dev))
+        f32, i32, f64, u8 = torch.float32, torch.int32, torch.float64, torch.uint8
+        new = lambda dt, *shape: torch.empty(n, *shape, dtype=dt, device=dev)      # noqa: E731
+        if not want.maps:
+            return new(f64, 8, 3)
+        S, cap = self.cfg["img_size"], want.cap
+        out = {"bbox": new(f64, 8, 3), "depth": new(f32, S, S), "conf": new(f32, S, S), "points": new(f32, S, S, 3), "window": new(i32, 4),
+               "Kcrop": new(f64, 3, 3), "valid": new(i32)}
+        if want.cloud:
+            out.update(depth2=new(f32, S, S), conf2=new(f32, S, S), window2=new(i32, 4), Kcrop2=new(f64, 3, 3), mask1=new(u8, S, S),
+                       mask2=new(u8, S, S), cloud=new(f32, cap, 3), cloud_index=new(i32, cap), count=new(i32, 2))
             for v in (1, 2):
-                out.update({f"fused{v}": m(torch.float32), f"keep{v}": m(torch.uint8), f"reproj{v}": m(torch.float32), f"rel{v}": m(torch.float32)})
-            if "fit_seed" in dense:
-                out.update(nocs1=torch.empty(n, S, S, 3, dtype=torch.float32, device=dev), nocs2=torch.empty(n, S, S, 3, dtype=torch.float32, device=dev),
-                           cloud_nocs=torch.empty(n, cap, 3, dtype=torch.float32, device=dev))
-            return out
-        if not dense:
-            return torch.empty(n, 8, 3, dtype=torch.float64, device=dev)
-        S = self.cfg["img_size"]
-        f32 = dict(dtype=torch.float32, device=dev)
-        return {"bbox": torch.empty(n, 8, 3, dtype=torch.float64, device=dev), "depth": torch.empty(n, S, S, **f32),
-                "conf": torch.empty(n, S, S, **f32), "points": torch.empty(n, S, S, 3, **f32),
-                "window": torch.empty(n, 4, dtype=torch.int32, device=dev), "Kcrop": torch.empty(n, 3, 3, dtype=torch.float64, device=dev),
-                "valid": torch.empty(n, dtype=torch.int32, device=dev)}
+                out.update({f"fused{v}": new(f32, S, S), f"keep{v}": new(u8, S, S), f"reproj{v}": new(f32, S, S), f"rel{v}": new(f32, S, S)})
+            if want.fit:
+                out.update(nocs1=new(f32, S, S, 3), nocs2=new(f32, S, S, 3), cloud_nocs=new(f32, cap, 3))
+        return out
 
     def estimate_device_indexed(self, K, rgb_pool, mask_pool, E1, E2, map1, map2, fresh=None):
         """`estimate_device` reading the two views of sample i from entries map1[i] / map2[i] of a frame pool
@@ -657,7 +659,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             cached = self._slots.update(rgb_pool, mask_pool, S, fresh, map1, map2, self.prepare_seed)
         a = self._prepare(rgb_pool, mask_pool, K, S, 1024, self.prepare_seed, frame_map=map1, want_pts2d=wp)
         b = self._prepare(rgb_pool, mask_pool, K, S, 1024, self.prepare_seed + 1, frame_map=map2, want_pts2d=wp)
-        return self._estimate_prepared(a, b, E1, E2, K, cached=cached)
+        return self._estimate_prepared(a, b, E1, E2, K, cached=cached, want=BOXES)
 
     def invalidate_features(self):
         """Forget every cached feature map (the frame pool is about to be rewritten: `ControlInterface.reset_queue`)."""
@@ -667,54 +669,58 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     def _estimate_keyed(self, pend, E1, E2, K):
         """The network for the views of `ContentFeatureCache.keys`, from the cache's records; a call with more distinct crops than
         records (finish: None) runs the plain path, bit for bit."""
-        return self._estimate_prepared(pend.a, pend.b, E1, E2, K, cached=self._content.finish(pend))
+        return self._estimate_prepared(pend.a, pend.b, E1, E2, K, cached=self._content.finish(pend), want=BOXES)
 
     def _pnp_branch(self):
         return not self.cfg.get("direct_regression", True) and not self.cfg.get("use_depth", True)
 
-    def _estimate_prepared(self, a, b, E1, E2, K=None, cached: CachedViews | None = None, dense: bool = False):
+    def _consts(self, dev):
+        """(DEFAULT_BBOX, _DEPTH_PLANES) on the device: a pageable host -> device copy per call would block the host until the stream has
+        drained, i.e. serialise the chunk pipeline of _estimate_host_frames (measured: staging, copy and kernels ran back to back)."""
+        if self._dev_consts is None or self._dev_consts[0].device != dev:
+            self._dev_consts = (torch.from_numpy(DEFAULT_BBOX).to(dev), torch.from_numpy(_DEPTH_PLANES).to(dev))
+        return self._dev_consts
+
+    def _projection(self, Kc, E):
+        """P = K' E[:3], padded to 4x4 (interface_v5.py:264-270), fp64 -> fp32."""
+        n = int(E.shape[0])
+        P = torch.empty(n, 4, 4, dtype=torch.float32, device=E.device)
+        _lib.check(_lib.load().rgbm_projection(_lib.ptr(Kc.contiguous()), _lib.ptr(E.contiguous()), _lib.ptr(P), n, _lib.stream_ptr()), "rgbm_projection")
+        return P
+
+    def _forward(self, a, b, E1, E2, want: ResultPlan, cached: CachedViews | None = None):
+        """The network on the prepared views a / b: from the cache's records, or from the crops as `want` says, which the two counters count."""
+        n = int(E1.shape[0])
+        P1, P2 = self._projection(a["Kcrop"], E1), self._projection(b["Kcrop"], E2)
+        depths = self._consts(E1.device)[1][None].expand(n, 24).contiguous()
+        if cached is not None:
+            return self.estimator.forward_cached(cached.pool, cached.slot1, cached.slot2, a["choose"], b["choose"], P1, P2, depths)
+        pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], P1, P2, depths, **want.network_kw)
+        self._plain_views += 2 * n
+        if want.maps:
+            self._content.bypassed += int(self.feature_cache)      # a call / chunk the cache was set for and did not serve
+        return pred
+
+    def _estimate_prepared(self, a, b, E1, E2, K=None, cached: CachedViews | None = None, *, want: ResultPlan):
         dev = self.estimator.device
         E1d = torch.as_tensor(E1).to(device=dev, dtype=torch.float64)
         E2d = torch.as_tensor(E2).to(device=dev, dtype=torch.float64)
         n = E1d.shape[0]
-
-        def proj(Kc, E):                                  # P = K' E[:3], padded to 4x4 (interface_v5.py:264-270), fp64 -> fp32
-            P = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
-            _lib.check(_lib.load().rgbm_projection(_lib.ptr(Kc.contiguous()), _lib.ptr(E.contiguous()), _lib.ptr(P), n, _lib.stream_ptr()),
-                       "rgbm_projection")
-            return P
-        # constants live on the device: a pageable host -> device copy here would block the host until the stream has drained, i.e.
-        # serialise the chunk pipeline of _estimate_host_frames (measured: staging, copy and kernels ran back to back)
-        consts = self._dev_consts
-        if consts is None or consts[0].device != dev:
-            consts = self._dev_consts = (torch.from_numpy(DEFAULT_BBOX).to(dev), torch.from_numpy(_DEPTH_PLANES).to(dev))
-        depths = consts[1][None].expand(n, 24).contiguous()
-        if dense:
-            assert cached is None
-            nk = {"dense_nocs": True} if isinstance(dense, _Cloud) and "fit_seed" in dense else {}
-            pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], proj(a["Kcrop"], E1d), proj(b["Kcrop"], E2d), depths,
-                                  dense_depth=True, **nk)
-            self._plain_views += 2 * n
-            self._content.bypassed += int(self.feature_cache)      # a call / chunk the cache was set for and did not serve
-        elif cached is None:
-            pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], proj(a["Kcrop"], E1d), proj(b["Kcrop"], E2d), depths)
-            self._plain_views += 2 * n
-        else:
-            pred = self.estimator.forward_cached(cached.pool, cached.slot1, cached.slot2, a["choose"], b["choose"], proj(a["Kcrop"], E1d),
-                                                 proj(b["Kcrop"], E2d), depths)
+        assert cached is None or not want.maps
+        pred = self._forward(a, b, E1d, E2d, want, cached)
         bbox = self._bbox_tail(pred, a["choose"], a["Kcrop"], E1d, pts2d=(a.get("pts2d"), b.get("pts2d")), E2=E2d, K=K)
         ok = (a["valid"] != 0) & (b["valid"] != 0)
         if cached is not None and cached.ok is not None:
             ok = ok & cached.ok
-        box = torch.where(ok.view(n, 1, 1), bbox, consts[0].expand(n, 8, 3))
-        if not dense:
+        box = torch.where(ok.view(n, 1, 1), bbox, self._consts(dev)[0].expand(n, 8, 3))
+        if not want.maps:
             return box
         nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
         depth = torch.where(ok.view(n, 1, 1), pred["view1_depth_map"], nan)
         conf = torch.where(ok.view(n, 1, 1), pred["view1_depth_conf"], nan)
         res = {"bbox": box, "depth": depth, "conf": conf, "points": depth_to_points(depth, a["Kcrop"], E1d),      # NaN depth -> NaN points
                "window": a["window"], "Kcrop": a["Kcrop"], "valid": ok.to(torch.int32)}
-        return self._cloud_tail(res, pred, a, b, E1d, E2d, ok, dense) if isinstance(dense, _Cloud) else res
+        return self._cloud_tail(res, pred, a, b, E1d, E2d, ok, want) if want.cloud else res
 
     def _bbox_tail(self, pred, choose, Kcrop, E1, pts2d=None, E2=None, K=None):
         """interface_v5.py:318-374: scale / translation from the regressed rotation (`direct_regression`, the shipped configs)

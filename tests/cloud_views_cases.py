@@ -4,7 +4,7 @@ import functools
 import numpy as np
 
 from rgbmanip_amd import synth
-from rgbmanip_amd.adapose import depth_fusion_ref
+from rgbmanip_amd.cloud import depth_fusion_ref
 
 S = 224
 SCENES = {4: (0, 5), 6: (0, 5, 11)}      # V -> the seeds whose camera pairs make up the views

@@ -10,7 +10,7 @@ import pytest
 
 from cloud_fit_cases import CASES, SEED, oracle_fit, planted
 from rgbmanip_amd import _lib
-from rgbmanip_amd.adapose import cloud_similarity_ref
+from rgbmanip_amd.cloud import cloud_similarity_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("rgbm_adapose_forward_maps", "rgbm_nocs_map", "rgbm_cloud_gather", "rgbm_cloud_similarity", "rgbm_cloud_similarity_scratch_bytes")
@@ -121,6 +121,6 @@ def test_python_argument_errors():
     est.view2_heads = True
     with pytest.raises(ValueError, match="max_points"):
         est.estimate_cloud_pose_device(None, None, None, None, None, None, None, max_points=-1)
-    assert est._cloud_options(1.0, 0.01, 0.0, True, None, fit_seed=None)["fit_seed"] == 7
-    assert est._cloud_options(1.0, 0.01, 0.0, True, None, fit_seed=3)["fit_seed"] == 3
-    assert "fit_seed" not in est._cloud_options(1.0, 0.01, 0.0, True, None)
+    assert est._cloud_options(1.0, 0.01, 0.0, True, None, fit_seed=None).fit_seed == 7
+    assert est._cloud_options(1.0, 0.01, 0.0, True, None, fit_seed=3).fit_seed == 3
+    assert est._cloud_options(1.0, 0.01, 0.0, True, None).fit_seed is None

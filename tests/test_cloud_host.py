@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from rgbmanip_amd import _lib, synth
-from rgbmanip_amd.adapose import depth_consistency_ref
+from rgbmanip_amd.cloud import depth_consistency_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("rgbm_depth_consistency", "rgbm_cloud_pack")

@@ -10,7 +10,7 @@ import pytest
 
 from cloud_views_cases import SCENES, assert_scene_preconditions, sphere_ref, sphere_views
 from rgbmanip_amd import _lib, synth
-from rgbmanip_amd.adapose import depth_consistency_ref, depth_fusion_ref
+from rgbmanip_amd.cloud import depth_consistency_ref, depth_fusion_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("rgbm_depth_fusion", "rgbm_cloud_pack_views", "rgbm_cloud_gather_views")
@@ -133,8 +133,8 @@ def test_estimator_refusals_need_no_device():
     est.upload_mode = "frames"
     with pytest.raises(ValueError, match="max_points"):
         est.estimate_cloud_views_device(None, None, None, None, max_points=-1)
-    assert est._views_options(1, 1.0, 0.01, 0.0, True, None, True, None)["fit_seed"] == 7
-    assert "fit_seed" not in est._views_options(1, 1.0, 0.01, 0.0, True, None, False, 3)
+    assert est._views_options(1, 1.0, 0.01, 0.0, True, None, True, None).fit_seed == 7
+    assert est._views_options(1, 1.0, 0.01, 0.0, True, None, False, 3).fit_seed is None
     base = AdaPoseEstimator_baseline.__new__(AdaPoseEstimator_baseline)
     for name in ("estimate_cloud_views", "estimate_cloud_views_device"):
         with pytest.raises(NotImplementedError, match=name):

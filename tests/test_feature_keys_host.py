@@ -193,7 +193,7 @@ def test_content_mode_is_a_superset_of_true(monkeypatch):
     for mode in (True, "content"):
         e = _est(hip_feature_cache=mode)
         monkeypatch.setattr(e._slots, "update", lambda *a: seen.append(("update", a[3])) or "CACHED")
-        monkeypatch.setattr(e, "_estimate_prepared", lambda a, b, E1, E2, K, cached=None: seen.append(("run", cached)) or "BOX")
+        monkeypatch.setattr(e, "_estimate_prepared", lambda a, b, E1, E2, K, cached=None, want=None: seen.append(("run", cached)) or "BOX")
         assert e.estimate_device_indexed("K", "rgb", "mask", "E1", "E2", [0], [1], fresh=[1]) == "BOX"
     assert seen == [("update", [1]), ("run", "CACHED")] * 2
 
@@ -243,7 +243,7 @@ def test_slot_cache_result_reaches_estimate_prepared(monkeypatch):
     views = CachedViews("POOL", "S1", "S2", "OK")
     calls, seen = [], []
     monkeypatch.setattr(est._slots, "update", lambda *a: calls.append(a) or views)
-    monkeypatch.setattr(est, "_estimate_prepared", lambda a, b, E1, E2, K, cached=None: seen.append(cached) or "BOX")
+    monkeypatch.setattr(est, "_estimate_prepared", lambda a, b, E1, E2, K, cached=None, want=None: seen.append(cached) or "BOX")
     assert est.estimate_device_indexed("K", "rgb", "mask", "E1", "E2", [0], [1], fresh=[1]) == "BOX"
     assert calls == [("rgb", "mask", est.cfg["img_size"], [1], [0], [1], est.prepare_seed)]
     assert len(seen) == 1 and seen[0] is views and seen[0].pool == "POOL" and seen[0].ok == "OK"

@@ -8,8 +8,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from rgbmanip_amd import synth, upload  # noqa: E402
-from rgbmanip_amd.adapose import (AdaPoseNet, cloud_pack, depth_consistency, depth_consistency_ref, depth_to_points, prepare_inputs,  # noqa: E402
-                                  prepare_inputs_windows)
+from rgbmanip_amd.adapose import AdaPoseNet, prepare_inputs, prepare_inputs_windows  # noqa: E402
+from rgbmanip_amd.cloud import cloud_pack, depth_consistency, depth_consistency_ref, depth_to_points  # noqa: E402
 
 S = 224
 H, W = 480, 640

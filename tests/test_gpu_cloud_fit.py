@@ -7,7 +7,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from cloud_fit_cases import CASES, SEED, oracle_fit, planted  # noqa: E402
-from rgbmanip_amd.adapose import cloud_similarity  # noqa: E402
+from rgbmanip_amd.cloud import cloud_similarity  # noqa: E402
 
 S = 224
 

@@ -9,8 +9,9 @@ pytestmark = pytest.mark.gpu
 
 from cloud_views_cases import assert_scene_preconditions, conf_and_mask, sphere_ref, sphere_views  # noqa: E402
 from rgbmanip_amd import synth  # noqa: E402
-from rgbmanip_amd.adapose import (AdaPoseNet, cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity,  # noqa: E402
-                                  depth_consistency, depth_fusion, depth_fusion_ref, depth_to_points)
+from rgbmanip_amd.adapose import AdaPoseNet  # noqa: E402
+from rgbmanip_amd.cloud import (cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity,  # noqa: E402
+                                depth_consistency, depth_fusion, depth_fusion_ref, depth_to_points)
 
 S = 224
 H, W = 480, 640

@@ -9,7 +9,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from rgbmanip_amd import _lib, synth, upload  # noqa: E402
-from rgbmanip_amd.adapose import AdaPoseNet, depth_to_points, depth_to_points_ref, prepare_inputs  # noqa: E402
+from rgbmanip_amd.adapose import AdaPoseNet, prepare_inputs  # noqa: E402
+from rgbmanip_amd.cloud import depth_to_points, depth_to_points_ref  # noqa: E402
 
 RTOL_FP32 = 1e-4            # the number tests/test_gpu_adapose.py applies to the point depth
 OUT_KEYS = ["view1_nocs", "view2_nocs", "view1_depth", "view2_depth", "view1_r", "view2_r", "view1_t", "view2_t", "view1_s", "view2_s"]

@@ -7,7 +7,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from rgbmanip_amd import synth  # noqa: E402
-from rgbmanip_amd.adapose import AdaPoseNet, cloud_gather, nocs_map  # noqa: E402
+from rgbmanip_amd.adapose import AdaPoseNet, nocs_map  # noqa: E402
+from rgbmanip_amd.cloud import cloud_gather  # noqa: E402
 
 RTOL_FP32 = 1e-4            # the project's tensor-normalised gate (tests/test_gpu_adapose.py)
 KERNEL_ATOL = 2e-6          # the fp32 entry of tests/test_gpu_adapose.py:781, on tanh-bounded values

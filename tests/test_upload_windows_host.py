@@ -203,7 +203,7 @@ def test_upload_bytes_last_call_formulas(frame_dtype, monkeypatch):
     est = _stub_est(hip_upload="windows")
     seen = []
     monkeypatch.setattr(est, "_prepare_windows", lambda d, v, Kd, *a, **kw: seen.append((v, d.window[v].numpy().copy(), kw["frame0"])) or {})
-    monkeypatch.setattr(est, "_estimate_prepared", lambda a, b, E1, E2, K=None, cached=None: torch.zeros(len(E1), 8, 3, dtype=torch.float64))
+    monkeypatch.setattr(est, "_estimate_prepared", lambda a, b, E1, E2, K=None, cached=None, want=None: torch.zeros(len(E1), 8, 3, dtype=torch.float64))
     assert est.upload_bytes_last_call == 0
     box = est.estimate(K, frames, m8, E, rgb2, mask2, E)
     assert box.shape == (n, 8, 3) and [s[0] for s in seen] == [0, 1] and seen[0][2] == 0

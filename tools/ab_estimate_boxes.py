@@ -2,6 +2,7 @@
 trees (each run its own process, both with RGBM_HIP_LIB at the same librgbm_hip.so) and compare bit for bit.
 
 usage: ab_estimate_boxes.py out.npz            (in each tree)
+       ab_estimate_boxes.py --dense out.npz    (the dense calls alone: `dense` below)
        ab_estimate_boxes.py --compare a.npz b.npz
 
 Inputs: n = 5 poses of 480x640 with one empty mask (big ellipse, blob at the border, empty, two corner blobs, thin line) — three chunks
@@ -20,8 +21,8 @@ def compare(a, b):
         print("different call lists:", sorted(set(A.files) ^ set(B.files)))
         return 1
     for k in A.files:
-        if A[k].shape != B[k].shape or not np.array_equal(A[k], B[k]):
-            print(f"FIRST DIFFERENCE at {k}: shapes {A[k].shape} {B[k].shape}")
+        if A[k].shape != B[k].shape or A[k].dtype != B[k].dtype or A[k].tobytes() != B[k].tobytes():      # bytes: the dense maps hold NaN
+            print(f"FIRST DIFFERENCE at {k}: shapes {A[k].shape} {B[k].shape}, dtypes {A[k].dtype} {B[k].dtype}")
             return 1
     print(f"all equal: {len(A.files)} arrays\n" + "\n".join(sorted(A.files)))
     return 0
@@ -128,12 +129,54 @@ def main(path):
     net = AdaPoseNet(sd, dtype="bf16x3", poison_workspace=True, options={"view2_heads": 0})
     est = AdaPoseEstimator_v5(None, dict(base, hip_feature_cache="content"), None, dtype="bf16x3", net=net)
     put("bf16x3 poison_workspace cache=content", est, est.estimate(K, rgb, mask, E1, rgb2, mask2, E2))
+    del net, est
+    dense(out)
     torch.cuda.synchronize()
     np.savez(path, **out)
     print(f"{len(out)} arrays -> {path}")
 
 
+def dense(out):
+    """Every array of the four dense dicts — estimate_depth, estimate_cloud, estimate_cloud_pose(fit_seed) and estimate_cloud_views(fit=True,
+    V = 3) — on the five poses, max_points 4096, at hip_upload frames / windows x hip_upload_chunk 32 / 2 (the views call: frames only),
+    with hip_feature_cache: "content" set so that the bypass counter moves; the two counters after each call."""
+    from rgbmanip_amd import synth
+    from rgbmanip_amd.adapose import AdaPoseNet
+    from rgbmanip_amd.config import ADAPOSE_CFGS
+    from rgbmanip_amd.estimator import AdaPoseEstimator_v5
+    rgb, mask, K = case()
+    u8 = np.clip(np.rint(rgb * 255.0), 0, 255).astype(np.uint8)
+    views = [(u8, mask), (np.ascontiguousarray(u8[:, :, ::-1]), np.ascontiguousarray(mask[:, :, ::-1])),
+             (np.ascontiguousarray(u8[:, ::-1]), np.ascontiguousarray(mask[:, ::-1]))]
+    i1, i2 = synth.adapose_inputs(len(rgb), seed=2), synth.adapose_inputs(len(rgb), seed=4)
+    E = [i1["E1"].astype(np.float64), i1["E2"].astype(np.float64), i2["E2"].astype(np.float64)]
+    net = AdaPoseNet(synth.adapose_state_dict(seed=0, prefix="module."), dtype="bf16x3", options={"view2_heads": 1})
+    base = dict(ADAPOSE_CFGS["adapose_cabinet"], load=False, hip_prepare="device", hip_prepare_seed=9, hip_view2_heads=True,
+                hip_feature_cache="content")
+    pair = (K, views[0][0], views[0][1], E[0], views[1][0], views[1][1], E[1])
+    for upload in ("frames", "windows"):
+        for chunk in (32, 2):
+            est = AdaPoseEstimator_v5(None, dict(base, hip_upload=upload, hip_upload_chunk=chunk), None, dtype="bf16x3", net=net)
+            calls = [("estimate_depth", lambda: est.estimate_depth(*pair)), ("estimate_cloud", lambda: est.estimate_cloud(*pair, max_points=4096)),
+                     ("estimate_cloud_pose", lambda: est.estimate_cloud_pose(*pair, max_points=4096, fit_seed=5))]
+            if upload == "frames":
+                calls.append(("estimate_cloud_views", lambda: est.estimate_cloud_views(
+                    K, np.stack([v[0] for v in views], axis=1), np.stack([v[1] for v in views], axis=1), np.stack(E, axis=1), max_points=4096,
+                    fit=True, fit_seed=5)))
+            for name, call in calls:
+                tag = f"dense {name} upload={upload} chunk={chunk}"
+                for k, v in call().items():
+                    out[f"{tag} {k}"] = np.asarray(v)
+                out[tag + "|counters"] = np.array([est.feature_views_computed, est.feature_cache_bypassed])
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "--compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
-    main(sys.argv[1])
+    if sys.argv[1] == "--dense":                      # the dense calls alone
+        arrays = {}
+        dense(arrays)
+        np.savez(sys.argv[2], **arrays)
+        print(f"{len(arrays)} arrays -> {sys.argv[2]}")
+    else:
+        main(sys.argv[1])
