@@ -138,6 +138,44 @@ int rgbm_adapose_forward(rgbm_adapose_t* h, int B, const float* img1, const floa
                          const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
                          size_t workspace_bytes, const rgbm_adapose_out* out, void* stream);
 
+/* S Dropout2d samples of each of B poses from one pass over the shared part of the backbone.
+ * rgbm_adapose_forward_samples: the inputs of rgbm_adapose_forward for B poses; the ten outputs in `out` have leading dimension S * B,
+ *   row s * B + b = sample s of pose b.  The result is DEFINED as what rgbm_adapose_forward returns for the batch of S * B poses that is
+ *   the B poses tiled S times, with the masks that forward would draw: pose s * B + b has global pose index counter + s * B + b, the counter
+ *   advances by S * B, rgbm_adapose_dropout_masks(h, S * B, ..) afterwards returns those [2 S B][320] factors in the usual order (the view-1
+ *   rows, then the view-2 rows), and masks loaded with rgbm_adapose_set_dropout_masks for S * B poses are used once, as by a plain forward.
+ *   Both Dropout2d sites lie behind up_1's stacked GEMM, so the stem, ResNet-34, the PSP stage, the concat and that GEMM run once on
+ *   the 2B input views; up_1's tap combination then runs once per (sample, view half) on the same stacked rows with that block's mask
+ *   rows, and up_2, the tail, the homographies, the cost volume and the heads run as they are on 2 S B views (choose, P and depths tiled
+ *   on the device).  Same kernels as the plain forward: where the kernel selection of the shared part does not depend on the number of
+ *   views (small batches choose other GEMM tiles than large ones; tuning key ws_min_rows pins them) the outputs equal the tiled forward's
+ *   bit for bit, elsewhere to the rounding between those tiles.  S = 1 is the plain forward.
+ *   Works with norm_mode 0 and 1, every storage type, option view2_heads 0 / 1 and the cost-volume chunking.  Refused with a message,
+ *   before anything is launched: Dropout2d off with no masks loaded (the samples would be equal), masks loaded for another batch than
+ *   S * B, option upconv without bits 0 and 1, the baseline network, S < 1, a workspace that is too small.  Eager on one stream (the
+ *   one-stream rule of rgbm_adapose_set_dropout applies).  There is no hipGraph form, no feature-cache form and no dense / maps form.
+ * rgbm_adapose_samples_workspace_bytes: the workspace of such a call (256-byte aligned): the plan for S * B poses behind a staging block
+ *   for the tiled inputs. */
+int rgbm_adapose_samples_workspace_bytes(rgbm_adapose_t* h, int B, int S, size_t* bytes);
+int rgbm_adapose_forward_samples(rgbm_adapose_t* h, int B, int S, const float* img1, const float* img2, const int32_t* choose1,
+                                 const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
+                                 size_t workspace_bytes, const rgbm_adapose_out* out, void* stream);
+/* Statistics over S samples per pose (sample_stats.hip; float64 numpy twins in rgbmanip_amd/samples.py).  Device pointers.
+ * rgbm_sample_box_stats: boxes [S][n][8][3] fp64 (world-frame corners in get_3d_bbox's order, lib/utils.py:49-56), ok [S][n] uint8.
+ *   A sample counts if its ok is set and all 24 of its coordinates are finite.  Per pose, over the counted samples in ascending s, in
+ *   fp64 with two passes (mean, then deviations): count [n] int32; bbox_mean / bbox_std [n][8][3] (population std); center_mean [n][3]
+ *   and center_cov [n][3][3] (centre = mean of the 8 corners); extent_mean / extent_std [n][3], the lengths of the three edges that
+ *   leave corner 0, in the order x, y, z of the box frame (to corners 2, 4, 1); axis_spread_deg [n][3], per edge direction the RMS
+ *   angle in degrees between each sample's unit edge vector and the normalised sum of the samples' unit vectors (acos of the dot
+ *   product clamped to [-1, 1]).  count = 0: every statistic is NaN.  count = 1: the spreads are 0.  One workgroup per pose, no atomics.
+ *   1 <= S <= 64 and 1 <= n <= 65535, refused otherwise.
+ * rgbm_sample_point_stats: x [S][n][M] fp32 -> mean / std [n][M] fp32, per element over s ascending: accumulated in fp64, two passes,
+ *   population std, rounded once to fp32; NaN propagates.  S, n, M >= 1. */
+int rgbm_sample_box_stats(const double* boxes, const uint8_t* ok, int n, int S, int32_t* count, double* bbox_mean, double* bbox_std,
+                          double* center_mean, double* center_cov, double* extent_mean, double* extent_std, double* axis_spread_deg,
+                          void* stream);
+int rgbm_sample_point_stats(const float* x, int n, int S, int64_t M, float* mean, float* std, void* stream);
+
 /* Dense depth and confidence maps of the crops (what lib/network_v3.py:406-408 returns as view1_depth: softmax over the D planes of the
  * regularised cost volume, then the expectation with the depth values), beside the ten point outputs.
  * rgbm_adapose_forward_dense: the arguments of rgbm_adapose_forward plus two caller-owned fp32 device buffers [V'][224][224],

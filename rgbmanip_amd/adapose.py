@@ -277,6 +277,38 @@ class AdaPoseNet:
             return {k: out[k] for k in ("view1_nocs", "view2_nocs", "view1_depth", "view2_depth")}
         return out
 
+    def samples_workspace_bytes(self, B: int, samples: int) -> int:
+        n = C.c_size_t()
+        _lib.check(self.lib.rgbm_adapose_samples_workspace_bytes(self._h, int(B), int(samples), C.byref(n)), "rgbm_adapose_samples_workspace_bytes")
+        return n.value
+
+    def forward_samples(self, view1_img, view1_choose, view2_img, view2_choose, view1_proj, view2_proj, depth_values, samples: int,
+                        stream=None):
+        """`samples` Dropout2d draws of every pose from one pass over the backbone in front of the first Dropout2d site
+        (rgbm_adapose_forward_samples): the arguments of `forward` for B poses -> the ten `OUT_KEYS` of `forward`, shaped
+        [samples, B, ...].  Sample s of pose b is pose s * B + b of a plain `forward` of the B poses tiled `samples` times - the masks of
+        global poses counter + s * B + b, the counter advanced by samples * B, `dropout_masks(samples * B)` and `set_dropout_masks` for
+        samples * B poses as there.  Needs Dropout2d on (`set_dropout`) or masks loaded; refused for arch "baseline".  Always eager and
+        on one stream, like every forward with dropout; no graph, split, dense or cached form."""
+        S = int(samples)
+        dts = (torch.float32, torch.float32, torch.int32, torch.int32, torch.float32, torch.float32, torch.float32)
+        args = (view1_img, view2_img, view1_choose, view2_choose, view1_proj, view2_proj, depth_values)
+        img1, img2, ch1, ch2, P1, P2, dep = t = tuple(self._prep(a, d) for a, d in zip(args, dts))
+        B = img1.shape[0]
+        assert img1.shape == (B, 3, 224, 224) and img2.shape == img1.shape, img1.shape
+        assert ch1.shape == (B, 1024) and ch2.shape == ch1.shape
+        assert P1.shape == (B, 4, 4) and P2.shape == (B, 4, 4) and dep.shape == (B, 24)
+        out = self._empty_outputs(max(S, 1) * B)
+        o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
+        ws_ptr, ws_bytes = self._workspace_at_least(self.samples_workspace_bytes(B, S))      # refuses S < 1 and the baseline network
+        self._poison(self._ws, stream)
+        _lib.check(self.lib.rgbm_adapose_forward_samples(self._h, B, S, *[_lib.ptr(x) for x in t], C.c_void_p(ws_ptr), ws_bytes, C.byref(o),
+                                                         _lib.stream_ptr(stream)), "rgbm_adapose_forward_samples")
+        self._drop_explicit = False
+        self._last_split = self._last_graph = False
+        self._last = t                                        # keep inputs alive until the stream has consumed them
+        return {k: v.view(S, B, *v.shape[1:]) for k, v in out.items()}
+
     def view_fusion(self, x1, x2, stream=None):
         """The attention stack alone (rgbm_view_fusion) with this net's weights: rows x1 / x2 [B, P, 32] (point-major; read as float32),
         P a multiple of 32 in [32, 4096] -> (y1, y2) [B, P, 32] float32 CUDA."""

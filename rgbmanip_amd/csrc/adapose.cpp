@@ -6,6 +6,7 @@
 // per-view bias.  Views are ordered v = side*B + b (all view-1 images, then all view-2 images).
 #include "adapose.h"
 #include "cost3d.h"
+#include "sample_stats.h"
 #include "view_fusion.h"
 
 #include <math.h>
@@ -402,8 +403,12 @@ size_t AdaPose::workspace_bytes(int B) const {
   return A.peak + 256;
 }
 
-int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* img2, const Call& call) const {
+// samples > 1 (forward_samples): Vout = samples x 2B views leave the PSPNet, and in front of the first Dropout2d site only the 2B input views
+// differ.  Everything up to up_1's stacked GEMM runs on those 2B views; up_1's tap combination then runs once per sample and view half,
+// writing the B views of that block where the tiled batch has them (view rows half * samples * B + k * B) with that block's mask rows.
+int AdaPose::pspnet(const Buffers& bf, int Vout, const float* img1, const float* img2, const Call& call, int samples) const {
   const int S = img;
+  int V = Vout / samples;            // views of the shared prefix; all Vout behind up_1's tap combination
   hipStream_t s = call.stream;
   const float* drop = call.dropout != Dropout::None ? drop_masks.get<float>() : nullptr;      // factors [V][kDropoutPerView]
   int H = S / 2, W = S / 2;
@@ -478,7 +483,19 @@ int AdaPose::pspnet(const Buffers& bf, int V, const float* img1, const float* im
   // tensor it replaces) + tap combination; or, for A/B, the x2 resize followed by the 3x3 conv on the up-sampled grid
   // Dropout2d is applied in the tap combination's epilogue only: the A/B paths refuse it
   RGBM_REQUIRE(drop == nullptr || (upconv & 3) == 3, "dropout needs option upconv bits 0 and 1 (up_1 / up_2 through the tap combination)");
-  if (upconv & 1) {
+  if (samples > 1) {
+    RGBM_REQUIRE(drop != nullptr && (upconv & 3) == 3 && img2 != nullptr && V % 2 == 0, "pspnet: samples need Dropout2d masks and both views");
+    const int B = V / 2;
+    const size_t zview = up1c.scratch_elems(1, H, W) * dtype_size(dtype), oview = (size_t)4 * H * W * 256 * dtype_size(dtype);
+    if (int rc = up1c.run_gemm(bf.cat, bf.ups, V, H, W, s)) return rc;
+    for (int half = 0; half < 2; ++half)
+      for (int k = 0; k < samples; ++k) {
+        const size_t row = (size_t)half * samples * B + (size_t)k * B;
+        if (int rc = up1c.combine((const char*)bf.ups + (size_t)half * B * zview, (char*)bf.u1 + row * oview, B, H, W, 256, s,
+                                  drop + row * kDropoutPerView)) return rc;
+      }
+    V = Vout;
+  } else if (upconv & 1) {
     if (int rc = up1c.run(bf.cat, bf.ups, bf.u1, V, H, W, 256, s, drop)) return rc;
   } else {
     if (int rc = launch_resize_bilinear_ac(dtype, bf.cat, bf.ups, V, H, W, 1024, 2 * H, 2 * W, 1024, 0, s)) return rc;
@@ -670,6 +687,56 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   if (call.stop_after == 1) return 0;
   if (arch == ARCH_BASELINE) return heads_baseline(bf, B, out, call);
   return heads(bf, B, depths, out, call);
+}
+
+// S Dropout2d samples of B poses: forward() of the S x B poses that are the B poses tiled S times (pose k * B + b = sample k of pose b),
+// with the part of the PSPNet in front of the first Dropout2d site run once (pspnet(): samples).  The per-pose inputs are tiled into a
+// staging block at the head of the workspace; the plan for S x B poses follows it.
+static size_t samples_staging_bytes(const AdaPose& n, int SB) {
+  return align_up((size_t)SB * (2 * 16 * sizeof(float) + 2 * n.n_pts * sizeof(int) + n.n_depth * sizeof(float)), 256);
+}
+
+size_t AdaPose::samples_workspace_bytes(int B, int S) const { return samples_staging_bytes(*this, S * B) + workspace_bytes(S * B); }
+
+int AdaPose::forward_samples(int B, int S, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
+                             const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
+                             const Call& call) const {
+  RGBM_REQUIRE(B > 0 && S >= 1 && (long long)S * B <= (1 << 20), "forward_samples: B >= 1 poses and S >= 1 samples");
+  RGBM_REQUIRE(arch != ARCH_BASELINE, "forward_samples: not implemented for the baseline network (it has no Dropout2d)");
+  RGBM_REQUIRE(!(call.dense || call.depth_map || call.conf_map || call.nocs_map) && call.stop_after == 0, "forward_samples: no dense / maps form");
+  RGBM_REQUIRE(call.dropout == Dropout::Draw || call.dropout == Dropout::Loaded,
+               "forward_samples: Dropout2d is off and no masks are loaded (rgbm_adapose_set_dropout / rgbm_adapose_set_dropout_masks): the samples would be equal");
+  RGBM_REQUIRE((upconv & 3) == 3, "forward_samples needs option upconv bits 0 and 1 (the masks are applied in the tap combination of up_1 / up_2)");
+  const int SB = S * B, V = 2 * SB;
+  RGBM_REQUIRE(V <= drop_cap_views && drop_masks && (call.dropout == Dropout::Loaded || drop_state), "forward_samples: mask buffer smaller than S x B poses");
+  RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
+  const size_t need = samples_workspace_bytes(B, S);
+  RGBM_REQUIRE(workspace_size >= need, "forward_samples: workspace too small: need " + std::to_string(need) + " (rgbm_adapose_samples_workspace_bytes)");
+  hipStream_t s = call.stream;
+  // staging block: P1, P2 [SB][16], choose1, choose2 [SB][P], depths [SB][D]
+  const size_t stage = samples_staging_bytes(*this, SB);
+  float* tP1 = (float*)workspace;
+  float* tP2 = tP1 + (size_t)SB * 16;
+  int* tc1 = (int*)(tP2 + (size_t)SB * 16);
+  int* tc2 = tc1 + (size_t)SB * n_pts;
+  float* tdep = (float*)(tc2 + (size_t)SB * n_pts);
+  Arena A((char*)workspace + stage, workspace_size - stage);
+  Buffers bf;
+  plan(SB, A, bf);
+  if (int rc = launch_tile_words(P1, tP1, (long long)B * 16, S, s)) return rc;
+  if (int rc = launch_tile_words(P2, tP2, (long long)B * 16, S, s)) return rc;
+  if (int rc = launch_tile_words(choose1, tc1, (long long)B * n_pts, S, s)) return rc;
+  if (int rc = launch_tile_words(choose2, tc2, (long long)B * n_pts, S, s)) return rc;
+  if (int rc = launch_tile_words(depths, tdep, (long long)B * n_depth, S, s)) return rc;
+  if (int rc = launch_stage_in(tP1, tP2, tc1, tc2, bf.Pviews, bf.choose, SB, n_pts, s)) return rc;
+  if (call.dropout == Dropout::Draw)      // poses counter .. counter + SB - 1, as the plain forward of the tiled batch draws them
+    if (int rc = launch_dropout_masks(drop_masks.get<float>(), drop_state.get<unsigned long long>(), SB, drop_p, drop_seed, 1, s)) return rc;
+  if (int rc = pspnet(bf, V, img1, img2, call, S)) return rc;
+  if (int rc = launch_homography(bf.Pviews, bf.homog, V, SB, s)) return rc;
+  if (dtype == BF16X3 && !feat_f32_only())
+    if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * img * img * 32, s)) return rc;
+  return heads(bf, SB, tdep, out, call);
 }
 
 // Everything behind the PSPNet of the baseline network (network_baseline.py:617-669): the gathered rows feed the NOCS branch as in v5 and,

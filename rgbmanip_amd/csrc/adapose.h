@@ -142,6 +142,13 @@ struct AdaPose {
   // the map rules of a call (depth_map needs dense, conf_map needs depth_map, nocs_map needs the point MLP table) are checked here
   int forward(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
               const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out, const Call& call) const;
+  // S Dropout2d samples of each of B poses from one pass over the part of the PSPNet in front of up_1's tap combination: the ten
+  // outputs [S * B] (row k * B + b) of forward() on the B poses tiled S times, masks and pose counter included.  Refuses, before anything
+  // is launched, a call without Dropout2d masks (call.dropout Draw or Loaded), the upconv A/B paths and the baseline network.  Eager, one
+  // stream; no dense / maps, feature-cache or graph form.
+  size_t samples_workspace_bytes(int B, int S) const;
+  int forward_samples(int B, int S, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
+                      const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out, const Call& call) const;
   // the workspace of a dense call: the plan holds u11 whatever the options and the call say
   size_t dense_workspace_bytes(int B) const { return workspace_bytes(B); }
   int nocs_map_of(const float* feat_f32, long long pixels, float* nocs_map, hipStream_t s) const;      // the kernel alone on an fp32 feature array
@@ -171,7 +178,8 @@ struct AdaPose {
   // exposed for layer-level tests
   int plan(int B, Arena& A, Buffers& bf) const;
   // img2 == nullptr: all V views (any V >= 1) lie in img1
-  int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, const Call& call) const;
+  // samples > 1: V = samples x 2B views, the 2B input views shared up to up_1's stacked GEMM (forward_samples)
+  int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, const Call& call, int samples = 1) const;
   int cost_volume(const Buffers& bf, int V, int B, const float* depths, const Call& call) const;
   int chunk_views(int V) const;
   // bf16x3 on the default path: nothing reads the split-pair feature map (the sweep and the point heads gather from plain fp32), so

@@ -16,6 +16,7 @@
 #include "cost3d.h"
 #include "conv_plan.h"
 #include "prof.h"
+#include "sample_stats.h"
 #include "view_fusion.h"
 
 using namespace rgbm;
@@ -385,6 +386,41 @@ int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int 
   if (int rc = prepare_call(h, "forward_cached", B, {pool, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
   return h->net.forward_cached(B, pool, pool_records, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, workspace_bytes,
                                to_out(out), call);      // refuses a call with Dropout2d
+}
+
+int rgbm_adapose_samples_workspace_bytes(rgbm_adapose_t* h, int B, int S, size_t* bytes) {
+  RGBM_REQUIRE(h && bytes && B > 0, "samples_workspace_bytes arguments");
+  RGBM_REQUIRE(S >= 1 && (long long)S * B <= (1 << 20), "samples_workspace_bytes: S >= 1 samples");
+  RGBM_REQUIRE(!is_baseline(h), "samples_workspace_bytes: forward_samples is not implemented for the baseline network");
+  *bytes = h->net.samples_workspace_bytes(B, S);
+  return 0;
+}
+
+int rgbm_adapose_forward_samples(rgbm_adapose_t* h, int B, int S, const float* img1, const float* img2, const int32_t* choose1,
+                                 const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace,
+                                 size_t workspace_bytes, const rgbm_adapose_out* out, void* stream) {
+  RGBM_REQUIRE(h != nullptr, "forward_samples arguments");
+  RGBM_REQUIRE(!is_baseline(h), "forward_samples: not implemented for the baseline network (it has no Dropout2d)");
+  RGBM_REQUIRE(B > 0 && S >= 1 && (long long)S * B <= (1 << 20), "forward_samples: B >= 1 poses and S >= 1 samples");
+  RGBM_REQUIRE(h->net.drop_p > 0.f || h->drop_explicit, "forward_samples: Dropout2d is off and no masks are loaded (rgbm_adapose_set_dropout / "
+               "rgbm_adapose_set_dropout_masks): the samples would be equal");
+  RGBM_REQUIRE(h->drop_explicit == 0 || h->drop_explicit == S * B, "forward_samples: the masks set for the next forward are for batch " +
+               std::to_string(h->drop_explicit) + ", not S x B = " + std::to_string(S * B));
+  AdaPose::Call call;      // the net refuses the upconv A/B paths and a short workspace, also before anything is launched
+  if (int rc = prepare_call(h, "forward_samples", S * B, {img1, img2, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
+  return finish_call(h, S * B, call, h->net.forward_samples(B, S, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes,
+                                                            to_out(out), call));
+}
+
+int rgbm_sample_box_stats(const double* boxes, const uint8_t* ok, int n, int S, int32_t* count, double* bbox_mean, double* bbox_std,
+                          double* center_mean, double* center_cov, double* extent_mean, double* extent_std, double* axis_spread_deg,
+                          void* stream) {
+  return rgbm::launch_sample_box_stats(boxes, ok, n, S, count, bbox_mean, bbox_std, center_mean, center_cov, extent_mean, extent_std,
+                                       axis_spread_deg, (hipStream_t)stream);
+}
+
+int rgbm_sample_point_stats(const float* x, int n, int S, int64_t M, float* mean, float* std, void* stream) {
+  return rgbm::launch_sample_point_stats(x, n, S, (long long)M, mean, std, (hipStream_t)stream);
 }
 
 int rgbm_adapose_graph_clear(rgbm_adapose_t* h) {

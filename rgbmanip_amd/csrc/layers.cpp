@@ -316,11 +316,20 @@ int UpConvLayer::init(int dtype, int Cin, int Cout_, const float* w, const float
   return 0;
 }
 
-int UpConvLayer::run(const void* in, void* z, void* out, int V, int h, int w, int ldo, hipStream_t s, const float* drop) const {
+int UpConvLayer::run_gemm(const void* in, void* z, int V, int h, int w, hipStream_t s) const {
   if (int rc = gemm.run(in, z, V, 1, h, w, 9 * Cout, nullptr, RES_NONE, nullptr, 0, s)) return rc;
   if (split)
     if (int rc = gemm2.run(in, reinterpret_cast<char*>(z) + (size_t)split * dtype_size(gemm.dtype), V, 1, h, w, 9 * Cout, nullptr, RES_NONE, nullptr, 0, s)) return rc;
+  return 0;
+}
+
+int UpConvLayer::combine(const void* z, void* out, int V, int h, int w, int ldo, hipStream_t s, const float* drop) const {
   return launch_upconv_combine(gemm.dtype, z, bias.get<float>(), out, V, h, w, Cout, ldo, act, slope, s, drop);
+}
+
+int UpConvLayer::run(const void* in, void* z, void* out, int V, int h, int w, int ldo, hipStream_t s, const float* drop) const {
+  if (int rc = run_gemm(in, z, V, h, w, s)) return rc;
+  return combine(z, out, V, h, w, ldo, s, drop);
 }
 
 int UpConvFinal::init(int dtype_, const float* w3, const float* b3, float slope_, const float* wfin, const float* bfin) {

@@ -108,6 +108,10 @@ struct UpConvLayer {
   // in [V][h][w][Cin] -> z scratch [V][h][w][9*Cout] -> out [V][2h][2w][ldo]
   // drop (optional): Dropout2d factors, drop[v * kDropoutPerView + channel] (kernels.h)
   int run(const void* in, void* z, void* out, int V, int h, int w, int ldo, hipStream_t s, const float* drop = nullptr) const;
+  // run()'s two halves: the stacked GEMM in -> z, and the tap combination z -> out.  AdaPose::forward_samples runs the first once and
+  // the second once per Dropout2d sample, on the same z with that sample's rows of `drop`.
+  int run_gemm(const void* in, void* z, int V, int h, int w, hipStream_t s) const;
+  int combine(const void* z, void* out, int V, int h, int w, int ldo, hipStream_t s, const float* drop = nullptr) const;
 };
 
 // PSPNet tail: up_3 (x2 bilinear -> conv3x3 64 -> 64 + bias -> PReLU) and `final` (conv1x1 64 -> 32 + bias) in ONE kernel

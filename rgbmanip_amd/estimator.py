@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, host_prepare
+from . import samples as samples_mod
 from .adapose import AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs, prepare_inputs_windows
 from .cloud import (DEFAULT_BBOX, cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity, depth_consistency, depth_fusion,
                     depth_to_points)
@@ -749,6 +750,113 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         return self.estimate([camera_intrinsic], [rgb1], [view1_mask], [view1_extrinsic], [rgb2], [view2_mask],
                              [view2_extrinsic])[0]
 
+    # ------------------------------------------------------------------ S Dropout2d samples per pose
+    _SAMPLE_ROWS = 256                # network poses (samples x poses) per forward_samples call
+
+    def _samples_check(self, samples) -> int:
+        if self.feature_cache:
+            raise ValueError("estimate_samples: cfg hip_feature_cache keeps feature maps across forwards; there is no cached form of the "
+                             "sampled forward")
+        if self.estimator.dropout <= 0:
+            raise ValueError("estimate_samples samples PSPNet's Dropout2d, which this estimator runs without: it needs cfg hip_dropout > 0 "
+                             "or hip_as_shipped: true (every sample would be the same box otherwise)")
+        if self.prepare_mode != "device":
+            raise ValueError(f'estimate_samples crops on the device: it needs hip_prepare: "device", got {self.prepare_mode!r}')
+        S = int(samples)
+        if not 1 <= S <= samples_mod.MAX_SAMPLES or S != samples:
+            raise ValueError(f"estimate_samples: samples must be an integer in 1 .. {samples_mod.MAX_SAMPLES}, got {samples!r}")
+        return S
+
+    def estimate_samples(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
+                         view2_extrinsic_batch, samples: int = 8):
+        """`estimate` (same arguments, frame types and hip_upload modes) drawing `samples` = S Dropout2d samples of every pose instead of
+        one, and what they say about the box, as a dict of numpy arrays.  The frames are uploaded and cropped once and the `choose`
+        subsets drawn once; `AdaPoseNet.forward_samples` runs the backbone in front of the first Dropout2d site once per pose and the
+        rest once per sample; the configured box tail (median, v4's regressed, RANSAC or PnP) runs on the S n rows as one batch of S n
+        poses (a seeded tail sees pose index s n + i).  Returns `bbox` [n,8,3] f64 (the mean box over the counted samples, the +10 cube
+        where none counts), `bbox_samples` [n,S,8,3] f64, `count` [n] i32, `bbox_std` [n,8,3], `center_cov` [n,3,3], `extent_mean` /
+        `extent_std` [n,3] (edges x, y, z of the box frame), `axis_spread_deg` [n,3] (all f64, `samples.box_stats`), `nocs_mean` /
+        `nocs_std` [n,1024,3] and `depth_mean` / `depth_std` [n,1024] f32 of the view-1 point outputs (`samples.point_stats`; NaN for a
+        pose with an empty mask) and `valid` [n] i32 (count > 0).  A sample counts if its pose was valid at prepare, its tail did not
+        return the +10 cube and its box is finite.  Poses are processed in chunks of at most 256 // S, each chunk one `forward_samples`:
+        the mask sequence is therefore per chunk (pose i of a chunk starting at pose c, sample s, draws global pose index
+        counter + s m + (i - c), m the poses of the chunk; the counter advances by S m per chunk).  Needs cfg hip_dropout > 0 or
+        hip_as_shipped, no hip_feature_cache, hip_prepare: "device" and 1 <= samples <= 64."""
+        S = self._samples_check(samples)
+        n = len(rgb1_batch)
+        dev = self.estimator.device
+        Kd = torch.as_tensor(np.asarray(camera_intrinsic_batch)).to(dev)
+        args = (rgb1_batch, rgb2_batch, view1_mask_batch, view2_mask_batch)
+        cuda = [isinstance(x, torch.Tensor) and x.is_cuda for x in args]
+        wp = self._pnp_branch()
+        size = self.cfg["img_size"]
+        if self.upload_mode == "windows" and not any(cuda):
+            srcs = [host_array(x) for x in args]
+            ring = self._wring = WindowRing.matching(self._wring, n, srcs, dev, slots=1, grow=True)
+            ring.payload_bytes = ring.table_bytes = 0
+            ring.wait(0)
+            ring.stage(0, srcs, 0, n)
+            d = ring.copy(0, n)
+            a, b = (self._prepare_windows(d, v, Kd, size, 1024, self.prepare_seed + v, want_pts2d=wp) for v in (0, 1))
+            self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
+        else:
+            self.upload_bytes_last_call, self.upload_table_bytes_last_call = frames_payload_bytes(*args), 0
+            a = self._prepare(self._upload_frames(rgb1_batch), self._upload_masks(view1_mask_batch), Kd, size, 1024, self.prepare_seed, want_pts2d=wp)
+            b = self._prepare(self._upload_frames(rgb2_batch), self._upload_masks(view2_mask_batch), Kd, size, 1024, self.prepare_seed + 1, want_pts2d=wp)
+        return _to_host(self._samples_prepared(a, b, np.asarray(view1_extrinsic_batch), np.asarray(view2_extrinsic_batch), Kd, S))
+
+    def estimate_samples_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, samples: int = 8, frame0: int = 0):
+        """`estimate_samples` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
+        S = self._samples_check(samples)
+        size, dev = self.cfg["img_size"], self.estimator.device
+        Kd = torch.as_tensor(K).to(dev)
+        kw = dict(want_pts2d=self._pnp_branch(), frame0=frame0)
+        a = self._prepare(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, size, 1024, self.prepare_seed, **kw)
+        b = self._prepare(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, size, 1024, self.prepare_seed + 1, **kw)
+        return self._samples_prepared(a, b, E1, E2, Kd, S)
+
+    def _samples_prepared(self, a, b, E1, E2, K, S: int):
+        """The sampled network, the box tail on the S n rows and the statistics, for the prepared views a / b."""
+        dev = self.estimator.device
+        E1d = torch.as_tensor(E1).to(device=dev, dtype=torch.float64)
+        E2d = torch.as_tensor(E2).to(device=dev, dtype=torch.float64)
+        n = int(E1d.shape[0])
+        depths = self._consts(dev)[1][None].expand(n, 24).contiguous()
+        P1, P2 = self._projection(a["Kcrop"], E1d), self._projection(b["Kcrop"], E2d)
+        chunk = max(self._SAMPLE_ROWS // S, 1)
+        pred = None
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            part = self.estimator.forward_samples(a["img"][lo:hi], a["choose"][lo:hi], b["img"][lo:hi], b["choose"][lo:hi], P1[lo:hi], P2[lo:hi],
+                                                  depths[lo:hi], samples=S)
+            self._plain_views += 2 * (hi - lo)
+            if hi - lo == n:
+                pred = part
+                break
+            if pred is None:
+                pred = {k: torch.empty(S, n, *v.shape[2:], dtype=v.dtype, device=dev) for k, v in part.items()}
+            for k, v in part.items():
+                pred[k][:, lo:hi] = v
+        rows = {k: v.reshape(S * n, *v.shape[2:]) for k, v in pred.items()}                # row s n + i
+        tile = lambda t: None if t is None else torch.as_tensor(t).to(dev).repeat(S, *([1] * (t.dim() - 1)))      # noqa: E731
+        bbox = self._bbox_tail(rows, tile(a["choose"]), tile(a["Kcrop"]), tile(E1d), pts2d=(tile(a.get("pts2d")), tile(b.get("pts2d"))),
+                               E2=tile(E2d), K=tile(torch.as_tensor(K)))
+        dflt = self._consts(dev)[0]
+        prepared = (a["valid"] != 0) & (b["valid"] != 0)
+        ok = prepared.repeat(S) & ~(bbox == dflt).all(dim=2).all(dim=1)
+        box = torch.where(prepared.repeat(S).view(S * n, 1, 1), bbox, dflt.expand(S * n, 8, 3)).view(S, n, 8, 3)
+        st = samples_mod.box_stats(box, ok.view(S, n))
+        counted = st["count"] > 0
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+        res = {"bbox": torch.where(counted.view(n, 1, 1), st["bbox_mean"], dflt.expand(n, 8, 3)), "bbox_samples": box.transpose(0, 1).contiguous(),
+               "count": st["count"], "valid": counted.to(torch.int32)}
+        res.update({k: st[k] for k in ("bbox_std", "center_cov", "extent_mean", "extent_std", "axis_spread_deg")})
+        for key, src in (("nocs", "view1_nocs"), ("depth", "view1_depth")):
+            mean, std = samples_mod.point_stats(pred[src])
+            keep = prepared.view(n, *([1] * (mean.dim() - 1)))
+            res[f"{key}_mean"], res[f"{key}_std"] = torch.where(keep, mean, nan), torch.where(keep, std, nan)
+        return res
+
 
 class AdaPoseEstimator_v4(AdaPoseEstimator_v5):
     """`pose_estimator.name: adapose_v4` (`interface_v4.py:37-378`): the constructor, call surface and `hip_*` keys of
@@ -795,6 +903,14 @@ class AdaPoseEstimator_baseline(AdaPoseEstimator_v5):
     def _no_cost_volume(self, name):
         raise NotImplementedError(f"AdaPoseEstimator_baseline.{name}: the dense maps come from the cost volume, which the baseline network "
                                   "does not have")
+
+    def estimate_samples(self, *a, **k):
+        raise NotImplementedError("AdaPoseEstimator_baseline.estimate_samples: Dropout2d (cfg hip_dropout / hip_as_shipped) is not implemented "
+                                  "for the baseline network, so there is nothing to sample")
+
+    def estimate_samples_device(self, *a, **k):
+        raise NotImplementedError("AdaPoseEstimator_baseline.estimate_samples_device: Dropout2d (cfg hip_dropout / hip_as_shipped) is not "
+                                  "implemented for the baseline network, so there is nothing to sample")
 
     def estimate_depth(self, *a, **k):
         self._no_cost_volume("estimate_depth")
