@@ -11,6 +11,8 @@
 // The 5-point samples come from a seeded hash (sample k of iteration i of pose b = mix32(seed, 128 b + i, k) mod P) where
 // the reference uses the global np.random.randint — the same distribution, reproducible, restated in oracle/align_ref.py.
 // A NaN covariance makes the reference raise; here the pose is marked invalid (default bbox).
+// The hypothesis, the inlier test and the scan are align_math.h's (ransac_hypothesis / ransac_inlier / ransac_scan), which cloud_fit.hip
+// calls on streamed rows; the hash and the block sums are common.h's, the box is bbox_emit.h's.
 #include "common.h"
 #include "kernels.h"
 #include "bbox_emit.h"
@@ -25,19 +27,6 @@ namespace {
 constexpr int AL_THREADS = 256;
 constexpr int AL_MAXP = 1024;
 constexpr int AL_ITERS = 128;
-
-__device__ double al_block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = AL_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 
 }  // namespace
 
@@ -72,70 +61,42 @@ __global__ __launch_bounds__(AL_THREADS) void umeyama_ransac_kernel(
     atomicMax((int*)&hmax[2], __float_as_int(fabsf(n[2])));
   }
   // inlier threshold: a tenth of the source diameter (align.py:52-57)
-  const double mx = al_block_sum(ax, red) / P, my = al_block_sum(ay, red) / P, mz = al_block_sum(az, red) / P;
+  const double mx = block_sum<AL_THREADS>(ax, red) / P, my = block_sum<AL_THREADS>(ay, red) / P, mz = block_sum<AL_THREADS>(az, red) / P;
   double far = 0.0;
   for (int p = t; p < P; p += AL_THREADS) {
     const double dx = sx[p] - mx, dy = sy[p] - my, dz = sz[p] - mz;
     far = fmax(far, sqrt((dx * dx + dy * dy) + dz * dz));
   }
-  red[t] = far;
-  __syncthreads();
-  for (int s = AL_THREADS / 2; s > 0; s >>= 1) { if (t < s) red[t] = fmax(red[t], red[t + s]); __syncthreads(); }
-  const double inlier_t = 2 * red[0] / 10.0;
-  __syncthreads();
+  const double inlier_t = 2 * block_max<AL_THREADS>(far, red) / 10.0;
+  const auto inlier = [&](const double* m, int p) -> bool {
+    const double s[3] = {sx[p], sy[p], sz[p]}, w[3] = {tx[p], ty[p], tz[p]};
+    return ransac_inlier(m, s, w);
+  };
 
   // ---- 128 five-point hypotheses, one per thread (align.py:66-70) ----
   if (t < AL_ITERS) {
-    int idx[5];
-    double ms[3] = {0, 0, 0}, mt[3] = {0, 0, 0};
+    double sv[5][3], tv[5][3];
     for (int k = 0; k < 5; ++k) {
-      idx[k] = (int)(al_mix32(seed, (unsigned)b * AL_ITERS + t, k) % (unsigned)P);
-      ms[0] += sx[idx[k]]; ms[1] += sy[idx[k]]; ms[2] += sz[idx[k]];
-      mt[0] += tx[idx[k]]; mt[1] += ty[idx[k]]; mt[2] += tz[idx[k]];
+      const int i = (int)(mix32(seed, (unsigned)b * AL_ITERS + t, k) % (unsigned)P);
+      sv[k][0] = sx[i]; sv[k][1] = sy[i]; sv[k][2] = sz[i];
+      tv[k][0] = tx[i]; tv[k][1] = ty[i]; tv[k][2] = tz[i];
     }
-    for (int j = 0; j < 3; ++j) { ms[j] /= 5; mt[j] /= 5; }
-    double cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, var = 0.0;
-    for (int k = 0; k < 5; ++k) {
-      const double cs[3] = {sx[idx[k]] - ms[0], sy[idx[k]] - ms[1], sz[idx[k]] - ms[2]};
-      const double ct[3] = {tx[idx[k]] - mt[0], ty[idx[k]] - mt[1], tz[idx[k]] - mt[2]};
-      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) cov[i * 3 + j] += ct[i] * cs[j];
-      var += (cs[0] * cs[0] + cs[1] * cs[1]) + cs[2] * cs[2];
-    }
-    for (int i = 0; i < 9; ++i) cov[i] /= 5;
-    var /= 5;
-    double scale, R[9], tr[3];
-    if (!umeyama_from_stats(cov, ms, mt, var, scale, R, tr)) { s_fail = 1; scale = 0; for (int i = 0; i < 9; ++i) R[i] = 0; tr[0] = tr[1] = tr[2] = 0; }
-    for (int i = 0; i < 9; ++i) hyp[t][i] = scale * R[i];
-    hyp[t][9] = tr[0]; hyp[t][10] = tr[1]; hyp[t][11] = tr[2];
-    hyp[t][12] = scale * inlier_t;
+    if (!ransac_hypothesis(sv, tv, inlier_t, hyp[t])) s_fail = 1;
   }
   __syncthreads();
 
   // ---- inlier counts of every hypothesis: wave w takes hypotheses w, w+4, ... (align.py:71-76) ----
   for (int h = wave; h < AL_ITERS; h += AL_THREADS / 64) {
-    const double* m = hyp[h];
     int c = 0;
-    for (int p = lane; p < P; p += 64) {
-      const double rx = tx[p] - (((m[0] * sx[p] + m[1] * sy[p]) + m[2] * sz[p]) + m[9]);
-      const double ry = ty[p] - (((m[3] * sx[p] + m[4] * sy[p]) + m[5] * sz[p]) + m[10]);
-      const double rz = tz[p] - (((m[6] * sx[p] + m[7] * sy[p]) + m[8] * sz[p]) + m[11]);
-      c += __popcll(__ballot(sqrt((rx * rx + ry * ry) + rz * rz) < m[12]));
-    }
+    for (int p = lane; p < P; p += 64) c += __popcll(__ballot(inlier(hyp[h], p)));
     if (lane == 0) cnt[h] = c;
   }
   __syncthreads();
 
-  // ---- the reference's sequential scan: strictly better ratio wins, early break by confidence (align.py:77-87) ----
+  // ---- the reference's sequential scan picks the hypothesis (align.py:77-87) ----
   if (t == 0) {
-    double best = 0.0;
-    int best_h = -1;
-    for (int i = 0; i < AL_ITERS; ++i) {
-      const double ratio = (double)cnt[i] / (double)P;
-      if (ratio > best) { best = ratio; best_h = i; }
-      const double b5 = (best * best) * (best * best) * best;
-      if ((1 - pow(1 - b5, (double)i)) > 0.99) break;
-    }
-    s_best = best < 0.1 ? -1 : best_h;
+    int examined;
+    s_best = ransac_scan(cnt, AL_ITERS, P, examined);
   }
   __syncthreads();
   const int best_h = s_best;
@@ -144,21 +105,17 @@ __global__ __launch_bounds__(AL_THREADS) void umeyama_ransac_kernel(
   // ---- final fit over the inliers of the kept hypothesis (align.py:93-95) ----
   double n_in = 0, a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0;
   if (best_h >= 0) {
-    const double* m = hyp[best_h];
     for (int p = t; p < P; p += AL_THREADS) {
-      const double rx = tx[p] - (((m[0] * sx[p] + m[1] * sy[p]) + m[2] * sz[p]) + m[9]);
-      const double ry = ty[p] - (((m[3] * sx[p] + m[4] * sy[p]) + m[5] * sz[p]) + m[10]);
-      const double rz = tz[p] - (((m[6] * sx[p] + m[7] * sy[p]) + m[8] * sz[p]) + m[11]);
-      if (sqrt((rx * rx + ry * ry) + rz * rz) < m[12]) {
+      if (inlier(hyp[best_h], p)) {
         n_in += 1; a0 += sx[p]; a1 += sy[p]; a2 += sz[p]; b0 += tx[p]; b1 += ty[p]; b2 += tz[p];
       } else {
         sx[p] = __builtin_nan("");              // mark as outlier for the second pass (this thread owns p)
       }
     }
   }
-  const double n = al_block_sum(n_in, red);
-  const double ms[3] = {al_block_sum(a0, red) / n, al_block_sum(a1, red) / n, al_block_sum(a2, red) / n};
-  const double mt[3] = {al_block_sum(b0, red) / n, al_block_sum(b1, red) / n, al_block_sum(b2, red) / n};
+  const double n = block_sum<AL_THREADS>(n_in, red);
+  const double ms[3] = {block_sum<AL_THREADS>(a0, red) / n, block_sum<AL_THREADS>(a1, red) / n, block_sum<AL_THREADS>(a2, red) / n};
+  const double mt[3] = {block_sum<AL_THREADS>(b0, red) / n, block_sum<AL_THREADS>(b1, red) / n, block_sum<AL_THREADS>(b2, red) / n};
   double cv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, var = 0.0;
   if (best_h >= 0) {
     for (int p = t; p < P; p += AL_THREADS) {
@@ -170,9 +127,9 @@ __global__ __launch_bounds__(AL_THREADS) void umeyama_ransac_kernel(
     }
   }
   double cov[9];
-  for (int i = 0; i < 9; ++i) cov[i] = al_block_sum(cv[i], red) / n;
-  var = al_block_sum(var, red) / n;
-  const double any_nan = al_block_sum(nan_in ? 1.0 : 0.0, red);
+  for (int i = 0; i < 9; ++i) cov[i] = block_sum<AL_THREADS>(cv[i], red) / n;
+  var = block_sum<AL_THREADS>(var, red) / n;
+  const double any_nan = block_sum<AL_THREADS>(nan_in ? 1.0 : 0.0, red);
   if (t == 0) {
     double scale = 0, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tr[3] = {0, 0, 0};
     bool ok = best_h >= 0 && !fail && any_nan == 0.0;

@@ -1,5 +1,6 @@
 // The similarity-fit arithmetic shared by align.hip (umeyama_ransac_kernel) and cloud_fit.hip (the fit over the two-view cloud):
-// the sample hash, a 3 x 3 SVD by one-sided Jacobi and Umeyama's closed form from sufficient statistics (lib/align.py:10-41), fp64.
+// a 3 x 3 SVD by one-sided Jacobi, Umeyama's closed form from sufficient statistics (lib/align.py:10-41) and the three steps of the RANSAC
+// around it (five-point hypothesis, inlier test, sequential scan; lib/align.py:44-104), fp64.  The sample hash is common.h's mix32.
 // Both files are built without mul+add contraction; the pragma below keeps that true for this text wherever it is included.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,12 +8,6 @@
 #pragma clang fp contract(off)
 
 namespace rgbm {
-
-__device__ __forceinline__ unsigned al_mix32(unsigned seed, unsigned frame, unsigned idx) {      // = mix32 of prepare.hip
-  unsigned h = seed ^ (frame * 0x9E3779B9u) ^ (idx * 0x85EBCA6Bu);
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return h;
-}
 
 __device__ inline double det3(const double* m) {
   return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
@@ -84,6 +79,61 @@ __device__ inline bool umeyama_from_stats(const double* cov, const double* ms, c
   scale = 1 / varP * ((S[0] + S[1]) + S[2]);
   for (int j = 0; j < 3; ++j) t[j] = mt[j] - ((ms[0] * (scale * R[j * 3]) + ms[1] * (scale * R[j * 3 + 1])) + ms[2] * (scale * R[j * 3 + 2]));
   return true;
+}
+
+// ---- the similarity RANSAC of lib/align.py:44-104, one piece per step --------------------------------------------------------------
+// A hypothesis is 13 doubles: s R (row-major), t, and the inlier threshold s * inlier_t.
+
+// Five-point hypothesis (align.py:66-70) from the sampled source rows s and target rows t.  false: NaN covariance (the reference
+// raises), hyp is all zero then, so that no row is its inlier.
+__device__ inline bool ransac_hypothesis(const double s[5][3], const double t[5][3], double inlier_t, double* hyp /*[13]*/) {
+  double ms[3] = {0, 0, 0}, mt[3] = {0, 0, 0};
+  for (int k = 0; k < 5; ++k)
+    for (int j = 0; j < 3; ++j) { ms[j] += s[k][j]; mt[j] += t[k][j]; }
+  for (int j = 0; j < 3; ++j) { ms[j] /= 5; mt[j] /= 5; }
+  double cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, var = 0.0;
+  for (int k = 0; k < 5; ++k) {
+    const double cs[3] = {s[k][0] - ms[0], s[k][1] - ms[1], s[k][2] - ms[2]};
+    const double ct[3] = {t[k][0] - mt[0], t[k][1] - mt[1], t[k][2] - mt[2]};
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) cov[i * 3 + j] += ct[i] * cs[j];
+    var += (cs[0] * cs[0] + cs[1] * cs[1]) + cs[2] * cs[2];
+  }
+  for (int i = 0; i < 9; ++i) cov[i] /= 5;
+  var /= 5;
+  double scale, R[9], tr[3];
+  const bool ok = umeyama_from_stats(cov, ms, mt, var, scale, R, tr);
+  if (!ok) { scale = 0; for (int i = 0; i < 9; ++i) R[i] = 0; tr[0] = tr[1] = tr[2] = 0; }
+  for (int i = 0; i < 9; ++i) hyp[i] = scale * R[i];
+  hyp[9] = tr[0]; hyp[10] = tr[1]; hyp[11] = tr[2];
+  hyp[12] = scale * inlier_t;
+  return ok;
+}
+
+// Is row (s, t) an inlier of hypothesis m (align.py:71-76): the counting and every inlier pass evaluate this and nothing else
+__device__ inline bool ransac_inlier(const double* m /*[13]*/, const double s[3], const double t[3]) {
+  const double rx = t[0] - (((m[0] * s[0] + m[1] * s[1]) + m[2] * s[2]) + m[9]);
+  const double ry = t[1] - (((m[3] * s[0] + m[4] * s[1]) + m[5] * s[2]) + m[10]);
+  const double rz = t[2] - (((m[6] * s[0] + m[7] * s[1]) + m[8] * s[2]) + m[11]);
+  return sqrt((rx * rx + ry * ry) + rz * rz) < m[12];
+}
+
+// The reference's sequential scan over the inlier counts of `iters` hypotheses among m rows (align.py:77-91): a strictly better ratio
+// wins, the confidence rule breaks early, a best ratio < 0.1 keeps none.  Returns the kept hypothesis or -1; examined = the hypotheses
+// the sequential loop would have run (0 when m < 5: the reference does not fit fewer than five rows).
+__device__ inline int ransac_scan(const int* cnt, int iters, int m, int& examined) {
+  double best = 0.0;
+  int best_h = -1;
+  examined = 0;
+  if (m >= 5) {
+    for (int i = 0; i < iters; ++i) {
+      examined = i + 1;
+      const double ratio = (double)cnt[i] / (double)m;
+      if (ratio > best) { best = ratio; best_h = i; }
+      const double b5 = (best * best) * (best * best) * best;
+      if ((1 - pow(1 - b5, (double)i)) > 0.99) break;
+    }
+  }
+  return best < 0.1 ? -1 : best_h;
 }
 
 }  // namespace rgbm

@@ -50,8 +50,8 @@ __device__ inline void backproject_world(const double* inv /*[12]*/, double x, d
   for (int r = 0; r < 3; ++r) out[r] = inv[r * 4 + 0] * c0 + inv[r * 4 + 1] * c1 + inv[r * 4 + 2] * z + inv[r * 4 + 3];
 }
 
-// world X -> (u, v, z) of a view with rows E[0..11] of its extrinsic and fx, fy, cx, cy of its cropped intrinsics: the ONE projection of
-// depth_consistency.hip and depth_fusion.hip (both built without contraction), whose V = 2 results are the same bits
+// world X -> (u, v, z) of a view with rows E[0..11] of its extrinsic and fx, fy, cx, cy of its cropped intrinsics (cloud_geom.h:
+// reproject_round_trip)
 __device__ inline void project_view(const double* E /*[12]*/, const double X[3], double fx, double fy, double cx, double cy, double& u,
                                     double& v, double& z) {
   const double c0 = E[0] * X[0] + E[1] * X[1] + E[2] * X[2] + E[3];
@@ -61,8 +61,15 @@ __device__ inline void project_view(const double* E /*[12]*/, const double X[3],
   v = fy * c1 / z + cy;
 }
 
-// camera-frame corners -> world frame through `a` (invert_extrinsic), or default_bbox (+10 cube) and valid = 0 when !ok or a corner is
-// non-finite
+// the corners of pose b as they are, or default_bbox (+10 cube) when !ok; valid = ok
+__device__ inline void emit_corners(long long b, const double c[8][3], bool ok, double* __restrict__ bbox, int* __restrict__ valid) {
+  const double dflt[8][3] = {{0, 0, 0}, {0, 0, 1}, {0, 1, 0}, {0, 1, 1}, {1, 0, 0}, {1, 0, 1}, {1, 1, 0}, {1, 1, 1}};
+  for (int k = 0; k < 8; ++k)
+    for (int i = 0; i < 3; ++i) bbox[(b * 8 + k) * 3 + i] = ok ? c[k][i] : dflt[k][i] + 10.0;
+  valid[b] = ok ? 1 : 0;
+}
+
+// camera-frame corners -> world frame through `a` (invert_extrinsic), or default_bbox and valid = 0 when !ok or a corner is non-finite
 __device__ inline void emit_corners_world(long long b, const double cam[8][3], bool ok, const double a[4][8], double* __restrict__ bbox,
                                           int* __restrict__ valid) {
   double out[8][3];
@@ -71,10 +78,15 @@ __device__ inline void emit_corners_world(long long b, const double cam[8][3], b
       if (!isfinite(cam[k][i])) ok = false;
       out[k][i] = a[i][4] * cam[k][0] + a[i][5] * cam[k][1] + a[i][6] * cam[k][2] + a[i][7];
     }
-  const double dflt[8][3] = {{0, 0, 0}, {0, 0, 1}, {0, 1, 0}, {0, 1, 1}, {1, 0, 0}, {1, 0, 1}, {1, 1, 0}, {1, 1, 1}};
-  for (int k = 0; k < 8; ++k)
-    for (int i = 0; i < 3; ++i) bbox[(b * 8 + k) * 3 + i] = ok ? out[k][i] : dflt[k][i] + 10.0;
-  valid[b] = ok ? 1 : 0;
+  emit_corners(b, out, ok, bbox, valid);
+}
+
+// the corners of a box of `size` in the frame sRT = [R | t] maps to; R and t are the float32 values the reference's sRT holds
+__device__ inline void bbox_corners_srt(const double R[9] /* float32 values */, const float tf[3], const double size[3], double c[8][3]) {
+  for (int k = 0; k < 8; ++k) {
+    const double p[3] = {bbox_sign(k, 0) * size[0] / 2, bbox_sign(k, 1) * size[1] / 2, bbox_sign(k, 2) * size[2] / 2};
+    for (int i = 0; i < 3; ++i) c[k][i] = R[i * 3 + 0] * p[0] + R[i * 3 + 1] * p[1] + R[i * 3 + 2] * p[2] + (double)tf[i];
+  }
 }
 
 __device__ inline void emit_bbox_world(long long b, const double R[9] /* float32 values */, const float tf[3], const double size[3],
@@ -82,10 +94,7 @@ __device__ inline void emit_bbox_world(long long b, const double R[9] /* float32
   double a[4][8];
   if (!invert_extrinsic(b, E1, a)) ok = false;
   double cam[8][3];
-  for (int k = 0; k < 8 && ok; ++k) {
-    const double p[3] = {bbox_sign(k, 0) * size[0] / 2, bbox_sign(k, 1) * size[1] / 2, bbox_sign(k, 2) * size[2] / 2};
-    for (int i = 0; i < 3; ++i) cam[k][i] = R[i * 3 + 0] * p[0] + R[i * 3 + 1] * p[1] + R[i * 3 + 2] * p[2] + (double)tf[i];
-  }
+  if (ok) bbox_corners_srt(R, tf, size, cam);
   emit_corners_world(b, cam, ok, a, bbox, valid);
 }
 

@@ -22,8 +22,12 @@ for f in conv_igemm.hip conv_igemm_glds.hip conv3d_tile.hip conv0_sweep.hip conv
   EXTRA=""
   # files that must round like numpy / torch elementwise ops: no mul+add -> fma contraction
   case "$f" in postproc.hip|postproc_regressed.hip|depth_points.hip|depth_consistency.hip|depth_fusion.hip|ppo_kernels.hip|prepare.hip|control.hip|synth_env.hip|align.hip|cloud_fit.hip|pnp.hip|sample_stats.hip|misc_kernels.hip|bn_kernels.hip) EXTRA="-ffp-contract=off";; esac
-  if [ ! -f build/${f%.hip}.o ] || [ "$f" -nt build/${f%.hip}.o ] || [ common.h -nt build/${f%.hip}.o ] || [ kernels.h -nt build/${f%.hip}.o ] || [ conv_plan.h -nt build/${f%.hip}.o ] || [ conv_igemm_m32.inc -nt build/${f%.hip}.o ] || [ conv3d_tile_table.h -nt build/${f%.hip}.o ] || [ control.h -nt build/${f%.hip}.o ] || [ quantize.h -nt build/${f%.hip}.o ] || [ bbox_emit.h -nt build/${f%.hip}.o ] || [ align_math.h -nt build/${f%.hip}.o ] || { [ "$f" = view_fusion.hip ] && [ view_fusion.h -nt build/view_fusion.o ]; } || { [ "$f" = sample_stats.hip ] && [ sample_stats.h -nt build/sample_stats.o ]; } || [ build.sh -nt build/${f%.hip}.o ]; then
-    hipcc $FLAGS $EXTRA -c "$f" -o build/${f%.hip}.o &
+  # an object is stale when its source, this script or ANY header of this directory is newer: no per-header list to forget a header in
+  o=build/${f%.hip}.o
+  stale=0
+  for d in "$f" build.sh *.h *.inc; do if [ ! -f $o ] || [ "$d" -nt $o ]; then stale=1; break; fi; done
+  if [ $stale = 1 ]; then
+    hipcc $FLAGS $EXTRA -c "$f" -o $o &
     pids+=($!)
   fi
 done

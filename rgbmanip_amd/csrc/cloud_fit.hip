@@ -16,6 +16,8 @@
 //   6 cf_inlier_sum  per slice: count and coordinate sums of the kept hypothesis's inliers
 //   7 cf_inlier_cov  per slice: their covariance and source variance about the centroids
 //   8 cf_finish      per pose: Umeyama over the inliers, the box (no world transform: the cloud is in the world frame), srt, info, valid
+// Steps 3, 4 / 6 / 7 and 5 call align_math.h's ransac_hypothesis, ransac_inlier and ransac_scan, the ones umeyama_ransac_kernel (align.hip)
+// runs on its 1024 rows in LDS; the box corners and the default box are bbox_emit.h's, the hash and the block reductions common.h's.
 #include "common.h"
 #include "kernels.h"
 #include "bbox_emit.h"
@@ -66,40 +68,6 @@ __device__ inline void cf_range(int cap, int ns, int sl, int m, int& r0, int& r1
   r0 = sl * len; r1 = r0 + len;
   if (r0 > m) r0 = m;
   if (r1 > m) r1 = m;
-}
-
-// sum over the workgroup in a fixed tree order; every thread gets the result
-__device__ inline double cf_block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = CF_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-__device__ inline double cf_block_max(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = CF_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = fmax(red[t], red[t + s]);
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-// residual of row (s, t) against hypothesis m (s R row-major, t, threshold): the ONE expression the counting and both inlier passes evaluate
-__device__ inline bool cf_inlier(const double* m, const double s[3], const double t[3]) {
-  const double rx = t[0] - (((m[0] * s[0] + m[1] * s[1]) + m[2] * s[2]) + m[9]);
-  const double ry = t[1] - (((m[3] * s[0] + m[4] * s[1]) + m[5] * s[2]) + m[10]);
-  const double rz = t[2] - (((m[6] * s[0] + m[7] * s[1]) + m[8] * s[2]) + m[11]);
-  return sqrt((rx * rx + ry * ry) + rz * rz) < m[12];
 }
 
 __device__ inline void cf_row(const float* __restrict__ a, long long row, double v[3]) {
@@ -157,10 +125,10 @@ __global__ __launch_bounds__(CF_THREADS) void cf_sum_kernel(const float* __restr
   }
   double* o = scratch + (size_t)b * L.per_pose + L.o_sum + (size_t)sl * 8;
   for (int j = 0; j < 3; ++j) {
-    const double sj = cf_block_sum(a[j], red), hj = cf_block_max(h[j], red);
+    const double sj = block_sum<CF_THREADS>(a[j], red), hj = block_max<CF_THREADS>(h[j], red);
     if (t == 0) { o[j] = sj; o[3 + j] = hj; }
   }
-  const double bd = cf_block_max(bad, red);
+  const double bd = block_max<CF_THREADS>(bad, red);
   if (t == 0) { o[6] = bd; o[7] = 0; }
 }
 
@@ -191,7 +159,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_far_kernel(const float* __restr
     const double dx = s[0] - c[0], dy = s[1] - c[1], dz = s[2] - c[2];
     far = fmax(far, sqrt((dx * dx + dy * dy) + dz * dz));
   }
-  far = cf_block_max(far, red);
+  far = block_max<CF_THREADS>(far, red);
   if (t == 0) pose[L.o_far + sl] = far;
 }
 
@@ -211,28 +179,13 @@ __global__ __launch_bounds__(CF_ITERS) void cf_hypotheses_kernel(const float* __
     double far = 0.0;
     for (int sl = 0; sl < L.ns; ++sl) far = fmax(far, pose[L.o_far + sl]);
     const double inlier_t = 2 * far / 10.0;
-    double sv[5][3], tv[5][3], ms[3] = {0, 0, 0}, mt[3] = {0, 0, 0};
+    double sv[5][3], tv[5][3];
     for (int k = 0; k < 5; ++k) {
-      const int idx = (int)(al_mix32(seed, (unsigned)b * CF_ITERS + t, k) % (unsigned)m);
+      const int idx = (int)(mix32(seed, (unsigned)b * CF_ITERS + t, k) % (unsigned)m);
       cf_row(nocs, (long long)b * cap + idx, sv[k]);
       cf_row(cloud, (long long)b * cap + idx, tv[k]);
-      for (int j = 0; j < 3; ++j) { ms[j] += sv[k][j]; mt[j] += tv[k][j]; }
     }
-    for (int j = 0; j < 3; ++j) { ms[j] /= 5; mt[j] /= 5; }
-    double cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, var = 0.0;
-    for (int k = 0; k < 5; ++k) {
-      const double cs[3] = {sv[k][0] - ms[0], sv[k][1] - ms[1], sv[k][2] - ms[2]};
-      const double ct[3] = {tv[k][0] - mt[0], tv[k][1] - mt[1], tv[k][2] - mt[2]};
-      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) cov[i * 3 + j] += ct[i] * cs[j];
-      var += (cs[0] * cs[0] + cs[1] * cs[1]) + cs[2] * cs[2];
-    }
-    for (int i = 0; i < 9; ++i) cov[i] /= 5;
-    var /= 5;
-    double scale, R[9], tr[3];
-    if (!umeyama_from_stats(cov, ms, mt, var, scale, R, tr)) { atomicOr(&s_fail, 1); scale = 0; for (int i = 0; i < 9; ++i) R[i] = 0; tr[0] = tr[1] = tr[2] = 0; }
-    for (int i = 0; i < 9; ++i) hy[i] = scale * R[i];
-    hy[9] = tr[0]; hy[10] = tr[1]; hy[11] = tr[2];
-    hy[12] = scale * inlier_t;
+    if (!ransac_hypothesis(sv, tv, inlier_t, hy)) atomicOr(&s_fail, 1);
   } else {
     for (int i = 0; i < 13; ++i) hy[i] = 0.0;
   }
@@ -269,7 +222,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_count_kernel(const float* __res
       const double* mh = hyp + h * 13;
       int c = 0;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) c += __popcll(__ballot(in[q] && cf_inlier(mh, s[q], w[q])));
+      for (int q = 0; q < 4; ++q) c += __popcll(__ballot(in[q] && ransac_inlier(mh, s[q], w[q])));
       if (lane == 0 && c) atomicAdd(&cnt[h], c);      // integer: order-free
     }
   }
@@ -290,19 +243,8 @@ __global__ __launch_bounds__(CF_ITERS) void cf_scan_kernel(int cap, double* __re
   cnt[t] = c;
   __syncthreads();
   if (t == 0) {
-    const int m = sel[0];
-    double best = 0.0;
-    int best_h = -1, examined = 0;
-    if (m >= 5) {
-      for (int i = 0; i < CF_ITERS; ++i) {
-        examined = i + 1;
-        const double ratio = (double)cnt[i] / (double)m;
-        if (ratio > best) { best = ratio; best_h = i; }
-        const double b5 = (best * best) * (best * best) * best;
-        if ((1 - pow(1 - b5, (double)i)) > 0.99) break;
-      }
-    }
-    if (best < 0.1) best_h = -1;
+    int examined;
+    const int best_h = ransac_scan(cnt, CF_ITERS, sel[0], examined);
     sel[1] = best_h;
     sel[2] = best_h >= 0 ? cnt[best_h] : 0;
     sel[3] = examined;
@@ -329,12 +271,12 @@ __global__ __launch_bounds__(CF_THREADS) void cf_inlier_sum_kernel(const float* 
       double s[3], w[3];
       cf_row(nocs, (long long)b * cap + p, s);
       cf_row(cloud, (long long)b * cap + p, w);
-      if (cf_inlier(mh, s, w)) { acc[0] += 1; for (int j = 0; j < 3; ++j) { acc[1 + j] += s[j]; acc[4 + j] += w[j]; } }
+      if (ransac_inlier(mh, s, w)) { acc[0] += 1; for (int j = 0; j < 3; ++j) { acc[1 + j] += s[j]; acc[4 + j] += w[j]; } }
     }
   }
   double* o = pose + L.o_isum + (size_t)sl * 8;
   for (int j = 0; j < 7; ++j) {
-    const double v = cf_block_sum(acc[j], red);
+    const double v = block_sum<CF_THREADS>(acc[j], red);
     if (t == 0) o[j] = v;
   }
   if (t == 0) o[7] = 0;
@@ -371,7 +313,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_inlier_cov_kernel(const float* 
       double s[3], w[3];
       cf_row(nocs, (long long)b * cap + p, s);
       cf_row(cloud, (long long)b * cap + p, w);
-      if (!cf_inlier(mh, s, w)) continue;
+      if (!ransac_inlier(mh, s, w)) continue;
       const double cs[3] = {s[0] - ms[0], s[1] - ms[1], s[2] - ms[2]};
       const double ct[3] = {w[0] - mt[0], w[1] - mt[1], w[2] - mt[2]};
       for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) acc[i * 3 + j] += ct[i] * cs[j];
@@ -380,7 +322,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_inlier_cov_kernel(const float* 
   }
   double* o = pose + L.o_icov + (size_t)sl * 10;
   for (int j = 0; j < 10; ++j) {
-    const double v = cf_block_sum(acc[j], red);
+    const double v = block_sum<CF_THREADS>(acc[j], red);
     if (t == 0) o[j] = v;
   }
 }
@@ -420,20 +362,16 @@ __global__ void cf_finish_kernel(int n, int cap, const double* __restrict__ scra
   info[4 * b + 2] = usable ? sel[2] : 0;
   info[4 * b + 3] = usable ? sel[3] : 0;
   // sRT is a float32 matrix in the reference (interface_v5.py:357-361): R and t are rounded to float32 there
-  double corner[8][3];
-  for (int k = 0; k < 8; ++k) {
-    const double p[3] = {bbox_sign(k, 0) * (2.0 * hmax[0] * scale) / 2, bbox_sign(k, 1) * (2.0 * hmax[1] * scale) / 2,
-                         bbox_sign(k, 2) * (2.0 * hmax[2] * scale) / 2};
-    for (int i = 0; i < 3; ++i) {
-      corner[k][i] = (double)(float)R[i * 3 + 0] * p[0] + (double)(float)R[i * 3 + 1] * p[1] + (double)(float)R[i * 3 + 2] * p[2] + (double)(float)tr[i];
-      if (!isfinite(corner[k][i])) ok = false;
-    }
-  }
-  const double dflt[8][3] = {{0, 0, 0}, {0, 0, 1}, {0, 1, 0}, {0, 1, 1}, {1, 0, 0}, {1, 0, 1}, {1, 1, 0}, {1, 1, 1}};
+  double Rf[9], corner[8][3];
+  for (int i = 0; i < 9; ++i) Rf[i] = (double)(float)R[i];
+  const float tf[3] = {(float)tr[0], (float)tr[1], (float)tr[2]};
+  const double size[3] = {2.0 * hmax[0] * scale, 2.0 * hmax[1] * scale, 2.0 * hmax[2] * scale};
+  bbox_corners_srt(Rf, tf, size, corner);
   for (int k = 0; k < 8; ++k)
-    for (int i = 0; i < 3; ++i) bbox[((long long)b * 8 + k) * 3 + i] = ok ? corner[k][i] : dflt[k][i] + 10.0;
+    for (int i = 0; i < 3; ++i)
+      if (!isfinite(corner[k][i])) ok = false;
   if (!ok) o[0] = __builtin_nan("");
-  valid[b] = ok ? 1 : 0;
+  emit_corners(b, corner, ok, bbox, valid);      // no world transform: the cloud is in the world frame
 }
 
 size_t cloud_similarity_scratch_bytes(int n, int cap) {

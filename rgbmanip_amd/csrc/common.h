@@ -221,6 +221,37 @@ __device__ __forceinline__ void bx3_pair(const uint4& c0, const uint4& c1, uint4
   lo = make_uint4(c0.z, c0.w, c1.z, c1.w);
 }
 
+// ---- small utilities of the pre- and post-processing kernels ----------------------------------------------------------
+// The package's seeded hash (murmur3 finaliser): the 1024-subset keys of prepare.hip and the RANSAC sample streams of align.hip,
+// cloud_fit.hip and pnp.hip; rgbm_prepare_mix32 exports it to the host, oracle/postproc_ref.py restates it.
+__host__ __device__ inline unsigned mix32(unsigned seed, unsigned frame, unsigned idx) {
+  unsigned h = seed ^ (frame * 0x9E3779B9u) ^ (idx * 0x85EBCA6Bu);
+  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+
+// fp64 sum / maximum over a workgroup of THREADS threads (a power of two) in a fixed tree order in LDS, so that the result is the same
+// bits from run to run; red[THREADS] is scratch, every thread calls and every thread gets the result.  Ends with a barrier: red may be
+// reused at once.
+template <int THREADS, class Op> __device__ inline double block_reduce(double v, double* red, Op op) {
+  const int t = threadIdx.x;
+  red[t] = v;
+  __syncthreads();
+  for (int s = THREADS / 2; s > 0; s >>= 1) {
+    if (t < s) red[t] = op(red[t], red[t + s]);
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+template <int THREADS> __device__ inline double block_sum(double v, double* red) {
+  return block_reduce<THREADS>(v, red, [](double a, double b) { return a + b; });
+}
+template <int THREADS> __device__ inline double block_max(double v, double* red) {      // fmax: a NaN operand is dropped
+  return block_reduce<THREADS>(v, red, [](double a, double b) { return fmax(a, b); });
+}
+
 // ---- generic implicit-GEMM convolution descriptor (conv_igemm.hip) -------------------
 struct ConvDesc {
   const void* in; const void* wgt; void* out; const float* bias; const void* res;

@@ -12,17 +12,20 @@
 //   5. keep = reproj < px_max && rel < rel_max && (no conf_a || conf >= conf_min) && (no mask_a || mask != 0);
 //      fused = keep ? (d + d') / 2 : NaN
 // All of it in fp64 on the float32 maps, rounded once into the float32 results; built without mul + add contraction (build.sh) like
-// depth_points.hip, whose back-projection expression it shares (bbox_emit.h: backproject_world).
+// depth_points.hip, whose back-projection expression it shares (bbox_emit.h: backproject_world).  Rules 2-4 are reproject_round_trip
+// of cloud_geom.h, which depth_fusion_kernel calls once per source view; the kernel keeps rule 1, the thresholds and what is written.
 //
 // cloud_pack_kernel: deterministic ordered compaction of the kept pixels into [n][cap][3] world-frame points: for pose i the kept pixels
 // of view 1 in row-major order, then those of view 2.  No atomics: the slot of a pixel is the number of kept pixels before it.  A pose is
 // cut into PACK_BLOCKS contiguous pieces, one workgroup each.  A workgroup first counts the keep bytes of the whole pose (three integer
 // sums: kept before its piece, kept in view 1, kept in view 2 — integer addition, so the order of the reduction does not matter), then
 // walks its piece in chunks of PACK_THREADS pixels with a wave ballot / popcount and a 16-entry LDS table of wave totals.  Rows from
-// min(cap, total) to cap are filled with NaN / -1 by the pose's workgroups together.
+// min(cap, total) to cap are filled with NaN / -1 by the pose's workgroups together.  The walk, the row and the fill are pack_walk /
+// pack_emit_row / pack_fill_unused of cloud_geom.h, which cloud_pack_views_kernel (depth_fusion.hip) calls from its own counting
+// prologue; a view's camera comes into LDS through load_view_pose in all four kernels.
 #include <cmath>
 
-#include "bbox_emit.h"
+#include "cloud_geom.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -32,25 +35,20 @@ namespace {
 constexpr int PACK_THREADS = 1024;      // 16 waves
 constexpr int PACK_BLOCKS = 8;          // workgroups per pose
 constexpr int PACK_WAVES = PACK_THREADS / 64;
-}  // namespace                         // project_view: bbox_emit.h, shared with depth_fusion.hip
+}  // namespace
 
-__global__ __launch_bounds__(256) void depth_consistency_kernel(const float* __restrict__ depth_a, const float* __restrict__ conf_a,
+// (256, 5): the one-off 4 x 4 inversion of load_view_pose, not the per-pixel code, sets the register count; five waves per SIMD are what the
+// kernel has run at, and the bound keeps the inversion from costing one of them
+__global__ __launch_bounds__(256, 5) void depth_consistency_kernel(const float* __restrict__ depth_a, const float* __restrict__ conf_a,
                                                                 const unsigned char* __restrict__ mask_a, const double* __restrict__ Ka,
                                                                 const double* __restrict__ Ea, const float* __restrict__ depth_b,
                                                                 const double* __restrict__ Kb, const double* __restrict__ Eb, int S,
                                                                 double px_max, double rel_max, float conf_min, float* __restrict__ fused,
                                                                 float* __restrict__ reproj, float* __restrict__ rel,
                                                                 unsigned char* __restrict__ keep) {
-  __shared__ double inv[2][12];      // inv(E_a), inv(E_b)
-  __shared__ double ext[2][12];      // E_a[:3], E_b[:3]
-  __shared__ int inv_ok[2];
+  __shared__ ViewPose cam[2];      // a, b
   const long long f = blockIdx.y;
-  if (threadIdx.x == 0 || threadIdx.x == 64) {      // one lane of two different waves
-    const int w = threadIdx.x >> 6;
-    const double* E = w ? Eb : Ea;
-    inv_ok[w] = invert_extrinsic_rows(f, E, inv[w]) ? 1 : 0;
-    for (int j = 0; j < 12; ++j) ext[w][j] = E[f * 16 + j];
-  }
+  if (threadIdx.x == 0 || threadIdx.x == 64) load_view_pose(f, threadIdx.x ? Eb : Ea, cam[threadIdx.x >> 6]);      // two different waves
   __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S * S) return;
@@ -60,31 +58,17 @@ __global__ __launch_bounds__(256) void depth_consistency_kernel(const float* __r
   float r_fused = qnan, r_reproj = qnan, r_rel = qnan;
   unsigned char r_keep = 0;
   const float df = depth_a[o];
-  if (isfinite(df) && df > 0.f && inv_ok[0] && inv_ok[1]) {
-    const double fxa = Ka[f * 9 + 0], fya = Ka[f * 9 + 4], cxa = Ka[f * 9 + 2], cya = Ka[f * 9 + 5];
-    const double fxb = Kb[f * 9 + 0], fyb = Kb[f * 9 + 4], cxb = Kb[f * 9 + 2], cyb = Kb[f * 9 + 5];
-    const double d = (double)df, top = (double)(S - 1);
-    double X[3], u, v, z;
-    backproject_world(inv[0], (double)x, (double)y, d, fxa, fya, cxa, cya, X);
-    project_view(ext[1], X, fxb, fyb, cxb, cyb, u, v, z);
-    if (z > 0.0 && u >= 0.0 && u <= top && v >= 0.0 && v <= top) {      // false for NaN
-      const int x0 = (int)floor(u), y0 = (int)floor(v);                  // 0 .. S - 1
-      const int x1 = min(x0 + 1, S - 1), y1 = min(y0 + 1, S - 1);
-      const float* B = depth_b + f * S * S;
-      const float t00 = B[y0 * S + x0], t01 = B[y0 * S + x1], t10 = B[y1 * S + x0], t11 = B[y1 * S + x1];
-      if (isfinite(t00) && isfinite(t01) && isfinite(t10) && isfinite(t11) && t00 > 0.f && t01 > 0.f && t10 > 0.f && t11 > 0.f) {
-        const double ax = u - (double)x0, ay = v - (double)y0;
-        const double db = ((double)t00 * (1.0 - ax) + (double)t01 * ax) * (1.0 - ay) + ((double)t10 * (1.0 - ax) + (double)t11 * ax) * ay;
-        double Xb[3], xr, yr, dr;
-        backproject_world(inv[1], u, v, db, fxb, fyb, cxb, cyb, Xb);
-        project_view(ext[0], Xb, fxa, fya, cxa, cya, xr, yr, dr);
-        const double e_px = hypot(xr - (double)x, yr - (double)y), e_rel = fabs(dr - d) / d;
-        r_reproj = (float)e_px;
-        r_rel = (float)e_rel;
-        const bool k = e_px < px_max && e_rel < rel_max && (!conf_a || conf_a[o] >= conf_min) && (!mask_a || mask_a[o] != 0);
-        r_keep = k ? 1 : 0;
-        if (k) r_fused = (float)((d + dr) / 2.0);
-      }
+  if (isfinite(df) && df > 0.f && cam[0].ok && cam[1].ok) {
+    const double d = (double)df;
+    const ViewK ka = view_intrinsics(f, Ka), kb = view_intrinsics(f, Kb);
+    double X[3], e_px, e_rel, dr;
+    backproject_world(cam[0].inv, (double)x, (double)y, d, ka.fx, ka.fy, ka.cx, ka.cy, X);
+    if (reproject_round_trip(X, (double)x, (double)y, d, cam[0], ka, cam[1], kb, depth_b + f * S * S, S, e_px, e_rel, dr)) {
+      r_reproj = (float)e_px;
+      r_rel = (float)e_rel;
+      const bool k = e_px < px_max && e_rel < rel_max && (!conf_a || conf_a[o] >= conf_min) && (!mask_a || mask_a[o] != 0);
+      r_keep = k ? 1 : 0;
+      if (k) r_fused = (float)((d + dr) / 2.0);
     }
   }
   fused[o] = r_fused;
@@ -106,21 +90,21 @@ int launch_depth_consistency(const float* depth_a, const float* conf_a, const un
   return 0;
 }
 
-__global__ __launch_bounds__(PACK_THREADS) void cloud_pack_kernel(const float* __restrict__ fused1, const unsigned char* __restrict__ keep1,
+// (PACK_THREADS, 5): as for depth_consistency_kernel
+__global__ __launch_bounds__(PACK_THREADS, 5) void cloud_pack_kernel(const float* __restrict__ fused1, const unsigned char* __restrict__ keep1,
                                                                   const double* __restrict__ K1, const double* __restrict__ E1,
                                                                   const float* __restrict__ fused2, const unsigned char* __restrict__ keep2,
                                                                   const double* __restrict__ K2, const double* __restrict__ E2, int S,
                                                                   int cap, float* __restrict__ cloud, int* __restrict__ index,
                                                                   int* __restrict__ count) {
-  __shared__ double inv[2][12];
-  __shared__ int inv_ok[2];
-  __shared__ int wsum[PACK_WAVES][3];
+  __shared__ ViewPose cam[2];
+  __shared__ int wsum[3][PACK_WAVES];
   const long long f = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int SS = S * S, views = keep2 ? 2 : 1, T = views * SS;      // T <= 2^25
   const int piece = (T + PACK_BLOCKS - 1) / PACK_BLOCKS;
-  const int lo = min((int)blockIdx.x * piece, T), hi = min(lo + piece, T);
-  if (tid == 0 || (tid == 64 && views == 2)) inv_ok[wave] = invert_extrinsic_rows(f, wave ? E2 : E1, inv[wave]) ? 1 : 0;
+  const int lo = min((int)blockIdx.x * piece, T), hi = min(lo + piece, T);      // blockIdx.x: uniform over the workgroup
+  if (tid == 0 || (tid == 64 && views == 2)) load_view_pose(f, wave ? E2 : E1, cam[wave]);
   const unsigned char* k1 = keep1 + f * SS;
   const unsigned char* k2 = keep2 ? keep2 + f * SS : nullptr;
   auto kept = [&](int p) -> bool { return (p < SS ? k1[p] : k2[p - SS]) != 0; };
@@ -136,53 +120,21 @@ __global__ __launch_bounds__(PACK_THREADS) void cloud_pack_kernel(const float* _
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     for (int m = 32; m > 0; m >>= 1) c[j] += __shfl_xor(c[j], m, 64);
-    if (lane == 0) wsum[wave][j] = c[j];
+    if (lane == 0) wsum[j][wave] = c[j];
   }
   __syncthreads();
-  int base = 0, n1 = 0, n2 = 0;
-  for (int w = 0; w < PACK_WAVES; ++w) { base += wsum[w][0]; n1 += wsum[w][1]; n2 += wsum[w][2]; }
-  __syncthreads();      // wsum is reused below
+  int base = 0, n1 = 0, n2 = 0;      // sums over all waves: the same in every thread
+  for (int w = 0; w < PACK_WAVES; ++w) { base += wsum[0][w]; n1 += wsum[1][w]; n2 += wsum[2][w]; }
+  __syncthreads();      // wsum[0] is the walk's table
   if (blockIdx.x == 0 && tid == 0) { count[f * 2 + 0] = n1; count[f * 2 + 1] = n2; }
 
   float* cl = cloud + f * (long long)cap * 3;
   int* ix = index + f * (long long)cap;
-  const float qnan = __uint_as_float(0x7fc00000u);
-  for (int p0 = lo; p0 < hi && base < cap; p0 += PACK_THREADS) {      // base, p0: the same in every thread
-    const int p = p0 + tid;
-    const bool k = p < hi && kept(p);
-    const unsigned long long b = __ballot(k);
-    if (lane == 0) wsum[wave][0] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int w = 0; w < PACK_WAVES; ++w) { const int t = wsum[w][0]; before += w < wave ? t : 0; all += t; }
-    const int slot = base + before + __popcll(b & ((1ull << lane) - 1ull));
-    if (k && slot < cap) {
-      const int v = p < SS ? 0 : 1, q = p - v * SS, y = q / S, x = q - y * S;
-      const float zf = (v ? fused2 : fused1)[f * SS + q];
-      const double* K = (v ? K2 : K1) + f * 9;
-      float o[3] = {qnan, qnan, qnan};
-      if (isfinite(zf) && inv_ok[v]) {
-        double w3[3];
-        backproject_world(inv[v], (double)x, (double)y, (double)zf, K[0], K[4], K[2], K[5], w3);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) o[r] = (float)w3[r];
-      }
-      cl[(long long)slot * 3 + 0] = o[0];
-      cl[(long long)slot * 3 + 1] = o[1];
-      cl[(long long)slot * 3 + 2] = o[2];
-      ix[slot] = p;
-    }
-    base += all;
-    __syncthreads();
-  }
-
-  // the rows no pixel fills: [min(cap, total), cap), shared among the pose's workgroups
-  const long long total = (long long)n1 + n2;
-  const long long t0 = total < cap ? total : cap;
-  for (long long r = t0 + (long long)blockIdx.x * PACK_THREADS + tid; r < cap; r += (long long)PACK_BLOCKS * PACK_THREADS) {
-    cl[r * 3 + 0] = qnan; cl[r * 3 + 1] = qnan; cl[r * 3 + 2] = qnan;
-    ix[r] = -1;
-  }
+  pack_walk<PACK_THREADS>(lo, hi, base, cap, wsum[0], kept, [&](int slot, int p) {
+    const int v = p < SS ? 0 : 1, q = p - v * SS;
+    pack_emit_row(cl, ix, slot, p, cam[v], view_intrinsics(f, v ? K2 : K1), q, S, (v ? fused2 : fused1)[f * SS + q]);
+  });
+  pack_fill_unused(cl, ix, (long long)n1 + n2, cap, (long long)blockIdx.x * PACK_THREADS + tid, (long long)PACK_BLOCKS * PACK_THREADS);
 }
 
 int launch_cloud_pack(const float* fused1, const unsigned char* keep1, const double* K1, const double* E1, const float* fused2,

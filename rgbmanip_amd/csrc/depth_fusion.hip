@@ -1,12 +1,11 @@
 // Multi-view fusion of dense depth maps and the packed point cloud of V views, gfx950.
 //
 // depth_fusion_kernel: the MVSNet fusion step over V >= 2 views of a pose.  One thread per pixel (x, y) of reference view a with depth
-// d; the V inverses, extrinsic rows and intrinsics of the pose sit in LDS:
+// d; the V views' inverses and extrinsic rows sit in LDS (cloud_geom.h: ViewPose):
 //   0. d not finite, d <= 0, or E_a without a finite inverse                               -> keep 0, fused NaN, nviews 0, agree 0
 //   1. for the sources b = 0 .. V - 1, b != a, in increasing order: a source whose E_b has no finite inverse does not agree; otherwise
-//      rules 2-4 of depth_consistency.hip (same expressions: backproject_world / project_view of bbox_emit.h, same taps, same clamp of
-//      the second tap, same NaN / <= 0 tap rule) give (x', y', d'_b); b agrees iff hypot(x' - x, y' - y) < px_max && |d'_b - d| / d <
-//      rel_max
+//      rules 2-4 of depth_consistency.hip (cloud_geom.h: reproject_round_trip, the function depth_consistency_kernel calls) give
+//      (x', y', d'_b), or no witness; b agrees iff hypot(x' - x, y' - y) < px_max && |d'_b - d| / d < rel_max
 //   2. c = the agreeing sources; nviews = c, agree = their bit set                           (written whatever 3 decides)
 //   3. keep = c >= n_min && (no conf || conf >= conf_min) && (no mask || mask != 0);
 //      fused = keep ? (d + sum of d'_b over the agreeing b, in increasing b) / (1 + c) : NaN
@@ -17,12 +16,13 @@
 // Two launches, no atomics: cloud_count_views_kernel writes count [n][V] (one workgroup per view of a pose), cloud_pack_views_kernel
 // cuts every view into `pieces` contiguous pieces, one workgroup each, whose first slot is the counts of the views before its own plus
 // the kept pixels of its own view before its piece — a workgroup reads at most one view's keep bytes, whatever V is (cloud_pack_kernel
-// reads the whole pose in each of its 8 workgroups).  The walk of a piece is cloud_pack_kernel's (wave ballot, 16-entry LDS table).
+// reads the whole pose in each of its 8 workgroups).  The walk of a piece, the row and the NaN / -1 fill are the functions
+// cloud_pack_kernel calls (cloud_geom.h: pack_walk, pack_emit_row, pack_fill_unused).
 //
 // cloud_gather_views: cloud_gather_kernel for maps [n][V][S2][C] and indices view * S2 + pixel.
 #include <cmath>
 
-#include "bbox_emit.h"
+#include "cloud_geom.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -42,19 +42,10 @@ __global__ __launch_bounds__(256) void depth_fusion_kernel(const float* __restri
                                                            float conf_min, int n_min, float* __restrict__ fused,
                                                            unsigned char* __restrict__ keep, unsigned char* __restrict__ nviews,
                                                            unsigned short* __restrict__ agree) {
-  __shared__ double inv[FUSE_MAX_VIEWS][12];      // inv(E_v)
-  __shared__ double ext[FUSE_MAX_VIEWS][12];      // E_v[:3]
-  __shared__ double kk[FUSE_MAX_VIEWS][4];        // fx, fy, cx, cy
-  __shared__ int inv_ok[FUSE_MAX_VIEWS];
+  __shared__ ViewPose cam[FUSE_MAX_VIEWS];
   const int pose = blockIdx.y / V, a = blockIdx.y - pose * V;
   const long long v0 = (long long)pose * V;      // first view of the pose
-  if ((int)threadIdx.x < V) {
-    const int w = threadIdx.x;
-    const long long f = v0 + w;
-    inv_ok[w] = invert_extrinsic_rows(f, E, inv[w]) ? 1 : 0;
-    for (int j = 0; j < 12; ++j) ext[w][j] = E[f * 16 + j];
-    kk[w][0] = Kc[f * 9 + 0]; kk[w][1] = Kc[f * 9 + 4]; kk[w][2] = Kc[f * 9 + 2]; kk[w][3] = Kc[f * 9 + 5];
-  }
+  if ((int)threadIdx.x < V) load_view_pose(v0 + threadIdx.x, E, cam[threadIdx.x]);
   __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int SS = S * S;
@@ -66,28 +57,15 @@ __global__ __launch_bounds__(256) void depth_fusion_kernel(const float* __restri
   int c = 0;
   unsigned bits = 0;
   const float df = depth[o];
-  if (isfinite(df) && df > 0.f && inv_ok[a]) {
-    const double fxa = kk[a][0], fya = kk[a][1], cxa = kk[a][2], cya = kk[a][3];
-    const double d = (double)df, top = (double)(S - 1);
+  if (isfinite(df) && df > 0.f && cam[a].ok) {
+    const double d = (double)df;
+    const ViewK ka = view_intrinsics(v0 + a, Kc);
     double X[3], sum = d;
-    backproject_world(inv[a], (double)x, (double)y, d, fxa, fya, cxa, cya, X);
+    backproject_world(cam[a].inv, (double)x, (double)y, d, ka.fx, ka.fy, ka.cx, ka.cy, X);
     for (int b = 0; b < V; ++b) {
-      if (b == a || !inv_ok[b]) continue;
-      const double fxb = kk[b][0], fyb = kk[b][1], cxb = kk[b][2], cyb = kk[b][3];
-      double u, v, z;
-      project_view(ext[b], X, fxb, fyb, cxb, cyb, u, v, z);
-      if (!(z > 0.0 && u >= 0.0 && u <= top && v >= 0.0 && v <= top)) continue;      // true for NaN
-      const int x0 = (int)floor(u), y0 = (int)floor(v);                               // 0 .. S - 1
-      const int x1 = min(x0 + 1, S - 1), y1 = min(y0 + 1, S - 1);
-      const float* B = depth + (v0 + b) * SS;
-      const float t00 = B[y0 * S + x0], t01 = B[y0 * S + x1], t10 = B[y1 * S + x0], t11 = B[y1 * S + x1];
-      if (!(isfinite(t00) && isfinite(t01) && isfinite(t10) && isfinite(t11) && t00 > 0.f && t01 > 0.f && t10 > 0.f && t11 > 0.f)) continue;
-      const double ax = u - (double)x0, ay = v - (double)y0;
-      const double db = ((double)t00 * (1.0 - ax) + (double)t01 * ax) * (1.0 - ay) + ((double)t10 * (1.0 - ax) + (double)t11 * ax) * ay;
-      double Xb[3], xr, yr, dr;
-      backproject_world(inv[b], u, v, db, fxb, fyb, cxb, cyb, Xb);
-      project_view(ext[a], Xb, fxa, fya, cxa, cya, xr, yr, dr);
-      const double e_px = hypot(xr - (double)x, yr - (double)y), e_rel = fabs(dr - d) / d;
+      double e_px, e_rel, dr;
+      if (b == a || !cam[b].ok) continue;
+      if (!reproject_round_trip(X, (double)x, (double)y, d, cam[a], ka, cam[b], view_intrinsics(v0 + b, Kc), depth + (v0 + b) * SS, S, e_px, e_rel, dr)) continue;
       if (e_px < px_max && e_rel < rel_max) {
         sum += dr;
         ++c;
@@ -143,17 +121,16 @@ __global__ __launch_bounds__(PACKV_THREADS) void cloud_pack_views_kernel(const f
                                                                          const double* __restrict__ Kc, const double* __restrict__ E, int V,
                                                                          int S, int pieces, int cap, const int* __restrict__ count,
                                                                          float* __restrict__ cloud, int* __restrict__ index) {
-  __shared__ double inv[12];
-  __shared__ int inv_ok;
+  __shared__ ViewPose cam;
   __shared__ int wsum[PACKV_WAVES];
   const long long pose = blockIdx.y;
-  const int v = blockIdx.x / pieces, j = blockIdx.x - v * pieces;
+  const int v = blockIdx.x / pieces, j = blockIdx.x - v * pieces;      // blockIdx.x, pieces: uniform over the workgroup
   const long long f = pose * V + v;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int SS = S * S;
   const int piece = (SS + pieces - 1) / pieces;
   const int lo = min(j * piece, SS), hi = min(lo + piece, SS);
-  if (tid == 0) inv_ok = invert_extrinsic_rows(f, E, inv) ? 1 : 0;
+  if (tid == 0) load_view_pose(f, E, cam);
   const unsigned char* kv = keep + f * SS;
 
   // kept pixels of this view before the piece
@@ -162,49 +139,17 @@ __global__ __launch_bounds__(PACKV_THREADS) void cloud_pack_views_kernel(const f
   for (int m = 32; m > 0; m >>= 1) c += __shfl_xor(c, m, 64);
   if (lane == 0) wsum[wave] = c;
   __syncthreads();
-  long long base = 0, total = 0;                    // V S S <= 2^28
+  int base = 0, total = 0;                          // V S S <= 2^28; sums over all waves and views: the same in every thread
   for (int w = 0; w < PACKV_WAVES; ++w) base += wsum[w];
   for (int w = 0; w < V; ++w) { const int t = count[pose * V + w]; base += w < v ? t : 0; total += t; }
-  __syncthreads();      // wsum is reused below
+  __syncthreads();      // wsum is the walk's table
 
   float* cl = cloud + pose * (long long)cap * 3;
   int* ix = index + pose * (long long)cap;
-  const float qnan = __uint_as_float(0x7fc00000u);
-  const double* K = Kc + f * 9;
-  for (int p0 = lo; p0 < hi && base < cap; p0 += PACKV_THREADS) {      // base, p0: the same in every thread
-    const int p = p0 + tid;
-    const bool k = p < hi && kv[p] != 0;
-    const unsigned long long b = __ballot(k);
-    if (lane == 0) wsum[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int w = 0; w < PACKV_WAVES; ++w) { const int t = wsum[w]; before += w < wave ? t : 0; all += t; }
-    const long long slot = base + before + __popcll(b & ((1ull << lane) - 1ull));
-    if (k && slot < cap) {
-      const int y = p / S, x = p - y * S;
-      const float zf = fused[f * SS + p];
-      float o[3] = {qnan, qnan, qnan};
-      if (isfinite(zf) && inv_ok) {
-        double w3[3];
-        backproject_world(inv, (double)x, (double)y, (double)zf, K[0], K[4], K[2], K[5], w3);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) o[r] = (float)w3[r];
-      }
-      cl[slot * 3 + 0] = o[0];
-      cl[slot * 3 + 1] = o[1];
-      cl[slot * 3 + 2] = o[2];
-      ix[slot] = v * SS + p;
-    }
-    base += all;
-    __syncthreads();
-  }
-
-  // the rows no pixel fills: [min(cap, total), cap), shared among the pose's workgroups
-  const long long t0 = total < cap ? total : cap;
-  for (long long r = t0 + (long long)blockIdx.x * PACKV_THREADS + tid; r < cap; r += (long long)gridDim.x * PACKV_THREADS) {
-    cl[r * 3 + 0] = qnan; cl[r * 3 + 1] = qnan; cl[r * 3 + 2] = qnan;
-    ix[r] = -1;
-  }
+  const ViewK kc = view_intrinsics(f, Kc);
+  pack_walk<PACKV_THREADS>(lo, hi, base, cap, wsum, [&](int p) -> bool { return kv[p] != 0; },
+                           [&](int slot, int p) { pack_emit_row(cl, ix, slot, v * SS + p, cam, kc, p, S, fused[f * SS + p]); });
+  pack_fill_unused(cl, ix, total, cap, (long long)blockIdx.x * PACKV_THREADS + tid, (long long)gridDim.x * PACKV_THREADS);
 }
 
 int launch_cloud_pack_views(const float* fused, const unsigned char* keep, const double* Kc, const double* E, int n, int V, int S, int cap,

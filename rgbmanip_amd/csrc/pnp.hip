@@ -28,12 +28,6 @@ constexpr int PN_P = 1024;
 constexpr int PN_ITERS = 100;
 constexpr int PN_MODEL = 5;
 
-__device__ __forceinline__ unsigned pn_mix32(unsigned seed, unsigned frame, unsigned idx) {      // = mix32 of prepare.hip
-  unsigned h = seed ^ (frame * 0x9E3779B9u) ^ (idx * 0x85EBCA6Bu);
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return h;
-}
-
 // ------------------------------------------------------------------------------------------------ small dense linear algebra
 // symmetric n x n (row-major, n <= 12): cyclic Jacobi; on return ev[] ascending, V columns = eigenvectors in that order
 __device__ void eig_sym(double* A, int n, double* ev, double* V) {
@@ -298,18 +292,6 @@ __device__ bool epnp(const PnpData& D, const int* idx, int n, double* R, double*
   return have;
 }
 
-__device__ double pn_block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = PN_T / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 __device__ unsigned pn_block_count(unsigned v, unsigned* cnt) {
   if (threadIdx.x == 0) *cnt = 0u;
   __syncthreads();
@@ -504,7 +486,7 @@ __global__ __launch_bounds__(PN_T) void pnp_ransac_kernel(
   if (t < PN_ITERS) {
     int idx[PN_MODEL], have = 0;
     for (unsigned k = 0; have < PN_MODEL; ++k) {
-      const int c = (int)(pn_mix32(seed, (unsigned)b * 128u + (unsigned)t, k) % (unsigned)P);
+      const int c = (int)(mix32(seed, (unsigned)b * 128u + (unsigned)t, k) % (unsigned)P);
       bool dup = false;
       for (int j = 0; j < have; ++j) dup |= idx[j] == c;
       if (!dup) idx[have++] = c;
@@ -584,8 +566,8 @@ __global__ __launch_bounds__(PN_T) void pnp_ransac_kernel(
       for (int a = 0; a < 6; ++a) acc[21 + a] += Lx[a] * ex + Ly[a] * ey;                                     // L^T e (6)
     }
     double sum[27];
-    for (int i = 0; i < 27; ++i) sum[i] = pn_block_sum(acc[i], red);
-    const double err = sqrt(pn_block_sum(e2, red) / P);
+    for (int i = 0; i < 27; ++i) sum[i] = block_sum<PN_T>(acc[i], red);
+    const double err = sqrt(block_sum<PN_T>(e2, red) / P);
     if (fabs(err - prev) < 1e-6) break;                    // every thread sees the same sums: uniform exit
     prev = err;
     if (t == 0) {

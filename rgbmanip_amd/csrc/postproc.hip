@@ -137,20 +137,6 @@ __device__ __forceinline__ void for_pairs_approx(const PPArrays& A, int P, int r
   run(P - 1 - r, q_lo > split ? q_lo : split, q_hi, 1);
 }
 
-__device__ double block_sum(double v, double* red) {
-  // 1024 threads -> deterministic tree in LDS
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = PP_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // Block-wide bucket selection (all 1024 threads, 4 bins each; `hist` complete and visible): the first bin whose cumulative count
 // exceeds rank rk (rk = total / 2 when `half`), the count below it, its own count, the total.  An empty histogram (or a rank past
 // the end) reports digit 4095 with eq = 0.  (A single thread walking 4096 bins per pass cost ~0.9 ms of the 3.3 ms the first
@@ -497,8 +483,8 @@ __global__ __launch_bounds__(PP_THREADS) void postprocess_kernel(
     atomicMax((int*)&hmax[1], __float_as_int(fabsf(ny[t])));
     atomicMax((int*)&hmax[2], __float_as_int(fabsf(nz[t])));
   }
-  const double mcx = block_sum(sx, red) / P, mcy = block_sum(sy, red) / P, mcz = block_sum(sz, red) / P;
-  const double mtx = block_sum(tx, red) / P, mty = block_sum(ty, red) / P, mtz = block_sum(tz, red) / P;
+  const double mcx = block_sum<PP_THREADS>(sx, red) / P, mcy = block_sum<PP_THREADS>(sy, red) / P, mcz = block_sum<PP_THREADS>(sz, red) / P;
+  const double mtx = block_sum<PP_THREADS>(tx, red) / P, mty = block_sum<PP_THREADS>(ty, red) / P, mtz = block_sum<PP_THREADS>(tz, red) / P;
   if (t == 0) {
     double tr[3] = {mcx - mtx, mcy - mty, mcz - mtz};
     // NaN in nocs makes np.max propagate NaN; atomicMax on bit patterns would hide it -> re-check via the sums

@@ -20,12 +20,6 @@ namespace {
 
 constexpr int PRE_THREADS = 1024;
 
-__host__ __device__ inline unsigned mix32(unsigned seed, unsigned frame, unsigned idx) {
-  unsigned h = seed ^ (frame * 0x9E3779B9u) ^ (idx * 0x85EBCA6Bu);
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;     // murmur3 finaliser
-  return h;
-}
-
 // ---- cropped intrinsics of a window: interface_v5.py:153-168 (python floats = fp64), shared by the two kernels that write Kcrop ----
 __device__ inline void crop_intrinsics(const double* __restrict__ Ki, int rmin, int rmax, int cmin, int cmax, int S, double* __restrict__ Ko) {
   const double ratio = (double)S / (double)(rmax - rmin);
