@@ -176,6 +176,33 @@ int rgbm_sample_box_stats(const double* boxes, const uint8_t* ok, int n, int S, 
                           void* stream);
 int rgbm_sample_point_stats(const float* x, int n, int S, int64_t M, float* mean, float* std, void* stream);
 
+/* Agreement of two oriented boxes (box_overlap.hip; float64 numpy twins in rgbmanip_amd/boxes.py).  Device pointers, fp64.
+ * A box is [8][3] corners in get_3d_bbox's order (lib/utils.py:49-56), read as the parallelepiped o + a ex + b ey + c ez,
+ *   0 <= a, b, c <= 1, o = corner 0, ex / ey / ez = corner 2 / 4 / 1 - corner 0 (the edges of rgbm_sample_box_stats); the other four
+ *   corners enter the finiteness check, the centre (mean of the 8) and corner_dist only.  volume = |det[ex ey ez]|.  A box is unusable
+ *   when one of its 24 coordinates is not finite, its volume is not > 0 or its ok byte is 0; ok_a / ok_b may be NULL (every box may
+ *   count).  Every metric of a pair with an unusable box is NaN, its valid 0.  Coordinate range: edge lengths within 1e-60 .. 1e60
+ *   (boxes are metres); the face normals go through products of four edge lengths, and where those overflow or vanish the results
+ *   are not defined.
+ * Intersection volume: exact for two parallelepipeds, 1/3 sum_f d_f area(P_f) over the 12 faces with P_f the face clipped by the other
+ *   box's half-spaces, in coordinates relative to the centre of box A, summed in face order (A's, then B's; no atomics: two calls give
+ *   the same bytes).  Coincident planes, tau = 1e-12, L the longer of |ex + ey + ez|: a plane of B with n_A . n_B >= 1 - tau and
+ *   |d_A - d_B| <= tau L against a plane of A is dropped, one with n_A . n_B <= -(1 - tau) and |d_A + d_B| <= tau L makes the volume 0.
+ *   inter = clamp(sum, 0, min(volume_a, volume_b)), iou = inter / (volume_a + volume_b - inter).
+ * rgbm_box_agreement: a, b [n][8][3], ok_a, ok_b [n] uint8 -> for pair i = (a[i], b[i]): valid [n] int32, iou, inter_volume, volume_a,
+ *   volume_b [n]; center_dist [n] and center_delta [n][3] (b - a); corner_dist [n], the mean over the 8 corners of |a_k - b_k|;
+ *   extent_a, extent_b [n][3], the edge lengths x, y, z; axis_angle_deg [n][3] = acos(clamp(u_a . u_b)) of the unit edges, 0..180;
+ *   axis_fold_deg [n][3] = min(angle, 180 - angle); rot_deg [n] = acos(clamp((sum_e u_a[e] . u_b[e] - 1) / 2)).
+ *   1 <= n <= 2^24, refused otherwise; every output pointer is required.
+ * rgbm_box_iou_matrix: a [n][P][8][3], b [n][Q][8][3], ok_a [n][P], ok_b [n][Q] -> iou [n][P][Q], NaN where either box is unusable.
+ *   1 <= P, Q <= 64 and n >= 1, n P Q <= 2^31 - 1, refused otherwise.  A refused call launches nothing and writes nothing. */
+int rgbm_box_agreement(const double* a, const double* b, const uint8_t* ok_a, const uint8_t* ok_b, int n, int32_t* valid, double* iou,
+                       double* inter_volume, double* volume_a, double* volume_b, double* center_dist, double* center_delta,
+                       double* corner_dist, double* extent_a, double* extent_b, double* axis_angle_deg, double* axis_fold_deg,
+                       double* rot_deg, void* stream);
+int rgbm_box_iou_matrix(const double* a, const double* b, const uint8_t* ok_a, const uint8_t* ok_b, int n, int P, int Q, double* iou,
+                        void* stream);
+
 /* Dense depth and confidence maps of the crops (what lib/network_v3.py:406-408 returns as view1_depth: softmax over the D planes of the
  * regularised cost volume, then the expectation with the depth values), beside the ten point outputs.
  * rgbm_adapose_forward_dense: the arguments of rgbm_adapose_forward plus two caller-owned fp32 device buffers [V'][224][224],

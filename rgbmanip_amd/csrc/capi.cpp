@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "adapose.h"
+#include "box_overlap.h"
 #include "control.h"
 #include "cost3d.h"
 #include "conv_plan.h"
@@ -417,6 +418,20 @@ int rgbm_sample_box_stats(const double* boxes, const uint8_t* ok, int n, int S, 
                           void* stream) {
   return rgbm::launch_sample_box_stats(boxes, ok, n, S, count, bbox_mean, bbox_std, center_mean, center_cov, extent_mean, extent_std,
                                        axis_spread_deg, (hipStream_t)stream);
+}
+
+int rgbm_box_agreement(const double* a, const double* b, const uint8_t* ok_a, const uint8_t* ok_b, int n, int32_t* valid, double* iou,
+                       double* inter_volume, double* volume_a, double* volume_b, double* center_dist, double* center_delta,
+                       double* corner_dist, double* extent_a, double* extent_b, double* axis_angle_deg, double* axis_fold_deg,
+                       double* rot_deg, void* stream) {
+  const rgbm::BoxAgreementOut o{valid, iou, inter_volume, volume_a, volume_b, center_dist, center_delta, corner_dist,
+                                extent_a, extent_b, axis_angle_deg, axis_fold_deg, rot_deg};
+  return rgbm::launch_box_agreement(a, b, ok_a, ok_b, n, o, (hipStream_t)stream);
+}
+
+int rgbm_box_iou_matrix(const double* a, const double* b, const uint8_t* ok_a, const uint8_t* ok_b, int n, int P, int Q, double* iou,
+                        void* stream) {
+  return rgbm::launch_box_iou_matrix(a, b, ok_a, ok_b, n, P, Q, iou, (hipStream_t)stream);
 }
 
 int rgbm_sample_point_stats(const float* x, int n, int S, int64_t M, float* mean, float* std, void* stream) {
