@@ -631,6 +631,30 @@ int rgbm_conv_nd(int dtype, const void* in_dev, int N, int D, int H, int W, int 
 int rgbm_conv_plan(int dtype, int N, int D, int H, int W, int Cin, int Cin_pad, int Cout, int Cout_pad, int KD, int KH, int KW,
                    int stride_d, int stride_hw, int pad_d, int pad_hw, int dil_hw, int transposed, int has_bias, int res_mode, int act,
                    int cls, int n_cu, int32_t* plan);
+/* Border-class tiles of a dilated 2-D conv (K x K, stride, pad, dil; one pre-activation residual when res_mode = 1) on the 256 x 256
+ * tiles of kernel 7: output pixels whose set of in-range taps is the same form a class, a tile is 256 rows of one class taken across
+ * views (row r of a class: view r / n, class pixel r % n, row-major inside the class, up to the last GEMM row of the 256 x 256 launch; the class
+ * is padded to whole tiles with dead rows)
+ * and walks only the class's taps, and the tiles are dealt in the order of the views they cover (the last round longest first) to the
+ * workgroup with the fewest K steps so far.  Every row then
+ * of the 256 x 256 launch (rgbm_conv_plan's [4]) then runs on these tiles; the rows behind them keep their tail launch.  Works without a GPU when n_cu > 0 (as rgbm_conv_plan).  The plan declines (head[0] = 0,
+ * nothing else filled) for 1 x 1 convs, stride != 1, launches that do not reach the 256 x 256 tiles, shapes where no K step is saved,
+ * and under debug flag 32 / 1048576; a layer whose weights hold a NaN / inf declines at its launches.
+ *   head[RGBM_BORDER_HEAD_INTS]: [0] 1 = taken  [1] classes  [2] tiles  [3] workgroups  [4] table rows (dead ones included)
+ *     [5] K steps of the busiest workgroup  [6] K steps of all tiles (mean per workgroup = [6] / [3])
+ *     [7] K steps of the row-major tiles (every tile walks every tap)  [8] K steps per tap (Cin / 64; split pairs: Cin / 32)
+ *     [9] residual steps per tile
+ *   classes[3 * cap_classes]: {pixels of a view, tap mask (bit kh * K + kw), first table row} per class
+ *   tiles[5 * cap_tiles]: {class, channel tile, tap mask, K steps (residual steps included), first table row} per tile
+ *   order[cap_tiles] + wg_off[cap_wg]: workgroup b runs tiles order[wg_off[b] .. wg_off[b + 1]) in this order
+ *   rows[cap_rows]: GEMM row (view * H + h) * W + w (below rgbm_conv_plan's [4]) of every table row, -1 = dead
+ * Every array may be null (not wanted); a capacity that is too small is an error. */
+#define RGBM_BORDER_HEAD_INTS 10
+int rgbm_conv_border_plan(int dtype, int N, int H, int W, int Cin, int Cout, int K, int stride, int pad, int dil, int res_mode, int n_cu,
+                          int32_t* head, int32_t* classes, int cap_classes, int32_t* tiles, int32_t* order, int cap_tiles, int32_t* wg_off,
+                          int cap_wg, int32_t* rows, int64_t cap_rows);
+/* Launches that ran on border-class tiles since the library was loaded (process-wide; what a test reads to see that a launch took them). */
+int rgbm_conv_border_launches(int64_t* count);
 /* Per-sample BatchNorm3d of the as-shipped mode (norm_mode = 1), in place: y_dev [V][nvox][C] (C % 4 == 0, C <= 64) in `dtype`
  * -> relu(gamma * (y - mean_v) / sqrt(var_v + 1e-5) + beta) + res, with the biased mean / variance of each view v's own volume;
  * relu 0 skips the ReLU, res_dev may be null (post-activation skip add otherwise, same layout).  gamma_dev / beta_dev [C] fp32;
@@ -774,6 +798,8 @@ int rgbm_crop_fingerprint(const float* img, int V, int n_words, uint64_t* keys_o
  *      8  no persistent ws kernels (generic tiles)
  *     16  treat every conv as non-uniform taps (v3 / generic kernels)                          64  v3 kernel instead of the ws kernel
  *    128  no ws64 kernel      256  ws64 without the row-halo variant      512  generic resize instead of the x2 kernel
+ *     32  no border-class tiles: dilated 3 x 3 layers on the 256 x 256 tiles run row-major tiles and multiply the padding taps
+ *          (default: rgbm_conv_border_plan; same bits either way)
  *  32768  layer2's 128-channel layers at one to four poses on the 64 x 256 tile of conv_igemm_ws_kernel as before (default since round 6:
  *          64-channel x 128-pixel tiles of conv_igemm_m32_kernel with the K split, residual added in the epilogue)
  *  16384  no K split of the 256-channel GEMM's launches of few tiles (small batches; default since round 6: the K loop of a 64 / 128-channel x

@@ -163,6 +163,9 @@ SIGNATURES = {
     "rgbm_conv_nd": (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                           _vp, _i, _i, _f, _vp, _vp]),
     "rgbm_conv_plan": (_i, [_i] * 23 + [C.POINTER(C.c_int32)]),
+    "rgbm_conv_border_plan": (_i, [_i] * 12 + [C.POINTER(C.c_int32)] * 2 + [_i] + [C.POINTER(C.c_int32)] * 2 + [_i, C.POINTER(C.c_int32), _i,
+                                   C.POINTER(C.c_int32), _i64]),
+    "rgbm_conv_border_launches": (_i, [C.POINTER(C.c_int64)]),
     "rgbm_bn_per_sample_scratch_bytes": (_i, [_i, C.POINTER(_sz)]),
     "rgbm_bn_per_sample": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     "rgbm_conv3d_tile": (_i, [_i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -638,6 +638,63 @@ int rgbm_conv_plan(int dtype, int N, int D, int H, int W, int Cin, int Cin_pad, 
   return 0;
 }
 
+int rgbm_conv_border_plan(int dtype, int N, int H, int W, int Cin, int Cout, int K, int stride, int pad, int dil, int res_mode, int n_cu,
+                          int32_t* head, int32_t* classes, int cap_classes, int32_t* tiles, int32_t* order, int cap_tiles, int32_t* wg_off,
+                          int cap_wg, int32_t* rows, int64_t cap_rows) {
+  RGBM_REQUIRE(head && n_cu >= 0 && dtype >= F32 && dtype <= BF16X3 && N > 0 && H > 0 && W > 0 && K > 0, "conv_border_plan arguments");
+  const ConvGeom g = conv_nd_geom(Cin, Cout, 1, K, K, 1, stride, 0, pad, dil, 0, ACT_RELU, 0.f);
+  PackedConv pc;
+  const int E = dtype_chunk(dtype);
+  const int Cin_pad = (Cin + E - 1) / E * E, Cout_pad = (Cout + 3) / 4 * 4;
+  if (int rc = conv_pack_geom(g, dtype, Cin_pad, Cout_pad, 0, &pc)) return rc;
+  ConvDesc d;
+  conv_desc_geom(d, g, pc, Cin_pad, Cout_pad, N, 1, H, W, Cout_pad, 0);
+  alignas(16) static const float buffer[4] = {};      // stands for every device buffer, as in rgbm_conv_plan
+  d.in = d.wgt = buffer; d.out = const_cast<float*>(buffer);
+  d.res = res_mode != RES_NONE ? buffer : nullptr;
+  d.res_mode = res_mode;
+  d.w_finite = 1;
+  ConvTuning t;
+  ConvPlan p;
+  if (int rc = conv_tuning(n_cu, &t)) return rc;
+  if (int rc = plan_conv(d, dtype, t, &p)) return rc;
+  memset(head, 0, RGBM_BORDER_HEAD_INTS * sizeof(int32_t));
+  BorderPlan bp;
+  if (p.kernel != CONV_M32 || !p.border || !plan_border(d, dtype, t.flags, p.main_rows, t.n_cu, &bp)) return 0;
+  const int32_t h[RGBM_BORDER_HEAD_INTS] = {1, (int32_t)bp.classes.size(), (int32_t)bp.tiles.size(), bp.n_wg, (int32_t)bp.rows.size(),
+                                             (int32_t)bp.max_wg_steps, (int32_t)bp.total_steps, (int32_t)bp.parent_steps, bp.steps_per_tap, bp.kr};
+  memcpy(head, h, sizeof(h));
+  if (classes) {
+    RGBM_REQUIRE((int)bp.classes.size() <= cap_classes, "conv_border_plan: cap_classes too small");
+    for (size_t c = 0; c < bp.classes.size(); ++c) {
+      classes[3 * c] = bp.classes[c].n_pix; classes[3 * c + 1] = bp.classes[c].mask; classes[3 * c + 2] = (int32_t)bp.classes[c].row0;
+    }
+  }
+  if (tiles || order) RGBM_REQUIRE((int)bp.tiles.size() <= cap_tiles, "conv_border_plan: cap_tiles too small");
+  if (tiles)
+    for (size_t i = 0; i < bp.tiles.size(); ++i) {
+      const BorderTile& bt = bp.tiles[i];
+      const int32_t v[5] = {bt.cls, bt.ch, bt.mask, bt.steps, (int32_t)bt.row0};
+      memcpy(tiles + 5 * i, v, sizeof(v));
+    }
+  if (order) memcpy(order, bp.order.data(), bp.order.size() * sizeof(int32_t));
+  if (wg_off) {
+    RGBM_REQUIRE(bp.n_wg + 1 <= cap_wg, "conv_border_plan: cap_wg too small");
+    memcpy(wg_off, bp.wg_off.data(), bp.wg_off.size() * sizeof(int32_t));
+  }
+  if (rows) {
+    RGBM_REQUIRE((int64_t)bp.rows.size() <= cap_rows, "conv_border_plan: cap_rows too small");
+    memcpy(rows, bp.rows.data(), bp.rows.size() * sizeof(int32_t));
+  }
+  return 0;
+}
+
+int rgbm_conv_border_launches(int64_t* count) {
+  RGBM_REQUIRE(count, "conv_border_launches arguments");
+  *count = border_launch_count();
+  return 0;
+}
+
 int rgbm_upsample_conv3x3(int dtype, const void* in_dev, int V, int h, int w, int Cin, const float* w_host, int Cout,
                           const float* bias_host, int act, float slope, void* z_scratch_dev, void* out_dev, void* stream) {
   RGBM_REQUIRE(in_dev && w_host && z_scratch_dev && out_dev, "upsample_conv3x3 arguments");

@@ -281,6 +281,12 @@ struct ConvDesc {
   // each; a part leaves its fp32 accumulators in kscratch, the LAST of a tile's parts to arrive (kcount, per tile and multiply wave) adds the
   // parts in ascending order and runs the epilogue (conv_igemm_m32.inc).  0 / 1 = no split.
   int ksplit; float* kscratch; unsigned* kcount;
+  // conv_igemm_m32_kernel, 256 x 256 tiles of border classes (conv_plan.h, plan_border).  w_finite: the layer's packed weights hold no
+  // NaN / inf (set at create; the plan declines otherwise: NaN * 0 is the one product a skipped padding tap would change).  btab: the
+  // layer's device table for this shape, set by ConvLayer::run (null: row-major tiles): [0, b_nwg] first entry of each workgroup, then at
+  // int b_ent four ints per tile in workgroup-major order {first table row, K steps without the residual steps,
+  // kh0 | kh1 << 4 | kw0 << 8 | kw1 << 12 | channel tile << 16, 0}, then at int b_rows the GEMM row of every table row (-1: dead).
+  int w_finite; const int* btab; int b_nwg, b_ent, b_rows;
 };
 
 int launch_conv(const ConvDesc& d, int dtype, hipStream_t s);

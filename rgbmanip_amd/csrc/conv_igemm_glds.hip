@@ -4,6 +4,7 @@
 // is needed.  The LDS image of a tile is lane-linear (wave-uniform base + lane*16 bytes), therefore the bank-conflict
 // swizzle is applied on the SOURCE side: the lane that fills LDS slot (row, j) fetches global chunk j ^ ((row>>1)&7),
 // and readers XOR the same value (an involution).  Out-of-image / padded-K lanes fetch from a 16-byte zero page.
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <type_traits>

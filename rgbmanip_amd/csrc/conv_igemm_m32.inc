@@ -107,9 +107,23 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
   const bool res_in_acc = d.ident != nullptr && d.res_mode == RES_PRE_ACT;      // the residual reaches the accumulators through KR identity steps (of the last K part)
   const int KR = (res_in_acc && part == nsp - 1) ? BCH / BK : 0;
   const int KTT = KT + KR;
-  const int n_my = vtile >= 0 ? 1 : ((int)d.n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int total = n_my * KTT;              // K-tile steps of this workgroup; every wave passes `total` barriers
+  // Border-class tiles (256 x 256, d.btab set; conv_plan.h): this workgroup's tiles are the table entries [be0, be0 + n_my).  An entry
+  // names the tile's 256 table rows, its K steps and the rectangle of taps they walk; EVERY wave takes a tile's step count from that one
+  // entry (bsteps), so the multiply waves, the request waves and `total` count the same barriers.
+  const bool bm = STAGED && !X3 && d.btab != nullptr;      // (16-bit types: with split pairs the table's registers push 390 bytes of accumulators into scratch)
+  const int* __restrict__ bent = d.btab;
+  int n_my = vtile >= 0 ? 1 : ((int)d.n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+  int total = n_my * KTT;                    // K-tile steps of this workgroup; every wave passes `total` barriers
+  if (bm) {
+    const int be0 = d.btab[blockIdx.x];
+    n_my = d.btab[blockIdx.x + 1] - be0;
+    bent = d.btab + d.b_ent + 4 * be0;
+    total = 0;
+    for (int k = 0; k < n_my; ++k) total += bent[4 * k + 1] + KR;
+  }
+  auto bsteps = [&](int k) { return bm ? __builtin_amdgcn_readfirstlane(bent[4 * k + 1]) : KT; };      // K steps of tile k without the residual steps
   auto tile_of = [&](int k, int& pix_tile, int& ch_tile) {
+    if (bm) { pix_tile = 0; ch_tile = __builtin_amdgcn_readfirstlane(bent[4 * k + 2]) >> 16; return; }
     const int v = vtile >= 0 ? vtile : (int)blockIdx.x + k * (int)gridDim.x;          // virtual workgroup id -> XCD-aware tile order
     const int nblk = d.n_tiles, bq = nblk >> 3, br = nblk & 7, xcd = v & 7, bidx = v >> 3;
     const int lid = (xcd < br ? xcd * (bq + 1) : br * (bq + 1) + (xcd - br) * bq) + bidx;
@@ -151,17 +165,16 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
     long long mybase = 0;
     unsigned mymask = 0;
     int my_ch_tile = 0, my_pix_tile = 0;
-    auto prepare_tile = [&](int k) {         // lane j of a row group decodes GEMM row r0 + 32*j; the group exchanges them (enter_tile)
-      int pix_tile, ch_tile;
-      tile_of(k, pix_tile, ch_tile);
-      my_ch_tile = ch_tile;
-      my_pix_tile = pix_tile;
+    int ikt = 0, itile = 0;                  // K tile / tile index of the next request
+    // border-class tiles: the request side's copy of the current tile's entry (K steps, tap rectangle) and this lane's GEMM row (-1: dead)
+    int KTc = KT, KTTc = KTT, bkh0 = 0, bkh1 = 0, bkw0 = 0, bkw1 = 0, mym = -1;
+    int* lrow = reinterpret_cast<int*>(lbias + 2560);      // [2][256]: the GEMM rows of tile k at (k & 1) * 256, for the multiply waves' epilogue
+    auto decode_my = [&](long long m) {      // this lane's row: its first input pixel and which taps are in range (border-class tiles: all of the tile's)
       mybase = 0;
       mymask = 0;
       if (j < XR) {
-        const long long m = d.m0 + (long long)pix_tile * BPIX + r0 + 32 * j;
         int xn = 0, xd0 = -(1 << 20), xh0 = 0, xw0 = 0;
-        if (m < d.M) {
+        if (m >= 0 && m < d.M) {
           unsigned n, qd, qh, qw;
           decode_row(d, (unsigned)m, n, qd, qh, qw);
           xn = (int)n * d.Di;
@@ -172,19 +185,42 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
         for (int kk = 0; kk < d.KD; ++kk) mymask |= (unsigned)((unsigned)(xd0 + kk * d.dild) < (unsigned)d.Di) << kk;
         for (int kk = 0; kk < d.KH; ++kk) mymask |= (unsigned)((unsigned)(xh0 + kk * d.dilh) < (unsigned)d.Hi) << (8 + kk);
         for (int kk = 0; kk < d.KW; ++kk) mymask |= (unsigned)((unsigned)(xw0 + kk * d.dilw) < (unsigned)d.Wi) << (16 + kk);
+        if (bm) mymask = m >= 0 ? 0x00ffffffu : 0u;      // every tap the walker visits is in range for every live row
         const long long pix0 = ((long long)(xn + xd0) * d.Hi + xh0) * d.Wi + xw0;
         mybase = pix0 * d.Cin * (long long)sizeof(T);
       }
     };
+    auto prepare_tile = [&](int k) {         // lane j of a row group decodes GEMM row r0 + 32*j; the group exchanges them (enter_tile)
+      int pix_tile, ch_tile;
+      tile_of(k, pix_tile, ch_tile);
+      my_ch_tile = ch_tile;
+      my_pix_tile = pix_tile;
+      if (bm) {
+        // the row comes from the table; it is decoded in enter_tile, behind the next counted wait (its load queues behind this step's pieces)
+        const int tr = __builtin_amdgcn_readfirstlane(bent[4 * k + 2]);
+        KTc = bsteps(k);
+        KTTc = KTc + KR;
+        bkh0 = tr & 15; bkh1 = (tr >> 4) & 15; bkw0 = (tr >> 8) & 15; bkw1 = (tr >> 12) & 15;
+        mym = j < XR ? d.btab[d.b_rows + __builtin_amdgcn_readfirstlane(bent[4 * k]) + r0 + 32 * j] : -1;
+        return;
+      }
+      decode_my(d.m0 + (long long)pix_tile * BPIX + r0 + 32 * j);
+    };
     auto enter_tile = [&]() {
       const int grp = (tp & 63) & 56;
+      if (bm) {
+        decode_my(mym);
+        if (j < XR) lrow[(itile & 1) * 256 + r0 + 32 * j] = mym;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // written before this wave's next barrier; read behind the tile's last one
+      }
 #pragma unroll
       for (int i = 0; i < XR; ++i) {
         const long long b = __shfl(mybase, grp | i, 64);
         rmask[i] = (unsigned)__shfl((int)mymask, grp | i, 64);
         xoff[i] = (unsigned)(b + xbias + (long long)(js * E) * (long long)sizeof(T));
         if (KR) {
-          const long long m = d.m0 + (long long)my_pix_tile * BPIX + r0 + 32 * i;      // residual row of GEMM row m (dense output: row m of [M][ldo])
+          long long m = d.m0 + (long long)my_pix_tile * BPIX + r0 + 32 * i;      // residual row of GEMM row m (dense output: row m of [M][ldo])
+          if (bm) { m = __shfl(mym, grp | i, 64); if (m < 0) m = d.M; }
           roff[i] = m < d.M ? (unsigned)((m * d.ldo + my_ch_tile * BCH + js * E) * (long long)sizeof(T)) : 0xffffffffu;
         }
       }
@@ -195,6 +231,10 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
       }
       tkd = tkh = tkw = tc = 0;
       wko = 0;
+      if (bm) {                                // the walker starts at the first tap of the tile's rectangle
+        tkh = bkh0; tkw = bkw0;
+        wko = (unsigned)((tkh * d.KW + tkw) * d.Cin) * (unsigned)sizeof(T);
+      }
       if (kt0 > 0) {                           // K split: the walker starts at K step kt0 (the closed form of the advance at the end of issue())
         if (d.korder && d.lcin >= 0) {         // channel block outer, taps inner
           const int tap = kt0 % d.ntaps, cb = kt0 / d.ntaps;
@@ -214,16 +254,15 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
       }
     };
 
-    int ikt = 0, itile = 0;                  // K tile / tile index of the next request
     auto issue = [&](int stage) {
       if (ikt == 0) enter_tile();
       const unsigned sbase = lds0 + (unsigned)stage * (STAGE * 16);
       const unsigned sel = (1u << tkd) | (256u << tkh) | (65536u << tkw);
       const unsigned soff = (unsigned)(((long long)((tkd * d.dild * d.Hi + tkh * d.dilh) * d.Wi + tkw * d.dilw) * d.Cin + tc) * (long long)sizeof(T));
       const bool cok = tkd < d.KD && tc + js * E < d.Cin;
-      if (ikt >= KT) {
+      if (ikt >= KTc) {
         // residual step r: X = residual rows, channels 64r .. 64r+63 of this channel tile; W = identity rows, the same 64 columns
-        const unsigned ro = (unsigned)(ikt - KT) * (unsigned)(BK * sizeof(T));
+        const unsigned ro = (unsigned)(ikt - KTc) * (unsigned)(BK * sizeof(T));
 #pragma unroll
         for (int i = 0; i < XR; ++i) blds16(roff[i], rsrc_r, ro, sbase + (BCH * 8 + i * 256) * 16);
         // (256 x 256: the multiply waves hold the identity's diagonal blocks as a constant A fragment — no W rows for these steps)
@@ -240,7 +279,10 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
 #pragma unroll
         for (int i = 0; i < WL; ++i) blds16(woff[i], rsrc_w, wko, sbase + (i * 256) * 16);          // W rows 32*i + 8*pw .. +7
       }
-      if (ikt >= KT) {
+      if (ikt >= KTc) {
+      } else if (bm) {                       // channel block outer, the rectangle's taps inner; the weight K offset jumps with the tap
+        if (++tkw == bkw1) { tkw = bkw0; if (++tkh == bkh1) { tkh = bkh0; tc += BK; } }
+        wko = (unsigned)((tkh * d.KW + tkw) * d.Cin + tc) * (unsigned)sizeof(T);
       } else if (d.korder && d.lcin >= 0) {  // channel block outer, taps inner (see conv_igemm_ws_kernel)
         wko += (unsigned)d.Cin * (unsigned)sizeof(T);
         if (++tkw == d.KW) { tkw = 0; if (++tkh == d.KH) { tkh = 0; if (++tkd == d.KD) { tkd = 0; tc += BK; wko = (unsigned)tc * (unsigned)sizeof(T); } } }
@@ -252,13 +294,14 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
           if (++tkw == d.KW) { tkw = 0; if (++tkh == d.KH) { tkh = 0; ++tkd; } }
         }
       }
-      if (++ikt == KTT) { ikt = 0; ++itile; if (itile < n_my) prepare_tile(itile); }
+      if (++ikt == KTTc) { ikt = 0; ++itile; if (itile < n_my) prepare_tile(itile); }
     };
 
     if (total > 0) prepare_tile(0);
     if (total > 0) issue(0);
     if (NST == 3 && total > 1) issue(1);
-    int st = 0, gk = 0;
+    int st = 0, gk = 0, gtile = 0;
+    int gKTT = total > 0 ? bsteps(0) + KR : KTT;      // steps of the tile that step g belongs to (the requests run one step ahead of it)
     for (int g = 0; g < total; ++g) {
       // three stages: step g landed, step g+1 may still fly; two stages: the one request in flight is step g
       if (NST == 2 || g + 1 >= total) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -269,7 +312,7 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
       st = st == NST - 1 ? 0 : st + 1;
       // 256 x 256: the multiply waves stage their output tile in the ring stage of the tile's last K step; the workgroup meets once more
       // behind that step (every multiply wave's fragment reads have returned) before the first staging write — see the epilogue
-      if (STAGED) { if (++gk == KTT) { gk = 0; RGBM_BARRIER(); } }
+      if (STAGED) { if (++gk == gKTT) { gk = 0; RGBM_BARRIER(); if (++gtile < n_my) gKTT = bsteps(gtile) + KR; } }
     }
     return;
   }
@@ -320,10 +363,12 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
   T* __restrict__ out = reinterpret_cast<T*>(d.out);
   const T* __restrict__ res = reinterpret_cast<const T*>(d.res);
   auto tile_interior = [&](int pix_tile, int ch_tile) {
+    if (bm) return true;      // (the plan takes only layers whose every tile has the straight-line epilogue; dead rows are not stored)
     return (d.bias == nullptr || bias_lds) && d.m0 + (long long)(pix_tile + 1) * BPIX <= d.M && (ch_tile + 1) * BCH <= d.Cout && d.act != ACT_TANH;
   };
   int st = 0;
   for (int k = 0; k < n_my; ++k) {
+    const int KTk = BIG ? bsteps(k) : KT;      // this tile's K steps (border-class tiles: from its table entry)
     {
       int pt, ct;
       tile_of(k, pt, ct);
@@ -366,7 +411,7 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
         hi = make_uint4(c0.x, c0.y, c1.x, c1.y);
         lo = make_uint4(c0.z, c0.w, c1.z, c1.w);
       };
-      const int KTM = BIG ? KT : KTT;          // 256 x 256: the residual steps follow in their block-diagonal form
+      const int KTM = BIG ? KTk : KTT;         // 256 x 256: the residual steps follow in their block-diagonal form
       for (int kt = 0; kt < KTM; ++kt) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         RGBM_BARRIER();
@@ -472,7 +517,7 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
 #pragma unroll
       for (int a = 0; a < FA; ++a) ldAs(st, 0, a);
       __builtin_amdgcn_sched_barrier(0);
-      for (int kt = 0; kt + 1 < KT; ++kt) {
+      for (int kt = 0; kt + 1 < KTk; ++kt) {
         first3();
         if (M32_SHIFT) {
           // every read of this K tile's stage has been issued: wait for them, meet, and go on into the next K tile's stage
@@ -722,6 +767,19 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
 #pragma unroll
               for (int q = 0; q < NQ; ++q)
                 *reinterpret_cast<uint4*>(stg + (wofs ^ (unsigned)((a * 2 * NQ + q) << 4))) = pk[a][q];
+            if (bm) {
+              // border-class tiles: staging row 4t + (lane>>4) of this half is table row wpix + 32 b + 4t + (lane>>4) of the tile, whose
+              // GEMM row the request waves left in LDS (enter_tile); a dead row is not stored
+              const int* lrow = reinterpret_cast<const int*>(lbias + 2560) + (k & 1) * 256 + wpix + b * 32 + (lane >> 4);
+              char* oc = reinterpret_cast<char*>(out + ch0 + ar * AR * 32) + (lane & 15) * 16;
+#pragma unroll
+              for (int t = 0; t < 8; ++t) {
+                const int m = lrow[4 * t];
+                const uint4 v = *reinterpret_cast<const uint4*>(stg + t * 1024 + (rofs ^ (unsigned)(((4 * t) & 15) << 4)));
+                if (m >= 0) *reinterpret_cast<uint4*>(oc + (long long)m * d.ldo * (long long)sizeof(T)) = v;
+              }
+              return;
+            }
             char* ob = reinterpret_cast<char*>(out + (mrow + b * 32) * d.ldo + ch0 + ar * AR * 32);
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
@@ -802,11 +860,15 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
   }
 }
 
+static std::atomic<long long> g_border_launches{0};
+long long border_launch_count() { return g_border_launches.load(std::memory_order_relaxed); }
+
 // GEMM rows [d.m0, d.M) on tiles of BCH channels x BPIX pixels
 template <typename T, int BPIX, int BCH = 256>
 static int launch_m32_range(ConvDesc d, hipStream_t s) {
   constexpr int NST = BPIX == 256 ? 2 : 3;
-  constexpr size_t LDS = ((size_t)NST * (BCH + BPIX) * 8) * sizeof(uint4) + 2560 * sizeof(float);      // K-tile ring + bias table (up_1's stacked taps: 2304 channels)
+  // K-tile ring + bias table (up_1's stacked taps: 2304 channels) + 256 x 256: the GEMM rows of two border-class tiles
+  constexpr size_t LDS = ((size_t)NST * (BCH + BPIX) * 8) * sizeof(uint4) + 2560 * sizeof(float) + (BPIX == 256 && BCH == 256 ? 2 * 256 * sizeof(int) : 0);
   d.n_pix_tiles = (int)((d.M - d.m0 + BPIX - 1) / BPIX);
   d.n_ch_tiles = (d.Cout + BCH - 1) / BCH;
   const long long ntiles = (long long)d.n_pix_tiles * d.n_ch_tiles;
@@ -820,6 +882,8 @@ static int launch_m32_range(ConvDesc d, hipStream_t s) {
   if (int rc = persistent_grid_cus(&n_cu)) return rc;
   RGBM_REQUIRE(d.ksplit <= 1 || (BPIX == 128 && BCH <= 128 && ntiles * d.ksplit <= 4096 && d.kscratch && d.kcount), "K split: 64 / 128-channel x 128-pixel tiles, one workgroup per (tile, part)");
   const int grid = d.ksplit > 1 ? (int)(ntiles * d.ksplit) : ntiles < n_cu ? (int)ntiles : n_cu;
+  RGBM_REQUIRE(d.btab == nullptr || (BPIX == 256 && BCH == 256 && d.m0 == 0 && grid == d.b_nwg), "border-class table: made for another grid");
+  if (d.btab) g_border_launches.fetch_add(1, std::memory_order_relaxed);
   // profiler rows: 31 / 33 = the 256 x 256 launches (the roofline kernel), 40 / 41 = every other tile of this kernel
   prof_begin_launch(s, BPIX == 256 && BCH == 256 ? (std::is_same<T, bx3_t>::value ? 33 : 31) : (std::is_same<T, bx3_t>::value ? 41 : 40), d.algo_flops, d.algo_bytes);
   hipLaunchKernelGGL((conv_igemm_m32_kernel<T, BPIX, BCH>), dim3((unsigned)grid), dim3(BPIX == 256 ? 768 : 512), LDS, s, d);
@@ -905,6 +969,7 @@ static int launch_m32_tiles128(const ConvDesc& d, int bch, hipStream_t s) {
 template <typename T>
 static int launch_m32_small(ConvDesc d, const ConvPlan& p, hipStream_t s) {
   if (int rc = m32_setup<T>(d, p, s)) return rc;
+  d.btab = nullptr;
   return launch_m32_tiles128<T>(d, p.bch, s);
 }
 
@@ -912,6 +977,7 @@ static int launch_m32_small(ConvDesc d, const ConvPlan& p, hipStream_t s) {
 template <typename T>
 static int launch_m32(ConvDesc d, const ConvPlan& p, hipStream_t s) {
   if (int rc = m32_setup<T>(d, p, s)) return rc;
+  if (!p.border) d.btab = nullptr;           // (the main launch's rows on border-class tiles where the layer brought their table: conv_plan.h)
   if (p.main_rows > 0) {
     ConvDesc m = d;
     m.M = p.main_rows;
@@ -919,6 +985,7 @@ static int launch_m32(ConvDesc d, const ConvPlan& p, hipStream_t s) {
     m.algo_flops = d.algo_flops * frac; m.algo_bytes = d.algo_bytes * frac;
     if (int rc = launch_m32_range<T, 256, 256>(m, s)) return rc;
     d.m0 = m.M;
+    d.btab = nullptr;
     d.algo_flops *= 1.0 - frac; d.algo_bytes *= 1.0 - frac;
   }
   return p.tail_bch ? launch_m32_tiles128<T>(d, p.tail_bch, s) : 0;

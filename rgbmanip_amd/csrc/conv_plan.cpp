@@ -1,5 +1,10 @@
 #include "conv_plan.h"
 
+#include <algorithm>
+#include <functional>
+#include <queue>
+#include <utility>
+
 #include "kernels.h"
 
 namespace rgbm {
@@ -64,7 +69,170 @@ int m32_ksplit_choice(const ConvDesc& d, int flags, long long tiles, int n_cu, i
   return n;
 }
 
+// in-range taps [k0, k1) of output position q along one axis: 0 <= q - pad + k * dil < n
+void tap_range(int q, int pad, int dil, int K, int n, int& k0, int& k1) {
+  k0 = K; k1 = 0;
+  for (int k = 0; k < K; ++k) {
+    const int x = q - pad + k * dil;
+    if (x >= 0 && x < n) { if (k < k0) k0 = k; k1 = k + 1; }
+  }
+  if (k0 > k1) k0 = k1 = 0;
+}
+
+// the classes of one axis: distinct tap ranges in order of first appearance; cls[q] = the class of position q
+struct AxisClasses {
+  std::vector<int> k0, k1, count, cls;
+};
+bool axis_classes(int nq, int pad, int dil, int K, int n, AxisClasses* a) {
+  a->cls.resize(nq);
+  for (int q = 0; q < nq; ++q) {
+    int k0, k1;
+    tap_range(q, pad, dil, K, n, k0, k1);
+    if (k1 == k0) return false;                          // a position that reads padding only: a tile of it would have no K step
+    for (int k = k0; k < k1; ++k) {                      // (an interval by construction; checked because the walker relies on it)
+      const int x = q - pad + k * dil;
+      if (x < 0 || x >= n) return false;
+    }
+    size_t c = 0;
+    while (c < a->k0.size() && !(a->k0[c] == k0 && a->k1[c] == k1)) ++c;
+    if (c == a->k0.size()) { a->k0.push_back(k0); a->k1.push_back(k1); a->count.push_back(0); }
+    a->count[c] += 1;
+    a->cls[q] = (int)c;
+  }
+  return true;
+}
+
+// the shapes the row table exists for: 2-D, stride 1, more than one tap, whole 256 x 256 interior tiles (what launch_m32's main launch takes)
+bool border_shape_ok(const ConvDesc& d, int dtype) {
+  return (dtype == BF16 || dtype == F16) && d.w_finite && d.KD == 1 && d.Di == 1 && d.Dq == 1 && d.pd == 0 && d.sd == 1 && d.sh == 1 && d.sw == 1 &&
+         d.KH * d.KW > 1 && d.KH <= 4 && d.KW <= 4 && d.lcin >= 0 && d.Cin % conv_bk(dtype) == 0 && d.Cout % 256 == 0 && d.ph >= 0 && d.pw >= 0 &&
+         d.dilh >= 1 && d.dilw >= 1 && d.N > 0 && d.M == (long long)d.N * d.Hq * d.Wq;
+}
+
+int popcount_int(int v) { int n = 0; for (; v; v &= v - 1) ++n; return n; }
+
 }  // namespace
+
+// rows of class (i, j) among the GEMM rows [0, main_rows): whole views, then the pixels of the last, partial view in front of its cut
+static long long class_live_rows(const ConvDesc& d, const AxisClasses& ah, const AxisClasses& aw, long long main_rows, int i, int j) {
+  const long long hw = (long long)d.Hq * d.Wq, whole = main_rows / hw, rem = main_rows % hw;
+  const int hr = (int)(rem / d.Wq), wr = (int)(rem % d.Wq);
+  long long h_below = 0, w_below = 0;
+  for (int h = 0; h < hr; ++h) h_below += ah.cls[h] == i;
+  for (int w = 0; w < wr; ++w) w_below += aw.cls[w] == j;
+  return whole * ah.count[i] * aw.count[j] + h_below * aw.count[j] + (ah.cls[hr < d.Hq ? hr : 0] == i && hr < d.Hq ? w_below : 0);
+}
+
+bool border_applies(const ConvDesc& d, int dtype, int flags, long long main_rows) {
+  if ((flags & (DBG_NO_BORDER_TILES | DBG_KORDER_TAPS_OUTER)) || !border_shape_ok(d, dtype)) return false;
+  if (main_rows <= 0 || main_rows > d.M || main_rows % 256) return false;
+  AxisClasses ah, aw;
+  if (!axis_classes(d.Hq, d.ph, d.dilh, d.KH, d.Hi, &ah) || !axis_classes(d.Wq, d.pw, d.dilw, d.KW, d.Wi, &aw)) return false;
+  long long tiles = 0, taps = 0;                         // pixel tiles, and taps summed over them
+  for (size_t i = 0; i < ah.k0.size(); ++i)
+    for (size_t j = 0; j < aw.k0.size(); ++j) {
+      const long long t = (class_live_rows(d, ah, aw, main_rows, (int)i, (int)j) + 255) / 256;
+      tiles += t;
+      taps += t * (ah.k1[i] - ah.k0[i]) * (aw.k1[j] - aw.k0[j]);
+    }
+  // a tap saved: fewer K steps in all than the row-major tiles walk (dead rows of small classes can cost more than the classes save)
+  return taps < (main_rows / 256) * (long long)d.ntaps && tiles < (1ll << 20);
+}
+
+bool plan_border(const ConvDesc& d, int dtype, int flags, long long main_rows, int n_wg, BorderPlan* out) {
+  if (n_wg <= 0 || !border_applies(d, dtype, flags, main_rows)) return false;
+  AxisClasses ah, aw;
+  axis_classes(d.Hq, d.ph, d.dilh, d.KH, d.Hi, &ah);
+  axis_classes(d.Wq, d.pw, d.dilw, d.KW, d.Wi, &aw);
+  BorderPlan p;
+  p.n_wg = n_wg;
+  p.n_ch = d.Cout / 256;
+  p.steps_per_tap = d.Cin / conv_bk(dtype);
+  const bool dense_out = d.osd == 1 && d.osh == 1 && d.osw == 1 && d.opd == 0 && d.oph == 0 && d.opw == 0 && d.Dq == d.Do && d.Hq == d.Ho && d.Wq == d.Wo;
+  p.kr = (dense_out && d.res_mode == RES_PRE_ACT && d.res != nullptr) ? 256 / conv_bk(dtype) : 0;      // (plan_conv's ident_ok: the main launch adds the residual by identity steps)
+  const int nw = (int)aw.k0.size();
+  std::vector<int> of_class(ah.k0.size() * nw, -1);
+  for (int h = 0; h < d.Hq; ++h)                         // classes in order of first appearance, row-major
+    for (int w = 0; w < d.Wq; ++w) {
+      int& c = of_class[ah.cls[h] * nw + aw.cls[w]];
+      if (c < 0) {
+        c = (int)p.classes.size();
+        BorderClass bc = {};
+        bc.kh0 = ah.k0[ah.cls[h]]; bc.kh1 = ah.k1[ah.cls[h]]; bc.kw0 = aw.k0[aw.cls[w]]; bc.kw1 = aw.k1[aw.cls[w]];
+        for (int kh = bc.kh0; kh < bc.kh1; ++kh)
+          for (int kw = bc.kw0; kw < bc.kw1; ++kw) bc.mask |= 1 << (kh * d.KW + kw);
+        bc.n_pix = ah.count[ah.cls[h]] * aw.count[aw.cls[w]];
+        p.classes.push_back(bc);
+      }
+    }
+  int pix0 = 0;
+  for (BorderClass& bc : p.classes) { bc.pix0 = pix0; pix0 += bc.n_pix; }
+  p.pix.assign((size_t)d.Hq * d.Wq, 0);
+  {
+    std::vector<int> fill(p.classes.size(), 0);
+    for (int h = 0; h < d.Hq; ++h)
+      for (int w = 0; w < d.Wq; ++w) {
+        const int c = of_class[ah.cls[h] * nw + aw.cls[w]];
+        p.pix[p.classes[c].pix0 + fill[c]++] = h * d.Wq + w;
+      }
+  }
+  // Only the GEMM rows [0, main_rows) are taken: the rows behind them stay with the tail launch, whose 128-pixel tiles they ran on before
+  // (its ReLU writes +0 where this kernel's writes -0: a row keeps its bits only on the tile shape it had).
+  const long long hw = (long long)d.Hq * d.Wq;
+  p.total_steps = 0;
+  for (size_t c = 0; c < p.classes.size(); ++c) {
+    BorderClass& bc = p.classes[c];
+    bc.row0 = (long long)p.rows.size();
+    for (long long v = 0; v * hw < main_rows; ++v)        // row r of a class: view r / n_pix, class pixel r % n_pix; the last view stops at the cut
+      for (int i = 0; i < bc.n_pix; ++i) {
+        const long long m = v * hw + p.pix[bc.pix0 + i];
+        if (m < main_rows) p.rows.push_back((int)m);
+      }
+    const long long live = (long long)p.rows.size() - bc.row0;
+    p.rows.resize((size_t)(bc.row0 + (live + 255) / 256 * 256), -1);
+    if (p.rows.size() >= (1u << 30)) return false;
+    const int steps = popcount_int(bc.mask) * p.steps_per_tap + p.kr;
+    for (long long t = 0; t < (live + 255) / 256; ++t)
+      for (int ch = 0; ch < p.n_ch; ++ch) {
+        p.tiles.push_back(BorderTile{(int)c, ch, bc.mask, steps, bc.row0 + t * 256});
+        p.total_steps += steps;
+      }
+  }
+  p.parent_steps = (main_rows / 256) * p.n_ch * (long long)(d.ntaps * p.steps_per_tap + p.kr);
+  // The tiles in the order of the views they cover (a tile's middle row: view (row - class row0 + 128) / n_pix), each to the workgroup
+  // with the fewest steps so far; among equals the next in XCD-major order (workgroups b, b + 8, .. share an XCD), so that a pixel tile's
+  // channel tiles and its neighbours run on one L2 at about the same time.  View order, because the classes of a view gather the same
+  // input pixels: dealt longest first (all interior tiles, then the edges, then the corners) every class sweeps the whole input again,
+  // long after the last one did (measured: profiles/border_tiles_ab.txt).  The last n_wg tiles go longest first, which evens the ends.
+  std::vector<int> by_steps(p.tiles.size());
+  for (size_t i = 0; i < by_steps.size(); ++i) by_steps[i] = (int)i;
+  auto mid_view = [&](int i) { const BorderClass& bc = p.classes[p.tiles[i].cls]; return (double)(p.tiles[i].row0 - bc.row0 + 128) / bc.n_pix; };
+  std::stable_sort(by_steps.begin(), by_steps.end(), [&](int a, int b) { return mid_view(a) < mid_view(b); });
+  if ((int)by_steps.size() > n_wg)
+    std::stable_sort(by_steps.end() - n_wg, by_steps.end(), [&](int a, int b) { return p.tiles[a].steps > p.tiles[b].steps; });
+  typedef std::pair<long long, std::pair<int, int>> Load;      // (steps so far, (XCD-major rank, workgroup))
+  std::priority_queue<Load, std::vector<Load>, std::greater<Load>> q;
+  const int per_xcd = (n_wg + 7) / 8;
+  for (int b = 0; b < n_wg; ++b) q.push(Load(0, std::make_pair((b & 7) * per_xcd + (b >> 3), b)));
+  std::vector<std::vector<int>> mine(n_wg);
+  for (int i : by_steps) {
+    Load l = q.top();
+    q.pop();
+    mine[l.second.second].push_back(i);
+    l.first += p.tiles[i].steps;
+    q.push(l);
+  }
+  p.max_wg_steps = 0;
+  p.wg_off.assign(1, 0);
+  for (int b = 0; b < n_wg; ++b) {
+    long long s = 0;
+    for (int i : mine[b]) { p.order.push_back(i); s += p.tiles[i].steps; }
+    p.wg_off.push_back((int)p.order.size());
+    if (s > p.max_wg_steps) p.max_wg_steps = s;
+  }
+  *out = std::move(p);
+  return true;
+}
 
 int plan_conv(const ConvDesc& d, int dtype, const ConvTuning& t, ConvPlan* out) {
   RGBM_REQUIRE(d.M > 0 && d.M < (1ll << 31), "conv M out of range");
@@ -160,6 +328,7 @@ int plan_conv(const ConvDesc& d, int dtype, const ConvTuning& t, ConvPlan* out) 
       }
       p.main_rows = Pm * 256;
       p.identity_residual = ident_ok;
+      p.border = p.main_rows > 0 && p.korder == 1 && uni && border_applies(d, dtype, f, p.main_rows);
       p.tail_bch = p.main_rows == d.M ? 0 : 256;
       // the rest: 128-pixel tiles, channels cut so that the tiles fill (at most) one round of the grid (DBG_M32_TAILS_R5: 256 channels)
       const long long pt = (d.M - p.main_rows + 127) / 128;

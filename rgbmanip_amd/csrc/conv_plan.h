@@ -2,6 +2,8 @@
 // of its arguments (no HIP runtime call, no global read), so it can be asked without a GPU (rgbm_conv_plan in rgbm.h) and tested
 // directly; launch_conv (conv_igemm_glds.hip) gathers the ConvTuning, calls it and launches what it says.
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 namespace rgbm {
@@ -36,7 +38,43 @@ struct ConvPlan {
   int ksplit;              // K parts the launch asks for (1 = none); the executor runs unsplit where the stream has no scratch
   bool identity_residual;  // the m32 kernels add the residual through identity K steps (else in the epilogue)
   int korder, buf_ok;      // ConvDesc fields of the same names
+  bool border;             // CONV_M32: the main launch's rows on class-pure 256 x 256 tiles from a row table (plan_border); the launcher
+                           // runs them row-major where the layer has no table for this shape yet (a capture in progress)
 };
+
+// ---- border-class tiles of a dilated 2-D conv (CONV_M32, ConvPlan::border) ------------------------------------------------------------
+// Output pixels whose set of in-range taps is the same form a border class (3 x 3, pad = dil: interior, four edges, four corners).  A
+// tile is 256 rows of ONE class taken across views, so it walks only the class's taps: every K step of a tap that reads nothing but
+// padding is gone, and every step that runs is the step the row-major tiles run.  The in-range taps of a class are a rectangle
+// [kh0, kh1) x [kw0, kw1) of the kernel (in-range positions along an axis are an interval).
+struct BorderClass {
+  int kh0, kh1, kw0, kw1;  // in-range taps
+  int mask;                // bit kh * KW + kw
+  int n_pix;               // pixels of a view in this class
+  int pix0;                // its first entry in BorderPlan::pix
+  long long row0;          // its first table row; it owns its live rows rounded up to whole tiles, the last ones dead
+};
+struct BorderTile {
+  int cls, ch;             // class, channel tile
+  int mask;                // the class's tap mask
+  int steps;               // K steps: popcount(mask) * Cin / BK, + the residual steps
+  long long row0;          // first table row
+};
+struct BorderPlan {
+  int n_wg, n_ch, kr, steps_per_tap;
+  std::vector<BorderClass> classes;
+  std::vector<int> pix;           // per class, the pixels h * Wq + w of a view in row-major order
+  std::vector<BorderTile> tiles;  // class-major, rows ascending, channel tiles innermost
+  std::vector<int> order;         // tile indices, workgroup-major: workgroup b runs order[wg_off[b] .. wg_off[b + 1]) in this order
+  std::vector<int> wg_off;        // n_wg + 1
+  std::vector<int> rows;          // table row -> GEMM row m = (view * Hq + h) * Wq + w < main_rows, -1 = dead
+  long long total_steps, parent_steps, max_wg_steps;      // parent_steps: every 256-row tile of the row-major order walks every tap
+};
+// Whether the GEMM rows [0, main_rows) of d (the main launch of CONV_M32) run on border-class tiles: cheap (O(Hq + Wq)), called by
+// plan_conv per launch.
+bool border_applies(const ConvDesc& d, int dtype, int flags, long long main_rows);
+// The whole table for n_wg workgroups.  false: declined (border_applies says no).  Pure: no HIP call, no global read.
+bool plan_border(const ConvDesc& d, int dtype, int flags, long long main_rows, int n_wg, BorderPlan* out);
 
 // K-split scratch of a stream: fp32 partial accumulators and arrival counters (m32_ksplit_buffers); a split that would not fit is not planned
 constexpr size_t kM32SplitFloats = 8u << 20, kM32SplitCounters = 16384;

@@ -174,9 +174,10 @@ enum DebugFlag {
   DBG_PSP_STAGE_R5 = 1024, DBG_POINT_MLP_R5 = 2048, DBG_TILE_CONV0 = 4096, DBG_NO_KSPLIT = 16384, DBG_L2_SLIM_TILE = 32768,
   DBG_WS_128x256 = 65536, DBG_NO_SLIM64 = 262144, DBG_KORDER_TAPS_OUTER = 1 << 20, DBG_SWEEP_ALT_BLEND = 1 << 21, DBG_SWEEP_DOT2 = 1 << 22,
   DBG_PP_ONE_KERNEL = 1 << 23, DBG_NO_SLIM_SMALL = 1 << 24, DBG_PP_GENERIC_SELECT = 1 << 25, DBG_PP_GUARD = 1 << 26, DBG_GLOBAL_ADDR = 1 << 27,
-  DBG_SWEEP_PER_TILE = 1 << 28, DBG_SPARSE_TAIL_R5 = 1 << 29, DBG_M32_TAILS_R5 = 1 << 30, DBG_POSE_MLP_R6 = 1 << 19,
+  DBG_SWEEP_PER_TILE = 1 << 28, DBG_SPARSE_TAIL_R5 = 1 << 29, DBG_M32_TAILS_R5 = 1 << 30, DBG_POSE_MLP_R6 = 1 << 19, DBG_NO_BORDER_TILES = 32,
 };
 extern int g_debug_flags;
+long long border_launch_count();      // launches of conv_igemm_m32_kernel on border-class tiles since the library was loaded (conv_igemm_glds.hip)
 extern long long g_ws_min_rows;
 extern int g_tuning_version;
 extern int g_gemm_kernel;

@@ -1,8 +1,10 @@
 #include "layers.h"
+#include "conv_plan.h"
 #include "kernels.h"
 
 #include <string.h>
 
+#include <array>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -136,6 +138,14 @@ int conv_pack_geom(const ConvGeom& g, int dtype, int Cin_pad, int Cout_pad, int 
   return 0;
 }
 
+// Device tables of a layer's border-class tiles (plan_border), keyed by what they depend on.  Uploaded at the first launch of a shape,
+// never per call; the layer owns them.
+struct BorderTables {
+  struct Entry { DevBuf buf; int n_wg = 0, b_ent = 0, b_rows = 0; };
+  std::mutex mu;
+  std::map<std::array<long long, 7>, Entry> per_shape;      // (device, N, Hi, Wi, workgroups, residual steps, main_rows)
+};
+
 int ConvLayer::init(int dtype_, const ConvGeom& g_, const float* w, const float* bias_h, const float* bn_scale,
                     const float* bn_shift, int Cin_pad_, int Cout_pad_) {
   g = g_;
@@ -174,6 +184,11 @@ int ConvLayer::init(int dtype_, const ConvGeom& g_, const float* w, const float*
         for (int t = 0; t < pc.ntaps; ++t)
           packed[(size_t)o * pc.Kpad + (size_t)t * Cin_pad + c] = w[((long long)o * g.Cin + c) * kvol + t] * sc;
     }
+    // finite in every storage type: within bf16's largest value (f16 saturates on upload; a NaN fails the comparison)
+    w_finite = true;
+    for (float v : packed)
+      if (!((v < 0.f ? -v : v) <= 3.3895313892515355e38f)) { w_finite = false; break; }
+    border = std::make_shared<BorderTables>();
     return finish(pc, packed);
   }
 
@@ -246,11 +261,52 @@ int ConvLayer::build_desc(ConvDesc& d, const void* in, void* out, int N, int Di,
   d.bias_stride = bias_override ? bias_stride : 0;
   d.res_mode = res ? res_mode : RES_NONE;
   d.out_f32 = (out_plain_f32 && dtype == BF16X3) ? 1 : 0;
+  d.w_finite = w_finite ? 1 : 0;
   // algorithmic work: real (unpadded) channels, every tap counted (zero padding included, as usual)
   d.algo_flops = 2.0 * (double)d.M * g.Cout * (double)pc.ntaps * g.Cin;
   d.algo_bytes = ((double)d.M * g.Cout + (cls == 0 ? (double)N * Di * Hi * Wi * g.Cin : 0.0) +
                   (res ? (double)d.M * g.Cout : 0.0)) * (double)dtype_size(dtype) +
                  (double)g.Cout * pc.ntaps * g.Cin * (double)dtype_size(dtype);
+  return 0;
+}
+
+int ConvLayer::attach_border(ConvDesc& d, hipStream_t s) const {
+  if (!border || !w_finite || g.transposed || dtype == F32 || g.KH * g.KW == 1) return 0;
+  ConvTuning t;
+  ConvPlan p;
+  if (int rc = conv_tuning(0, &t)) return rc;
+  if (int rc = plan_conv(d, dtype, t, &p)) return rc;
+  if (p.kernel != CONV_M32 || !p.border) return 0;
+  int dev = 0;
+  RGBM_CHECK_HIP(hipGetDevice(&dev));
+  const std::array<long long, 7> key = {dev, d.N, d.Hi, d.Wi, t.n_cu, p.identity_residual ? 1 : 0, p.main_rows};
+  std::lock_guard<std::mutex> lock(border->mu);
+  auto it = border->per_shape.find(key);
+  if (it == border->per_shape.end()) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return 0;      // (no upload inside a capture)
+    BorderPlan bp;
+    if (!plan_border(d, dtype, t.flags, p.main_rows, t.n_cu, &bp)) return 0;
+    std::vector<int> tab(bp.wg_off);
+    BorderTables::Entry e;
+    e.n_wg = bp.n_wg;
+    e.b_ent = (int)tab.size();
+    for (int i : bp.order) {
+      const BorderTile& bt = bp.tiles[i];
+      const BorderClass& bc = bp.classes[bt.cls];
+      tab.push_back((int)bt.row0);
+      tab.push_back(bt.steps - bp.kr);
+      tab.push_back(bc.kh0 | bc.kh1 << 4 | bc.kw0 << 8 | bc.kw1 << 12 | bt.ch << 16);
+      tab.push_back(0);
+    }
+    e.b_rows = (int)tab.size();
+    tab.insert(tab.end(), bp.rows.begin(), bp.rows.end());
+    RGBM_CHECK_HIP(hipMalloc(e.buf.out(), tab.size() * sizeof(int)));
+    RGBM_CHECK_HIP(hipMemcpy(e.buf.get(), tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    it = border->per_shape.emplace(key, std::move(e)).first;
+  }
+  d.btab = it->second.buf.get<int>();
+  d.b_nwg = it->second.n_wg; d.b_ent = it->second.b_ent; d.b_rows = it->second.b_rows;
   return 0;
 }
 
@@ -260,6 +316,7 @@ int ConvLayer::run(const void* in, void* out, int N, int Di, int Hi, int Wi, int
   for (int cls = 0; cls < nclass; ++cls) {
     ConvDesc d;
     if (int rc = build_desc(d, in, out, N, Di, Hi, Wi, ldo, res, res_mode, bias_override, bias_stride, cls, out_plain_f32)) return rc;
+    if (int rc = attach_border(d, s)) return rc;
     if (int rc = launch_conv(d, dtype, s)) return rc;
   }
   return 0;

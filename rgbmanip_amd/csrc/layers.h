@@ -2,6 +2,7 @@
 // ConvDesc construction for the generic implicit-GEMM kernel.
 #pragma once
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -65,6 +66,8 @@ void conv_out_dims(const ConvGeom& g, int Di, int Hi, int Wi, int& Do, int& Ho, 
 void conv_desc_geom(ConvDesc& d, const ConvGeom& g, const PackedConv& pc, int Cin_pad, int Cout_pad, int N, int Di, int Hi, int Wi,
                     int ldo, int cls);      // zeroes d, then every field that is not a pointer
 
+struct BorderTables;              // device tables of a layer's border-class tiles, one per launch shape (layers.cpp; conv_plan.h)
+
 struct ConvLayer {
   ConvGeom g;
   int dtype = F32;
@@ -72,6 +75,8 @@ struct ConvLayer {
   int Cout_pad = 0;              // physical output channels written (multiple of 4)
   DevBuf bias;                   // [Cout_pad] fp32 or null
   std::vector<PackedConv> packs; // 1, or 8 for transposed
+  bool w_finite = false;         // no packed weight is NaN / inf in the storage type (ConvDesc::w_finite), checked once in init
+  std::shared_ptr<BorderTables> border;      // filled by run(): uploaded once per (device, views, map size), freed with the layer
 
   // weights: [Cout][Cin][KD][KH][KW] (or [Cin][Cout][3][3][3] when transposed), optional per-Cout scale/shift
   // (folded BN) and bias.  Cin_pad: physical channel count of the input tensor.
@@ -91,6 +96,9 @@ struct ConvLayer {
                    bool allow_fuse, bool* fused, hipStream_t s, bool out2_plain_f32 = false) const;
   int build_desc(ConvDesc& d, const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res, int res_mode,
                  const float* bias_override, int bias_stride, int cls, bool out_plain_f32 = false) const;
+  // points d at this layer's border-class table where plan_conv asks for one (ConvPlan::border); no table yet and `s` is being captured:
+  // d stays as it is and the launch runs its row-major tiles (same bits)
+  int attach_border(ConvDesc& d, hipStream_t s) const;
 };
 
 // PSPUpsample (x2 bilinear align_corners -> conv3x3 pad 1 + bias -> activation; pspnet.py:100-107) as a 1x1 GEMM at the low
