@@ -112,8 +112,51 @@ int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views);
  * FMAs and multiplies with f16 MFMAs; c0 and everything behind it stay bf16.  Features beyond +-65504 saturate, as in an fp16 net; 0 =
  * bf16 feature map and the fp32 blend of rounds 1-4.  The "feat" tap of rgbm_adapose_fetch converts from whichever form was written.
  * With 1 the one-kernel up_3 + `final` also runs its tap combination, PReLU and `final` in packed f16: faster, and closer to fp32).
- * Set before querying the workspace size. */
+ * Set before querying the workspace size.
+ * Where an option applies only to some storage types, cost_impl values or weight packs, the rule is stated once, in code: the paths[]
+ * entry of rgbm_forward_paths (below) named here.  fuse_final: [4].  sparse_tail: [12].  cost_impl: [7] [8] [13].  igemm_conv6: [9].
+ * upconv: [2] [3] [4].  stem: [0].  sparse_dec: [10] [11].  sweep_f16: [5] and [8].  view2_heads: facts [26]. */
 int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value);
+/* Path selection: which of its alternative kernel paths a forward runs, decided in one pure function (csrc/forward_paths.cpp) of plain
+ * ints.  rgbm_forward_paths never touches the HIP runtime (works without a GPU): facts [n_rows][RGBM_PATH_FACT_INTS] ->
+ * paths [n_rows][RGBM_PATH_INTS], row by row.
+ *   facts: [0] arch 0 v5 / 1 baseline  [1] dtype (RGBM_F32 ..)  [2] norm_mode
+ *     [3] cost_impl [4] sparse_tail [5] sparse_dec [6] sweep_f16 [7] igemm_conv6 [8] fuse_final [9] upconv [10] stem [11] view2_heads: the
+ *     options of rgbm_adapose_set_option  [12] pose_x3 (1: split-pair nets run the per-point pose layers on split pairs)
+ *     [13] the rgbm_debug_flags word (negative: the process's current one, as rgbm_conv_plan takes it); read here: 1024 (PSP stage of rounds 1-5), 2048 (per-layer point MLP), 4096 (halo-tile conv0
+ *     instead of the depth-sweeping kernels), 524288 (per-layer pose MLP)
+ *     0 / 1, what the handle's create built:  [14] one-kernel stem pack  [15] depth-sweeping conv0 pack  [16] its f16 form (bf16 nets whose
+ *     conv0 weights f16 can hold)  [17] conv11 split-pair pack of the sparse tail  [18] conv11 in-plane-tap pack  [19] one-kernel up_3 + final
+ *     [20] its f16 form  [21] point MLP table  [22] the four PSP 1x1 layers fit the one-launch stage  [23] the four per-point pose layers
+ *     and the point count fit the fused pose MLP
+ *     the call:  [24] dense  [25] views entering the PSPNet  [26] views that get heads  [27] points per view
+ *   paths: [0] stem: 0 copy + implicit-GEMM conv + pool, 1 one kernel (option stem and [14])
+ *     [1] PSP stage: 0 pooling + four implicit GEMMs, 1 pooling and the 50 cells per view in one launch (at most 32 views and [22]),
+ *         2 rounds 1-5 (flag 1024)
+ *     [2] up_1  [3] up_2: 1 = 1x1 GEMM at the low resolution + tap combination (upconv bit 0 / 1), 0 = x2 resize + 3x3 conv
+ *     [4] up_3 + final: 2 one kernel from the half-resolution tensor (upconv bit 2 and [19]), else 1 `final` inside up_3's kernel
+ *         (fuse_final) or 0 two launches
+ *     [5] feature map: 0 the storage type; 1 plain fp32 only (split pairs, cost_impl 3, [15], norm_mode 0, not flag 4096: nothing reads
+ *         the split-pair map); 2 f16 (bf16, sweep_f16, cost_impl 3, [16], norm_mode 0, not flag 4096, paths [4] = 2 and [20])
+ *     [6] 1 = the split-pair map is copied to plain fp32 by a launch of its own (split pairs without [5] = 1)
+ *     [7] cost regularisation: 0 none (baseline), 1 per-sample BatchNorm3d on generic layers (norm_mode 1), 2 generic implicit GEMM
+ *         (cost_impl 0), 3 halo tiles
+ *     [8] conv0: 0 the layer of body 1 / 2 on the materialised volume; in body 3: 1 halo tile on the volume (cost_impl 1), 2 halo tile with
+ *         the plane sweep fused in, 3 depth-sweeping kernel (16-bit storage, cost_impl 3, [15], not flag 4096), 4 the same on f16 features
+ *         ([5] = 2), 5 split-pair depth-sweeping kernel (same conditions)
+ *     [9] 1 = conv6 on the implicit-GEMM kernel (body 3, cost_impl 3, 16-bit or split-pair storage, igemm_conv6)
+ *     [10] tile masks: 0 none, 1 conv7 / conv9, 2 conv1 .. conv5 too (sparse_dec, [12], cost_impl 3, [15], not flag 4096)
+ *     [11] 1 = the depth-sweeping conv0 walks the list of needed tiles ([10] = 2)
+ *     [12] 1 = sparse tail (sparse_tail, not a dense call, body 3, cost_impl 3, 16-bit storage or split pairs with [17])
+ *     [13] 1 = the workspace holds the plane-sweep volume (v5 and not (cost_impl >= 2 and norm_mode 0))  [14] ... the BatchNorm scratch (body 1)
+ *     [15] point MLP: 1 one launch ([21], not flag 2048, [26] x [27] a multiple of 64; the baseline network: always), 0 per layer
+ *     [16] pose MLP: 1 two fused launches (bf16 nets, [23], not flag 524288), 0 per layer
+ * rgbm_adapose_paths: the handle's own facts for a call of B poses (dense = 1: a rgbm_adapose_forward_dense call) under the process's
+ * current debug flags, and the paths a forward issued now would run.  Launches nothing. */
+#define RGBM_PATH_FACT_INTS 28
+#define RGBM_PATH_INTS 17
+int rgbm_forward_paths(const int32_t* facts, int n_rows, int32_t* paths);
+int rgbm_adapose_paths(rgbm_adapose_t* h, int B, int dense, int32_t* facts_out, int32_t* paths_out);
 int rgbm_adapose_workspace_bytes(rgbm_adapose_t* h, int B, size_t* bytes);
 /* Seeded Dropout2d of PSPNet (pspnet.py:122,150,154: p = 0.15 after up_1 and after up_2), active in the reference as shipped
  * (interface_v5.py:39-56 never calls .eval()).  p = 0 is off (the default: no kernel changes); otherwise 0 < p < 1.  Every

@@ -110,6 +110,8 @@ SIGNATURES = {
     "rgbm_adapose_destroy": (_i, [_vp]),
     "rgbm_adapose_set_chunk": (_i, [_vp, _i]),
     "rgbm_adapose_set_option": (_i, [_vp, C.c_char_p, _i]),
+    "rgbm_forward_paths": (_i, [C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
+    "rgbm_adapose_paths": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rgbm_adapose_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),
     "rgbm_adapose_set_dropout": (_i, [_vp, _f, C.c_uint64]),
     "rgbm_adapose_dropout_masks": (_i, [_vp, _i, _vp]),

@@ -5,6 +5,7 @@
 // so its footprint is bounded, the second half of pose_mlp2's first layer (global feature) turned into a
 // per-view bias.  Views are ordered v = side*B + b (all view-1 images, then all view-2 images).
 #include "adapose.h"
+#include "../../include/rgbm.h"
 #include "cost3d.h"
 #include "sample_stats.h"
 #include "view_fusion.h"
@@ -19,8 +20,6 @@ static const int kLayerBlocks[4] = {3, 4, 6, 3};
 static const int kLayerStride[4] = {1, 2, 1, 1};
 static const int kLayerDil[4] = {1, 1, 2, 4};
 static const int kPspBins[4] = {1, 2, 3, 6};
-static const int kPspSmallViews = 32;      // up to this many views the PSP stage pools and multiplies its 50 cells per view in one launch (see AdaPose::pspnet)
-
 
 static const HostTensor* find(const StateDict& sd, const std::string& name) {
   auto it = sd.find(name);
@@ -291,25 +290,30 @@ int AdaPose::create_pose(const StateDict& sd) {
   return 0;
 }
 
-bool AdaPose::feat_f32_only() const {
-  return dtype == BF16X3 && cost_impl == 3 && sweep_w && norm_mode == 0 && !(g_debug_flags & DBG_TILE_CONV0);
-}
+static_assert(F32 == RGBM_F32 && BF16 == RGBM_BF16 && F16 == RGBM_F16 && BF16X3 == RGBM_BF16X3, "forward_paths.cpp reads DType by its C-ABI values");
+static_assert(PATH_FLAG_PSP_STAGE_R5 == DBG_PSP_STAGE_R5 && PATH_FLAG_POINT_MLP_R5 == DBG_POINT_MLP_R5 && PATH_FLAG_TILE_CONV0 == DBG_TILE_CONV0 &&
+              PATH_FLAG_POSE_MLP_R6 == DBG_POSE_MLP_R6, "forward_paths.h names the DebugFlag bits it reads");
 
-// bf16 nets: what `final` writes and what the plane sweep and the point heads read is f16 - same bytes, three more mantissa bits, and the
-// sweep's blend becomes four v_pk_fma_f16 per dword.  Needs the one-kernel up_3 + final (its epilogue knows the f16 form) and the
-// depth-sweeping conv0 (the halo-tile / volume paths read the storage type).
-bool AdaPose::feat_f16() const {
-  return dtype == BF16 && sweep_f16 != 0 && cost_impl == 3 && sweep_w_f16 && norm_mode == 0 && !(g_debug_flags & DBG_TILE_CONV0) && (upconv & 4) &&
-         tail.ready() && tail.f16_ready();
-}
-
-bool AdaPose::sparse_tail_active(bool dense) const {
-  const bool b16 = dtype_size(dtype) == 2;
-  return !dense && sparse_tail && norm_mode == 0 && cost_impl == 3 && (b16 || (dtype == BF16X3 && w11_x3));
-}
-
-bool AdaPose::sparse_active(bool dense) const {
-  return sparse_dec != 0 && sparse_tail_active(dense) && sweep_w && !(g_debug_flags & DBG_TILE_CONV0);
+// the only reader of the options and the debug flags behind set_option: everything below an entry point reads the ForwardPaths made of these
+PathFacts AdaPose::path_facts(int B, bool dense) const {
+  PathFacts f = {};
+  f.arch = arch; f.dtype = dtype; f.norm_mode = norm_mode;
+  f.cost_impl = cost_impl; f.sparse_tail = sparse_tail; f.sparse_dec = sparse_dec; f.sweep_f16 = sweep_f16; f.igemm_conv6 = igemm_conv6;
+  f.fuse_final = fuse_final; f.upconv = upconv; f.stem = stem; f.view2_heads = view2_heads; f.pose_x3 = pose_x3;
+  f.flags = g_debug_flags;
+  f.stem_w = (bool)stem_w; f.sweep_w = (bool)sweep_w; f.sweep_w_f16 = (bool)sweep_w_f16; f.w11_x3 = (bool)w11_x3; f.w11_taps = (bool)w11_taps;
+  f.tail_ready = tail.ready(); f.tail_f16_ready = tail.f16_ready(); f.pmlp_table = (bool)pmlp_table;
+  f.psp_shape_ok = 1;
+  for (const ConvLayer& L : psp)
+    f.psp_shape_ok &= L.packs.size() == 1 && L.packs[0].Kpad == 512 && L.Cout_pad == 128 && !L.bias;
+  auto pose_layer_ok = [](const ConvLayer& L, int cin, int cout) {
+    return L.dtype == F16 && L.packs.size() == 1 && L.packs[0].ntaps == 1 && L.Cin_pad == cin && L.Cout_pad == cout && L.g.act == ACT_RELU &&
+           L.packs[0].Kpad >= cin && L.bias;
+  };
+  f.pose_shape_ok = pose_mlp_fits(n_pts) && pose_layer_ok(pm1[0], 96, 128) && pose_layer_ok(pm1[1], 128, 128) && pose_layer_ok(pm2[0], 128, 256) &&
+                    pose_layer_ok(pm2[1], 256, 256);
+  f.dense = dense; f.V = 2 * B; f.Vh = view2_heads ? 2 * B : B; f.n_pts = n_pts;
+  return f;
 }
 
 int AdaPose::chunk_poses(int B) const {
@@ -323,7 +327,7 @@ int AdaPose::chunk_views(int V) const {
 }
 
 // Shared by workspace_bytes() (base == nullptr) and forward(): identical allocation order => identical offsets.
-int AdaPose::plan(int B, Arena& A, Buffers& bf) const {
+int AdaPose::plan(int B, const ForwardPaths& p, Arena& A, Buffers& bf) const {
   const int V = 2 * B, P = n_pts, S = img;
   const size_t es = dtype_size(dtype);
   const size_t VP = (size_t)V * P;
@@ -389,30 +393,42 @@ int AdaPose::plan(int B, Arena& A, Buffers& bf) const {
   const int Vc = chunk_views(V);
   const int D = n_depth;
   const size_t vox = (size_t)D * S * S;
-  bf.vol = (cost_impl >= 2 && norm_mode == 0) ? nullptr : A.alloc((size_t)Vc * vox * 32 * es);   // fused-warp conv0 never materialises it
-  bf.bn_scratch = norm_mode == 1 ? A.alloc(bn_scratch_bytes(Vc)) : nullptr;
+  bf.vol = p.vol ? A.alloc((size_t)Vc * vox * 32 * es) : nullptr;
+  bf.bn_scratch = p.bn_scratch ? A.alloc(bn_scratch_bytes(Vc)) : nullptr;
   for (int l = 0; l < kCost3dLayers; ++l) bf.c3[l] = A.alloc(cost3d_out_elems(l, Vc, D, S) * es);
   A.release(m0);
   return 0;
 }
 
-size_t AdaPose::workspace_bytes(int B) const {
+static size_t plan_bytes(const AdaPose& n, int B, const ForwardPaths& p) {
   Arena A(nullptr, 0);
-  Buffers bf;
-  plan(B, A, bf);
+  AdaPose::Buffers bf;
+  n.plan(B, p, A, bf);
   return A.peak + 256;
+}
+
+size_t AdaPose::workspace_bytes(int B) const { return plan_bytes(*this, B, paths(B)); }
+
+int AdaPose::open_workspace(int B, const ForwardPaths& p, void* workspace, size_t workspace_size, size_t head, const char* pre, const char* post,
+                            Buffers& bf) const {
+  RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
+  const size_t need = head + plan_bytes(*this, B, p);
+  RGBM_REQUIRE(workspace_size >= need, std::string(pre) + "workspace too small: need " + std::to_string(need) + post);
+  Arena A((char*)workspace + head, workspace_size - head);
+  return plan(B, p, A, bf);
 }
 
 // samples > 1 (forward_samples): Vout = samples x 2B views leave the PSPNet, and in front of the first Dropout2d site only the 2B input views
 // differ.  Everything up to up_1's stacked GEMM runs on those 2B views; up_1's tap combination then runs once per sample and view half,
 // writing the B views of that block where the tiled batch has them (view rows half * samples * B + k * B) with that block's mask rows.
-int AdaPose::pspnet(const Buffers& bf, int Vout, const float* img1, const float* img2, const Call& call, int samples) const {
+int AdaPose::pspnet(const Buffers& bf, int Vout, const float* img1, const float* img2, const Call& call, const ForwardPaths& p, int samples) const {
   const int S = img;
   int V = Vout / samples;            // views of the shared prefix; all Vout behind up_1's tap combination
   hipStream_t s = call.stream;
   const float* drop = call.dropout != Dropout::None ? drop_masks.get<float>() : nullptr;      // factors [V][kDropoutPerView]
   int H = S / 2, W = S / 2;
-  if (stem && stem_w) {
+  if (p.stem == STEM_FUSED) {
     // NCHW fp32 images -> conv1 + ReLU + max-pool in one kernel (no padded copy, no 112 x 112 x 64 tensor)
     // img2 == nullptr (features()): all V views, any V >= 1, lie in img1
     if (img2 == nullptr) { if (int rc = launch_stem_views(dtype, img1, stem_w.get(), bf.lb[0], V, S, s)) return rc; }
@@ -448,7 +464,7 @@ int AdaPose::pspnet(const Buffers& bf, int Vout, const float* img1, const float*
   }
   const void* f = bf.lb[xi];                    // [V][H][W][512], H = W = S/8; xi == layer4_index()
   RGBM_REQUIRE(H == S / 8 && W == S / 8, "feature stride");
-  if (g_debug_flags & DBG_PSP_STAGE_R5) {      // the PSP stage as rounds 1-5 ran it: copy, pooling, four GEMM launches, four resizes
+  if (p.psp_stage == PSP_ROUND5) {      // the PSP stage as rounds 1-5 ran it: copy, pooling, four GEMM launches, four resizes
     if (int rc = launch_copy_channels(dtype, f, bf.cat, (long long)V * H * W, 512, 1024, 0, s)) return rc;
     {
       void* outs[4] = {bf.pooled[0], bf.pooled[1], bf.pooled[2], bf.pooled[3]};
@@ -463,10 +479,7 @@ int AdaPose::pspnet(const Buffers& bf, int Vout, const float* img1, const float*
     // Small batches (the deployment shape, B = 1 .. 8): pooling and the four 512 -> 128 convs of the 50 cells per view in one launch on the
     // vector pipe (misc_kernels.hip; the GEMM launches it replaces had 2 .. 576 rows); larger ones keep the pooling launch and the
     // implicit GEMMs.  The concat (backbone channels + the four resized stages) is one launch at any size.
-    bool small = V <= kPspSmallViews;
-    for (int i = 0; i < 4; ++i)
-      small = small && psp[i].packs.size() == 1 && psp[i].packs[0].Kpad == 512 && psp[i].Cout_pad == 128 && !psp[i].bias;
-    if (small) {
+    if (p.psp_stage == PSP_ONE_LAUNCH) {
       const void* w[4] = {psp[0].packs[0].w.get(), psp[1].packs[0].w.get(), psp[2].packs[0].w.get(), psp[3].packs[0].w.get()};
       void* outs[4] = {bf.stage[0], bf.stage[1], bf.stage[2], bf.stage[3]};
       if (int rc = launch_psp_pool_conv(dtype, f, 512, w, outs, kPspBins, V, H, W, psp[0].g.act, psp[0].g.slope, s)) return rc;
@@ -482,9 +495,9 @@ int AdaPose::pspnet(const Buffers& bf, int Vout, const float* img1, const float*
   // up_1 / up_2: 1x1 GEMM at the low resolution (nine taps stacked on the output channels, z in `ups`: 9/16 of the up-sampled
   // tensor it replaces) + tap combination; or, for A/B, the x2 resize followed by the 3x3 conv on the up-sampled grid
   // Dropout2d is applied in the tap combination's epilogue only: the A/B paths refuse it
-  RGBM_REQUIRE(drop == nullptr || (upconv & 3) == 3, "dropout needs option upconv bits 0 and 1 (up_1 / up_2 through the tap combination)");
+  RGBM_REQUIRE(drop == nullptr || (p.up1 && p.up2), "dropout needs option upconv bits 0 and 1 (up_1 / up_2 through the tap combination)");
   if (samples > 1) {
-    RGBM_REQUIRE(drop != nullptr && (upconv & 3) == 3 && img2 != nullptr && V % 2 == 0, "pspnet: samples need Dropout2d masks and both views");
+    RGBM_REQUIRE(drop != nullptr && p.up1 && p.up2 && img2 != nullptr && V % 2 == 0, "pspnet: samples need Dropout2d masks and both views");
     const int B = V / 2;
     const size_t zview = up1c.scratch_elems(1, H, W) * dtype_size(dtype), oview = (size_t)4 * H * W * 256 * dtype_size(dtype);
     if (int rc = up1c.run_gemm(bf.cat, bf.ups, V, H, W, s)) return rc;
@@ -495,33 +508,37 @@ int AdaPose::pspnet(const Buffers& bf, int Vout, const float* img1, const float*
                                   drop + row * kDropoutPerView)) return rc;
       }
     V = Vout;
-  } else if (upconv & 1) {
+  } else if (p.up1) {
     if (int rc = up1c.run(bf.cat, bf.ups, bf.u1, V, H, W, 256, s, drop)) return rc;
   } else {
     if (int rc = launch_resize_bilinear_ac(dtype, bf.cat, bf.ups, V, H, W, 1024, 2 * H, 2 * W, 1024, 0, s)) return rc;
     if (int rc = up1.run(bf.ups, bf.u1, V, 1, 2 * H, 2 * W, 256, nullptr, 0, nullptr, 0, s)) return rc;
   }
-  if (upconv & 2) {
+  if (p.up2) {
     if (int rc = up2c.run(bf.u1, bf.ups, bf.u2, V, 2 * H, 2 * W, 64, s, drop ? drop + 256 : nullptr)) return rc;
   } else {
     if (int rc = launch_resize_bilinear_ac(dtype, bf.u1, bf.ups, V, 2 * H, 2 * W, 256, 4 * H, 4 * W, 256, 0, s)) return rc;
     if (int rc = up2.run(bf.ups, bf.u2, V, 1, 4 * H, 4 * W, 64, nullptr, 0, nullptr, 0, s)) return rc;
   }
-  const bool plain_f32 = feat_f32_only();
-  if ((upconv & 4) && tail.ready())       // up_3 + final from the half-resolution tensor in one kernel: no up-sampled tensor, no z, no u3
-    return tail.run(bf.u2, plain_f32 ? (void*)bf.featf : bf.feat, plain_f32 ? 1 : feat_f16() ? 2 : 0, V, 4 * H, 4 * W, s);
+  const bool plain_f32 = p.feat_form == FEAT_F32_ONLY;
+  void* const feat = plain_f32 ? (void*)bf.featf : bf.feat;
+  if (p.up3 == UP3_TAIL_KERNEL)       // up_3 + final from the half-resolution tensor in one kernel: no up-sampled tensor, no z, no u3
+    return tail.run(bf.u2, feat, p.feat_form, V, 4 * H, 4 * W, s);
   if (int rc = launch_resize_bilinear_ac(dtype, bf.u2, bf.ups, V, 4 * H, 4 * W, 64, 8 * H, 8 * W, 64, 0, s)) return rc;
   // up_3 + final: one launch on the bf16 path (the 64-channel up_3 output then never reaches HBM: `u3` is not written)
   // bf16x3, default path: `final` writes the plain-fp32 feature map directly (no split-pair copy, no 6.6 GB conversion pass)
-  return up3.run_then_1x1(fin, bf.ups, bf.u3, 64, plain_f32 ? (void*)bf.featf : bf.feat, 32, V, 1, 8 * H, 8 * W, fuse_final != 0, nullptr, s, plain_f32);
+  return up3.run_then_1x1(fin, bf.ups, bf.u3, 64, feat, 32, V, 1, 8 * H, 8 * W, p.up3 == UP3_FUSED_FINAL, nullptr, s, plain_f32);
 }
 
-int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, const Call& call) const {
+int AdaPose::feat_copy(const Buffers& bf, int V, const Call& call, const ForwardPaths& p) const {
+  return p.feat_copy ? launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * img * img * 32, call.stream) : 0;
+}
+
+int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, const Call& call, const ForwardPaths& p) const {
   const int S = img, D = n_depth, P = n_pts;
   hipStream_t s = call.stream;
   const int Vh = view2_heads ? V : B;      // views whose probability volume is computed (partners are looked up among all V)
   const int Vc0 = chunk_views(V);
-  const bool b16 = dtype_size(dtype) == 2;      // 16-bit storage: the depth-sweeping conv0, implicit-GEMM conv6 and the sparse tail exist for these
   // the rows of kCost3d on this forward's buffers, as the three chunk bodies walk them: input, output, skip tensor, down-sampling of the
   // input grid, output channels
   struct Layer3d { const void* in; void* out; const void* res; int div, C; };
@@ -529,8 +546,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
   for (int i = 0; i < kCost3dLayers; ++i)
     l3d[i] = {i == 0 ? bf.vol : bf.c3[i - 1], bf.c3[i], kCost3d[i].skip >= 0 ? bf.c3[kCost3d[i].skip] : nullptr, kCost3d[i].in_div, kCost3d[i].cout};
   void* const u11 = bf.c3[kCost3dLayers - 1];
-  // halo-tiled path (cost_impl >= 1): one launch per layer; conv0 optionally builds its input on the fly
-  bool sweep_sparse = false;     // set per chunk below: the depth-sweeping conv0 walks the list of needed tiles
+  // halo-tiled path (COST_TILES): one launch per layer; conv0 optionally builds its input on the fly
   // layer: the kernel's id, a row of kCost3d or 10 = row 0 with the plane sweep fused in (no input tensor); grids and channels come from the row
   auto tile = [&](int layer, const Layer3d& l, int Vc, int v0, const unsigned char* tmask) -> int {
     const int li = layer == 10 ? 0 : layer;
@@ -548,7 +564,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
     d.out_classmajor = layer == 9 ? 1 : 0;      // u11 is only gathered sparsely by the prob kernel
     d.tile_mask = tmask;
     d.tile_mask_stride = sparse_mask_bytes_per_view(S);
-    if (layer == 10 && sweep_sparse) { d.tile_list = bf.sweep_list; d.tile_count = bf.sweep_count; }
+    if (layer == 10 && p.sweep_list) { d.tile_list = bf.sweep_list; d.tile_count = bf.sweep_count; }
     // profiler rows (prof.h): conv0 + fused warp on its own; bf16 layers one row each, f32 layers aggregated
     d.prof_variant = dtype == BF16X3 ? (layer == 10 ? 28 : 27) : layer == 10 ? 10 + (dtype != F32 ? 1 : 0) : (dtype != F32 ? 16 + layer : 8);
     d.algo_flops = 2.0 * Vc * (double)(transposed ? Di * Hi * Wi : Do * Ho * Wo) * Cout * 27.0 * Cin;
@@ -556,14 +572,12 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
     // never materialises: algorithmic bytes = features in + c0 out
     d.algo_bytes = ((layer == 10 ? (double)Vc * Hi * Wi * Cin : (double)Vc * Di * Hi * Wi * Cin) +
                     (double)Vc * Do * Ho * Wo * Cout * (res ? 2 : 1)) * (double)dtype_size(dtype);
-    // debug flag 4096: the halo-tile conv0 instead of either depth-sweeping kernel, in every storage type (the runtime way out
-    // should a compiler update bring the sweep kernels' hand-counted asm gathers out of step)
-    if (layer == 10 && cost_impl == 3 && b16 && sweep_w && !(g_debug_flags & DBG_TILE_CONV0)) {
+    if (layer == 10 && (p.conv0 == CONV0_SWEEP16 || p.conv0 == CONV0_SWEEP16_F16)) {
       d.wgt = sweep_w.get();
-      if (feat_f16()) { d.wgt = sweep_w_f16.get(); d.feat_f16 = 1; }
+      if (p.conv0 == CONV0_SWEEP16_F16) { d.wgt = sweep_w_f16.get(); d.feat_f16 = 1; }
       return launch_conv0_sweep(d, dtype, s);
     }
-    if (layer == 10 && cost_impl == 3 && dtype == BF16X3 && sweep_w && !(g_debug_flags & DBG_TILE_CONV0)) {
+    if (layer == 10 && p.conv0 == CONV0_SWEEP_X3) {
       d.wgt = sweep_w.get();
       d.feat = bf.featf;
       return launch_conv0_sweep_x3(d, s);
@@ -574,11 +588,10 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
   // layer is needed only inside their dependency cones (prob_sparse.hip: sparse_mask_kernel) — conv1 .. conv5, conv7 / conv9 skip the
   // other tiles, the depth-sweeping conv0 walks the list of needed ones.  conv6 stays dense (a 0.3 ms GEMM): what it computes from
   // unwritten input tiles is never read by anything that is read.
-  const bool sparse_ok = sparse_active(call.dense);
   for (int v0 = 0; v0 < Vh; v0 += Vc0) {
     const int Vc = Vh - v0 < Vc0 ? Vh - v0 : Vc0;
     int classmajor = 0;      // layout of the u11 the chunk body leaves behind
-    if (norm_mode == 1) {
+    if (p.cost_body == COST_BN_PER_SAMPLE) {
       // per-sample BatchNorm3d: every layer = un-normalised conv (generic implicit GEMM) -> per-view batch statistics -> normalise + ReLU (+ skip)
       if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
       for (int i = 0; i < 10; ++i) {
@@ -590,7 +603,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
         if (int rc = launch_bn_per_sample(dtype, l.out, l.res, bn_gamma[i].get<float>(), bn_beta[i].get<float>(), bf.bn_scratch, Vc,
                                           (long long)Do * Ho * Wo, l.C, 1, s)) return rc;
       }
-    } else if (cost_impl == 0) {
+    } else if (p.cost_body == COST_GENERIC) {
       // generic implicit GEMM on the materialised volume; the skip adds of conv7 / 9 / 11 are post-ReLU (network_v5.py:287-289)
       if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
       for (int i = 0; i < 10; ++i) {
@@ -600,34 +613,29 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
     } else {
       // halo-tiled layers; conv0 on the materialised volume (cost_impl 1) or with the plane sweep fused in
       const unsigned char* mk[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      sweep_sparse = false;
-      if (sparse_ok) {
+      if (p.mask_level > 0) {
         int td, th, tw;
         for (int L : {1, 2, 3, 4, 5, 7, 8}) RGBM_REQUIRE(!conv3d_tile_dims(L, dtype, &td, &th, &tw) && th == 8 && tw == 8, "sparse cost regularisation: 8 x 8 tiles expected");
         if (int rc = launch_sparse_masks(bf.choose, v0, Vc, P, S, bf.masks, bf.sweep_list, bf.sweep_count, s)) return rc;
         for (int L : {7, 8}) mk[L] = bf.masks + sparse_mask_offset(S, L);
-        if (sparse_dec >= 2) {
+        if (p.mask_level >= 2)
           for (int L : {1, 2, 3, 4, 5}) mk[L] = bf.masks + sparse_mask_offset(S, L);
-          sweep_sparse = true;
-        }
       }
       // one launch per row; the rows that are not simply their halo-tile kernel say so
-      const bool tail_sparse = sparse_tail_active(call.dense);
-      for (int i = 0; i < (tail_sparse ? 9 : kCost3dLayers); ++i) {
+      for (int i = 0; i < (p.tail_sparse ? 9 : kCost3dLayers); ++i) {
         const Layer3d& l = l3d[i];
-        if (i == 0 && cost_impl == 1) {
+        if (i == 0 && p.conv0 == CONV0_TILE_VOLUME) {
           if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
           if (int rc = tile(0, l, Vc, v0, nullptr)) return rc;
         } else if (i == 0) {
           if (int rc = tile(10, l, Vc, v0, nullptr)) return rc;
-        } else if (i == 6 && cost_impl == 3 && (b16 || dtype == BF16X3) && igemm_conv6) {
-          // conv6 (64 -> 64, K = 27 x 64): a plain GEMM shape, 2.7x faster on the role-specialised implicit-GEMM kernel
+        } else if (i == 6 && p.conv6_igemm) {
           if (int rc = c3d[6].run(l.in, l.out, Vc, D / l.div, S / l.div, S / l.div, l.C, nullptr, RES_NONE, nullptr, 0, s)) return rc;
         } else {
           if (int rc = tile(i, l, Vc, v0, mk[i])) return rc;      // masks: rows 1-5, 7 and 8 (above)
         }
       }
-      if (tail_sparse) {
+      if (p.tail_sparse) {
         // conv11 + skip + prob conv + softmax + depth only on the 3x3 neighbourhoods of the chosen pixels (prob_sparse.hip)
         if (int rc = launch_prob_sparse(l3d[9].in, l3d[9].res, dtype == BF16X3 ? w11_x3.get() : t3d[9].w.get(), t3d[9].bias.get<float>(),
                                         wprob.get<float>(), bf.choose, depths, bf.prob, bf.depth, v0, Vc, B, P, D, S, S, dtype, s, w11_taps.get())) return rc;
@@ -653,15 +661,10 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   RGBM_REQUIRE(arch != ARCH_BASELINE || !(call.dense || call.depth_map || call.conf_map || call.nocs_map),
                "baseline network: the dense / maps forwards are not implemented (they read the cost volume this network does not have)");
   RGBM_REQUIRE(arch != ARCH_BASELINE || call.dropout == Dropout::None, "baseline network: Dropout2d is not implemented");
-  RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
-  const size_t need = workspace_bytes(B);
-  RGBM_REQUIRE(workspace_size >= need, call.dense ? "forward_dense: workspace too small: need " + std::to_string(need) + " (rgbm_adapose_dense_workspace_bytes)"
-                                                  : "workspace too small: need " + std::to_string(need));
-  Arena A(workspace, workspace_size);
+  const ForwardPaths p = paths(B, call.dense);
   Buffers bf;
-  plan(B, A, bf);
-  const int V = 2 * B, S = img;
+  if (int rc = open_workspace(B, p, workspace, workspace_size, 0, call.dense ? "forward_dense: " : "", call.dense ? " (rgbm_adapose_dense_workspace_bytes)" : "", bf)) return rc;
+  const int V = 2 * B;
   hipStream_t s = call.stream;
 
   // ---- stage inputs: views = [view1 batch ; view2 batch] ----
@@ -678,15 +681,13 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
     if (!loaded)
       if (int rc = launch_dropout_masks(drop_masks.get<float>(), drop_state.get<unsigned long long>(), B, drop_p, drop_seed, call.dropout == Dropout::Draw ? 1 : 0, s)) return rc;
   }
-  if (int rc = pspnet(bf, V, img1, img2, call)) return rc;
+  if (int rc = pspnet(bf, V, img1, img2, call, p)) return rc;
   if (arch != ARCH_BASELINE)
     if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
-  // bf16x3 nets: everything that GATHERS from the feature map (plane sweep, point heads) reads a plain fp32 copy of it
-  if (dtype == BF16X3 && !feat_f32_only())
-    if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * S * S * 32, s)) return rc;
+  if (int rc = feat_copy(bf, V, call, p)) return rc;
   if (call.stop_after == 1) return 0;
-  if (arch == ARCH_BASELINE) return heads_baseline(bf, B, out, call);
-  return heads(bf, B, depths, out, call);
+  if (arch == ARCH_BASELINE) return heads_baseline(bf, B, out, call, p);
+  return heads(bf, B, depths, out, call, p);
 }
 
 // S Dropout2d samples of B poses: forward() of the S x B poses that are the B poses tiled S times (pose k * B + b = sample k of pose b),
@@ -709,21 +710,19 @@ int AdaPose::forward_samples(int B, int S, const float* img1, const float* img2,
   RGBM_REQUIRE((upconv & 3) == 3, "forward_samples needs option upconv bits 0 and 1 (the masks are applied in the tap combination of up_1 / up_2)");
   const int SB = S * B, V = 2 * SB;
   RGBM_REQUIRE(V <= drop_cap_views && drop_masks && (call.dropout == Dropout::Loaded || drop_state), "forward_samples: mask buffer smaller than S x B poses");
-  RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
-  const size_t need = samples_workspace_bytes(B, S);
-  RGBM_REQUIRE(workspace_size >= need, "forward_samples: workspace too small: need " + std::to_string(need) + " (rgbm_adapose_samples_workspace_bytes)");
-  hipStream_t s = call.stream;
+  PathFacts facts = path_facts(SB, false);
+  facts.V = 2 * B;      // the PSPNet's shared prefix runs on the 2B input views
+  const ForwardPaths p = forward_paths(facts);
   // staging block: P1, P2 [SB][16], choose1, choose2 [SB][P], depths [SB][D]
   const size_t stage = samples_staging_bytes(*this, SB);
+  Buffers bf;
+  if (int rc = open_workspace(SB, p, workspace, workspace_size, stage, "forward_samples: ", " (rgbm_adapose_samples_workspace_bytes)", bf)) return rc;
+  hipStream_t s = call.stream;
   float* tP1 = (float*)workspace;
   float* tP2 = tP1 + (size_t)SB * 16;
   int* tc1 = (int*)(tP2 + (size_t)SB * 16);
   int* tc2 = tc1 + (size_t)SB * n_pts;
   float* tdep = (float*)(tc2 + (size_t)SB * n_pts);
-  Arena A((char*)workspace + stage, workspace_size - stage);
-  Buffers bf;
-  plan(SB, A, bf);
   if (int rc = launch_tile_words(P1, tP1, (long long)B * 16, S, s)) return rc;
   if (int rc = launch_tile_words(P2, tP2, (long long)B * 16, S, s)) return rc;
   if (int rc = launch_tile_words(choose1, tc1, (long long)B * n_pts, S, s)) return rc;
@@ -732,18 +731,24 @@ int AdaPose::forward_samples(int B, int S, const float* img1, const float* img2,
   if (int rc = launch_stage_in(tP1, tP2, tc1, tc2, bf.Pviews, bf.choose, SB, n_pts, s)) return rc;
   if (call.dropout == Dropout::Draw)      // poses counter .. counter + SB - 1, as the plain forward of the tiled batch draws them
     if (int rc = launch_dropout_masks(drop_masks.get<float>(), drop_state.get<unsigned long long>(), SB, drop_p, drop_seed, 1, s)) return rc;
-  if (int rc = pspnet(bf, V, img1, img2, call, S)) return rc;
+  if (int rc = pspnet(bf, V, img1, img2, call, p, S)) return rc;
   if (int rc = launch_homography(bf.Pviews, bf.homog, V, SB, s)) return rc;
-  if (dtype == BF16X3 && !feat_f32_only())
-    if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * img * img * 32, s)) return rc;
-  return heads(bf, SB, tdep, out, call);
+  if (int rc = feat_copy(bf, V, call, p)) return rc;
+  return heads(bf, SB, tdep, out, call, p);
 }
 
 // Everything behind the PSPNet of the baseline network (network_baseline.py:617-669): the gathered rows feed the NOCS branch as in v5 and,
 // untouched, the attention stack; depth_head and the pose branch read the fused rows.
-AdaPose::FeatSource AdaPose::gather_source(const Buffers& bf) const {
+AdaPose::FeatSource AdaPose::gather_source(const Buffers& bf, const ForwardPaths& p) const {
   if (dtype == BF16X3) return {bf.featf, F32};
-  return {bf.feat, feat_f16() ? (int)F16 : dtype};
+  return {bf.feat, p.feat_form == FEAT_F16 ? (int)F16 : dtype};
+}
+
+PointMlpDesc AdaPose::point_mlp_desc(const Buffers& bf, const FeatSource& src, int Vh) const {
+  PointMlpDesc pd{};
+  pd.table = pmlp_table.get<float>(); pd.feat = src.feat; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = n_pts; pd.HW = img * img;
+  pd.N = (long long)Vh * n_pts;
+  return pd;
 }
 
 // view2_heads = 0: the view-2 outputs are filled with NaN, so that a consumer of one fails loudly instead of reading stale numbers
@@ -756,18 +761,15 @@ int AdaPose::stage_out(const Buffers& bf, int B, const Outputs& out, hipStream_t
   return launch_stage_out(bf.nocs4, bf.depth, bf.R, bf.tv, bf.sv, on, od, orr, ot, os, B, n_pts, view2_heads, s);
 }
 
-int AdaPose::heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call) const {
+int AdaPose::heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call, const ForwardPaths& p) const {
   const int V = 2 * B, P = n_pts, S = img;
   hipStream_t s = call.stream;
-  const FeatSource src = gather_source(bf);
+  const FeatSource src = gather_source(bf, p);
   const int Vh = view2_heads ? V : B;
   RGBM_REQUIRE(pmlp_table && ((long long)Vh * P) % 64 == 0, "baseline network: the point MLP kernel needs a multiple of 64 points");
   // both views' rows: view 2's are every block's keys even without its heads
   if (int rc = launch_gather_points(src.dtype, src.feat, bf.choose, bf.X0, V, P, S * S, 32, s)) return rc;
-  PointMlpDesc pd{};
-  pd.table = pmlp_table.get<float>(); pd.feat = src.feat; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = P; pd.HW = S * S;
-  pd.N = (long long)Vh * P;
-  if (int rc = launch_point_mlp(src.dtype, pd, s)) return rc;
+  if (int rc = launch_point_mlp(src.dtype, point_mlp_desc(bf, src, Vh), s)) return rc;
   // the attention stack, a chunk of poses at a time (max_chunk views = max_chunk / 2 poses): a pose's rows do not depend on its chunk
   const size_t view2 = (size_t)B * P * 32;
   const int Bc0 = chunk_poses(B);
@@ -781,7 +783,7 @@ int AdaPose::heads_baseline(const Buffers& bf, int B, const Outputs& out, const 
   // depth_head on the fused rows; the same rows are channels 0..31 of the pose feature (network_baseline.py:633-641)
   if (int rc = launch_depth_head(dh_w.get<float>(), bf.fused, (long long)Vh * P, bf.depth, regress_pose ? bf.PF96 : nullptr, 96, s)) return rc;
   if (regress_pose)
-    if (int rc = pose_branch(bf, Vh, call)) return rc;
+    if (int rc = pose_branch(bf, Vh, call, p)) return rc;
   if (int rc = stage_out(bf, B, out, s)) return rc;
   if (!regress_pose) {      // no pose branch: the six r / t / s outputs are NaN
     float* const rts[6] = {out.r1, out.t1, out.s1, out.r2, out.t2, out.s2};
@@ -797,19 +799,16 @@ int AdaPose::nocs_map_of(const float* feat_f32, long long pixels, float* nocs_ma
 }
 
 // Everything behind the PSPNet: reads the feature map(s) in bf.feat / bf.featf, bf.homog, bf.choose (forward() and forward_cached() fill them)
-int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call) const {
+int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const {
   const int V = 2 * B, P = n_pts, S = img, D = n_depth;
   hipStream_t s = call.stream;
-  const FeatSource src = gather_source(bf);
+  const FeatSource src = gather_source(bf, p);
 
   const int Vh = view2_heads ? V : B;      // views that get heads: both crops of every pose, or the view-1 crops only (option view2_heads)
   // ---- per-point NOCS branch (network_v5.py:432-444) ----
-  if (pmlp_table && !(g_debug_flags & DBG_POINT_MLP_R5) && ((long long)Vh * P) % 64 == 0) {
+  if (p.point_mlp) {
     // gather + the six layers in one launch (head_kernels.hip): a wave carries 16 points through the whole branch, weights and activations in LDS
-    PointMlpDesc pd{};
-    pd.table = pmlp_table.get<float>(); pd.feat = src.feat; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = P; pd.HW = S * S;
-    pd.N = (long long)Vh * P;
-    if (int rc = launch_point_mlp(src.dtype, pd, s)) return rc;
+    if (int rc = launch_point_mlp(src.dtype, point_mlp_desc(bf, src, Vh), s)) return rc;
   } else {
     if (int rc = launch_gather_points(src.dtype, src.feat, bf.choose, bf.X0, Vh, P, S * S, 32, s)) return rc;
     if (int rc = inst.run(bf.X0, bf.X1, Vh, 1, 1, P, 64, nullptr, 0, nullptr, 0, s)) return rc;
@@ -825,12 +824,12 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
     if (int rc = launch_dense_nocs(src.dtype, pmlp_table.get<float>(), src.feat, call.nocs_map, (long long)Vh * S * S, s)) return rc;
 
   // ---- plane-sweep cost volume -> probability at the sampled pixels -> depth ----
-  if (int rc = cost_volume(bf, V, B, depths, call)) return rc;
+  if (int rc = cost_volume(bf, V, B, depths, call, p)) return rc;
   if (call.stop_after == 2) return 0;
 
   // ---- depth-guided fusion + pose regression (network_v5.py:457-508) ----
   if (int rc = launch_fuse_points(src.dtype, src.feat, bf.homog, depths, bf.choose, bf.prob, bf.PF96, V, B, P, D, S, S, 96, 0, s, Vh)) return rc;
-  if (int rc = pose_branch(bf, Vh, call)) return rc;
+  if (int rc = pose_branch(bf, Vh, call, p)) return rc;
 
   // ---- outputs (fp32, reference shapes) ----
   return stage_out(bf, B, out, s);
@@ -838,7 +837,7 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
 
 // pose_mlp1 -> mean -> pose_mlp2 -> mean -> the three heads + Ortho6d on the pose features PF96 of views 0 .. Vh - 1 (network_v5.py:470-508;
 // network_baseline.py:643-659 is the same code)
-int AdaPose::pose_branch(const Buffers& bf, int Vh, const Call& call) const {
+int AdaPose::pose_branch(const Buffers& bf, int Vh, const Call& call, const ForwardPaths& p) const {
   const int P = n_pts;
   hipStream_t s = call.stream;
   // bf16 nets: the four big per-point layers of the pose MLP run in fp16 storage (fp32 they took 1.8 ms per 512 views at
@@ -847,13 +846,7 @@ int AdaPose::pose_branch(const Buffers& bf, int Vh, const Call& call) const {
   // ... and since round 7 as two launches (pose_mlp.hip): neither PF96h, Q128a nor the two 256-channel per-point tensors reach memory;
   // the slices' sums land where launch_mean_points_partial put them.  Debug flag 524288: the per-layer launches (also taken for a point
   // count that is not a whole number of slabs per slice, and for layers of another shape)
-  auto pose_layer_ok = [](const ConvLayer& L, int cin, int cout) {
-    return L.dtype == F16 && L.packs.size() == 1 && L.packs[0].ntaps == 1 && L.Cin_pad == cin && L.Cout_pad == cout && L.g.act == ACT_RELU &&
-           L.packs[0].Kpad >= cin && L.bias;
-  };
-  const bool pose_fused = pdt == F16 && !(g_debug_flags & DBG_POSE_MLP_R6) && pose_mlp_fits(P) && pose_layer_ok(pm1[0], 96, 128) &&
-                          pose_layer_ok(pm1[1], 128, 128) && pose_layer_ok(pm2[0], 128, 256) && pose_layer_ok(pm2[1], 256, 256);
-  if (pose_fused) {
+  if (p.pose_mlp) {
     PoseMlpDesc pd{};
     const ConvLayer* L[4] = {&pm1[0], &pm1[1], &pm2[0], &pm2[1]};
     for (int l = 0; l < 4; ++l) { pd.w[l] = L[l]->packs[0].w.get(); pd.ldw[l] = L[l]->packs[0].Kpad; pd.bias[l] = L[l]->bias.get<float>(); }
@@ -889,10 +882,10 @@ int AdaPose::pose_branch(const Buffers& bf, int Vh, const Call& call) const {
 // ---- feature cache (feature_cache.hip, DESIGN.md "Feature cache") ----
 // A record is what heads() reads of one view's feature map: bf.feat for 16-bit and fp32 storage, bf.featf for split pairs - preceded by
 // the split-pair map where something still reads it (per-sample BN, the halo-tile conv0 and the materialised volume do).
-int AdaPose::feature_parts(const Buffers& bf, FeaturePart parts[2]) const {
+int AdaPose::feature_parts(const Buffers& bf, const ForwardPaths& p, FeaturePart parts[2]) const {
   const size_t one = (size_t)img * img * 32;
   if (dtype != BF16X3) { parts[0] = {bf.feat, 0, one * dtype_size(dtype)}; return 1; }
-  if (feat_f32_only()) { parts[0] = {bf.featf, 0, one * 4}; return 1; }
+  if (p.feat_form == FEAT_F32_ONLY) { parts[0] = {bf.featf, 0, one * 4}; return 1; }
   parts[0] = {bf.feat, 0, one * 4};
   parts[1] = {bf.featf, one * 4, one * 4};
   return 2;
@@ -901,7 +894,7 @@ int AdaPose::feature_parts(const Buffers& bf, FeaturePart parts[2]) const {
 size_t AdaPose::feature_bytes() const {
   Buffers bf{};
   FeaturePart parts[2];
-  const int n = feature_parts(bf, parts);
+  const int n = feature_parts(bf, paths(1), parts);
   return parts[n - 1].off + parts[n - 1].bytes;
 }
 
@@ -915,17 +908,16 @@ int AdaPose::features(int V, const float* images, const int* slots, void* pool, 
   RGBM_REQUIRE(call.dropout == Dropout::None, "features: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would change "
                "what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "features: workspace must be 256-byte, pool 16-byte aligned");
-  const size_t need = features_workspace_bytes(V);
-  RGBM_REQUIRE(workspace_size >= need, "features workspace too small: need " + std::to_string(need));
-  Arena A(workspace, workspace_size);
+  PathFacts facts = path_facts((V + 1) / 2, false);
+  facts.V = V;      // any V >= 1 views enter the PSPNet
+  const ForwardPaths p = forward_paths(facts);
   Buffers bf;
-  plan((V + 1) / 2, A, bf);
-  if (int rc = pspnet(bf, V, images, nullptr, call)) return rc;
-  if (dtype == BF16X3 && !feat_f32_only())
-    if (int rc = launch_bx3_to_f32(bf.feat, bf.featf, (long long)V * img * img * 32, s)) return rc;
+  if (int rc = open_workspace((V + 1) / 2, p, workspace, workspace_size, 0, "features ", "", bf)) return rc;
+  if (int rc = pspnet(bf, V, images, nullptr, call, p)) return rc;
+  if (int rc = feat_copy(bf, V, call, p)) return rc;
   FeaturePart parts[2];
-  const int np = feature_parts(bf, parts);
-  const size_t rec = feature_bytes();
+  const int np = feature_parts(bf, p, parts);
+  const size_t rec = parts[np - 1].off + parts[np - 1].bytes;
   for (int i = 0; i < np; ++i)
     if (int rc = launch_feature_store(parts[i].buf, pool, slots, V, pool_records, parts[i].off, parts[i].bytes, rec, s)) return rc;
   return 0;
@@ -940,21 +932,18 @@ int AdaPose::forward_cached(int B, const void* pool, int pool_records, const int
   RGBM_REQUIRE(call.dropout == Dropout::None, "forward_cached: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would "
                "change what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "forward_cached: workspace must be 256-byte, pool 16-byte aligned");
-  RGBM_REQUIRE(n_depth % 8 == 0 && img % 8 == 0, "depth/img must be multiples of 8");
-  const size_t need = workspace_bytes(B);
-  RGBM_REQUIRE(workspace_size >= need, "workspace too small: need " + std::to_string(need));
-  Arena A(workspace, workspace_size);
+  const ForwardPaths p = paths(B, call.dense);
   Buffers bf;
-  plan(B, A, bf);
+  if (int rc = open_workspace(B, p, workspace, workspace_size, 0, "", "", bf)) return rc;
   const int V = 2 * B, P = n_pts;
   if (int rc = launch_stage_in(P1, P2, choose1, choose2, bf.Pviews, bf.choose, B, P, s)) return rc;
   FeaturePart parts[2];
-  const int np = feature_parts(bf, parts);
-  const size_t rec = feature_bytes();
+  const int np = feature_parts(bf, p, parts);
+  const size_t rec = parts[np - 1].off + parts[np - 1].bytes;
   for (int i = 0; i < np; ++i)
     if (int rc = launch_feature_gather(pool, parts[i].buf, slot1, slot2, B, pool_records, parts[i].off, parts[i].bytes, rec, s)) return rc;
   if (int rc = launch_homography(bf.Pviews, bf.homog, V, B, s)) return rc;
-  if (int rc = heads(bf, B, depths, out, call)) return rc;
+  if (int rc = heads(bf, B, depths, out, call, p)) return rc;
   // a slot outside the pool: that pose's ten outputs are NaN (nothing was read for it; every other pose is what a clean call gives)
   float* const o[10] = {out.nocs1, out.nocs2, out.depth1, out.depth2, out.r1, out.r2, out.t1, out.t2, out.s1, out.s2};
   const int per[10] = {3 * P, 3 * P, P, P, 9, 9, 3, 3, 3, 3};

@@ -1,4 +1,5 @@
 #pragma once
+#include "forward_paths.h"
 #include "kernels.h"
 #include "layers.h"
 
@@ -21,7 +22,7 @@ struct Arena {
 struct AdaPose {
   // which network the handle holds: network_v5.py's StereoPoseNet_with_depth, or network_baseline.py's StereoPoseNet_with_depth_baseline
   // (the cost volume and the depth-guided fusion replaced by the cross-view attention stack and depth_head: view_fusion.hip)
-  enum { ARCH_V5 = 0, ARCH_BASELINE = 1 };
+  enum { ARCH_V5 = PATH_ARCH_V5, ARCH_BASELINE = PATH_ARCH_BASELINE };
   int arch = ARCH_V5;
   int regress_pose = 1;           // baseline only: 0 = no pose branch (the six r / t / s outputs are NaN)
   DevBuf vf_w;                    // baseline: the attention stack's 32 linears (view_fusion.h: kVfWeightFloats)
@@ -33,7 +34,7 @@ struct AdaPose {
   // raise the rotation error from 4e-5 to 3e-4)
   // storage type of the four per-point layers of the pose MLP: fp16 for bf16 nets, split pairs for split-pair nets (the exact-fp32
   // matrix path runs at a sixteenth of the bf16 rate: 1.5 ms per step for these layers), fp32 otherwise
-  int pose_dtype() const { return dtype == BF16 ? F16 : (dtype == BF16X3 && pose_x3) ? BF16X3 : F32; }
+  int pose_dtype() const { return pose_storage(dtype, pose_x3); }
   int pose_x3 = 1;
   int img = 224, n_pts = 1024, n_depth = 24;
   int img_cpad = 4;
@@ -89,7 +90,8 @@ struct AdaPose {
   int drop_cap_views = 0;
 
   // What one call wants beyond the network's inputs and outputs.  The entry point (capi.cpp) fills it; forward() / forward_cached() pass
-  // it down pspnet() / heads() / cost_volume(), none of which writes the net.
+  // it down pspnet() / heads() / cost_volume(), none of which writes the net.  Beside it travel the call's ForwardPaths: every entry
+  // point asks paths() once, and nothing below it reads an option or the debug flags again.
   enum class Dropout {
     None,            // no Dropout2d
     Loaded,          // the factors rgbm_adapose_set_dropout_masks put into drop_masks
@@ -138,6 +140,10 @@ struct AdaPose {
   int create_cost(const StateDict& sd);
   int create_point_heads(const StateDict& sd, bool pts_mlp);
   int create_pose(const StateDict& sd);
+  // Path selection (forward_paths.h): the facts of a call of B poses as this handle and the process's debug flags stand now, and what
+  // forward_paths makes of them.  forward_samples() and features() set the views entering the PSPNet (PathFacts::V) themselves.
+  PathFacts path_facts(int B, bool dense) const;
+  ForwardPaths paths(int B, bool dense = false) const { return forward_paths(path_facts(B, dense)); }
   size_t workspace_bytes(int B) const;
   // the map rules of a call (depth_map needs dense, conf_map needs depth_map, nocs_map needs the point MLP table) are checked here
   int forward(int B, const float* img1, const float* img2, const int* choose1, const int* choose2, const float* P1,
@@ -164,32 +170,31 @@ struct AdaPose {
                      const float* P1, const float* P2, const float* depths, void* workspace, size_t workspace_size, const Outputs& out,
                      const Call& call) const;
   struct FeaturePart { void* buf; size_t off, bytes; };      // a feature buffer of the workspace and its place inside a record
-  int feature_parts(const Buffers& bf, FeaturePart parts[2]) const;
-  int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call) const;
-  int heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call) const;
-  // what the point heads gather from: the feature map of this forward and its element type (fp32 copy for split pairs, f16 with feat_f16())
+  int feature_parts(const Buffers& bf, const ForwardPaths& p, FeaturePart parts[2]) const;
+  int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const;
+  int heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call, const ForwardPaths& p) const;
+  // what the point heads gather from: the feature map of this forward and its element type (fp32 copy for split pairs, f16 with FEAT_F16)
   struct FeatSource { const void* feat; int dtype; };
-  FeatSource gather_source(const Buffers& bf) const;
+  FeatSource gather_source(const Buffers& bf, const ForwardPaths& p) const;
+  PointMlpDesc point_mlp_desc(const Buffers& bf, const FeatSource& src, int Vh) const;      // the one-launch per-point branch on views 0 .. Vh - 1
   int stage_out(const Buffers& bf, int B, const Outputs& out, hipStream_t s) const;      // the staged point / pose results -> the ten outputs
-  int pose_branch(const Buffers& bf, int Vh, const Call& call) const;
+  int pose_branch(const Buffers& bf, int Vh, const Call& call, const ForwardPaths& p) const;
   int chunk_poses(int B) const;      // baseline: poses per launch of the attention stack (max_chunk views)
   int layer4_index() const { return (3 * n_blocks) & 3; }      // which of the rotating buffers bf.lb holds the layer4 output (debug fetch)
 
   // exposed for layer-level tests
-  int plan(int B, Arena& A, Buffers& bf) const;
+  int plan(int B, const ForwardPaths& p, Arena& A, Buffers& bf) const;
+  // What every forward does in front of its first launch: the workspace is aligned and holds the plan of B poses behind `head` bytes
+  // (forward_samples' staging block), which is laid out into bf.  The size error reads pre + "workspace too small: need N" + post.
+  int open_workspace(int B, const ForwardPaths& p, void* workspace, size_t workspace_size, size_t head, const char* pre, const char* post,
+                     Buffers& bf) const;
   // img2 == nullptr: all V views (any V >= 1) lie in img1
   // samples > 1: V = samples x 2B views, the 2B input views shared up to up_1's stacked GEMM (forward_samples)
-  int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, const Call& call, int samples = 1) const;
-  int cost_volume(const Buffers& bf, int V, int B, const float* depths, const Call& call) const;
+  int pspnet(const Buffers& bf, int V, const float* img1, const float* img2, const Call& call, const ForwardPaths& p, int samples = 1) const;
+  // behind the PSPNet, split pairs: the plain-fp32 copy of the feature map where the paths ask for it
+  int feat_copy(const Buffers& bf, int V, const Call& call, const ForwardPaths& p) const;
+  int cost_volume(const Buffers& bf, int V, int B, const float* depths, const Call& call, const ForwardPaths& p) const;
   int chunk_views(int V) const;
-  // bf16x3 on the default path: nothing reads the split-pair feature map (the sweep and the point heads gather from plain fp32), so
-  // `final` writes fp32 directly; the A/B paths (materialised volume, halo-tile conv0, per-sample BN) still want split pairs
-  bool feat_f32_only() const;
-  bool feat_f16() const;        // bf16 nets: the feature map (bf.feat) holds f16 in this forward (option sweep_f16 and the paths that can produce / consume it)
-  // the sparse tail (conv11 + prob only where prob is gathered: option sparse_tail) runs in a call that is not dense, and with it
-  // cost_volume() skips tiles outside the chosen pixels' dependency cones (option sparse_dec)
-  bool sparse_tail_active(bool dense) const;
-  bool sparse_active(bool dense = false) const;
 };
 
 const char* last_error_cstr();

@@ -31,7 +31,7 @@ for f in conv_igemm.hip conv_igemm_glds.hip conv3d_tile.hip conv0_sweep.hip conv
     pids+=($!)
   fi
 done
-for f in layers.cpp adapose.cpp capi.cpp prof.cpp conv_plan.cpp; do
+for f in layers.cpp adapose.cpp capi.cpp prof.cpp conv_plan.cpp forward_paths.cpp; do
   hipcc $FLAGS -x hip -c "$f" -o build/${f%.cpp}.o &
   pids+=($!)
 done

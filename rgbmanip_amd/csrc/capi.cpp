@@ -510,13 +510,38 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
   return finish_call(h, B, call, 0);
 }
 
+static_assert(sizeof(PathFacts) == RGBM_PATH_FACT_INTS * sizeof(int32_t) && sizeof(ForwardPaths) == RGBM_PATH_INTS * sizeof(int32_t),
+              "rgbm.h documents PathFacts and ForwardPaths int by int");
+
+int rgbm_forward_paths(const int32_t* facts, int n_rows, int32_t* paths) {
+  RGBM_REQUIRE(facts && paths && n_rows > 0, "forward_paths arguments");
+  for (int r = 0; r < n_rows; ++r) {
+    PathFacts f;
+    memcpy(&f, facts + (size_t)r * RGBM_PATH_FACT_INTS, sizeof(f));
+    if (f.flags < 0) f.flags = g_debug_flags;
+    const ForwardPaths p = forward_paths(f);
+    memcpy(paths + (size_t)r * RGBM_PATH_INTS, &p, sizeof(p));
+  }
+  return 0;
+}
+
+int rgbm_adapose_paths(rgbm_adapose_t* h, int B, int dense, int32_t* facts_out, int32_t* paths_out) {
+  RGBM_REQUIRE(h && B > 0 && (dense == 0 || dense == 1) && facts_out && paths_out, "adapose_paths arguments");
+  const PathFacts f = h->net.path_facts(B, dense != 0);
+  const ForwardPaths p = forward_paths(f);
+  memcpy(facts_out, &f, sizeof(f));
+  memcpy(paths_out, &p, sizeof(p));
+  return 0;
+}
+
 int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* name, float* out_dev, size_t capacity,
                        size_t* n_elems, void* stream) {
   RGBM_REQUIRE(h && workspace && name && out_dev && n_elems, "fetch arguments");
   const AdaPose& n = h->net;
+  const ForwardPaths p = n.paths(B);      // of a plain forward issued now: what the forward whose workspace this is ran, unless options or flags changed since
   Arena A(workspace, 0);
   AdaPose::Buffers bf;
-  n.plan(B, A, bf);
+  n.plan(B, p, A, bf);
   const size_t V = 2 * (size_t)B, S = n.img, P = n.n_pts, D = n.n_depth;
   const size_t Vc = n.chunk_views((int)V);
   const std::string nm = name;
@@ -528,7 +553,7 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   else if (nm == "u1") { src = bf.u1; cnt = V * (S / 4) * (S / 4) * 256; }
   else if (nm == "u2") { src = bf.u2; cnt = V * (S / 2) * (S / 2) * 64; }
   else if (nm == "u3") { src = bf.u3; cnt = V * S * S * 64; }
-  else if (nm == "feat") { src = bf.feat; cnt = V * S * S * 32; if (n.feat_f32_only()) { src = bf.featf; dt = F32; } else if (n.feat_f16()) dt = F16; }
+  else if (nm == "feat") { src = bf.feat; cnt = V * S * S * 32; if (p.feat_form == FEAT_F32_ONLY) { src = bf.featf; dt = F32; } else if (p.feat_form == FEAT_F16) dt = F16; }
   else if (nm == "vol") { src = bf.vol; cnt = Vc * D * S * S * 32; }
   else if (nm == "homog") { src = bf.homog; cnt = V * 12; dt = F32; }
   else if (nm == "prob") { src = bf.prob; cnt = V * P * D; dt = F32; }
@@ -550,7 +575,7 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   // with sparse cost regularisation c0..c5 / u7 / u9 are written only inside the chosen pixels' dependency cones (and c6 is computed
   // from them): the rest of these tensors is whatever the workspace held, so a tap of them is refused instead of returned partly stale
   const bool tap3d = row3d >= 0 && row3d < 9;      // u11 exists only with the dense tail, which computes all of it
-  RGBM_REQUIRE(!(tap3d && n.sparse_active()), "tap '" + nm + "' needs a dense cost regularisation: set option sparse_dec = 0 before the forward "
+  RGBM_REQUIRE(!(tap3d && p.mask_level > 0), "tap '" + nm + "' needs a dense cost regularisation: set option sparse_dec = 0 before the forward "
                "(the default computes it only inside the chosen pixels' dependency cones)");
   *n_elems = cnt;
   RGBM_REQUIRE(cnt <= capacity, "fetch capacity too small");

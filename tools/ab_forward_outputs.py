@@ -7,7 +7,9 @@ usage: ab_forward_outputs.py out.npz            (in each tree)
 Only the Python names both trees have are used.  Arrays are compared as bytes (view2_heads = 0 fills the view-2 outputs with NaN).
 Besides the forwards of the v5 and the baseline network the list holds the 3-D taps of a dense cost regularisation (element count and
 SHA-256 each), and under "sizes" the node counts of the captured graphs, workspace_bytes(B) for B = 1, 2, 3, 256 and feature_bytes
-(the baseline network has no feature cache, so only its workspace sizes are listed)."""
+(the baseline network has no feature cache, so only its workspace sizes are listed).  The path-selection block runs every option value
+and debug flag that moves a decision of the forward (csrc/forward_paths.cpp) once: B = 2 plain and dense, the captured B = 1 forward, and
+under "sizes" that configuration's workspace, dense-workspace and feature sizes and node count; an fp16 net, forward_samples at S = 2."""
 import hashlib
 import os
 import sys
@@ -41,6 +43,7 @@ def main(path):
 
     def put(name, pred):
         torch.cuda.synchronize()
+        print(name, flush=True)
         for k, v in pred.items():
             out[f"{name} | {k}"] = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
@@ -115,6 +118,48 @@ def main(path):
             for t in taps:
                 a = net.fetch(1, t, 2 * 24 * 224 * 224 * 8).cpu().numpy()
                 put(f"{dt} sparse_dec=0 B=1 tap {t}", {"count": a.size, "sha256": np.frombuffer(hashlib.sha256(a.tobytes()).digest(), np.uint8)})
+    # path selection: every option value and debug flag that moves a decision of the forward, once each at B = 2 (eager), with the sizes
+    # the configuration asks for and the node count of its captured B = 1 forward
+    from rgbmanip_amd import _lib
+    lib = _lib.load()
+
+    def config(name, dt, flags=0, state=sd, **kw):
+        _lib.check(lib.rgbm_debug_flags(flags), "rgbm_debug_flags")
+        try:
+            net = AdaPoseNet(state, dtype=dt, **kw)
+            put(f"{name} B=2", call(net, 2))
+            sz = [net.workspace_bytes(1), net.workspace_bytes(2), net.workspace_bytes(256)]
+            if net.arch == "v5":      # the baseline network has neither dense calls, a feature cache nor graph replay
+                put(f"{name} B=2 dense_depth", call(net, 2, dense_depth=True))
+                sz += [net.dense_workspace_bytes(1), net.dense_workspace_bytes(2), net.feature_bytes]
+                net.graph = True
+                call(net, 1)
+                put(f"{name} graph B=1", call(net, 1))
+                sz.append(net.last_graph_nodes)
+            sizes[name] = sz
+        finally:
+            _lib.check(lib.rgbm_debug_flags(0), "rgbm_debug_flags")
+
+    for dt in ("bf16", "bf16x3", "fp32"):
+        for opts in ({"sweep_f16": 0}, {"upconv": 0}, {"upconv": 3}, {"upconv": 4}, {"stem": 0}, {"fuse_final": 0}, {"igemm_conv6": 0},
+                     {"sparse_dec": 1}, {"sparse_tail": 0}):
+            if dt == "fp32" and next(iter(opts)) in ("sweep_f16", "igemm_conv6", "sparse_dec", "sparse_tail", "stem"):
+                continue      # no pack of an fp32 net answers to these: the defaults above cover it
+            config(f"{dt} options {opts}", dt, options=opts)
+        for flag in (1024, 2048, 4096, 524288):
+            config(f"{dt} debug flag {flag}", dt, flags=flag)
+    config("fp16", "fp16")
+    config("fp16 options {'sparse_dec': 0}", "fp16", options={"sparse_dec": 0})
+    for rp in (True, False):
+        config(f"bf16 baseline regress_pose={rp} options {{'upconv': 0, 'stem': 0}}", "bf16", state=synth.baseline_state_dict(seed=0, regress_pose=rp),
+               arch="baseline", regress_pose=rp, options={"upconv": 0, "stem": 0})
+        config(f"bf16 baseline regress_pose={rp} debug flags 1024 + 2048 + 524288", "bf16", flags=1024 | 2048 | 524288,
+               state=synth.baseline_state_dict(seed=0, regress_pose=rp), arch="baseline", regress_pose=rp)
+    for dt in ("bf16", "bf16x3"):
+        net = AdaPoseNet(sd, dtype=dt, dropout=0.1, dropout_seed=3)
+        i = inputs[2]
+        put(f"{dt} forward_samples S=2 B=2", net.forward_samples(i["img1"], i["choose1"], i["img2"], i["choose2"], i["P1"], i["P2"], i["depths"], 2))
+        sizes[f"{dt} samples_workspace_bytes"] = [net.samples_workspace_bytes(2, 2)]
     # what a captured forward consists of, and what the plan asks for
     for dt in ("bf16", "bf16x3", "fp32"):
         net = AdaPoseNet(sd, dtype=dt, graph=True)
