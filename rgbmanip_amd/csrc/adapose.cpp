@@ -30,7 +30,7 @@ static const HostTensor* find(const StateDict& sd, const std::string& name) {
   const HostTensor* var = find(sd, name);                            \
   RGBM_REQUIRE(var != nullptr, std::string("missing weight ") + (name))
 
-static int init_conv2d(ConvLayer& L, int dtype, const StateDict& sd, const std::string& wname, const char* bname, int Cin,
+static int init_conv2d(ConvLayer& L, const std::shared_ptr<ConvScratch>& scratch, int dtype, const StateDict& sd, const std::string& wname, const char* bname, int Cin,
                        int Cout, int k, int stride, int pad, int dil, int act, float slope, int Cin_pad) {
   GET(w, wname);
   RGBM_REQUIRE(w->numel() == (long long)Cout * Cin * k * k, "weight shape " + wname);
@@ -39,7 +39,7 @@ static int init_conv2d(ConvLayer& L, int dtype, const StateDict& sd, const std::
   ConvGeom g;
   g.Cin = Cin; g.Cout = Cout; g.KH = g.KW = k; g.sh = g.sw = stride; g.ph = g.pw = pad; g.dilh = g.dilw = dil;
   g.act = act; g.slope = slope;
-  return L.init(dtype, g, w->data, b, nullptr, nullptr, Cin_pad, Cout);
+  return L.init(dtype, g, w->data, b, nullptr, nullptr, Cin_pad, Cout, scratch);
 }
 
 static int bn_fold(const StateDict& sd, const std::string& p, int C, std::vector<float>& scale, std::vector<float>& shift) {
@@ -62,12 +62,12 @@ static ConvGeom cost3d_geom(const Cost3dLayer& L, int act) {
   return g;
 }
 
-static int init_linear(ConvLayer& L, const StateDict& sd, const std::string& p, int Cin, int Cout, int act, int Cin_pad,
+static int init_linear(ConvLayer& L, const std::shared_ptr<ConvScratch>& scratch, const StateDict& sd, const std::string& p, int Cin, int Cout, int act, int Cin_pad,
                        int Cout_pad, const float* w_override = nullptr, int ldtype = F32) {
   GET(w, p + ".weight"); GET(b, p + ".bias");
   ConvGeom g;
   g.Cin = Cin; g.Cout = Cout; g.act = act;
-  return L.init(ldtype, g, w_override ? w_override : w->data, b->data, nullptr, nullptr, Cin_pad, Cout_pad);
+  return L.init(ldtype, g, w_override ? w_override : w->data, b->data, nullptr, nullptr, Cin_pad, Cout_pad, scratch);
 }
 
 int AdaPose::create(const StateDict& sd, int dtype_, int norm_mode_) {
@@ -121,7 +121,7 @@ int AdaPose::create_backbone(const StateDict& sd) {
   const int E = dtype_chunk(dtype);
   img_cpad = E;                              // RGB padded to one 16-byte chunk
   const std::string fe = "img_extractor.feats.";
-  if (int rc = init_conv2d(conv1, dtype, sd, fe + "conv1.weight", nullptr, 3, 64, 7, 2, 3, 1, ACT_RELU, 0.f, img_cpad)) return rc;
+  if (int rc = init_conv2d(conv1, scratch, dtype, sd, fe + "conv1.weight", nullptr, 3, 64, 7, 2, 3, 1, ACT_RELU, 0.f, img_cpad)) return rc;
   if (dtype != F32) {
     GET(w1, fe + "conv1.weight");
     RGBM_REQUIRE(w1->numel() == 64 * 3 * 7 * 7, "conv1 shape");
@@ -141,31 +141,31 @@ int AdaPose::create_backbone(const StateDict& sd) {
       const int stride = b == 0 ? kLayerStride[li] : 1;
       const int dil = b == 0 ? 1 : kLayerDil[li];      // block 0 never dilated (pspnet.py:59-62)
       const std::string p = fe + "layer" + std::to_string(li + 1) + "." + std::to_string(b) + ".";
-      if (int rc = init_conv2d(blk.c1, dtype, sd, p + "conv1.weight", nullptr, cin, planes, 3, stride, dil, dil, ACT_RELU, 0.f, cin)) return rc;
-      if (int rc = init_conv2d(blk.c2, dtype, sd, p + "conv2.weight", nullptr, planes, planes, 3, 1, dil, dil, ACT_RELU, 0.f, planes)) return rc;
+      if (int rc = init_conv2d(blk.c1, scratch, dtype, sd, p + "conv1.weight", nullptr, cin, planes, 3, stride, dil, dil, ACT_RELU, 0.f, cin)) return rc;
+      if (int rc = init_conv2d(blk.c2, scratch, dtype, sd, p + "conv2.weight", nullptr, planes, planes, 3, 1, dil, dil, ACT_RELU, 0.f, planes)) return rc;
       blk.has_ds = find(sd, p + "downsample.0.weight") != nullptr;
       if (blk.has_ds)
-        if (int rc = init_conv2d(blk.ds, dtype, sd, p + "downsample.0.weight", nullptr, cin, planes, 1, stride, 0, 1, ACT_NONE, 0.f, cin)) return rc;
+        if (int rc = init_conv2d(blk.ds, scratch, dtype, sd, p + "downsample.0.weight", nullptr, cin, planes, 1, stride, 0, 1, ACT_NONE, 0.f, cin)) return rc;
       blk.stride = stride; blk.planes = planes;
     }
     inpl = kLayerPlanes[li];
   }
   n_blocks = nb;
   for (int i = 0; i < 4; ++i)
-    if (int rc = init_conv2d(psp[i], dtype, sd, "img_extractor.psp.stages." + std::to_string(i) + ".1.weight", nullptr, 512, 128, 1, 1, 0, 1, ACT_RELU, 0.f, 512)) return rc;
+    if (int rc = init_conv2d(psp[i], scratch, dtype, sd, "img_extractor.psp.stages." + std::to_string(i) + ".1.weight", nullptr, 512, 128, 1, 1, 0, 1, ACT_RELU, 0.f, 512)) return rc;
   struct { ConvLayer* L; const char* nm; int cin, cout; } ups[3] = {{&up1, "up_1", 1024, 256}, {&up2, "up_2", 256, 64}, {&up3, "up_3", 64, 64}};
   for (auto& u : ups) {
     const std::string p = std::string("img_extractor.") + u.nm + ".conv.";
     GET(sl, p + "1.weight");
     const std::string bn = p + "0.bias";
-    if (int rc = init_conv2d(*u.L, dtype, sd, p + "0.weight", bn.c_str(), u.cin, u.cout, 3, 1, 1, 1, ACT_PRELU, sl->data[0], u.cin)) return rc;
+    if (int rc = init_conv2d(*u.L, scratch, dtype, sd, p + "0.weight", bn.c_str(), u.cin, u.cout, 3, 1, 1, 1, ACT_PRELU, sl->data[0], u.cin)) return rc;
     UpConvLayer* uc = u.L == &up1 ? &up1c : u.L == &up2 ? &up2c : nullptr;
     if (uc) {
       GET(w, p + "0.weight"); GET(b, bn);
-      if (int rc = uc->init(dtype, u.cin, u.cout, w->data, b->data, ACT_PRELU, sl->data[0])) return rc;
+      if (int rc = uc->init(dtype, u.cin, u.cout, w->data, b->data, ACT_PRELU, sl->data[0], scratch)) return rc;
     }
   }
-  if (int rc = init_conv2d(fin, dtype, sd, "img_extractor.final.weight", "img_extractor.final.bias", 64, 32, 1, 1, 0, 1, ACT_NONE, 0.f, 64)) return rc;
+  if (int rc = init_conv2d(fin, scratch, dtype, sd, "img_extractor.final.weight", "img_extractor.final.bias", 64, 32, 1, 1, 0, 1, ACT_NONE, 0.f, 64)) return rc;
   if (dtype != F32) {
     GET(w3, "img_extractor.up_3.conv.0.weight"); GET(b3, "img_extractor.up_3.conv.0.bias"); GET(s3, "img_extractor.up_3.conv.1.weight");
     GET(wf, "img_extractor.final.weight"); GET(bfin, "img_extractor.final.bias");
@@ -185,10 +185,10 @@ int AdaPose::create_cost(const StateDict& sd) {
     RGBM_REQUIRE(w->numel() == (long long)L.cout * L.cin * 27, "weight shape " + p);
     std::vector<float> scale, shift, packed;
     if (int rc = bn_fold(sd, p + "bn.", L.cout, scale, shift)) return rc;
-    if (int rc = c3d[i].init(dtype, cost3d_geom(L, ACT_RELU), w->data, nullptr, scale.data(), shift.data(), L.cin, L.cout)) return rc;
+    if (int rc = c3d[i].init(dtype, cost3d_geom(L, ACT_RELU), w->data, nullptr, scale.data(), shift.data(), L.cin, L.cout, scratch)) return rc;
     if (norm_mode == 1) {
       GET(gm, p + "bn.weight"); GET(bt, p + "bn.bias");
-      if (int rc = c3d_raw[i].init(dtype, cost3d_geom(L, ACT_NONE), w->data, nullptr, nullptr, nullptr, L.cin, L.cout)) return rc;
+      if (int rc = c3d_raw[i].init(dtype, cost3d_geom(L, ACT_NONE), w->data, nullptr, nullptr, nullptr, L.cin, L.cout, scratch)) return rc;
       if (upload_f32(gm->data, L.cout, bn_gamma[i])) return -2;
       if (upload_f32(bt->data, L.cout, bn_beta[i])) return -2;
     }
@@ -234,13 +234,13 @@ int AdaPose::create_cost(const StateDict& sd) {
 // pts_mlp = false (the baseline network without its pose branch has no nocs_pts_mlp): layers 4 / 5 of the point kernel's table are zero
 int AdaPose::create_point_heads(const StateDict& sd, bool pts_mlp) {
   // fp32 point heads as 1x1 convs
-  if (int rc = init_linear(inst, sd, "instance_color.0", 32, 64, ACT_RELU, 32, 64)) return rc;
-  if (int rc = init_linear(nh[0], sd, "nocs_head.0", 64, 128, ACT_RELU, 64, 128)) return rc;
-  if (int rc = init_linear(nh[1], sd, "nocs_head.2", 128, 64, ACT_RELU, 128, 64)) return rc;
-  if (int rc = init_linear(nh[2], sd, "nocs_head.4", 64, 3, ACT_TANH, 64, 4)) return rc;
+  if (int rc = init_linear(inst, scratch, sd, "instance_color.0", 32, 64, ACT_RELU, 32, 64)) return rc;
+  if (int rc = init_linear(nh[0], scratch, sd, "nocs_head.0", 64, 128, ACT_RELU, 64, 128)) return rc;
+  if (int rc = init_linear(nh[1], scratch, sd, "nocs_head.2", 128, 64, ACT_RELU, 128, 64)) return rc;
+  if (int rc = init_linear(nh[2], scratch, sd, "nocs_head.4", 64, 3, ACT_TANH, 64, 4)) return rc;
   if (pts_mlp) {
-    if (int rc = init_linear(npm[0], sd, "nocs_pts_mlp.0", 3, 32, ACT_RELU, 4, 32)) return rc;
-    if (int rc = init_linear(npm[1], sd, "nocs_pts_mlp.2", 32, 64, ACT_RELU, 32, 64)) return rc;
+    if (int rc = init_linear(npm[0], scratch, sd, "nocs_pts_mlp.0", 3, 32, ACT_RELU, 4, 32)) return rc;
+    if (int rc = init_linear(npm[1], scratch, sd, "nocs_pts_mlp.2", 32, 64, ACT_RELU, 32, 64)) return rc;
   }
   {
     // the same six layers as one LDS image for point_mlp_kernel (head_kernels.hip)
@@ -262,19 +262,19 @@ int AdaPose::create_point_heads(const StateDict& sd, bool pts_mlp) {
 }
 
 int AdaPose::create_pose(const StateDict& sd) {
-  if (int rc = init_linear(pm1[0], sd, "pose_mlp1.0", 96, 128, ACT_RELU, 96, 128, nullptr, pose_dtype())) return rc;
-  if (int rc = init_linear(pm1[1], sd, "pose_mlp1.2", 128, 128, ACT_RELU, 128, 128, nullptr, pose_dtype())) return rc;
+  if (int rc = init_linear(pm1[0], scratch, sd, "pose_mlp1.0", 96, 128, ACT_RELU, 96, 128, nullptr, pose_dtype())) return rc;
+  if (int rc = init_linear(pm1[1], scratch, sd, "pose_mlp1.2", 128, 128, ACT_RELU, 128, 128, nullptr, pose_dtype())) return rc;
   {
     // pose_mlp2.0 sees cat(point feature[128], global mean[128]); the global half becomes a per-view bias
     GET(w, "pose_mlp2.0.weight"); GET(b, "pose_mlp2.0.bias");
     RGBM_REQUIRE(w->numel() == 256 * 256, "pose_mlp2.0 shape");
     std::vector<float> wl(256 * 128);
     for (int o = 0; o < 256; ++o) for (int i = 0; i < 128; ++i) wl[o * 128 + i] = w->data[o * 256 + i];
-    if (int rc = init_linear(pm2[0], sd, "pose_mlp2.0", 128, 256, ACT_RELU, 128, 256, wl.data(), pose_dtype())) return rc;
+    if (int rc = init_linear(pm2[0], scratch, sd, "pose_mlp2.0", 128, 256, ACT_RELU, 128, 256, wl.data(), pose_dtype())) return rc;
     if (upload_f32(w->data, 256 * 256, pm2_0_wfull)) return -2;
     if (upload_f32(b->data, 256, pm2_0_bias)) return -2;
   }
-  if (int rc = init_linear(pm2[1], sd, "pose_mlp2.2", 256, 256, ACT_RELU, 256, 256, nullptr, pose_dtype())) return rc;
+  if (int rc = init_linear(pm2[1], scratch, sd, "pose_mlp2.2", 256, 256, ACT_RELU, 256, 256, nullptr, pose_dtype())) return rc;
   const char* hn[3] = {"rotation_estimator", "translation_estimator", "size_estimator"};
   const int hout[3] = {6, 3, 3};
   for (int h = 0; h < 3; ++h) {

@@ -40,6 +40,8 @@ struct AdaPose {
   int img_cpad = 4;
   int max_chunk = 512;           // views per cost-volume chunk (bounds the workspace: ~80 MB per view in bf16; 512 = batch 256 in one chunk)
 
+  // the K-split buffers (per stream) and identity matrices of this net's implicit-GEMM launches: handed to every ConvLayer below, freed with the net
+  std::shared_ptr<ConvScratch> scratch = std::make_shared<ConvScratch>();
   struct Block { ConvLayer c1, c2, ds; bool has_ds = false; int stride = 1, planes = 0; };
   ConvLayer conv1;
   Block blocks[16];

@@ -24,8 +24,8 @@ using namespace rgbm;
 
 // One captured forward: the launch sequence of AdaPose::forward for a fixed batch size and fixed device pointers, replayed with a
 // single hipGraphLaunch (small batches are launch-bound: ~150 launches of a few microseconds each per forward).  The capture stream is part
-// of the key: the K-split scratch and its arrival counters belong to the capture stream (m32_ksplit_buffers), so a replay on another stream
-// would share them with whatever runs on the first.
+// of the key: the graph's split launches point at the net's scratch for that stream (ConvScratch, layers.h), so a replay on another stream
+// would share the partial sums and arrival counters with whatever this net runs on the first.
 struct ForwardGraph {
   int B = 0;
   hipStream_t stream = nullptr;
@@ -620,6 +620,14 @@ int rgbm_adv_normalise(int64_t n_local, float* adv, const double* sums, double c
   return launch_adv_normalise(n_local, adv, sums, count_total, (hipStream_t)stream);
 }
 
+// The one-shot entry points below (tests) build a layer, run it and free it; their launches share ONE ConvScratch that lives as long as
+// the process, so consecutive calls on a stream see the K-split counters the previous call left (zero), as a net's launches do.  Never
+// destroyed: nothing is freed behind the runtime's own teardown at exit.
+static const std::shared_ptr<ConvScratch>& one_shot_scratch() {
+  static const auto* const scratch = new std::shared_ptr<ConvScratch>(std::make_shared<ConvScratch>());
+  return *scratch;
+}
+
 static ConvGeom conv_nd_geom(int Cin, int Cout, int KD, int KH, int KW, int stride_d, int stride_hw, int pad_d, int pad_hw, int dil_hw,
                              int transposed, int act, float slope) {
   ConvGeom g;
@@ -636,7 +644,7 @@ int rgbm_conv_nd(int dtype, const void* in_dev, int N, int D, int H, int W, int 
   RGBM_REQUIRE(in_dev && w_host && out_dev, "conv arguments");
   const ConvGeom g = conv_nd_geom(Cin, Cout, KD, KH, KW, stride_d, stride_hw, pad_d, pad_hw, dil_hw, transposed, act, slope);
   ConvLayer L;
-  if (int rc = L.init(dtype, g, w_host, bias_host, bn_scale_host, bn_shift_host, Cin_pad, Cout_pad)) return rc;
+  if (int rc = L.init(dtype, g, w_host, bias_host, bn_scale_host, bn_shift_host, Cin_pad, Cout_pad, one_shot_scratch())) return rc;
   return finish_one_shot(L.run(in_dev, out_dev, N, D, H, W, Cout_pad, res_dev, res_mode, nullptr, 0, (hipStream_t)stream), stream);
 }
 
@@ -724,7 +732,7 @@ int rgbm_upsample_conv3x3(int dtype, const void* in_dev, int V, int h, int w, in
                           const float* bias_host, int act, float slope, void* z_scratch_dev, void* out_dev, void* stream) {
   RGBM_REQUIRE(in_dev && w_host && z_scratch_dev && out_dev, "upsample_conv3x3 arguments");
   UpConvLayer L;
-  if (int rc = L.init(dtype, Cin, Cout, w_host, bias_host, act, slope)) return rc;
+  if (int rc = L.init(dtype, Cin, Cout, w_host, bias_host, act, slope, one_shot_scratch())) return rc;
   return finish_one_shot(L.run(in_dev, z_scratch_dev, out_dev, V, h, w, Cout, (hipStream_t)stream), stream);
 }
 

@@ -269,8 +269,8 @@ struct ConvDesc {
   // persistent kernel only (filled by its launcher): tiles in total, and exact-division magics for Wq, Hq, Dq
   int n_tiles; unsigned fd_m[3]; int fd_s[3];
   int korder;                             // K-tile walk of the request waves: 1 = channel block outer, taps inner; 0 = taps outer
-  int buf_ok;                             // request waves may use 32-bit buffer offsets for both operands (set by the launcher)
-  const void* ident;                      // conv_igemm_m32_kernel<256 pixels>: 256 x 256 identity in the storage type (residual steps), set by the launcher
+  int buf_ok;                             // request waves may use 32-bit buffer offsets for both operands (ConvPlan::buf_ok)
+  const void* ident;                      // conv_igemm_m32_kernel<256 pixels>: 256 x 256 identity in the storage type (residual steps), the ConvScratch's
   long long m0;                           // first GEMM row of this launch (conv_igemm_m32_kernel: a layer split into a main and a tail launch)
   // optional 1x1 conv fused behind the activation (conv_igemm_ws64_kernel only): y2 = act2(W2 . act(y) + bias2); when set,
   // `out` is not written.  w2: [cout2_pad][kpad2] K-major bf16 rows of 64 input channels.
@@ -283,15 +283,16 @@ struct ConvDesc {
   int ksplit; float* kscratch; unsigned* kcount;
   // conv_igemm_m32_kernel, 256 x 256 tiles of border classes (conv_plan.h, plan_border).  w_finite: the layer's packed weights hold no
   // NaN / inf (set at create; the plan declines otherwise: NaN * 0 is the one product a skipped padding tap would change).  btab: the
-  // layer's device table for this shape, set by ConvLayer::run (null: row-major tiles): [0, b_nwg] first entry of each workgroup, then at
+  // layer's device table for this shape, set by ConvLayer::launch (null: row-major tiles): [0, b_nwg] first entry of each workgroup, then at
   // int b_ent four ints per tile in workgroup-major order {first table row, K steps without the residual steps,
   // kh0 | kh1 << 4 | kw0 << 8 | kw1 << 12 | channel tile << 16, 0}, then at int b_rows the GEMM row of every table row (-1: dead).
   int w_finite; const int* btab; int b_nwg, b_ent, b_rows;
 };
 
-int launch_conv(const ConvDesc& d, int dtype, hipStream_t s);
-// true if launch_conv would run d on the three-role 64-channel kernel (the only one that can fuse a trailing 1x1)
-bool conv_ws64_eligible(const ConvDesc& d, int dtype);
+// launches d on the kernel and tiles that p, plan_conv's plan of d (conv_plan.h), names; d's launch-time fields are already bound
+// (ConvLayer::launch, layers.h)
+struct ConvPlan;
+int launch_conv(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s);
 // picks the channel-tile size used by launch_conv for Cout (weights must be padded to it)
 int conv_ch_tile(int Cout);
 int conv_bk(int dtype);  // K-tile in elements

@@ -5,10 +5,7 @@
 // swizzle is applied on the SOURCE side: the lane that fills LDS slot (row, j) fetches global chunk j ^ ((row>>1)&7),
 // and readers XOR the same value (an involution).  Out-of-image / padded-K lanes fetch from a 16-byte zero page.
 #include <atomic>
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <vector>
 #include "common.h"
 #include "conv_plan.h"
 #include "kernels.h"
@@ -1329,7 +1326,7 @@ static void make_fastdiv(int dvs, unsigned& m, int& sh) {
 }
 
 template <typename T, bool WIDE, bool RH, bool SLIM = false>
-static int launch_ws(ConvDesc d, const ConvPlan& p, hipStream_t s) {
+static int launch_ws(ConvDesc d, hipStream_t s) {
   constexpr int BCH = SLIM ? 64 : WIDE ? 256 : 128, BPIX = (WIDE && !SLIM) ? 128 : 256;
   constexpr size_t LDS = (RH ? (3 * (size_t)(BCH + 136) * 8 + 8) : 3 * (size_t)(BCH + BPIX) * 8) * sizeof(uint4) + 2048 * sizeof(float);      // K-tile ring(s) + per-channel bias table
   d.n_pix_tiles = (int)((d.M + BPIX - 1) / BPIX);
@@ -1340,8 +1337,6 @@ static int launch_ws(ConvDesc d, const ConvPlan& p, hipStream_t s) {
   make_fastdiv(d.Wq, d.fd_m[0], d.fd_s[0]);
   make_fastdiv(d.Hq, d.fd_m[1], d.fd_s[1]);
   make_fastdiv(d.Dq, d.fd_m[2], d.fd_s[2]);
-  d.korder = p.korder;
-  d.buf_ok = p.buf_ok;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_igemm_ws_kernel<T, WIDE, RH, SLIM>), (int)LDS)) return rc;
   int n_cu = 0;
   if (int rc = persistent_grid_cus(&n_cu)) return rc;
@@ -1895,12 +1890,12 @@ static int launch_plan(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
     case CONV_M32_SMALL:
       if constexpr (M32) return launch_m32_small<T>(d, p, s);
       break;
-    case CONV_WS_SLIM: return launch_ws<T, false, false, true>(d, p, s);
+    case CONV_WS_SLIM: return launch_ws<T, false, false, true>(d, s);
     case CONV_M32:
       if constexpr (M32) return launch_m32<T>(d, p, s);
       break;
-    case CONV_WS_WIDE: return launch_ws<T, true, false>(d, p, s);
-    case CONV_WS: return launch_ws<T, false, false>(d, p, s);
+    case CONV_WS_WIDE: return launch_ws<T, true, false>(d, s);
+    case CONV_WS: return launch_ws<T, false, false>(d, s);
     case CONV_V3: return p.uniform_taps ? launch_v3<T, true>(d, s) : launch_v3<T, false>(d, s);
     case CONV_WS64:
     case CONV_WS64_ROWHALO:
@@ -1910,19 +1905,9 @@ static int launch_plan(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   RGBM_REQUIRE(false, "conv plan names a kernel this storage type does not have");
 }
 
-int launch_conv(const ConvDesc& d, int dtype, hipStream_t s) {
-  ConvTuning t;
-  ConvPlan p;
-  if (int rc = conv_tuning(0, &t)) return rc;
-  if (int rc = plan_conv(d, dtype, t, &p)) return rc;
+int launch_conv(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s) {
   return dtype == BF16 ? launch_plan<unsigned short>(d, p, s) : dtype == F16 ? launch_plan<f16_t>(d, p, s)
          : dtype == BF16X3 ? launch_plan<bx3_t>(d, p, s) : launch_plan<float>(d, p, s);
-}
-
-bool conv_ws64_eligible(const ConvDesc& d, int dtype) {
-  ConvTuning t;
-  ConvPlan p;
-  return !conv_tuning(0, &t) && !plan_conv(d, dtype, t, &p) && (p.kernel == CONV_WS64 || p.kernel == CONV_WS64_ROWHALO);
 }
 
 }  // namespace rgbm

@@ -892,92 +892,21 @@ static int launch_m32_range(ConvDesc d, hipStream_t s) {
   return 0;
 }
 
-// 256 x 256 identity in the storage type of T (bf16 / fp16 ones), one per device: the W operand of the residual steps
-template <typename T>
-static int m32_identity(const void** out) {
-  static std::mutex mu;
-  static std::map<int, void*> per_dev;
-  int dev = 0;
-  RGBM_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  void*& p = per_dev[dev];
-  if (!p) {
-    if (std::is_same<T, bx3_t>::value) {
-      // split pairs: element e of a 4-element chunk has its hi half in 16-bit slot e of the chunk's first 8 bytes; lo = 0
-      std::vector<unsigned short> h(256 * 256 * 2, 0);
-      for (int i = 0; i < 256; ++i) h[(i * 256 + (i & ~3)) * 2 + (i & 3)] = 0x3f80;
-      RGBM_CHECK_HIP(hipMalloc(&p, h.size() * 2));
-      RGBM_CHECK_HIP(hipMemcpy(p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    } else {
-      std::vector<unsigned short> h(256 * 256, 0);
-      const unsigned short one = std::is_same<T, f16_t>::value ? 0x3c00 : 0x3f80;
-      for (int i = 0; i < 256; ++i) h[i * 256 + i] = one;
-      RGBM_CHECK_HIP(hipMalloc(&p, h.size() * 2));
-      RGBM_CHECK_HIP(hipMemcpy(p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    }
-  }
-  *out = p;
-  return 0;
-}
-
-// K-split scratch of a stream (launches on one stream are ordered; forwards on other streams have their own): 32 MB of partial
-// accumulators + 16384 arrival counters (zero: every launch leaves them so), allocated at the first small launch on that stream —
-// in an eager forward: rgbm_adapose_forward_graph runs one in front of a capture
-static int m32_ksplit_buffers(hipStream_t s, float** scratch, unsigned** count) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, std::pair<float*, unsigned*>> per_stream;
-  int dev = 0;
-  RGBM_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  auto& e = per_stream[std::make_pair(dev, s)];
-  if (!e.first) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { *scratch = nullptr; *count = nullptr; return 0; }      // (no split in this capture)
-    float* sc = nullptr; unsigned* cn = nullptr;
-    RGBM_CHECK_HIP(hipMalloc(&sc, kM32SplitFloats * sizeof(float)));
-    RGBM_CHECK_HIP(hipMalloc(&cn, kM32SplitCounters * sizeof(unsigned)));
-    // zeroed on the stream that uses them: a plain hipMemset goes to the null stream, which a non-blocking stream (torch's side streams)
-    // does not wait for — the first split launch there could read the counters before they were zero
-    RGBM_CHECK_HIP(hipMemsetAsync(cn, 0, kM32SplitCounters * sizeof(unsigned), s));
-    e.first = sc; e.second = cn;
-  }
-  *scratch = e.first; *count = e.second;
-  return 0;
-}
-
-// What plan_conv (conv_plan.cpp) decided, for both launch forms of this kernel.  Two things are facts of the launch, not of the plan: a
-// stream that is being captured before it has K-split scratch runs unsplit, and the identity matrix is per device.
-template <typename T>
-static int m32_setup(ConvDesc& d, const ConvPlan& p, hipStream_t s) {
-  d.m0 = 0;
-  d.ident = nullptr;
-  d.korder = p.korder;
-  d.ksplit = 1; d.kscratch = nullptr; d.kcount = nullptr;
-  if (p.ksplit > 1) {
-    if (int rc = m32_ksplit_buffers(s, &d.kscratch, &d.kcount)) return rc;
-    if (d.kscratch) d.ksplit = p.ksplit;
-  }
-  return p.identity_residual ? m32_identity<T>(&d.ident) : 0;
-}
-
 template <typename T>
 static int launch_m32_tiles128(const ConvDesc& d, int bch, hipStream_t s) {
   return bch == 64 ? launch_m32_range<T, 128, 64>(d, s) : bch == 128 ? launch_m32_range<T, 128, 128>(d, s) : launch_m32_range<T, 128, 256>(d, s);
 }
 
-// CONV_M32_SMALL: every row on bch x 128 tiles
+// CONV_M32_SMALL: every row on bch x 128 tiles (d.ksplit parts of each tile's K loop where the layer bound the stream's scratch)
 template <typename T>
-static int launch_m32_small(ConvDesc d, const ConvPlan& p, hipStream_t s) {
-  if (int rc = m32_setup<T>(d, p, s)) return rc;
-  d.btab = nullptr;
+static int launch_m32_small(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   return launch_m32_tiles128<T>(d, p.bch, s);
 }
 
-// CONV_M32: rows [0, main_rows) on 256 x 256 tiles, the rest on tail_bch x 128 tiles in a second launch
+// CONV_M32: rows [0, main_rows) on 256 x 256 tiles (on border-class tiles where the layer bound their table, d.btab: conv_plan.h), the
+// rest on tail_bch x 128 tiles in a second launch
 template <typename T>
 static int launch_m32(ConvDesc d, const ConvPlan& p, hipStream_t s) {
-  if (int rc = m32_setup<T>(d, p, s)) return rc;
-  if (!p.border) d.btab = nullptr;           // (the main launch's rows on border-class tiles where the layer brought their table: conv_plan.h)
   if (p.main_rows > 0) {
     ConvDesc m = d;
     m.M = p.main_rows;
@@ -985,8 +914,8 @@ static int launch_m32(ConvDesc d, const ConvPlan& p, hipStream_t s) {
     m.algo_flops = d.algo_flops * frac; m.algo_bytes = d.algo_bytes * frac;
     if (int rc = launch_m32_range<T, 256, 256>(m, s)) return rc;
     d.m0 = m.M;
-    d.btab = nullptr;
     d.algo_flops *= 1.0 - frac; d.algo_bytes *= 1.0 - frac;
   }
+  d.btab = nullptr;
   return p.tail_bch ? launch_m32_tiles128<T>(d, p.tail_bch, s) : 0;
 }

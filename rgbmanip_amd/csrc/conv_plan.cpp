@@ -347,7 +347,7 @@ int plan_conv(const ConvDesc& d, int dtype, const ConvTuning& t, ConvPlan* out) 
   if (bits16 && uni && !(f & DBG_NO_WS64) && ch_tile == 64 && d.res_mode == RES_NONE && d.KT >= 2 && ws_rows &&
       (d.w2 ? d.Cout == 64 && d.kpad2 == 64 && (d.cout2 == 16 || d.cout2 == 32) && d.ldo2 % 4 == 0 : out16))
     return rowhalo_ok(d) && !(f & DBG_NO_ROWHALO) ? pick(CONV_WS64_ROWHALO, 64, 256) : pick(CONV_WS64, 64, 256);
-  RGBM_REQUIRE(d.w2 == nullptr, "a fused 1x1 needs the ws64 kernel (check conv_ws64_eligible first)");
+  RGBM_REQUIRE(d.w2 == nullptr, "a fused 1x1 needs the ws64 kernel (ConvLayer::run_then_1x1 then runs the two layers)");
   // 33..64 output channels where there is no ws64 kernel (split pairs, fp32) or it does not apply (residual adds): the
   // role-specialised kernel with a 64 x 256 tile and four multiply waves
   // (round 6 measured 64-channel x 256-pixel tiles of the 32x32x16 kernel for layer1's 64-channel layers at batch 256: split pairs 0.542 ms

@@ -1,6 +1,7 @@
 // Which kernel, tile and K split an implicit-GEMM convolution runs on: the decision, and nothing else.  plan_conv is a pure function
 // of its arguments (no HIP runtime call, no global read), so it can be asked without a GPU (rgbm_conv_plan in rgbm.h) and tested
-// directly; launch_conv (conv_igemm_glds.hip) gathers the ConvTuning, calls it and launches what it says.
+// directly.  A launch asks it once: ConvLayer::run / run_then_1x1 (layers.cpp) gather the ConvTuning and call it, ConvLayer::launch binds what
+// the plan needs on the device (K-split scratch, identity, border table) and launch_conv (conv_igemm_glds.hip) launches what it says.
 #pragma once
 #include <vector>
 
@@ -35,11 +36,11 @@ struct ConvPlan {
   bool uniform_taps;       // every K tile inside one tap (the UNI forms of the generic / v3 kernels)
   long long main_rows;     // CONV_M32: rows [0, main_rows) on 256 x 256 tiles
   int tail_bch;            // CONV_M32: channel tile of the 128-pixel launch of rows [main_rows, M) (0 = no tail)
-  int ksplit;              // K parts the launch asks for (1 = none); the executor runs unsplit where the stream has no scratch
+  int ksplit;              // K parts the launch asks for (1 = none); ConvLayer::launch runs it unsplit where a capture finds the stream without scratch
   bool identity_residual;  // the m32 kernels add the residual through identity K steps (else in the epilogue)
   int korder, buf_ok;      // ConvDesc fields of the same names
-  bool border;             // CONV_M32: the main launch's rows on class-pure 256 x 256 tiles from a row table (plan_border); the launcher
-                           // runs them row-major where the layer has no table for this shape yet (a capture in progress)
+  bool border;             // CONV_M32: the main launch's rows on class-pure 256 x 256 tiles from a row table (plan_border); ConvLayer::launch
+                           // runs them row-major where a capture finds the layer without a table for this shape
 };
 
 // ---- border-class tiles of a dilated 2-D conv (CONV_M32, ConvPlan::border) ------------------------------------------------------------
@@ -76,7 +77,7 @@ bool border_applies(const ConvDesc& d, int dtype, int flags, long long main_rows
 // The whole table for n_wg workgroups.  false: declined (border_applies says no).  Pure: no HIP call, no global read.
 bool plan_border(const ConvDesc& d, int dtype, int flags, long long main_rows, int n_wg, BorderPlan* out);
 
-// K-split scratch of a stream: fp32 partial accumulators and arrival counters (m32_ksplit_buffers); a split that would not fit is not planned
+// K-split scratch of a stream: fp32 partial accumulators and arrival counters (ConvScratch, layers.h); a split that would not fit is not planned
 constexpr size_t kM32SplitFloats = 8u << 20, kM32SplitCounters = 16384;
 
 // 0, or -1 with the error set where no kernel takes d (a malformed descriptor)

@@ -66,6 +66,50 @@ static int upload_bytes(const void* host, size_t bytes, DevBuf& dev) {
 
 int upload_f32(const float* host, size_t n, DevBuf& dev) { return upload_bytes(host, n * sizeof(float), dev); }
 
+int ConvScratch::ksplit(hipStream_t s, bool allocate, KSplit* out) {
+  int dev = 0;
+  RGBM_CHECK_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu_);
+  auto it = per_stream_.find(std::make_pair(dev, s));
+  if (it == per_stream_.end()) {
+    *out = KSplit();
+    if (!allocate) return 0;
+    std::pair<DevBuf, DevBuf> e;
+    RGBM_CHECK_HIP(hipMalloc(e.first.out(), kM32SplitFloats * sizeof(float)));
+    RGBM_CHECK_HIP(hipMalloc(e.second.out(), kM32SplitCounters * sizeof(unsigned)));
+    // zeroed on the stream that uses them: a plain hipMemset goes to the null stream, which a non-blocking stream (torch's side streams)
+    // does not wait for — the first split launch there could read the counters before they were zero
+    RGBM_CHECK_HIP(hipMemsetAsync(e.second.get(), 0, kM32SplitCounters * sizeof(unsigned), s));
+    it = per_stream_.emplace(std::make_pair(dev, s), std::move(e)).first;
+  }
+  out->scratch = it->second.first.get<float>();
+  out->count = it->second.second.get<unsigned>();
+  return 0;
+}
+
+int ConvScratch::identity(int dtype, const void** out) {
+  RGBM_REQUIRE(dtype == BF16 || dtype == F16 || dtype == BF16X3, "identity matrix: 16-bit or split-pair storage");
+  int dev = 0;
+  RGBM_CHECK_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu_);
+  DevBuf& p = ident_[std::make_pair(dev, dtype)];
+  if (!p) {
+    // bf16 / fp16 ones on the diagonal.  Split pairs: element e of a 4-element chunk has its hi half in 16-bit slot e of the chunk's
+    // first 8 bytes; lo = 0
+    const bool x3 = dtype == BF16X3;
+    std::vector<unsigned short> h(256 * 256 * (x3 ? 2 : 1), 0);
+    for (int i = 0; i < 256; ++i) {
+      if (x3) h[(i * 256 + (i & ~3)) * 2 + (i & 3)] = 0x3f80;
+      else h[i * 256 + i] = dtype == F16 ? 0x3c00 : 0x3f80;
+    }
+    DevBuf m;
+    if (int rc = upload_bytes(h.data(), h.size() * 2, m)) return rc;
+    p = std::move(m);
+  }
+  *out = p.get();
+  return 0;
+}
+
 static inline unsigned short host_f32_to_f16(float f) {
   const _Float16 h = (_Float16)(f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f));      // round to nearest even, saturating
   unsigned short u;
@@ -147,8 +191,9 @@ struct BorderTables {
 };
 
 int ConvLayer::init(int dtype_, const ConvGeom& g_, const float* w, const float* bias_h, const float* bn_scale,
-                    const float* bn_shift, int Cin_pad_, int Cout_pad_) {
+                    const float* bn_shift, int Cin_pad_, int Cout_pad_, std::shared_ptr<ConvScratch> scratch_) {
   g = g_;
+  scratch = std::move(scratch_);
   dtype = dtype_;
   Cin_pad = Cin_pad_;
   Cout_pad = Cout_pad_;
@@ -270,23 +315,20 @@ int ConvLayer::build_desc(ConvDesc& d, const void* in, void* out, int N, int Di,
   return 0;
 }
 
-int ConvLayer::attach_border(ConvDesc& d, hipStream_t s) const {
-  if (!border || !w_finite || g.transposed || dtype == F32 || g.KH * g.KW == 1) return 0;
-  ConvTuning t;
-  ConvPlan p;
-  if (int rc = conv_tuning(0, &t)) return rc;
-  if (int rc = plan_conv(d, dtype, t, &p)) return rc;
-  if (p.kernel != CONV_M32 || !p.border) return 0;
+static bool stream_is_capturing(hipStream_t s) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+int ConvLayer::attach_border(ConvDesc& d, const ConvPlan& p, int n_cu, int flags, bool upload) const {
   int dev = 0;
   RGBM_CHECK_HIP(hipGetDevice(&dev));
-  const std::array<long long, 7> key = {dev, d.N, d.Hi, d.Wi, t.n_cu, p.identity_residual ? 1 : 0, p.main_rows};
+  const std::array<long long, 7> key = {dev, d.N, d.Hi, d.Wi, n_cu, p.identity_residual ? 1 : 0, p.main_rows};
   std::lock_guard<std::mutex> lock(border->mu);
   auto it = border->per_shape.find(key);
   if (it == border->per_shape.end()) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return 0;      // (no upload inside a capture)
     BorderPlan bp;
-    if (!plan_border(d, dtype, t.flags, p.main_rows, t.n_cu, &bp)) return 0;
+    if (!upload || !plan_border(d, dtype, flags, p.main_rows, n_cu, &bp)) return 0;
     std::vector<int> tab(bp.wg_off);
     BorderTables::Entry e;
     e.n_wg = bp.n_wg;
@@ -301,8 +343,7 @@ int ConvLayer::attach_border(ConvDesc& d, hipStream_t s) const {
     }
     e.b_rows = (int)tab.size();
     tab.insert(tab.end(), bp.rows.begin(), bp.rows.end());
-    RGBM_CHECK_HIP(hipMalloc(e.buf.out(), tab.size() * sizeof(int)));
-    RGBM_CHECK_HIP(hipMemcpy(e.buf.get(), tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (int rc = upload_bytes(tab.data(), tab.size() * sizeof(int), e.buf)) return rc;
     it = border->per_shape.emplace(key, std::move(e)).first;
   }
   d.btab = it->second.buf.get<int>();
@@ -310,14 +351,46 @@ int ConvLayer::attach_border(ConvDesc& d, hipStream_t s) const {
   return 0;
 }
 
+int ConvLayer::launch(ConvDesc& d, const ConvPlan& p, const ConvTuning& t, hipStream_t s) const {
+  d.m0 = 0;
+  d.korder = p.korder; d.buf_ok = p.buf_ok;
+  d.ksplit = 1; d.kscratch = nullptr; d.kcount = nullptr;
+  d.ident = nullptr;
+  d.btab = nullptr; d.b_nwg = d.b_ent = d.b_rows = 0;
+  RGBM_REQUIRE(scratch != nullptr || (p.ksplit <= 1 && !p.identity_residual), "conv layer initialised without a ConvScratch");
+  // Two facts of the launch, not of the plan: what a launch needs on the device is allocated and uploaded at its first use, which must
+  // not happen on a stream that is being captured.  Both forms of either launch give the same bits.  (The capture is asked about only
+  // where something is missing; rgbm_adapose_forward_graph runs an eager forward in front of its capture, so its graphs lack neither.)
+  if (p.ksplit > 1) {
+    ConvScratch::KSplit k;
+    if (int rc = scratch->ksplit(s, false, &k)) return rc;
+    if (!k.scratch && !stream_is_capturing(s))
+      if (int rc = scratch->ksplit(s, true, &k)) return rc;
+    // 1. no K-split scratch for this stream and the stream is being captured: unsplit
+    if (k.scratch) { d.ksplit = p.ksplit; d.kscratch = k.scratch; d.kcount = k.count; }
+  }
+  if (p.border && border) {      // (no tables: a transposed layer, whose shapes border_shape_ok does not take)
+    if (int rc = attach_border(d, p, t.n_cu, t.flags, false)) return rc;
+    // 2. no border table for this shape and the stream is being captured: row-major tiles
+    if (!d.btab && !stream_is_capturing(s))
+      if (int rc = attach_border(d, p, t.n_cu, t.flags, true)) return rc;
+  }
+  if (p.identity_residual)
+    if (int rc = scratch->identity(dtype, &d.ident)) return rc;
+  return launch_conv(d, dtype, p, s);
+}
+
 int ConvLayer::run(const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res, int res_mode,
                    const float* bias_override, int bias_stride, hipStream_t s, bool out_plain_f32) const {
   const int nclass = g.transposed ? 8 : 1;
   for (int cls = 0; cls < nclass; ++cls) {
     ConvDesc d;
+    ConvTuning t;
+    ConvPlan p;
     if (int rc = build_desc(d, in, out, N, Di, Hi, Wi, ldo, res, res_mode, bias_override, bias_stride, cls, out_plain_f32)) return rc;
-    if (int rc = attach_border(d, s)) return rc;
-    if (int rc = launch_conv(d, dtype, s)) return rc;
+    if (int rc = conv_tuning(0, &t)) return rc;
+    if (int rc = plan_conv(d, dtype, t, &p)) return rc;
+    if (int rc = launch(d, p, t, s)) return rc;
   }
   return 0;
 }
@@ -330,13 +403,17 @@ int ConvLayer::run_then_1x1(const ConvLayer& next, const void* in, void* mid, in
                      ng.pd == 0 && ng.ph == 0 && ng.pw == 0 && next.packs.size() == 1;
   if (allow_fuse && is1x1 && !g.transposed && dtype_size(dtype) == 2 && next.dtype == dtype && next.Cin_pad == Cout_pad) {
     ConvDesc d;
+    ConvTuning t;
+    ConvPlan p;
     if (int rc = build_desc(d, in, mid, N, Di, Hi, Wi, ldmid, nullptr, RES_NONE, nullptr, 0, 0)) return rc;
     d.w2 = next.packs[0].w.get(); d.bias2 = next.bias.get<float>(); d.out2 = out2; d.ldo2 = ldo2; d.cout2 = next.Cout_pad;
     d.kpad2 = next.packs[0].Kpad; d.act2 = ng.act; d.slope2 = ng.slope;
-    if (conv_ws64_eligible(d, dtype)) {
+    // the fused form runs only on the three-role 64-channel kernel; a descriptor that no kernel takes with its 1x1 attached (plan_conv
+    // refuses it) or that another kernel takes goes the two-layer way below
+    if (!conv_tuning(0, &t) && !plan_conv(d, dtype, t, &p) && (p.kernel == CONV_WS64 || p.kernel == CONV_WS64_ROWHALO)) {
       d.algo_flops += 2.0 * (double)d.M * ng.Cout * ng.Cin;
       d.algo_bytes += ((double)d.M * ng.Cout - (double)d.M * g.Cout) * 2.0;      // writes y2 instead of y
-      if (int rc = launch_conv(d, dtype, s)) return rc;
+      if (int rc = launch(d, p, t, s)) return rc;
       if (fused) *fused = true;
       return 0;
     }
@@ -347,7 +424,8 @@ int ConvLayer::run_then_1x1(const ConvLayer& next, const void* in, void* mid, in
   return next.run(mid, out2, N, Do, Ho, Wo, ldo2, nullptr, RES_NONE, nullptr, 0, s, out2_plain_f32);
 }
 
-int UpConvLayer::init(int dtype, int Cin, int Cout_, const float* w, const float* bias_h, int act_, float slope_) {
+int UpConvLayer::init(int dtype, int Cin, int Cout_, const float* w, const float* bias_h, int act_, float slope_,
+                      std::shared_ptr<ConvScratch> scratch) {
   Cout = Cout_; act = act_; slope = slope_;
   RGBM_REQUIRE(Cout % dtype_chunk(dtype) == 0, "upconv Cout must be a multiple of the 16-byte chunk");
   std::vector<float> wz((size_t)9 * Cout * Cin);
@@ -364,10 +442,10 @@ int UpConvLayer::init(int dtype, int Cin, int Cout_, const float* w, const float
   if (split) {
     ConvGeom g1 = g, g2 = g;
     g1.Cout = split; g2.Cout = 9 * Cout - split;
-    if (int rc = gemm.init(dtype, g1, wz.data(), nullptr, nullptr, nullptr, Cin, g1.Cout)) return rc;
-    if (int rc = gemm2.init(dtype, g2, wz.data() + (size_t)split * Cin, nullptr, nullptr, nullptr, Cin, g2.Cout)) return rc;
+    if (int rc = gemm.init(dtype, g1, wz.data(), nullptr, nullptr, nullptr, Cin, g1.Cout, scratch)) return rc;
+    if (int rc = gemm2.init(dtype, g2, wz.data() + (size_t)split * Cin, nullptr, nullptr, nullptr, Cin, g2.Cout, scratch)) return rc;
   } else {
-    if (int rc = gemm.init(dtype, g, wz.data(), nullptr, nullptr, nullptr, Cin, 9 * Cout)) return rc;
+    if (int rc = gemm.init(dtype, g, wz.data(), nullptr, nullptr, nullptr, Cin, 9 * Cout, scratch)) return rc;
   }
   if (bias_h) { if (upload_f32(bias_h, Cout, bias)) return -2; }
   return 0;

@@ -3,7 +3,9 @@
 #pragma once
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -42,6 +44,25 @@ class DevBuf {
   void* p_ = nullptr;
 };
 
+// Device scratch of the conv_igemm_m32_kernel launches (conv_igemm_m32.inc), freed with the object.  Per (device, stream) the K-split
+// buffers: kM32SplitFloats fp32 partial accumulators and kM32SplitCounters arrival counters (conv_plan.h) — zero when allocated, and
+// every launch leaves them zero; launches on one stream are ordered, so a stream's launches can share them.  Per (device, storage type)
+// the 256 x 256 identity, the W operand of the residual steps.  A net owns one (AdaPose) and hands it to its layers, so the scratch
+// dies with the net; two nets never share one, whatever streams they run on.
+class ConvScratch {
+ public:
+  struct KSplit { float* scratch = nullptr; unsigned* count = nullptr; };
+  // the buffers of (current device, s), nulls where there are none; allocate: make them first (the counters are zeroed on s)
+  int ksplit(hipStream_t s, bool allocate, KSplit* out);
+  // uploaded at the first call (a blocking copy: not inside a capture)
+  int identity(int dtype, const void** out);
+
+ private:
+  std::mutex mu_;
+  std::map<std::pair<int, hipStream_t>, std::pair<DevBuf, DevBuf>> per_stream_;
+  std::map<std::pair<int, int>, DevBuf> ident_;
+};
+
 struct ConvGeom {
   int Cin = 0, Cout = 0;         // logical channels
   int KD = 1, KH = 1, KW = 1;
@@ -67,6 +88,8 @@ void conv_desc_geom(ConvDesc& d, const ConvGeom& g, const PackedConv& pc, int Ci
                     int ldo, int cls);      // zeroes d, then every field that is not a pointer
 
 struct BorderTables;              // device tables of a layer's border-class tiles, one per launch shape (layers.cpp; conv_plan.h)
+struct ConvPlan;
+struct ConvTuning;
 
 struct ConvLayer {
   ConvGeom g;
@@ -77,11 +100,12 @@ struct ConvLayer {
   std::vector<PackedConv> packs; // 1, or 8 for transposed
   bool w_finite = false;         // no packed weight is NaN / inf in the storage type (ConvDesc::w_finite), checked once in init
   std::shared_ptr<BorderTables> border;      // filled by run(): uploaded once per (device, views, map size), freed with the layer
+  std::shared_ptr<ConvScratch> scratch;      // the owner's (a net's, or capi.cpp's for the one-shot entry points), shared by its layers
 
   // weights: [Cout][Cin][KD][KH][KW] (or [Cin][Cout][3][3][3] when transposed), optional per-Cout scale/shift
   // (folded BN) and bias.  Cin_pad: physical channel count of the input tensor.
   int init(int dtype, const ConvGeom& g, const float* w, const float* bias, const float* bn_scale, const float* bn_shift,
-           int Cin_pad, int Cout_pad);
+           int Cin_pad, int Cout_pad, std::shared_ptr<ConvScratch> scratch);
 
   // Run on input [N][Di][Hi][Wi][Cin_pad] -> output [N][Do][Ho][Wo][ldo] (+ch offset via out pointer).
   // res: optional residual with the output's layout.  bias_override/bias_stride: per-sample bias.
@@ -96,9 +120,12 @@ struct ConvLayer {
                    bool allow_fuse, bool* fused, hipStream_t s, bool out2_plain_f32 = false) const;
   int build_desc(ConvDesc& d, const void* in, void* out, int N, int Di, int Hi, int Wi, int ldo, const void* res, int res_mode,
                  const float* bias_override, int bias_stride, int cls, bool out_plain_f32 = false) const;
-  // points d at this layer's border-class table where plan_conv asks for one (ConvPlan::border); no table yet and `s` is being captured:
-  // d stays as it is and the launch runs its row-major tiles (same bits)
-  int attach_border(ConvDesc& d, hipStream_t s) const;
+  // The one place where a plan becomes a launch: every launch-time field of d (ksplit, kscratch, kcount, ident, korder, buf_ok, btab,
+  // b_*, m0) from the plan p that run() / run_then_1x1() made of d under t, this layer's border tables and the scratch; then
+  // launch_conv, whose launchers only compute grids and launch.
+  int launch(ConvDesc& d, const ConvPlan& p, const ConvTuning& t, hipStream_t s) const;
+  // this layer's border-class table for (d, p) on t.n_cu workgroups, nulls where there is none; upload: make it first
+  int attach_border(ConvDesc& d, const ConvPlan& p, int n_cu, int flags, bool upload) const;
 };
 
 // PSPUpsample (x2 bilinear align_corners -> conv3x3 pad 1 + bias -> activation; pspnet.py:100-107) as a 1x1 GEMM at the low
@@ -111,7 +138,7 @@ struct UpConvLayer {
   int Cout = 0, act = ACT_NONE;
   float slope = 0.f;
   // w: [Cout][Cin][3][3] (nn.Conv2d layout)
-  int init(int dtype, int Cin, int Cout, const float* w, const float* bias_h, int act, float slope);
+  int init(int dtype, int Cin, int Cout, const float* w, const float* bias_h, int act, float slope, std::shared_ptr<ConvScratch> scratch);
   size_t scratch_elems(int V, int h, int w) const { return (size_t)V * h * w * 9 * Cout; }
   // in [V][h][w][Cin] -> z scratch [V][h][w][9*Cout] -> out [V][2h][2w][ldo]
   // drop (optional): Dropout2d factors, drop[v * kDropoutPerView + channel] (kernels.h)

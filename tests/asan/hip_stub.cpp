@@ -4,12 +4,28 @@
 // a hipMemcpy that reads or writes past a buffer is then an ASan report.  Test infrastructure; never linked into the product.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 
+// what the ownership test reads and sets (tests/host/conv_scratch_main.cpp): device allocations alive (hipMalloc minus hipFree), and
+// the one stream that answers "being captured" to hipStreamIsCapturing while `on`
+static std::atomic<long long> g_live{0};
+static struct { bool on = false; hipStream_t stream = nullptr; } g_capturing;
+
 extern "C" {
-hipError_t hipMalloc(void** p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
+long long hip_stub_live_allocations(void) { return g_live.load(); }
+void hip_stub_set_capturing(hipStream_t s, int on) { g_capturing.on = on != 0; g_capturing.stream = s; }
+hipError_t hipMalloc(void** p, size_t n) {
+  *p = std::malloc(n ? n : 1);
+  if (*p) ++g_live;
+  return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+hipError_t hipFree(void* p) {
+  if (p) --g_live;
+  std::free(p);
+  return hipSuccess;
+}
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { std::memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemset(void* d, int v, size_t n) { std::memset(d, v, n); return hipSuccess; }
@@ -37,7 +53,10 @@ hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t)
 // stream capture / graphs: handles are small heap blocks (so leaks and double frees of the library's graph cache are visible to the
 // sanitizer); a "captured" stream still executes nothing, like every launch of this stand-in
 hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipSuccess; }
-hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* st) { *st = hipStreamCaptureStatusNone; return hipSuccess; }
+hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus* st) {
+  *st = g_capturing.on && g_capturing.stream == s ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone;
+  return hipSuccess;
+}
 hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { *g = reinterpret_cast<hipGraph_t>(std::malloc(8)); return hipSuccess; }
 hipError_t hipGraphGetNodes(hipGraph_t, hipGraphNode_t*, size_t* n) { *n = 7; return hipSuccess; }
 hipError_t hipGraphInstantiate(hipGraphExec_t* e, hipGraph_t, hipGraphNode_t*, char*, size_t) { *e = reinterpret_cast<hipGraphExec_t>(std::malloc(8)); return hipSuccess; }

@@ -72,6 +72,17 @@ def main(path):
     net = AdaPoseNet(sd, dtype="bf16", split_streams=True, split_min_batch=4)
     for rep in range(2):
         put(f"bf16 split_streams B=4 run {rep}", call(net, 4))
+    # the K-split launches (B = 1 per stream) on two side streams of one net, and on a net created behind a destroyed one
+    net = AdaPoseNet(sd, dtype="bf16", split_streams=True, split_min_batch=2)
+    for rep in range(2):
+        put(f"bf16 split_streams B=2 run {rep}", call(net, 2))
+    on_device = [torch.as_tensor(inputs[1][k]).cuda().to(torch.int32 if k.startswith("choose") else torch.float32).contiguous()
+                 for k in ("img1", "choose1", "img2", "choose2", "P1", "P2", "depths")]
+    torch.cuda.synchronize()      # the side stream below reads them
+    for rep in range(2):
+        net = AdaPoseNet(sd, dtype="bf16")
+        put(f"bf16 B=1 on a fresh stream, net {rep} (the one before it destroyed)", net(*on_device, stream=torch.cuda.Stream()))
+        net.close()
     # Dropout2d: drawn masks (two eager forwards; capture + two replays), then explicit masks, then the sequence goes on
     for graph in (False, True):
         net = AdaPoseNet(sd, dtype="bf16", dropout=0.1, dropout_seed=3, graph=graph)
