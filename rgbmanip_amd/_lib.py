@@ -45,9 +45,9 @@ PROF_KERNELS = [
      ("conv_igemm_m32_kernel<unsigned short, 256, 256> (256 channels x 256 pixels, 32x32x16 MFMAs; gemm_kernel = 0: conv_igemm_ws_kernel<unsigned short, true, false>, 256 x 128)", "bf16"),
      ("pose_mlp2_kernel (pose_mlp2.0 + pose_mlp2.2 + the sum over points of a bf16 net in one launch)", "bf16"),
      ("conv_igemm_m32_kernel<rgbm::bx3_t, 256, 256> (256 channels x 256 pixels, 32x32x16 MFMAs; gemm_kernel = 0: conv_igemm_ws_kernel<rgbm::bx3_t, true, false>, 256 x 128)", "bf16x3"),
-     ("conv_igemm_ws_kernel<rgbm::bx3_t, false, false, true> (64 channels x 256 pixels, four multiply waves)", "bf16x3"),
-     ("conv_igemm_ws_kernel<unsigned short, false, false, true> (64 channels x 256 pixels, four multiply waves)", "bf16"),
-     ("conv_igemm_ws_kernel<float, false, false, true> (64 channels x 256 pixels, four multiply waves)", "fp32"),
+     ("conv_igemm_ws_kernel<rgbm::bx3_t, false, true> (64 channels x 256 pixels, four multiply waves)", "bf16x3"),
+     ("conv_igemm_ws_kernel<unsigned short, false, true> (64 channels x 256 pixels, four multiply waves)", "bf16"),
+     ("conv_igemm_ws_kernel<float, false, true> (64 channels x 256 pixels, four multiply waves)", "fp32"),
      ("upconv_combine_kernel<16-bit> (PSPUpsample tap combination)", "bf16"), ("upconv_combine_kernel<4-byte> (PSPUpsample tap combination)", "bf16x3"),
      ("upconv_final_kernel (up_3 + final in one kernel; either storage width)", "bf16"),
      ("conv_igemm_m32_kernel<unsigned short, 128, 64 / 128 / 256> (128-pixel tiles: tail and small-batch launches of the 256-channel GEMM)", "bf16"),

@@ -17,7 +17,7 @@ FLAGS="$FLAGS -Xclang -target-feature -Xclang -packed-fp32-ops"
 echo "$FLAGS" > build/.flags.new 2>/dev/null || true
 if ! cmp -s build/.flags.new build/.flags 2>/dev/null; then rm -f build/*.o build/*.asm_ok; cp build/.flags.new build/.flags; fi      # new flags: everything is rebuilt AND the sweep kernels' ISA is re-checked
 pids=()
-for f in conv_igemm.hip conv_igemm_glds.hip conv3d_tile.hip conv0_sweep.hip conv0_sweep_x3.hip prob_sparse.hip misc_kernels.hip bn_kernels.hip upconv.hip dropout.hip upconv_final.hip stem.hip feature_cache.hip head_kernels.hip dense_depth.hip depth_points.hip depth_consistency.hip depth_fusion.hip pose_mlp.hip view_fusion.hip postproc.hip postproc_regressed.hip prepare.hip ppo_kernels.hip policy_kernels.hip control.hip synth_env.hip align.hip cloud_fit.hip pnp.hip sample_stats.hip box_overlap.hip microbench.hip; do
+for f in igemm_m32.hip igemm_ws.hip igemm_generic.hip igemm_ws64.hip conv3d_tile.hip conv0_sweep.hip conv0_sweep_x3.hip prob_sparse.hip misc_kernels.hip bn_kernels.hip upconv.hip dropout.hip upconv_final.hip stem.hip feature_cache.hip head_kernels.hip dense_depth.hip depth_points.hip depth_consistency.hip depth_fusion.hip pose_mlp.hip view_fusion.hip postproc.hip postproc_regressed.hip prepare.hip ppo_kernels.hip policy_kernels.hip control.hip synth_env.hip align.hip cloud_fit.hip pnp.hip sample_stats.hip box_overlap.hip microbench.hip; do
   [ -f "$f" ] || continue
   EXTRA=""
   # files that must round like numpy / torch elementwise ops: no mul+add -> fma contraction
@@ -31,7 +31,7 @@ for f in conv_igemm.hip conv_igemm_glds.hip conv3d_tile.hip conv0_sweep.hip conv
     pids+=($!)
   fi
 done
-for f in layers.cpp adapose.cpp capi.cpp prof.cpp conv_plan.cpp forward_paths.cpp; do
+for f in layers.cpp adapose.cpp capi.cpp prof.cpp conv_plan.cpp conv_launch.cpp forward_paths.cpp; do
   hipcc $FLAGS -x hip -c "$f" -o build/${f%.cpp}.o &
   pids+=($!)
 done
@@ -49,5 +49,7 @@ for p in "${pids[@]}"; do wait $p; done
 for c in "${chk[@]}"; do
   if ! wait ${c%%:*}; then echo "check_asm_gathers FAILED for ${c#*:}"; cat build/$(basename ${c#*:} .hip).asm_log; exit 1; fi
 done
+# an object whose source left the tree (a file split or renamed) must not be linked beside what replaced it
+for o in build/*.o; do b=$(basename "$o" .o); [ -f "$b.hip" ] || [ -f "$b.cpp" ] || rm -f "$o"; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/librgbm_hip.so" build/*.o
 echo "built $OUT/librgbm_hip.so"

@@ -252,7 +252,7 @@ template <int THREADS> __device__ inline double block_max(double v, double* red)
   return block_reduce<THREADS>(v, red, [](double a, double b) { return fmax(a, b); });
 }
 
-// ---- generic implicit-GEMM convolution descriptor (conv_igemm.hip) -------------------
+// ---- implicit-GEMM convolution descriptor (igemm_*.hip, conv_launch.cpp) -------------
 struct ConvDesc {
   const void* in; const void* wgt; void* out; const float* bias; const void* res;
   int N, Di, Hi, Wi, Cin, lcin;           // input tensor NDHWC, Cin power of two
@@ -279,7 +279,7 @@ struct ConvDesc {
   int out_f32;                            // bf16x3 tensors, generic kernel only: write the result as PLAIN fp32 (same 4-byte slots) instead of split pairs
   // conv_igemm_m32_kernel, 128-pixel tiles, launches of few tiles (small batches): the K loop of a tile is cut into `ksplit` parts, one workgroup
   // each; a part leaves its fp32 accumulators in kscratch, the LAST of a tile's parts to arrive (kcount, per tile and multiply wave) adds the
-  // parts in ascending order and runs the epilogue (conv_igemm_m32.inc).  0 / 1 = no split.
+  // parts in ascending order and runs the epilogue (igemm_m32.hip).  0 / 1 = no split.
   int ksplit; float* kscratch; unsigned* kcount;
   // conv_igemm_m32_kernel, 256 x 256 tiles of border classes (conv_plan.h, plan_border).  w_finite: the layer's packed weights hold no
   // NaN / inf (set at create; the plan declines otherwise: NaN * 0 is the one product a skipped padding tap would change).  btab: the
@@ -293,7 +293,7 @@ struct ConvDesc {
 // (ConvLayer::launch, layers.h)
 struct ConvPlan;
 int launch_conv(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s);
-// picks the channel-tile size used by launch_conv for Cout (weights must be padded to it)
+// picks the channel-tile size used by launch_conv for Cout (weights must be padded to it); conv_plan.cpp
 int conv_ch_tile(int Cout);
 int conv_bk(int dtype);  // K-tile in elements
 

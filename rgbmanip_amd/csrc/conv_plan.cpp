@@ -9,6 +9,15 @@
 
 namespace rgbm {
 
+// channel tile of the generic kernel for Cout (the packed weights are padded to it)
+int conv_ch_tile(int Cout) {
+  if (Cout <= 16) return 16;
+  if (Cout <= 32) return 32;
+  if (Cout <= 64) return 64;
+  return 128;
+}
+int conv_bk(int dtype) { return 8 * dtype_chunk(dtype); }      // 128 bytes per row
+
 // parts to cut a small launch's K loop into: the tiles fill at most half the CUs, every part keeps at least eight K steps
 #ifndef M32_KSPLIT_MAX
 #define M32_KSPLIT_MAX 4
@@ -303,7 +312,7 @@ int plan_conv(const ConvDesc& d, int dtype, const ConvTuning& t, ConvPlan* out) 
           if (bch) return small(bch);
         }
         // layer2's 128-channel layers at one to four poses (13-52 tiles of 64 x 256): 64-channel x 128-pixel tiles of the 32x32x16 kernel with
-        // their K loop split (conv_igemm_m32.inc) — taken only where the split applies, i.e. while twice the tiles still fit the grid
+        // their K loop split (igemm_m32.hip) — taken only where the split applies, i.e. while twice the tiles still fit the grid
         if (d.Cout == 128 && ((d.M + 127) / 128) * 2 * 2 <= n_cu && t.gemm_kernel == 2 &&
             !(f & (DBG_M32_TAILS_R5 | DBG_WS_128x256 | DBG_NO_KSPLIT | DBG_L2_SLIM_TILE)) && d.w2 == nullptr && buffer_offsets_ok(d, 64, esz))
           return small(64);

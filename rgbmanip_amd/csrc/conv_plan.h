@@ -1,7 +1,7 @@
 // Which kernel, tile and K split an implicit-GEMM convolution runs on: the decision, and nothing else.  plan_conv is a pure function
 // of its arguments (no HIP runtime call, no global read), so it can be asked without a GPU (rgbm_conv_plan in rgbm.h) and tested
 // directly.  A launch asks it once: ConvLayer::run / run_then_1x1 (layers.cpp) gather the ConvTuning and call it, ConvLayer::launch binds what
-// the plan needs on the device (K-split scratch, identity, border table) and launch_conv (conv_igemm_glds.hip) launches what it says.
+// the plan needs on the device (K-split scratch, identity, border table) and launch_conv (conv_launch.cpp) launches what it says.
 #pragma once
 #include <vector>
 
@@ -82,7 +82,17 @@ constexpr size_t kM32SplitFloats = 8u << 20, kM32SplitCounters = 16384;
 
 // 0, or -1 with the error set where no kernel takes d (a malformed descriptor)
 int plan_conv(const ConvDesc& d, int dtype, const ConvTuning& t, ConvPlan* out);
-// the process's current tuning (conv_igemm_glds.hip); n_cu = 0: the current device's, else as given without a HIP runtime call
+// the process's current tuning (conv_launch.cpp); n_cu = 0: the current device's, else as given without a HIP runtime call
 int conv_tuning(int n_cu, ConvTuning* t);
+
+// One launcher per kernel family, each its own translation unit; launch_conv (conv_launch.cpp) picks by p.kernel:
+//   CONV_GENERIC -> igemm_generic.hip        CONV_V3 -> igemm_generic.hip        CONV_WS / _WIDE / _SLIM -> igemm_ws.hip
+//   CONV_WS64 / _ROWHALO -> igemm_ws64.hip   CONV_M32 / _SMALL -> igemm_m32.hip
+int launch_igemm_generic(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s);
+int launch_igemm_v3(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s);
+int launch_igemm_ws(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s);
+int launch_igemm_ws64(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s);
+int launch_igemm_m32(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s);
+int conv_no_kernel();      // -1 with the error set: the plan names a kernel the storage type does not have
 
 }  // namespace rgbm

@@ -1,6 +1,6 @@
-// Implicit-GEMM tiles of 256 output channels on v_mfma_f32_32x32x16 (gfx950), included from conv_igemm_glds.hip inside namespace rgbm.
+// Implicit-GEMM tiles on v_mfma_f32_32x32x16 (gfx950): conv_igemm_m32_kernel, 16-bit storage types and split pairs.  Shared pieces: igemm_device.h.
 // For the layers that carry the PSPNet backbone (lib/pspnet.py:11-30,42-43,59-62 of the reference: layer3 / layer4 BasicBlocks with
-// dilation 2 / 4, residual + ReLU epilogue; :97-107 up_1 as a 1x1 GEMM), 16-bit storage types.
+// dilation 2 / 4, residual + ReLU epilogue; :97-107 up_1 as a 1x1 GEMM).
 //
 // Round 5 measured what bounds conv_igemm_ws_kernel's K loop (timers in the request waves, tools/abl_m32_run*.sh): not the matrix pipe
 // but the request waves' ISSUE of LDS-DMA pieces — 1780 cycles per 48 KB K tile with 64-bit global addresses, 64 cycles waiting for
@@ -20,6 +20,11 @@
 // CONSECUTIVE channels of its pixel (two 16-byte stores; residual reads likewise), and with that permutation the plain (row>>1)&7
 // chunk swizzle is conflict-free for the 16-lane groups ds_read_b128 is served in, for W and X rows alike.
 // ---------------------------------------------------------------------------------------------------------
+#include <atomic>
+#include "igemm_device.h"
+
+namespace rgbm {
+
 #ifndef M32_SHIFT
 #define M32_SHIFT 1   // 256-pixel tiles, 16-bit types: the K-tile barrier is passed in front of a K tile's LAST sub-step (see the multiply waves; 0 = at its head, for A/B)
 #endif
@@ -40,10 +45,6 @@ template <> struct Mma32<f16_t> {
   __device__ static __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   }
-};
-
-template <> struct Mma32<bx3_t> {      // (never called: the split-pair K loop multiplies hi / lo halves with Mma32<unsigned short>)
-  __device__ static __forceinline__ void run(const uint4&, const uint4&, f32x16&) {}
 };
 
 // channel (within a 32-channel fragment) carried by MFMA row i
@@ -344,22 +345,6 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
     const int q = (id_c & 7) >> 1;
     return make_uint4(q == 0 ? w : 0u, q == 1 ? w : 0u, q == 2 ? w : 0u, q == 3 ? w : 0u);
   };
-  auto load_step = [&](int st, int s, uint4 (&af)[FA], uint4 (&bf)[FB]) {
-    const char* base = ldsc + st * (STAGE * 16);
-    const unsigned oa = offA ^ ((unsigned)s << 5), ob = offB ^ ((unsigned)s << 5);
-#pragma unroll
-    for (int b = 0; b < FB; ++b) bf[b] = *reinterpret_cast<const uint4*>(base + ob + b * 4096);
-#pragma unroll
-    for (int a = 0; a < FA; ++a) af[a] = *reinterpret_cast<const uint4*>(base + oa + a * 4096);
-  };
-  auto mma_step = [&](const uint4 (&af)[FA], const uint4 (&bf)[FB]) {
-#pragma unroll
-    for (int a = 0; a < FA; ++a)
-#pragma unroll
-      for (int b = 0; b < FB; ++b) {
-        Mma32<T>::run(af[a], bf[b], acc[a][b]);
-      }
-  };
   T* __restrict__ out = reinterpret_cast<T*>(d.out);
   const T* __restrict__ res = reinterpret_cast<const T*>(d.res);
   auto tile_interior = [&](int pix_tile, int ch_tile) {
@@ -475,7 +460,6 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
       // Only the first step of a K tile, behind the barrier, waits for all six reads.
       uint4 A[FA], B[FB], Bn[FB];
       unsigned oA = offA, oB = offB;
-      auto ldA = [&](int s, int a) { A[a] = *reinterpret_cast<const uint4*>(ldsc + st * (STAGE * 16) + (oA ^ ((unsigned)s << 5)) + a * 4096); };
       auto ldB = [&](int s, uint4 (&bf)[FB]) {
 #pragma unroll
         for (int b = 0; b < FB; ++b) bf[b] = *reinterpret_cast<const uint4*>(ldsc + st * (STAGE * 16) + (oB ^ ((unsigned)s << 5)) + b * 4096);
@@ -588,6 +572,23 @@ __global__ __launch_bounds__(BPIX == 256 ? 768 : 512) void conv_igemm_m32_kernel
         }
       }
     } else {
+      // 16-bit types, 128-pixel tiles: fragment reads one 16-deep step ahead of the MFMAs, in two register sets
+      auto load_step = [&](int st, int s, uint4 (&af)[FA], uint4 (&bf)[FB]) {
+        const char* base = ldsc + st * (STAGE * 16);
+        const unsigned oa = offA ^ ((unsigned)s << 5), ob = offB ^ ((unsigned)s << 5);
+#pragma unroll
+        for (int b = 0; b < FB; ++b) bf[b] = *reinterpret_cast<const uint4*>(base + ob + b * 4096);
+#pragma unroll
+        for (int a = 0; a < FA; ++a) af[a] = *reinterpret_cast<const uint4*>(base + oa + a * 4096);
+      };
+      auto mma_step = [&](const uint4 (&af)[FA], const uint4 (&bf)[FB]) {
+#pragma unroll
+        for (int a = 0; a < FA; ++a)
+#pragma unroll
+          for (int b = 0; b < FB; ++b) {
+            Mma32<T>::run(af[a], bf[b], acc[a][b]);
+          }
+      };
       uint4 A0[FA], B0[FB], A1[FA], B1[FB];
       for (int kt = 0; kt < KTT; ++kt) {
         // every fragment read of the previous step has returned before the request waves may refill its stage
@@ -874,9 +875,7 @@ static int launch_m32_range(ConvDesc d, hipStream_t s) {
   const long long ntiles = (long long)d.n_pix_tiles * d.n_ch_tiles;
   RGBM_REQUIRE(ntiles > 0 && ntiles < (1ll << 31) && d.M < (1ll << 31), "conv grid out of range");
   d.n_tiles = (int)ntiles;
-  make_fastdiv(d.Wq, d.fd_m[0], d.fd_s[0]);
-  make_fastdiv(d.Hq, d.fd_m[1], d.fd_s[1]);
-  make_fastdiv(d.Dq, d.fd_m[2], d.fd_s[2]);
+  fill_fastdiv(d);
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_igemm_m32_kernel<T, BPIX, BCH>), (int)LDS)) return rc;
   int n_cu = 0;
   if (int rc = persistent_grid_cus(&n_cu)) return rc;
@@ -919,3 +918,14 @@ static int launch_m32(ConvDesc d, const ConvPlan& p, hipStream_t s) {
   d.btab = nullptr;
   return p.tail_bch ? launch_m32_tiles128<T>(d, p.tail_bch, s) : 0;
 }
+
+// CONV_M32 / CONV_M32_SMALL (16-bit storage types and split pairs)
+int launch_igemm_m32(const ConvDesc& d, int dtype, const ConvPlan& p, hipStream_t s) {
+  const bool small = p.kernel == CONV_M32_SMALL;
+  if (dtype == BF16) return small ? launch_m32_small<unsigned short>(d, p, s) : launch_m32<unsigned short>(d, p, s);
+  if (dtype == F16) return small ? launch_m32_small<f16_t>(d, p, s) : launch_m32<f16_t>(d, p, s);
+  if (dtype == BF16X3) return small ? launch_m32_small<bx3_t>(d, p, s) : launch_m32<bx3_t>(d, p, s);
+  return conv_no_kernel();
+}
+
+}  // namespace rgbm

@@ -176,11 +176,11 @@ enum DebugFlag {
   DBG_PP_ONE_KERNEL = 1 << 23, DBG_NO_SLIM_SMALL = 1 << 24, DBG_PP_GENERIC_SELECT = 1 << 25, DBG_PP_GUARD = 1 << 26, DBG_GLOBAL_ADDR = 1 << 27,
   DBG_SWEEP_PER_TILE = 1 << 28, DBG_SPARSE_TAIL_R5 = 1 << 29, DBG_M32_TAILS_R5 = 1 << 30, DBG_POSE_MLP_R6 = 1 << 19, DBG_NO_BORDER_TILES = 32,
 };
-extern int g_debug_flags;
-long long border_launch_count();      // launches of conv_igemm_m32_kernel on border-class tiles since the library was loaded (conv_igemm_glds.hip)
+extern int g_debug_flags;      // the four settings: conv_launch.cpp
 extern long long g_ws_min_rows;
 extern int g_tuning_version;
 extern int g_gemm_kernel;
+long long border_launch_count();      // launches of conv_igemm_m32_kernel on border-class tiles since the library was loaded (igemm_m32.hip)
 void conv3d_tile_pack(const float* w, const float* scale, int Cin, int Cout, int coutp, bool transposed, int dtype,
                       std::vector<float>& packed);
 int launch_conv3d_tile(int layer, int dtype, const Conv3dTileDesc& d, hipStream_t s);

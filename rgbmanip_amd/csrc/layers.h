@@ -44,7 +44,7 @@ class DevBuf {
   void* p_ = nullptr;
 };
 
-// Device scratch of the conv_igemm_m32_kernel launches (conv_igemm_m32.inc), freed with the object.  Per (device, stream) the K-split
+// Device scratch of the conv_igemm_m32_kernel launches (igemm_m32.hip), freed with the object.  Per (device, stream) the K-split
 // buffers: kM32SplitFloats fp32 partial accumulators and kM32SplitCounters arrival counters (conv_plan.h) — zero when allocated, and
 // every launch leaves them zero; launches on one stream are ordered, so a stream's launches can share them.  Per (device, storage type)
 // the 256 x 256 identity, the W operand of the residual steps.  A net owns one (AdaPose) and hands it to its layers, so the scratch

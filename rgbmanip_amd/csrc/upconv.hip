@@ -240,7 +240,7 @@ int launch_upconv_combine(int dtype, const void* z, const float* bias, void* out
   // profiler rows 37 (16-bit storage) / 38 (4-byte slots); algorithmic flops: 36 multiply-adds per output element; bytes: z in + y out
   prof_begin_launch(s, dtype_size(dtype) == 2 ? 37 : 38, 72.0 * nout, ((double)V * h * w * 9.0 * Co + nout) * (double)dtype_size(dtype));
   // one branch-free activation: y = v < 0 ? max(v, -FLT_MAX) * nslope : v (none: 1, ReLU: 0, PReLU: its slope; NaN stays NaN, -inf
-  // under ReLU gives -0 instead of NaN, the form conv_igemm_glds.hip uses); per-element branches on `act`
+  // under ReLU gives -0 instead of NaN, the form igemm_ws.hip uses); per-element branches on `act`
   // made hipcc sink every accumulation chain into the epilogue (all interpolated values live at once)
   const float nslope = act == ACT_NONE ? 1.f : act == ACT_RELU ? 0.f : slope;
   int rc;

@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rgbmanip_amd", "csrc")
 CLANGXX = "/opt/rocm/lib/llvm/bin/clang++"      # the link: plain clang++, no HIP runtime behind the stand-in
 # the layer objects, the plan, the launchers they call, and what defines the globals those read
-SOURCES = [os.path.join(CSRC, f) for f in ("layers.cpp", "conv_plan.cpp", "prof.cpp", "conv_igemm_glds.hip", "conv_igemm.hip", "conv3d_tile.hip",
-                                           "upconv.hip", "upconv_final.hip")] + \
+SOURCES = [os.path.join(CSRC, f) for f in ("layers.cpp", "conv_plan.cpp", "conv_launch.cpp", "prof.cpp", "igemm_generic.hip", "igemm_ws.hip",
+                                           "igemm_m32.hip", "igemm_ws64.hip", "upconv.hip", "upconv_final.hip")] + \
           [os.path.join(ROOT, "tests", "asan", "hip_stub.cpp"), os.path.join(ROOT, "tests", "host", "conv_scratch_main.cpp")]
 FLAGS = ["--cuda-host-only", "-x", "hip", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize",
          "-fno-omit-frame-pointer", "-O1", "-g", "-std=c++17", "-I", CSRC]

@@ -135,6 +135,43 @@ def test_conv2d_switchable_igemm_variants(flags, dtype):
         assert torch.equal(y, y16)
 
 
+V3_CASES = [
+    # name, rgbm_debug_flags, Cin, K tiles with 16-bit / 4-byte storage.  1 x Cin x 32 x 33 -> 128 channels, 3 x 3, pad 1: M = 1056 rows =
+    # four whole 256-pixel tiles + a ragged one, padding on every edge; the smallest shapes that reach the kernel (ws_min_rows: 1024 rows)
+    ("nonuniform_taps", 0, 16, 3, 5),      # Cin < a K tile: K tiles straddle taps (the per-lane tap decode)
+    ("uniform_taps", 64, 64, 9, 18),       # flag 64: this kernel in place of conv_igemm_ws_kernel (the scalar tap walker)
+]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", V3_CASES, ids=[c[0] for c in V3_CASES])
+def test_conv2d_v3_kernel(case, dtype):
+    """conv_igemm_v3_kernel (128 x 256 tile, three stages, every wave requests and multiplies; igemm_generic.hip, whose own zero page feeds
+    its padded chunks) against F.conv2d on the same rounded operands, bias + pre-activation residual + ReLU.  No other case of the suite
+    plans this kernel, so the plan is asserted first."""
+    from gpu_util import conv_nd, conv_plan, rel_err
+    lib = _lib.load()
+    name, flags, Cin, kt16, kt32 = case
+    N, H, W, Cout = 1, 32, 33, 128
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000)
+    x = _q(torch.randn(N, Cin, H, W, generator=g), dtype)
+    w = _q(torch.randn(Cout, Cin, 3, 3, generator=g) / np.sqrt(Cin * 9), dtype)
+    b = torch.randn(Cout, generator=g) * 0.1
+    ref = F.conv2d(x, w, b, 1, 1, 1)
+    res = _q(torch.randn(ref.shape, generator=g), dtype)
+    ref = F.relu(ref + res)
+    try:
+        lib.rgbm_debug_flags(flags)
+        p = conv_plan(dtype, N, Cin, H, W, Cout, 3, 1, 1, 1, has_bias=True, res_mode=1, act=1)
+        assert (p["kernel"], p["bch"], p["bpix"], p["M"]) == (1, 128, 256, 1056), p      # 1 = CONV_V3
+        assert p["KT"] == (kt16 if dtype in QDT else kt32), p
+        y = conv_nd(dtype, x, w, stride=1, pad=1, dil=1, bias=b, res=res, res_mode=1, act=1)
+    finally:
+        lib.rgbm_debug_flags(0)
+    assert y.shape == ref.shape and torch.isfinite(y).all()
+    assert rel_err(y, ref) < TOL[dtype], name
+
+
 WIDE_CASES = [c for c in CONV2D_CASES if c[0].startswith("wide_") or c[0] == "ws128_dil2_bias_prelu"] + [
     # the backbone's own shapes at a small batch: layer3 (dilation 2, residual + ReLU, lib/pspnet.py:42), layer4 (dilation 4, :43), and a
     # launch with fewer tiles than CUs and one with K tiles < ring depth
@@ -204,7 +241,7 @@ def test_conv2d_gemm_kernel_variants(case, dtype):
 
 @pytest.mark.parametrize("dtype", [_lib.BF16, _lib.F16, _lib.BF16X3], ids=["bf16", "fp16", "bf16x3"])
 def test_conv2d_k_split_is_stable_over_many_runs(dtype):
-    """The K split of launches with few tiles (conv_igemm_m32.inc: parts of a tile's K loop on different workgroups — on any XCD —, partial
+    """The K split of launches with few tiles (igemm_m32.hip: parts of a tile's K loop on different workgroups — on any XCD —, partial
     sums through a scratch buffer with device-scope accesses, an arrival counter per tile and wave, the last part to arrive adds all parts
     in ascending order): layer3's and layer4's shapes at one pose (52 tiles x 4 parts, 104 x 2), 150 launches each — every result equals
     the first, and equals the unsplit launch to the storage type's rounding.  A partial sum read before it was visible, or a counter not

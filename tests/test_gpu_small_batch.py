@@ -2,7 +2,7 @@
 against high-precision references.
 
  * conv level: the small-launch tiles of conv_plan.cpp::plan_conv (64 / 128 / 256-channel x 128-pixel tiles, the kept
-   64 x 256 tile) and the K split of conv_igemm_m32.inc, at ResNet-34 layer2..4's own shapes (28 x 28, 2 .. 16 views) and synthetic
+   64 x 256 tile) and the K split of igemm_m32.hip, at ResNet-34 layer2..4's own shapes (28 x 28, 2 .. 16 views) and synthetic
    ones, against F.conv2d in float64 on the same rounded operands; the expected path comes from the library (rgbm_conv_plan);
  * network level: AdaPoseNet at B = 1, 3, 4, 5, 8 against the CPU oracle pose by pose, in every storage type, and the estimator's
    default cfg at B = 8 against the oracle pipeline;

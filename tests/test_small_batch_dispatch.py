@@ -23,7 +23,7 @@ def _small(N, Cin, Cout, k, dil=1, res_mode=1, dtype=_lib.BF16):
 
 
 def test_plans_match_the_documented_launches():
-    # layer3 / layer4 at one pose (conv_igemm_m32.inc; tests/test_gpu_kernels.py::test_conv2d_k_split_is_stable_over_many_runs):
+    # layer3 / layer4 at one pose (igemm_m32.hip; tests/test_gpu_kernels.py::test_conv2d_k_split_is_stable_over_many_runs):
     # M = 1568, KT = 36 / 72: 52 tiles x 4 parts, 104 x 2
     assert _small(2, 256, 256, 3, 2) == (64, 128, 4)
     assert _small(2, 512, 512, 3, 4) == (64, 128, 2)
