@@ -89,6 +89,35 @@ int rgbm_view_fusion(rgbm_adapose_t* h, const float* x1, const float* x2, int B,
                      size_t scratch_bytes, void* stream);
 int rgbm_view_fusion_scratch_bytes(int B, int P, size_t* bytes);
 int rgbm_depth_head(rgbm_adapose_t* h, const float* x, int64_t n_rows, float* out, void* stream);
+/* The real-world network, StereoPoseNet_with_depth_for_realdemo (lib/network_realworld.py; interface_realworld.py builds it): v5 with two
+ * pieces exchanged.  DESIGN.md section 5r.
+ *   - The fused plane-sweep volume is a variance: per view ref^2 + warped^2 - (ref + warped)^2 = -2 ref warped channel by channel
+ *     (network_realworld.py:145-166) where v5 has ref + warped; 0 where the partner view projects outside the image.  Every conv0 form this
+ *     network reaches takes the fusion as a compile-time parameter: the voxel is one fp32 product of the existing bilinear sum, rounded
+ *     once to the voxel's storage.  The packed-f16 forms do not (a product of two features squares their range, f16 saturates at 65504):
+ *     rgbm_forward_paths never answers paths[5] = 2 or paths[8] = 4 for arch 2, option sweep_f16 = 1 is an error, and dtype RGBM_F16 is
+ *     refused at create.  Everything behind conv0 is v5's code.
+ *   - The pose rows are camera_pts_mlp(x / W, y / H, depth) [64] in front of nocs_pts_mlp(nocs) [64] (one kernel, fp32, weights in LDS);
+ *     pose_mlp1.0 is 128 -> 128 and the pose MLP runs per layer.  There is no depth-guided fusion.
+ * rgbm_adapose_create_realworld: the same handle type from v5's keys plus camera_pts_mlp.{0,2}.{weight,bias}, pose_mlp1.0.weight
+ *   [128][128][1]; a missing weight is reported by name ("missing weight <key>") and what was uploaded is freed.
+ * rgbm_adapose_forward_realworld: rgbm_adapose_forward_ex with two more inputs, coor1 / coor2 [B][P][2] fp32 device: the chosen points'
+ *   pixel coordinates in the uncropped frame divided by its width and height (interface_realworld.py:264-269; rgbm_pts2d_to_coor).  The
+ *   other forwards refuse such a handle, as do Dropout2d, the feature cache, forward_samples and hipGraph replay.  Options view2_heads,
+ *   cost_impl, sparse_tail, sparse_dec, igemm_conv6, max_chunk, stem, upconv and fuse_final work as for v5; rgbm_adapose_fetch's "pf96"
+ *   holds the [2B][P][128] pose rows.
+ * rgbm_pts2d_to_coor: coor[i] = (pts2d[i][0] / W, pts2d[i][1] / H), n_points pairs, true IEEE float32 divisions (640 and 480 are no
+ *   powers of two: a reciprocal multiply rounds differently).
+ * rgbm_pose_rows: the pose-rows kernel alone with the handle's weights (tests, timing).  Views are ordered [view-1 poses ; view-2 poses];
+ *   nocs4 [views * P][4] fp32 (x, y, z, unused), depth [views * P] fp32, coor1 / coor2 [B][P][2] (coor2 may be NULL with views = B) ->
+ *   rows [views * P][128] fp32, 16-byte aligned; views = B or 2 B. */
+int rgbm_adapose_create_realworld(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype);
+int rgbm_adapose_forward_realworld(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1, const int32_t* choose2,
+                                   const float* coor1, const float* coor2, const float* P1, const float* P2, const float* depths, void* workspace,
+                                   size_t workspace_bytes, const rgbm_adapose_out* out, int stop_after, void* stream);
+int rgbm_pts2d_to_coor(const float* pts2d_dev, float* coor_dev, int64_t n_points, int W, int H, void* stream);
+int rgbm_pose_rows(rgbm_adapose_t* h, const float* nocs4, const float* coor1, const float* coor2, const float* depth, float* rows, int B, int P,
+                   int views, void* stream);
 /* views per cost-volume chunk (default 512 = batch 256 in one chunk); bounds the workspace */
 int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views);
 /* options: "max_chunk" (views per cost-volume chunk), "fuse_final" (bf16 only; 1 [default] = PSPNet's final 1x1 runs inside
@@ -120,7 +149,7 @@ int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value);
 /* Path selection: which of its alternative kernel paths a forward runs, decided in one pure function (csrc/forward_paths.cpp) of plain
  * ints.  rgbm_forward_paths never touches the HIP runtime (works without a GPU): facts [n_rows][RGBM_PATH_FACT_INTS] ->
  * paths [n_rows][RGBM_PATH_INTS], row by row.
- *   facts: [0] arch 0 v5 / 1 baseline  [1] dtype (RGBM_F32 ..)  [2] norm_mode
+ *   facts: [0] arch 0 v5 / 1 baseline / 2 real-world (v5's paths, never paths[5] = 2 or paths[8] = 4)  [1] dtype (RGBM_F32 ..)  [2] norm_mode
  *     [3] cost_impl [4] sparse_tail [5] sparse_dec [6] sweep_f16 [7] igemm_conv6 [8] fuse_final [9] upconv [10] stem [11] view2_heads: the
  *     options of rgbm_adapose_set_option  [12] pose_x3 (1: split-pair nets run the per-point pose layers on split pairs)
  *     [13] the rgbm_debug_flags word (negative: the process's current one, as rgbm_conv_plan takes it); read here: 1024 (PSP stage of rounds 1-5), 2048 (per-layer point MLP), 4096 (halo-tile conv0
@@ -414,6 +443,16 @@ int rgbm_adapose_postprocess_ransac(int B, int P, int img_size, uint32_t seed, c
 int rgbm_adapose_postprocess_pnp(int B, int P, uint32_t seed, const float* nocs1, const float* pts2d1, const float* nocs2,
                                  const float* pts2d2, const double* K, const double* E1, const double* E2, double* bbox_out,
                                  double* srt_out, int32_t* info_out, int32_t* valid_out, void* stream);
+/* Tail of AdaPoseEstimator_realworld.predict (interface_realworld.py:295-320): scale = ||s1|| in float32, as np.linalg.norm of the float32
+ * size vector the network regressed (s1 [B,3] f32), then the steps of rgbm_adapose_postprocess_pnp from EPnP-RANSAC on - the same device
+ * functions, the same hash stream, 5 <= P <= 1024 - on (nocs1 * scale, pixels of view 1): no NOCS matching, no triangulation.  The box is
+ * get_3d_bbox(2 max|nocs1| scale), a float32 product as in the reference, under [R | t], taken to the world frame through inv(E1).
+ * srt_out as above (scale as a double); info_out [B,4] i32 = P, RANSAC ok, inliers, hypotheses examined.  No consensus or a non-finite
+ * result gives the default box and valid = 0: the reference has no `success` check on this path and would use whatever cv2 left in r, t.
+ * Parity of the restated OpenCV routines with cv2 is unpinned, as for the tail above. */
+int rgbm_adapose_postprocess_pnp_scaled(int B, int P, uint32_t seed, const float* nocs1, const float* pts2d1, const float* s1,
+                                        const double* K, const double* E1, double* bbox_out, double* srt_out, int32_t* info_out,
+                                        int32_t* valid_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Batched device-side input preparation.
@@ -738,6 +777,10 @@ int rgbm_adaptive_avgpool(int dtype, const void* in_dev, void* out_dev, int V, i
  * depths [B][D] f32 -> vol [V][D][H][W][32]; homog_scratch: V*12 floats */
 int rgbm_build_volume(int dtype, const void* feat_dev, const float* P_views_dev, const float* depths_dev, float* homog_scratch,
                       void* vol_dev, int V, int B, int D, int H, int W, void* stream);
+/* the same with the fusion named: 0 = feat[v] + warped (rgbm_build_volume), 1 = the real-world network's variance -2 feat[v] warped
+ * (one fp32 product, rounded once to the storage type; not for RGBM_F16) */
+int rgbm_build_volume_fusion(int dtype, int fusion, const void* feat_dev, const float* P_views_dev, const float* depths_dev, float* homog_scratch,
+                             void* vol_dev, int V, int B, int D, int H, int W, void* stream);
 /* conv0 of the cost-regularisation net with the plane sweep fused in, depth-sweeping kernel (bf16 only; what
  * cost_impl = 3 runs): feat [V][H][W][32] bf16 (views 0..B-1 = view 1, B..2B-1 = view 2), P_views [V][4][4], depths [B][D],
  * homog_scratch [V*12] floats, w_host [8][32][3][3][3] + folded BatchNorm scale/shift [8] on the host ->

@@ -110,6 +110,10 @@ SIGNATURES = {
     "rgbm_adapose_destroy": (_i, [_vp]),
     "rgbm_adapose_set_chunk": (_i, [_vp, _i]),
     "rgbm_adapose_set_option": (_i, [_vp, C.c_char_p, _i]),
+    "rgbm_adapose_create_realworld": (_i, [C.POINTER(_vp), _i, C.POINTER(WeightDesc), _i, _i]),
+    "rgbm_adapose_forward_realworld": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _i, _vp]),
+    "rgbm_pose_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rgbm_pts2d_to_coor": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp]),
     "rgbm_forward_paths": (_i, [C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
     "rgbm_adapose_paths": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rgbm_adapose_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),
@@ -177,6 +181,8 @@ SIGNATURES = {
     "rgbm_maxpool3x3s2": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rgbm_resize_bilinear_ac": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "rgbm_adaptive_avgpool": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "rgbm_adapose_postprocess_pnp_scaled": (_i, [_i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rgbm_build_volume_fusion": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rgbm_build_volume": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rgbm_conv0_sweep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rgbm_conv0_sweep_dt": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

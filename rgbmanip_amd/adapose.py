@@ -35,8 +35,11 @@ class AdaPoseNet:
         # PSPNet and point heads, the cost volume replaced by the cross-view attention stack and depth_head.
         # regress_pose=False (baseline only): no pose branch; forward returns the reference's four keys.  hipGraph replay, Dropout2d,
         # per-sample BatchNorm3d, the dense maps and the feature cache are not implemented for it.
-        if arch not in ("v5", "baseline"):
-            raise ValueError(f"arch must be 'v5' or 'baseline', got {arch!r}")
+        # arch "realworld": the reference's StereoPoseNet_with_depth_for_realdemo (lib/network_realworld.py) from its state dict - v5 on a
+        # variance cost volume, the pose rows from camera points.  forward() needs coor1= / coor2=.  dtype fp16,
+        # hipGraph replay, Dropout2d, per-sample BatchNorm3d, the dense maps, forward_samples and the feature cache are refused.
+        if arch not in ("v5", "baseline", "realworld"):
+            raise ValueError(f"arch must be 'v5', 'baseline' or 'realworld', got {arch!r}")
         self.arch = arch
         self.regress_pose = bool(regress_pose)
         if arch == "baseline":
@@ -46,6 +49,11 @@ class AdaPoseNet:
                     raise _lib.RgbmError(f"AdaPoseNet(arch='baseline'): {key} is not implemented for the baseline network")
         elif not regress_pose:
             raise ValueError("regress_pose=False exists for arch='baseline' only")
+        if arch == "realworld":
+            for key, on in (("graph", graph), ("dropout", dropout), ("norm_mode", norm_mode not in (0, "eval")), ("split_streams", split_streams),
+                            ("dtype fp16", _DTYPES[dtype] == _lib.F16)):
+                if on:
+                    raise _lib.RgbmError(f"AdaPoseNet(arch='realworld'): {key} is not implemented for the real-world network")
         # graph: forwards of at most `graph_max_batch` poses are replayed from a hipGraph captured per batch size
         # (rgbm_adapose_forward_graph): static input / output / workspace buffers per batch size, one hipGraphLaunch instead of ~150
         # launches — the small-batch deployment path (interface_v5.py:213-227 calls the network per env; cfg/task/open_cabinet.yaml
@@ -96,6 +104,8 @@ class AdaPoseNet:
         if arch == "baseline":
             _lib.check(self.lib.rgbm_adapose_create_baseline(C.byref(self._h), device, arr, len(descs), self.dtype, int(self.regress_pose)),
                        "rgbm_adapose_create_baseline")
+        elif arch == "realworld":
+            _lib.check(self.lib.rgbm_adapose_create_realworld(C.byref(self._h), device, arr, len(descs), self.dtype), "rgbm_adapose_create_realworld")
         else:
             _lib.check(self.lib.rgbm_adapose_create(C.byref(self._h), device, arr, len(descs), self.dtype, int(self.norm_mode)),
                        "rgbm_adapose_create")
@@ -230,14 +240,23 @@ class AdaPoseNet:
         return {k: v.clone() for k, v in out.items()}      # the static outputs are overwritten by the next replay
 
     def forward(self, view1_img, view1_choose, view2_img, view2_choose, view1_proj, view2_proj, depth_values,
-                stop_after: int = 0, stream=None, dense_depth: bool = False, dense_nocs: bool = False):
+                stop_after: int = 0, stream=None, dense_depth: bool = False, dense_nocs: bool = False, coor1=None, coor2=None):
         """The reference network's call.  `dense_depth=True` (rgbm_adapose_forward_dense): the same dict plus `view1_depth_map` /
         `view1_depth_conf` and, with the view-2 heads, `view2_depth_map` / `view2_depth_conf` — [B, 224, 224] float32 each: the expected
         depth and the largest probability over the 24 planes at every pixel of the crop.  That call runs the dense cost regularisation
         and the dense tail whatever the net's options say (and leaves them as they are), always eagerly on one stream.
         `dense_nocs=True` (rgbm_adapose_forward_maps), alone or with `dense_depth`: plus `view1_nocs_map` (and `view2_nocs_map` with the
         view-2 heads) [B, 224, 224, 3] float32, the NOCS branch at every pixel; the map read at `choose` is `view*_nocs` bit for bit.
-        Alone it leaves the ten outputs those of the plain forward (the net's own options, eagerly on one stream)."""
+        Alone it leaves the ten outputs those of the plain forward (the net's own options, eagerly on one stream).
+        `coor1=` / `coor2=` [B, 1024, 2] float32 (arch "realworld" only, required there): the chosen points' pixel coordinates divided by
+        the frame's width and height, the reference network's view1_pts2d / view2_pts2d arguments (network_realworld.py:133)."""
+        if self.arch == "realworld":
+            if dense_depth or dense_nocs:
+                raise _lib.RgbmError("AdaPoseNet(arch='realworld'): dense_depth / dense_nocs are not implemented for the real-world network")
+            if coor1 is None or coor2 is None:
+                raise _lib.RgbmError("AdaPoseNet(arch='realworld'): forward needs coor1= and coor2= (the normalised point coordinates)")
+        elif coor1 is not None or coor2 is not None:
+            raise _lib.RgbmError("coor1 / coor2 are inputs of arch='realworld' only")
         if dense_depth or dense_nocs:
             assert stop_after == 0, "dense_depth / dense_nocs: the whole forward"
             return self._forward_dense((view1_img, view2_img, view1_choose, view2_choose, view1_proj, view2_proj, depth_values), stream,
@@ -269,6 +288,16 @@ class AdaPoseNet:
         o = _lib.AdaposeOut(*[out[n].data_ptr() for n, _ in _lib.AdaposeOut._fields_])
         ws_ptr, ws_bytes = self._workspace(B)
         self._poison(self._ws, stream)
+        if self.arch == "realworld":
+            c1 = self._prep(coor1, torch.float32)
+            c2 = self._prep(coor2, torch.float32)
+            assert c1.shape == (B, 1024, 2) and c2.shape == c1.shape, c1.shape
+            _lib.check(self.lib.rgbm_adapose_forward_realworld(self._h, B, _lib.ptr(img1), _lib.ptr(img2), _lib.ptr(ch1), _lib.ptr(ch2),
+                                                               _lib.ptr(c1), _lib.ptr(c2), _lib.ptr(P1), _lib.ptr(P2), _lib.ptr(dep),
+                                                               C.c_void_p(ws_ptr), ws_bytes, C.byref(o), stop_after, _lib.stream_ptr(stream)),
+                       "rgbm_adapose_forward_realworld")
+            self._last = (img1, img2, ch1, ch2, P1, P2, dep, c1, c2)
+            return out
         _lib.check(self.lib.rgbm_adapose_forward_ex(self._h, B, _lib.ptr(img1), _lib.ptr(img2), _lib.ptr(ch1), _lib.ptr(ch2),
                                                     _lib.ptr(P1), _lib.ptr(P2), _lib.ptr(dep), C.c_void_p(ws_ptr), ws_bytes,
                                                     C.byref(o), stop_after, _lib.stream_ptr(stream)), "rgbm_adapose_forward")
@@ -638,6 +667,38 @@ def postprocess_pnp(view1_nocs, view1_pts2d, view2_nocs, view2_pts2d, K, E1, E2,
                                                 _lib.ptr(Kd), _lib.ptr(E1d), _lib.ptr(E2d), _lib.ptr(bbox), _lib.ptr(srt), _lib.ptr(info),
                                                 _lib.ptr(valid), _lib.stream_ptr(stream)), "rgbm_adapose_postprocess_pnp")
     return bbox, srt, info, valid
+
+
+def postprocess_pnp_scaled(view1_nocs, view1_pts2d, view1_s, K, E1, seed: int = 0, stream=None):
+    """Device tail of `AdaPoseEstimator_realworld.predict` (`interface_realworld.py:295-320`): scale = ||view1_s|| in float32, then
+    `postprocess_pnp`'s steps from EPnP-RANSAC on with view 1 alone.  Returns (bbox_world [B,8,3] f64, srt [B,13] f64 = scale, R, t,
+    info [B,4] i32 = P / RANSAC ok / inliers / hypotheses examined, valid [B] i32) CUDA tensors.  view1_s [B,3] float32 (the network's
+    regressed size); pts2d: pixels of the chosen points in the ORIGINAL frame; K the original intrinsics.  5 <= P <= 1024."""
+    lib = _lib.load()
+    dev = view1_nocs.device
+    B, P = view1_nocs.shape[:2]
+    f32 = lambda x: torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    f64 = lambda x: torch.as_tensor(x).to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+    n1, p1, s1 = f32(view1_nocs), f32(view1_pts2d), f32(view1_s)
+    Kd, E1d = f64(K), f64(E1)
+    bbox = torch.empty(B, 8, 3, dtype=torch.float64, device=dev)
+    srt = torch.empty(B, 13, dtype=torch.float64, device=dev)
+    info = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    valid = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.rgbm_adapose_postprocess_pnp_scaled(B, P, int(seed) & 0xFFFFFFFF, _lib.ptr(n1), _lib.ptr(p1), _lib.ptr(s1), _lib.ptr(Kd),
+                                                       _lib.ptr(E1d), _lib.ptr(bbox), _lib.ptr(srt), _lib.ptr(info), _lib.ptr(valid),
+                                                       _lib.stream_ptr(stream)), "rgbm_adapose_postprocess_pnp_scaled")
+    return bbox, srt, info, valid
+
+
+def pts2d_to_coor(pts2d, W: int, H: int, stream=None):
+    """pts2d [..., 2] float32 CUDA (pixels in a W x H frame) -> (x / W, y / H) float32, the real-world network's coordinate inputs
+    (`interface_realworld.py:264-269`); true float32 divisions, equal to numpy's bit for bit."""
+    lib = _lib.load()
+    t = torch.as_tensor(pts2d).to(dtype=torch.float32).contiguous()
+    out = torch.empty_like(t)
+    _lib.check(lib.rgbm_pts2d_to_coor(_lib.ptr(t), _lib.ptr(out), t.numel() // 2, int(W), int(H), _lib.stream_ptr(stream)), "rgbm_pts2d_to_coor")
+    return out
 
 
 def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: int = 0, want_pts2d: bool = False, stream=None,

@@ -117,6 +117,33 @@ int AdaPose::create_baseline(const StateDict& sd, int dtype_, int regress_pose_)
   return regress_pose ? create_pose(sd) : 0;
 }
 
+// The real-world network (lib/network_realworld.py:133-232): v5's state dict plus camera_pts_mlp, pose_mlp1.0 128 wide.  Its per-point
+// branch stops at the NOCS (layers 4 / 5 of the point kernel's table are zero); pose_rows_kernel runs both 3 -> 32 -> 64 MLPs.
+int AdaPose::create_realworld(const StateDict& sd, int dtype_) {
+  RGBM_REQUIRE(dtype_ != F16, "create_realworld: dtype fp16 is not implemented for the real-world network (a voxel of its cost volume is a product of "
+               "two feature values, which squares their range, and f16 saturates at 65504): use fp32, bf16 or bf16x3");
+  dtype = dtype_;
+  norm_mode = 0;
+  arch = ARCH_REALWORLD;
+  if (int rc = create_backbone(sd)) return rc;
+  if (int rc = create_cost(sd)) return rc;
+  if (int rc = create_point_heads(sd, false)) return rc;
+  {
+    static const char* const names[4] = {"camera_pts_mlp.0", "camera_pts_mlp.2", "nocs_pts_mlp.0", "nocs_pts_mlp.2"};
+    const float* w[4]; const float* b[4];
+    for (int l = 0; l < 4; ++l) {
+      GET(wt, std::string(names[l]) + ".weight"); GET(bt, std::string(names[l]) + ".bias");
+      const int cin = l % 2 ? 32 : 3, cout = l % 2 ? 64 : 32;
+      RGBM_REQUIRE(wt->numel() == (long long)cin * cout && bt->numel() == cout, std::string("pose rows MLP shape ") + names[l]);
+      w[l] = wt->data; b[l] = bt->data;
+    }
+    std::vector<float> table((size_t)kPoseRowsFloats);
+    pose_rows_pack(w, b, table.data());
+    if (upload_f32(table.data(), table.size(), prow_w)) return -2;
+  }
+  return create_pose(sd);
+}
+
 int AdaPose::create_backbone(const StateDict& sd) {
   const int E = dtype_chunk(dtype);
   img_cpad = E;                              // RGB padded to one 16-byte chunk
@@ -218,7 +245,8 @@ int AdaPose::create_cost(const StateDict& sd) {
       if (dtype == BF16X3) { if (conv0_sweep_x3_upload(packed, sweep_w.out())) return -2; }
       else if (upload_packed(packed, dtype, sweep_w)) return -2;
       // the f16 form of the sweep (sweep_f16) only for weights that f16 can hold: otherwise sweep_w_f16 stays null and feat_f16() is false
-      if (dtype == BF16 && weights_fit_f16(packed) && upload_packed(packed, F16, sweep_w_f16)) return -2;
+      // (never for the real-world network: its variance volume has no f16 form)
+      if (dtype == BF16 && arch != ARCH_REALWORLD && weights_fit_f16(packed) && upload_packed(packed, F16, sweep_w_f16)) return -2;
     }
   }
   {
@@ -262,7 +290,11 @@ int AdaPose::create_point_heads(const StateDict& sd, bool pts_mlp) {
 }
 
 int AdaPose::create_pose(const StateDict& sd) {
-  if (int rc = init_linear(pm1[0], scratch, sd, "pose_mlp1.0", 96, 128, ACT_RELU, 96, 128, nullptr, pose_dtype())) return rc;
+  {
+    GET(w, "pose_mlp1.0.weight");
+    RGBM_REQUIRE(w->numel() == 128ll * pose_in(), "pose_mlp1.0 shape: " + std::to_string(pose_in()) + " input channels expected");
+  }
+  if (int rc = init_linear(pm1[0], scratch, sd, "pose_mlp1.0", pose_in(), 128, ACT_RELU, pose_in(), 128, nullptr, pose_dtype())) return rc;
   if (int rc = init_linear(pm1[1], scratch, sd, "pose_mlp1.2", 128, 128, ACT_RELU, 128, 128, nullptr, pose_dtype())) return rc;
   {
     // pose_mlp2.0 sees cat(point feature[128], global mean[128]); the global half becomes a per-view bias
@@ -345,8 +377,8 @@ int AdaPose::plan(int B, const ForwardPaths& p, Arena& A, Buffers& bf) const {
   bf.H64 = (float*)A.alloc(VP * 64 * 4);
   bf.nocs4 = (float*)A.alloc(VP * 4 * 4);
   bf.N32 = (float*)A.alloc(VP * 32 * 4);
-  bf.PF96 = (float*)A.alloc(VP * 96 * 4);
-  bf.PF96h = pose_dtype() == F16 ? A.alloc(VP * 96 * 2) : nullptr;
+  bf.PF96 = (float*)A.alloc(VP * pose_in() * 4);      // the pose rows: 96 channels, 128 for the real-world network
+  bf.PF96h = pose_dtype() == F16 ? A.alloc(VP * pose_in() * 2) : nullptr;
   bf.prob = (float*)A.alloc(VP * n_depth * 4);
   bf.depth = (float*)A.alloc(VP * 4);
   bf.Q128a = (float*)A.alloc(VP * 128 * 4);
@@ -563,6 +595,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
     d.feat = bf.feat; d.homog = bf.homog; d.depths = depths; d.v0 = v0; d.V = V; d.B = B;
     d.out_classmajor = layer == 9 ? 1 : 0;      // u11 is only gathered sparsely by the prob kernel
     d.tile_mask = tmask;
+    d.fusion = layer == 10 ? fusion() : FUSION_SUM;      // only the kernels that build voxels have a fusion
     d.tile_mask_stride = sparse_mask_bytes_per_view(S);
     if (layer == 10 && p.sweep_list) { d.tile_list = bf.sweep_list; d.tile_count = bf.sweep_count; }
     // profiler rows (prof.h): conv0 + fused warp on its own; bf16 layers one row each, f32 layers aggregated
@@ -593,7 +626,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
     int classmajor = 0;      // layout of the u11 the chunk body leaves behind
     if (p.cost_body == COST_BN_PER_SAMPLE) {
       // per-sample BatchNorm3d: every layer = un-normalised conv (generic implicit GEMM) -> per-view batch statistics -> normalise + ReLU (+ skip)
-      if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
+      if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s, fusion())) return rc;
       for (int i = 0; i < 10; ++i) {
         const Layer3d& l = l3d[i];
         const ConvLayer& L = c3d_raw[i];
@@ -605,7 +638,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
       }
     } else if (p.cost_body == COST_GENERIC) {
       // generic implicit GEMM on the materialised volume; the skip adds of conv7 / 9 / 11 are post-ReLU (network_v5.py:287-289)
-      if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
+      if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s, fusion())) return rc;
       for (int i = 0; i < 10; ++i) {
         const Layer3d& l = l3d[i];
         if (int rc = c3d[i].run(l.in, l.out, Vc, D / l.div, S / l.div, S / l.div, l.C, l.res, RES_POST_ACT, nullptr, 0, s)) return rc;
@@ -625,7 +658,7 @@ int AdaPose::cost_volume(const Buffers& bf, int V, int B, const float* depths, c
       for (int i = 0; i < (p.tail_sparse ? 9 : kCost3dLayers); ++i) {
         const Layer3d& l = l3d[i];
         if (i == 0 && p.conv0 == CONV0_TILE_VOLUME) {
-          if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s)) return rc;
+          if (int rc = launch_build_volume(dtype, bf.feat, bf.homog, depths, bf.vol, v0, Vc, V, B, D, S, S, s, fusion())) return rc;
           if (int rc = tile(0, l, Vc, v0, nullptr)) return rc;
         } else if (i == 0) {
           if (int rc = tile(10, l, Vc, v0, nullptr)) return rc;
@@ -661,6 +694,11 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   RGBM_REQUIRE(arch != ARCH_BASELINE || !(call.dense || call.depth_map || call.conf_map || call.nocs_map),
                "baseline network: the dense / maps forwards are not implemented (they read the cost volume this network does not have)");
   RGBM_REQUIRE(arch != ARCH_BASELINE || call.dropout == Dropout::None, "baseline network: Dropout2d is not implemented");
+  RGBM_REQUIRE(arch != ARCH_REALWORLD || !(call.dense || call.depth_map || call.conf_map || call.nocs_map),
+               "real-world network: the dense / maps forwards are not implemented");
+  RGBM_REQUIRE(arch != ARCH_REALWORLD || call.dropout == Dropout::None, "real-world network: Dropout2d is not implemented");
+  RGBM_REQUIRE(arch != ARCH_REALWORLD || (call.coor1 != nullptr && call.coor2 != nullptr),
+               "real-world network: the forward needs coor1 / coor2 (rgbm_adapose_forward_realworld)");
   const ForwardPaths p = paths(B, call.dense);
   Buffers bf;
   if (int rc = open_workspace(B, p, workspace, workspace_size, 0, call.dense ? "forward_dense: " : "", call.dense ? " (rgbm_adapose_dense_workspace_bytes)" : "", bf)) return rc;
@@ -704,6 +742,7 @@ int AdaPose::forward_samples(int B, int S, const float* img1, const float* img2,
                              const Call& call) const {
   RGBM_REQUIRE(B > 0 && S >= 1 && (long long)S * B <= (1 << 20), "forward_samples: B >= 1 poses and S >= 1 samples");
   RGBM_REQUIRE(arch != ARCH_BASELINE, "forward_samples: not implemented for the baseline network (it has no Dropout2d)");
+  RGBM_REQUIRE(arch != ARCH_REALWORLD, "forward_samples: not implemented for the real-world network");
   RGBM_REQUIRE(!(call.dense || call.depth_map || call.conf_map || call.nocs_map) && call.stop_after == 0, "forward_samples: no dense / maps form");
   RGBM_REQUIRE(call.dropout == Dropout::Draw || call.dropout == Dropout::Loaded,
                "forward_samples: Dropout2d is off and no masks are loaded (rgbm_adapose_set_dropout / rgbm_adapose_set_dropout_masks): the samples would be equal");
@@ -747,6 +786,7 @@ AdaPose::FeatSource AdaPose::gather_source(const Buffers& bf, const ForwardPaths
 PointMlpDesc AdaPose::point_mlp_desc(const Buffers& bf, const FeatSource& src, int Vh) const {
   PointMlpDesc pd{};
   pd.table = pmlp_table.get<float>(); pd.feat = src.feat; pd.choose = bf.choose; pd.nocs4 = bf.nocs4; pd.pf = bf.PF96 + 32; pd.ldpf = 96; pd.P = n_pts; pd.HW = img * img;
+  if (arch == ARCH_REALWORLD) { pd.pf = bf.X1; pd.ldpf = 64; }      // layers 4 / 5 of its table are zero: the 64 channels go to a buffer nothing reads
   pd.N = (long long)Vh * n_pts;
   return pd;
 }
@@ -815,8 +855,10 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
     if (int rc = nh[0].run(bf.X1, bf.H128, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
     if (int rc = nh[1].run(bf.H128, bf.H64, Vh, 1, 1, P, 64, nullptr, 0, nullptr, 0, s)) return rc;
     if (int rc = nh[2].run(bf.H64, bf.nocs4, Vh, 1, 1, P, 4, nullptr, 0, nullptr, 0, s)) return rc;
-    if (int rc = npm[0].run(bf.nocs4, bf.N32, Vh, 1, 1, P, 32, nullptr, 0, nullptr, 0, s)) return rc;
-    if (int rc = npm[1].run(bf.N32, bf.PF96 + 32, Vh, 1, 1, P, 96, nullptr, 0, nullptr, 0, s)) return rc;
+    if (arch != ARCH_REALWORLD) {      // (the real-world network's nocs_pts_mlp runs in pose_rows_kernel, below)
+      if (int rc = npm[0].run(bf.nocs4, bf.N32, Vh, 1, 1, P, 32, nullptr, 0, nullptr, 0, s)) return rc;
+      if (int rc = npm[1].run(bf.N32, bf.PF96 + 32, Vh, 1, 1, P, 96, nullptr, 0, nullptr, 0, s)) return rc;
+    }
   }
 
   // the same branch's layers 0..3 on every pixel of the Vh feature maps (the dense NOCS map)
@@ -828,7 +870,10 @@ int AdaPose::heads(const Buffers& bf, int B, const float* depths, const Outputs&
   if (call.stop_after == 2) return 0;
 
   // ---- depth-guided fusion + pose regression (network_v5.py:457-508) ----
-  if (int rc = launch_fuse_points(src.dtype, src.feat, bf.homog, depths, bf.choose, bf.prob, bf.PF96, V, B, P, D, S, S, 96, 0, s, Vh)) return rc;
+  // the real-world network (network_realworld.py:201-217): the pose rows are camera_pts_mlp(x / W, y / H, depth) | nocs_pts_mlp(nocs)
+  if (arch == ARCH_REALWORLD) {
+    if (int rc = launch_pose_rows(prow_w.get<float>(), bf.nocs4, call.coor1, call.coor2, bf.depth, bf.PF96, B, P, Vh, s)) return rc;
+  } else if (int rc = launch_fuse_points(src.dtype, src.feat, bf.homog, depths, bf.choose, bf.prob, bf.PF96, V, B, P, D, S, S, 96, 0, s, Vh)) return rc;
   if (int rc = pose_branch(bf, Vh, call, p)) return rc;
 
   // ---- outputs (fp32, reference shapes) ----
@@ -857,10 +902,10 @@ int AdaPose::pose_branch(const Buffers& bf, int Vh, const Call& call, const Forw
   } else {
     const void* pf_in = bf.PF96;
     if (pdt == F16) {
-      if (int rc = launch_f32_to_f16(bf.PF96, bf.PF96h, (long long)Vh * P * 96, s)) return rc;
+      if (int rc = launch_f32_to_f16(bf.PF96, bf.PF96h, (long long)Vh * P * pose_in(), s)) return rc;
       pf_in = bf.PF96h;
     } else if (pdt == BF16X3) {
-      if (int rc = launch_f32_to_bx3(bf.PF96, bf.PF96, (long long)Vh * P * 96, s)) return rc;      // in place: same 4-byte slots
+      if (int rc = launch_f32_to_bx3(bf.PF96, bf.PF96, (long long)Vh * P * pose_in(), s)) return rc;      // in place: same 4-byte slots
     }
     if (int rc = pm1[0].run(pf_in, bf.Q128a, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
     if (int rc = pm1[1].run(bf.Q128a, bf.Q128b, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
@@ -905,6 +950,7 @@ int AdaPose::features(int V, const float* images, const int* slots, void* pool, 
   hipStream_t s = call.stream;
   RGBM_REQUIRE(V > 0 && pool_records > 0, "features: views and pool records");
   RGBM_REQUIRE(arch != ARCH_BASELINE, "baseline network: the feature cache is not implemented");
+  RGBM_REQUIRE(arch != ARCH_REALWORLD, "real-world network: the feature cache is not implemented");
   RGBM_REQUIRE(call.dropout == Dropout::None, "features: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would change "
                "what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "features: workspace must be 256-byte, pool 16-byte aligned");
@@ -929,6 +975,7 @@ int AdaPose::forward_cached(int B, const void* pool, int pool_records, const int
   hipStream_t s = call.stream;
   RGBM_REQUIRE(B > 0 && pool_records > 0, "forward_cached: batch and pool records");
   RGBM_REQUIRE(arch != ARCH_BASELINE, "baseline network: the feature cache is not implemented");
+  RGBM_REQUIRE(arch != ARCH_REALWORLD, "real-world network: the feature cache is not implemented");
   RGBM_REQUIRE(call.dropout == Dropout::None, "forward_cached: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would "
                "change what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "forward_cached: workspace must be 256-byte, pool 16-byte aligned");

@@ -22,8 +22,14 @@ struct Arena {
 struct AdaPose {
   // which network the handle holds: network_v5.py's StereoPoseNet_with_depth, or network_baseline.py's StereoPoseNet_with_depth_baseline
   // (the cost volume and the depth-guided fusion replaced by the cross-view attention stack and depth_head: view_fusion.hip)
-  enum { ARCH_V5 = PATH_ARCH_V5, ARCH_BASELINE = PATH_ARCH_BASELINE };
+  // ARCH_REALWORLD, network_realworld.py's StereoPoseNet_with_depth_for_realdemo: v5 with the fused volume a variance (-2 ref warped
+  // instead of ref + warped: `fusion` of the conv0 kernels) and the pose rows built from camera points (camera_pts_mlp on x / W, y / H,
+  // depth in front of nocs_pts_mlp's 64 channels, pose_mlp1.0 128 wide: head_kernels.hip pose_rows_kernel) instead of depth-guided features
+  enum { ARCH_V5 = PATH_ARCH_V5, ARCH_BASELINE = PATH_ARCH_BASELINE, ARCH_REALWORLD = PATH_ARCH_REALWORLD };
   int arch = ARCH_V5;
+  int fusion() const { return arch == ARCH_REALWORLD ? FUSION_VARIANCE : FUSION_SUM; }      // how the plane sweep fuses a view with its warped partner
+  int pose_in() const { return arch == ARCH_REALWORLD ? 128 : 96; }                         // channels of a pose row (input of pose_mlp1.0)
+  DevBuf prow_w;                  // real-world: camera_pts_mlp and nocs_pts_mlp as pose_rows_kernel's LDS image (kernels.h: kPoseRowsFloats)
   int regress_pose = 1;           // baseline only: 0 = no pose branch (the six r / t / s outputs are NaN)
   DevBuf vf_w;                    // baseline: the attention stack's 32 linears (view_fusion.h: kVfWeightFloats)
   DevBuf dh_w;                    // baseline: depth_head (kDepthHeadFloats)
@@ -112,6 +118,8 @@ struct AdaPose {
     // point NOCS bit for bit; it needs nothing dense, and the ten outputs are the plain forward's bit for bit.
     float *depth_map = nullptr, *conf_map = nullptr, *nocs_map = nullptr;
     Dropout dropout = Dropout::None;
+    // real-world network only (required there): the chosen points' normalised image coordinates (x / W, y / H) [B][P][2] fp32 of both views
+    const float *coor1 = nullptr, *coor2 = nullptr;
   };
 
   struct Buffers {
@@ -137,6 +145,7 @@ struct AdaPose {
 
   int create(const StateDict& sd, int dtype, int norm_mode = 0);
   int create_baseline(const StateDict& sd, int dtype, int regress_pose);
+  int create_realworld(const StateDict& sd, int dtype);
   // the parts of a network create() / create_baseline() put together (dtype is set before)
   int create_backbone(const StateDict& sd);
   int create_cost(const StateDict& sd);

@@ -104,6 +104,7 @@ static int finish_call(rgbm_adapose* h, int B, const AdaPose::Call& call, int rc
 }
 
 static bool is_baseline(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_BASELINE; }
+static bool is_realworld(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_REALWORLD; }
 
 static int forward_call(rgbm_adapose* h, const char* name, int B, const float* img1, const float* img2, const int32_t* choose1,
                         const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace, size_t workspace_bytes,
@@ -114,6 +115,9 @@ static int forward_call(rgbm_adapose* h, const char* name, int B, const float* i
     if (int rc = prepare_call(h, name, B, {img1, img2, choose1, choose2, workspace, out}, stream, &call)) return rc;
     return h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), call);
   }
+  RGBM_REQUIRE(!is_realworld(h) || (call.coor1 && call.coor2), std::string(name) + ": the real-world network reads the chosen points' normalised "
+               "coordinates: call rgbm_adapose_forward_realworld (the dense / maps, graph, cached and samples forwards are not implemented for it)");
+  RGBM_REQUIRE(is_realworld(h) || !(call.coor1 || call.coor2), std::string(name) + ": coor1 / coor2 belong to the real-world network (rgbm_adapose_create_realworld)");
   if (int rc = prepare_call(h, name, B, {img1, img2, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
   RGBM_REQUIRE(h->drop_explicit == 0 || h->drop_explicit == B, "dropout: the masks set for the next forward are for batch " + std::to_string(h->drop_explicit));
   return finish_call(h, B, call, h->net.forward(B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, to_out(out), call));
@@ -146,7 +150,9 @@ static int create_handle(rgbm_adapose_t** h, const char* name, int device, const
   }
   std::unique_ptr<rgbm_adapose> obj(new rgbm_adapose());
   obj->device = device;
-  if (int rc = arch == AdaPose::ARCH_BASELINE ? obj->net.create_baseline(sd, dtype, mode) : obj->net.create(sd, dtype, mode)) return rc;
+  if (int rc = arch == AdaPose::ARCH_BASELINE    ? obj->net.create_baseline(sd, dtype, mode)
+               : arch == AdaPose::ARCH_REALWORLD ? obj->net.create_realworld(sd, dtype)
+                                                 : obj->net.create(sd, dtype, mode)) return rc;
   *h = obj.release();
   return 0;
 }
@@ -164,6 +170,31 @@ int rgbm_adapose_create(rgbm_adapose_t** h, int device, const rgbm_weight_desc* 
 int rgbm_adapose_create_baseline(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype, int regress_pose) {
   RGBM_REQUIRE(regress_pose == 0 || regress_pose == 1, "regress_pose: 0 or 1");
   return create_handle(h, "create_baseline", device, w, n_w, dtype, AdaPose::ARCH_BASELINE, regress_pose);
+}
+
+int rgbm_adapose_create_realworld(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype) {
+  return create_handle(h, "create_realworld", device, w, n_w, dtype, AdaPose::ARCH_REALWORLD, 0);
+}
+
+int rgbm_adapose_forward_realworld(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1, const int32_t* choose2,
+                                   const float* coor1, const float* coor2, const float* P1, const float* P2, const float* depths, void* workspace,
+                                   size_t workspace_bytes, const rgbm_adapose_out* out, int stop_after, void* stream) {
+  RGBM_REQUIRE(is_realworld(h), "forward_realworld: the handle does not hold the real-world network (rgbm_adapose_create_realworld)");
+  RGBM_REQUIRE(coor1 && coor2, "forward_realworld arguments");
+  AdaPose::Call call;
+  call.stop_after = stop_after;
+  call.coor1 = coor1; call.coor2 = coor2;
+  return forward_call(h, "forward_realworld", B, img1, img2, choose1, choose2, P1, P2, depths, workspace, workspace_bytes, out, stream, call);
+}
+
+int rgbm_pose_rows(rgbm_adapose_t* h, const float* nocs4, const float* coor1, const float* coor2, const float* depth, float* rows, int B, int P,
+                   int views, void* stream) {
+  RGBM_REQUIRE(is_realworld(h) && h->net.prow_w, "pose_rows: the handle does not hold the real-world network (rgbm_adapose_create_realworld)");
+  return launch_pose_rows(h->net.prow_w.get<float>(), nocs4, coor1, coor2, depth, rows, B, P, views, (hipStream_t)stream);
+}
+
+int rgbm_pts2d_to_coor(const float* pts2d_dev, float* coor_dev, int64_t n_points, int W, int H, void* stream) {
+  return launch_pts2d_to_coor(pts2d_dev, coor_dev, (long long)n_points, W, H, (hipStream_t)stream);
 }
 
 int rgbm_view_fusion_scratch_bytes(int B, int P, size_t* bytes) {
@@ -203,6 +234,8 @@ int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value) {
   if (is_baseline(h))
     for (const char* cv : {"cost_impl", "sparse_tail", "sparse_dec", "sweep_f16", "igemm_conv6"})
       RGBM_REQUIRE(k != cv, "option " + k + " belongs to the cost volume, which the baseline network does not have");
+  if (is_realworld(h))
+    RGBM_REQUIRE(!(k == "sweep_f16" && value != 0), "option sweep_f16 does not exist for the real-world network (its variance volume has no f16 form)");
   if (k == "max_chunk") { RGBM_REQUIRE(value > 0, "max_chunk"); h->net.max_chunk = value; }
   else if (k == "igemm_conv6") { RGBM_REQUIRE(value == 0 || value == 1, "igemm_conv6"); h->net.igemm_conv6 = value; }
   else if (k == "fuse_final") { RGBM_REQUIRE(value == 0 || value == 1, "fuse_final"); h->net.fuse_final = value; }
@@ -221,6 +254,7 @@ int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value) {
 int rgbm_adapose_set_dropout(rgbm_adapose_t* h, float p, uint64_t seed) {
   RGBM_REQUIRE(h && (p == 0.f || (p > 0.f && p < 1.f)), "set_dropout: p must be 0 (off) or lie in (0, 1)");
   RGBM_REQUIRE(!(is_baseline(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the baseline network");
+  RGBM_REQUIRE(!(is_realworld(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the real-world network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (!h->net.drop_state) RGBM_CHECK_HIP(hipMalloc(h->net.drop_state.out(), 2 * sizeof(unsigned long long)));
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // every forward issued before this call has drawn its masks
@@ -245,6 +279,7 @@ int rgbm_adapose_dropout_masks(rgbm_adapose_t* h, int B, float* out_dev) {
 int rgbm_adapose_set_dropout_masks(rgbm_adapose_t* h, int B, const float* masks_dev) {
   RGBM_REQUIRE(h && masks_dev && B > 0, "set_dropout_masks arguments");
   RGBM_REQUIRE(!is_baseline(h), "set_dropout_masks: Dropout2d is not implemented for the baseline network");
+  RGBM_REQUIRE(!is_realworld(h), "set_dropout_masks: Dropout2d is not implemented for the real-world network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (int rc = ensure_dropout_capacity(h, B)) return rc;
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // no forward in flight reads the buffer any more
@@ -451,6 +486,7 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
   if (n_nodes) *n_nodes = 0;
   if (captured) *captured = 0;
   RGBM_REQUIRE(!is_baseline(h), "forward_graph: hipGraph replay is not implemented for the baseline network");
+  RGBM_REQUIRE(!is_realworld(h), "forward_graph: hipGraph replay is not implemented for the real-world network");
   AdaPose::Call call;
   // the in-library profiler records events around launches: not capturable, and a timing run wants the launches themselves
   // masks loaded by rgbm_adapose_set_dropout_masks are for one forward: not captured
@@ -558,7 +594,7 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   else if (nm == "homog") { src = bf.homog; cnt = V * 12; dt = F32; }
   else if (nm == "prob") { src = bf.prob; cnt = V * P * D; dt = F32; }
   // pf96: after a forward of a split-pair net the buffer holds hi / lo pairs (adapose.cpp converts it in place for the pose MLP)
-  else if (nm == "pf96") { src = bf.PF96; cnt = V * P * 96; dt = n.pose_dtype() == BF16X3 ? BF16X3 : F32; }
+  else if (nm == "pf96") { src = bf.PF96; cnt = V * P * n.pose_in(); dt = n.pose_dtype() == BF16X3 ? BF16X3 : F32; }
   else if (nm == "pf2") { src = bf.pf2; cnt = V * 256; dt = F32; }
   else if (nm == "r6") { src = bf.r6; cnt = V * 6; dt = F32; }
   else if (nm == "fused1" && bf.fused) { src = bf.fused; cnt = (size_t)B * P * 32; dt = F32; }
@@ -778,6 +814,11 @@ int rgbm_build_volume(int dtype, const void* feat_dev, const float* P_views_dev,
   if (int rc = launch_homography(P_views_dev, homog_scratch, V, B, (hipStream_t)stream)) return rc;
   return launch_build_volume(dtype, feat_dev, homog_scratch, depths_dev, vol_dev, 0, V, V, B, D, H, W, (hipStream_t)stream);
 }
+int rgbm_build_volume_fusion(int dtype, int fusion, const void* feat_dev, const float* P_views_dev, const float* depths_dev, float* homog_scratch,
+                             void* vol_dev, int V, int B, int D, int H, int W, void* stream) {
+  if (int rc = launch_homography(P_views_dev, homog_scratch, V, B, (hipStream_t)stream)) return rc;
+  return launch_build_volume(dtype, feat_dev, homog_scratch, depths_dev, vol_dev, 0, V, V, B, D, H, W, (hipStream_t)stream, fusion);
+}
 
 }  // extern "C"
 
@@ -947,6 +988,12 @@ extern "C" int rgbm_adapose_postprocess_pnp(int B, int P, uint32_t seed, const f
                                             const float* pts2d2, const double* K, const double* E1, const double* E2, double* bbox_out,
                                             double* srt_out, int32_t* info_out, int32_t* valid_out, void* stream) {
   return launch_pnp_ransac(nocs1, pts2d1, nocs2, pts2d2, K, E1, E2, bbox_out, srt_out, info_out, valid_out, B, P, seed, (hipStream_t)stream);
+}
+
+extern "C" int rgbm_adapose_postprocess_pnp_scaled(int B, int P, uint32_t seed, const float* nocs1, const float* pts2d1, const float* s1,
+                                                   const double* K, const double* E1, double* bbox_out, double* srt_out, int32_t* info_out,
+                                                   int32_t* valid_out, void* stream) {
+  return launch_pnp_scaled(nocs1, pts2d1, s1, K, E1, bbox_out, srt_out, info_out, valid_out, B, P, seed, (hipStream_t)stream);
 }
 
 extern "C" int rgbm_projection(const double* Kcrop_dev, const double* E_dev, float* P_dev, int N, void* stream) {

@@ -157,7 +157,10 @@ template <> struct Sw16<f16_t> {
 //      4 perm + 4 dot2 + 1 convert per dword, no packed-fp32 instruction.  The products are exact (bf16 x bf16 in fp32), the weights
 //      carry 8 significant bits — the rounding the gathered features already have; a corner outside the image keeps weight 0 exactly,
 //      a non-finite projection keeps NaN.
-template <typename T, int BL>
+// FUSE (kernels.h: FUSION_*; mode 0 only): FUSION_VARIANCE makes the voxel -2 ref warped, the real-world network's variance volume - the
+// same bilinear sum in the same order on weights the caller has multiplied by -2 (exact, so the sum is -2 warped bit for bit), then one
+// fp32 product with the reference feature where the sum form has its add; rounded once by the pack.
+template <typename T, int BL, int FUSE = FUSION_SUM>
 __device__ __forceinline__ uint4 blend_chunk(const uint4& r, const u32x4& a, const u32x4& b, const u32x4& c, const u32x4& e,
                                              const Corner& cn) {
   const float* w = cn.w;
@@ -197,8 +200,13 @@ __device__ __forceinline__ uint4 blend_chunk(const uint4& r, const u32x4& a, con
     } else {
       const f32x2 fr = Sw16<T>::unpack(rr[q]), fa = Sw16<T>::unpack(aa[q]), fb = Sw16<T>::unpack(bb[q]);
       const f32x2 fc = Sw16<T>::unpack(cc[q]), fe = Sw16<T>::unpack(ee[q]);
-      const f32x2 v = fr + (((fa * w[0] + fb * w[1]) + fc * w[2]) + fe * w[3]);
-      o[q] = Sw16<T>::pack(v);
+      if constexpr (FUSE == FUSION_VARIANCE) {
+        const f32x2 v = fr * (((fa * w[0] + fb * w[1]) + fc * w[2]) + fe * w[3]);
+        o[q] = Sw16<T>::pack(v);
+      } else {
+        const f32x2 v = fr + (((fa * w[0] + fb * w[1]) + fc * w[2]) + fe * w[3]);
+        o[q] = Sw16<T>::pack(v);
+      }
     }
   }
   return make_uint4(o[0], o[1], o[2], o[3]);
@@ -299,8 +307,10 @@ __device__ __forceinline__ void sw_corner_weights(float rx, float ry, float rz, 
 // form below turns into a design (-DSW_OCC=4, two workgroups per CU at 128 registers: 64 bytes of scratch, slower).
 // T: storage type of the feature maps and the conv0 weights = the MFMA operand type; TO: storage type of c0.  <f16_t, unsigned short> is the
 // bf16 nets' default since round 5 (`final` writes their feature map as f16 for this kernel: adapose.cpp feat_f16()).
-template <typename T, typename TO, int BL>
+// FUSE: the variance volume of the real-world network, for <bf16, bf16, 0> (blend_chunk).
+template <typename T, typename TO, int BL, int FUSE = FUSION_SUM>
 __global__ __launch_bounds__(SW_THREADS, SW_OCC) void conv0_sweep_kernel(const SweepDesc d) {
+  static_assert(FUSE == FUSION_SUM || (std::is_same<T, unsigned short>::value && BL == 0), "the variance volume exists for the fp32 blend of bf16 feature maps");
   extern __shared__ __attribute__((aligned(16))) unsigned char planes[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
@@ -473,6 +483,10 @@ __global__ __launch_bounds__(SW_THREADS, SW_OCC) void conv0_sweep_kernel(const S
 
     auto corners = [&](int z, Corner& c) {
       sw_corner_weights(rx, ry, rz, t0, t1, t2, __int_as_float(__builtin_amdgcn_readlane(dbits, z)), sx, sy, W, H, inb, c.w, c.off);
+      if constexpr (FUSE == FUSION_VARIANCE) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) c.w[q] *= -2.f;
+      }
       if constexpr (BL == 2) {
         c.wp[0] = pack2_bf16(c.w[0], c.w[1]);
         c.wp[1] = pack2_bf16(c.w[2], c.w[3]);
@@ -508,7 +522,7 @@ __global__ __launch_bounds__(SW_THREADS, SW_OCC) void conv0_sweep_kernel(const S
     auto blend = [](const uint4& r, const u32x4& a, const u32x4& b, const u32x4& c, const u32x4& e, const Corner& cn) {
       if (SW_SKIP && std::is_same<T, unsigned short>::value && cn.skip) return r;      // wave-uniform; the gathers and their counted waits around this call are unconditional
       if constexpr (std::is_same<T, f16_t>::value) return blend_chunk_f16<BL == 3>(r, a, b, c, e, cn);
-      else return blend_chunk<T, BL>(r, a, b, c, e, cn);
+      else return blend_chunk<T, BL, FUSE>(r, a, b, c, e, cn);
     };
     u32x4 g[4][4];                                       // [chunk][corner]
 #pragma unroll
@@ -1010,7 +1024,10 @@ int launch_conv0_sweep(const Conv3dTileDesc& t, int dtype, hipStream_t s) {
   // without packed fp32 instructions the three bf16 modes are level - 44.11 / 44.15 / 44.09 ms per forward - and the dot2 form rounds the
   // bilinear weights to 8 bits); debug flag 4194304 = v_perm + v_dot2_f32_bf16 (the round-4 default), 2097152 = fp32 FMAs from inline asm.
   const bool f21 = (g_debug_flags & DBG_SWEEP_ALT_BLEND) != 0, f22 = (g_debug_flags & DBG_SWEEP_DOT2) != 0;
-  if (((dtype == BF16 && t.feat_f16) || dtype == F16) && !(g_debug_flags & DBG_SWEEP_PER_TILE)) {
+  RGBM_REQUIRE(t.fusion == FUSION_SUM || (t.fusion == FUSION_VARIANCE && dtype == BF16 && !t.feat_f16),
+               "conv0 sweep: the variance volume exists for bf16 feature maps only (no f16 form: a product of two features squares their range)");
+  if (t.fusion == FUSION_VARIANCE) SW_LAUNCH(u16, u16, 0, FUSION_VARIANCE);      // the fp32 blend, whatever the blend debug flags say
+  else if (((dtype == BF16 && t.feat_f16) || dtype == F16) && !(g_debug_flags & DBG_SWEEP_PER_TILE)) {
     // the persistent form (debug flag 268435456 = one workgroup per tile, for A/B); fp16 nets (round 6): with their fp32-accumulating blend,
     // debug flag 2097152 = the packed blend for them too
     auto kern = dtype == BF16 ? conv0_sweep_persistent_kernel<u16, false> : f21 ? conv0_sweep_persistent_kernel<f16_t, false>

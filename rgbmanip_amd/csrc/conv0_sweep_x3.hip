@@ -66,12 +66,24 @@ __device__ __forceinline__ f32x4 mma32(const uint4& a, const uint4& b, const f32
 
 // 4 channels of one voxel: ref + w0*a + w1*b + w2*c + w3*e as one fma chain (whole-vector arithmetic: the gathered registers
 // are tied inline-asm results, see hazard (4) in DESIGN.md about indexing them with an unrolled loop counter)
+// FUSE (kernels.h: FUSION_*) = FUSION_VARIANCE, the real-world network's volume -2 ref warped: the same chain without the reference
+// feature in front (the bilinear sum alone, corners in the same order) on weights the owner has multiplied by -2 (publish: exact, so
+// the sum is -2 warped bit for bit), then one fp32 product with the reference feature - before the hi / lo split
+template <int FUSE>
 __device__ __forceinline__ f4v blend4(const f4v& r, const f4v& a, const f4v& b, const f4v& c, const f4v& e, const float* w) {
-  f4v t = a * w[0] + r;
-  t = b * w[1] + t;
-  t = c * w[2] + t;
-  t = e * w[3] + t;
-  return t;
+  if constexpr (FUSE == FUSION_VARIANCE) {
+    f4v t = a * w[0];
+    t = b * w[1] + t;
+    t = c * w[2] + t;
+    t = e * w[3] + t;
+    return r * t;
+  } else {
+    f4v t = a * w[0] + r;
+    t = b * w[1] + t;
+    t = c * w[2] + t;
+    t = e * w[3] + t;
+    return t;
+  }
 }
 
 // 8 fp32 channels -> their bf16 hi parts (16 bytes) and lo parts (16 bytes)
@@ -89,6 +101,7 @@ __device__ __forceinline__ void split8(const float* o, uint4& hi, uint4& lo) {
 }  // namespace
 
 // one workgroup per CU (<= 256 VGPRs): 8 waves, a producer and a consumer per SIMD
+template <int FUSE = FUSION_SUM>
 __global__ __launch_bounds__(X3_THREADS, 2) void conv0_sweep_x3_kernel(const Sweep3Desc d) {
   extern __shared__ __attribute__((aligned(16))) unsigned char planes[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -216,6 +229,7 @@ __global__ __launch_bounds__(X3_THREADS, 2) void conv0_sweep_x3_kernel(const Swe
       w.z = (P.inb && xin0 && yin1) ? ux * ty : 0.f;
       w.w = (P.inb && xin1 && yin1) ? tx * ty : 0.f;
       if (P.inb && !fin) w.x = __builtin_nanf("");           // the voxel becomes NaN like the reference's
+      if constexpr (FUSE == FUSION_VARIANCE) w = w * -2.f;
       const unsigned r0 = (unsigned)(yc0 * W), r1 = (unsigned)(yc1 * W);
       u4v off;
       off.x = (r0 + (unsigned)xc0) * 128u;
@@ -241,7 +255,7 @@ __global__ __launch_bounds__(X3_THREADS, 2) void conv0_sweep_x3_kernel(const Swe
     {                                                                                                            \
       X3_WAITB((R) % X3_DEPTH);                                                                                  \
       const float wq[4] = {wc.x, wc.y, wc.z, wc.w};                                                              \
-      f4v t = blend4(ref[R], g[(R) % X3_DEPTH][0], g[(R) % X3_DEPTH][1], g[(R) % X3_DEPTH][2], g[(R) % X3_DEPTH][3], wq); \
+      f4v t = blend4<FUSE>(ref[R], g[(R) % X3_DEPTH][0], g[(R) % X3_DEPTH][1], g[(R) % X3_DEPTH][2], g[(R) % X3_DEPTH][3], wq); \
       /* the blend must be DONE before the registers are requested again: without this tie hipcc sank round 7's blend into \
          the `vact7` branch below the gathers and kept "the old values" in copies made before the wait, i.e. stale ones */ \
       asm volatile("" : "+v"(t));                                                                                \
@@ -527,13 +541,15 @@ int launch_conv0_sweep_x3(const Conv3dTileDesc& t, hipStream_t s) {
   d.n_tiles = (int)ntiles;
   d.tile_list = t.tile_list; d.tile_count = t.tile_count;
   RGBM_REQUIRE((d.tile_list == nullptr) == (d.tile_count == nullptr), "conv0 sweep: tile list and count go together");
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(conv0_sweep_x3_kernel), X3_LDS)) return rc;
+  RGBM_REQUIRE(t.fusion == FUSION_SUM || t.fusion == FUSION_VARIANCE, "conv0 sweep (bf16x3): fusion 0 (sum) or 1 (variance)");
+  auto kern = t.fusion == FUSION_VARIANCE ? conv0_sweep_x3_kernel<FUSION_VARIANCE> : conv0_sweep_x3_kernel<FUSION_SUM>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), X3_LDS)) return rc;
   int n_cu = 0;
   if (int rc = persistent_grid_cus(&n_cu)) return rc;
   // the tile order assumes a grid that is a multiple of 8 (XCD = block % 8); small launches round up and idle blocks exit
   int grid = ntiles < n_cu ? (int)((ntiles + 7) / 8 * 8) : n_cu;
   prof_begin_launch(s, t.prof_variant, t.algo_flops, t.algo_bytes);
-  hipLaunchKernelGGL(conv0_sweep_x3_kernel, dim3((unsigned)grid), dim3(X3_THREADS), X3_LDS, s, d);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(X3_THREADS), X3_LDS, s, d);
   prof_end_launch(s);
   RGBM_CHECK_HIP(hipGetLastError());
   return 0;

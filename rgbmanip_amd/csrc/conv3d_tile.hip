@@ -97,7 +97,8 @@ template <int N> struct IC { static constexpr int value = N; };
 template <int... I, typename F> __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(IC<I>{}), ...); }
 template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
-template <typename T, int CIN, int COUTP, int TD, int TH, int TW, int STRIDE, bool TR, bool WARP, int WC = 1>
+// FUSE (WARP only; kernels.h: FUSION_*): the staged voxel is ref + warped, or the real-world network's variance -2 ref warped
+template <typename T, int CIN, int COUTP, int TD, int TH, int TW, int STRIDE, bool TR, bool WARP, int WC = 1, int FUSE = FUSION_SUM>
 __global__ __launch_bounds__(256, 2) void conv3d_tile_kernel(const Conv3dTileDesc d) {
   using Cfg = C3Cfg<T, CIN, COUTP, TD, TH, TW, STRIDE, TR, WC>;
   constexpr int VS = Cfg::VS, CPV = Cfg::CPV, HH = Cfg::HH, HW = Cfg::HW, NVH = Cfg::NVH;
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_tile_kernel(const Conv3dTileDes
 #pragma unroll
           for (int q = 0; q < E; ++q) {
             const float wsum = ((fa[q] * w00 + fb[q] * w01) + fc[q] * w10) + fe[q] * w11;
-            o[q] = fin ? fr[q] + wsum : __builtin_nanf("");
+            o[q] = !fin ? __builtin_nanf("") : FUSE == FUSION_VARIANCE ? (-2.f * fr[q]) * wsum : fr[q] + wsum;
           }
           *reinterpret_cast<uint4*>(dst + (c0 + k) * 16) = pack_chunk(o, T());
         }
@@ -479,7 +480,7 @@ void conv3d_tile_pack(const float* w, const float* scale, int Cin, int Cout, int
   }
 }
 
-template <typename T, int CIN, int COUTP, int TD, int TH, int TW, int STRIDE, bool TR, bool WARP, int WC = 1>
+template <typename T, int CIN, int COUTP, int TD, int TH, int TW, int STRIDE, bool TR, bool WARP, int WC = 1, int FUSE = FUSION_SUM>
 static int launch_c3(Conv3dTileDesc d, hipStream_t s) {
   using Cfg = C3Cfg<T, CIN, COUTP, TD, TH, TW, STRIDE, TR, WC>;
   constexpr size_t LDS = Cfg::LDS_BYTES;
@@ -487,13 +488,20 @@ static int launch_c3(Conv3dTileDesc d, hipStream_t s) {
   d.ntd = (d.Dq + TD - 1) / TD; d.nth = (d.Hq + TH - 1) / TH; d.ntw = (d.Wq + TW - 1) / TW;
   const long long nblk = (long long)d.N * d.ntd * d.nth * d.ntw;
   RGBM_REQUIRE(nblk > 0 && nblk < (1ll << 31), "conv3d grid out of range");
-  auto kern = conv3d_tile_kernel<T, CIN, COUTP, TD, TH, TW, STRIDE, TR, WARP, WC>;
+  auto kern = conv3d_tile_kernel<T, CIN, COUTP, TD, TH, TW, STRIDE, TR, WARP, WC, FUSE>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)LDS)) return rc;
   prof_begin_launch(s, d.prof_variant, d.algo_flops, d.algo_bytes);
   hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), LDS, s, d);
   prof_end_launch(s);
   RGBM_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+// the variance form of a row with the fused plane sweep (the other rows have none: only the sweep builds voxels)
+template <typename T, int CIN, int COUTP, int TD, int TH, int TW, int STRIDE, bool TR, bool WARP, int WC>
+static int launch_c3_variance(const Conv3dTileDesc& d, hipStream_t s) {
+  if constexpr (WARP) return launch_c3<T, CIN, COUTP, TD, TH, TW, STRIDE, TR, WARP, WC, FUSION_VARIANCE>(d, s);
+  else return -1;
 }
 
 int conv3d_tile_dims(int layer, int dtype, int* TD, int* TH, int* TW) {
@@ -510,6 +518,17 @@ int conv3d_tile_dims(int layer, int dtype, int* TD, int* TH, int* TW) {
 
 // layer ids: 0..6 = conv0..conv6, 7..9 = conv7/9/11 (transposed), 10 = conv0 with fused warp
 int launch_conv3d_tile(int layer, int dtype, const Conv3dTileDesc& d, hipStream_t s) {
+  RGBM_REQUIRE(d.fusion == FUSION_SUM || (d.fusion == FUSION_VARIANCE && layer == 10 && dtype != F16),
+               "conv3d_tile: the variance volume exists for the fused plane sweep (layer 10) in fp32, bf16 and split-pair storage");
+  if (d.fusion == FUSION_VARIANCE) {      // row 10 of the table with FUSE = variance
+#define C3_CASE(L, CIN, COUTP, TDB, THB, TWB, TDF, THF, TWF, STRIDE, TR, WARP, WCB, WCF)                                        \
+    if (WARP)                                                                                                                   \
+      return dtype == BF16     ? launch_c3_variance<unsigned short, CIN, COUTP, TDB, THB, TWB, STRIDE, TR, WARP, WCB>(d, s)     \
+             : dtype == BF16X3 ? launch_c3_variance<bx3_t, CIN, COUTP, TDF, THF, TWF, STRIDE, TR, WARP, WCF>(d, s)              \
+                               : launch_c3_variance<float, CIN, COUTP, TDF, THF, TWF, STRIDE, TR, WARP, 1>(d, s);
+#include "conv3d_tile_table.h"
+#undef C3_CASE
+  }
 #define C3_CASE(L, CIN, COUTP, TDB, THB, TWB, TDF, THF, TWF, STRIDE, TR, WARP, WCB, WCF)                           \
   case L:                                                                                                          \
     return dtype == BF16  ? launch_c3<unsigned short, CIN, COUTP, TDB, THB, TWB, STRIDE, TR, WARP, WCB>(d, s)      \

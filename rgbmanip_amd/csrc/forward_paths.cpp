@@ -25,7 +25,7 @@ ForwardPaths forward_paths(const PathFacts& f) {
   p.up3 = (f.upconv & 4) && f.tail_ready ? UP3_TAIL_KERNEL : f.fuse_final ? UP3_FUSED_FINAL : UP3_TWO_LAUNCHES;
   // sweep_w_f16 exists only for conv0 weights that f16 can hold, tail_f16_ready only for such `final` weights: otherwise all bf16
   if (x3 && sweep && f.sweep_w && eval_bn) p.feat_form = FEAT_F32_ONLY;
-  else if (f.dtype == RGBM_BF16 && f.sweep_f16 && sweep && f.sweep_w_f16 && eval_bn && p.up3 == UP3_TAIL_KERNEL && f.tail_f16_ready) p.feat_form = FEAT_F16;
+  else if (f.arch != PATH_ARCH_REALWORLD && f.dtype == RGBM_BF16 && f.sweep_f16 && sweep && f.sweep_w_f16 && eval_bn && p.up3 == UP3_TAIL_KERNEL && f.tail_f16_ready) p.feat_form = FEAT_F16;
   else p.feat_form = FEAT_STORAGE;
   // split pairs: everything that GATHERS from the feature map (plane sweep, point heads) reads a plain fp32 copy of it
   p.feat_copy = x3 && p.feat_form != FEAT_F32_ONLY;
@@ -51,6 +51,7 @@ ForwardPaths forward_paths(const PathFacts& f) {
   // ---- heads ----
   // the baseline network has the one-launch point MLP only (heads_baseline refuses what it cannot run)
   p.point_mlp = f.arch == PATH_ARCH_BASELINE || (f.pmlp_table && !(f.flags & PATH_FLAG_POINT_MLP_R5) && ((long long)f.Vh * f.n_pts) % 64 == 0);
+  // (the real-world network's pose_mlp1.0 is 128 wide: pose_shape_ok asks for 96, so its pose MLP runs per layer)
   p.pose_mlp = pose_storage(f.dtype, f.pose_x3) == RGBM_F16 && !(f.flags & PATH_FLAG_POSE_MLP_R6) && f.pose_shape_ok;
   return p;
 }

@@ -796,6 +796,78 @@ int launch_ortho6d(const float* r6, float* R, int V, hipStream_t s) {
   return 0;
 }
 
+// ---------------------------------------------------------------- pose rows of the real-world network (network_realworld.py:201-209)
+// row[pt] = camera_pts_mlp(x / W, y / H, depth) [64] | nocs_pts_mlp(nocs) [64]: two Conv1d 3 -> 32 -> 64 + ReLU, fp32.  K is 3 and 32: no
+// matrix shape.  A wave carries 64 points through ONE of the two MLPs (wave-uniform, so every weight read is an LDS broadcast): the 32
+// hidden values of its point stay in a lane's registers, the 64 outputs leave as 16-byte stores.  Both tables (18 KB) sit in LDS.
+void pose_rows_pack(const float* const w[4], const float* const b[4], float* table) {
+  for (int m = 0; m < 2; ++m) {
+    float* t = table + m * kPoseRowsMlpFloats;
+    for (int j = 0; j < 32; ++j) {
+      for (int i = 0; i < 3; ++i) t[j * 4 + i] = w[2 * m][j * 3 + i];
+      t[j * 4 + 3] = 0.f;
+      t[128 + j] = b[2 * m][j];
+    }
+    for (int c = 0; c < 64; ++c) {
+      for (int k = 0; k < 32; ++k) t[160 + k * 64 + c] = w[2 * m + 1][c * 32 + k];
+      t[160 + 2048 + c] = b[2 * m + 1][c];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void pose_rows_kernel(const float* __restrict__ table, const float* __restrict__ nocs4, const float* __restrict__ coor1,
+                                                        const float* __restrict__ coor2, const float* __restrict__ depth, float* __restrict__ rows,
+                                                        int B, int P, long long N) {
+  __shared__ __attribute__((aligned(16))) float w[kPoseRowsFloats];
+  for (int i = threadIdx.x; i < kPoseRowsFloats; i += 256) w[i] = table[i];
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int m = wave & 1;                                      // 0: camera_pts_mlp -> channels 0-63, 1: nocs_pts_mlp -> channels 64-127
+  const long long pt = (long long)blockIdx.x * 128 + (wave >> 1) * 64 + lane;
+  if (pt >= N) return;
+  float x0, x1, x2;
+  if (m == 0) {
+    const long long v = pt / P, p = pt - v * P;
+    const float* c = v < B ? coor1 + (v * P + p) * 2 : coor2 + ((v - B) * P + p) * 2;
+    x0 = c[0]; x1 = c[1]; x2 = depth[pt];
+  } else {
+    const float4 n = *reinterpret_cast<const float4*>(nocs4 + pt * 4);
+    x0 = n.x; x1 = n.y; x2 = n.z;
+  }
+  const float* t = w + m * kPoseRowsMlpFloats;
+  float h[32];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const float4 wj = *reinterpret_cast<const float4*>(t + j * 4);
+    const float a = fmaf(wj.z, x2, fmaf(wj.y, x1, fmaf(wj.x, x0, t[128 + j])));
+    h[j] = a > 0.f ? a : 0.f;
+  }
+  float* o = rows + pt * 128 + m * 64;
+#pragma unroll 1
+  for (int c0 = 0; c0 < 64; c0 += 4) {
+    float4 acc = *reinterpret_cast<const float4*>(t + 160 + 2048 + c0);
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+      const float4 wk = *reinterpret_cast<const float4*>(t + 160 + k * 64 + c0);
+      acc.x = fmaf(h[k], wk.x, acc.x); acc.y = fmaf(h[k], wk.y, acc.y); acc.z = fmaf(h[k], wk.z, acc.z); acc.w = fmaf(h[k], wk.w, acc.w);
+    }
+    acc.x = acc.x > 0.f ? acc.x : 0.f; acc.y = acc.y > 0.f ? acc.y : 0.f; acc.z = acc.z > 0.f ? acc.z : 0.f; acc.w = acc.w > 0.f ? acc.w : 0.f;
+    *reinterpret_cast<float4*>(o + c0) = acc;
+  }
+}
+
+int launch_pose_rows(const float* table, const float* nocs4, const float* coor1, const float* coor2, const float* depth, float* rows, int B,
+                     int P, int Vh, hipStream_t s) {
+  RGBM_REQUIRE(table && nocs4 && coor1 && depth && rows && B > 0 && P > 0 && (Vh == B || Vh == 2 * B), "pose_rows arguments");
+  RGBM_REQUIRE(Vh == B || coor2 != nullptr, "pose_rows: coor2 is NULL and the view-2 rows are wanted");
+  const long long N = (long long)Vh * P;
+  const long long grid = (N + 127) / 128;
+  RGBM_REQUIRE(grid < (1ll << 31), "pose_rows grid out of range");
+  hipLaunchKernelGGL(pose_rows_kernel, dim3((unsigned)grid), dim3(256), 0, s, table, nocs4, coor1, coor2, depth, rows, B, P, N);
+  RGBM_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------- strided row copy (fp32), e.g. [rows][4] -> [rows][3]
 __global__ void copy_cols_kernel(const float* __restrict__ in, float* __restrict__ out, long long rows, int ldi, int ldo, int n) {
   const long long total = rows * n;

@@ -20,8 +20,13 @@ int launch_psp_pool_conv(int dtype, const void* in, int ldi, const void* const* 
                          int act, float slope, hipStream_t s);
 int launch_psp_resize_cat(int dtype, const void* f, const void* const* stages, const int* bins, void* out, int V, int Ho, int Wo, hipStream_t s);
 int launch_homography(const float* P_views, float* out, int V, int B, hipStream_t s);
+// How the plane sweep fuses a view's feature with its warped partner, a compile-time parameter of every kernel that builds voxels:
+// FUSION_SUM ref + warped (network_v5.py:429-430), FUSION_VARIANCE -2 ref warped = ref^2 + warped^2 - (ref + warped)^2
+// (network_realworld.py:145-166) - one fp32 product of the bilinear sum, rounded once to the voxel's storage; 0 where the partner
+// view projects outside the image.  The packed-f16 forms have no variance (a product of two features squares their range).
+enum { FUSION_SUM = 0, FUSION_VARIANCE = 1 };
 int launch_build_volume(int dtype, const void* feat, const float* homog, const float* depths, void* vol, int v0, int Vc, int V,
-                        int B, int D, int H, int W, hipStream_t s);
+                        int B, int D, int H, int W, hipStream_t s, int fusion = FUSION_SUM);
 
 // upconv.hip — tap-combining half of PSPUpsample evaluated as a low-resolution 1x1 GEMM (layers.h, UpConvLayer):
 // z [V][h][w][9*Co] (tap-major) -> out [V][2h][2w][ldo] = act(bias + sum_t bilinear(z_t)(p + t))
@@ -116,6 +121,16 @@ void point_mlp_pack(const float* const w[6], const float* const b[6], float* tab
 int launch_point_mlp(int feat_dtype, const PointMlpDesc& d, hipStream_t s);
 // the same table's layers 0..3 on every pixel: feat [N][32] (bf16 / f16 / fp32) -> out [N][3] fp32, N % 64 == 0
 int launch_dense_nocs(int feat_dtype, const float* table, const void* feat, float* out, long long N, hipStream_t s);
+// head_kernels.hip: the pose rows of the real-world network (network_realworld.py:201-209) in one launch.  Row of point p of view v < Vh
+// (views [view-1 crops ; view-2 crops] of B poses): channels 0-63 camera_pts_mlp(coor[p][0], coor[p][1], depth[p]), channels 64-127
+// nocs_pts_mlp(nocs4[p][0..2]); both Conv1d 3 -> 32 -> 64 with ReLU, fp32, weights in LDS.  coor1 / coor2 [B][P][2] hold x / W, y / H.
+constexpr int kPoseRowsMlpFloats = 32 * 4 + 32 + 32 * 64 + 64;      // one MLP: W0 [32][4] (column 3 zero), b0 [32], W1 transposed [32][64], b1 [64]
+constexpr int kPoseRowsFloats = 2 * kPoseRowsMlpFloats;             // camera_pts_mlp, then nocs_pts_mlp
+void pose_rows_pack(const float* const w[4], const float* const b[4], float* table);      // host; camera_pts_mlp.0 / .2, nocs_pts_mlp.0 / .2 as [Cout][Cin]
+int launch_pose_rows(const float* table, const float* nocs4, const float* coor1, const float* coor2, const float* depth, float* rows, int B,
+                     int P, int Vh, hipStream_t s);
+// coor[i] = (pts2d[i][0] / W, pts2d[i][1] / H) in IEEE float32 division (interface_realworld.py:264-269), n points
+int launch_pts2d_to_coor(const float* pts2d, float* coor, long long n, int W, int H, hipStream_t s);
 int launch_ortho6d(const float* r6, float* R, int V, hipStream_t s);
 // consumers that finish a mean over points themselves (one launch less per mean): launch_mean_points_partial writes the slices' sums
 int launch_mean_points_partial(int dtype, const void* in, float* scratch, int V, int P, int C, hipStream_t s);
@@ -165,6 +180,7 @@ struct Conv3dTileDesc {
   int feat_f16;      // depth-sweeping conv0 of a bf16 net: `feat` and `wgt` are f16 (AdaPose::feat_f16()), the output stays bf16
   const int* tile_list; const int* tile_count;      // depth-sweeping conv0 only: walk tile_list[0 .. tile_count[0]) instead of all tiles
   int tile_mask_stride;             // bytes between consecutive views' masks (0: nth * ntw)
+  int fusion;                       // fused-warp mode and the depth-sweeping conv0: FUSION_* (0 = sum)
   const unsigned char* tile_mask;   // optional [N][nth][ntw]: a workgroup whose (view, row tile, column tile) byte is 0 returns at once (its
                                     // output tile is never read: sparse decoder, see launch_decoder_tile_masks); all depth tiles share a byte
 };
@@ -243,6 +259,11 @@ int launch_projection(const double* Kc, const double* E, float* P, int n, hipStr
 // pnp.hip — the use_depth: False tail of predict (NOCS matches -> triangulation -> scale -> EPnP-RANSAC -> VVS -> world bbox)
 int launch_pnp_ransac(const float* nocs1, const float* pts1, const float* nocs2, const float* pts2, const double* K, const double* E1,
                       const double* E2, double* bbox, double* srt, int* info, int* valid, int B, int P, unsigned seed, hipStream_t s);
+
+// the real-world tail (interface_realworld.py:295-320): scale = ||s1|| in float32, then launch_pnp_ransac's steps from EPnP-RANSAC on
+// with view 1's points alone (no NOCS matching, no triangulation); info = {P, RANSAC ok, inliers, hypotheses examined}
+int launch_pnp_scaled(const float* nocs1, const float* pts1, const float* s1, const double* K, const double* E1, double* bbox, double* srt,
+                      int* info, int* valid, int B, int P, unsigned seed, hipStream_t s);
 
 int launch_mask_extent(const unsigned char* mask, int N, int H, int W, int* ext, int* count, hipStream_t s);
 

@@ -664,7 +664,8 @@ __device__ __forceinline__ Bilin bilin_setup(float ix, float iy) {
   return b;
 }
 
-template <typename T>
+// FUSE (kernels.h: FUSION_*): the voxel is ref + warped, or the real-world network's variance -2 ref warped as one fp32 product
+template <typename T, int FUSE = FUSION_SUM>
 __global__ void build_volume_kernel(const T* __restrict__ feat, const float* __restrict__ homog, const float* __restrict__ depths,
                                     T* __restrict__ vol, int v0, int Vc, int V, int B, int D, int H, int W) {
   constexpr int C = 32;
@@ -709,16 +710,26 @@ __global__ void build_volume_kernel(const T* __restrict__ feat, const float* __r
 #pragma unroll
         for (int e = 0; e < E; ++e) acc[e] += s[e] * bl.w11; }
 #pragma unroll
-      for (int e = 0; e < E; ++e) acc[e] = bl.nan ? __builtin_nanf("") : (r[e] + acc[e]);
+      for (int e = 0; e < E; ++e) acc[e] = bl.nan ? __builtin_nanf("") : FUSE == FUSION_VARIANCE ? (-2.f * r[e]) * acc[e] : (r[e] + acc[e]);
       *reinterpret_cast<uint4*>(o + cc * E) = pack_chunk(acc, T());
     }
   }
 }
 
 int launch_build_volume(int dtype, const void* feat, const float* homog, const float* depths, void* vol, int v0, int Vc, int V,
-                        int B, int D, int H, int W, hipStream_t s) {
+                        int B, int D, int H, int W, hipStream_t s, int fusion) {
   const long long total = (long long)Vc * D * H * W;
-  if (dtype == BF16)
+  RGBM_REQUIRE(fusion == FUSION_SUM || (fusion == FUSION_VARIANCE && dtype != F16), "build_volume: fusion 0 (sum) or 1 (variance; not in fp16 storage)");
+  if (fusion == FUSION_VARIANCE && dtype == BF16)
+    hipLaunchKernelGGL((build_volume_kernel<unsigned short, FUSION_VARIANCE>), dim3(grid_for(total) * 4), dim3(256), 0, s,
+                       (const unsigned short*)feat, homog, depths, (unsigned short*)vol, v0, Vc, V, B, D, H, W);
+  else if (fusion == FUSION_VARIANCE && dtype == BF16X3)
+    hipLaunchKernelGGL((build_volume_kernel<bx3_t, FUSION_VARIANCE>), dim3(grid_for(total) * 4), dim3(256), 0, s,
+                       (const bx3_t*)feat, homog, depths, (bx3_t*)vol, v0, Vc, V, B, D, H, W);
+  else if (fusion == FUSION_VARIANCE)
+    hipLaunchKernelGGL((build_volume_kernel<float, FUSION_VARIANCE>), dim3(grid_for(total) * 4), dim3(256), 0, s, (const float*)feat, homog,
+                       depths, (float*)vol, v0, Vc, V, B, D, H, W);
+  else if (dtype == BF16)
     hipLaunchKernelGGL(build_volume_kernel<unsigned short>, dim3(grid_for(total) * 4), dim3(256), 0, s,
                        (const unsigned short*)feat, homog, depths, (unsigned short*)vol, v0, Vc, V, B, D, H, W);
   else if (dtype == F16)

@@ -304,6 +304,179 @@ __device__ unsigned pn_block_count(unsigned v, unsigned* cnt) {
 
 }  // namespace
 
+// What both tails share from EPnP-RANSAC on (align.py:104-115, then the box): PnP of (nocs1 * sf, pixels of view 1) by 100 hashed five-point
+// hypotheses, OpenCV's sequential scan, the final EPnP over the inliers, VVS over all points, and the box of 2 max|nocs1| scale under
+// [R | t] in the world frame - or the default box.  S names the workgroup's shared arrays: n1, p1u / p1v and hmax filled, the rest
+// scratch.  scale is what srt reports (sf its float32 value, what multiplies the float32 NOCS); size_f32: the box size as the float32
+// product 2 max|nocs1| sf (interface_realworld.py:302-303, scale a float32 there) instead of the double one (interface_v5.py:349-350).
+// n0 goes to info[0].  Every thread of the block calls it.
+struct PnpWork {
+  float (*n1)[3];
+  double *p1u, *p1v, *wx, *wy, *wz;
+  int* l2r;                 // the inlier list of the kept hypothesis
+  double (*hyp)[12];
+  int *hcnt, *hok;
+  double* red;
+  unsigned* cnt;
+  int *s_best, *s_used, *s_nin;
+  double *s_R, *s_t;
+  const float* hmax;
+};
+
+__device__ __forceinline__ void pnp_from_scale(const PnpWork& S, int b, int P, unsigned seed, const double* __restrict__ K, double scale, float sf,
+                                               bool size_f32, int n0, const double* __restrict__ E1in, double* __restrict__ bbox,
+                                               double* __restrict__ srt, int* __restrict__ info, int* __restrict__ valid) {
+  const int t = threadIdx.x;
+  const bool have_scale = isfinite(scale);
+  // ---- PnP inputs: nocs1 (float32) * float32(scale), pixels of view 1 (align.py:105, interface_v5.py:345) ----
+  for (int p = t; p < P; p += PN_T) {
+    S.wx[p] = (double)(S.n1[p][0] * sf); S.wy[p] = (double)(S.n1[p][1] * sf); S.wz[p] = (double)(S.n1[p][2] * sf);
+  }
+  __syncthreads();
+  PnpData D;
+  D.pwx = S.wx; D.pwy = S.wy; D.pwz = S.wz; D.u = S.p1u; D.v = S.p1v; D.fu = K[0]; D.fv = K[4]; D.uc = K[2]; D.vc = K[5];
+  // ---- 100 five-point EPnP hypotheses, one per thread ----
+  if (t < PN_ITERS) {
+    int idx[PN_MODEL], have = 0;
+    for (unsigned k = 0; have < PN_MODEL; ++k) {
+      const int c = (int)(mix32(seed, (unsigned)b * 128u + (unsigned)t, k) % (unsigned)P);
+      bool dup = false;
+      for (int j = 0; j < have; ++j) dup |= idx[j] == c;
+      if (!dup) idx[have++] = c;
+    }
+    double R[9], tv[3];
+    const bool ok = have_scale && epnp(D, idx, PN_MODEL, R, tv);
+    S.hok[t] = ok ? 1 : 0;
+    for (int i = 0; i < 9; ++i) S.hyp[t][i] = ok ? R[i] : 0.0;
+    for (int i = 0; i < 3; ++i) S.hyp[t][9 + i] = ok ? tv[i] : 0.0;
+  }
+  __syncthreads();
+  auto sq_err = [&](const double* m, int p) -> double {
+    const double X = ((m[0] * S.wx[p] + m[1] * S.wy[p]) + m[2] * S.wz[p]) + m[9];
+    const double Y = ((m[3] * S.wx[p] + m[4] * S.wy[p]) + m[5] * S.wz[p]) + m[10];
+    const double Z = ((m[6] * S.wx[p] + m[7] * S.wy[p]) + m[8] * S.wz[p]) + m[11];
+    const double du = S.p1u[p] - (D.fu * X / Z + D.uc), dv = S.p1v[p] - (D.fv * Y / Z + D.vc);
+    return du * du + dv * dv;
+  };
+  for (int h = 0; h < PN_ITERS; ++h) {
+    unsigned c = 0;
+    if (S.hok[h]) for (int p = t; p < P; p += PN_T) c += sq_err(S.hyp[h], p) <= 9.0;
+    const unsigned n_in = pn_block_count(c, S.cnt);
+    if (t == 0) S.hcnt[h] = (int)n_in;
+  }
+  __syncthreads();
+  // ---- OpenCV's sequential scan (ptsetreg.cpp): a strictly better count wins and shrinks the iteration budget ----
+  if (t == 0) {
+    int best = 0, best_h = -1, niters = PN_ITERS, it = 0;
+    while (it < niters) {
+      const int h = it++;
+      if (!S.hok[h]) continue;
+      const int good = S.hcnt[h];
+      if (good > (best > PN_MODEL - 1 ? best : PN_MODEL - 1)) {
+        best = good; best_h = h;
+        const double ep = (double)(P - good) / (double)P;
+        double num = fmax(1.0 - 0.99, 2.2250738585072014e-308), den = 1.0 - pow(1.0 - ep, (double)PN_MODEL);
+        if (den < 2.2250738585072014e-308) niters = 0;
+        else {
+          num = log(num); den = log(den);
+          niters = (den >= 0 || -num >= niters * (-den)) ? niters : (int)rint(num / den);
+        }
+      }
+    }
+    *S.s_best = best_h; *S.s_used = it;
+  }
+  __syncthreads();
+  const int best_h = *S.s_best;
+  // ---- final EPnP over the inliers of the kept hypothesis (solvepnp.cpp), thread 0; inlier list reuses S.l2r ----
+  if (t == 0 && best_h >= 0) {
+    int n_in = 0;
+    for (int p = 0; p < P; ++p) if (sq_err(S.hyp[best_h], p) <= 9.0) S.l2r[n_in++] = p;
+    double R[9], tv[3];
+    const bool ok = epnp(D, S.l2r, n_in, R, tv);
+    if (!ok) *S.s_best = -1;
+    for (int i = 0; i < 9; ++i) S.s_R[i] = R[i];
+    for (int i = 0; i < 3; ++i) S.s_t[i] = tv[i];
+    *S.s_nin = n_in;
+  }
+  __syncthreads();
+  const bool ransac_ok = *S.s_best >= 0;
+  // ---- cv2.solvePnPRefineVVS over ALL points: Gauss-Newton on SE(3), lambda 1, <= 20 iterations, 1e-6 on the residual change ----
+  double prev = 1e300;
+  for (int iter = 0; ransac_ok && iter < 20; ++iter) {
+    double acc[27];
+    for (int i = 0; i < 27; ++i) acc[i] = 0.0;
+    double e2 = 0.0;
+    for (int p = t; p < P; p += PN_T) {
+      const double X = ((S.s_R[0] * S.wx[p] + S.s_R[1] * S.wy[p]) + S.s_R[2] * S.wz[p]) + S.s_t[0];
+      const double Y = ((S.s_R[3] * S.wx[p] + S.s_R[4] * S.wy[p]) + S.s_R[5] * S.wz[p]) + S.s_t[1];
+      const double Z = ((S.s_R[6] * S.wx[p] + S.s_R[7] * S.wy[p]) + S.s_R[8] * S.wz[p]) + S.s_t[2];
+      const double x = X / Z, y = Y / Z;
+      const double ex = x - (S.p1u[p] - D.uc) / D.fu, ey = y - (S.p1v[p] - D.vc) / D.fv;
+      e2 += ex * ex + ey * ey;
+      const double Lx[6] = {-1 / Z, 0.0, x / Z, x * y, -(1 + x * x), y}, Ly[6] = {0.0, -1 / Z, y / Z, 1 + y * y, -x * y, -x};
+      int k = 0;
+      for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) acc[k++] += Lx[a] * Lx[c] + Ly[a] * Ly[c];      // L^T L (21)
+      for (int a = 0; a < 6; ++a) acc[21 + a] += Lx[a] * ex + Ly[a] * ey;                                     // L^T e (6)
+    }
+    double sum[27];
+    for (int i = 0; i < 27; ++i) sum[i] = block_sum<PN_T>(acc[i], S.red);
+    const double err = sqrt(block_sum<PN_T>(e2, S.red) / P);
+    if (fabs(err - prev) < 1e-6) break;                    // every thread sees the same sums: uniform exit
+    prev = err;
+    if (t == 0) {
+      double A[36], g[6], dq[6];
+      int k = 0;
+      for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) { A[a * 6 + c] = sum[k]; A[c * 6 + a] = sum[k]; ++k; }
+      for (int a = 0; a < 6; ++a) g[a] = sum[21 + a];
+      const bool ok = ls_solve(A, g, 6, 6, dq);              // pinv(L) e = (L^T L)^-1 L^T e for a full-rank L
+      if (ok) {
+        for (int a = 0; a < 6; ++a) dq[a] = -dq[a];
+        const double w[3] = {dq[3], dq[4], dq[5]};
+        const double th = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+        double Rw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Vm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        if (th >= 1e-12) {
+          const double kx = w[0] / th, ky = w[1] / th, kz = w[2] / th;
+          const double Kx[9] = {0, -kz, ky, kz, 0, -kx, -ky, kx, 0};
+          double K2[9];
+          for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) K2[i * 3 + j] = Kx[i * 3] * Kx[j] + Kx[i * 3 + 1] * Kx[3 + j] + Kx[i * 3 + 2] * Kx[6 + j];
+          const double sn = sin(th), cs = cos(th);
+          for (int i = 0; i < 9; ++i) {
+            Rw[i] = (i % 4 == 0 ? 1.0 : 0.0) + sn * Kx[i] + (1 - cs) * K2[i];
+            Vm[i] = (i % 4 == 0 ? 1.0 : 0.0) + (1 - cs) / th * Kx[i] + (1 - sn / th) * K2[i];
+          }
+        }
+        double dt[3], Rn[9], tn[3];
+        for (int i = 0; i < 3; ++i) dt[i] = Vm[i * 3] * dq[0] + Vm[i * 3 + 1] * dq[1] + Vm[i * 3 + 2] * dq[2];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = Rw[0 * 3 + i] * S.s_R[0 * 3 + j] + Rw[1 * 3 + i] * S.s_R[1 * 3 + j] + Rw[2 * 3 + i] * S.s_R[2 * 3 + j];
+        for (int i = 0; i < 3; ++i) tn[i] = Rw[0 * 3 + i] * (S.s_t[0] - dt[0]) + Rw[1 * 3 + i] * (S.s_t[1] - dt[1]) + Rw[2 * 3 + i] * (S.s_t[2] - dt[2]);
+        for (int i = 0; i < 9; ++i) S.s_R[i] = Rn[i];
+        for (int i = 0; i < 3; ++i) S.s_t[i] = tn[i];
+      }
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    // a NaN pixel of view 1 leaves RANSAC standing (the point is no inlier) but reaches the refined pose through the residual: like
+    // every other failure that is the default box AND the identity in srt, not a box refused below with half a pose reported here
+    bool pose_finite = true;
+    for (int i = 0; i < 9; ++i) pose_finite = pose_finite && isfinite(S.s_R[i]);
+    for (int i = 0; i < 3; ++i) pose_finite = pose_finite && isfinite(S.s_t[i]);
+    const bool ok = have_scale && ransac_ok && pose_finite;
+    double* o = srt + (long long)b * 13;
+    o[0] = scale;
+    for (int i = 0; i < 9; ++i) o[1 + i] = ok ? S.s_R[i] : (i % 4 == 0 ? 1.0 : 0.0);
+    for (int i = 0; i < 3; ++i) o[10 + i] = ok ? S.s_t[i] : 0.0;
+    int* io = info + (long long)b * 4;
+    io[0] = n0; io[1] = ransac_ok ? 1 : 0; io[2] = ransac_ok ? *S.s_nin : 0; io[3] = *S.s_used;
+    double Rf[9];
+    for (int i = 0; i < 9; ++i) Rf[i] = (double)(float)S.s_R[i];
+    const float tf[3] = {(float)S.s_t[0], (float)S.s_t[1], (float)S.s_t[2]};
+    double size[3];
+    for (int i = 0; i < 3; ++i) size[i] = size_f32 ? (double)((2.f * S.hmax[i]) * sf) : 2.0 * (double)S.hmax[i] * scale;
+    emit_bbox_world(b, Rf, tf, size, ok, E1in, bbox, valid);
+  }
+}
+
 __global__ __launch_bounds__(PN_T) void pnp_ransac_kernel(
     const float* __restrict__ nocs1 /*[B,P,3]*/, const float* __restrict__ pts1 /*[B,P,2]*/, const float* __restrict__ nocs2,
     const float* __restrict__ pts2, const double* __restrict__ Kin /*[B,9]*/, const double* __restrict__ E1in /*[B,16]*/,
@@ -473,154 +646,52 @@ __global__ __launch_bounds__(PN_T) void pnp_ransac_kernel(
   }
   if (t == 0) s_scale = scale;
   __syncthreads();
-  const bool have_scale = isfinite(scale);
-  // ---- PnP inputs: nocs1 (float32) * float32(scale), pixels of view 1 (align.py:105, interface_v5.py:345) ----
+  const PnpWork S = {n1, p1u, p1v, wx, wy, wz, l2r, hyp, hcnt, hok, red, &cnt_s, &s_best, &s_used, &r2l[0], s_R, s_t, hmax};
+  pnp_from_scale(S, b, P, seed, K, scale, (float)scale, false, nm, E1in, bbox, srt, info, valid);
+}
+
+// The real-world tail (interface_realworld.py:295-320): the scale is the norm of the regressed size, ts = ||view1_s|| as np.linalg.norm of a
+// float32 vector gives it (float32), and everything else is pnp_from_scale on view 1's points - no NOCS matching, no triangulation.  The
+// reference has no `success` check on this path (it would use whatever cv2 left in r, t); here no consensus or a non-finite result is the
+// default box and valid = 0, as in the tail above.
+__global__ __launch_bounds__(PN_T) void pnp_scaled_kernel(
+    const float* __restrict__ nocs1 /*[B,P,3]*/, const float* __restrict__ pts1 /*[B,P,2]*/, const float* __restrict__ s1 /*[B,3]*/,
+    const double* __restrict__ Kin /*[B,9]*/, const double* __restrict__ E1in /*[B,16]*/, double* __restrict__ bbox /*[B,8,3]*/,
+    double* __restrict__ srt /*[B,13]: scale, R(9), t(3)*/, int* __restrict__ info /*[B,4]: P, ransac ok, inliers, hypotheses looked at*/,
+    int* __restrict__ valid, int P, unsigned seed) {
+  __shared__ float n1[PN_P][3];
+  __shared__ double p1u[PN_P], p1v[PN_P];
+  __shared__ double wx[PN_P], wy[PN_P], wz[PN_P];            // nocs1 * scale
+  __shared__ int inl[PN_P];
+  __shared__ double hyp[PN_ITERS][12];
+  __shared__ int hcnt[PN_ITERS], hok[PN_ITERS];
+  __shared__ double red[PN_T];
+  __shared__ unsigned cnt_s;
+  __shared__ int s_best, s_used, s_nin;
+  __shared__ double s_R[9], s_t[3];
+  __shared__ float hmax[3];
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (t == 0) { hmax[0] = hmax[1] = hmax[2] = 0.f; s_best = -1; s_used = 0; s_nin = 0; }
+  __syncthreads();
   for (int p = t; p < P; p += PN_T) {
-    const float sf = (float)scale;
-    wx[p] = (double)(n1[p][0] * sf); wy[p] = (double)(n1[p][1] * sf); wz[p] = (double)(n1[p][2] * sf);
+    for (int k = 0; k < 3; ++k) n1[p][k] = nocs1[((long long)b * P + p) * 3 + k];
+    p1u[p] = (double)pts1[((long long)b * P + p) * 2]; p1v[p] = (double)pts1[((long long)b * P + p) * 2 + 1];
+    for (int k = 0; k < 3; ++k) atomicMax((int*)&hmax[k], __float_as_int(fabsf(n1[p][k])));
   }
   __syncthreads();
-  PnpData D;
-  D.pwx = wx; D.pwy = wy; D.pwz = wz; D.u = p1u; D.v = p1v; D.fu = K[0]; D.fv = K[4]; D.uc = K[2]; D.vc = K[5];
-  // ---- 100 five-point EPnP hypotheses, one per thread ----
-  if (t < PN_ITERS) {
-    int idx[PN_MODEL], have = 0;
-    for (unsigned k = 0; have < PN_MODEL; ++k) {
-      const int c = (int)(mix32(seed, (unsigned)b * 128u + (unsigned)t, k) % (unsigned)P);
-      bool dup = false;
-      for (int j = 0; j < have; ++j) dup |= idx[j] == c;
-      if (!dup) idx[have++] = c;
-    }
-    double R[9], tv[3];
-    const bool ok = have_scale && epnp(D, idx, PN_MODEL, R, tv);
-    hok[t] = ok ? 1 : 0;
-    for (int i = 0; i < 9; ++i) hyp[t][i] = ok ? R[i] : 0.0;
-    for (int i = 0; i < 3; ++i) hyp[t][9 + i] = ok ? tv[i] : 0.0;
-  }
-  __syncthreads();
-  auto sq_err = [&](const double* m, int p) -> double {
-    const double X = ((m[0] * wx[p] + m[1] * wy[p]) + m[2] * wz[p]) + m[9];
-    const double Y = ((m[3] * wx[p] + m[4] * wy[p]) + m[5] * wz[p]) + m[10];
-    const double Z = ((m[6] * wx[p] + m[7] * wy[p]) + m[8] * wz[p]) + m[11];
-    const double du = p1u[p] - (D.fu * X / Z + D.uc), dv = p1v[p] - (D.fv * Y / Z + D.vc);
-    return du * du + dv * dv;
-  };
-  for (int h = 0; h < PN_ITERS; ++h) {
-    unsigned c = 0;
-    if (hok[h]) for (int p = t; p < P; p += PN_T) c += sq_err(hyp[h], p) <= 9.0;
-    const unsigned n_in = pn_block_count(c, &cnt_s);
-    if (t == 0) hcnt[h] = (int)n_in;
-  }
-  __syncthreads();
-  // ---- OpenCV's sequential scan (ptsetreg.cpp): a strictly better count wins and shrinks the iteration budget ----
-  if (t == 0) {
-    int best = 0, best_h = -1, niters = PN_ITERS, it = 0;
-    while (it < niters) {
-      const int h = it++;
-      if (!hok[h]) continue;
-      const int good = hcnt[h];
-      if (good > (best > PN_MODEL - 1 ? best : PN_MODEL - 1)) {
-        best = good; best_h = h;
-        const double ep = (double)(P - good) / (double)P;
-        double num = fmax(1.0 - 0.99, 2.2250738585072014e-308), den = 1.0 - pow(1.0 - ep, (double)PN_MODEL);
-        if (den < 2.2250738585072014e-308) niters = 0;
-        else {
-          num = log(num); den = log(den);
-          niters = (den >= 0 || -num >= niters * (-den)) ? niters : (int)rint(num / den);
-        }
-      }
-    }
-    s_best = best_h; s_used = it;
-  }
-  __syncthreads();
-  const int best_h = s_best;
-  // ---- final EPnP over the inliers of the kept hypothesis (solvepnp.cpp), thread 0; inlier list reuses l2r ----
-  if (t == 0 && best_h >= 0) {
-    int n_in = 0;
-    for (int p = 0; p < P; ++p) if (sq_err(hyp[best_h], p) <= 9.0) l2r[n_in++] = p;
-    double R[9], tv[3];
-    const bool ok = epnp(D, l2r, n_in, R, tv);
-    if (!ok) s_best = -1;
-    for (int i = 0; i < 9; ++i) s_R[i] = R[i];
-    for (int i = 0; i < 3; ++i) s_t[i] = tv[i];
-    r2l[0] = n_in;
-  }
-  __syncthreads();
-  const bool ransac_ok = s_best >= 0;
-  // ---- cv2.solvePnPRefineVVS over ALL points: Gauss-Newton on SE(3), lambda 1, <= 20 iterations, 1e-6 on the residual change ----
-  double prev = 1e300;
-  for (int iter = 0; ransac_ok && iter < 20; ++iter) {
-    double acc[27];
-    for (int i = 0; i < 27; ++i) acc[i] = 0.0;
-    double e2 = 0.0;
-    for (int p = t; p < P; p += PN_T) {
-      const double X = ((s_R[0] * wx[p] + s_R[1] * wy[p]) + s_R[2] * wz[p]) + s_t[0];
-      const double Y = ((s_R[3] * wx[p] + s_R[4] * wy[p]) + s_R[5] * wz[p]) + s_t[1];
-      const double Z = ((s_R[6] * wx[p] + s_R[7] * wy[p]) + s_R[8] * wz[p]) + s_t[2];
-      const double x = X / Z, y = Y / Z;
-      const double ex = x - (p1u[p] - D.uc) / D.fu, ey = y - (p1v[p] - D.vc) / D.fv;
-      e2 += ex * ex + ey * ey;
-      const double Lx[6] = {-1 / Z, 0.0, x / Z, x * y, -(1 + x * x), y}, Ly[6] = {0.0, -1 / Z, y / Z, 1 + y * y, -x * y, -x};
-      int k = 0;
-      for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) acc[k++] += Lx[a] * Lx[c] + Ly[a] * Ly[c];      // L^T L (21)
-      for (int a = 0; a < 6; ++a) acc[21 + a] += Lx[a] * ex + Ly[a] * ey;                                     // L^T e (6)
-    }
-    double sum[27];
-    for (int i = 0; i < 27; ++i) sum[i] = block_sum<PN_T>(acc[i], red);
-    const double err = sqrt(block_sum<PN_T>(e2, red) / P);
-    if (fabs(err - prev) < 1e-6) break;                    // every thread sees the same sums: uniform exit
-    prev = err;
-    if (t == 0) {
-      double A[36], g[6], dq[6];
-      int k = 0;
-      for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) { A[a * 6 + c] = sum[k]; A[c * 6 + a] = sum[k]; ++k; }
-      for (int a = 0; a < 6; ++a) g[a] = sum[21 + a];
-      const bool ok = ls_solve(A, g, 6, 6, dq);              // pinv(L) e = (L^T L)^-1 L^T e for a full-rank L
-      if (ok) {
-        for (int a = 0; a < 6; ++a) dq[a] = -dq[a];
-        const double w[3] = {dq[3], dq[4], dq[5]};
-        const double th = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
-        double Rw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Vm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        if (th >= 1e-12) {
-          const double kx = w[0] / th, ky = w[1] / th, kz = w[2] / th;
-          const double Kx[9] = {0, -kz, ky, kz, 0, -kx, -ky, kx, 0};
-          double K2[9];
-          for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) K2[i * 3 + j] = Kx[i * 3] * Kx[j] + Kx[i * 3 + 1] * Kx[3 + j] + Kx[i * 3 + 2] * Kx[6 + j];
-          const double sn = sin(th), cs = cos(th);
-          for (int i = 0; i < 9; ++i) {
-            Rw[i] = (i % 4 == 0 ? 1.0 : 0.0) + sn * Kx[i] + (1 - cs) * K2[i];
-            Vm[i] = (i % 4 == 0 ? 1.0 : 0.0) + (1 - cs) / th * Kx[i] + (1 - sn / th) * K2[i];
-          }
-        }
-        double dt[3], Rn[9], tn[3];
-        for (int i = 0; i < 3; ++i) dt[i] = Vm[i * 3] * dq[0] + Vm[i * 3 + 1] * dq[1] + Vm[i * 3 + 2] * dq[2];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = Rw[0 * 3 + i] * s_R[0 * 3 + j] + Rw[1 * 3 + i] * s_R[1 * 3 + j] + Rw[2 * 3 + i] * s_R[2 * 3 + j];
-        for (int i = 0; i < 3; ++i) tn[i] = Rw[0 * 3 + i] * (s_t[0] - dt[0]) + Rw[1 * 3 + i] * (s_t[1] - dt[1]) + Rw[2 * 3 + i] * (s_t[2] - dt[2]);
-        for (int i = 0; i < 9; ++i) s_R[i] = Rn[i];
-        for (int i = 0; i < 3; ++i) s_t[i] = tn[i];
-      }
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    // a NaN pixel of view 1 leaves RANSAC standing (the point is no inlier) but reaches the refined pose through the residual: like
-    // every other failure that is the default box AND the identity in srt, not a box refused below with half a pose reported here
-    bool pose_finite = true;
-    for (int i = 0; i < 9; ++i) pose_finite = pose_finite && isfinite(s_R[i]);
-    for (int i = 0; i < 3; ++i) pose_finite = pose_finite && isfinite(s_t[i]);
-    const bool ok = have_scale && ransac_ok && pose_finite;
-    double* o = srt + (long long)b * 13;
-    o[0] = scale;
-    for (int i = 0; i < 9; ++i) o[1 + i] = ok ? s_R[i] : (i % 4 == 0 ? 1.0 : 0.0);
-    for (int i = 0; i < 3; ++i) o[10 + i] = ok ? s_t[i] : 0.0;
-    int* io = info + (long long)b * 4;
-    io[0] = nm; io[1] = ransac_ok ? 1 : 0; io[2] = ransac_ok ? r2l[0] : 0; io[3] = s_used;
-    double Rf[9];
-    for (int i = 0; i < 9; ++i) Rf[i] = (double)(float)s_R[i];
-    const float tf[3] = {(float)s_t[0], (float)s_t[1], (float)s_t[2]};
-    const double size[3] = {2.0 * (double)hmax[0] * scale, 2.0 * (double)hmax[1] * scale, 2.0 * (double)hmax[2] * scale};
-    emit_bbox_world(b, Rf, tf, size, ok, E1in, bbox, valid);
-  }
+  const float* sv = s1 + (long long)b * 3;
+  const float sf = sqrtf((sv[0] * sv[0] + sv[1] * sv[1]) + sv[2] * sv[2]);
+  const PnpWork S = {n1, p1u, p1v, wx, wy, wz, inl, hyp, hcnt, hok, red, &cnt_s, &s_best, &s_used, &s_nin, s_R, s_t, hmax};
+  pnp_from_scale(S, b, P, seed, Kin + (long long)b * 9, (double)sf, sf, true, P, E1in, bbox, srt, info, valid);
+}
+
+int launch_pnp_scaled(const float* nocs1, const float* pts1, const float* s1, const double* K, const double* E1, double* bbox, double* srt,
+                      int* info, int* valid, int B, int P, unsigned seed, hipStream_t s) {
+  RGBM_REQUIRE(nocs1 && pts1 && s1 && K && E1 && bbox && srt && info && valid, "pnp_scaled arguments");
+  RGBM_REQUIRE(B > 0 && P >= PN_MODEL && P <= PN_P, "pnp_scaled needs 5 <= P <= 1024");
+  hipLaunchKernelGGL(pnp_scaled_kernel, dim3(B), dim3(PN_T), 0, s, nocs1, pts1, s1, K, E1, bbox, srt, info, valid, P, seed);
+  RGBM_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 int launch_pnp_ransac(const float* nocs1, const float* pts1, const float* nocs2, const float* pts2, const double* K, const double* E1,

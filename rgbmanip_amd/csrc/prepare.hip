@@ -423,6 +423,23 @@ int launch_prepare_inputs_windows(const void* pix, int pixel_type, int normalize
   return 0;
 }
 
+// The chosen points' pixel coordinates as the real-world network reads them (interface_realworld.py:264-269): x / W, y / H.  A true
+// IEEE float32 division: 640 and 480 are no powers of two, so a multiply by the reciprocal rounds differently.
+__global__ void pts2d_to_coor_kernel(const float* __restrict__ pts2d, float* __restrict__ coor, long long n, float W, float H) {
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float2 p = *reinterpret_cast<const float2*>(pts2d + 2 * i);
+  *reinterpret_cast<float2*>(coor + 2 * i) = make_float2(__fdiv_rn(p.x, W), __fdiv_rn(p.y, H));
+}
+
+int launch_pts2d_to_coor(const float* pts2d, float* coor, long long n, int W, int H, hipStream_t s) {
+  RGBM_REQUIRE(pts2d && coor && n > 0 && W > 0 && H > 0, "pts2d_to_coor arguments");
+  RGBM_REQUIRE((n + 255) / 256 < (1ll << 31), "pts2d_to_coor grid out of range");
+  hipLaunchKernelGGL(pts2d_to_coor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts2d, coor, n, (float)W, (float)H);
+  RGBM_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int launch_quantize_frames(const float* src, unsigned char* dst, size_t n, hipStream_t s) {
   RGBM_REQUIRE(src && dst && n > 0, "quantize_frames arguments");
   RGBM_REQUIRE(reinterpret_cast<uintptr_t>(src) % 4 == 0, "quantize_frames: src must be 4-byte aligned");

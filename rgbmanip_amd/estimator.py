@@ -28,7 +28,8 @@ import torch
 
 from . import _lib, host_prepare
 from . import samples as samples_mod
-from .adapose import AdaPoseNet, postprocess, postprocess_pnp, postprocess_ransac, postprocess_regressed, prepare_inputs, prepare_inputs_windows
+from .adapose import (AdaPoseNet, postprocess, postprocess_pnp, postprocess_pnp_scaled, postprocess_ransac, postprocess_regressed, prepare_inputs,
+                      prepare_inputs_windows, pts2d_to_coor)
 from .cloud import (DEFAULT_BBOX, cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity, depth_consistency, depth_fusion,
                     depth_to_points)
 from .feature_cache import CachedViews, ContentFeatureCache, SlotFeatureCache
@@ -696,11 +697,15 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         depths = self._consts(E1.device)[1][None].expand(n, 24).contiguous()
         if cached is not None:
             return self.estimator.forward_cached(cached.pool, cached.slot1, cached.slot2, a["choose"], b["choose"], P1, P2, depths)
-        pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], P1, P2, depths, **want.network_kw)
+        pred = self.estimator(a["img"], a["choose"], b["img"], b["choose"], P1, P2, depths, **want.network_kw, **self._network_inputs(a, b))
         self._plain_views += 2 * n
         if want.maps:
             self._content.bypassed += int(self.feature_cache)      # a call / chunk the cache was set for and did not serve
         return pred
+
+    def _network_inputs(self, a, b) -> dict:
+        """What the network reads of the prepared views beyond crops, chosen pixels and projections (the real-world interface: coordinates)."""
+        return {}
 
     def _estimate_prepared(self, a, b, E1, E2, K=None, cached: CachedViews | None = None, *, want: ResultPlan):
         dev = self.estimator.device
@@ -935,3 +940,93 @@ class AdaPoseEstimator_baseline(AdaPoseEstimator_v5):
 
     def estimate_cloud_views_device(self, *a, **k):
         self._no_cost_volume("estimate_cloud_views_device")
+
+
+class AdaPoseEstimator_realworld(AdaPoseEstimator_v5):
+    """`pose_estimator.name: adapose_realworld` (`interface_realworld.py`, whose `prepare_model_input` / `estimate` are `interface_v5.py`'s):
+    `StereoPoseNet_with_depth_for_realdemo` - v5 on a variance cost volume with the pose rows read from camera points (DESIGN.md section
+    5r) - and the PnP tail with the regressed size (`interface_realworld.py:295-320`, csrc/pnp.hip: pnp_scaled_kernel), which reads
+    view 1's NOCS and size only: `hip_view2_heads` defaults to False whatever `direct_regression` / `use_depth` say (the tail has no
+    such branches).  Crop, upload, 8-bit frames, windows and `hip_dtype` (not fp16) / `hip_upload` / `hip_options` are the code above.
+    One deliberate difference from the shipped interface: its line 287 calls the network with seven arguments where `forward` takes nine
+    and never passes the coordinates it computes at :264-269 (`predict` raises TypeError as shipped); this class passes them.  What is
+    not implemented for this network raises, naming the key."""
+
+    _UNSUPPORTED = ("hip_feature_cache", "hip_dropout", "hip_as_shipped", "hip_graph")
+
+    def __init__(self, env, cfg, logger, state_dict=None, dtype=None, device=0, net=None):
+        for key in self._UNSUPPORTED:
+            if cfg.get(key, False):
+                raise ValueError(f"AdaPoseEstimator_realworld: cfg key {key} is not implemented for the real-world network")
+        if cfg.get("hip_norm_mode", "eval") not in ("eval", 0):
+            raise ValueError("AdaPoseEstimator_realworld: cfg key hip_norm_mode: per-sample BatchNorm3d is not implemented for the real-world network")
+        if cfg.get("hip_prepare", "device") != "device":
+            raise ValueError('AdaPoseEstimator_realworld: cfg key hip_prepare: only "device" is implemented for the real-world network')
+        if (dtype or cfg.get("hip_dtype", "bf16x3")) in ("fp16", "f16", "float16"):
+            raise ValueError("AdaPoseEstimator_realworld: cfg key hip_dtype: fp16 is not implemented for the real-world network (a voxel of its "
+                             "variance volume is a product of two feature values; f16 saturates at 65504): use bf16x3, bf16 or fp32")
+        if net is not None and getattr(net, "arch", "v5") != "realworld":
+            raise ValueError("AdaPoseEstimator_realworld: the shared net must be an AdaPoseNet(arch='realworld')")
+        super().__init__(env, cfg, logger, state_dict=state_dict, dtype=dtype, device=device, net=net)
+
+    def _synthetic_state_dict(self):
+        from . import synth
+        return synth.realworld_state_dict(seed=0)
+
+    def _build_net(self, state_dict, device, norm_mode, drop_p, drop_seed, options):
+        return AdaPoseNet(state_dict, dtype=self.dtype, device=device, options=options, arch="realworld")
+
+    def _pnp_branch(self):
+        """No `direct_regression` / `use_depth` branches here: the one tail reads view 1 alone (the view-2 heads are not needed)."""
+        return False
+
+    # the pixels of the chosen points are always wanted: the network reads them normalised, the tail as they are
+    def _prepare(self, rgb, *args, **kw):
+        out = super()._prepare(rgb, *args, **{**kw, "want_pts2d": True})
+        out["coor"] = pts2d_to_coor(out["pts2d"], W=int(rgb.shape[2]), H=int(rgb.shape[1]))
+        return out
+
+    def _prepare_windows(self, d, v, K, *args, **kw):
+        out = super()._prepare_windows(d, v, K, *args, **{**kw, "want_pts2d": True})
+        out["coor"] = pts2d_to_coor(out["pts2d"], W=int(d.W), H=int(d.H))
+        return out
+
+    def _network_inputs(self, a, b) -> dict:
+        return {"coor1": a["coor"], "coor2": b["coor"]}
+
+    def _bbox_tail(self, pred, choose, Kcrop, E1, pts2d=None, E2=None, K=None):
+        """interface_realworld.py:295-320: ts = ||view1_s||, EPnP-RANSAC + VVS on (nocs1 ts, pixels of view 1, the ORIGINAL intrinsics)."""
+        return postprocess_pnp_scaled(pred["view1_nocs"], pts2d[0], pred["view1_s"], K, E1, seed=int(self.cfg.get("hip_ransac_seed", 0)))[0]
+
+    def _refused(self, name, why):
+        raise NotImplementedError(f"AdaPoseEstimator_realworld.{name}: {why} is not implemented for the real-world network")
+
+    def estimate_samples(self, *a, **k):
+        self._refused("estimate_samples", "Dropout2d (cfg hip_dropout / hip_as_shipped), so there is nothing to sample,")
+
+    def estimate_samples_device(self, *a, **k):
+        self._refused("estimate_samples_device", "Dropout2d (cfg hip_dropout / hip_as_shipped), so there is nothing to sample,")
+
+    def estimate_depth(self, *a, **k):
+        self._refused("estimate_depth", "the dense forward")
+
+    def estimate_depth_device(self, *a, **k):
+        self._refused("estimate_depth_device", "the dense forward")
+
+    def estimate_cloud(self, *a, **k):
+        self._refused("estimate_cloud", "the dense forward")
+
+    def estimate_cloud_device(self, *a, **k):
+        self._refused("estimate_cloud_device", "the dense forward")
+
+    def estimate_cloud_pose(self, *a, **k):
+        self._refused("estimate_cloud_pose", "the dense forward")
+
+    def estimate_cloud_pose_device(self, *a, **k):
+        self._refused("estimate_cloud_pose_device", "the dense forward")
+
+    def estimate_cloud_views(self, *a, **k):
+        self._refused("estimate_cloud_views", "the dense forward")
+
+    def estimate_cloud_views_device(self, *a, **k):
+        self._refused("estimate_cloud_views_device", "the dense forward")

@@ -132,6 +132,40 @@ def baseline_state_dict(seed: int = 0, regress_pose: bool = True, prefix: str = 
     return _draw_state_dict(baseline_schema(regress_pose), seed, prefix)
 
 
+def realworld_schema():
+    """(name, shape, kind) of StereoPoseNet_with_depth_for_realdemo (lib/network_realworld.py:10-96) in its state_dict order: v5's
+    entries with camera_pts_mlp in front of nocs_pts_mlp and pose_mlp1.0 reading 128 channels."""
+    s = []
+    for name, shape, kind in adapose_schema():
+        if name == "nocs_pts_mlp.0.weight":
+            for i, (a, b) in zip((0, 2), ((3, 32), (32, 64))):
+                s.append((f"camera_pts_mlp.{i}.weight", (b, a, 1), "w"))
+                s.append((f"camera_pts_mlp.{i}.bias", (b,), "b:%d" % a))
+        if name == "pose_mlp1.0.weight":
+            shape = (128, 128, 1)
+        s.append((name, shape, kind))
+    return s
+
+
+def realworld_state_dict(seed: int = 0, prefix: str = "") -> "OrderedDict[str, np.ndarray]":
+    """Synthetic checkpoint of the real-world network.  The generator is keyed by the tensor's name, so every tensor it shares with
+    `adapose_state_dict(seed)` - all of v5's but pose_mlp1.0.weight, which is [128, 128, 1] here - is the same draw, and
+    `adapose_state_dict` returns what it did."""
+    return _draw_state_dict(realworld_schema(), seed, prefix)
+
+
+def realworld_coor(B: int, seed: int = 0, n_pts: int = N_PTS, W: int = 640, H: int = 480):
+    """Chosen points' pixel coordinates in a W x H frame for the real-world network's goldens: (pts2d1, pts2d2) [B, n_pts, 2] float32
+    with whole-pixel values (what prepare_model_input emits), and the normalised (coor1, coor2) = pts2d / (W, H) in float32."""
+    g = _rng(f"realworld_coor.{B}.{n_pts}", seed)
+    out = []
+    for _ in range(2):
+        p = np.stack([g.integers(0, W, size=(B, n_pts)), g.integers(0, H, size=(B, n_pts))], axis=-1).astype(np.float32)
+        out.append(p)
+    wh = np.array([W, H], dtype=np.float32)
+    return out[0], out[1], out[0] / wh, out[1] / wh
+
+
 def view_fusion_inputs(B: int, P: int, seed: int = 0):
     """Rows for the attention stack alone: (x1, x2) [B, P, 32] float32, N(0, 1)."""
     g = _rng(f"view_fusion_inputs.{B}.{P}", seed)

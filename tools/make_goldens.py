@@ -233,6 +233,72 @@ def gen_adapose_baseline(out_dir):
     np.savez_compressed(os.path.join(out_dir, "view_fusion_small.npz"), **small)
 
 
+def gen_adapose_realworld(out_dir):
+    """The real-world network (lib/network_realworld.py) on the golden batch.  Data only: the ten outputs, the seeded point coordinates,
+    strided slices and statistics of both variance volumes, of conv0's output and of the 128-channel pose rows, the share of voxels whose
+    warp falls outside the partner image, and the class's state-dict keys and shapes.  The shipped interface_realworld.py:287 calls the
+    network without the coordinates it computes at :264-269 (a TypeError); the network itself is sound and is called here with them."""
+    from models.pose_estimator.AdaPose.lib.network_realworld import StereoPoseNet_with_depth_for_realdemo
+    from rgbmanip_amd import synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import realworld_ref as rr
+
+    net = StereoPoseNet_with_depth_for_realdemo(n_cat=1, nv_pts=1024, regress_pose=True).eval()
+    sd = synth.realworld_state_dict(seed=0)
+    print("load_state_dict:", net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True))
+    B = 2
+    inp = synth.adapose_inputs(B, seed=0)
+    pts1, pts2, coor1, coor2 = synth.realworld_coor(B, seed=0)
+    tin = {k: torch.from_numpy(v) for k, v in inp.items()}
+    vols, c0s, rows = [], [], []
+    hs = [net.cost_regularization.register_forward_pre_hook(lambda mod, i: vols.append(i[0].detach())),
+          net.cost_regularization.conv0.register_forward_hook(lambda mod, i, o: c0s.append(o.detach())),
+          net.pose_mlp1.register_forward_pre_hook(lambda mod, i: rows.append(i[0].detach()))]
+    args = (tin["img1"], tin["choose1"], torch.from_numpy(coor1), tin["img2"], tin["choose2"], torch.from_numpy(coor2), tin["P1"], tin["P2"],
+            tin["depths"])
+    with torch.no_grad():
+        out = net(*args)
+        save = {k: v.numpy() for k, v in out.items()}
+        for v in (1, 2):      # view 1's volume, c0 and rows come first in the forward
+            vol, c0, row = vols[v - 1], c0s[v - 1], rows[v - 1]
+            save[f"v{v}_vol_slice"] = rr.vol_slice(vol).contiguous().numpy()
+            save[f"v{v}_vol_absmean"] = np.array(vol.abs().mean().item(), dtype=np.float64)
+            save[f"v{v}_vol_absmax"] = np.array(vol.abs().max().item(), dtype=np.float64)
+            save[f"v{v}_c0_slice"] = rr.c0_slice(c0).contiguous().numpy()
+            save[f"v{v}_c0_absmean"] = np.array(c0.abs().mean().item(), dtype=np.float64)
+            save[f"v{v}_rows_slice"] = rr.rows_slice(row.transpose(1, 2)).contiguous().numpy()      # [B, P / 16, 128], point-major
+            save[f"v{v}_rows_absmean"] = np.array(row.abs().mean().item(), dtype=np.float64)
+        del vols[:], c0s[:], rows[:]
+        out2 = net(*args)
+        for h in hs:
+            h.remove()
+        for k in out:
+            assert torch.equal(out[k], out2[k]), k
+        # where the warp leaves the partner image (all four bilinear corners outside): per view, from the restatement's float32 grid
+        feat = {1: net.img_extractor(tin["img1"]), 2: net.img_extractor(tin["img2"])}
+        for v in (1, 2):
+            o = 3 - v
+            _, outside = rr.homo_warping(feat[o], tin[f"P{o}"], tin[f"P{v}"], tin["depths"], want_outside=True)
+            save[f"v{v}_outside_share"] = np.array(outside.double().mean().item(), dtype=np.float64)
+            save[f"v{v}_outside_share_slice"] = np.array(outside[:, ::3, 3::17, 5::17].double().mean().item(), dtype=np.float64)
+            print(f"view {v}: outside share {float(save[f'v{v}_outside_share']):.4f} (in the slice {float(save[f'v{v}_outside_share_slice']):.4f}), "
+                  f"|vol| max {float(save[f'v{v}_vol_absmax']):.1f} mean {float(save[f'v{v}_vol_absmean']):.2f}")
+            # the fixture conditions tests/test_realworld_host.py asserts: if the rig misses one, add a second seeded rig, do not loosen them
+            assert 0.05 <= save[f"v{v}_outside_share"] <= 0.95 and 0.05 <= save[f"v{v}_outside_share_slice"] <= 0.95, "degenerate rig"
+            assert save[f"v{v}_vol_absmax"] >= 10 * save[f"v{v}_vol_absmean"]
+    save["pts2d1"], save["pts2d2"] = pts1, pts2
+    save["coor1"], save["coor2"] = coor1, coor2
+    save["frame_wh"] = np.array([rr.FRAME_W, rr.FRAME_H], dtype=np.int64)
+    ref_sd = net.state_dict()
+    save["sd_keys"] = np.array(list(ref_sd.keys()))
+    save["sd_shapes"] = np.array(["x".join(str(d) for d in v.shape) for v in ref_sd.values()])
+    path = os.path.join(out_dir, "adapose_realworld_b2.npz")
+    np.savez_compressed(path, **save)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    for k, v in out.items():
+        print(k, tuple(v.shape), float(v.abs().mean()), bool(torch.isfinite(v).all()))
+
+
 def gen_adapose_trainbn(out_dir):
     """The as-shipped normalisation (interface_v5.py:39-56 never calls .eval()): the reference module in .train()
     with only its Dropout2d modules in .eval() (their masks are random), run the way the estimator runs it — ONE pose per call —
@@ -1038,6 +1104,8 @@ if __name__ == "__main__":
         gen_postproc_v4(out_dir)
     if "adapose_baseline" in which:       # on request only
         gen_adapose_baseline(out_dir)
-    if "adapose_dropout" in which:        # last: its torch.manual_seed cannot reach the generators above
+    if "adapose_realworld" in which:      # on request only
+        gen_adapose_realworld(out_dir)
+    if "adapose_dropout" in which:       # last: its torch.manual_seed cannot reach the generators above
         gen_adapose_dropout(out_dir)
     print("done")
