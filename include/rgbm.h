@@ -118,6 +118,24 @@ int rgbm_adapose_forward_realworld(rgbm_adapose_t* h, int B, const float* img1, 
 int rgbm_pts2d_to_coor(const float* pts2d_dev, float* coor_dev, int64_t n_points, int W, int H, void* stream);
 int rgbm_pose_rows(rgbm_adapose_t* h, const float* nocs4, const float* coor1, const float* coor2, const float* depth, float* rows, int B, int P,
                    int views, void* stream);
+/* The v2 network, StereoPoseNet (lib/network_v2.py; interface_v2.py builds it): v5's PSPNet and NOCS branch, no cost regularisation and no
+ * depth.  Its stereo part is pointwise - ref + warped over the 24 planes, volume_conv (three 1x1x1 Conv3d + BatchNorm + ReLU, 32 -> 16 ->
+ * 8 -> 1), fuse_conv (1x1 Conv2d 24 -> 32, ReLU, 32 -> 64), a gather at `choose` - so one kernel evaluates it at the chosen pixels only,
+ * with pose_mlp1 (64 -> 64 -> 64) behind it, in fp32 whatever the storage type: no volume exists in memory.  pose_mlp2 (128 -> 128 -> 128)
+ * and size_estimator (128 -> 128 -> 64 -> 3) follow; every mean over a view's points is finished in a fixed order.  DESIGN.md section 5s.
+ * rgbm_adapose_create_v2: the same handle type from a StereoPoseNet state dict (eval BatchNorm folded at create); all four storage types;
+ *   a missing weight is reported by name.  rgbm_adapose_forward / _forward_ex serve the handle: view*_nocs and view*_s are written,
+ *   view*_depth / _r / _t are NaN (this network has none), and with option view2_heads = 0 the view-2 outputs are NaN too.  The dense /
+ *   maps forwards, forward_realworld, forward_samples, the feature cache, Dropout2d and hipGraph replay refuse the handle by name; the
+ *   cost-volume options are errors.  rgbm_adapose_fetch knows "v2_rows" [2B][P][64] (pose_mlp1's output), "v2_fuse" [2B][P][64]
+ *   (fuse_conv's output at the chosen pixels) and "v2_planes" [2B][P][24] (volume_conv's) besides the PSPNet taps.
+ * rgbm_v2_point_rows: the kernel alone with the handle's weights (tests, timing).  feat [2B][S][S][32] fp32 maps, views ordered
+ *   [view-1 poses ; view-2 poses]; choose [views * P] pixel indices into the S x S crop; P_views [2B][16] the views' projections,
+ *   depths [B][24]; homog_scratch 2B x 12 floats -> rows [views * P][64], and, where not NULL, fuse64 [views * P][64] and planes
+ *   [views * P][24]; views = B or 2 B; feat, rows and fuse64 16-byte aligned.  A view whose projection cannot be inverted gets NaN rows, no other view does. */
+int rgbm_adapose_create_v2(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype);
+int rgbm_v2_point_rows(rgbm_adapose_t* h, const float* feat, const int32_t* choose, const float* P_views, const float* depths, float* homog_scratch,
+                       float* rows, float* fuse64, float* planes, int B, int P, int S, int views, void* stream);
 /* views per cost-volume chunk (default 512 = batch 256 in one chunk); bounds the workspace */
 int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views);
 /* options: "max_chunk" (views per cost-volume chunk), "fuse_final" (bf16 only; 1 [default] = PSPNet's final 1x1 runs inside
@@ -149,7 +167,7 @@ int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value);
 /* Path selection: which of its alternative kernel paths a forward runs, decided in one pure function (csrc/forward_paths.cpp) of plain
  * ints.  rgbm_forward_paths never touches the HIP runtime (works without a GPU): facts [n_rows][RGBM_PATH_FACT_INTS] ->
  * paths [n_rows][RGBM_PATH_INTS], row by row.
- *   facts: [0] arch 0 v5 / 1 baseline / 2 real-world (v5's paths, never paths[5] = 2 or paths[8] = 4)  [1] dtype (RGBM_F32 ..)  [2] norm_mode
+ *   facts: [0] arch 0 v5 / 1 baseline / 2 real-world (v5's paths, never paths[5] = 2 or paths[8] = 4) / 3 v2 (no 3-D paths: [7] .. [14] and [16] are 0; split pairs: [5] = 1)  [1] dtype (RGBM_F32 ..)  [2] norm_mode
  *     [3] cost_impl [4] sparse_tail [5] sparse_dec [6] sweep_f16 [7] igemm_conv6 [8] fuse_final [9] upconv [10] stem [11] view2_heads: the
  *     options of rgbm_adapose_set_option  [12] pose_x3 (1: split-pair nets run the per-point pose layers on split pairs)
  *     [13] the rgbm_debug_flags word (negative: the process's current one, as rgbm_conv_plan takes it); read here: 1024 (PSP stage of rounds 1-5), 2048 (per-layer point MLP), 4096 (halo-tile conv0
@@ -168,7 +186,7 @@ int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value);
  *     [5] feature map: 0 the storage type; 1 plain fp32 only (split pairs, cost_impl 3, [15], norm_mode 0, not flag 4096: nothing reads
  *         the split-pair map); 2 f16 (bf16, sweep_f16, cost_impl 3, [16], norm_mode 0, not flag 4096, paths [4] = 2 and [20])
  *     [6] 1 = the split-pair map is copied to plain fp32 by a launch of its own (split pairs without [5] = 1)
- *     [7] cost regularisation: 0 none (baseline), 1 per-sample BatchNorm3d on generic layers (norm_mode 1), 2 generic implicit GEMM
+ *     [7] cost regularisation: 0 none (baseline, v2), 1 per-sample BatchNorm3d on generic layers (norm_mode 1), 2 generic implicit GEMM
  *         (cost_impl 0), 3 halo tiles
  *     [8] conv0: 0 the layer of body 1 / 2 on the materialised volume; in body 3: 1 halo tile on the volume (cost_impl 1), 2 halo tile with
  *         the plane sweep fused in, 3 depth-sweeping kernel (16-bit storage, cost_impl 3, [15], not flag 4096), 4 the same on f16 features
@@ -504,6 +522,18 @@ int rgbm_prepare_inputs_opt(const void* rgb_dev, int pixel_type, int normalize, 
                             const int32_t* frame_map_dev, int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out,
                             int32_t* choose_out, float* pts2d_out, double* Kcrop_out, int32_t* window_out, int32_t* valid_out,
                             uint8_t* scratch, void* stream);
+/* rgbm_prepare_inputs_opt with the points drawn as AdaPoseEstimator_v2.prepare_model_input draws them (interface_v2.py:74-98, "sample, then
+ * resize"): the candidates are the non-zero pixels of mask[rmin:rmax, cmin:cmax] at the frame's own resolution, in row-major order, index
+ * i = row * crop_w + col with crop_w = rmax - rmin (up to 440 x 440 = 193 600 of them).  The subset rule is unchanged on that index: more
+ * than P candidates -> the P smallest (mix32(seed, frame0 + f, i), i) in index order; 1 .. P -> wrap padding; none, or an invalid frame ->
+ * zeros and valid = 0.  pts2d_out (may be NULL) = (cmin + col, rmin + row), whole pixels of the frame as float32; choose_out =
+ * floor(row * ratio) * S + floor(col * ratio), ratio = S / crop_w in fp64, so indices repeat when crop_w > S.  img_out, Kcrop_out and
+ * window_out are rgbm_prepare_inputs_opt's, same arguments, same scratch.  One workgroup per frame; the window's mask is staged as a bit
+ * mask in LDS.  P <= 8192. */
+int rgbm_prepare_inputs_native(const void* rgb_dev, int pixel_type, int normalize, const uint8_t* mask_dev, const double* K_dev,
+                               const int32_t* frame_map_dev, int frame0, int N, int H, int W, int S, int P, uint32_t seed, float* img_out,
+                               int32_t* choose_out, float* pts2d_out, double* Kcrop_out, int32_t* window_out, int32_t* valid_out,
+                               uint8_t* scratch, void* stream);
 /* rgbm_prepare_inputs_opt from crop windows the HOST has cut out of the frames (estimate() with cfg hip_upload: "windows"): only the
  * pixels the crop kernel reads cross PCIe.  The caller derives frame f's window (rmin, rmax, cmin, cmax) = window_dev[f] from the mask
  * with get_bbox's integer arithmetic (lib/utils.py:10-38 with H x W for 480 x 640; an empty mask: (0, 40, 0, 40) and valid_in_dev[f] = 0)

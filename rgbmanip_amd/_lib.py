@@ -111,6 +111,8 @@ SIGNATURES = {
     "rgbm_adapose_set_chunk": (_i, [_vp, _i]),
     "rgbm_adapose_set_option": (_i, [_vp, C.c_char_p, _i]),
     "rgbm_adapose_create_realworld": (_i, [C.POINTER(_vp), _i, C.POINTER(WeightDesc), _i, _i]),
+    "rgbm_adapose_create_v2": (_i, [C.POINTER(_vp), _i, C.POINTER(WeightDesc), _i, _i]),
+    "rgbm_v2_point_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rgbm_adapose_forward_realworld": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _i, _vp]),
     "rgbm_pose_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "rgbm_pts2d_to_coor": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp]),
@@ -192,6 +194,7 @@ SIGNATURES = {
     "rgbm_prepare_inputs_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_prepare_inputs_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_prepare_inputs_opt": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rgbm_prepare_inputs_native": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_prepare_inputs_windows": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbm_quantize_frames": (_i, [_vp, _vp, C.c_size_t, _vp]),
     "rgbm_projection": (_i, [_vp, _vp, _vp, _i, _vp]),

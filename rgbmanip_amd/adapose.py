@@ -38,8 +38,12 @@ class AdaPoseNet:
         # arch "realworld": the reference's StereoPoseNet_with_depth_for_realdemo (lib/network_realworld.py) from its state dict - v5 on a
         # variance cost volume, the pose rows from camera points.  forward() needs coor1= / coor2=.  dtype fp16,
         # hipGraph replay, Dropout2d, per-sample BatchNorm3d, the dense maps, forward_samples and the feature cache are refused.
-        if arch not in ("v5", "baseline", "realworld"):
-            raise ValueError(f"arch must be 'v5', 'baseline' or 'realworld', got {arch!r}")
+        # arch "v2": the reference's StereoPoseNet (lib/network_v2.py) from its state dict - v5's PSPNet and NOCS branch, the pointwise stereo
+        # part and pose_mlp1 evaluated at the chosen pixels by one kernel, a size branch and no depth / rotation / translation (DESIGN.md
+        # section 5s): forward() returns view*_nocs and view*_s, the other six outputs are NaN.  All four dtypes; hipGraph replay, Dropout2d,
+        # per-sample BatchNorm3d, split_streams, the dense maps, forward_samples and the feature cache are refused.
+        if arch not in ("v5", "baseline", "realworld", "v2"):
+            raise ValueError(f"arch must be 'v5', 'baseline', 'realworld' or 'v2', got {arch!r}")
         self.arch = arch
         self.regress_pose = bool(regress_pose)
         if arch == "baseline":
@@ -54,6 +58,11 @@ class AdaPoseNet:
                             ("dtype fp16", _DTYPES[dtype] == _lib.F16)):
                 if on:
                     raise _lib.RgbmError(f"AdaPoseNet(arch='realworld'): {key} is not implemented for the real-world network")
+        if arch == "v2":
+            for key, on in (("graph", graph), ("dropout", dropout), ("norm_mode", norm_mode not in (0, "eval")), ("split_streams", split_streams),
+                            ("cost_impl", cost_impl is not None), ("sparse_tail", sparse_tail is not None)):
+                if on:
+                    raise _lib.RgbmError(f"AdaPoseNet(arch='v2'): {key} is not implemented for the v2 network")
         # graph: forwards of at most `graph_max_batch` poses are replayed from a hipGraph captured per batch size
         # (rgbm_adapose_forward_graph): static input / output / workspace buffers per batch size, one hipGraphLaunch instead of ~150
         # launches — the small-batch deployment path (interface_v5.py:213-227 calls the network per env; cfg/task/open_cabinet.yaml
@@ -106,6 +115,8 @@ class AdaPoseNet:
                        "rgbm_adapose_create_baseline")
         elif arch == "realworld":
             _lib.check(self.lib.rgbm_adapose_create_realworld(C.byref(self._h), device, arr, len(descs), self.dtype), "rgbm_adapose_create_realworld")
+        elif arch == "v2":
+            _lib.check(self.lib.rgbm_adapose_create_v2(C.byref(self._h), device, arr, len(descs), self.dtype), "rgbm_adapose_create_v2")
         else:
             _lib.check(self.lib.rgbm_adapose_create(C.byref(self._h), device, arr, len(descs), self.dtype, int(self.norm_mode)),
                        "rgbm_adapose_create")
@@ -257,6 +268,8 @@ class AdaPoseNet:
                 raise _lib.RgbmError("AdaPoseNet(arch='realworld'): forward needs coor1= and coor2= (the normalised point coordinates)")
         elif coor1 is not None or coor2 is not None:
             raise _lib.RgbmError("coor1 / coor2 are inputs of arch='realworld' only")
+        if self.arch == "v2" and (dense_depth or dense_nocs):
+            raise _lib.RgbmError("AdaPoseNet(arch='v2'): dense_depth / dense_nocs are not implemented for the v2 network")
         if dense_depth or dense_nocs:
             assert stop_after == 0, "dense_depth / dense_nocs: the whole forward"
             return self._forward_dense((view1_img, view2_img, view1_choose, view2_choose, view1_proj, view2_proj, depth_values), stream,
@@ -518,6 +531,29 @@ class AdaPoseNet:
         self._last = (s1, s2, ch1, ch2, P1, P2, dep)
         return out
 
+    def v2_point_rows(self, feat, choose, P_views, depth_values, views: int | None = None, stream=None):
+        """The per-point plane-sweep head alone with this net's weights (arch "v2"; rgbm_v2_point_rows): feat [2B, S, S, 32] float32 feature
+        maps (views = the view-1 crops, then the view-2 crops), choose [views, P] pixel indices, P_views [2B, 4, 4], depth_values [B, 24]
+        -> (rows [views, P, 64] = pose_mlp1's output, fuse [views, P, 64] = fuse_conv's, planes [views, P, 24] = volume_conv's)."""
+        feat = self._prep(feat, torch.float32)
+        ch = self._prep(choose, torch.int32)
+        Pv = self._prep(P_views, torch.float32)
+        dep = self._prep(depth_values, torch.float32)
+        V, S = feat.shape[0], feat.shape[1]
+        B = V // 2
+        views = ch.shape[0] if views is None else int(views)
+        P = ch.shape[1]
+        assert feat.shape == (2 * B, S, S, 32) and Pv.shape == (2 * B, 4, 4) and dep.shape == (B, 24) and views in (B, 2 * B), (feat.shape, ch.shape)
+        assert ch.shape == (views, P)
+        homog = torch.empty(2 * B, 12, dtype=torch.float32, device=self.device)
+        rows = torch.empty(views, P, 64, dtype=torch.float32, device=self.device)
+        fuse = torch.empty(views, P, 64, dtype=torch.float32, device=self.device)
+        planes = torch.empty(views, P, 24, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.rgbm_v2_point_rows(self._h, _lib.ptr(feat), _lib.ptr(ch), _lib.ptr(Pv), _lib.ptr(dep), _lib.ptr(homog), _lib.ptr(rows),
+                                               _lib.ptr(fuse), _lib.ptr(planes), B, P, S, views, _lib.stream_ptr(stream)), "rgbm_v2_point_rows")
+        self._last_v2 = (feat, ch, Pv, dep, homog)      # keep inputs alive until the stream has consumed them
+        return rows, fuse, planes
+
     def fetch(self, B: int, name: str, max_elems: int) -> torch.Tensor:
         """Debug/test access to a named intermediate of the last forward (fp32, flat)."""
         if self._last_split:
@@ -702,7 +738,7 @@ def pts2d_to_coor(pts2d, W: int, H: int, stream=None):
 
 
 def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: int = 0, want_pts2d: bool = False, stream=None,
-                   frame_map=None, frame0: int = 0, normalize: bool = True, want_mask: bool = False):
+                   frame_map=None, frame0: int = 0, normalize: bool = True, want_mask: bool = False, sample: str = "resized"):
     """Batched device-side `AdaPoseEstimator_v5.prepare_model_input` (`interface_v5.py:58-170`).
 
     rgb [N,H,W,3] float32 in [0,1], mask [N,H,W] (0/1), K [N,3,3]: torch CUDA tensors (or anything torch.as_tensor accepts).
@@ -713,6 +749,10 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     `normalize=False` (`rgbm_prepare_inputs_opt`): img is the resized crop itself, without the ImageNet mean / std step — the plain
     `ToTensor` transform of `AdaPoseEstimator_v4` for every task but "pots" (`interface_v4.py:52-58`); every other output is unchanged.
     `want_mask=True` adds `mask` [N,S,S] uint8: the nearest-neighbour resize of the frame mask's crop window that `choose` is drawn from.
+    `sample="native"` (`rgbm_prepare_inputs_native`; `AdaPoseEstimator_v2.prepare_model_input`, `interface_v2.py:74-98`): the points are drawn
+    from the frame mask at native resolution inside the crop window (candidate i = row * crop_w + col, the same seeded subset rule on i)
+    and mapped into the crop afterwards: pts2d are whole pixels of the frame, choose = floor(row * ratio) * S + floor(col * ratio) with
+    ratio = S / crop_w, which repeats when the window is larger than the crop.  img, Kcrop and window are unchanged.
     Returns dict(img [N,3,S,S] f32, choose [N,P] i32, Kcrop [N,3,3] f64, window [N,4] i32, valid [N] i32[, pts2d][, mask])."""
     lib = _lib.load()
     dev = rgb.device if isinstance(rgb, torch.Tensor) and rgb.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -741,7 +781,12 @@ def prepare_inputs(rgb, mask, K, img_size: int = 224, n_pts: int = 1024, seed: i
     scratch = torch.empty(N * S * S, dtype=torch.uint8, device=dev)
     tail = (N, H, W, S, P, int(seed) & 0xFFFFFFFF, _lib.ptr(img), _lib.ptr(choose), _lib.ptr(pts2d), _lib.ptr(Kcrop), _lib.ptr(window),
             _lib.ptr(valid), _lib.ptr(scratch), _lib.stream_ptr(stream))
-    if not normalize:
+    if sample not in ("resized", "native"):
+        raise ValueError(f"prepare_inputs: sample must be 'resized' or 'native', got {sample!r}")
+    if sample == "native":
+        _lib.check(lib.rgbm_prepare_inputs_native(_lib.ptr(rgb), int(u8), int(bool(normalize)), _lib.ptr(mask), _lib.ptr(K), _lib.ptr(frame_map),
+                                                  int(frame0), *tail), "rgbm_prepare_inputs_native")
+    elif not normalize:
         _lib.check(lib.rgbm_prepare_inputs_opt(_lib.ptr(rgb), int(u8), 0, _lib.ptr(mask), _lib.ptr(K), _lib.ptr(frame_map), int(frame0), *tail),
                    "rgbm_prepare_inputs_opt")
     elif u8:

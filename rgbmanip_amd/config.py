@@ -32,6 +32,9 @@ RL_CONTROLLER_CFG = {
 # hip_as_shipped and hip_graph are refused for it) or "adapose_realworld" (train.py:246-248: AdaPoseEstimator_realworld, the variance-volume
 # network of lib/network_realworld.py with the scaled PnP tail; its checkpoint is v5's plus camera_pts_mlp and a 128-wide pose_mlp1.0;
 # direct_regression / use_depth are not read; the four keys above, hip_norm_mode: 1, hip_prepare: host and hip_dtype: fp16 are refused)
+# or "adapose_v2" (train.py:226-228: AdaPoseEstimator_v2, the StereoPoseNet of lib/network_v2.py behind a prepare step that draws the points
+# at native resolution, with the scaled PnP tail; direct_regression / use_depth are not read; the four keys above, hip_norm_mode: 1,
+# hip_prepare: host and hip_upload: windows are refused)
 def adapose_cfg(task_name="one_door_cabinet", checkpoint_path="downloads/pose_estimator/one_door_cabinet.pth", load=True, name="adapose_v5"):
     return {"name": name, "task_name": task_name, "load": load, "checkpoint_path": checkpoint_path, "img_size": 224,
             "use_depth": True, "n_pts": 1024, "direct_regression": True, "real_world": False}

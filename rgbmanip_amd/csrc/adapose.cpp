@@ -144,6 +144,64 @@ int AdaPose::create_realworld(const StateDict& sd, int dtype_) {
   return create_pose(sd);
 }
 
+// The v2 network (lib/network_v2.py:40-197): PSPNet, instance_color and nocs_head as v5's; volume_conv, fuse_conv and pose_mlp1 become the
+// LDS image of v2_point_rows_kernel; pose_mlp2 (128 -> 128 -> 128) keeps its global half as a per-view bias, as create_pose does at 256;
+// size_estimator 128 -> 128 -> 64 -> 3 sits in row 2 of head_w / head_b.  Every layer behind the feature map is fp32.
+int AdaPose::create_v2(const StateDict& sd, int dtype_) {
+  dtype = dtype_;
+  norm_mode = 0;
+  arch = ARCH_V2;
+  if (int rc = create_backbone(sd)) return rc;
+  if (int rc = create_point_heads(sd, false)) return rc;
+  {
+    V2HeadWeights m{};
+    std::vector<float> scale[3], shift[3];
+    static const int vc_in[3] = {32, 16, 8}, vc_out[3] = {16, 8, 1};
+    for (int l = 0; l < 3; ++l) {
+      const std::string p = "volume_conv." + std::to_string(l) + ".";
+      GET(w, p + "conv.weight");
+      RGBM_REQUIRE(w->numel() == (long long)vc_in[l] * vc_out[l], "weight shape " + p + "conv.weight");
+      if (int rc = bn_fold(sd, p + "bn.", vc_out[l], scale[l], shift[l])) return rc;
+      m.vc_w[l] = w->data; m.vc_scale[l] = scale[l].data(); m.vc_shift[l] = shift[l].data();
+    }
+    static const char* const fc[2] = {"fuse_conv.0", "fuse_conv.2"};
+    static const char* const pm[2] = {"pose_mlp1.0", "pose_mlp1.2"};
+    static const int fc_in[2] = {24, 32}, fc_out[2] = {32, 64};
+    for (int l = 0; l < 2; ++l) {
+      GET(fw, std::string(fc[l]) + ".weight"); GET(fb, std::string(fc[l]) + ".bias");
+      RGBM_REQUIRE(fw->numel() == (long long)fc_in[l] * fc_out[l] && fb->numel() == fc_out[l], std::string("weight shape ") + fc[l]);
+      GET(pw, std::string(pm[l]) + ".weight"); GET(pb, std::string(pm[l]) + ".bias");
+      RGBM_REQUIRE(pw->numel() == 64 * 64 && pb->numel() == 64, std::string("weight shape ") + pm[l] + ": 64 x 64 expected");
+      m.fc_w[l] = fw->data; m.fc_b[l] = fb->data; m.pm_w[l] = pw->data; m.pm_b[l] = pb->data;
+    }
+    std::vector<float> table((size_t)kV2HeadFloats);
+    v2_head_pack(m, table.data());
+    if (upload_f32(table.data(), table.size(), v2_w)) return -2;
+  }
+  {
+    // pose_mlp2.0 sees cat(point row[64], global mean[64]); the global half becomes a per-view bias
+    GET(w, "pose_mlp2.0.weight"); GET(b, "pose_mlp2.0.bias");
+    RGBM_REQUIRE(w->numel() == 128 * 128 && b->numel() == 128, "pose_mlp2.0 shape: 128 x 128 expected");
+    std::vector<float> wl(128 * 64);
+    for (int o = 0; o < 128; ++o) for (int i = 0; i < 64; ++i) wl[o * 64 + i] = w->data[o * 128 + i];
+    if (int rc = init_linear(pm2[0], scratch, sd, "pose_mlp2.0", 64, 128, ACT_RELU, 64, 128, wl.data(), F32)) return rc;
+    if (upload_f32(w->data, 128 * 128, pm2_0_wfull)) return -2;
+    if (upload_f32(b->data, 128, pm2_0_bias)) return -2;
+    GET(w2, "pose_mlp2.2.weight");
+    RGBM_REQUIRE(w2->numel() == 128 * 128, "pose_mlp2.2 shape: 128 x 128 expected");
+    if (int rc = init_linear(pm2[1], scratch, sd, "pose_mlp2.2", 128, 128, ACT_RELU, 128, 128, nullptr, F32)) return rc;
+  }
+  const int dims[4] = {128, 128, 64, 3};
+  for (int l = 0; l < 3; ++l) {
+    GET(w, "size_estimator." + std::to_string(2 * l) + ".weight");
+    GET(b, "size_estimator." + std::to_string(2 * l) + ".bias");
+    RGBM_REQUIRE(w->numel() == (long long)dims[l] * dims[l + 1] && b->numel() == dims[l + 1], "size_estimator weight shape");
+    if (upload_f32(w->data, w->numel(), head_w[2][l])) return -2;
+    if (upload_f32(b->data, b->numel(), head_b[2][l])) return -2;
+  }
+  return 0;
+}
+
 int AdaPose::create_backbone(const StateDict& sd) {
   const int E = dtype_chunk(dtype);
   img_cpad = E;                              // RGB padded to one 16-byte chunk
@@ -419,6 +477,11 @@ int AdaPose::plan(int B, const ForwardPaths& p, Arena& A, Buffers& bf) const {
     bf.vol = bf.bn_scratch = nullptr;
     for (auto& c : bf.c3) c = nullptr;
     A.release(m0);
+    return 0;
+  }
+  if (arch == ARCH_V2) {      // no cost volume: the per-point buffers above are all its heads need
+    bf.vol = bf.bn_scratch = nullptr;
+    for (auto& c : bf.c3) c = nullptr;
     return 0;
   }
   // ---- phase B: cost volume, per chunk of views ----
@@ -699,6 +762,10 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   RGBM_REQUIRE(arch != ARCH_REALWORLD || call.dropout == Dropout::None, "real-world network: Dropout2d is not implemented");
   RGBM_REQUIRE(arch != ARCH_REALWORLD || (call.coor1 != nullptr && call.coor2 != nullptr),
                "real-world network: the forward needs coor1 / coor2 (rgbm_adapose_forward_realworld)");
+  RGBM_REQUIRE(arch != ARCH_V2 || !(call.dense || call.depth_map || call.conf_map || call.nocs_map),
+               "v2 network: the dense / maps forwards are not implemented (it has no probability volume, and its stereo part runs at the chosen pixels only)");
+  RGBM_REQUIRE(arch != ARCH_V2 || call.dropout == Dropout::None, "v2 network: Dropout2d is not implemented");
+  RGBM_REQUIRE(arch != ARCH_V2 || (call.coor1 == nullptr && call.coor2 == nullptr), "v2 network: coor1 / coor2 belong to the real-world network");
   const ForwardPaths p = paths(B, call.dense);
   Buffers bf;
   if (int rc = open_workspace(B, p, workspace, workspace_size, 0, call.dense ? "forward_dense: " : "", call.dense ? " (rgbm_adapose_dense_workspace_bytes)" : "", bf)) return rc;
@@ -725,6 +792,7 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   if (int rc = feat_copy(bf, V, call, p)) return rc;
   if (call.stop_after == 1) return 0;
   if (arch == ARCH_BASELINE) return heads_baseline(bf, B, out, call, p);
+  if (arch == ARCH_V2) return heads_v2(bf, B, depths, out, call, p);
   return heads(bf, B, depths, out, call, p);
 }
 
@@ -743,6 +811,7 @@ int AdaPose::forward_samples(int B, int S, const float* img1, const float* img2,
   RGBM_REQUIRE(B > 0 && S >= 1 && (long long)S * B <= (1 << 20), "forward_samples: B >= 1 poses and S >= 1 samples");
   RGBM_REQUIRE(arch != ARCH_BASELINE, "forward_samples: not implemented for the baseline network (it has no Dropout2d)");
   RGBM_REQUIRE(arch != ARCH_REALWORLD, "forward_samples: not implemented for the real-world network");
+  RGBM_REQUIRE(arch != ARCH_V2, "forward_samples: not implemented for the v2 network (it has no Dropout2d)");
   RGBM_REQUIRE(!(call.dense || call.depth_map || call.conf_map || call.nocs_map) && call.stop_after == 0, "forward_samples: no dense / maps form");
   RGBM_REQUIRE(call.dropout == Dropout::Draw || call.dropout == Dropout::Loaded,
                "forward_samples: Dropout2d is off and no masks are loaded (rgbm_adapose_set_dropout / rgbm_adapose_set_dropout_masks): the samples would be equal");
@@ -830,6 +899,44 @@ int AdaPose::heads_baseline(const Buffers& bf, int B, const Outputs& out, const 
     for (int i = 0; i < 6; ++i)
       if (int rc = launch_fill_nan(rts[i], (long long)B * (i % 3 == 0 ? 9 : 3), s)) return rc;
   }
+  return 0;
+}
+
+// Everything behind the PSPNet of the v2 network (network_v2.py:152-197): the NOCS branch as in v5; the stereo part and pose_mlp1 at the
+// chosen pixels in one kernel (v2_head.hip); the size branch pose_mlp2 -> mean -> size_estimator on 64 / 128 channels, every mean over a
+// view's points finished in the fixed order of launch_mean_points_partial's slices.  No depth, rotation or translation: those outputs are NaN.
+int AdaPose::heads_v2(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const {
+  const int V = 2 * B, P = n_pts, S = img, D = n_depth;
+  hipStream_t s = call.stream;
+  const FeatSource src = gather_source(bf, p);
+  const int Vh = view2_heads ? V : B;
+  RGBM_REQUIRE(v2_w, "v2 network: no packed head table");
+  if (p.point_mlp) {
+    if (int rc = launch_point_mlp(src.dtype, point_mlp_desc(bf, src, Vh), s)) return rc;
+  } else {
+    if (int rc = launch_gather_points(src.dtype, src.feat, bf.choose, bf.X0, Vh, P, S * S, 32, s)) return rc;
+    if (int rc = inst.run(bf.X0, bf.X1, Vh, 1, 1, P, 64, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = nh[0].run(bf.X1, bf.H128, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = nh[1].run(bf.H128, bf.H64, Vh, 1, 1, P, 64, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = nh[2].run(bf.H64, bf.nocs4, Vh, 1, 1, P, 4, nullptr, 0, nullptr, 0, s)) return rc;
+  }
+  // rows (pose_mlp1's output) in X1; fuse_conv's output in H64 and volume_conv's 24 values in prob, for rgbm_adapose_fetch
+  if (int rc = launch_v2_point_rows(src.dtype, v2_w.get<float>(), src.feat, bf.homog, depths, bf.choose, bf.X1, bf.H64, bf.prob, V, B, P, D, S, S, Vh, s)) return rc;
+  if (call.stop_after == 2) return 0;
+  if (int rc = launch_mean_points_partial(F32, bf.X1, bf.Q128a, Vh, P, 64, s)) return rc;
+  if (int rc = launch_view_linear_mean(bf.Q128a, P, bf.glob, pm2_0_wfull.get<float>(), pm2_0_bias.get<float>(), bf.vbias, Vh, 64, 128, 128, 64, 0, s)) return rc;
+  if (int rc = pm2[0].run(bf.X1, bf.Q128b, Vh, 1, 1, P, 128, nullptr, 0, bf.vbias, 128, s)) return rc;
+  if (int rc = pm2[1].run(bf.Q128b, bf.G256b, Vh, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
+  if (int rc = launch_mean_points_partial(F32, bf.G256b, bf.G256a, Vh, P, 128, s)) return rc;
+  if (int rc = launch_view_linear_mean(bf.G256a, P, bf.pf2, head_w[2][0].get<float>(), head_b[2][0].get<float>(), bf.h1, Vh, 128, 128, 128, 0, 1, s)) return rc;
+  if (int rc = launch_view_linear(bf.h1, head_w[2][1].get<float>(), head_b[2][1].get<float>(), bf.h2, Vh, 128, 64, 128, 0, 1, s)) return rc;
+  if (int rc = launch_view_linear(bf.h2, head_w[2][2].get<float>(), head_b[2][2].get<float>(), bf.sv, Vh, 64, 3, 64, 0, 0, s)) return rc;
+  // nocs and s through the staging kernel (view 2's are NaN without its heads); what this network does not compute is NaN
+  if (int rc = stage_out(bf, B, out, s)) return rc;
+  float* const nan_out[6] = {out.depth1, out.depth2, out.r1, out.r2, out.t1, out.t2};
+  const long long nan_n[6] = {(long long)B * P, (long long)B * P, (long long)B * 9, (long long)B * 9, (long long)B * 3, (long long)B * 3};
+  for (int i = 0; i < 6; ++i)
+    if (int rc = launch_fill_nan(nan_out[i], nan_n[i], s)) return rc;
   return 0;
 }
 
@@ -951,6 +1058,7 @@ int AdaPose::features(int V, const float* images, const int* slots, void* pool, 
   RGBM_REQUIRE(V > 0 && pool_records > 0, "features: views and pool records");
   RGBM_REQUIRE(arch != ARCH_BASELINE, "baseline network: the feature cache is not implemented");
   RGBM_REQUIRE(arch != ARCH_REALWORLD, "real-world network: the feature cache is not implemented");
+  RGBM_REQUIRE(arch != ARCH_V2, "v2 network: the feature cache is not implemented");
   RGBM_REQUIRE(call.dropout == Dropout::None, "features: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would change "
                "what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "features: workspace must be 256-byte, pool 16-byte aligned");
@@ -976,6 +1084,7 @@ int AdaPose::forward_cached(int B, const void* pool, int pool_records, const int
   RGBM_REQUIRE(B > 0 && pool_records > 0, "forward_cached: batch and pool records");
   RGBM_REQUIRE(arch != ARCH_BASELINE, "baseline network: the feature cache is not implemented");
   RGBM_REQUIRE(arch != ARCH_REALWORLD, "real-world network: the feature cache is not implemented");
+  RGBM_REQUIRE(arch != ARCH_V2, "v2 network: the feature cache is not implemented");
   RGBM_REQUIRE(call.dropout == Dropout::None, "forward_cached: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would "
                "change what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "forward_cached: workspace must be 256-byte, pool 16-byte aligned");

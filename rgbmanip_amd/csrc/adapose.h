@@ -25,8 +25,12 @@ struct AdaPose {
   // ARCH_REALWORLD, network_realworld.py's StereoPoseNet_with_depth_for_realdemo: v5 with the fused volume a variance (-2 ref warped
   // instead of ref + warped: `fusion` of the conv0 kernels) and the pose rows built from camera points (camera_pts_mlp on x / W, y / H,
   // depth in front of nocs_pts_mlp's 64 channels, pose_mlp1.0 128 wide: head_kernels.hip pose_rows_kernel) instead of depth-guided features
-  enum { ARCH_V5 = PATH_ARCH_V5, ARCH_BASELINE = PATH_ARCH_BASELINE, ARCH_REALWORLD = PATH_ARCH_REALWORLD };
+  // ARCH_V2, network_v2.py's StereoPoseNet: no cost regularisation and no depth; the stereo part is pointwise (ref + warped over the planes
+  // -> volume_conv -> fuse_conv, all 1x1), so it is evaluated at the chosen pixels only, together with pose_mlp1 (v2_head.hip); a 64 / 128
+  // wide size branch behind it, no rotation or translation head (the depth / r / t outputs are NaN)
+  enum { ARCH_V5 = PATH_ARCH_V5, ARCH_BASELINE = PATH_ARCH_BASELINE, ARCH_REALWORLD = PATH_ARCH_REALWORLD, ARCH_V2 = PATH_ARCH_V2 };
   int arch = ARCH_V5;
+  DevBuf v2_w;                    // v2: volume_conv (BatchNorm folded), fuse_conv and pose_mlp1 as v2_point_rows_kernel's LDS image (kernels.h: kV2HeadFloats)
   int fusion() const { return arch == ARCH_REALWORLD ? FUSION_VARIANCE : FUSION_SUM; }      // how the plane sweep fuses a view with its warped partner
   int pose_in() const { return arch == ARCH_REALWORLD ? 128 : 96; }                         // channels of a pose row (input of pose_mlp1.0)
   DevBuf prow_w;                  // real-world: camera_pts_mlp and nocs_pts_mlp as pose_rows_kernel's LDS image (kernels.h: kPoseRowsFloats)
@@ -146,6 +150,7 @@ struct AdaPose {
   int create(const StateDict& sd, int dtype, int norm_mode = 0);
   int create_baseline(const StateDict& sd, int dtype, int regress_pose);
   int create_realworld(const StateDict& sd, int dtype);
+  int create_v2(const StateDict& sd, int dtype);
   // the parts of a network create() / create_baseline() put together (dtype is set before)
   int create_backbone(const StateDict& sd);
   int create_cost(const StateDict& sd);
@@ -184,6 +189,7 @@ struct AdaPose {
   int feature_parts(const Buffers& bf, const ForwardPaths& p, FeaturePart parts[2]) const;
   int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const;
   int heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call, const ForwardPaths& p) const;
+  int heads_v2(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const;
   // what the point heads gather from: the feature map of this forward and its element type (fp32 copy for split pairs, f16 with FEAT_F16)
   struct FeatSource { const void* feat; int dtype; };
   FeatSource gather_source(const Buffers& bf, const ForwardPaths& p) const;

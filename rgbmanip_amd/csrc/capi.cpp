@@ -105,6 +105,7 @@ static int finish_call(rgbm_adapose* h, int B, const AdaPose::Call& call, int rc
 
 static bool is_baseline(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_BASELINE; }
 static bool is_realworld(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_REALWORLD; }
+static bool is_v2(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_V2; }
 
 static int forward_call(rgbm_adapose* h, const char* name, int B, const float* img1, const float* img2, const int32_t* choose1,
                         const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace, size_t workspace_bytes,
@@ -152,6 +153,7 @@ static int create_handle(rgbm_adapose_t** h, const char* name, int device, const
   obj->device = device;
   if (int rc = arch == AdaPose::ARCH_BASELINE    ? obj->net.create_baseline(sd, dtype, mode)
                : arch == AdaPose::ARCH_REALWORLD ? obj->net.create_realworld(sd, dtype)
+               : arch == AdaPose::ARCH_V2        ? obj->net.create_v2(sd, dtype)
                                                  : obj->net.create(sd, dtype, mode)) return rc;
   *h = obj.release();
   return 0;
@@ -174,6 +176,19 @@ int rgbm_adapose_create_baseline(rgbm_adapose_t** h, int device, const rgbm_weig
 
 int rgbm_adapose_create_realworld(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype) {
   return create_handle(h, "create_realworld", device, w, n_w, dtype, AdaPose::ARCH_REALWORLD, 0);
+}
+
+int rgbm_adapose_create_v2(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype) {
+  return create_handle(h, "create_v2", device, w, n_w, dtype, AdaPose::ARCH_V2, 0);
+}
+
+int rgbm_v2_point_rows(rgbm_adapose_t* h, const float* feat, const int32_t* choose, const float* P_views, const float* depths, float* homog_scratch,
+                       float* rows, float* fuse64, float* planes, int B, int P, int S, int views, void* stream) {
+  RGBM_REQUIRE(is_v2(h) && h->net.v2_w, "v2_point_rows: the handle does not hold the v2 network (rgbm_adapose_create_v2)");
+  RGBM_REQUIRE(feat && choose && P_views && depths && homog_scratch && rows && B > 0, "v2_point_rows arguments");
+  if (int rc = launch_homography(P_views, homog_scratch, 2 * B, B, (hipStream_t)stream)) return rc;
+  return launch_v2_point_rows(F32, h->net.v2_w.get<float>(), feat, homog_scratch, depths, choose, rows, fuse64, planes, 2 * B, B, P, h->net.n_depth, S, S,
+                              views, (hipStream_t)stream);
 }
 
 int rgbm_adapose_forward_realworld(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1, const int32_t* choose2,
@@ -231,9 +246,9 @@ int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views) {
 int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value) {
   RGBM_REQUIRE(h && key, "set_option arguments");
   const std::string k = key;
-  if (is_baseline(h))
+  if (is_baseline(h) || is_v2(h))
     for (const char* cv : {"cost_impl", "sparse_tail", "sparse_dec", "sweep_f16", "igemm_conv6"})
-      RGBM_REQUIRE(k != cv, "option " + k + " belongs to the cost volume, which the baseline network does not have");
+      RGBM_REQUIRE(k != cv, "option " + k + " belongs to the cost volume, which the " + (is_v2(h) ? "v2" : "baseline") + " network does not have");
   if (is_realworld(h))
     RGBM_REQUIRE(!(k == "sweep_f16" && value != 0), "option sweep_f16 does not exist for the real-world network (its variance volume has no f16 form)");
   if (k == "max_chunk") { RGBM_REQUIRE(value > 0, "max_chunk"); h->net.max_chunk = value; }
@@ -255,6 +270,7 @@ int rgbm_adapose_set_dropout(rgbm_adapose_t* h, float p, uint64_t seed) {
   RGBM_REQUIRE(h && (p == 0.f || (p > 0.f && p < 1.f)), "set_dropout: p must be 0 (off) or lie in (0, 1)");
   RGBM_REQUIRE(!(is_baseline(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the baseline network");
   RGBM_REQUIRE(!(is_realworld(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the real-world network");
+  RGBM_REQUIRE(!(is_v2(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the v2 network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (!h->net.drop_state) RGBM_CHECK_HIP(hipMalloc(h->net.drop_state.out(), 2 * sizeof(unsigned long long)));
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // every forward issued before this call has drawn its masks
@@ -280,6 +296,7 @@ int rgbm_adapose_set_dropout_masks(rgbm_adapose_t* h, int B, const float* masks_
   RGBM_REQUIRE(h && masks_dev && B > 0, "set_dropout_masks arguments");
   RGBM_REQUIRE(!is_baseline(h), "set_dropout_masks: Dropout2d is not implemented for the baseline network");
   RGBM_REQUIRE(!is_realworld(h), "set_dropout_masks: Dropout2d is not implemented for the real-world network");
+  RGBM_REQUIRE(!is_v2(h), "set_dropout_masks: Dropout2d is not implemented for the v2 network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (int rc = ensure_dropout_capacity(h, B)) return rc;
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // no forward in flight reads the buffer any more
@@ -391,6 +408,7 @@ int rgbm_cloud_gather_views(const float* maps, const int32_t* index, int n, int 
 int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes) {
   RGBM_REQUIRE(h && bytes, "feature_bytes arguments");
   RGBM_REQUIRE(!is_baseline(h), "feature_bytes: the feature cache is not implemented for the baseline network");
+  RGBM_REQUIRE(!is_v2(h), "feature_bytes: the feature cache is not implemented for the v2 network");
   *bytes = h->net.feature_bytes();
   return 0;
 }
@@ -398,6 +416,7 @@ int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes) {
 int rgbm_adapose_features_workspace_bytes(rgbm_adapose_t* h, int V, size_t* bytes) {
   RGBM_REQUIRE(h && bytes && V > 0, "features_workspace_bytes arguments");
   RGBM_REQUIRE(!is_baseline(h), "features_workspace_bytes: the feature cache is not implemented for the baseline network");
+  RGBM_REQUIRE(!is_v2(h), "features_workspace_bytes: the feature cache is not implemented for the v2 network");
   *bytes = h->net.features_workspace_bytes(V);
   return 0;
 }
@@ -405,6 +424,7 @@ int rgbm_adapose_features_workspace_bytes(rgbm_adapose_t* h, int V, size_t* byte
 int rgbm_adapose_features(rgbm_adapose_t* h, int V, const float* img, const int32_t* slots_dev, void* pool, int pool_records,
                           void* workspace, size_t workspace_bytes, void* stream) {
   RGBM_REQUIRE(!is_baseline(h), "features: the feature cache is not implemented for the baseline network");
+  RGBM_REQUIRE(!is_v2(h), "features: the feature cache is not implemented for the v2 network");
   AdaPose::Call call;      // a handle with Dropout2d on (or masks loaded) is refused by the net
   if (int rc = prepare_call(h, "features", 0, {img, slots_dev, pool, workspace}, stream, &call)) return rc;
   return h->net.features(V, img, slots_dev, pool, pool_records, workspace, workspace_bytes, call);
@@ -418,6 +438,7 @@ int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int 
                                 const int32_t* slot2_dev, const int32_t* choose1, const int32_t* choose2, const float* P1, const float* P2,
                                 const float* depths, void* workspace, size_t workspace_bytes, const rgbm_adapose_out* out, void* stream) {
   RGBM_REQUIRE(!is_baseline(h), "forward_cached: the feature cache is not implemented for the baseline network");
+  RGBM_REQUIRE(!is_v2(h), "forward_cached: the feature cache is not implemented for the v2 network");
   AdaPose::Call call;
   if (int rc = prepare_call(h, "forward_cached", B, {pool, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
   return h->net.forward_cached(B, pool, pool_records, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, workspace_bytes,
@@ -428,6 +449,7 @@ int rgbm_adapose_samples_workspace_bytes(rgbm_adapose_t* h, int B, int S, size_t
   RGBM_REQUIRE(h && bytes && B > 0, "samples_workspace_bytes arguments");
   RGBM_REQUIRE(S >= 1 && (long long)S * B <= (1 << 20), "samples_workspace_bytes: S >= 1 samples");
   RGBM_REQUIRE(!is_baseline(h), "samples_workspace_bytes: forward_samples is not implemented for the baseline network");
+  RGBM_REQUIRE(!is_v2(h), "samples_workspace_bytes: forward_samples is not implemented for the v2 network");
   *bytes = h->net.samples_workspace_bytes(B, S);
   return 0;
 }
@@ -437,6 +459,7 @@ int rgbm_adapose_forward_samples(rgbm_adapose_t* h, int B, int S, const float* i
                                  size_t workspace_bytes, const rgbm_adapose_out* out, void* stream) {
   RGBM_REQUIRE(h != nullptr, "forward_samples arguments");
   RGBM_REQUIRE(!is_baseline(h), "forward_samples: not implemented for the baseline network (it has no Dropout2d)");
+  RGBM_REQUIRE(!is_v2(h), "forward_samples: forward_samples is not implemented for the v2 network");
   RGBM_REQUIRE(B > 0 && S >= 1 && (long long)S * B <= (1 << 20), "forward_samples: B >= 1 poses and S >= 1 samples");
   RGBM_REQUIRE(h->net.drop_p > 0.f || h->drop_explicit, "forward_samples: Dropout2d is off and no masks are loaded (rgbm_adapose_set_dropout / "
                "rgbm_adapose_set_dropout_masks): the samples would be equal");
@@ -487,6 +510,7 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
   if (captured) *captured = 0;
   RGBM_REQUIRE(!is_baseline(h), "forward_graph: hipGraph replay is not implemented for the baseline network");
   RGBM_REQUIRE(!is_realworld(h), "forward_graph: hipGraph replay is not implemented for the real-world network");
+  RGBM_REQUIRE(!is_v2(h), "forward_graph: hipGraph replay is not implemented for the v2 network");
   AdaPose::Call call;
   // the in-library profiler records events around launches: not capturable, and a timing run wants the launches themselves
   // masks loaded by rgbm_adapose_set_dropout_masks are for one forward: not captured
@@ -597,6 +621,10 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   else if (nm == "pf96") { src = bf.PF96; cnt = V * P * n.pose_in(); dt = n.pose_dtype() == BF16X3 ? BF16X3 : F32; }
   else if (nm == "pf2") { src = bf.pf2; cnt = V * 256; dt = F32; }
   else if (nm == "r6") { src = bf.r6; cnt = V * 6; dt = F32; }
+  // the v2 network's per-point head (v2_head.hip): pose_mlp1's rows, fuse_conv's output and volume_conv's 24 plane values at the chosen pixels
+  else if (nm == "v2_rows" && is_v2(h)) { src = bf.X1; cnt = V * P * 64; dt = F32; }
+  else if (nm == "v2_fuse" && is_v2(h)) { src = bf.H64; cnt = V * P * 64; dt = F32; }
+  else if (nm == "v2_planes" && is_v2(h)) { src = bf.prob; cnt = V * P * D; dt = F32; }
   else if (nm == "fused1" && bf.fused) { src = bf.fused; cnt = (size_t)B * P * 32; dt = F32; }
   else if (nm == "fused2" && bf.fused) { src = bf.fused + (size_t)B * P * 32; cnt = (size_t)B * P * 32; dt = F32; }
   // the taps of the cost regularisation: the outputs of these rows of kCost3d
@@ -607,6 +635,9 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   if (is_baseline(h))      // the cost-volume buffers do not exist in this handle's workspace
     RGBM_REQUIRE(nm == "feat" || nm == "fused1" || nm == "fused2" || nm == "pf96" || nm == "pf2" || nm == "r6" || nm == "layer4" || nm == "cat" ||
                  nm == "u1" || nm == "u2", "tap '" + nm + "' does not exist in the baseline network");
+  if (is_v2(h))      // neither the cost-volume buffers nor v5's pose buffers are written in this handle's workspace
+    RGBM_REQUIRE(nm == "feat" || nm == "homog" || nm == "v2_rows" || nm == "v2_fuse" || nm == "v2_planes" || nm == "layer4" || nm == "cat" || nm == "u1" ||
+                 nm == "u2", "tap '" + nm + "' does not exist in the v2 network");
   RGBM_REQUIRE(src != nullptr, "unknown intermediate name: " + nm);
   // with sparse cost regularisation c0..c5 / u7 / u9 are written only inside the chosen pixels' dependency cones (and c6 is computed
   // from them): the rest of these tensors is whatever the workspace held, so a tap of them is refused instead of returned partly stale
@@ -963,6 +994,15 @@ extern "C" int rgbm_prepare_inputs_opt(const void* rgb_dev, int pixel_type, int 
   RGBM_REQUIRE(frame0 >= 0, "prepare_inputs_opt frame0");
   return launch_prepare_inputs_opt(rgb_dev, pixel_type, normalize, mask_dev, K_dev, frame_map_dev, N, H, W, S, P, seed, img_out, choose_out,
                                    pts2d_out, Kcrop_out, window_out, valid_out, scratch, (hipStream_t)stream, frame0);
+}
+
+extern "C" int rgbm_prepare_inputs_native(const void* rgb_dev, int pixel_type, int normalize, const uint8_t* mask_dev, const double* K_dev,
+                                          const int32_t* frame_map_dev, int frame0, int N, int H, int W, int S, int P, uint32_t seed,
+                                          float* img_out, int32_t* choose_out, float* pts2d_out, double* Kcrop_out, int32_t* window_out,
+                                          int32_t* valid_out, uint8_t* scratch, void* stream) {
+  RGBM_REQUIRE(frame0 >= 0, "prepare_inputs_native frame0");
+  return launch_prepare_inputs_native(rgb_dev, pixel_type, normalize, mask_dev, K_dev, frame_map_dev, N, H, W, S, P, seed, img_out, choose_out,
+                                      pts2d_out, Kcrop_out, window_out, valid_out, scratch, (hipStream_t)stream, frame0);
 }
 
 extern "C" int rgbm_prepare_inputs_windows(const void* pix_dev, int pixel_type, int normalize, const uint8_t* mask_pix_dev,

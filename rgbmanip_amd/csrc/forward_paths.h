@@ -18,7 +18,9 @@ struct PathFacts {
 
 // PATH_ARCH_REALWORLD: v5's network on a variance cost volume (-2 ref warped); a product of two features squares their range, so no f16
 // feature map and no packed-f16 sweep for it (forward_paths never answers FEAT_F16 / CONV0_SWEEP16_F16)
-enum { PATH_ARCH_V5 = 0, PATH_ARCH_BASELINE = 1, PATH_ARCH_REALWORLD = 2 };
+// PATH_ARCH_V2: network_v2.py's StereoPoseNet - PSPNet and point heads as v5, no 3-D paths (as for the baseline); its pose branch is a
+// kernel of its own (v2_head.hip), so pose_mlp is never answered 1
+enum { PATH_ARCH_V5 = 0, PATH_ARCH_BASELINE = 1, PATH_ARCH_REALWORLD = 2, PATH_ARCH_V2 = 3 };
 enum { STEM_GENERIC = 0, STEM_FUSED = 1 };
 enum { PSP_POOLED_GEMMS = 0, PSP_ONE_LAUNCH = 1, PSP_ROUND5 = 2 };
 enum { UP3_TWO_LAUNCHES = 0, UP3_FUSED_FINAL = 1, UP3_TAIL_KERNEL = 2 };

@@ -129,6 +129,21 @@ constexpr int kPoseRowsFloats = 2 * kPoseRowsMlpFloats;             // camera_pt
 void pose_rows_pack(const float* const w[4], const float* const b[4], float* table);      // host; camera_pts_mlp.0 / .2, nocs_pts_mlp.0 / .2 as [Cout][Cin]
 int launch_pose_rows(const float* table, const float* nocs4, const float* coor1, const float* coor2, const float* depth, float* rows, int B,
                      int P, int Vh, hipStream_t s);
+// v2_head.hip: the per-point plane-sweep head of the v2 network (network_v2.py:152-184) in one launch.  For point p of view v < Vh (views
+// [view-1 crops ; view-2 crops] of B poses, partners among all V = 2B): ref + warped at pixel choose[v][p] over the D = 24 planes ->
+// volume_conv (BatchNorm folded) -> fuse_conv -> pose_mlp1 -> rows [Vh * P][64] fp32.  fuse64 [Vh * P][64] (fuse_conv's output) and
+// planes [Vh * P][24] (volume_conv's) are written when not null.  feat: fp32, bf16 or f16 maps [V][H][W][32]; homog: launch_homography's.
+struct V2HeadWeights {         // host fp32, [Cout][Cin] row-major
+  const float* vc_w[3];        // volume_conv.{0,1,2}.conv.weight: 16 x 32, 8 x 16, 1 x 8
+  const float* vc_scale[3];    // their eval BatchNorm as scale / shift per output channel
+  const float* vc_shift[3];
+  const float *fc_w[2], *fc_b[2];      // fuse_conv.0 (32 x 24), fuse_conv.2 (64 x 32)
+  const float *pm_w[2], *pm_b[2];      // pose_mlp1.0 / .2 (64 x 64)
+};
+constexpr int kV2HeadFloats = (16 * 32 + 16) + (8 * 16 + 8) + (8 + 4) + (24 * 32 + 32) + (32 * 64 + 64) + 2 * (64 * 64 + 64);
+void v2_head_pack(const V2HeadWeights& m, float* table);
+int launch_v2_point_rows(int feat_dtype, const float* table, const void* feat, const float* homog, const float* depths, const int* choose,
+                         float* rows, float* fuse64, float* planes, int V, int B, int P, int D, int H, int W, int Vh, hipStream_t s);
 // coor[i] = (pts2d[i][0] / W, pts2d[i][1] / H) in IEEE float32 division (interface_realworld.py:264-269), n points
 int launch_pts2d_to_coor(const float* pts2d, float* coor, long long n, int W, int H, hipStream_t s);
 int launch_ortho6d(const float* r6, float* R, int V, hipStream_t s);
@@ -237,6 +252,11 @@ int launch_prepare_inputs_u8(const unsigned char* rgb, const unsigned char* mask
 int launch_prepare_inputs_opt(const void* rgb, int pixel_type, int normalize, const unsigned char* mask, const double* K, const int* frame_map,
                               int N, int H, int W, int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop,
                               int* window, int* valid, unsigned char* small_scratch, hipStream_t s, int frame0 = 0);
+// launch_prepare_inputs_opt with the 1024 points drawn from the frame mask at native resolution inside the crop window and mapped into the
+// S x S crop afterwards (interface_v2.py:74-98; prepare.hip choose_native_kernel); img, Kcrop and window are launch_prepare_inputs_opt's
+int launch_prepare_inputs_native(const void* rgb, int pixel_type, int normalize, const unsigned char* mask, const double* K, const int* frame_map,
+                                 int N, int H, int W, int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop,
+                                 int* window, int* valid, unsigned char* small_scratch, hipStream_t s, int frame0 = 0);
 // launch_prepare_inputs_opt from crop windows the host has cut out and packed back to back (pix / mask_pix at the element offsets `offset`,
 // `window` = the windows mask_window_kernel would derive, valid_in 0 = an empty mask); same img / choose / pts2d / Kcrop / valid, bit for bit
 int launch_prepare_inputs_windows(const void* pix, int pixel_type, int normalize, const unsigned char* mask_pix, const long long* offset,

@@ -268,6 +268,135 @@ __global__ __launch_bounds__(PRE_THREADS) void choose_kernel(const unsigned char
   }
 }
 
+// ---- 3b. choose at native resolution: the v2 interface's "sample, then resize" (interface_v2.py:74-98) -----------------------
+// The candidates are the non-zero pixels of mask[rmin:rmax, cmin:cmax] itself, index i = row * crop_w + col: up to 440 x 440 = 193 600 of
+// them, past what 16-bit indices or an index list in LDS can hold.  The window's mask is staged as a bit mask (a wave ballots 64
+// neighbouring pixels into two words: 24.2 KB for the largest window); counts, the key threshold and the ordered compaction are derived
+// from it, every thread owning a contiguous range of words so that order is index order.  The subset rule is choose_kernel's on the native
+// index; the at most P kept indices go to LDS, and from them pts2d = (cmin + col, rmin + row) - whole pixels of the frame - and
+// choose = floor(row * ratio) * S + floor(col * ratio) with ratio = S / crop_w in fp64 like the python float (duplicates when crop_w > S).
+constexpr int kNativeMaxWin = 440;                                                  // get_bbox's largest window (mask_window_kernel)
+constexpr int kNativeWords = (kNativeMaxWin * kNativeMaxWin + 63) / 64 * 2;         // 32-bit words of the bit mask
+
+// A second copy of the scan choose_kernel holds as a lambda, on purpose: moving that lambda out would change choose_kernel's code, whose
+// instructions are kept what they were (contiguous thread ranges keep order).
+__device__ inline int block_excl_scan(int mine, int& total, int* wsum) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int o = __shfl_up(incl, off);
+    if (lane >= off) incl += o;
+  }
+  __syncthreads();                                // wsum free to overwrite
+  if (lane == 63) wsum[wv] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+  for (int k = 0; k < PRE_THREADS / 64; ++k) { if (k < wv) base += wsum[k]; tot += wsum[k]; }
+  total = tot;
+  return base + incl - mine;
+}
+
+__global__ __launch_bounds__(PRE_THREADS) void choose_native_kernel(const unsigned char* __restrict__ mask, const int* __restrict__ frame_map,
+                                                                     const int* __restrict__ window, int H, int W, int S, int P, unsigned seed,
+                                                                     int* __restrict__ choose /*[N,P]*/, float* __restrict__ pts2d /*[N,P,2] or null*/,
+                                                                     int* __restrict__ valid, int frame0) {
+  extern __shared__ int sel[];                      // the kept native indices, in order (P of them at most)
+  __shared__ unsigned bits[kNativeWords];
+  __shared__ int wsum[PRE_THREADS / 64];
+  __shared__ int s_cnt;
+  const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int rmin = window[f * 4 + 0], rmax = window[f * 4 + 1], cmin = window[f * 4 + 2], cmax = window[f * 4 + 3];
+  const int h = rmax - rmin, w = cmax - cmin;
+  const int mf = frame_map ? frame_map[f] : f;
+  // a window the frame does not hold, or one larger than the bit mask, is not read (mask_window_kernel writes neither)
+  const bool ok = valid[f] != 0 && mf >= 0 && h > 0 && w > 0 && h <= kNativeMaxWin && w <= kNativeMaxWin && rmin >= 0 && cmin >= 0 && rmax <= H && cmax <= W;
+  const int M = ok ? h * w : 0;
+  const int nwords = (M + 63) / 64 * 2;
+  const unsigned char* m = mask + (long long)(mf < 0 ? 0 : mf) * H * W;
+  for (int c = wv; c < nwords / 2; c += PRE_THREADS / 64) {
+    const int i = c * 64 + lane;
+    bool on = false;
+    if (i < M) {
+      const int row = i / w, col = i - row * w;
+      on = m[(long long)(rmin + row) * W + cmin + col] != 0;
+    }
+    const unsigned long long b = __ballot(on);
+    if (lane == 0) { bits[2 * c] = (unsigned)b; bits[2 * c + 1] = (unsigned)(b >> 32); }
+  }
+  __syncthreads();
+  const int per = (nwords + PRE_THREADS - 1) / PRE_THREADS;
+  const int lo = min(t * per, nwords), hi = min(lo + per, nwords);
+  int cnt = 0;
+  for (int k = lo; k < hi; ++k) cnt += __popc(bits[k]);
+  int n;
+  const int pos0 = block_excl_scan(cnt, n, wsum);
+  int* out = choose + (long long)f * P;
+  const unsigned hf = (unsigned)(f + frame0);
+  int kept = 0;                                     // entries of sel
+  if (n == 0) {                                     // reference: None -> default bbox; keep the tensors finite
+    for (int i = t; i < P; i += PRE_THREADS) {
+      out[i] = 0;
+      if (pts2d) { pts2d[((long long)f * P + i) * 2 + 0] = 0.f; pts2d[((long long)f * P + i) * 2 + 1] = 0.f; }
+    }
+    if (t == 0) valid[f] = 0;
+    return;
+  } else if (n <= P) {
+    int pos = pos0;
+    for (int k = lo; k < hi; ++k)
+      for (unsigned b = bits[k]; b; b &= b - 1) sel[pos++] = k * 32 + (__ffs(b) - 1);
+    kept = n;
+  } else {
+    // smallest threshold T with count(key <= T) >= P, by bisection over the 32-bit key space
+    unsigned tlo = 0u, thi = 0xFFFFFFFFu;
+    while (tlo < thi) {
+      const unsigned mid = tlo + ((thi - tlo) >> 1);
+      int c = 0;
+      for (int k = lo; k < hi; ++k)
+        for (unsigned b = bits[k]; b; b &= b - 1) c += mix32(seed, hf, (unsigned)(k * 32 + (__ffs(b) - 1))) <= mid ? 1 : 0;
+      if (t == 0) s_cnt = 0;
+      __syncthreads();
+      atomicAdd(&s_cnt, c);
+      __syncthreads();
+      const int tot = s_cnt;
+      __syncthreads();
+      if (tot >= P) thi = mid; else tlo = mid + 1;
+    }
+    const unsigned T = tlo;
+    // keep every key < T and, in index order, as many key == T as still fit
+    int c_lt = 0, c_eq = 0;
+    for (int k = lo; k < hi; ++k)
+      for (unsigned b = bits[k]; b; b &= b - 1) {
+        const unsigned key = mix32(seed, hf, (unsigned)(k * 32 + (__ffs(b) - 1)));
+        c_lt += key < T; c_eq += key == T;
+      }
+    int n_lt, n_eq;
+    int p_lt = block_excl_scan(c_lt, n_lt, wsum);
+    int p_eq = block_excl_scan(c_eq, n_eq, wsum);
+    const int eq_keep = P - n_lt;                   // ties kept (>= 1)
+    for (int k = lo; k < hi; ++k)
+      for (unsigned b = bits[k]; b; b &= b - 1) {
+        const int i = k * 32 + (__ffs(b) - 1);
+        const unsigned key = mix32(seed, hf, (unsigned)i);
+        if (key < T) { sel[p_lt + min(p_eq, eq_keep)] = i; ++p_lt; }
+        else if (key == T) { if (p_eq < eq_keep) sel[p_lt + p_eq] = i; ++p_eq; }
+      }
+    (void)n_eq;
+    kept = P;
+  }
+  __syncthreads();
+  const double ratio = (double)S / (double)h;       // crop_w = rmax - rmin (interface_v2.py:94-95)
+  for (int j = t; j < P; j += PRE_THREADS) {
+    const int i = sel[j % kept];                    // np.pad(choose, ..., "wrap") when fewer than P
+    const int row = i / w, col = i - row * w;       // the window is square: crop_w == w
+    out[j] = (int)(floor((double)row * ratio) * (double)S + floor((double)col * ratio));
+    if (pts2d) {
+      pts2d[((long long)f * P + j) * 2 + 0] = (float)(cmin + col);
+      pts2d[((long long)f * P + j) * 2 + 1] = (float)(rmin + row);
+    }
+  }
+}
+
 // ---- float frames -> bytes: the write side of an 8-bit view queue whose environment hands over float frames -----------------
 // q(x) = min(max(rint(x * 255), 0), 255) with rint = round half to even, NaN -> 0: quantize_px of quantize.h.
 
@@ -346,14 +475,22 @@ namespace {
 template <typename Px, bool NORM = true>
 int prepare_inputs_impl(const Px* rgb, const unsigned char* mask, const double* K, const int* frame_map, int N, int H, int W, int S, int P,
                         unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop, int* window, int* valid,
-                        unsigned char* small_scratch, hipStream_t s, int frame0) {
+                        unsigned char* small_scratch, hipStream_t s, int frame0, int sample_mode = 0) {
   RGBM_REQUIRE(rgb && mask && K && img && choose && Kcrop && window && valid && small_scratch, "prepare_inputs arguments");
+  RGBM_REQUIRE(sample_mode == 0 || sample_mode == 1, "prepare_inputs: sample_mode 0 (resize the mask, then sample) or 1 (sample at native resolution)");
   // the crop window is a square of up to 440 pixels shifted back into the frame (lib/utils.py:10-38 does it for 480 x 640): a
   // smaller frame could not hold it and the shifted window would start at a negative row / column
   RGBM_REQUIRE(N > 0 && H >= 440 && W >= 440 && S > 0 && P > 0 && S * S <= 65536, "prepare_inputs sizes (frames must be at least 440 x 440)");
   hipLaunchKernelGGL(mask_window_kernel, dim3(N), dim3(PRE_THREADS), 0, s, mask, K, frame_map, H, W, S, window, Kcrop, valid);
   const long long tot = (long long)N * S * S;
   hipLaunchKernelGGL((crop_resize_kernel<Px, NORM>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, rgb, mask, frame_map, window, N, H, W, S, img, small_scratch);
+  if (sample_mode == 1) {      // the image, Kcrop and the window are the kernels' above; only the points are drawn differently
+    RGBM_REQUIRE(P <= 8192, "prepare_inputs: native sampling keeps its P chosen indices in LDS (P <= 8192)");
+    hipLaunchKernelGGL(choose_native_kernel, dim3(N), dim3(PRE_THREADS), (size_t)P * sizeof(int), s, mask, frame_map, window, H, W, S, P, seed, choose,
+                       pts2d, valid, frame0);
+    RGBM_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   const size_t lds = (size_t)S * S * sizeof(unsigned short);
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(choose_kernel), 150 * 1024)) return rc;
   hipLaunchKernelGGL(choose_kernel, dim3(N), dim3(PRE_THREADS), lds, s, small_scratch, window, S, P, seed, choose, pts2d, valid, frame0);
@@ -386,6 +523,20 @@ int launch_prepare_inputs_opt(const void* rgb, int pixel_type, int normalize, co
                       : launch_prepare_inputs(f32, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
   return pixel_type ? prepare_inputs_impl<unsigned char, false>(u8, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0)
                     : prepare_inputs_impl<float, false>(f32, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0);
+}
+
+// launch_prepare_inputs_opt with the points drawn at native resolution (sample_mode 1: choose_native_kernel)
+int launch_prepare_inputs_native(const void* rgb, int pixel_type, int normalize, const unsigned char* mask, const double* K, const int* frame_map,
+                                 int N, int H, int W, int S, int P, unsigned seed, float* img, int* choose, float* pts2d, double* Kcrop,
+                                 int* window, int* valid, unsigned char* small_scratch, hipStream_t s, int frame0) {
+  RGBM_REQUIRE((pixel_type == 0 || pixel_type == 1) && (normalize == 0 || normalize == 1), "prepare_inputs_native: pixel_type and normalize are 0 or 1");
+  const float* f32 = static_cast<const float*>(rgb);
+  const unsigned char* u8 = static_cast<const unsigned char*>(rgb);
+  if (normalize)
+    return pixel_type ? prepare_inputs_impl<unsigned char, true>(u8, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0, 1)
+                      : prepare_inputs_impl<float, true>(f32, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0, 1);
+  return pixel_type ? prepare_inputs_impl<unsigned char, false>(u8, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0, 1)
+                    : prepare_inputs_impl<float, false>(f32, mask, K, frame_map, N, H, W, S, P, seed, img, choose, pts2d, Kcrop, window, valid, small_scratch, s, frame0, 1);
 }
 
 namespace {

@@ -1030,3 +1030,85 @@ class AdaPoseEstimator_realworld(AdaPoseEstimator_v5):
 
     def estimate_cloud_views_device(self, *a, **k):
         self._refused("estimate_cloud_views_device", "the dense forward")
+
+
+class AdaPoseEstimator_v2(AdaPoseEstimator_v5):
+    """`pose_estimator.name: adapose_v2` (`interface_v2.py`): `StereoPoseNet` - v5's PSPNet and NOCS branch, a pointwise stereo part
+    evaluated at the chosen pixels and a size branch, no depth, rotation or translation - behind a
+    `prepare_model_input` that draws the 1024 points from the frame mask at native resolution and maps them into the crop afterwards
+    (`interface_v2.py:74-98`; `prepare_inputs(sample="native")`), and the PnP tail with the regressed size (`interface_v2.py:242-266`,
+    csrc/pnp.hip: pnp_scaled_kernel), which reads view 1's NOCS, pixels and size only: `hip_view2_heads` defaults to False, and
+    `use_depth` / `direct_regression` are not read, as in the reference.  `hip_dtype` (all four) and `hip_options` are the code above.
+    One deliberate difference from the shipped interface: its line 239 calls `depth_estimation_from_nocs_matches` with 7 arguments where
+    `lib/utils.py:121` takes 9, so `predict` raises TypeError as shipped; the call's result is unused there, and it is not made here.
+    What is not implemented for this network raises, naming the key."""
+
+    _UNSUPPORTED = ("hip_feature_cache", "hip_dropout", "hip_as_shipped", "hip_graph")
+
+    def __init__(self, env, cfg, logger, state_dict=None, dtype=None, device=0, net=None):
+        for key in self._UNSUPPORTED:
+            if cfg.get(key, False):
+                raise ValueError(f"AdaPoseEstimator_v2: cfg key {key} is not implemented for the v2 network")
+        if cfg.get("hip_norm_mode", "eval") not in ("eval", 0):
+            raise ValueError("AdaPoseEstimator_v2: cfg key hip_norm_mode: per-sample BatchNorm3d is not implemented for the v2 network (it would "
+                             "need the whole volume, which this network's kernel never builds)")
+        if cfg.get("hip_prepare", "device") != "device":
+            raise ValueError('AdaPoseEstimator_v2: cfg key hip_prepare: only "device" is implemented for the v2 network')
+        if cfg.get("hip_upload", "frames") != "frames":
+            raise ValueError('AdaPoseEstimator_v2: cfg key hip_upload: only "frames" is implemented for the v2 network (the points are drawn '
+                             "from the whole frame's mask)")
+        if net is not None and getattr(net, "arch", "v5") != "v2":
+            raise ValueError("AdaPoseEstimator_v2: the shared net must be an AdaPoseNet(arch='v2')")
+        super().__init__(env, cfg, logger, state_dict=state_dict, dtype=dtype, device=device, net=net)
+
+    def _synthetic_state_dict(self):
+        from . import synth
+        return synth.v2_state_dict(seed=0)
+
+    def _build_net(self, state_dict, device, norm_mode, drop_p, drop_seed, options):
+        return AdaPoseNet(state_dict, dtype=self.dtype, device=device, options=options, arch="v2")
+
+    def _pnp_branch(self):
+        """No `direct_regression` / `use_depth` branches here: the one tail reads view 1 alone (the view-2 heads are not needed)."""
+        return False
+
+    # the points are drawn at native resolution, and their pixels are always wanted: the tail reads them
+    def _prepare(self, rgb, *args, **kw):
+        return super()._prepare(rgb, *args, **{**kw, "want_pts2d": True, "sample": "native"})
+
+    def _bbox_tail(self, pred, choose, Kcrop, E1, pts2d=None, E2=None, K=None):
+        """interface_v2.py:242-266: ts = ||view1_s||, EPnP-RANSAC + VVS on (nocs1 ts, pixels of view 1, the ORIGINAL intrinsics)."""
+        return postprocess_pnp_scaled(pred["view1_nocs"], pts2d[0], pred["view1_s"], K, E1, seed=int(self.cfg.get("hip_ransac_seed", 0)))[0]
+
+    def _refused(self, name, why):
+        raise NotImplementedError(f"AdaPoseEstimator_v2.{name}: {why} is not implemented for the v2 network")
+
+    def estimate_samples(self, *a, **k):
+        self._refused("estimate_samples", "Dropout2d (cfg hip_dropout / hip_as_shipped), so there is nothing to sample,")
+
+    def estimate_samples_device(self, *a, **k):
+        self._refused("estimate_samples_device", "Dropout2d (cfg hip_dropout / hip_as_shipped), so there is nothing to sample,")
+
+    def estimate_depth(self, *a, **k):
+        self._refused("estimate_depth", "the dense forward")
+
+    def estimate_depth_device(self, *a, **k):
+        self._refused("estimate_depth_device", "the dense forward")
+
+    def estimate_cloud(self, *a, **k):
+        self._refused("estimate_cloud", "the dense forward")
+
+    def estimate_cloud_device(self, *a, **k):
+        self._refused("estimate_cloud_device", "the dense forward")
+
+    def estimate_cloud_pose(self, *a, **k):
+        self._refused("estimate_cloud_pose", "the dense forward")
+
+    def estimate_cloud_pose_device(self, *a, **k):
+        self._refused("estimate_cloud_pose_device", "the dense forward")
+
+    def estimate_cloud_views(self, *a, **k):
+        self._refused("estimate_cloud_views", "the dense forward")
+
+    def estimate_cloud_views_device(self, *a, **k):
+        self._refused("estimate_cloud_views_device", "the dense forward")

@@ -154,6 +154,45 @@ def realworld_state_dict(seed: int = 0, prefix: str = "") -> "OrderedDict[str, n
     return _draw_state_dict(realworld_schema(), seed, prefix)
 
 
+# The v2 network's draw.  At the plain draw volume_conv.2's ReLU zeroes every value of the golden batch (and none at seed 1), and
+# view1_s == view2_s to four decimals: a fixture that cannot tell a correct stereo part from none.  A gain on volume_conv.2.bn.weight, a
+# shift on its bias and a gain on the two fuse_conv weights bring the last ReLU's clip share near one half and let the size output depend
+# on the plane values; the golden generator (tools/make_goldens.py: gen_adapose_v2) asserts the resulting conditions on the golden batch.
+V2_VC2_BN_GAIN = 16.0
+V2_VC2_BN_SHIFT = 8.3
+V2_FUSE_GAIN = 4.0
+
+
+def v2_schema():
+    """(name, shape, kind) of StereoPoseNet (lib/network_v2.py:40-102) in its state_dict order: v5's PSPNet and instance_color, then
+    volume_conv, fuse_conv, nocs_head and the 64 / 128 wide size branch."""
+    v5 = adapose_schema()
+    by_prefix = lambda *pre: [e for e in v5 if e[0].startswith(pre)]      # noqa: E731
+    s = by_prefix("img_extractor.", "instance_color.")
+    for i, (a, b) in enumerate(((32, 16), (16, 8), (8, 1))):
+        p = f"volume_conv.{i}"
+        last = i == 2
+        s.append((p + ".conv.weight", (b, a, 1, 1, 1), "w"))
+        s += [(p + ".bn.weight", (b,), "v2_bn_g" if last else "bn_g"), (p + ".bn.bias", (b,), "v2_bn_b" if last else "bn_b"),
+              (p + ".bn.running_mean", (b,), "bn_m"), (p + ".bn.running_var", (b,), "bn_v"), (p + ".bn.num_batches_tracked", (), "nbt")]
+    for i, (a, b) in zip((0, 2), ((24, 32), (32, 64))):
+        s.append((f"fuse_conv.{i}.weight", (b, a, 1, 1), "v2_fw"))
+        s.append((f"fuse_conv.{i}.bias", (b,), "b:%d" % a))
+    s += by_prefix("nocs_head.")
+    for pre, dims, idx, conv1d in (("pose_mlp1", (64, 64, 64), (0, 2), True), ("pose_mlp2", (128, 128, 128), (0, 2), True),
+                                   ("size_estimator", (128, 128, 64, 3), (0, 2, 4), False)):
+        for i, (a, b) in zip(idx, zip(dims[:-1], dims[1:])):
+            s.append((f"{pre}.{i}.weight", (b, a, 1) if conv1d else (b, a), "w"))
+            s.append((f"{pre}.{i}.bias", (b,), "b:%d" % a))
+    return s
+
+
+def v2_state_dict(seed: int = 0, prefix: str = "") -> "OrderedDict[str, np.ndarray]":
+    """Synthetic checkpoint of the v2 network.  The generator is keyed by the tensor's name, so the tensors it shares with
+    `adapose_state_dict(seed)` (PSPNet, instance_color, nocs_head) are the same draws, and `adapose_state_dict` returns what it did."""
+    return _draw_state_dict(v2_schema(), seed, prefix)
+
+
 def realworld_coor(B: int, seed: int = 0, n_pts: int = N_PTS, W: int = 640, H: int = 480):
     """Chosen points' pixel coordinates in a W x H frame for the real-world network's goldens: (pts2d1, pts2d2) [B, n_pts, 2] float32
     with whole-pixel values (what prepare_model_input emits), and the normalised (coor1, coor2) = pts2d / (W, H) in float32."""
@@ -197,6 +236,13 @@ def _draw_state_dict(schema, seed: int, prefix: str):
         elif kind.startswith("b+:"):
             bound = 1.0 / np.sqrt(int(kind[3:]))
             v = g.uniform(-bound, bound, size=shape) + BASELINE_DEPTH_BIAS
+        elif kind == "v2_fw":
+            bound = V2_FUSE_GAIN / np.sqrt(int(np.prod(shape[1:])))
+            v = g.uniform(-bound, bound, size=shape)
+        elif kind == "v2_bn_g":
+            v = g.uniform(0.5, 1.5, size=shape) * V2_VC2_BN_GAIN
+        elif kind == "v2_bn_b":
+            v = g.normal(0.0, 0.1, size=shape) + V2_VC2_BN_SHIFT
         elif kind == "prelu":
             v = np.full(shape, 0.25)
         elif kind == "bn_g":

@@ -37,6 +37,7 @@ def kernels(so, work):
 
 
 def key(name):
+    name = name.replace("(anonymous namespace)", "{anonymous}")      # its parentheses are no argument list
     name = re.sub(r"\(.*$", "", name)                       # drop the argument list
     name = re.sub(r"^void ", "", name)
     name = name.replace("<0>", "")                           # a kernel that became a template with its old meaning as <0>

@@ -299,6 +299,82 @@ def gen_adapose_realworld(out_dir):
         print(k, tuple(v.shape), float(v.abs().mean()), bool(torch.isfinite(v).all()))
 
 
+def gen_adapose_v2(out_dir):
+    """The v2 network (lib/network_v2.py: StereoPoseNet) on the golden batch.  Data only: the four outputs; for both views, at the chosen
+    pixels, volume_conv's 24 values, fuse_conv's 64 channels and pose_mlp1's output (every 8th point, and the whole tensor's largest
+    magnitude: 128 of the 1024 points per view and pose, which keeps the file at 251 KB); as scalars measured here on all points, not
+    recomputable from the stored slices except the planes' zero share, the clip share of the four ReLUs in front of them and
+    the share of (point, plane) pairs whose warp leaves the partner image; the class's state-dict keys and shapes.  The forward runs view
+    2's volume_conv / fuse_conv first (network_v2.py:158-159) and view 1's pose_mlp1 first (:184, :190)."""
+    from models.pose_estimator.AdaPose.lib.network_v2 import StereoPoseNet
+    from rgbmanip_amd import synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import v2_ref
+
+    net = StereoPoseNet(n_cat=1).eval()
+    sd = synth.v2_state_dict(seed=0)
+    print("load_state_dict:", net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True))
+    B = 2
+    inp = synth.adapose_inputs(B, seed=0)
+    tin = {k: torch.from_numpy(v) for k, v in inp.items()}
+    choose = {1: tin["choose1"].long(), 2: tin["choose2"].long()}
+    vc = [[], [], []]
+    fc_relu, fc_out, pm1 = [], [], []
+
+    def at_choose(t, v):      # [B, C, (D,) H, W] -> [B, P, C (, D)] at view v's chosen pixels
+        t = t.reshape(t.shape[0], t.shape[1], -1, t.shape[-2] * t.shape[-1])
+        g = torch.stack([t[b][:, :, choose[v][b]] for b in range(t.shape[0])])      # [B, C, D', P]
+        return g.permute(0, 3, 1, 2).contiguous()
+
+    # view 2's chain comes first: call k of these hooks belongs to view 2 - k
+    hs = [net.volume_conv[l].register_forward_hook(lambda mod, i, o, l=l: vc[l].append(at_choose(o.detach(), 2 - len(vc[l])))) for l in range(3)]
+    hs.append(net.fuse_conv[1].register_forward_hook(lambda mod, i, o: fc_relu.append(at_choose(o.detach(), 2 - len(fc_relu)))))
+    hs.append(net.fuse_conv.register_forward_hook(lambda mod, i, o: fc_out.append(at_choose(o.detach(), 2 - len(fc_out)))))
+    hs.append(net.pose_mlp1.register_forward_hook(lambda mod, i, o: pm1.append(o.detach().transpose(1, 2).contiguous())))      # view 1 first
+    args = (tin["img1"], tin["choose1"], tin["img2"], tin["choose2"], tin["P1"], tin["P2"], tin["depths"])
+    with torch.no_grad():
+        out = net(*args)
+        for h in hs:
+            h.remove()
+        out2 = net(*args)
+        for k in out:
+            assert torch.equal(out[k], out2[k]), k
+        save = {k: v.numpy() for k, v in out.items()}
+        feat = {1: net.img_extractor(tin["img1"]), 2: net.img_extractor(tin["img2"])}
+        for v in (1, 2):
+            o, k = 3 - v, 2 - v      # k: position of view v in the lists of the hooks that see view 2 first
+            planes = vc[2][k][:, :, 0, :]                                      # [B, P, 24]
+            fuse = fc_out[k][:, :, :, 0]                                       # [B, P, 64]
+            rows = pm1[v - 1]                                                  # [B, P, 64]
+            for name, t in (("planes", planes), ("fuse", fuse), ("rows", rows)):      # every 8th point: [B, P / 8, C]
+                save[f"v{v}_{name}_slice"] = v2_ref.points_slice(t).contiguous().numpy()
+                save[f"v{v}_{name}_absmax"] = np.array(float(t.abs().max()), dtype=np.float64)
+            clip = [float((vc[l][k] == 0).double().mean()) for l in range(3)] + [float((fc_relu[k] == 0).double().mean())]
+            ix, iy, _ = v2_ref.warp_grid_at(tin[f"P{o}"], tin[f"P{v}"], tin["depths"], choose[v], feat[v].shape[2], feat[v].shape[3], torch.float32)
+            outside = float((v2_ref.taps_inside(ix, iy, feat[v].shape[2], feat[v].shape[3]) == 0).double().mean())
+            spread = float(rows.std(dim=1).mean() / rows.abs().mean())
+            save[f"v{v}_clip"] = np.array(clip, dtype=np.float64)
+            save[f"v{v}_outside"] = np.array(outside, dtype=np.float64)
+            save[f"v{v}_rows_spread"] = np.array(spread, dtype=np.float64)
+            print(f"view {v}: clip shares {['%.3f' % c for c in clip]}, outside share {outside:.3f}, rows' std over points / mean |row| {spread:.3f}")
+            # the fixture conditions tests/test_v2_host.py re-asserts: if the draw misses one, change the draw or add a second seeded rig
+            assert all(0.05 <= c <= 0.95 for c in clip), "a ReLU that clips (almost) nothing or everything"
+            assert 0.05 <= outside <= 0.95, "degenerate rig"
+            assert spread >= 0.25, "rows that do not depend on the point"
+        s1, s2 = out["view1_s"], out["view2_s"]
+        sdiff = float((s1 - s2).abs().max() / torch.maximum(s1.abs().max(), s2.abs().max()))
+        print(f"max|s1 - s2| / max|s| {sdiff:.4f}")
+        assert sdiff >= 0.02, "a size output that does not depend on the view"
+    ref_sd = net.state_dict()
+    save["sd_keys"] = np.array(list(ref_sd.keys()))
+    save["sd_shapes"] = np.array(["x".join(str(d) for d in v.shape) for v in ref_sd.values()])
+    path = os.path.join(out_dir, "adapose_v2_b2.npz")
+    np.savez_compressed(path, **save)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    for k, v in out.items():
+        print(k, tuple(v.shape), float(v.abs().mean()), bool(torch.isfinite(v).all()))
+
+
 def gen_adapose_trainbn(out_dir):
     """The as-shipped normalisation (interface_v5.py:39-56 never calls .eval()): the reference module in .train()
     with only its Dropout2d modules in .eval() (their masks are random), run the way the estimator runs it — ONE pose per call —
@@ -1106,6 +1182,8 @@ if __name__ == "__main__":
         gen_adapose_baseline(out_dir)
     if "adapose_realworld" in which:      # on request only
         gen_adapose_realworld(out_dir)
+    if "adapose_v2" in which:             # on request only
+        gen_adapose_v2(out_dir)
     if "adapose_dropout" in which:       # last: its torch.manual_seed cannot reach the generators above
         gen_adapose_dropout(out_dir)
     print("done")
