@@ -136,6 +136,28 @@ int rgbm_pose_rows(rgbm_adapose_t* h, const float* nocs4, const float* coor1, co
 int rgbm_adapose_create_v2(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype);
 int rgbm_v2_point_rows(rgbm_adapose_t* h, const float* feat, const int32_t* choose, const float* P_views, const float* depths, float* homog_scratch,
                        float* rows, float* fuse64, float* planes, int B, int P, int S, int views, void* stream);
+/* The v1 network, StereoPoseNet (lib/network.py; interface.py builds it): v2's pointwise stereo part with a 32-channel fuse_conv whose
+ * result is a residual on the feature row, fused = relu(feat + fuse_conv(volume_conv(ref + warped))), then v5's heads on the new rows:
+ * instance_color 32 -> 64, nocs_head, nocs_pts_mlp, pose rows cat(instance_color 64, nocs_pts_mlp 64) = 128 channels, pose_mlp1 / pose_mlp2
+ * at v5's widths and the three regression heads with Ortho6d.  No depth.  Two launches at the chosen pixels, fp32 whatever the storage
+ * type: stage A (v1_fused_points_kernel) writes the residual rows, stage B (point_mlp_kernel on rows) the NOCS and the pose rows.
+ * DESIGN.md section 5t.
+ * rgbm_adapose_create_v1: the same handle type from that class's state dict (eval BatchNorm folded at create); all four storage types; a
+ *   missing weight is reported by name.  rgbm_adapose_forward / _forward_ex serve the handle: view*_nocs, _r, _t and _s are written,
+ *   view*_depth is NaN, and with option view2_heads = 0 the view-2 outputs are NaN too.  The dense / maps forwards, forward_realworld,
+ *   forward_samples, the feature cache (rgbm_adapose_feature_bytes included), Dropout2d and hipGraph replay refuse the handle by name;
+ *   the cost-volume options are errors.  rgbm_adapose_fetch knows "v1_fused" [2B][P][32] (stage A's rows), "v1_planes" [2B][P][24]
+ *   (volume_conv's) and "v1_rows" [2B][P][128] (the pose rows) besides the PSPNet taps.
+ * rgbm_v1_point_rows: stages A and B alone with the handle's weights (tests, timing).  feat, choose, P_views, depths, homog_scratch, B, P,
+ *   S and views as for rgbm_v2_point_rows -> fused32 [views * P][32]; where not NULL, planes [views * P][24]; nocs4 [views * P][4] and
+ *   rows128 [views * P][128] are NULL together (stage A alone) or given together.  Stage B is one launch when views * P is a multiple of
+ *   64 and debug flag 2048 is off; otherwise it runs per layer and needs layer_scratch (views * P * 288 floats; may be NULL else).  feat
+ *   and every output 16-byte aligned: a misaligned buffer is refused before any launch.  A view whose projection cannot be inverted
+ *   gets NaN rows, no other view does. */
+int rgbm_adapose_create_v1(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype);
+int rgbm_v1_point_rows(rgbm_adapose_t* h, const float* feat, const int32_t* choose, const float* P_views, const float* depths, float* homog_scratch,
+                       float* fused32, float* nocs4, float* rows128, float* planes, float* layer_scratch, int B, int P, int S, int views,
+                       void* stream);
 /* views per cost-volume chunk (default 512 = batch 256 in one chunk); bounds the workspace */
 int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views);
 /* options: "max_chunk" (views per cost-volume chunk), "fuse_final" (bf16 only; 1 [default] = PSPNet's final 1x1 runs inside
@@ -167,7 +189,7 @@ int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value);
 /* Path selection: which of its alternative kernel paths a forward runs, decided in one pure function (csrc/forward_paths.cpp) of plain
  * ints.  rgbm_forward_paths never touches the HIP runtime (works without a GPU): facts [n_rows][RGBM_PATH_FACT_INTS] ->
  * paths [n_rows][RGBM_PATH_INTS], row by row.
- *   facts: [0] arch 0 v5 / 1 baseline / 2 real-world (v5's paths, never paths[5] = 2 or paths[8] = 4) / 3 v2 (no 3-D paths: [7] .. [14] and [16] are 0; split pairs: [5] = 1)  [1] dtype (RGBM_F32 ..)  [2] norm_mode
+ *   facts: [0] arch 0 v5 / 1 baseline / 2 real-world (v5's paths, never paths[5] = 2 or paths[8] = 4) / 3 v2 (no 3-D paths: [7] .. [14] and [16] are 0; split pairs: [5] = 1) / 4 v1 (as 3: paths [7] .. [14] are 0, [15] by v5's rule, [16] = 0)  [1] dtype (RGBM_F32 ..)  [2] norm_mode
  *     [3] cost_impl [4] sparse_tail [5] sparse_dec [6] sweep_f16 [7] igemm_conv6 [8] fuse_final [9] upconv [10] stem [11] view2_heads: the
  *     options of rgbm_adapose_set_option  [12] pose_x3 (1: split-pair nets run the per-point pose layers on split pairs)
  *     [13] the rgbm_debug_flags word (negative: the process's current one, as rgbm_conv_plan takes it); read here: 1024 (PSP stage of rounds 1-5), 2048 (per-layer point MLP), 4096 (halo-tile conv0

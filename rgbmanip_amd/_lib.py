@@ -113,6 +113,8 @@ SIGNATURES = {
     "rgbm_adapose_create_realworld": (_i, [C.POINTER(_vp), _i, C.POINTER(WeightDesc), _i, _i]),
     "rgbm_adapose_create_v2": (_i, [C.POINTER(_vp), _i, C.POINTER(WeightDesc), _i, _i]),
     "rgbm_v2_point_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rgbm_adapose_create_v1": (_i, [C.POINTER(_vp), _i, C.POINTER(WeightDesc), _i, _i]),
+    "rgbm_v1_point_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rgbm_adapose_forward_realworld": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _i, _vp]),
     "rgbm_pose_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "rgbm_pts2d_to_coor": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp]),

@@ -42,8 +42,12 @@ class AdaPoseNet:
         # part and pose_mlp1 evaluated at the chosen pixels by one kernel, a size branch and no depth / rotation / translation (DESIGN.md
         # section 5s): forward() returns view*_nocs and view*_s, the other six outputs are NaN.  All four dtypes; hipGraph replay, Dropout2d,
         # per-sample BatchNorm3d, split_streams, the dense maps, forward_samples and the feature cache are refused.
-        if arch not in ("v5", "baseline", "realworld", "v2"):
-            raise ValueError(f"arch must be 'v5', 'baseline', 'realworld' or 'v2', got {arch!r}")
+        # arch "v1": the reference's StereoPoseNet (lib/network.py) from its state dict - v2's pointwise stereo part with a 32-channel
+        # fuse_conv whose result is a residual on the feature row (stage A, one kernel at the chosen pixels), v5's NOCS branch on those rows
+        # (stage B) and v5's pose branch on 128-channel rows: forward() returns nocs, r, t, s of both views, the
+        # depth outputs are NaN.  The refusals are those of arch "v2".
+        if arch not in ("v5", "baseline", "realworld", "v2", "v1"):
+            raise ValueError(f"arch must be 'v5', 'baseline', 'realworld', 'v2' or 'v1', got {arch!r}")
         self.arch = arch
         self.regress_pose = bool(regress_pose)
         if arch == "baseline":
@@ -58,11 +62,11 @@ class AdaPoseNet:
                             ("dtype fp16", _DTYPES[dtype] == _lib.F16)):
                 if on:
                     raise _lib.RgbmError(f"AdaPoseNet(arch='realworld'): {key} is not implemented for the real-world network")
-        if arch == "v2":
+        if arch in ("v2", "v1"):
             for key, on in (("graph", graph), ("dropout", dropout), ("norm_mode", norm_mode not in (0, "eval")), ("split_streams", split_streams),
                             ("cost_impl", cost_impl is not None), ("sparse_tail", sparse_tail is not None)):
                 if on:
-                    raise _lib.RgbmError(f"AdaPoseNet(arch='v2'): {key} is not implemented for the v2 network")
+                    raise _lib.RgbmError(f"AdaPoseNet(arch='{arch}'): {key} is not implemented for the {arch} network")
         # graph: forwards of at most `graph_max_batch` poses are replayed from a hipGraph captured per batch size
         # (rgbm_adapose_forward_graph): static input / output / workspace buffers per batch size, one hipGraphLaunch instead of ~150
         # launches — the small-batch deployment path (interface_v5.py:213-227 calls the network per env; cfg/task/open_cabinet.yaml
@@ -117,6 +121,8 @@ class AdaPoseNet:
             _lib.check(self.lib.rgbm_adapose_create_realworld(C.byref(self._h), device, arr, len(descs), self.dtype), "rgbm_adapose_create_realworld")
         elif arch == "v2":
             _lib.check(self.lib.rgbm_adapose_create_v2(C.byref(self._h), device, arr, len(descs), self.dtype), "rgbm_adapose_create_v2")
+        elif arch == "v1":
+            _lib.check(self.lib.rgbm_adapose_create_v1(C.byref(self._h), device, arr, len(descs), self.dtype), "rgbm_adapose_create_v1")
         else:
             _lib.check(self.lib.rgbm_adapose_create(C.byref(self._h), device, arr, len(descs), self.dtype, int(self.norm_mode)),
                        "rgbm_adapose_create")
@@ -268,8 +274,8 @@ class AdaPoseNet:
                 raise _lib.RgbmError("AdaPoseNet(arch='realworld'): forward needs coor1= and coor2= (the normalised point coordinates)")
         elif coor1 is not None or coor2 is not None:
             raise _lib.RgbmError("coor1 / coor2 are inputs of arch='realworld' only")
-        if self.arch == "v2" and (dense_depth or dense_nocs):
-            raise _lib.RgbmError("AdaPoseNet(arch='v2'): dense_depth / dense_nocs are not implemented for the v2 network")
+        if self.arch in ("v2", "v1") and (dense_depth or dense_nocs):
+            raise _lib.RgbmError(f"AdaPoseNet(arch='{self.arch}'): dense_depth / dense_nocs are not implemented for the {self.arch} network")
         if dense_depth or dense_nocs:
             assert stop_after == 0, "dense_depth / dense_nocs: the whole forward"
             return self._forward_dense((view1_img, view2_img, view1_choose, view2_choose, view1_proj, view2_proj, depth_values), stream,
@@ -553,6 +559,30 @@ class AdaPoseNet:
                                                _lib.ptr(fuse), _lib.ptr(planes), B, P, S, views, _lib.stream_ptr(stream)), "rgbm_v2_point_rows")
         self._last_v2 = (feat, ch, Pv, dep, homog)      # keep inputs alive until the stream has consumed them
         return rows, fuse, planes
+
+    def v1_point_rows(self, feat, choose, P_views, depth_values, views: int | None = None, stream=None, stage_b: bool = True):
+        """Stages A and B of the v1 heads alone with this net's weights (arch "v1"; rgbm_v1_point_rows): feat [2B, S, S, 32] float32 feature
+        maps (views = the view-1 crops, then the view-2 crops), choose [views, P] pixel indices, P_views [2B, 4, 4], depth_values [B, 24]
+        -> (fused [views, P, 32] = relu(feat + fuse_conv(planes)), nocs4 [views, P, 4], rows [views, P, 128] = the pose rows,
+        planes [views, P, 24] = volume_conv's).  stage_b=False: stage A alone, nocs4 and rows are None."""
+        feat = self._prep(feat, torch.float32)
+        ch = self._prep(choose, torch.int32)
+        Pv = self._prep(P_views, torch.float32)
+        dep = self._prep(depth_values, torch.float32)
+        V, S = feat.shape[0], feat.shape[1]
+        B = V // 2
+        views = ch.shape[0] if views is None else int(views)
+        P = ch.shape[1]
+        assert feat.shape == (2 * B, S, S, 32) and Pv.shape == (2 * B, 4, 4) and dep.shape == (B, 24) and views in (B, 2 * B), (feat.shape, ch.shape)
+        assert ch.shape == (views, P)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)      # noqa: E731
+        homog, fused, planes = new(2 * B, 12), new(views, P, 32), new(views, P, 24)
+        nocs4, rows, scratch = (new(views, P, 4), new(views, P, 128), new(views * P * 288)) if stage_b else (None, None, None)
+        _lib.check(self.lib.rgbm_v1_point_rows(self._h, _lib.ptr(feat), _lib.ptr(ch), _lib.ptr(Pv), _lib.ptr(dep), _lib.ptr(homog), _lib.ptr(fused),
+                                               _lib.ptr(nocs4), _lib.ptr(rows), _lib.ptr(planes), _lib.ptr(scratch), B, P, S, views,
+                                               _lib.stream_ptr(stream)), "rgbm_v1_point_rows")
+        self._last_v1 = (feat, ch, Pv, dep, homog, scratch)      # keep inputs and scratch alive until the stream has consumed them
+        return fused, nocs4, rows, planes
 
     def fetch(self, B: int, name: str, max_elems: int) -> torch.Tensor:
         """Debug/test access to a named intermediate of the last forward (fp32, flat)."""

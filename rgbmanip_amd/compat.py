@@ -9,6 +9,7 @@
     from models.pose_estimator.AdaPose.interface_baseline import AdaPoseEstimator_baseline    # train.py:38
     from models.pose_estimator.AdaPose.interface_realworld import AdaPoseEstimator_realworld  # train.py:246-248
     from models.pose_estimator.AdaPose.interface_v2 import AdaPoseEstimator_v2              # train.py:226-228
+    from models.pose_estimator.AdaPose.interface import AdaPoseEstimator                    # train.py:222-224
     from models.pose_estimator.base_estimator import BasePoseEstimator            # train.py:40, rl_pose.py:1
     from models.controller.base_controller import BaseController                  # train.py:20, rl_pose.py:3
     from algo.ppo.ppo import PPO / prepare_obs / RolloutStorage / ActorCritic     # rl_pose.py:10,494, rl.py:9, ppo.py:19-21
@@ -40,6 +41,8 @@ ALIASES = {
                                                           "BasePoseEstimator": "rgbmanip_amd.estimator:BasePoseEstimator"},
     "models.pose_estimator.AdaPose.interface_v2": {"AdaPoseEstimator_v2": "rgbmanip_amd.estimator:AdaPoseEstimator_v2",
                                                    "BasePoseEstimator": "rgbmanip_amd.estimator:BasePoseEstimator"},
+    "models.pose_estimator.AdaPose.interface": {"AdaPoseEstimator": "rgbmanip_amd.estimator:AdaPoseEstimator_v1",
+                                                "BasePoseEstimator": "rgbmanip_amd.estimator:BasePoseEstimator"},
     "models.controller.base_controller": {"BaseController": "rgbmanip_amd.control_interface:BaseController"},
     "models.controller.rl_pose": {"RLPoseController": "rgbmanip_amd.control_interface:RLPoseController",
                                   "ControlInterface": "rgbmanip_amd.control_interface:ControlInterface",

@@ -34,7 +34,8 @@ RL_CONTROLLER_CFG = {
 # direct_regression / use_depth are not read; the four keys above, hip_norm_mode: 1, hip_prepare: host and hip_dtype: fp16 are refused)
 # or "adapose_v2" (train.py:226-228: AdaPoseEstimator_v2, the StereoPoseNet of lib/network_v2.py behind a prepare step that draws the points
 # at native resolution, with the scaled PnP tail; direct_regression / use_depth are not read; the four keys above, hip_norm_mode: 1,
-# hip_prepare: host and hip_upload: windows are refused)
+# hip_prepare: host and hip_upload: windows are refused) or "adapose" (train.py:222-224: AdaPoseEstimator of interface.py, here
+# AdaPoseEstimator_v1 - the StereoPoseNet of lib/network.py behind AdaPoseEstimator_v2's prepare step and tail; the same keys are refused)
 def adapose_cfg(task_name="one_door_cabinet", checkpoint_path="downloads/pose_estimator/one_door_cabinet.pth", load=True, name="adapose_v5"):
     return {"name": name, "task_name": task_name, "load": load, "checkpoint_path": checkpoint_path, "img_size": 224,
             "use_depth": True, "n_pts": 1024, "direct_regression": True, "real_world": False}

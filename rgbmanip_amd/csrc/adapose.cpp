@@ -202,6 +202,39 @@ int AdaPose::create_v2(const StateDict& sd, int dtype_) {
   return 0;
 }
 
+// The v1 network (lib/network.py:39-218): PSPNet, instance_color, nocs_head and nocs_pts_mlp as v5's; volume_conv and fuse_conv (24 -> 32
+// -> 32) become the LDS image of v1_fused_points_kernel; the pose branch is v5's on 128-channel rows (create_pose at pose_in() == 128).
+int AdaPose::create_v1(const StateDict& sd, int dtype_) {
+  dtype = dtype_;
+  norm_mode = 0;
+  arch = ARCH_V1;
+  if (int rc = create_backbone(sd)) return rc;
+  if (int rc = create_point_heads(sd, true)) return rc;
+  {
+    V1HeadWeights m{};
+    std::vector<float> scale[3], shift[3];
+    static const int vc_in[3] = {32, 16, 8}, vc_out[3] = {16, 8, 1};
+    for (int l = 0; l < 3; ++l) {
+      const std::string p = "volume_conv." + std::to_string(l) + ".";
+      GET(w, p + "conv.weight");
+      RGBM_REQUIRE(w->numel() == (long long)vc_in[l] * vc_out[l], "weight shape " + p + "conv.weight");
+      if (int rc = bn_fold(sd, p + "bn.", vc_out[l], scale[l], shift[l])) return rc;
+      m.vc_w[l] = w->data; m.vc_scale[l] = scale[l].data(); m.vc_shift[l] = shift[l].data();
+    }
+    static const char* const fc[2] = {"fuse_conv.0", "fuse_conv.2"};
+    static const int fc_in[2] = {24, 32}, fc_out[2] = {32, 32};
+    for (int l = 0; l < 2; ++l) {
+      GET(fw, std::string(fc[l]) + ".weight"); GET(fb, std::string(fc[l]) + ".bias");
+      RGBM_REQUIRE(fw->numel() == (long long)fc_in[l] * fc_out[l] && fb->numel() == fc_out[l], std::string("weight shape ") + fc[l]);
+      m.fc_w[l] = fw->data; m.fc_b[l] = fb->data;
+    }
+    std::vector<float> table((size_t)kV1HeadFloats);
+    v1_head_pack(m, table.data());
+    if (upload_f32(table.data(), table.size(), v1_w)) return -2;
+  }
+  return create_pose(sd);
+}
+
 int AdaPose::create_backbone(const StateDict& sd) {
   const int E = dtype_chunk(dtype);
   img_cpad = E;                              // RGB padded to one 16-byte chunk
@@ -435,7 +468,7 @@ int AdaPose::plan(int B, const ForwardPaths& p, Arena& A, Buffers& bf) const {
   bf.H64 = (float*)A.alloc(VP * 64 * 4);
   bf.nocs4 = (float*)A.alloc(VP * 4 * 4);
   bf.N32 = (float*)A.alloc(VP * 32 * 4);
-  bf.PF96 = (float*)A.alloc(VP * pose_in() * 4);      // the pose rows: 96 channels, 128 for the real-world network
+  bf.PF96 = (float*)A.alloc(VP * pose_in() * 4);      // the pose rows: 96 channels, 128 for the real-world and the v1 network
   bf.PF96h = pose_dtype() == F16 ? A.alloc(VP * pose_in() * 2) : nullptr;
   bf.prob = (float*)A.alloc(VP * n_depth * 4);
   bf.depth = (float*)A.alloc(VP * 4);
@@ -479,7 +512,7 @@ int AdaPose::plan(int B, const ForwardPaths& p, Arena& A, Buffers& bf) const {
     A.release(m0);
     return 0;
   }
-  if (arch == ARCH_V2) {      // no cost volume: the per-point buffers above are all its heads need
+  if (arch == ARCH_V2 || arch == ARCH_V1) {      // no cost volume: the per-point buffers above are all its heads need
     bf.vol = bf.bn_scratch = nullptr;
     for (auto& c : bf.c3) c = nullptr;
     return 0;
@@ -766,6 +799,10 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
                "v2 network: the dense / maps forwards are not implemented (it has no probability volume, and its stereo part runs at the chosen pixels only)");
   RGBM_REQUIRE(arch != ARCH_V2 || call.dropout == Dropout::None, "v2 network: Dropout2d is not implemented");
   RGBM_REQUIRE(arch != ARCH_V2 || (call.coor1 == nullptr && call.coor2 == nullptr), "v2 network: coor1 / coor2 belong to the real-world network");
+  RGBM_REQUIRE(arch != ARCH_V1 || !(call.dense || call.depth_map || call.conf_map || call.nocs_map),
+               "v1 network: the dense / maps forwards are not implemented (it has no probability volume, and its stereo part runs at the chosen pixels only)");
+  RGBM_REQUIRE(arch != ARCH_V1 || call.dropout == Dropout::None, "v1 network: Dropout2d is not implemented");
+  RGBM_REQUIRE(arch != ARCH_V1 || (call.coor1 == nullptr && call.coor2 == nullptr), "v1 network: coor1 / coor2 belong to the real-world network");
   const ForwardPaths p = paths(B, call.dense);
   Buffers bf;
   if (int rc = open_workspace(B, p, workspace, workspace_size, 0, call.dense ? "forward_dense: " : "", call.dense ? " (rgbm_adapose_dense_workspace_bytes)" : "", bf)) return rc;
@@ -793,6 +830,7 @@ int AdaPose::forward(int B, const float* img1, const float* img2, const int* cho
   if (call.stop_after == 1) return 0;
   if (arch == ARCH_BASELINE) return heads_baseline(bf, B, out, call, p);
   if (arch == ARCH_V2) return heads_v2(bf, B, depths, out, call, p);
+  if (arch == ARCH_V1) return heads_v1(bf, B, depths, out, call, p);
   return heads(bf, B, depths, out, call, p);
 }
 
@@ -812,6 +850,7 @@ int AdaPose::forward_samples(int B, int S, const float* img1, const float* img2,
   RGBM_REQUIRE(arch != ARCH_BASELINE, "forward_samples: not implemented for the baseline network (it has no Dropout2d)");
   RGBM_REQUIRE(arch != ARCH_REALWORLD, "forward_samples: not implemented for the real-world network");
   RGBM_REQUIRE(arch != ARCH_V2, "forward_samples: not implemented for the v2 network (it has no Dropout2d)");
+  RGBM_REQUIRE(arch != ARCH_V1, "forward_samples: not implemented for the v1 network (it has no Dropout2d)");
   RGBM_REQUIRE(!(call.dense || call.depth_map || call.conf_map || call.nocs_map) && call.stop_after == 0, "forward_samples: no dense / maps form");
   RGBM_REQUIRE(call.dropout == Dropout::Draw || call.dropout == Dropout::Loaded,
                "forward_samples: Dropout2d is off and no masks are loaded (rgbm_adapose_set_dropout / rgbm_adapose_set_dropout_masks): the samples would be equal");
@@ -940,6 +979,48 @@ int AdaPose::heads_v2(const Buffers& bf, int B, const float* depths, const Outpu
   return 0;
 }
 
+// Stages A and B of the v1 heads (network.py:167-197), two launches: A waits on gathers and wants many waves per CU, B keeps 88 KB of
+// weights resident with one wave per SIMD.  Without the one-launch B (a point count that is no multiple of 64, or the point-MLP debug
+// flag) the same six layers run as the GEMM launches of v5's per-layer branch, and a column copy puts instance_color's output into the rows.
+int AdaPose::v1_stages(int feat_dtype, const void* feat, const float* homog, const float* depths, const int* choose, float* fused32, float* planes,
+                       float* nocs4, float* rows128, const V1Scratch& sc, int B, int P, int S, int Vh, bool fused_mlp, hipStream_t s) const {
+  RGBM_REQUIRE(v1_w && pmlp_table, "v1 network: no packed head tables");
+  if (int rc = launch_v1_fused_points(feat_dtype, v1_w.get<float>(), feat, homog, depths, choose, fused32, planes, 2 * B, B, P, n_depth, S, S, Vh, s)) return rc;
+  if (nocs4 == nullptr || rows128 == nullptr) return 0;      // stage A alone
+  const long long N = (long long)Vh * P;
+  if (fused_mlp) return launch_point_mlp_rows(pmlp_table.get<float>(), fused32, nocs4, rows128, N, s);
+  RGBM_REQUIRE(sc.h64a && sc.h128 && sc.h64b && sc.n32, "v1 network: the per-layer point branch needs its scratch");
+  // One view per launch: which GEMM kernel and K split a launch takes depends on its row count (conv_plan.cpp), and with it the rounding
+  // of its sums; launches of P rows each make a view's rows the same bits whether B or 2B views get heads.  6 Vh small launches: this is
+  // the stand-in path, the forward at 1024 points runs the one-launch kernel above.
+  for (long long v = 0; v < Vh; ++v) {
+    const long long r = v * P;
+    if (int rc = inst.run(fused32 + r * 32, sc.h64a + r * 64, 1, 1, 1, P, 64, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = nh[0].run(sc.h64a + r * 64, sc.h128 + r * 128, 1, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = nh[1].run(sc.h128 + r * 128, sc.h64b + r * 64, 1, 1, 1, P, 64, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = nh[2].run(sc.h64b + r * 64, nocs4 + r * 4, 1, 1, 1, P, 4, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = npm[0].run(nocs4 + r * 4, sc.n32 + r * 32, 1, 1, 1, P, 32, nullptr, 0, nullptr, 0, s)) return rc;
+    if (int rc = npm[1].run(sc.n32 + r * 32, rows128 + r * 128 + 64, 1, 1, 1, P, 128, nullptr, 0, nullptr, 0, s)) return rc;
+  }
+  return launch_copy_cols(sc.h64a, rows128, N, 64, 128, 64, s);
+}
+
+// Everything behind the PSPNet of the v1 network: stage A (fused32 in X0, volume_conv's 24 values in prob, for rgbm_adapose_fetch), stage
+// B (nocs4, the 128-channel pose rows in PF96), then v5's pose branch and staging unchanged.  This network has no depth: those outputs are NaN.
+int AdaPose::heads_v1(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const {
+  const int V = 2 * B, P = n_pts, S = img;
+  hipStream_t s = call.stream;
+  const FeatSource src = gather_source(bf, p);
+  const int Vh = view2_heads ? V : B;
+  const V1Scratch sc = {bf.X1, bf.H128, bf.H64, bf.N32};
+  if (int rc = v1_stages(src.dtype, src.feat, bf.homog, depths, bf.choose, bf.X0, bf.prob, bf.nocs4, bf.PF96, sc, B, P, S, Vh, p.point_mlp != 0, s)) return rc;
+  if (call.stop_after == 2) return 0;
+  if (int rc = pose_branch(bf, Vh, call, p)) return rc;
+  if (int rc = stage_out(bf, B, out, s)) return rc;
+  if (int rc = launch_fill_nan(out.depth1, (long long)B * P, s)) return rc;
+  return launch_fill_nan(out.depth2, (long long)B * P, s);
+}
+
 int AdaPose::nocs_map_of(const float* feat_f32, long long pixels, float* nocs_map, hipStream_t s) const {
   RGBM_REQUIRE(pmlp_table, "nocs_map: no point MLP table");
   return launch_dense_nocs(F32, pmlp_table.get<float>(), feat_f32, nocs_map, pixels, s);
@@ -1059,6 +1140,7 @@ int AdaPose::features(int V, const float* images, const int* slots, void* pool, 
   RGBM_REQUIRE(arch != ARCH_BASELINE, "baseline network: the feature cache is not implemented");
   RGBM_REQUIRE(arch != ARCH_REALWORLD, "real-world network: the feature cache is not implemented");
   RGBM_REQUIRE(arch != ARCH_V2, "v2 network: the feature cache is not implemented");
+  RGBM_REQUIRE(arch != ARCH_V1, "v1 network: the feature cache is not implemented");
   RGBM_REQUIRE(call.dropout == Dropout::None, "features: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would change "
                "what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "features: workspace must be 256-byte, pool 16-byte aligned");
@@ -1085,6 +1167,7 @@ int AdaPose::forward_cached(int B, const void* pool, int pool_records, const int
   RGBM_REQUIRE(arch != ARCH_BASELINE, "baseline network: the feature cache is not implemented");
   RGBM_REQUIRE(arch != ARCH_REALWORLD, "real-world network: the feature cache is not implemented");
   RGBM_REQUIRE(arch != ARCH_V2, "v2 network: the feature cache is not implemented");
+  RGBM_REQUIRE(arch != ARCH_V1, "v1 network: the feature cache is not implemented");
   RGBM_REQUIRE(call.dropout == Dropout::None, "forward_cached: Dropout2d is on (its masks are drawn per pose and per forward, so a kept feature map would "
                "change what the net computes); the feature cache needs set_dropout(0)");
   RGBM_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)pool & 15) == 0, "forward_cached: workspace must be 256-byte, pool 16-byte aligned");

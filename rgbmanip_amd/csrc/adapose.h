@@ -28,11 +28,15 @@ struct AdaPose {
   // ARCH_V2, network_v2.py's StereoPoseNet: no cost regularisation and no depth; the stereo part is pointwise (ref + warped over the planes
   // -> volume_conv -> fuse_conv, all 1x1), so it is evaluated at the chosen pixels only, together with pose_mlp1 (v2_head.hip); a 64 / 128
   // wide size branch behind it, no rotation or translation head (the depth / r / t outputs are NaN)
-  enum { ARCH_V5 = PATH_ARCH_V5, ARCH_BASELINE = PATH_ARCH_BASELINE, ARCH_REALWORLD = PATH_ARCH_REALWORLD, ARCH_V2 = PATH_ARCH_V2 };
+  // ARCH_V1, network.py's StereoPoseNet: v2's pointwise stereo part with a 32-channel fuse_conv whose result is a residual on the feature
+  // row (v1_head.hip, stage A), then v5's NOCS branch on those rows with instance_color's output kept as the first half of a 128-channel
+  // pose row (point_mlp_kernel's rows variant, stage B) and v5's pose branch at that width; no depth (the depth outputs are NaN)
+  enum { ARCH_V5 = PATH_ARCH_V5, ARCH_BASELINE = PATH_ARCH_BASELINE, ARCH_REALWORLD = PATH_ARCH_REALWORLD, ARCH_V2 = PATH_ARCH_V2, ARCH_V1 = PATH_ARCH_V1 };
   int arch = ARCH_V5;
   DevBuf v2_w;                    // v2: volume_conv (BatchNorm folded), fuse_conv and pose_mlp1 as v2_point_rows_kernel's LDS image (kernels.h: kV2HeadFloats)
+  DevBuf v1_w;                    // v1: volume_conv (BatchNorm folded) and fuse_conv as v1_fused_points_kernel's LDS image (kernels.h: kV1HeadFloats)
   int fusion() const { return arch == ARCH_REALWORLD ? FUSION_VARIANCE : FUSION_SUM; }      // how the plane sweep fuses a view with its warped partner
-  int pose_in() const { return arch == ARCH_REALWORLD ? 128 : 96; }                         // channels of a pose row (input of pose_mlp1.0)
+  int pose_in() const { return arch == ARCH_REALWORLD || arch == ARCH_V1 ? 128 : 96; }      // channels of a pose row (input of pose_mlp1.0)
   DevBuf prow_w;                  // real-world: camera_pts_mlp and nocs_pts_mlp as pose_rows_kernel's LDS image (kernels.h: kPoseRowsFloats)
   int regress_pose = 1;           // baseline only: 0 = no pose branch (the six r / t / s outputs are NaN)
   DevBuf vf_w;                    // baseline: the attention stack's 32 linears (view_fusion.h: kVfWeightFloats)
@@ -151,6 +155,7 @@ struct AdaPose {
   int create_baseline(const StateDict& sd, int dtype, int regress_pose);
   int create_realworld(const StateDict& sd, int dtype);
   int create_v2(const StateDict& sd, int dtype);
+  int create_v1(const StateDict& sd, int dtype);
   // the parts of a network create() / create_baseline() put together (dtype is set before)
   int create_backbone(const StateDict& sd);
   int create_cost(const StateDict& sd);
@@ -190,6 +195,12 @@ struct AdaPose {
   int heads(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const;
   int heads_baseline(const Buffers& bf, int B, const Outputs& out, const Call& call, const ForwardPaths& p) const;
   int heads_v2(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const;
+  int heads_v1(const Buffers& bf, int B, const float* depths, const Outputs& out, const Call& call, const ForwardPaths& p) const;
+  // stages A and B of the v1 heads on N = Vh * P points: feat (dtype) -> fused32 [N][32], nocs4 [N][4], rows128 [N][128]; `fused_mlp` picks
+  // B's one-launch kernel (N % 64 == 0) or the per-layer composition, which needs the scratch h64a [N][64], h128 [N][128], h64b [N][64], n32 [N][32]
+  struct V1Scratch { float *h64a, *h128, *h64b, *n32; };
+  int v1_stages(int feat_dtype, const void* feat, const float* homog, const float* depths, const int* choose, float* fused32, float* planes,
+                float* nocs4, float* rows128, const V1Scratch& sc, int B, int P, int S, int Vh, bool fused_mlp, hipStream_t s) const;
   // what the point heads gather from: the feature map of this forward and its element type (fp32 copy for split pairs, f16 with FEAT_F16)
   struct FeatSource { const void* feat; int dtype; };
   FeatSource gather_source(const Buffers& bf, const ForwardPaths& p) const;

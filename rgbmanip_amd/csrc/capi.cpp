@@ -106,6 +106,7 @@ static int finish_call(rgbm_adapose* h, int B, const AdaPose::Call& call, int rc
 static bool is_baseline(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_BASELINE; }
 static bool is_realworld(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_REALWORLD; }
 static bool is_v2(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_V2; }
+static bool is_v1(const rgbm_adapose* h) { return h != nullptr && h->net.arch == AdaPose::ARCH_V1; }
 
 static int forward_call(rgbm_adapose* h, const char* name, int B, const float* img1, const float* img2, const int32_t* choose1,
                         const int32_t* choose2, const float* P1, const float* P2, const float* depths, void* workspace, size_t workspace_bytes,
@@ -154,6 +155,7 @@ static int create_handle(rgbm_adapose_t** h, const char* name, int device, const
   if (int rc = arch == AdaPose::ARCH_BASELINE    ? obj->net.create_baseline(sd, dtype, mode)
                : arch == AdaPose::ARCH_REALWORLD ? obj->net.create_realworld(sd, dtype)
                : arch == AdaPose::ARCH_V2        ? obj->net.create_v2(sd, dtype)
+               : arch == AdaPose::ARCH_V1        ? obj->net.create_v1(sd, dtype)
                                                  : obj->net.create(sd, dtype, mode)) return rc;
   *h = obj.release();
   return 0;
@@ -189,6 +191,26 @@ int rgbm_v2_point_rows(rgbm_adapose_t* h, const float* feat, const int32_t* choo
   if (int rc = launch_homography(P_views, homog_scratch, 2 * B, B, (hipStream_t)stream)) return rc;
   return launch_v2_point_rows(F32, h->net.v2_w.get<float>(), feat, homog_scratch, depths, choose, rows, fuse64, planes, 2 * B, B, P, h->net.n_depth, S, S,
                               views, (hipStream_t)stream);
+}
+
+int rgbm_adapose_create_v1(rgbm_adapose_t** h, int device, const rgbm_weight_desc* w, int n_w, int dtype) {
+  return create_handle(h, "create_v1", device, w, n_w, dtype, AdaPose::ARCH_V1, 0);
+}
+
+int rgbm_v1_point_rows(rgbm_adapose_t* h, const float* feat, const int32_t* choose, const float* P_views, const float* depths, float* homog_scratch,
+                       float* fused32, float* nocs4, float* rows128, float* planes, float* layer_scratch, int B, int P, int S, int views,
+                       void* stream) {
+  RGBM_REQUIRE(is_v1(h) && h->net.v1_w, "v1_point_rows: the handle does not hold the v1 network (rgbm_adapose_create_v1)");
+  RGBM_REQUIRE(feat && choose && P_views && depths && homog_scratch && fused32 && B > 0 && P > 0 && (views == B || views == 2 * B), "v1_point_rows arguments");
+  RGBM_REQUIRE((nocs4 == nullptr) == (rows128 == nullptr), "v1_point_rows: nocs4 and rows128 come together (stage B writes both)");
+  const long long N = (long long)views * P;
+  const bool fused_mlp = N % 64 == 0 && !(g_debug_flags & DBG_POINT_MLP_R5);
+  RGBM_REQUIRE(nocs4 == nullptr || fused_mlp || layer_scratch, "v1_point_rows: the per-layer stage B needs layer_scratch (views * P * 288 floats)");
+  RGBM_REQUIRE((((uintptr_t)nocs4 | (uintptr_t)rows128 | (uintptr_t)layer_scratch) & 15) == 0, "v1_point_rows: nocs4, rows128 and layer_scratch must be 16-byte aligned");
+  AdaPose::V1Scratch sc{};
+  if (layer_scratch) sc = {layer_scratch, layer_scratch + N * 64, layer_scratch + N * 192, layer_scratch + N * 256};
+  if (int rc = launch_homography(P_views, homog_scratch, 2 * B, B, (hipStream_t)stream)) return rc;
+  return h->net.v1_stages(F32, feat, homog_scratch, depths, choose, fused32, planes, nocs4, rows128, sc, B, P, S, views, fused_mlp, (hipStream_t)stream);
 }
 
 int rgbm_adapose_forward_realworld(rgbm_adapose_t* h, int B, const float* img1, const float* img2, const int32_t* choose1, const int32_t* choose2,
@@ -246,9 +268,9 @@ int rgbm_adapose_set_chunk(rgbm_adapose_t* h, int max_chunk_views) {
 int rgbm_adapose_set_option(rgbm_adapose_t* h, const char* key, int value) {
   RGBM_REQUIRE(h && key, "set_option arguments");
   const std::string k = key;
-  if (is_baseline(h) || is_v2(h))
+  if (is_baseline(h) || is_v2(h) || is_v1(h))
     for (const char* cv : {"cost_impl", "sparse_tail", "sparse_dec", "sweep_f16", "igemm_conv6"})
-      RGBM_REQUIRE(k != cv, "option " + k + " belongs to the cost volume, which the " + (is_v2(h) ? "v2" : "baseline") + " network does not have");
+      RGBM_REQUIRE(k != cv, "option " + k + " belongs to the cost volume, which the " + (is_v2(h) ? "v2" : is_v1(h) ? "v1" : "baseline") + " network does not have");
   if (is_realworld(h))
     RGBM_REQUIRE(!(k == "sweep_f16" && value != 0), "option sweep_f16 does not exist for the real-world network (its variance volume has no f16 form)");
   if (k == "max_chunk") { RGBM_REQUIRE(value > 0, "max_chunk"); h->net.max_chunk = value; }
@@ -271,6 +293,7 @@ int rgbm_adapose_set_dropout(rgbm_adapose_t* h, float p, uint64_t seed) {
   RGBM_REQUIRE(!(is_baseline(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the baseline network");
   RGBM_REQUIRE(!(is_realworld(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the real-world network");
   RGBM_REQUIRE(!(is_v2(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the v2 network");
+  RGBM_REQUIRE(!(is_v1(h) && p > 0.f), "set_dropout: Dropout2d is not implemented for the v1 network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (!h->net.drop_state) RGBM_CHECK_HIP(hipMalloc(h->net.drop_state.out(), 2 * sizeof(unsigned long long)));
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // every forward issued before this call has drawn its masks
@@ -297,6 +320,7 @@ int rgbm_adapose_set_dropout_masks(rgbm_adapose_t* h, int B, const float* masks_
   RGBM_REQUIRE(!is_baseline(h), "set_dropout_masks: Dropout2d is not implemented for the baseline network");
   RGBM_REQUIRE(!is_realworld(h), "set_dropout_masks: Dropout2d is not implemented for the real-world network");
   RGBM_REQUIRE(!is_v2(h), "set_dropout_masks: Dropout2d is not implemented for the v2 network");
+  RGBM_REQUIRE(!is_v1(h), "set_dropout_masks: Dropout2d is not implemented for the v1 network");
   RGBM_CHECK_HIP(hipSetDevice(h->device));
   if (int rc = ensure_dropout_capacity(h, B)) return rc;
   RGBM_CHECK_HIP(hipDeviceSynchronize());      // no forward in flight reads the buffer any more
@@ -409,6 +433,7 @@ int rgbm_adapose_feature_bytes(rgbm_adapose_t* h, size_t* bytes) {
   RGBM_REQUIRE(h && bytes, "feature_bytes arguments");
   RGBM_REQUIRE(!is_baseline(h), "feature_bytes: the feature cache is not implemented for the baseline network");
   RGBM_REQUIRE(!is_v2(h), "feature_bytes: the feature cache is not implemented for the v2 network");
+  RGBM_REQUIRE(!is_v1(h), "feature_bytes: the feature cache is not implemented for the v1 network");
   *bytes = h->net.feature_bytes();
   return 0;
 }
@@ -417,6 +442,7 @@ int rgbm_adapose_features_workspace_bytes(rgbm_adapose_t* h, int V, size_t* byte
   RGBM_REQUIRE(h && bytes && V > 0, "features_workspace_bytes arguments");
   RGBM_REQUIRE(!is_baseline(h), "features_workspace_bytes: the feature cache is not implemented for the baseline network");
   RGBM_REQUIRE(!is_v2(h), "features_workspace_bytes: the feature cache is not implemented for the v2 network");
+  RGBM_REQUIRE(!is_v1(h), "features_workspace_bytes: the feature cache is not implemented for the v1 network");
   *bytes = h->net.features_workspace_bytes(V);
   return 0;
 }
@@ -425,6 +451,7 @@ int rgbm_adapose_features(rgbm_adapose_t* h, int V, const float* img, const int3
                           void* workspace, size_t workspace_bytes, void* stream) {
   RGBM_REQUIRE(!is_baseline(h), "features: the feature cache is not implemented for the baseline network");
   RGBM_REQUIRE(!is_v2(h), "features: the feature cache is not implemented for the v2 network");
+  RGBM_REQUIRE(!is_v1(h), "features: the feature cache is not implemented for the v1 network");
   AdaPose::Call call;      // a handle with Dropout2d on (or masks loaded) is refused by the net
   if (int rc = prepare_call(h, "features", 0, {img, slots_dev, pool, workspace}, stream, &call)) return rc;
   return h->net.features(V, img, slots_dev, pool, pool_records, workspace, workspace_bytes, call);
@@ -439,6 +466,7 @@ int rgbm_adapose_forward_cached(rgbm_adapose_t* h, int B, const void* pool, int 
                                 const float* depths, void* workspace, size_t workspace_bytes, const rgbm_adapose_out* out, void* stream) {
   RGBM_REQUIRE(!is_baseline(h), "forward_cached: the feature cache is not implemented for the baseline network");
   RGBM_REQUIRE(!is_v2(h), "forward_cached: the feature cache is not implemented for the v2 network");
+  RGBM_REQUIRE(!is_v1(h), "forward_cached: the feature cache is not implemented for the v1 network");
   AdaPose::Call call;
   if (int rc = prepare_call(h, "forward_cached", B, {pool, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, out}, stream, &call)) return rc;
   return h->net.forward_cached(B, pool, pool_records, slot1_dev, slot2_dev, choose1, choose2, P1, P2, depths, workspace, workspace_bytes,
@@ -450,6 +478,7 @@ int rgbm_adapose_samples_workspace_bytes(rgbm_adapose_t* h, int B, int S, size_t
   RGBM_REQUIRE(S >= 1 && (long long)S * B <= (1 << 20), "samples_workspace_bytes: S >= 1 samples");
   RGBM_REQUIRE(!is_baseline(h), "samples_workspace_bytes: forward_samples is not implemented for the baseline network");
   RGBM_REQUIRE(!is_v2(h), "samples_workspace_bytes: forward_samples is not implemented for the v2 network");
+  RGBM_REQUIRE(!is_v1(h), "samples_workspace_bytes: forward_samples is not implemented for the v1 network");
   *bytes = h->net.samples_workspace_bytes(B, S);
   return 0;
 }
@@ -460,6 +489,7 @@ int rgbm_adapose_forward_samples(rgbm_adapose_t* h, int B, int S, const float* i
   RGBM_REQUIRE(h != nullptr, "forward_samples arguments");
   RGBM_REQUIRE(!is_baseline(h), "forward_samples: not implemented for the baseline network (it has no Dropout2d)");
   RGBM_REQUIRE(!is_v2(h), "forward_samples: forward_samples is not implemented for the v2 network");
+  RGBM_REQUIRE(!is_v1(h), "forward_samples: forward_samples is not implemented for the v1 network");
   RGBM_REQUIRE(B > 0 && S >= 1 && (long long)S * B <= (1 << 20), "forward_samples: B >= 1 poses and S >= 1 samples");
   RGBM_REQUIRE(h->net.drop_p > 0.f || h->drop_explicit, "forward_samples: Dropout2d is off and no masks are loaded (rgbm_adapose_set_dropout / "
                "rgbm_adapose_set_dropout_masks): the samples would be equal");
@@ -511,6 +541,7 @@ int rgbm_adapose_forward_graph(rgbm_adapose_t* h, int B, const float* img1, cons
   RGBM_REQUIRE(!is_baseline(h), "forward_graph: hipGraph replay is not implemented for the baseline network");
   RGBM_REQUIRE(!is_realworld(h), "forward_graph: hipGraph replay is not implemented for the real-world network");
   RGBM_REQUIRE(!is_v2(h), "forward_graph: hipGraph replay is not implemented for the v2 network");
+  RGBM_REQUIRE(!is_v1(h), "forward_graph: hipGraph replay is not implemented for the v1 network");
   AdaPose::Call call;
   // the in-library profiler records events around launches: not capturable, and a timing run wants the launches themselves
   // masks loaded by rgbm_adapose_set_dropout_masks are for one forward: not captured
@@ -625,6 +656,11 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   else if (nm == "v2_rows" && is_v2(h)) { src = bf.X1; cnt = V * P * 64; dt = F32; }
   else if (nm == "v2_fuse" && is_v2(h)) { src = bf.H64; cnt = V * P * 64; dt = F32; }
   else if (nm == "v2_planes" && is_v2(h)) { src = bf.prob; cnt = V * P * D; dt = F32; }
+  // the v1 network's stages A and B (v1_head.hip, point_mlp_kernel's rows variant): the residual rows, volume_conv's plane values and the
+  // 128-channel pose rows (split pairs behind a whole forward of a split-pair net, as pf96)
+  else if (nm == "v1_fused" && is_v1(h)) { src = bf.X0; cnt = V * P * 32; dt = F32; }
+  else if (nm == "v1_planes" && is_v1(h)) { src = bf.prob; cnt = V * P * D; dt = F32; }
+  else if (nm == "v1_rows" && is_v1(h)) { src = bf.PF96; cnt = V * P * 128; dt = n.pose_dtype() == BF16X3 ? BF16X3 : F32; }
   else if (nm == "fused1" && bf.fused) { src = bf.fused; cnt = (size_t)B * P * 32; dt = F32; }
   else if (nm == "fused2" && bf.fused) { src = bf.fused + (size_t)B * P * 32; cnt = (size_t)B * P * 32; dt = F32; }
   // the taps of the cost regularisation: the outputs of these rows of kCost3d
@@ -638,6 +674,9 @@ int rgbm_adapose_fetch(rgbm_adapose_t* h, int B, void* workspace, const char* na
   if (is_v2(h))      // neither the cost-volume buffers nor v5's pose buffers are written in this handle's workspace
     RGBM_REQUIRE(nm == "feat" || nm == "homog" || nm == "v2_rows" || nm == "v2_fuse" || nm == "v2_planes" || nm == "layer4" || nm == "cat" || nm == "u1" ||
                  nm == "u2", "tap '" + nm + "' does not exist in the v2 network");
+  if (is_v1(h))      // no cost-volume buffers in this handle's workspace
+    RGBM_REQUIRE(nm == "feat" || nm == "homog" || nm == "v1_fused" || nm == "v1_planes" || nm == "v1_rows" || nm == "pf2" || nm == "r6" || nm == "layer4" ||
+                 nm == "cat" || nm == "u1" || nm == "u2", "tap '" + nm + "' does not exist in the v1 network");
   RGBM_REQUIRE(src != nullptr, "unknown intermediate name: " + nm);
   // with sparse cost regularisation c0..c5 / u7 / u9 are written only inside the chosen pixels' dependency cones (and c6 is computed
   // from them): the rest of these tensors is whatever the workspace held, so a tap of them is refused instead of returned partly stale

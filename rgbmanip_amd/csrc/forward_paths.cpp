@@ -13,7 +13,7 @@ ForwardPaths forward_paths(const PathFacts& f) {
   const bool eval_bn = f.norm_mode == 0;
   // debug flag 4096: the halo-tile conv0 instead of either depth-sweeping kernel, in every storage type (the runtime way out should a
   // compiler update bring the sweep kernels' hand-counted asm gathers out of step)
-  const bool v2 = f.arch == PATH_ARCH_V2;      // no cost regularisation: nothing below may depend on its options
+  const bool v2 = f.arch == PATH_ARCH_V2 || f.arch == PATH_ARCH_V1;      // no cost regularisation: nothing below may depend on its options
   const bool sweep = !v2 && f.cost_impl == 3 && !(f.flags & PATH_FLAG_TILE_CONV0);
 
   // ---- PSPNet ----
@@ -25,14 +25,14 @@ ForwardPaths forward_paths(const PathFacts& f) {
   p.up2 = (f.upconv >> 1) & 1;
   p.up3 = (f.upconv & 4) && f.tail_ready ? UP3_TAIL_KERNEL : f.fuse_final ? UP3_FUSED_FINAL : UP3_TWO_LAUNCHES;
   // sweep_w_f16 exists only for conv0 weights that f16 can hold, tail_f16_ready only for such `final` weights: otherwise all bf16
-  // (the v2 network only gathers from the map: nothing of it reads split pairs)
+  // (the v2 and v1 networks only gather from the map: nothing of them reads split pairs)
   if (x3 && (v2 || (sweep && f.sweep_w && eval_bn))) p.feat_form = FEAT_F32_ONLY;
   else if (f.arch != PATH_ARCH_REALWORLD && f.dtype == RGBM_BF16 && f.sweep_f16 && sweep && f.sweep_w_f16 && eval_bn && p.up3 == UP3_TAIL_KERNEL && f.tail_f16_ready) p.feat_form = FEAT_F16;
   else p.feat_form = FEAT_STORAGE;
   // split pairs: everything that GATHERS from the feature map (plane sweep, point heads) reads a plain fp32 copy of it
   p.feat_copy = x3 && p.feat_form != FEAT_F32_ONLY;
 
-  // ---- cost regularisation (the baseline and the v2 network have none) ----
+  // ---- cost regularisation (the baseline, the v2 and the v1 network have none) ----
   if (f.arch != PATH_ARCH_BASELINE && !v2) {
     p.cost_body = !eval_bn ? COST_BN_PER_SAMPLE : f.cost_impl == 0 ? COST_GENERIC : COST_TILES;
     p.vol = !(f.cost_impl >= 2 && eval_bn);      // the fused-warp and depth-sweeping conv0 never materialise it

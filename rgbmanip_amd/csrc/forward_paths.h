@@ -20,7 +20,9 @@ struct PathFacts {
 // feature map and no packed-f16 sweep for it (forward_paths never answers FEAT_F16 / CONV0_SWEEP16_F16)
 // PATH_ARCH_V2: network_v2.py's StereoPoseNet - PSPNet and point heads as v5, no 3-D paths (as for the baseline); its pose branch is a
 // kernel of its own (v2_head.hip), so pose_mlp is never answered 1
-enum { PATH_ARCH_V5 = 0, PATH_ARCH_BASELINE = 1, PATH_ARCH_REALWORLD = 2, PATH_ARCH_V2 = 3 };
+// PATH_ARCH_V1: network.py's StereoPoseNet - as PATH_ARCH_V2 in front of the heads (no 3-D paths, split pairs write the plain fp32 map
+// only); point_mlp follows v5's rule (it picks stage B's one-launch kernel); its pose rows are 128 wide, so pose_mlp is never answered 1
+enum { PATH_ARCH_V5 = 0, PATH_ARCH_BASELINE = 1, PATH_ARCH_REALWORLD = 2, PATH_ARCH_V2 = 3, PATH_ARCH_V1 = 4 };
 enum { STEM_GENERIC = 0, STEM_FUSED = 1 };
 enum { PSP_POOLED_GEMMS = 0, PSP_ONE_LAUNCH = 1, PSP_ROUND5 = 2 };
 enum { UP3_TWO_LAUNCHES = 0, UP3_FUSED_FINAL = 1, UP3_TAIL_KERNEL = 2 };

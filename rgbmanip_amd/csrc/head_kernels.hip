@@ -70,7 +70,9 @@ constexpr int ACT_A = 128 * 16, ACT_B = 64 * 16;          // floats of a wave's 
 constexpr size_t LDS_BYTES = (size_t)(W_FLOATS + B_FLOATS + 4 * (ACT_A + ACT_B)) * sizeof(float);
 }  // namespace pmlp
 
-template <int L, bool G4 = true>      // G4 = false (dense_nocs_kernel): layer 3 keeps its tile in LDS only, the caller stores it
+// G4 = false (dense_nocs_kernel): layer 3 keeps its tile in LDS only, the caller stores it
+// S0 = true (the rows variant of point_mlp_kernel): layer 0 also stores its tile to gout64, as layer 5 does
+template <int L, bool G4 = true, bool S0 = false>
 __device__ __forceinline__ void pmlp_layer(const float* __restrict__ wl, const float* __restrict__ bl, const float* __restrict__ xin,
                                            float* __restrict__ xout, int lane, float* __restrict__ gout4, float* __restrict__ gout64, int ldg) {
   using namespace pmlp;
@@ -109,6 +111,7 @@ __device__ __forceinline__ void pmlp_layer(const float* __restrict__ wl, const f
       if (L == 3 && G4) {
         if (lane < 16) *reinterpret_cast<float4*>(gout4 + (long long)lane * 4) = make_float4(v[0], v[1], v[2], v[3]);      // nocs4: channels 0..3 of the tile
       }
+      if (L == 0 && S0) *reinterpret_cast<float4*>(gout64 + (long long)(lane & 15) * ldg + ch) = make_float4(v[0], v[1], v[2], v[3]);
       if (L == NL - 1) {
         *reinterpret_cast<float4*>(gout64 + (long long)(lane & 15) * ldg + ch) = make_float4(v[0], v[1], v[2], v[3]);
       } else {
@@ -119,7 +122,10 @@ __device__ __forceinline__ void pmlp_layer(const float* __restrict__ wl, const f
   }
 }
 
-template <typename TF>
+// ROWS = 1 (stage B of the v1 network, launch_point_mlp_rows): the layer-0 input is not gathered from a map but read from contiguous fp32
+// rows d.feat [N][32] (no choose), and layer 0's tile (instance_color's output) is stored to d.pf[0 .. 63] beside layer 5's at
+// d.pf[64 .. 127] (ldpf = 128): the v1 pose row is cat(instance_color, nocs_pts_mlp) (network.py:196).
+template <typename TF, int ROWS = 0>
 __global__ __launch_bounds__(256) void point_mlp_kernel(const PointMlpDesc d) {
   using namespace pmlp;
   extern __shared__ __attribute__((aligned(16))) float pm_lds[];
@@ -140,20 +146,25 @@ __global__ __launch_bounds__(256) void point_mlp_kernel(const PointMlpDesc d) {
     for (int r = 0; r < 2; ++r) {
       const int q = lane + 64 * r, pt = q >> 3, c4 = q & 7;
       const long long vp = p0 + pt;
-      const long long v = vp / d.P;
-      const int pix = d.choose[vp];
       float x[4];
-      load4(feat + (v * d.HW + pix) * 32 + c4 * 4, x);
+      if (ROWS) {
+        load4(feat + vp * 32 + c4 * 4, x);      // the wave's 16 rows are one contiguous 2 KB run
+      } else {
+        const long long v = vp / d.P;
+        const int pix = d.choose[vp];
+        load4(feat + (v * d.HW + pix) * 32 + c4 * 4, x);
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) xa[(c4 * 4 + e) * 16 + pt] = x[e];
     }
     // (wave-private buffers: a wave's LDS writes are seen by its own later reads in program order, no barrier)
-    pmlp_layer<0>(wl, bl, xa, xb, lane, nullptr, nullptr, 0);
+    if (ROWS) pmlp_layer<0, true, true>(wl, bl, xa, xb, lane, nullptr, d.pf + p0 * d.ldpf, d.ldpf);
+    else pmlp_layer<0>(wl, bl, xa, xb, lane, nullptr, nullptr, 0);
     pmlp_layer<1>(wl, bl, xb, xa, lane, nullptr, nullptr, 0);
     pmlp_layer<2>(wl, bl, xa, xb, lane, nullptr, nullptr, 0);
     pmlp_layer<3>(wl, bl, xb, xa, lane, d.nocs4 + p0 * 4, nullptr, 0);
     pmlp_layer<4>(wl, bl, xa, xb, lane, nullptr, nullptr, 0);
-    pmlp_layer<5>(wl, bl, xb, xa, lane, nullptr, d.pf + p0 * d.ldpf, d.ldpf);
+    pmlp_layer<5>(wl, bl, xb, xa, lane, nullptr, d.pf + p0 * d.ldpf + (ROWS ? 64 : 0), d.ldpf);
   }
 }
 
@@ -197,6 +208,21 @@ int launch_point_mlp(int feat_dtype, const PointMlpDesc& d, hipStream_t s) {
     hipLaunchKernelGGL(point_mlp_kernel<bx3_t>, dim3(grid), dim3(256), pmlp::LDS_BYTES, s, d);
   else
     hipLaunchKernelGGL(point_mlp_kernel<float>, dim3(grid), dim3(256), pmlp::LDS_BYTES, s, d);
+  RGBM_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_point_mlp_rows(const float* table, const float* x, float* nocs4, float* pf, long long N, hipStream_t s) {
+  RGBM_REQUIRE(table && x && nocs4 && pf && N > 0 && N % 64 == 0, "point MLP on rows: N must be a multiple of 64");
+  RGBM_REQUIRE((((uintptr_t)x | (uintptr_t)nocs4 | (uintptr_t)pf | (uintptr_t)table) & 15) == 0, "point MLP on rows: the buffers must be 16-byte aligned");
+  PointMlpDesc d{};
+  d.table = table; d.feat = x; d.choose = nullptr; d.nocs4 = nocs4; d.pf = pf; d.ldpf = 128; d.P = 1; d.HW = 0; d.N = N;
+  int n_cu = 0;
+  if (int rc = persistent_grid_cus(&n_cu)) return rc;
+  const long long ntile = N / 64;
+  const unsigned grid = (unsigned)(ntile < n_cu ? ntile : n_cu);
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(point_mlp_kernel<float, 1>), (int)pmlp::LDS_BYTES)) return rc;
+  hipLaunchKernelGGL((point_mlp_kernel<float, 1>), dim3(grid), dim3(256), pmlp::LDS_BYTES, s, d);
   RGBM_CHECK_HIP(hipGetLastError());
   return 0;
 }

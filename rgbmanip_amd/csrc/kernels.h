@@ -144,6 +144,22 @@ constexpr int kV2HeadFloats = (16 * 32 + 16) + (8 * 16 + 8) + (8 + 4) + (24 * 32
 void v2_head_pack(const V2HeadWeights& m, float* table);
 int launch_v2_point_rows(int feat_dtype, const float* table, const void* feat, const float* homog, const float* depths, const int* choose,
                          float* rows, float* fuse64, float* planes, int V, int B, int P, int D, int H, int W, int Vh, hipStream_t s);
+// v1_head.hip: stage A of the v1 network's heads (network.py:167-177) in one launch.  For point p of view v < Vh (views and partners as
+// above): planes = volume_conv(ref + warped) over the D = 24 planes, fused32 = relu(ref + fuse_conv.2(relu(fuse_conv.0(planes)))) ->
+// fused32 [Vh * P][32] fp32, and planes [Vh * P][24] when not null.  feat, fused32 and planes 16-byte aligned.
+struct V1HeadWeights {         // host fp32, [Cout][Cin] row-major
+  const float* vc_w[3];        // volume_conv.{0,1,2}.conv.weight: 16 x 32, 8 x 16, 1 x 8
+  const float* vc_scale[3];    // their eval BatchNorm as scale / shift per output channel
+  const float* vc_shift[3];
+  const float *fc_w[2], *fc_b[2];      // fuse_conv.0 (32 x 24), fuse_conv.2 (32 x 32)
+};
+constexpr int kV1HeadFloats = (16 * 32 + 16) + (8 * 16 + 8) + (8 + 4) + (24 * 32 + 32) + (32 * 32 + 32);
+void v1_head_pack(const V1HeadWeights& m, float* table);
+int launch_v1_fused_points(int feat_dtype, const float* table, const void* feat, const float* homog, const float* depths, const int* choose,
+                           float* fused32, float* planes, int V, int B, int P, int D, int H, int W, int Vh, hipStream_t s);
+// head_kernels.hip: stage B, the six layers of point_mlp_kernel on contiguous fp32 rows x [N][32] (no choose, no map), N % 64 == 0 ->
+// nocs4 [N][4] and the pose rows pf [N][128]: channels 0-63 instance_color's output (layer 0), 64-127 nocs_pts_mlp's (layer 5)
+int launch_point_mlp_rows(const float* table, const float* x, float* nocs4, float* pf, long long N, hipStream_t s);
 // coor[i] = (pts2d[i][0] / W, pts2d[i][1] / H) in IEEE float32 division (interface_realworld.py:264-269), n points
 int launch_pts2d_to_coor(const float* pts2d, float* coor, long long n, int W, int H, hipStream_t s);
 int launch_ortho6d(const float* r6, float* R, int V, hipStream_t s);

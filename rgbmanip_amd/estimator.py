@@ -1044,21 +1044,23 @@ class AdaPoseEstimator_v2(AdaPoseEstimator_v5):
     What is not implemented for this network raises, naming the key."""
 
     _UNSUPPORTED = ("hip_feature_cache", "hip_dropout", "hip_as_shipped", "hip_graph")
+    _ARCH = "v2"      # the AdaPoseNet arch behind this class and the name its messages carry (AdaPoseEstimator_v1 overrides it)
 
     def __init__(self, env, cfg, logger, state_dict=None, dtype=None, device=0, net=None):
+        arch, who = self._ARCH, "AdaPoseEstimator_" + self._ARCH
         for key in self._UNSUPPORTED:
             if cfg.get(key, False):
-                raise ValueError(f"AdaPoseEstimator_v2: cfg key {key} is not implemented for the v2 network")
+                raise ValueError(f"{who}: cfg key {key} is not implemented for the {arch} network")
         if cfg.get("hip_norm_mode", "eval") not in ("eval", 0):
-            raise ValueError("AdaPoseEstimator_v2: cfg key hip_norm_mode: per-sample BatchNorm3d is not implemented for the v2 network (it would "
+            raise ValueError(f"{who}: cfg key hip_norm_mode: per-sample BatchNorm3d is not implemented for the {arch} network (it would "
                              "need the whole volume, which this network's kernel never builds)")
         if cfg.get("hip_prepare", "device") != "device":
-            raise ValueError('AdaPoseEstimator_v2: cfg key hip_prepare: only "device" is implemented for the v2 network')
+            raise ValueError(f'{who}: cfg key hip_prepare: only "device" is implemented for the {arch} network')
         if cfg.get("hip_upload", "frames") != "frames":
-            raise ValueError('AdaPoseEstimator_v2: cfg key hip_upload: only "frames" is implemented for the v2 network (the points are drawn '
+            raise ValueError(f'{who}: cfg key hip_upload: only "frames" is implemented for the {arch} network (the points are drawn '
                              "from the whole frame's mask)")
-        if net is not None and getattr(net, "arch", "v5") != "v2":
-            raise ValueError("AdaPoseEstimator_v2: the shared net must be an AdaPoseNet(arch='v2')")
+        if net is not None and getattr(net, "arch", "v5") != arch:
+            raise ValueError(f"{who}: the shared net must be an AdaPoseNet(arch='{arch}')")
         super().__init__(env, cfg, logger, state_dict=state_dict, dtype=dtype, device=device, net=net)
 
     def _synthetic_state_dict(self):
@@ -1081,7 +1083,7 @@ class AdaPoseEstimator_v2(AdaPoseEstimator_v5):
         return postprocess_pnp_scaled(pred["view1_nocs"], pts2d[0], pred["view1_s"], K, E1, seed=int(self.cfg.get("hip_ransac_seed", 0)))[0]
 
     def _refused(self, name, why):
-        raise NotImplementedError(f"AdaPoseEstimator_v2.{name}: {why} is not implemented for the v2 network")
+        raise NotImplementedError(f"AdaPoseEstimator_{self._ARCH}.{name}: {why} is not implemented for the {self._ARCH} network")
 
     def estimate_samples(self, *a, **k):
         self._refused("estimate_samples", "Dropout2d (cfg hip_dropout / hip_as_shipped), so there is nothing to sample,")
@@ -1112,3 +1114,20 @@ class AdaPoseEstimator_v2(AdaPoseEstimator_v5):
 
     def estimate_cloud_views_device(self, *a, **k):
         self._refused("estimate_cloud_views_device", "the dense forward")
+
+
+class AdaPoseEstimator_v1(AdaPoseEstimator_v2):
+    """`pose_estimator.name: adapose` (`interface.py`, `train.py:222-224`): the v1 `StereoPoseNet` (lib/network.py)
+    behind the code of `AdaPoseEstimator_v2` - `interface.py` equals `interface_v2.py` line for line apart from the class name and the
+    network import: the points drawn at native resolution, the PnP tail scaled by the regressed size, the unused helper call that is not
+    made.  The network also regresses r and t for both views; the tail reads view 1's NOCS, pixels and size only, so `hip_view2_heads`
+    defaults to False here too.  The same cfg keys are refused, under this class's name."""
+
+    _ARCH = "v1"
+
+    def _synthetic_state_dict(self):
+        from . import synth
+        return synth.v1_state_dict(seed=0)
+
+    def _build_net(self, state_dict, device, norm_mode, drop_p, drop_seed, options):
+        return AdaPoseNet(state_dict, dtype=self.dtype, device=device, options=options, arch="v1")

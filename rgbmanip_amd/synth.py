@@ -193,6 +193,30 @@ def v2_state_dict(seed: int = 0, prefix: str = "") -> "OrderedDict[str, np.ndarr
     return _draw_state_dict(v2_schema(), seed, prefix)
 
 
+def v1_schema():
+    """(name, shape, kind) of StereoPoseNet (lib/network.py:39-117) in its state_dict order: v5's PSPNet and instance_color, v2's
+    volume_conv and fuse_conv (the latter ending in 32 channels), then v5's nocs_head, nocs_pts_mlp and pose branch with pose_mlp1.0
+    reading 128 channels.  volume_conv and fuse_conv carry the v2 draw's offsets (V2_VC2_BN_GAIN, V2_VC2_BN_SHIFT, V2_FUSE_GAIN), for
+    the same reason; the golden generator (tools/make_goldens.py: gen_adapose_v1) asserts the fixture conditions on the golden batch."""
+    v5 = adapose_schema()
+    by_prefix = lambda *pre: [e for e in v5 if e[0].startswith(pre)]      # noqa: E731
+    s = by_prefix("img_extractor.", "instance_color.")
+    s += [e for e in v2_schema() if e[0].startswith("volume_conv.")]
+    for i, (a, b) in zip((0, 2), ((24, 32), (32, 32))):
+        s.append((f"fuse_conv.{i}.weight", (b, a, 1, 1), "v2_fw"))
+        s.append((f"fuse_conv.{i}.bias", (b,), "b:%d" % a))
+    s += by_prefix("nocs_head.", "nocs_pts_mlp.")
+    s += [(n, (128, 128, 1) if n == "pose_mlp1.0.weight" else shp, k) for n, shp, k in by_prefix("pose_mlp1.")]
+    s += by_prefix("pose_mlp2.", "rotation_estimator.", "translation_estimator.", "size_estimator.")
+    return s
+
+
+def v1_state_dict(seed: int = 0, prefix: str = "") -> "OrderedDict[str, np.ndarray]":
+    """Synthetic checkpoint of the v1 network.  The generator is keyed by the tensor's name, so the tensors it shares with
+    `adapose_state_dict(seed)` and `v2_state_dict(seed)` are the same draws, and both return what they did."""
+    return _draw_state_dict(v1_schema(), seed, prefix)
+
+
 def realworld_coor(B: int, seed: int = 0, n_pts: int = N_PTS, W: int = 640, H: int = 480):
     """Chosen points' pixel coordinates in a W x H frame for the real-world network's goldens: (pts2d1, pts2d2) [B, n_pts, 2] float32
     with whole-pixel values (what prepare_model_input emits), and the normalised (coor1, coor2) = pts2d / (W, H) in float32."""

@@ -375,6 +375,83 @@ def gen_adapose_v2(out_dir):
         print(k, tuple(v.shape), float(v.abs().mean()), bool(torch.isfinite(v).all()))
 
 
+def gen_adapose_v1(out_dir):
+    """The v1 network (lib/network.py: StereoPoseNet) on the golden batch.  Data only: the eight outputs; for both views, at every 8th
+    chosen point (v2_ref.points_slice), volume_conv's 24 values, the new feature rows relu(feat + fuse_conv(planes)) and the 128-channel
+    pose rows, with each whole tensor's largest magnitude; as scalars measured here on all points, the clip shares of the five ReLUs of the
+    stereo part (the residual one last) and the share of (point, plane) pairs whose warp leaves the partner image; the class's state-dict
+    keys and shapes.  The forward runs view 2's volume_conv first (network.py:173-174) and view 1's heads first."""
+    from models.pose_estimator.AdaPose.lib.network import StereoPoseNet
+    from rgbmanip_amd import synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import v2_ref
+
+    net = StereoPoseNet(n_cat=1).eval()
+    sd = synth.v1_state_dict(seed=0)
+    print("load_state_dict:", net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True))
+    B = 2
+    inp = synth.adapose_inputs(B, seed=0)
+    tin = {k: torch.from_numpy(v) for k, v in inp.items()}
+    choose = {1: tin["choose1"].long(), 2: tin["choose2"].long()}
+    vc = [[], [], []]
+    fc_relu, inst_in, pm1_in = [], [], []
+
+    def at_choose(t, v):      # [B, C, (D,) H, W] -> [B, P, C (, D)] at view v's chosen pixels
+        t = t.reshape(t.shape[0], t.shape[1], -1, t.shape[-2] * t.shape[-1])
+        g = torch.stack([t[b][:, :, choose[v][b]] for b in range(t.shape[0])])      # [B, C, D', P]
+        return g.permute(0, 3, 1, 2).contiguous()
+
+    # volume_conv sees view 2 first, fuse_conv view 1 first; instance_color and pose_mlp1 see view 1 first: their inputs are the gathered
+    # new feature rows and the pose rows
+    hs = [net.volume_conv[l].register_forward_hook(lambda mod, i, o, l=l: vc[l].append(at_choose(o.detach(), 2 - len(vc[l])))) for l in range(3)]
+    hs.append(net.fuse_conv[1].register_forward_hook(lambda mod, i, o: fc_relu.append(at_choose(o.detach(), 1 + len(fc_relu)))))
+    hs.append(net.instance_color.register_forward_pre_hook(lambda mod, i: inst_in.append(i[0].detach().transpose(1, 2).contiguous())))
+    hs.append(net.pose_mlp1.register_forward_pre_hook(lambda mod, i: pm1_in.append(i[0].detach().transpose(1, 2).contiguous())))
+    args = (tin["img1"], tin["choose1"], tin["img2"], tin["choose2"], tin["P1"], tin["P2"], tin["depths"])
+    with torch.no_grad():
+        out = net(*args)
+        for h in hs:
+            h.remove()
+        out2 = net(*args)
+        for k in out:
+            assert torch.equal(out[k], out2[k]), k
+        save = {k: v.numpy() for k, v in out.items()}
+        feat = {1: net.img_extractor(tin["img1"]), 2: net.img_extractor(tin["img2"])}
+        for v in (1, 2):
+            o, k = 3 - v, 2 - v      # k: position of view v in the lists of volume_conv's hooks, which see view 2 first
+            planes = vc[2][k][:, :, 0, :]                                      # [B, P, 24]
+            fused = inst_in[v - 1]                                             # [B, P, 32]
+            rows = pm1_in[v - 1]                                               # [B, P, 128]
+            for name, t in (("planes", planes), ("fused", fused), ("rows", rows)):      # every 8th point: [B, P / 8, C]
+                save[f"v{v}_{name}_slice"] = v2_ref.points_slice(t).contiguous().numpy()
+                save[f"v{v}_{name}_absmax"] = np.array(float(t.abs().max()), dtype=np.float64)
+            clip = [float((vc[l][k] == 0).double().mean()) for l in range(3)] + [float((fc_relu[v - 1] == 0).double().mean()),
+                                                                                 float((fused == 0).double().mean())]
+            H, W = feat[v].shape[2], feat[v].shape[3]
+            ix, iy, _ = v2_ref.warp_grid_at(tin[f"P{o}"], tin[f"P{v}"], tin["depths"], choose[v], H, W, torch.float32)
+            outside = float((v2_ref.taps_inside(ix, iy, H, W) == 0).double().mean())
+            save[f"v{v}_clip"] = np.array(clip, dtype=np.float64)
+            save[f"v{v}_outside"] = np.array(outside, dtype=np.float64)
+            print(f"view {v}: clip shares {['%.3f' % c for c in clip]}, outside share {outside:.3f}")
+            # the fixture conditions tests/test_v1_host.py re-asserts: if the draw misses one, change the draw, not the condition
+            assert all(0.05 <= c <= 0.95 for c in clip), "a ReLU that clips (almost) nothing or everything"
+            assert 0.0 < outside < 1.0, "every warp leaves the partner image, or none does"
+            r = out[f"view{v}_r"].double()
+            assert float((r.transpose(1, 2) @ r - torch.eye(3, dtype=torch.float64)).abs().max()) < 1e-5 and bool((torch.linalg.det(r) > 0.999).all()), "r is no rotation"
+        s1, s2 = out["view1_s"], out["view2_s"]
+        sdiff = float((s1 - s2).abs().max() / torch.maximum(s1.abs().max(), s2.abs().max()))
+        print(f"max|s1 - s2| / max|s| {sdiff:.4f}")
+        assert not torch.equal(s1, s2) and sdiff >= 1e-3, "a size output that does not depend on the view"
+    ref_sd = net.state_dict()
+    save["sd_keys"] = np.array(list(ref_sd.keys()))
+    save["sd_shapes"] = np.array(["x".join(str(d) for d in v.shape) for v in ref_sd.values()])
+    path = os.path.join(out_dir, "adapose_v1_b2.npz")
+    np.savez_compressed(path, **save)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    for k, v in out.items():
+        print(k, tuple(v.shape), float(v.abs().mean()), bool(torch.isfinite(v).all()))
+
+
 def gen_adapose_trainbn(out_dir):
     """The as-shipped normalisation (interface_v5.py:39-56 never calls .eval()): the reference module in .train()
     with only its Dropout2d modules in .eval() (their masks are random), run the way the estimator runs it — ONE pose per call —
@@ -1184,6 +1261,8 @@ if __name__ == "__main__":
         gen_adapose_realworld(out_dir)
     if "adapose_v2" in which:             # on request only
         gen_adapose_v2(out_dir)
+    if "adapose_v1" in which:             # on request only
+        gen_adapose_v1(out_dir)
     if "adapose_dropout" in which:       # last: its torch.manual_seed cannot reach the generators above
         gen_adapose_dropout(out_dir)
     print("done")
