@@ -315,6 +315,40 @@ int rgbm_box_agreement(const double* a, const double* b, const uint8_t* ok_a, co
 int rgbm_box_iou_matrix(const double* a, const double* b, const uint8_t* ok_a, const uint8_t* ok_b, int n, int P, int Q, double* iou,
                         void* stream);
 
+/* Box verification without ground truth (box_verify.hip; float64 numpy twins in rgbmanip_amd/verify.py, which evaluate the same
+ * expressions in the same order: every output is an integer and kernel and twin are equal).  Device pointers; the box model is the one
+ * above (o = corner 0, e_0 / e_1 / e_2 = corner 2 / 4 / 1 - o).
+ * rgbm_box_silhouette: boxes [n][S][8][3] fp64 world frame, ok [n][S] uint8 or NULL, K [n][V][3][3] fp64 (the original intrinsics;
+ *   only K00, K11, K02, K12 are read), E [n][V][4][4] fp64 world -> camera (X_cam = E X_world), mask [n][V][H][W] uint8 (any non-zero
+ *   byte is foreground).  For box s of pose i in view v: camera-frame corners c_k = ((E_r0 x + E_r1 y) + E_r2 z) + E_r3; o = c_0,
+ *   e_0, e_1, e_2 = c_2 - o, c_4 - o, c_1 - o; n_k = e_{k+1} x e_{k+2}; det = e_0 . n_0; lo = min(0, det), hi = max(0, det).  Pixel
+ *   (v, u) has xn = (u - K02) / K00, yn = (v - K12) / K11 (the integer pixel coordinate, no half-pixel offset).  Slab k: q0 = -(n_k . o),
+ *   dq = (n_k.x xn + n_k.y yn) + n_k.z; dq != 0: t1 = (lo - q0) / dq, t2 = (hi - q0) / dq, tn = min, tf = max; otherwise tn = -inf if
+ *   lo <= q0 <= hi, else +inf, and tf = +inf.  tmin = max_k tn, tmax = min_k tf; the pixel is inside the silhouette iff tmax >= tmin
+ *   and tmin > 0 (the hit rule of rgbm_synth_render: a box that contains the camera has an empty silhouette and is flagged).  A box is
+ *   usable when its 24 coordinates, the first three rows of E and K00, K11, K02, K12 are finite, K00 and K11 are not 0, |det| > 0 and
+ *   its ok byte is not 0.  Outputs, all int32: area_box [n][S][V] silhouette pixels inside the frame; inter [n][S][V] those with a
+ *   non-zero mask byte; area_mask [n][V] non-zero mask bytes; rect [n][S][V][4] row min, col min, row max, col max of the silhouette,
+ *   (H, W, -1, -1) when it is empty; flags [n][S][V]: bit 1 usable, bit 2 the camera is inside the box (lo <= q0_k <= hi for all k),
+ *   bit 4 the silhouette touches the frame border, bit 8 some c_k has z <= 0.  An unusable box has zero counts, the empty rect and
+ *   flags 0.  The mask of a (pose, view) is read once whatever S is; integer atomics only, so two calls give the same bytes.
+ *   1 <= S <= 64, 1 <= V <= 16, n >= 1, n S V <= 2^24, H W < 2^31, refused otherwise; scratch: rgbm_box_silhouette_scratch_bytes
+ *   bytes, 8-byte aligned (one record and one pixel bound per pose, view and box).
+ * rgbm_cloud_in_box: cloud [n][cap][3] fp32 and count [n][count_cols] int32 as rgbm_cloud_pack (count_cols = 2) or
+ *   rgbm_cloud_pack_views (count_cols = V, or a folded count with 1) write them: the first total = min(sum_c max(count_c, 0), cap) rows
+ *   of a pose hold its points.  boxes [n][S][8][3] fp64 world frame, ok [n][S] or NULL, inflate >= 0.  With the world-frame o, n_k, det,
+ *   lo, hi of a box and p a row converted to fp64: a_k = n_k . (p - o) = (n_k.x d_x + n_k.y d_y) + n_k.z d_z; p is inside iff
+ *   lo - inflate |det| <= a_k <= hi + inflate |det| for k = 0, 1, 2 (the box grown by inflate edge lengths on every side); a row that
+ *   is not finite is never inside.  inside [n][S] int32 (0 for an unusable box: a non-finite coordinate, |det| not > 0, ok 0),
+ *   total [n] int32.  The cloud is read once per pose for all S boxes.  1 <= S <= 64, n >= 1, n S <= 2^24, 1 <= count_cols <= 16,
+ *   0 <= cap <= 2^30, refused otherwise.  A refused call launches nothing and writes nothing. */
+int rgbm_box_silhouette_scratch_bytes(int n, int S, int V, size_t* bytes);
+int rgbm_box_silhouette(const double* boxes, const uint8_t* ok, const double* K, const double* E, const uint8_t* mask, int n, int S, int V,
+                        int H, int W, int32_t* area_box, int32_t* inter, int32_t* area_mask, int32_t* rect, int32_t* flags, void* scratch,
+                        size_t scratch_bytes, void* stream);
+int rgbm_cloud_in_box(const float* cloud, const int32_t* count, int count_cols, const double* boxes, const uint8_t* ok, int n, int S, int cap,
+                      double inflate, int32_t* inside, int32_t* total, void* stream);
+
 /* Dense depth and confidence maps of the crops (what lib/network_v3.py:406-408 returns as view1_depth: softmax over the D planes of the
  * regularised cost volume, then the expectation with the depth values), beside the ten point outputs.
  * rgbm_adapose_forward_dense: the arguments of rgbm_adapose_forward plus two caller-owned fp32 device buffers [V'][224][224],

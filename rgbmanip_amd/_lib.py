@@ -134,6 +134,9 @@ SIGNATURES = {
     "rgbm_sample_point_stats": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp]),
     "rgbm_box_agreement": (_i, [_vp, _vp, _vp, _vp, _i] + [_vp] * 14),
     "rgbm_box_iou_matrix": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "rgbm_box_silhouette_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "rgbm_box_silhouette": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rgbm_cloud_in_box": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp]),
     "rgbm_adapose_dense_workspace_bytes": (_i, [_vp, _i, C.POINTER(_sz)]),
     "rgbm_adapose_forward_dense": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp, _vp, _vp]),
     "rgbm_adapose_forward_maps": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(AdaposeOut), _vp, _vp, _vp, _vp]),

@@ -17,6 +17,7 @@ import torch
 from . import _lib
 from .cloud import (cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity, cloud_similarity_ref,      # noqa: F401  (part of this module's surface)
                     depth_consistency, depth_consistency_ref, depth_fusion, depth_fusion_ref, depth_to_points, depth_to_points_ref)
+from .verify import box_silhouette, box_silhouette_ref, cloud_in_box, cloud_in_box_ref      # noqa: F401  (likewise)
 
 _DTYPES = {"fp32": _lib.F32, "f32": _lib.F32, "float32": _lib.F32, "bf16": _lib.BF16, "bfloat16": _lib.BF16,
            "fp16": _lib.F16, "f16": _lib.F16, "float16": _lib.F16, "bf16x3": _lib.BF16X3}

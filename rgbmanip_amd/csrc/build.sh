@@ -17,11 +17,11 @@ FLAGS="$FLAGS -Xclang -target-feature -Xclang -packed-fp32-ops"
 echo "$FLAGS" > build/.flags.new 2>/dev/null || true
 if ! cmp -s build/.flags.new build/.flags 2>/dev/null; then rm -f build/*.o build/*.asm_ok; cp build/.flags.new build/.flags; fi      # new flags: everything is rebuilt AND the sweep kernels' ISA is re-checked
 pids=()
-for f in igemm_m32.hip igemm_ws.hip igemm_generic.hip igemm_ws64.hip conv3d_tile.hip conv0_sweep.hip conv0_sweep_x3.hip prob_sparse.hip misc_kernels.hip bn_kernels.hip upconv.hip dropout.hip upconv_final.hip stem.hip feature_cache.hip head_kernels.hip v2_head.hip v1_head.hip dense_depth.hip depth_points.hip depth_consistency.hip depth_fusion.hip pose_mlp.hip view_fusion.hip postproc.hip postproc_regressed.hip prepare.hip ppo_kernels.hip policy_kernels.hip control.hip synth_env.hip align.hip cloud_fit.hip pnp.hip sample_stats.hip box_overlap.hip microbench.hip; do
+for f in igemm_m32.hip igemm_ws.hip igemm_generic.hip igemm_ws64.hip conv3d_tile.hip conv0_sweep.hip conv0_sweep_x3.hip prob_sparse.hip misc_kernels.hip bn_kernels.hip upconv.hip dropout.hip upconv_final.hip stem.hip feature_cache.hip head_kernels.hip v2_head.hip v1_head.hip dense_depth.hip depth_points.hip depth_consistency.hip depth_fusion.hip pose_mlp.hip view_fusion.hip postproc.hip postproc_regressed.hip prepare.hip ppo_kernels.hip policy_kernels.hip control.hip synth_env.hip align.hip cloud_fit.hip pnp.hip sample_stats.hip box_overlap.hip box_verify.hip microbench.hip; do
   [ -f "$f" ] || continue
   EXTRA=""
   # files that must round like numpy / torch elementwise ops: no mul+add -> fma contraction
-  case "$f" in postproc.hip|postproc_regressed.hip|depth_points.hip|depth_consistency.hip|depth_fusion.hip|ppo_kernels.hip|prepare.hip|control.hip|synth_env.hip|align.hip|cloud_fit.hip|pnp.hip|sample_stats.hip|box_overlap.hip|misc_kernels.hip|bn_kernels.hip|v2_head.hip|v1_head.hip) EXTRA="-ffp-contract=off";; esac
+  case "$f" in postproc.hip|postproc_regressed.hip|depth_points.hip|depth_consistency.hip|depth_fusion.hip|ppo_kernels.hip|prepare.hip|control.hip|synth_env.hip|align.hip|cloud_fit.hip|pnp.hip|sample_stats.hip|box_overlap.hip|box_verify.hip|misc_kernels.hip|bn_kernels.hip|v2_head.hip|v1_head.hip) EXTRA="-ffp-contract=off";; esac
   # an object is stale when its source, this script or ANY header of this directory is newer: no per-header list to forget a header in
   o=build/${f%.hip}.o
   stale=0

@@ -13,6 +13,7 @@
 
 #include "adapose.h"
 #include "box_overlap.h"
+#include "box_verify.h"
 #include "control.h"
 #include "cost3d.h"
 #include "conv_plan.h"
@@ -520,6 +521,26 @@ int rgbm_box_agreement(const double* a, const double* b, const uint8_t* ok_a, co
 int rgbm_box_iou_matrix(const double* a, const double* b, const uint8_t* ok_a, const uint8_t* ok_b, int n, int P, int Q, double* iou,
                         void* stream) {
   return rgbm::launch_box_iou_matrix(a, b, ok_a, ok_b, n, P, Q, iou, (hipStream_t)stream);
+}
+
+int rgbm_box_silhouette_scratch_bytes(int n, int S, int V, size_t* bytes) {
+  RGBM_REQUIRE(bytes, "box_silhouette_scratch_bytes arguments");
+  RGBM_REQUIRE(S >= 1 && S <= rgbm::kVerifyBoxesMax && V >= 1 && V <= rgbm::kVerifyViewsMax && n >= 1 &&
+               (long long)n * S * V <= (long long)rgbm::kVerifyRecordsMax, "box_silhouette: 1 <= S <= 64, 1 <= V <= 16, n >= 1 and n * S * V <= 2^24");
+  *bytes = rgbm::box_silhouette_scratch_bytes(n, S, V);
+  return 0;
+}
+
+int rgbm_box_silhouette(const double* boxes, const uint8_t* ok, const double* K, const double* E, const uint8_t* mask, int n, int S, int V,
+                        int H, int W, int32_t* area_box, int32_t* inter, int32_t* area_mask, int32_t* rect, int32_t* flags, void* scratch,
+                        size_t scratch_bytes, void* stream) {
+  const rgbm::BoxSilhouetteOut o{area_box, inter, area_mask, rect, flags};
+  return rgbm::launch_box_silhouette(boxes, ok, K, E, mask, n, S, V, H, W, o, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int rgbm_cloud_in_box(const float* cloud, const int32_t* count, int count_cols, const double* boxes, const uint8_t* ok, int n, int S, int cap,
+                      double inflate, int32_t* inside, int32_t* total, void* stream) {
+  return rgbm::launch_cloud_in_box(cloud, count, count_cols, boxes, ok, n, S, cap, inflate, inside, total, (hipStream_t)stream);
 }
 
 int rgbm_sample_point_stats(const float* x, int n, int S, int64_t M, float* mean, float* std, void* stream) {

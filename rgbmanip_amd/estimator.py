@@ -28,6 +28,7 @@ import torch
 
 from . import _lib, host_prepare
 from . import samples as samples_mod
+from . import verify as verify_mod
 from .adapose import (AdaPoseNet, postprocess, postprocess_pnp, postprocess_pnp_scaled, postprocess_ransac, postprocess_regressed, prepare_inputs,
                       prepare_inputs_windows, pts2d_to_coor)
 from .cloud import (DEFAULT_BBOX, cloud_gather, cloud_gather_views, cloud_pack, cloud_pack_views, cloud_similarity, depth_consistency, depth_fusion,
@@ -477,7 +478,8 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
 
     # ------------------------------------------------------------------ a box fitted to the two-view cloud
     def estimate_cloud_pose(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
-                            view2_extrinsic_batch, *, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True, max_points=None, fit_seed=None):
+                            view2_extrinsic_batch, *, px_max=1.0, rel_max=0.01, conf_min=0.0, masked=True, max_points=None, fit_seed=None,
+                            verify=False, inflate=0.0):
         """`estimate_cloud` (same arguments, keywords, frame types, upload modes, chunk pipeline and errors) plus the object-space
         coordinate of every cloud row and a second, independent box per pose fitted to them.  Everything `estimate_cloud` returns,
         unchanged, plus `nocs1` / `nocs2` [n,S,S,3] f32 (the network's NOCS branch at every pixel of the two crops; read at `choose` they
@@ -486,15 +488,32 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         hip_ransac_seed; pose b of the call draws stream b, whatever the chunking): `bbox_cloud` [n,8,3] f64 (world frame), `srt_cloud`
         [n,13] f64 (scale, R, t), `fit_info` [n,4] i32 (rows used, kept hypothesis or -1, its inliers, hypotheses examined) and
         `valid_cloud` [n] i32.  A sample with valid 0, fewer than 5 rows or no consensus has valid_cloud 0 and the +10 cube; a sample with
-        valid 0 has NaN NOCS maps."""
-        return self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
-                                          view2_extrinsic_batch, want=self._cloud_options(px_max, rel_max, conf_min, masked, max_points, fit_seed=fit_seed))
+        valid 0 has NaN NOCS maps.  `verify`: the two boxes are checked against the frame masks and the cloud (`verify.cloud_pose_verify`
+        with `inflate`; hypothesis 0 is `bbox`, 1 is `bbox_cloud`) and the dict gains `mask_iou` [n,2,2] f64 (box, view), `mask_score`
+        [n,2] f64, `cloud_share` [n,2] f64 and `best` [n] i64 (-1: neither box is usable); the uint8 masks are uploaded once more for it."""
+        r = self._estimate_host_frames(camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
+                                       view2_extrinsic_batch, want=self._cloud_options(px_max, rel_max, conf_min, masked, max_points, fit_seed=fit_seed))
+        if verify:
+            r = self._cloud_pose_verified(r, camera_intrinsic_batch, view1_extrinsic_batch, self._upload_masks(view1_mask_batch),
+                                          view2_extrinsic_batch, self._upload_masks(view2_mask_batch), inflate)
+        return r
 
     def estimate_cloud_pose_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, frame0: int = 0, *, px_max=1.0, rel_max=0.01, conf_min=0.0,
-                                   masked=True, max_points=None, fit_seed=None):
+                                   masked=True, max_points=None, fit_seed=None, verify=False, inflate=0.0):
         """`estimate_cloud_pose` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
         opts = self._cloud_options(px_max, rel_max, conf_min, masked, max_points, fit_seed=fit_seed)
-        return self._cloud_fit(self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, want=opts), want=opts)
+        dev = self.estimator.device
+        mask1, mask2 = torch.as_tensor(mask1).to(dev), torch.as_tensor(mask2).to(dev)
+        r = self._cloud_fit(self._estimate_device(K, rgb1, mask1, E1, rgb2, mask2, E2, frame0=frame0, want=opts), want=opts)
+        return self._cloud_pose_verified(r, K, E1, mask1, E2, mask2, inflate) if verify else r
+
+    @staticmethod
+    def _cloud_pose_verified(r, K, E1, mask1, E2, mask2, inflate):
+        """r plus the keys of `verify=True`: numpy for a dict of numpy arrays, CUDA tensors for one of CUDA tensors."""
+        v = verify_mod.cloud_pose_verify(r, np.asarray(K) if not isinstance(K, torch.Tensor) else K, E1, mask1, E2, mask2, inflate=inflate)
+        r = dict(r)
+        r.update(mask_iou=v["iou"], mask_score=v["score"], cloud_share=v["share"], best=v["best"])
+        return r
 
     def _cloud_fit(self, out, want: ResultPlan):
         """The fit of `estimate_cloud_pose` over all poses of a call at once (so that pose b draws sample stream b however the call was
@@ -758,7 +777,9 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
     # ------------------------------------------------------------------ S Dropout2d samples per pose
     _SAMPLE_ROWS = 256                # network poses (samples x poses) per forward_samples call
 
-    def _samples_check(self, samples) -> int:
+    def _samples_check(self, samples, select=None) -> int:
+        if select not in (None, "mask"):
+            raise ValueError(f'estimate_samples: select must be None or "mask", got {select!r}')
         if self.feature_cache:
             raise ValueError("estimate_samples: cfg hip_feature_cache keeps feature maps across forwards; there is no cached form of the "
                              "sampled forward")
@@ -773,7 +794,7 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         return S
 
     def estimate_samples(self, camera_intrinsic_batch, rgb1_batch, view1_mask_batch, view1_extrinsic_batch, rgb2_batch, view2_mask_batch,
-                         view2_extrinsic_batch, samples: int = 8):
+                         view2_extrinsic_batch, samples: int = 8, select=None):
         """`estimate` (same arguments, frame types and hip_upload modes) drawing `samples` = S Dropout2d samples of every pose instead of
         one, and what they say about the box, as a dict of numpy arrays.  The frames are uploaded and cropped once and the `choose`
         subsets drawn once; `AdaPoseNet.forward_samples` runs the backbone in front of the first Dropout2d site once per pose and the
@@ -786,8 +807,12 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
         return the +10 cube and its box is finite.  Poses are processed in chunks of at most 256 // S, each chunk one `forward_samples`:
         the mask sequence is therefore per chunk (pose i of a chunk starting at pose c, sample s, draws global pose index
         counter + s m + (i - c), m the poses of the chunk; the counter advances by S m per chunk).  Needs cfg hip_dropout > 0 or
-        hip_as_shipped, no hip_feature_cache, hip_prepare: "device" and 1 <= samples <= 64."""
-        S = self._samples_check(samples)
+        hip_as_shipped, no hip_feature_cache, hip_prepare: "device" and 1 <= samples <= 64.  `select="mask"`: the S draws and the mean
+        box (hypothesis S) are scored against the two frame masks (`verify.samples_verify`) and the dict gains `bbox_best` [n,8,3] f64
+        (the hypothesis with the largest mean mask IoU, the +10 cube where none is usable), `best` [n] i64 (its index, -1 for none),
+        `mask_score` [n,S+1] and `mask_iou` [n,S+1,2] f64; the masks are the ones uploaded for the crops (hip_upload: "windows", which
+        uploads crop windows only: one upload of the uint8 masks).  Any other `select` but None is refused."""
+        S = self._samples_check(samples, select)
         n = len(rgb1_batch)
         dev = self.estimator.device
         Kd = torch.as_tensor(np.asarray(camera_intrinsic_batch)).to(dev)
@@ -804,21 +829,34 @@ class AdaPoseEstimator_v5(BasePoseEstimator):
             d = ring.copy(0, n)
             a, b = (self._prepare_windows(d, v, Kd, size, 1024, self.prepare_seed + v, want_pts2d=wp) for v in (0, 1))
             self.upload_bytes_last_call, self.upload_table_bytes_last_call = ring.payload_bytes, ring.table_bytes
+            m1, m2 = (self._upload_masks(view1_mask_batch), self._upload_masks(view2_mask_batch)) if select else (None, None)
         else:
             self.upload_bytes_last_call, self.upload_table_bytes_last_call = frames_payload_bytes(*args), 0
-            a = self._prepare(self._upload_frames(rgb1_batch), self._upload_masks(view1_mask_batch), Kd, size, 1024, self.prepare_seed, want_pts2d=wp)
-            b = self._prepare(self._upload_frames(rgb2_batch), self._upload_masks(view2_mask_batch), Kd, size, 1024, self.prepare_seed + 1, want_pts2d=wp)
-        return _to_host(self._samples_prepared(a, b, np.asarray(view1_extrinsic_batch), np.asarray(view2_extrinsic_batch), Kd, S))
+            m1, m2 = self._upload_masks(view1_mask_batch), self._upload_masks(view2_mask_batch)
+            a = self._prepare(self._upload_frames(rgb1_batch), m1, Kd, size, 1024, self.prepare_seed, want_pts2d=wp)
+            b = self._prepare(self._upload_frames(rgb2_batch), m2, Kd, size, 1024, self.prepare_seed + 1, want_pts2d=wp)
+        E1, E2 = np.asarray(view1_extrinsic_batch), np.asarray(view2_extrinsic_batch)
+        return _to_host(self._samples_selected(self._samples_prepared(a, b, E1, E2, Kd, S), select, Kd, E1, m1, E2, m2))
 
-    def estimate_samples_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, samples: int = 8, frame0: int = 0):
+    def estimate_samples_device(self, K, rgb1, mask1, E1, rgb2, mask2, E2, samples: int = 8, frame0: int = 0, select=None):
         """`estimate_samples` for frames that live on the GPU (the arguments of `estimate_device`): the same dict, as CUDA tensors."""
-        S = self._samples_check(samples)
+        S = self._samples_check(samples, select)
         size, dev = self.cfg["img_size"], self.estimator.device
         Kd = torch.as_tensor(K).to(dev)
         kw = dict(want_pts2d=self._pnp_branch(), frame0=frame0)
-        a = self._prepare(torch.as_tensor(rgb1).to(dev), torch.as_tensor(mask1).to(dev), Kd, size, 1024, self.prepare_seed, **kw)
-        b = self._prepare(torch.as_tensor(rgb2).to(dev), torch.as_tensor(mask2).to(dev), Kd, size, 1024, self.prepare_seed + 1, **kw)
-        return self._samples_prepared(a, b, E1, E2, Kd, S)
+        m1, m2 = torch.as_tensor(mask1).to(dev), torch.as_tensor(mask2).to(dev)
+        a = self._prepare(torch.as_tensor(rgb1).to(dev), m1, Kd, size, 1024, self.prepare_seed, **kw)
+        b = self._prepare(torch.as_tensor(rgb2).to(dev), m2, Kd, size, 1024, self.prepare_seed + 1, **kw)
+        return self._samples_selected(self._samples_prepared(a, b, E1, E2, Kd, S), select, Kd, E1, m1, E2, m2)
+
+    @staticmethod
+    def _samples_selected(res, select, K, E1, mask1, E2, mask2):
+        """The result of `_samples_prepared` (CUDA tensors), with the keys of `select="mask"` where that is asked for."""
+        if select is None:
+            return res
+        v = verify_mod.samples_verify(res, K, E1, mask1, E2, mask2)
+        res.update(bbox_best=v["bbox_best"], best=v["best"], mask_score=v["score"], mask_iou=v["iou"])
+        return res
 
     def _samples_prepared(self, a, b, E1, E2, K, S: int):
         """The sampled network, the box tail on the S n rows and the statistics, for the prepared views a / b."""
